@@ -14,12 +14,18 @@ plus pseudo-random keys mix64(1..n); half of the reads are drawn from the host g
 half are random.  Weak scaling: every rank holds a full index replica and filters its own batches; the only
 collective is the all-reduce of the six summary counters (RCCL) at the end of the timed region.
 
+A plain run sets up, warms up, times the K steps, writes the outputs if asked (--dump-outputs DIR: keep / hits / total of the
+batch the last timed step filtered, see dump_outputs()) and prints the line.  Everything else below (decisions-only pass, probe
+ceilings, CPU baselines, live PMC traffic, extra legs; at N > 1 the host path on every rank and the C ABI's RCCL check) runs
+only with --full.
+
 Output.  The LAST stdout line (rank 0) is the contract's JSON, kept small (compact_line(): < 4 KB, never above 8 KB):
 value = whole-job Mbp/s of that workload, plus
   roofline      dominant kernel (scan): algorithmic HBM bytes / HIP-event time on the kernel's own stream; `traffic` = HBM bytes
-                per launch from PMC counters, measured after the timed region by child runs of this file under rocprofv3 --pmc
-  cpu_baseline  the CPU oracle (oracle/, "port") on a bounded sample of the same reads, all host cores
-and one scalar per extra leg measured at N = 1 after the timed region (none of it enters `value`):
+                per launch from the committed PMC passes, or (--full, extra `pmc`) measured after the timed region by child runs
+                of this file under rocprofv3 --pmc
+  cpu_baseline  (--full) the CPU oracle (oracle/, "port") on a bounded sample of the same reads, all host cores; null otherwise
+and (--full) one scalar per extra leg measured at N = 1 after the timed region (none of it enters `value`):
   legs.{long,paired,union950m,...}           BASELINE configs[2], [3], [4]-sized table: Mbp/s + the oracle check
   host_path.{pageable,pinned,packed}         the PCIe-inclusive rate of dcn_filter_batch* from host memory
   cli.{search50,deplete95,deplete95_gz,paired} `deacon-hip filter` file to file (deplete95_gz: from one gzip stream)
@@ -385,9 +391,10 @@ def host_cores():
 
 
 # ---- the device-resident measurement ---------------------------------------------------------------------------------
-def run_device_workload(index, batches, params, steps, warmup, world, device, reserve_long=False, coll_device=None):
-    """K steps over the rotating batches, counting mode (keep + distinct hits + totals), then the same K steps asking
-    for decisions only.  Returns (result dict, counters of the timed region)."""
+def run_device_workload(index, batches, params, steps, warmup, world, device, reserve_long=False, coll_device=None,
+                        decisions_only=True):
+    """K steps over the rotating batches, counting mode (keep + distinct hits + totals), then (decisions_only) the same K
+    steps asking for decisions only.  Returns (result dict, counters of the timed region)."""
     coll_device = device if coll_device is None else coll_device
     max_bases = max(b.n_bases for b in batches)
     max_reads = max(b.n_reads for b in batches)
@@ -418,6 +425,7 @@ def run_device_workload(index, batches, params, steps, warmup, world, device, re
         for i in range(warmup):
             step(i, counts)
         proc.synchronize()
+        # kept in a plain run too: three steps (~12 ms), and the timed steps start from the state they always started from
         stage = stage_breakdown(counts)
         proc.reset_stats()
         proc.set_profiling(2)  # HIP events around the scan kernel of every timed step, on the stream it runs on
@@ -444,7 +452,8 @@ def run_device_workload(index, batches, params, steps, warmup, world, device, re
         return float(t.item()), counters, stage
 
     elapsed, counters, stage = timed(True)
-    elapsed2, _, stage2 = timed(False)
+    if decisions_only:
+        elapsed2, _, stage2 = timed(False)
     proc.close()
     bases_done = sum(batches[i % len(batches)].n_bases for i in range(steps))  # this rank
     total_bp = counters["total_bp"]
@@ -469,13 +478,42 @@ def run_device_workload(index, batches, params, steps, warmup, world, device, re
         },
         "stage_ms_per_launch": stage,
         "kept_fraction": float(np.mean([float(b.d_keep.float().mean().item()) for b in batches[:min(len(batches), steps)]])),
+    }
+    if decisions_only:
         # not the headline: same batches, same K steps, caller passes no hits/total arrays (what the CLI does outside
         # --debug); reads whose decision is fixed after abs_threshold distinct hits are not probed further
-        "decisions_only": {"value": bases_done * world / elapsed2 / 1e6, "unit": "Mbp/s", "ms_per_step": elapsed2 / steps * 1e3,
-                           "scan_ms_per_launch": stage2["scan"], "stage_ms_per_launch": stage2,
-                           "decisions_identical_to_counting_mode": all(bool(torch.equal(b.d_keep, b.d_keep2)) for b in batches[:min(len(batches), steps)])},
-    }
+        res["decisions_only"] = {"value": bases_done * world / elapsed2 / 1e6, "unit": "Mbp/s", "ms_per_step": elapsed2 / steps * 1e3,
+                                 "scan_ms_per_launch": stage2["scan"], "stage_ms_per_launch": stage2,
+                                 "decisions_identical_to_counting_mode": all(bool(torch.equal(b.d_keep, b.d_keep2)) for b in batches[:min(len(batches), steps)])}
     return res, counters, elapsed, bases_done
+
+
+# ---- --dump-outputs: what the timed path handed its caller in the last timed step ----------------------------------
+DUMP_MAX_UNITS = 2_000_000  # 20 B per sampled unit (three float32 arrays + a float64 index): 40 MB at most
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, batch, max_units=DUMP_MAX_UNITS):
+    """Write the result arrays of `batch` (the one the last timed step filtered) to out_dir/<name>.npy: keep, hits and total
+    per unit (read, or pair) as float32, at the units of `unit_index` (float64): every unit, or a fixed seeded sample of
+    `max_units` of them in ascending order when there are more.  summary.npy (float64) covers the whole arrays:
+    [n_units, sum(keep), sum(hits), sum(total)].  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = batch.n_units
+    if n > max_units:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=max_units, replace=False))
+    else:
+        idx = np.arange(n)
+    d_idx = torch.from_numpy(idx.astype(np.int64)).to(batch.d_keep.device)
+    arrays = {"unit_index": idx.astype(np.float64)}
+    summary = [float(n)]
+    for name, t in (("keep", batch.d_keep), ("hits", batch.d_hits), ("total", batch.d_total)):
+        arrays[name] = t[:n].index_select(0, d_idx).cpu().numpy().astype(np.float32)
+        summary.append(float(t[:n].sum(dtype=torch.int64).item()))
+    arrays["summary"] = np.array(summary, dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: a.shape for name, a in arrays.items()}
 
 
 def c_abi_rccl_check(index, batch, params, world, device, coll_device, timeout_s=90.0):
@@ -1118,18 +1156,28 @@ def main():
                     help="the workload `value` is measured on.  short: configs[1] 150 bp single reads (the headline); "
                          "paired: configs[3] 2x150 bp --deplete; long: configs[2] ONT-style lognormal reads, mean 10 kbp; "
                          "mixed: configs[4]'s stream, half of the bases long and half short in one batch, --deplete")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline as well: the decisions-only pass, the probe ceilings, "
+                         "the CPU baselines with the oracle check, and the extras (at N > 1: the host path on every rank and the "
+                         "C ABI's RCCL check).  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (keep, hits, total per unit) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the other configs and the host-path measurements that follow the headline at N = 1")
+                    help="with --full: skip the other configs and the host-path measurements that follow the headline at N = 1")
     ap.add_argument("--extras", default=DEFAULT_EXTRAS,
-                    help="which of the extra measurements to run (comma separated); all of them: " + ALL_EXTRAS)
+                    help="with --full: which of the extra measurements to run (comma separated); all of them: " + ALL_EXTRAS)
     ap.add_argument("--pmc-child", action="store_true",
                     help="(internal) the run live_traffic() starts under rocprofv3 --pmc: the timed steps only, nothing else measured or written")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
                     help="where the full result goes (the last stdout line is its compact form); '' = nowhere")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.pmc_child:
-        args.no_cpu_baseline, args.no_extras, args.detail = True, True, ""
+        args.full, args.dump_outputs, args.detail = False, None, ""
+    if not args.full:
+        args.no_cpu_baseline, args.no_extras = True, True
 
     # torch sizes its CPU thread pool by the machine (256 hardware threads on the GPU box) while the job's CPU quota is a
     # 16th of it: one parallel CPU op would spend the quota of its 100 ms period at once and the host legs that follow
@@ -1181,7 +1229,11 @@ def main():
     log(f"{args.workload}: {len(batches)} batches of {batches[0].n_reads:,} reads / {batches[0].n_bases / 1e6:.0f} Mbp resident in HBM")
 
     head, counters, elapsed, bases_done = run_device_workload(index, batches, params, args.steps, args.warmup, world, device,
-                                                              reserve_long=args.workload in ("long", "mixed"), coll_device=coll_device)
+                                                              reserve_long=args.workload in ("long", "mixed"), coll_device=coll_device,
+                                                              decisions_only=args.full)
+    if args.dump_outputs and rank == 0:
+        shapes = dump_outputs(args.dump_outputs, batches[(args.steps - 1) % len(batches)])
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {shapes}")
     # what the job's one collective delivered, checked against an independent sum of what every rank put in
     t_exp = torch.tensor([bases_done], dtype=torch.int64, device=coll_device)
     if world > 1:
@@ -1208,20 +1260,20 @@ def main():
         except Exception as ex:  # every rank fails or none does (same code, same sizes); never take the line with it
             log(f"host_path at N = {world} failed: {ex!r}")
             host_path_all = {"error": repr(ex)}
-    if world > 1 and not args.pmc_child:
+    if world > 1 and args.full:
         collective["c_abi_rccl"] = "checked after the line is printed: stderr and bench_detail.json carry the result"
     if rank == 0:
         total_bp = counters["total_bp"]
         rf = head["roofline"]
         traffic = committed_traffic(rf, args.workload, batches[0].n_bases, int(index.n_keys), args.host_genome)
         try:
-            if not args.pmc_child:
+            if args.full:
                 rf["probe_only_kernel_live_per_s"] = probe_only_rate(index, device)
                 rf["frac_of_probe_only_kernel_live"] = rf["scattered_probes_per_s"] / rf["probe_only_kernel_live_per_s"]
         except Exception as ex:
             log(f"probe-only measurement failed: {ex!r}")
         try:
-            if not args.pmc_child:
+            if args.full:
                 # ONE bound the kernel cannot exceed: the same table serving the same key stream -- batch 0's own
                 # minimizer hashes, in the kernel's order -- to a kernel that does nothing but issue the home-group reads
                 # (dcn_index_probe_ceiling: best of six launch shapes).  Beside it, the same for uniformly random groups (no
@@ -1265,7 +1317,7 @@ def main():
             "roofline": rf,
             "stage_ms_per_launch": head["stage_ms_per_launch"],
             "kept_fraction": head["kept_fraction"],
-            "decisions_only": head["decisions_only"],
+            "decisions_only": head.get("decisions_only"),
             "index_build_s": index_build_s,
             "collective": collective,
         }
@@ -1449,7 +1501,7 @@ def main():
             out["cli"] = cli
         out["bench_wall_s"] = time.time() - T0
         emit(out, args.detail)
-    if world > 1 and not args.pmc_child:
+    if world > 1 and args.full:
         # The LAST thing the ranks do together, AFTER rank 0 has printed the line: the C ABI's own RCCL communicator has never met
         # more than one device before the driver's scaling run, and nothing it does (a fault inside the library included) may
         # cost that run its line.  Result: stderr, and `collective.c_abi_rccl` of bench_detail.json.

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""gpurun_out/r3_pmc_<workload>_{fetch,write}/ (profiles/collect_r3.sh) -> profiles/r03_traffic[_<workload>].json: mean FETCH_SIZE /
+"""$DCN_PROFILE_OUT/r3_pmc_<workload>_{fetch,write}/ (profiles/collect_r3.sh; default profiles/out) -> profiles/r03_traffic[_<workload>].json: mean FETCH_SIZE /
 WRITE_SIZE per dispatch of the counting scan kernel, in the calibration of profiles/r02_traffic.json (scattered 16-byte reads:
 counter x 1024 B = sector bytes, no x2), plus the per-kernel time summary of the kernel-trace run.
 usage: python profiles/make_traffic_json.py short|long|mixed [round, default 3]
-(round >= 4: profiles/collect_r4.sh; the bench's full result is read from gpurun_out/r4_*_detail.json, its stdout line being the compact one;
+(round >= 4: profiles/collect_r4.sh; the bench's full result is read from $DCN_PROFILE_OUT/r4_*_detail.json, its stdout line being the compact one;
 the per-dispatch durations of the counting scan kernel from the kernel trace are summarised per rotated batch as well)"""
 import csv
 import glob
@@ -14,11 +14,12 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 wl = sys.argv[1]
 RND = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+OUT = os.environ.get("DCN_PROFILE_OUT", os.path.join(ROOT, "profiles", "out"))  # where collect_r*.sh wrote
 
 
 def counters(kind):
     acc = {}
-    for path in glob.glob(os.path.join(ROOT, "gpurun_out", f"r{RND}_pmc_{wl}_{kind}", "**", "*counter_collection.csv"), recursive=True):
+    for path in glob.glob(os.path.join(OUT, f"r{RND}_pmc_{wl}_{kind}", "**", "*counter_collection.csv"), recursive=True):
         for r in csv.DictReader(open(path)):
             if "scan_kernel" in r["Kernel_Name"] and r["Kernel_Name"].rstrip().endswith("false>(dcn_scan_args)") is False:
                 pass
@@ -31,7 +32,7 @@ def counters(kind):
 
 f, nf = counters("fetch")
 w, nw = counters("write")
-line = json.load(open(os.path.join(ROOT, "gpurun_out", f"r{RND}_pmc_{wl}_fetch.json" if RND < 4 else f"r{RND}_pmc_{wl}_fetch_detail.json")))
+line = json.load(open(os.path.join(OUT, f"r{RND}_pmc_{wl}_fetch.json" if RND < 4 else f"r{RND}_pmc_{wl}_fetch_detail.json")))
 cal = json.load(open(os.path.join(ROOT, "profiles", "r02_traffic.json")))["calibration"]
 out = {
     "source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, profiles/collect_r{RND}.sh) on `python3 bench.py --steps 3 --warmup 1 "
@@ -51,7 +52,7 @@ name = f"r{RND:02d}_traffic.json" if wl == "short" else f"r{RND:02d}_traffic_{wl
 json.dump(out, open(os.path.join(ROOT, "profiles", name), "w"), indent=1)
 print(name, json.dumps(out["scan_kernel"]))
 # kernel-trace summary of the same workload
-for path in glob.glob(os.path.join(ROOT, "gpurun_out", f"r{RND}_stats_{wl}", "**", "*kernel_stats.csv"), recursive=True):
+for path in glob.glob(os.path.join(OUT, f"r{RND}_stats_{wl}", "**", "*kernel_stats.csv"), recursive=True):
     dst = os.path.join(ROOT, "profiles", f"r{RND:02d}_kernel_stats.csv" if wl == "short" else f"r{RND:02d}_kernel_stats_{wl}.csv")
     rows = list(csv.reader(open(path)))
     keep = [rows[0]] + [r for r in rows[1:] if any(s in r[0] for s in ("scan_kernel", "pack_kernel", "plan_kernel", "distinct", "big_insert", "finish_kernel", "table_", "probe_"))]
@@ -60,7 +61,7 @@ for path in glob.glob(os.path.join(ROOT, "gpurun_out", f"r{RND}_stats_{wl}", "**
 
 # per-dispatch durations of the counting scan kernel, in launch order (kernel trace): is the spread a property of the batch
 # (three are rotated: dispatch i runs batch i % 3), of time, or neither?
-for path in glob.glob(os.path.join(ROOT, "gpurun_out", f"r{RND}_stats_{wl}", "**", "*kernel_trace.csv"), recursive=True):
+for path in glob.glob(os.path.join(OUT, f"r{RND}_stats_{wl}", "**", "*kernel_trace.csv"), recursive=True):
     rows = [r for r in csv.DictReader(open(path)) if "scan_kernel<15, false, false, false" in r["Kernel_Name"]]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     ms = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in rows]

@@ -6,4 +6,5 @@
 # the C ABI's communicator is not part of it (tests/test_distributed.py covers that with one rank).
 # usage: profiles/rehearse_two_ranks.sh [output.json] [extra bench.py args]
 out=${1:-/dev/stdout}; shift
-DCN_BENCH_BACKEND=gloo DCN_BENCH_SINGLE_DEVICE=1 python3 bench.py --gpus 2 --steps 20 --warmup 5 --detail gpurun_out/r4_rehearse2_detail.json "$@" | tail -n 1 > "$out"
+outdir=${DCN_PROFILE_OUT:-profiles/out}; mkdir -p "$outdir"
+DCN_BENCH_BACKEND=gloo DCN_BENCH_SINGLE_DEVICE=1 python3 bench.py --full --gpus 2 --steps 20 --warmup 5 --detail $outdir/r4_rehearse2_detail.json "$@" | tail -n 1 > "$out"

@@ -61,3 +61,43 @@ def test_mix64_keys_have_decidable_membership():
     h = mix64(i)
     assert bench.unmix64(h).tolist() == i.tolist()                       # bench.py's inverse of the key generator
     assert len(set(h.tolist())) == len(i)
+
+
+def _filled_batch(n_reads, seed, paired=False):
+    dev = torch.device("cpu")
+    b = bench.Batch(torch.zeros(n_reads * 150, dtype=torch.uint8), torch.arange(n_reads + 1, dtype=torch.int64) * 150,
+                    (torch.arange(n_reads, dtype=torch.int32) // 2) if paired else None)
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    b.d_keep.copy_(torch.randint(0, 2, (b.n_units,), generator=g, dtype=torch.uint8))
+    b.d_hits.copy_(torch.randint(0, 50, (b.n_units,), generator=g, dtype=torch.int32))
+    b.d_total.copy_(torch.randint(50, 300, (b.n_units,), generator=g, dtype=torch.int32))
+    return b
+
+
+def test_dump_outputs_writes_every_unit_of_a_small_batch(tmp_path):
+    b = _filled_batch(1000, 1, paired=True)
+    shapes = bench.dump_outputs(str(tmp_path), b)
+    assert shapes["keep"] == (500,) and shapes["summary"] == (4,)
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in ("unit_index", "keep", "hits", "total", "summary")}
+    assert got["unit_index"].dtype == np.float64 and got["summary"].dtype == np.float64
+    assert all(got[n].dtype == np.float32 for n in ("keep", "hits", "total"))
+    assert got["unit_index"].tolist() == list(range(500))
+    assert got["keep"].tolist() == b.d_keep.tolist() and got["hits"].tolist() == b.d_hits.tolist()
+    assert got["total"].tolist() == b.d_total.tolist()
+    assert got["summary"].tolist() == [500, int(b.d_keep.sum()), int(b.d_hits.sum()), int(b.d_total.sum())]
+
+
+def test_dump_outputs_samples_a_large_batch_the_same_way_every_time(tmp_path):
+    b = _filled_batch(5000, 2)
+    a1, a2 = tmp_path / "a1", tmp_path / "a2"
+    bench.dump_outputs(str(a1), b, max_units=700)
+    bench.dump_outputs(str(a2), b, max_units=700)
+    for n in ("unit_index", "keep", "hits", "total", "summary"):
+        assert np.load(a1 / f"{n}.npy").tobytes() == np.load(a2 / f"{n}.npy").tobytes(), n
+    idx = np.load(a1 / "unit_index.npy").astype(np.int64)
+    assert len(idx) == 700 and (np.diff(idx) > 0).all() and idx[-1] < 5000
+    assert np.load(a1 / "hits.npy").tolist() == b.d_hits.numpy()[idx].astype(np.float32).tolist()
+    assert np.load(a1 / "summary.npy")[2] == int(b.d_hits.sum())      # the summary covers every unit, not just the sample
+    # the default sample of the headline batch (10 M reads) stays far below 64 MB
+    assert bench.DUMP_MAX_UNITS * (3 * 4 + 8) + 4 * 8 < 64 << 20

@@ -153,3 +153,12 @@ def test_self_launch_decides_before_any_gpu_library_is_loaded():
         assert bench.self_launch_if_needed(["--gpus", "2"]) is None   # already under a launcher
     finally:
         del os.environ["WORLD_SIZE"]
+
+
+def test_plain_run_is_lean_and_full_is_an_option():
+    """a plain `bench.py --gpus 1 --steps K --warmup W` measures the headline only; everything else sits behind --full"""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0
+    assert "--full" in p.stdout and "--dump-outputs" in p.stdout
+    p = run_bench(["--gpus", "1", "--steps", "0", "--warmup", "0", "--reads", "10", "--detail", ""], {})
+    assert p.returncode != 0 and "--steps" in p.stderr
