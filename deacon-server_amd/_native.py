@@ -113,10 +113,16 @@ _SIGNATURES = {
     "dcn_ctx_reset_stats": (C.c_int, [_vp]),
     "dcn_ctx_set_profiling": (C.c_int, [_vp, C.c_int]),
     "dcn_ctx_profile": (C.c_int, [_vp, C.POINTER(C.c_double), _u64p]),
+    "dcn_index_set_create": (C.c_int, [C.POINTER(_vp), C.c_uint32, C.POINTER(_vp)]),
+    "dcn_index_set_destroy": (None, [_vp]),
+    "dcn_index_set_info": (C.c_int, [_vp, _u32p, _u8p, _u8p, _u64p, _u64p]),
+    "dcn_classify_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(Params), _vp, _vp, _vp]),
+    "dcn_classify_batch_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32,
+                                            C.POINTER(Params), _vp, _vp, _vp]),
 }
 
 _lib = None
-ABI = (1, 1)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 2)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

@@ -7,6 +7,8 @@
 //   deacon-hip index diff  <first.idx> <second.idx | fastx> [-k K -w W] [-o out.idx]
 //   deacon-hip filter <index> [input|-] [input2|-] [-o out] [-O out2] [-a 2] [-r 0.01] [-p 0] [-d] [-R]
 //                     [-s summary.json] [-t threads] [--compression-level 2] [--debug] [-q]
+//   deacon-hip classify -x <index> [-x <index>...] [input|-] [input2] [-a 2] [-r 0.01] [-p 0] [--per-read out.tsv|-]
+//                     [-s summary.json] [-q]
 //
 // Flags, defaults, stderr messages and the JSON summary follow src/main.rs:24-234, src/local_filter.rs:575-824 and
 // src/filter_common.rs:11-38 of the reference.  The per-record loop of local_filter.rs (paraseq workers calling
@@ -2920,10 +2922,182 @@ int run_index_diff(const std::string &first, const std::string &second, int k_op
     return 0;
 }
 
+// `deacon-hip classify`: which of up to 32 indexes each read (or pair) matches, from one pass over the input against one
+// labelled index set (dcn_index_set_create / dcn_classify_batch).  No reference counterpart: its nearest is N runs of
+// `deacon filter` in search mode, one per index -- a unit matches index j exactly when that run would keep it.
+struct ClassifyArgs {
+    std::vector<std::string> indexes;
+    std::string input = "-", input2, per_read, summary;
+    bool has_input2 = false, has_per_read = false, has_summary = false, quiet = false;
+    unsigned abs_threshold = 2;
+    double rel_threshold = 0.01;
+    size_t prefix_length = 0;
+};
+
+std::string index_stem(const std::string &path) {
+    std::string b = path.substr(path.find_last_of('/') == std::string::npos ? 0 : path.find_last_of('/') + 1);
+    const size_t dot = b.find_last_of('.');
+    return dot == std::string::npos || dot == 0 ? b : b.substr(0, dot);
+}
+
+int run_classify(const ClassifyArgs &a) {
+    const auto start = std::chrono::steady_clock::now();
+    if (a.indexes.empty()) die("the following required arguments were not provided: -x <INDEX>");
+    if (a.indexes.size() > 32) die("classify takes at most 32 indexes");
+    const uint32_t n = (uint32_t)a.indexes.size();
+    std::vector<RawIndex> members(n);
+    std::vector<const dcn_index *> mp(n);
+    std::vector<uint8_t> mk(n), mw(n);
+    std::vector<uint64_t> mkeys(n);
+    for (uint32_t j = 0; j < n; ++j) {
+        deacon::check(dcn_index_from_file(a.indexes[j].c_str(), 0, &members[j].p));
+        deacon::check(dcn_index_header(members[j].p, &mk[j], &mw[j], &mkeys[j]));
+        mp[j] = members[j].p;
+    }
+    RawIndex set;
+    deacon::check(dcn_index_set_create(mp.data(), n, &set.p));
+    for (auto &m : members) { // the set holds its own table: the members' memory goes back at once
+        dcn_index_destroy(m.p);
+        m.p = nullptr;
+    }
+    uint64_t max_bases = 64ull << 20;
+    const uint32_t max_reads = 1u << 20;
+    dcn_ctx *ctx = nullptr;
+    deacon::check(dcn_ctx_create(set.p, max_bases, max_reads, &ctx));
+    struct CtxGuard {
+        dcn_ctx **c;
+        ~CtxGuard() {
+            if (*c) dcn_ctx_destroy(*c);
+        }
+    } guard{&ctx};
+    dcn_params prm = {};
+    prm.abs_threshold = a.abs_threshold;
+    prm.rel_threshold = a.rel_threshold;
+    prm.prefix_length = a.prefix_length;
+
+    std::vector<std::string> stems(n);
+    for (uint32_t j = 0; j < n; ++j) stems[j] = index_stem(a.indexes[j]);
+    FILE *tsv = nullptr;
+    if (a.has_per_read) {
+        tsv = a.per_read == "-" ? stdout : std::fopen(a.per_read.c_str(), "w");
+        if (!tsv) die("cannot open " + a.per_read + " for writing");
+        std::fputs("id\tlength\tminimizers", tsv);
+        for (auto &st : stems) std::fprintf(tsv, "\thits:%s", st.c_str());
+        std::fputs("\tmatched\n", tsv);
+    }
+    FastxReader r1(a.input);
+    std::unique_ptr<FastxReader> r2;
+    if (a.has_input2) r2.reset(new FastxReader(a.input2));
+    const bool paired = a.has_input2;
+    uint64_t seqs_in = 0, bp_in = 0;
+    std::vector<uint64_t> seqs_m(n, 0), bp_m(n, 0);
+    Batch b;
+    std::vector<uint32_t> match, hits, total;
+    auto run_batch = [&]() {
+        const uint32_t n_reads = (uint32_t)b.recs.size();
+        if (n_reads == 0) return;
+        const uint64_t nb = b.offsets.back();
+        if (nb > max_bases) { // a record longer than the context's batch: a context of its size
+            dcn_ctx_destroy(ctx);
+            ctx = nullptr;
+            max_bases = nb;
+            deacon::check(dcn_ctx_create(set.p, max_bases, max_reads, &ctx));
+        }
+        const uint32_t n_units = paired ? n_reads / 2 : n_reads;
+        match.assign(n_units, 0);
+        hits.assign((size_t)n_units * n, 0);
+        total.assign(n_units, 0);
+        deacon::check(dcn_classify_batch(ctx, set.p, b.bases.data(), b.offsets.data(), paired ? b.unit_id.data() : nullptr,
+                                         n_reads, &prm, match.data(), hits.data(), total.data()));
+        const uint32_t per = paired ? 2 : 1;
+        std::string row;
+        for (uint32_t u = 0; u < n_units; ++u) {
+            uint64_t len = 0;
+            for (uint32_t q = 0; q < per; ++q) len += b.recs[u * per + q].seq_len;
+            seqs_in += per;
+            bp_in += len;
+            for (uint32_t j = 0; j < n; ++j)
+                if (match[u] >> j & 1u) seqs_m[j] += per, bp_m[j] += len;
+            if (!tsv) continue;
+            const Rec &r = b.recs[u * per];
+            const char *id = b.chars() + r.id_off;
+            size_t id_len = 0;
+            while (id_len < r.id_len && id[id_len] != ' ' && id[id_len] != '\t') ++id_len;
+            row.assign(id, id_len);
+            row += '\t' + std::to_string(len) + '\t' + std::to_string(total[u]);
+            for (uint32_t j = 0; j < n; ++j) row += '\t' + std::to_string(hits[(size_t)u * n + j]);
+            row += '\t';
+            bool any = false;
+            for (uint32_t j = 0; j < n; ++j)
+                if (match[u] >> j & 1u) {
+                    if (any) row += ',';
+                    row += stems[j];
+                    any = true;
+                }
+            if (!any) row += '-';
+            row += '\n';
+            std::fwrite(row.data(), 1, row.size(), tsv);
+        }
+        b.clear();
+    };
+    const uint64_t batch_bases = 32ull << 20;
+    const uint32_t batch_reads = max_reads - 2;
+    for (;;) {
+        if (!r1.next(b)) {
+            if (r2 && r2->next(b)) die("the second input has more records than the first");
+            break;
+        }
+        if (r2) {
+            if (!r2->next(b)) die("the first input has more records than the second");
+            const uint32_t u = (uint32_t)(b.recs.size() / 2 - 1);
+            b.unit_id.push_back(u);
+            b.unit_id.push_back(u);
+        }
+        if (b.offsets.back() >= batch_bases || b.recs.size() >= batch_reads) run_batch();
+    }
+    run_batch();
+    if (tsv && tsv != stdout) std::fclose(tsv);
+    else if (tsv) std::fflush(tsv);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+    auto prop = [](uint64_t x, uint64_t y) { return y ? (double)x / (double)y : 0.0; };
+    if (!a.quiet) {
+        for (uint32_t j = 0; j < n; ++j)
+            std::fprintf(stderr, "%s: %llu/%llu (%.3f%%) sequences matched\n", stems[j].c_str(), (unsigned long long)seqs_m[j],
+                         (unsigned long long)seqs_in, prop(seqs_m[j], seqs_in) * 100.0);
+        std::fprintf(stderr, "Classified %llu sequences (%llu bp) against %u indexes in %s\n", (unsigned long long)seqs_in,
+                     (unsigned long long)bp_in, n, fmt_duration(secs).c_str());
+    }
+    if (a.has_summary) {
+        std::string js = "{\n  \"version\": " + json_str(std::string("deacon-hip ") + VERSION) + ",\n  \"input\": " +
+                         json_str(a.input) + ",\n  \"input2\": " + (a.has_input2 ? json_str(a.input2) : std::string("null"));
+        char buf[512];
+        std::snprintf(buf, sizeof buf, ",\n  \"abs_threshold\": %u,\n  \"rel_threshold\": %.17g,\n  \"prefix_length\": %zu,\n"
+                                       "  \"seqs_in\": %llu,\n  \"bp_in\": %llu,\n  \"time\": %.17g,\n  \"indexes\": [",
+                      a.abs_threshold, a.rel_threshold, a.prefix_length, (unsigned long long)seqs_in, (unsigned long long)bp_in, secs);
+        js += buf;
+        for (uint32_t j = 0; j < n; ++j) {
+            js += (j ? ",\n    {" : "\n    {");
+            js += "\"path\": " + json_str(a.indexes[j]) + ", \"name\": " + json_str(stems[j]);
+            std::snprintf(buf, sizeof buf, ", \"k\": %u, \"w\": %u, \"keys\": %llu, \"seqs_matched\": %llu, "
+                                           "\"seqs_matched_proportion\": %.17g, \"bp_matched\": %llu, \"bp_matched_proportion\": %.17g}",
+                          (unsigned)mk[j], (unsigned)mw[j], (unsigned long long)mkeys[j], (unsigned long long)seqs_m[j],
+                          prop(seqs_m[j], seqs_in), (unsigned long long)bp_m[j], prop(bp_m[j], bp_in));
+            js += buf;
+        }
+        js += "\n  ]\n}\n";
+        FILE *f = std::fopen(a.summary.c_str(), "w");
+        if (!f) die("cannot open " + a.summary + " for writing");
+        std::fwrite(js.data(), 1, js.size(), f);
+        std::fclose(f);
+    }
+    return 0;
+}
+
 void usage() {
     std::fprintf(stderr,
                  "Usage: deacon-hip <COMMAND>\n\nCommands:\n  index   Build and compose minimizer indexes (build, info, union, diff)\n"
                  "  filter  Keep or discard DNA fastx records with sufficient minimizer hits to an index\n"
+                 "  classify  Report which of several indexes each record (or pair) matches, in one pass\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -2986,6 +3160,22 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "  -q, --quiet                    Suppress progress reporting\n"
                "      --gpus <N>                 Use GPUs 0..N-1, one pipeline context and one index replica each [default: 1]\n"
                "      --devices <LIST>           Explicit device list, e.g. 0,2,3 (a repeated id = another context on that GPU)\n"
+               "  -h, --help                     Print help\n";
+    else if (sub == "classify")
+        text = "Report which of several indexes each record (or pair) matches, in one pass over the input\n\n"
+               "Usage: deacon-hip classify -x <INDEX> [-x <INDEX>...] [OPTIONS] [INPUT] [INPUT2]\n\n"
+               "Arguments:\n"
+               "  [INPUT]   Optional path to fastx file (or - for stdin; gz, bgzf, zst, xz and bz2 found by content) [default: -]\n"
+               "  [INPUT2]  Optional path to second paired fastx file\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Path to a minimizer index file; repeat for up to 32 indexes (same k and w)\n"
+               "  -a, --abs-threshold <N>        Minimum absolute number of minimizer hits for a match [default: 2]\n"
+               "  -r, --rel-threshold <F>        Minimum relative proportion (0.0-1.0) of minimizer hits for a match [default: 0.01]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per sequence (0 = entire sequence) [default: 0]\n"
+               "      --per-read <PATH>          One TSV row per record or pair (- for stdout): id, length, minimizers, hits per index, matched\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
                "  -h, --help                     Print help\n";
     else if (sub == "index build")
         text = "Index minimizers contained within a fastx file\n\n"
@@ -3102,6 +3292,30 @@ int main(int argc, char **argv) {
             if (pos.size() > 2) a.input2 = pos[2], a.has_input2 = true;
             if (pos.size() > 3) die("unexpected argument '" + pos[3] + "'");
             return run_filter(a);
+        }
+        if (args[0] == "classify") {
+            ClassifyArgs a;
+            std::vector<std::string> pos;
+            for (size_t i = 1; i < args.size(); ++i) {
+                const std::string &s = args[i];
+                if (s == "-x" || s == "--index") a.indexes.push_back(need(++i));
+                else if (s == "-a" || s == "--abs-threshold") {
+                    long v = std::atol(need(++i).c_str());
+                    if (v < 1 || v > 65535) die("invalid value for --abs-threshold: must be 1..65535");
+                    a.abs_threshold = (unsigned)v;
+                } else if (s == "-r" || s == "--rel-threshold") a.rel_threshold = std::atof(need(++i).c_str());
+                else if (s == "-p" || s == "--prefix-length") a.prefix_length = (size_t)std::atoll(need(++i).c_str());
+                else if (s == "--per-read") a.per_read = need(++i), a.has_per_read = true;
+                else if (s == "-s" || s == "--summary") a.summary = need(++i), a.has_summary = true;
+                else if (s == "-t" || s == "--threads") ++i;
+                else if (s == "-q" || s == "--quiet") a.quiet = true;
+                else if (s.size() > 1 && s[0] == '-' && s != "-") die("unexpected argument '" + s + "'");
+                else pos.push_back(s);
+            }
+            if (pos.size() > 0) a.input = pos[0];
+            if (pos.size() > 1) a.input2 = pos[1], a.has_input2 = true;
+            if (pos.size() > 2) die("unexpected argument '" + pos[2] + "'");
+            return run_classify(a);
         }
         if (args[0] == "cat" && args.size() >= 2) {  // hidden: the input side alone (format found by content, decoded to stdout; no GPU)
             Input in(args[1]);

@@ -8,6 +8,7 @@
 // the host fills the other buffer; the compute stream waits on the copy's event.
 #include "dcn_internal.h"
 #include "dcn_plan.h"
+#include "dcn_classify.h"
 #include "dcn_host_pool.h"
 
 #include <algorithm>
@@ -308,6 +309,9 @@ extern "C" int dcn_index_clone(const dcn_index *index, int device, dcn_index **o
     if (!idx) return dcn_fail(DCN_ERR_NOMEM, "host allocation failed");
     idx->device = device;
     idx->d_slots = nullptr;
+    idx->d_labels = nullptr; // a replica of a labelled set is a plain index over the union of its members
+    idx->n_members = 0;
+    idx->zero_label = 0;
     const uint64_t bytes = idx->n_groups * DCN_GROUP_SLOTS * sizeof(uint64_t);
     // Another GPU: the keys cross the link, not the table (a tenth of the bytes at the default 8 slots per key; dcn_table_clone_by_keys).
     // The same GPU: a device-to-device copy of the table at HBM's pace.  DCN_CLONE_BY_KEYS=1 / DCN_CLONE_BY_COPY=1 force one form
@@ -356,6 +360,7 @@ extern "C" void dcn_index_destroy(dcn_index *index) {
     if (!index) return;
     hipSetDevice(index->device);
     if (index->d_slots) hipFree(index->d_slots);
+    if (index->d_labels) hipFree(index->d_labels);
     delete index;
 }
 
@@ -480,6 +485,11 @@ struct dcn_ctx {
     uint64_t *d_dump_hash = nullptr;
     uint32_t *d_dump_pos = nullptr, *d_dump_count = nullptr, *d_tile_read_pos = nullptr;
     uint8_t *d_dump_valid = nullptr;
+    // classification buffers (lazy, first dcn_classify_batch*): work list of the workgroup kernel + its length, and the
+    // host form's outputs (hits: cls_hits_members per unit)
+    uint32_t *d_cls_big = nullptr, *d_cls_n_big = nullptr;
+    uint32_t *d_cls_match = nullptr, *d_cls_hits = nullptr, *d_cls_total = nullptr;
+    uint32_t cls_hits_members = 0;
     // deferred state of the last enqueued device-API batch
     bool batch_pending = false;
     bool lean = false; // a small host batch is being submitted: copies and result copies go on `stream` itself (submit_impl)
@@ -566,7 +576,8 @@ void free_ctx(dcn_ctx *c) {
                    c->d_read_tiles, c->d_read_tile_first, c->d_unit_first_read, c->d_unit_tile_first, c->d_unit_tile_count, c->d_tiles,
                    c->d_keep, c->d_unit_state, c->d_hits, c->d_total, c->d_unit_scratch, c->d_caps,
                    c->d_set_off, c->d_tile_hits, c->d_pending, c->d_big, c->d_rec_hash, c->d_set_slots, c->d_status, c->d_report, c->d_dump_hash,
-                   c->d_dump_pos, c->d_dump_count, c->d_dump_valid, c->d_tile_read_pos};
+                   c->d_dump_pos, c->d_dump_count, c->d_dump_valid, c->d_tile_read_pos,
+                   c->d_cls_big, c->d_cls_n_big, c->d_cls_match, c->d_cls_hits, c->d_cls_total};
     for (void *p : dev)
         if (p && !((char *)p >= c->d_slab && (char *)p < c->d_slab + c->slab_bytes)) hipFree(p);
     if (c->d_slab) hipFree(c->d_slab);
@@ -2472,4 +2483,261 @@ int dcn_build_index_impl(const uint8_t *bases, const uint64_t *offsets, uint32_t
     rc = body();
     dcn_ctx_destroy(c);
     return rc;
+}
+
+// ----------------------------------------------------------------------------------------------------
+// labelled index sets and classification (classify.hip)
+// ----------------------------------------------------------------------------------------------------
+namespace {
+int check_set(const dcn_index *set) {
+    if (!set) return dcn_fail(DCN_ERR_ARG, "set is NULL");
+    if (set->n_members == 0 || !set->d_labels) return dcn_fail(DCN_ERR_ARG, "index is not a labelled set (dcn_index_set_create)");
+    return DCN_OK;
+}
+} // namespace
+
+extern "C" int dcn_index_set_create(const dcn_index *const *members, uint32_t n, dcn_index **out) {
+    if (!out) return dcn_fail(DCN_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (!members) return dcn_fail(DCN_ERR_ARG, "members is NULL");
+    if (n == 0 || n > DCN_MAX_SET_MEMBERS)
+        return dcn_fail(DCN_ERR_ARG, "an index set has 1 to 32 members, not " + std::to_string(n));
+    uint64_t sum = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!members[i]) return dcn_fail(DCN_ERR_ARG, "member index " + std::to_string(i) + " is NULL");
+        int rc = same_params(members[0], members[i]);
+        if (rc != DCN_OK) return rc;
+        sum += members[i]->n_keys; // worst case, as union sizes its table
+    }
+    dcn_index *set = new (std::nothrow) dcn_index();
+    if (!set) return dcn_fail(DCN_ERR_NOMEM, "host allocation failed");
+    set->device = members[0]->device;
+    set->variant = members[0]->variant;
+    set->k = members[0]->k;
+    set->w = members[0]->w;
+    int rc = dcn_table_alloc(set, std::max<uint64_t>(sum, 16));
+    if (rc == DCN_OK) {
+        const uint64_t n_slots = set->n_groups * DCN_GROUP_SLOTS;
+        hipError_t e = hipMalloc((void **)&set->d_labels, n_slots * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(set->d_labels, 0, n_slots * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess)
+            rc = dcn_fail(e == hipErrorOutOfMemory ? DCN_ERR_NOMEM : DCN_ERR_HIP, std::string("index set labels: ") + hipGetErrorString(e));
+    }
+    set->n_members = n;
+    for (uint32_t i = 0; i < n && rc == DCN_OK; ++i) rc = dcn_set_add_member(set, members[i], i);
+    if (rc != DCN_OK) {
+        dcn_index_destroy(set);
+        return rc;
+    }
+    *out = set;
+    return DCN_OK;
+}
+
+extern "C" void dcn_index_set_destroy(dcn_index *set) { dcn_index_destroy(set); }
+
+extern "C" int dcn_index_set_info(const dcn_index *set, uint32_t *n_members, uint8_t *k, uint8_t *w, uint64_t *n_keys,
+                                  uint64_t *table_bytes) {
+    DCN_TRY(check_set(set));
+    if (n_members) *n_members = set->n_members;
+    if (k) *k = set->k;
+    if (w) *w = set->w;
+    if (n_keys) *n_keys = set->n_keys;
+    if (table_bytes) *table_bytes = set->n_groups * DCN_GROUP_SLOTS * (sizeof(uint64_t) + sizeof(uint32_t));
+    return DCN_OK;
+}
+
+namespace {
+int classify_check(dcn_ctx *ctx, const dcn_index *set, const dcn_params *params) {
+    if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
+    DCN_TRY(check_set(set));
+    DCN_TRY(check_params(params));
+    const dcn_index *ix = ctx->index;
+    if (ix->k != set->k || ix->w != set->w)
+        return dcn_fail(DCN_ERR_ARG, "the context's index (k=" + std::to_string((int)ix->k) + ", w=" + std::to_string((int)ix->w) +
+                                         ") and the set (k=" + std::to_string((int)set->k) + ", w=" + std::to_string((int)set->w) +
+                                         ") differ");
+    if (ix->device != set->device) return dcn_fail(DCN_ERR_ARG, "the context and the set live on different devices");
+    if (ix->variant != set->variant)
+        return dcn_fail(DCN_ERR_ARG, "the context's index and the set were created under different minimizer rules");
+    if (slots_busy(ctx) || ctx->batch_pending) return dcn_fail(DCN_ERR_ARG, "batches are in flight on this context: wait for them first");
+    return DCN_OK;
+}
+
+// the lazily allocated buffers of classification: the dump arrays, the work list and (host form) the outputs
+int classify_buffers(dcn_ctx *c, uint32_t n_members, bool host_outputs) {
+    if (!c->d_dump_hash) {
+        DCN_TRY(dev_alloc(&c->d_dump_hash, c->max_bases + 2, "dump_hash"));
+        DCN_TRY(dev_alloc(&c->d_dump_pos, c->max_bases + 2, "dump_pos"));
+        DCN_TRY(dev_alloc(&c->d_dump_valid, c->max_bases + 2, "dump_valid"));
+        DCN_TRY(dev_alloc(&c->d_dump_count, c->max_tiles, "dump_count"));
+    }
+    if (!c->d_cls_big) {
+        DCN_TRY(dev_alloc(&c->d_cls_big, c->max_reads, "classify work list"));
+        DCN_TRY(dev_alloc(&c->d_cls_n_big, 1, "classify work list length"));
+    }
+    if (host_outputs) {
+        if (!c->d_cls_match) {
+            DCN_TRY(dev_alloc(&c->d_cls_match, c->max_reads, "classify match"));
+            DCN_TRY(dev_alloc(&c->d_cls_total, c->max_reads, "classify total"));
+        }
+        if (c->cls_hits_members < n_members) {
+            if (c->d_cls_hits) hipFree(c->d_cls_hits);
+            c->d_cls_hits = nullptr;
+            c->cls_hits_members = 0;
+            DCN_TRY(dev_alloc(&c->d_cls_hits, (uint64_t)c->max_reads * n_members, "classify hits"));
+            c->cls_hits_members = n_members;
+        }
+    }
+    return DCN_OK;
+}
+
+// pack -> plan -> scan (minimizer dump) -> classification kernels, on the context's stream; the batch's inputs are
+// device pointers (the host form has staged them into the context's buffers).  Leaves the six counters alone.
+int classify_enqueue(dcn_ctx *c, const dcn_index *set, const uint8_t *d_ascii, const uint64_t *d_offsets,
+                     const uint32_t *d_unit_id, uint32_t n_reads, uint64_t n_bases, uint32_t n_units,
+                     const dcn_params *params, uint32_t *d_match, uint32_t *d_hits, uint32_t *d_total) {
+    hipStream_t st = c->stream;
+    DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
+    DCN_HIP(hipMemsetAsync(c->d_cls_n_big, 0, sizeof(uint32_t), st));
+    int prof_slot = -1;
+    DCN_TRY(prof_begin(c, &prof_slot));
+    uint32_t *packed = c->d_packed + DCN_FRONT_PAD, *invmask = c->d_invmask + DCN_FRONT_PAD;
+    DCN_TRY(dcn_launch_pack(d_ascii, 0, n_bases, packed, invmask, c->d_status, st));
+    DCN_PROF_MARK(DCN_STAGE_PACK);
+    dcn_plan_args pa = {};
+    pa.ascii = d_ascii;
+    pa.offsets = d_offsets;
+    pa.unit_id = d_unit_id;
+    pa.n_reads = n_reads;
+    pa.n_units = n_units;
+    pa.k = set->k;
+    pa.w = set->w;
+    pa.prefix_length = params->prefix_length;
+    pa.tile_windows = c->tile_windows;
+    pa.read_tiles = c->d_read_tiles;
+    pa.read_tile_first = c->d_read_tile_first;
+    pa.unit_first_read = c->d_unit_first_read;
+    pa.unit_tile_first = c->d_unit_tile_first;
+    pa.unit_tile_count = c->d_unit_tile_count;
+    pa.tile_cursor = &c->d_status->n_tiles;
+    pa.tiles = c->d_tiles;
+    pa.status = c->d_status;
+    pa.stream_bases = n_bases;
+    pa.check_offsets = 1;
+    pa.max_tiles = c->max_tiles;
+    DCN_TRY(dcn_launch_plan(pa, st));
+    DCN_PROF_MARK(DCN_STAGE_PLAN);
+    dcn_scan_args sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.packed = packed;
+    sa.invmask = invmask;
+    sa.tiles = c->d_tiles;
+    sa.n_tiles = &c->d_status->n_tiles;
+    sa.table = set->view();
+    sa.k = set->k;
+    sa.variant = set->variant;
+    sa.w = set->w;
+    sa.stream_bases = n_bases;
+    sa.status = c->d_status;
+    sa.dump_hash = c->d_dump_hash;
+    sa.dump_pos = c->d_dump_pos;
+    sa.dump_valid = c->d_dump_valid;
+    sa.dump_count = c->d_dump_count;
+    sa.dump_abs = 1; // (positions are not looked at)
+    uint64_t tile_bound = std::min<uint64_t>((uint64_t)n_reads + n_bases / c->tile_windows + 1, c->max_tiles);
+    DCN_TRY(dcn_launch_scan(sa, (uint32_t)tile_bound, true, st));
+    DCN_PROF_MARK(DCN_STAGE_SCAN);
+    dcn_classify_args ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.table = set->view();
+    ca.labels = set->d_labels;
+    ca.zero_label = set->zero_label;
+    ca.n_members = set->n_members;
+    ca.tiles = c->d_tiles;
+    ca.n_tiles = &c->d_status->n_tiles;
+    ca.offsets = d_offsets;
+    ca.read_tiles = c->d_read_tiles;
+    ca.read_tile_first = c->d_read_tile_first;
+    ca.unit_first_read = d_unit_id ? c->d_unit_first_read : nullptr;
+    ca.dump_hash = c->d_dump_hash;
+    ca.dump_valid = c->d_dump_valid;
+    ca.dump_count = c->d_dump_count;
+    ca.tile_windows = c->tile_windows;
+    ca.n_units = n_units;
+    ca.abs_threshold = params->abs_threshold;
+    ca.rel_threshold = params->rel_threshold;
+    ca.match = d_match;
+    ca.hits = d_hits;
+    ca.total = d_total;
+    ca.big = c->d_cls_big;
+    ca.n_big = c->d_cls_n_big;
+    ca.status = c->d_status;
+    ca.report = c->d_report;
+    DCN_TRY(dcn_launch_classify_units(ca, st));
+    DCN_PROF_MARK(DCN_STAGE_DISTINCT);
+    DCN_TRY(dcn_launch_classify_big(ca, st));
+    DCN_PROF_MARK(DCN_STAGE_FINISH);
+    if (prof_slot >= 0) c->prof_used[prof_slot] = true;
+    // a later device-pointer filter batch packs one batch ahead into these packed buffers on its own stream, after the
+    // events below: they now stand after this run
+    if (c->pack_ahead_state == 1) {
+        DCN_HIP(hipEventRecord(c->plan_done, st));
+        for (int i = 0; i < 2; ++i) DCN_HIP(hipEventRecord(c->buf_free[i], st));
+    }
+    c->batch_pending = true; // dcn_ctx_synchronize reports what the plan kernel found wrong with the batch
+    return DCN_OK;
+}
+} // namespace
+
+extern "C" int dcn_classify_batch(dcn_ctx *ctx, const dcn_index *set, const uint8_t *bases, const uint64_t *offsets,
+                                  const uint32_t *unit_id, uint32_t n_reads, const dcn_params *params, uint32_t *match,
+                                  uint32_t *hits, uint32_t *total) {
+    DCN_TRY(classify_check(ctx, set, params));
+    if (n_reads == 0) return DCN_OK;
+    if (!offsets || !match) return dcn_fail(DCN_ERR_ARG, "offsets/match is NULL");
+    DCN_TRY(validate_host_batch(ctx, offsets, n_reads));
+    uint32_t n_units = n_reads;
+    if (unit_id) {
+        if (unit_id[0] != 0) return dcn_fail(DCN_ERR_ARG, "unit_id[0] must be 0");
+        for (uint32_t r = 1; r < n_reads; ++r)
+            if (unit_id[r] != unit_id[r - 1] && unit_id[r] != unit_id[r - 1] + 1)
+                return dcn_fail(DCN_ERR_ARG, "unit_id must be non-decreasing in steps of 0 or 1");
+        n_units = unit_id[n_reads - 1] + 1;
+    }
+    const uint64_t n_bases = offsets[n_reads];
+    if (n_bases > 0 && !bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
+    dcn_ctx *c = ctx;
+    DCN_HIP(hipSetDevice(c->device));
+    DCN_TRY(classify_buffers(c, set->n_members, true));
+    DCN_TRY(staged_h2d(c, c->d_ascii, bases, n_bases));
+    DCN_TRY(staged_h2d(c, c->d_offsets, offsets, (uint64_t)(n_reads + 1) * sizeof(uint64_t)));
+    if (unit_id) DCN_TRY(staged_h2d(c, c->d_unit_id, unit_id, (uint64_t)n_reads * sizeof(uint32_t)));
+    DCN_HIP(hipEventRecord(c->copy_done, c->copy_stream));
+    DCN_HIP(hipStreamWaitEvent(c->stream, c->copy_done, 0));
+    DCN_TRY(classify_enqueue(c, set, c->d_ascii, c->d_offsets, unit_id ? c->d_unit_id : nullptr, n_reads, n_bases, n_units,
+                             params, c->d_cls_match, c->d_cls_hits, c->d_cls_total));
+    DCN_TRY(sync_and_check(c, nullptr));
+    DCN_HIP(hipMemcpy(match, c->d_cls_match, (uint64_t)n_units * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (hits)
+        DCN_HIP(hipMemcpy(hits, c->d_cls_hits, (uint64_t)n_units * set->n_members * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (total) DCN_HIP(hipMemcpy(total, c->d_cls_total, (uint64_t)n_units * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return DCN_OK;
+}
+
+extern "C" int dcn_classify_batch_device(dcn_ctx *ctx, const dcn_index *set, const uint8_t *d_bases,
+                                         const uint64_t *d_offsets, const uint32_t *d_unit_id, uint32_t n_reads,
+                                         uint64_t n_bases, uint32_t n_units, const dcn_params *params, uint32_t *d_match,
+                                         uint32_t *d_hits, uint32_t *d_total) {
+    DCN_TRY(classify_check(ctx, set, params));
+    if (n_reads == 0) return DCN_OK;
+    if (!d_bases || !d_offsets || !d_match) return dcn_fail(DCN_ERR_ARG, "d_bases/d_offsets/d_match is NULL");
+    if (n_reads > ctx->max_reads) return dcn_fail(DCN_ERR_CAPACITY, "n_reads exceeds the context's max_batch_reads");
+    if (n_bases > ctx->max_bases) return dcn_fail(DCN_ERR_CAPACITY, "n_bases exceeds the context's max_batch_bases");
+    if (n_units == 0 || n_units > n_reads || (!d_unit_id && n_units != n_reads))
+        return dcn_fail(DCN_ERR_ARG, "n_units inconsistent with n_reads / d_unit_id");
+    DCN_HIP(hipSetDevice(ctx->device));
+    DCN_TRY(classify_buffers(ctx, set->n_members, false));
+    return classify_enqueue(ctx, set, d_bases, d_offsets, d_unit_id, n_reads, n_bases, n_units, params, d_match, d_hits,
+                            d_total);
 }

@@ -1,0 +1,368 @@
+// classify.hip -- labelled index sets and per-member classification of a batch (dcn_index_set_create,
+// dcn_classify_batch*).
+//
+// A set is one open-addressing table over the union of its members' keys (the slot layout of index_table.hip) with a
+// parallel u32 array of member masks.  A probe reads the home group as dcn_table_contains_dev does; a hit reads the
+// 4-byte label at the slot it matched, so one probe answers "which members hold this key" for up to 32 members.
+//
+// Classification runs on the minimizer dump of the batch (scan_kernel<..., DUMP=true>, which leaves every window's
+// minimizer hash and its ACGT flag in the dump arrays) and then:
+//   classify_units_kernel  one lane per unit: walks the unit's tiles, counts the valid entries (total), probes the set
+//                          for each, keeps the distinct hits of the unit in an LDS list and their member bits in LDS
+//                          counters, applies the thresholds per member.  A unit with more entries than the lane takes,
+//                          or more distinct hits than its list holds, is appended to a work list instead.
+//   classify_big_kernel    one workgroup per listed unit: the same counts with an LDS hash set, in hash partitions
+//                          sized so that each fits the set (more partitions if one overflows): exact for any unit size,
+//                          without global scratch.
+#include "dcn_classify.h"
+#include "dcn_probe.h"
+
+#include <algorithm>
+
+namespace {
+
+__device__ inline uint32_t set_slot_label(const dcn_classify_args &a, uint32_t g, uint32_t s) {
+    return a.labels[(uint64_t)g * DCN_GROUP_SLOTS + s];
+}
+
+// member mask of `key` (non-zero) whose home group g has been loaded into grp: 0 = in no member
+__device__ inline uint32_t set_label_from(const dcn_classify_args &a, uint64_t key, uint32_t g, dcn_group grp) {
+    for (;;) {
+        if (grp.a.x == key) return set_slot_label(a, g, 0);
+        if (grp.a.y == key) return set_slot_label(a, g, 1);
+#if DCN_GROUP_SLOTS == 4
+        if (grp.b.x == key) return set_slot_label(a, g, 2);
+        if (grp.b.y == key) return set_slot_label(a, g, 3);
+        if (grp.a.x == 0 || grp.a.y == 0 || grp.b.x == 0 || grp.b.y == 0) return 0;
+#else
+        if (grp.a.x == 0 || grp.a.y == 0) return 0;
+#endif
+        g = (g + 1) & a.table.group_mask;
+        grp = dcn_load_group(a.table, g);
+    }
+}
+
+// slot index of `key` (non-zero) in the set, ~0 when it is in no member
+__device__ inline uint64_t set_find_slot(const dcn_classify_args &a, uint64_t key, uint32_t g, dcn_group grp) {
+    for (;;) {
+        const uint64_t s0 = (uint64_t)g * DCN_GROUP_SLOTS;
+        if (grp.a.x == key) return s0;
+        if (grp.a.y == key) return s0 + 1;
+#if DCN_GROUP_SLOTS == 4
+        if (grp.b.x == key) return s0 + 2;
+        if (grp.b.y == key) return s0 + 3;
+        if (grp.a.x == 0 || grp.a.y == 0 || grp.b.x == 0 || grp.b.y == 0) return ~0ull;
+#else
+        if (grp.a.x == 0 || grp.a.y == 0) return ~0ull;
+#endif
+        g = (g + 1) & a.table.group_mask;
+        grp = dcn_load_group(a.table, g);
+    }
+}
+
+__device__ inline uint32_t set_label(const dcn_classify_args &a, uint64_t key) {
+    if (key == 0) return a.zero_label;
+    const uint32_t g = dcn_group_of(key, a.table.group_shift, a.table.group_mask);
+    return set_label_from(a, key, g, dcn_load_group(a.table, g));
+}
+
+__device__ inline void unit_reads(const dcn_classify_args &a, uint32_t u, uint32_t *r0, uint32_t *r1) {
+    *r0 = a.unit_first_read ? a.unit_first_read[u] : u;
+    *r1 = a.unit_first_read ? a.unit_first_read[u + 1] : u + 1;
+}
+
+__device__ inline void write_unit(const dcn_classify_args &a, uint32_t u, uint32_t total, uint32_t match) {
+    if (a.total) a.total[u] = total;
+    a.match[u] = match;
+}
+
+__global__ __launch_bounds__(DCN_CLS_LANES) void classify_units_kernel(dcn_classify_args a) {
+    __shared__ uint64_t s_hash[DCN_CLS_LANE_HITS][DCN_CLS_LANES];
+    __shared__ uint8_t s_cnt[DCN_MAX_SET_MEMBERS][DCN_CLS_LANES];
+    const uint32_t lane = threadIdx.x, u = blockIdx.x * DCN_CLS_LANES + lane;
+    if (u >= a.n_units) return;
+    const uint32_t n = a.n_members;
+    if (a.status->bad_offsets) { // tiles and read ranges are not looked at (api.hip reports DCN_ERR_ARG)
+        if (u == 0) a.report->bad_offsets = 1;
+        write_unit(a, u, 0, 0);
+        if (a.hits)
+            for (uint32_t j = 0; j < n; ++j) a.hits[(uint64_t)u * n + j] = 0;
+        return;
+    }
+    const uint32_t NT = *a.n_tiles, tw = a.tile_windows;
+    uint32_t r0, r1;
+    unit_reads(a, u, &r0, &r1);
+    uint32_t n_entries = 0;
+    for (uint32_t r = r0; r < r1; ++r) {
+        const uint32_t first = a.read_tile_first[r], ntl = a.read_tiles[r];
+        for (uint32_t j = 0; j < ntl && first + j < NT; ++j) n_entries += a.dump_count[first + j];
+    }
+    if (n_entries > DCN_CLS_LANE_ENTRIES) {
+        a.big[atomicAdd(a.n_big, 1u)] = u;
+        return;
+    }
+    for (uint32_t j = 0; j < n; ++j) s_cnt[j][lane] = 0;
+    uint32_t tot = 0, nh = 0;
+    bool over = false;
+    uint64_t hb[4];
+    uint32_t nb = 0;
+    // probes of up to four entries are issued together: their home groups are loaded before any is resolved, and the
+    // labels of the hits among them before any is counted
+    auto flush = [&]() {
+        dcn_group gr[4];
+        uint32_t gi[4];
+        uint32_t m[4];
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) {
+            if (i < nb && hb[i] != 0) {
+                gi[i] = dcn_group_of(hb[i], a.table.group_shift, a.table.group_mask);
+                gr[i] = dcn_load_group(a.table, gi[i]);
+            }
+        }
+        uint64_t at[4];
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) at[i] = (i < nb && hb[i] != 0) ? set_find_slot(a, hb[i], gi[i], gr[i]) : ~0ull;
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) m[i] = at[i] != ~0ull ? a.labels[at[i]] : (i < nb && hb[i] == 0 ? a.zero_label : 0u);
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) {
+            if (i >= nb || over || !m[i]) continue;
+            const uint64_t h = hb[i];
+            bool dup = false;
+            for (uint32_t q = 0; q < nh && !dup; ++q) dup = s_hash[q][lane] == h;
+            if (dup) continue;
+            if (nh == DCN_CLS_LANE_HITS) {
+                over = true;
+                continue;
+            }
+            s_hash[nh++][lane] = h;
+            for (uint32_t mm = m[i]; mm; mm &= mm - 1) s_cnt[__ffs(mm) - 1][lane]++;
+        }
+        nb = 0;
+    };
+    for (uint32_t r = r0; r < r1 && !over; ++r) {
+        const uint64_t off = a.offsets[r];
+        const uint32_t first = a.read_tile_first[r], ntl = a.read_tiles[r];
+        for (uint32_t j = 0; j < ntl && first + j < NT && !over; ++j) {
+            const uint64_t base = off + (uint64_t)j * tw; // the tile's entries (scan_start + carry)
+            const uint32_t cnt = a.dump_count[first + j];
+            for (uint32_t e0 = 0; e0 < cnt && !over; e0 += 4) {
+                // four entries' flags and hashes loaded before any is looked at
+                uint8_t v[4];
+                uint64_t hv[4];
+#pragma unroll
+                for (uint32_t i = 0; i < 4; ++i) {
+                    const bool in = e0 + i < cnt;
+                    v[i] = in ? a.dump_valid[base + e0 + i] : 0;
+                    hv[i] = in ? a.dump_hash[base + e0 + i] : 0;
+                }
+#pragma unroll
+                for (uint32_t i = 0; i < 4; ++i) {
+                    if (!v[i] || over) continue;
+                    ++tot;
+#pragma unroll
+                    for (uint32_t q = 0; q < 4; ++q) // (constant indices: hb stays in registers)
+                        if (q == nb) hb[q] = hv[i];
+                    if (++nb == 4) flush();
+                }
+            }
+        }
+    }
+    if (nb && !over) flush();
+    if (over) {
+        a.big[atomicAdd(a.n_big, 1u)] = u;
+        return;
+    }
+    uint32_t match = 0;
+    for (uint32_t j = 0; j < n; ++j) {
+        const uint32_t c = s_cnt[j][lane];
+        if (a.hits) a.hits[(uint64_t)u * n + j] = c;
+        if (dcn_decide(c, tot, a.abs_threshold, a.rel_threshold, 0)) match |= 1u << j;
+    }
+    write_unit(a, u, tot, match);
+}
+
+// every valid dump entry of unit u's reads, spread over the workgroup's threads: BODY sees `h` (its hash)
+#define DCN_CLS_FOR_ENTRIES(BODY)                                                                                  \
+    for (uint32_t r = r0; r < r1; ++r) {                                                                           \
+        const uint64_t off = a.offsets[r];                                                                         \
+        const uint32_t first = a.read_tile_first[r];                                                               \
+        const uint64_t span = (uint64_t)a.read_tiles[r] * tw;                                                      \
+        for (uint64_t s = tid; s < span; s += DCN_CLS_BIG_THREADS) {                                               \
+            const uint32_t j = (uint32_t)(s / tw), e = (uint32_t)(s - (uint64_t)j * tw);                           \
+            if (first + j >= NT || e >= a.dump_count[first + j] || !a.dump_valid[off + s]) continue;               \
+            const uint64_t h = a.dump_hash[off + s];                                                               \
+            BODY                                                                                                   \
+        }                                                                                                          \
+    }
+
+__global__ __launch_bounds__(DCN_CLS_BIG_THREADS) void classify_big_kernel(dcn_classify_args a) {
+    __shared__ unsigned long long s_set[DCN_CLS_SET];
+    __shared__ uint32_t s_cnt[DCN_MAX_SET_MEMBERS];
+    __shared__ uint32_t s_tot, s_fill, s_over, s_zero;
+    if (a.status->bad_offsets) return;
+    const uint32_t tid = threadIdx.x, n = a.n_members, NB = *a.n_big;
+    const uint32_t NT = *a.n_tiles, tw = a.tile_windows;
+    constexpr uint32_t HALF = DCN_CLS_SET / 2, FULL = DCN_CLS_SET * 3 / 4;
+    for (uint32_t item = blockIdx.x; item < NB; item += gridDim.x) {
+        const uint32_t u = a.big[item];
+        uint32_t r0, r1;
+        unit_reads(a, u, &r0, &r1);
+        if (tid == 0) s_tot = 0;
+        __syncthreads();
+        uint32_t mine = 0;
+        DCN_CLS_FOR_ENTRIES({ (void)h; ++mine; })
+        if (mine) atomicAdd(&s_tot, mine);
+        __syncthreads();
+        const uint32_t tot = s_tot;
+        // hash partitions of at most ~HALF entries each: partition p takes the hashes whose mixed top bits fall in it
+        uint32_t P = max(1u, (tot + HALF - 1) / HALF);
+        for (;;) {
+            if (tid < DCN_MAX_SET_MEMBERS) s_cnt[tid] = 0;
+            if (tid == 0) {
+                s_over = 0;
+                s_zero = 0;
+            }
+            for (uint32_t p = 0; p < P; ++p) {
+                for (uint32_t i = tid; i < DCN_CLS_SET; i += DCN_CLS_BIG_THREADS) s_set[i] = 0;
+                if (tid == 0) s_fill = 0;
+                __syncthreads();
+                DCN_CLS_FOR_ENTRIES({
+                    if (P > 1 && __umulhi((uint32_t)((h * 0x9E3779B97F4A7C15ull) >> 32), P) != p) continue;
+                    uint32_t m = set_label(a, h);
+                    if (!m) continue;
+                    bool fresh = false;
+                    if (h == 0) {
+                        fresh = atomicExch(&s_zero, 1u) == 0u;
+                    } else {
+                        uint32_t slot = (uint32_t)h & (DCN_CLS_SET - 1);
+                        for (;;) {
+                            const unsigned long long cur = s_set[slot];
+                            if (cur == h) break;
+                            if (cur == 0) {
+                                // a fill limit below the set size keeps every walk finite; crossing it redoes the
+                                // unit with twice the partitions
+                                if (atomicAdd(&s_fill, 1u) >= FULL) {
+                                    s_over = 1;
+                                    break;
+                                }
+                                const unsigned long long old = atomicCAS(&s_set[slot], 0ull, (unsigned long long)h);
+                                if (old == 0) {
+                                    fresh = true;
+                                    break;
+                                }
+                                if (old == h) break;
+                            }
+                            slot = (slot + 1) & (DCN_CLS_SET - 1);
+                        }
+                    }
+                    if (fresh) {
+                        while (m) {
+                            atomicAdd(&s_cnt[__ffs(m) - 1], 1u);
+                            m &= m - 1;
+                        }
+                    }
+                })
+                __syncthreads();
+                if (s_over) break;
+            }
+            const bool again = s_over != 0;
+            __syncthreads();
+            if (!again) break;
+            P *= 2;
+        }
+        if (tid < n && a.hits) a.hits[(uint64_t)u * n + tid] = s_cnt[tid];
+        if (tid == 0) {
+            uint32_t match = 0;
+            for (uint32_t j = 0; j < n; ++j)
+                if (dcn_decide(s_cnt[j], tot, a.abs_threshold, a.rel_threshold, 0)) match |= 1u << j;
+            write_unit(a, u, tot, match);
+        }
+        __syncthreads();
+    }
+}
+#undef DCN_CLS_FOR_ENTRIES
+
+// insert-or-OR: every key of a member's slot array into the set, its bit into the label of the slot that holds it
+__global__ void set_add_member_kernel(uint64_t *slots, uint32_t *labels, uint32_t shift, uint32_t mask, const uint64_t *src,
+                                      uint64_t src_slots, uint32_t bit, unsigned long long *n_new) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    unsigned long long fresh = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < src_slots; i += stride) {
+        const uint64_t key = src[i];
+        if (key == 0) continue;
+        uint32_t g = dcn_group_of(key, shift, mask);
+        for (;;) {
+            unsigned long long *grp = (unsigned long long *)(slots + (uint64_t)g * DCN_GROUP_SLOTS);
+            int at = -1;
+            for (int s = 0; s < DCN_GROUP_SLOTS && at < 0; ++s) {
+                unsigned long long cur = __hip_atomic_load(&grp[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (cur == key) {
+                    at = s;
+                } else if (cur == 0) {
+                    unsigned long long old = atomicCAS(&grp[s], 0ull, (unsigned long long)key);
+                    if (old == 0) {
+                        fresh++;
+                        at = s;
+                    } else if (old == key) {
+                        at = s;
+                    }
+                }
+            }
+            if (at >= 0) {
+                atomicOr(&labels[(uint64_t)g * DCN_GROUP_SLOTS + at], bit);
+                break;
+            }
+            g = (g + 1) & mask;
+        }
+    }
+    if (fresh) atomicAdd(n_new, fresh);
+}
+
+} // namespace
+
+int dcn_launch_classify_units(const dcn_classify_args &a, hipStream_t stream) {
+    if (a.n_units == 0) return DCN_OK;
+    if (a.n_members == 0 || a.n_members > DCN_MAX_SET_MEMBERS) return dcn_fail(DCN_ERR_INTERNAL, "classify: member count");
+    const uint32_t blocks = (a.n_units + DCN_CLS_LANES - 1) / DCN_CLS_LANES;
+    hipLaunchKernelGGL(classify_units_kernel, dim3(blocks), dim3(DCN_CLS_LANES), 0, stream, a);
+    DCN_HIP(hipGetLastError());
+    return DCN_OK;
+}
+
+int dcn_launch_classify_big(const dcn_classify_args &a, hipStream_t stream) {
+    if (a.n_units == 0) return DCN_OK;
+    // a grid over the device's CUs (a few workgroups each), looping over the work list whose length is on the device
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const uint32_t blocks = std::min<uint32_t>(a.n_units, (uint32_t)std::max(cus, 1) * 4);
+    hipLaunchKernelGGL(classify_big_kernel, dim3(blocks), dim3(DCN_CLS_BIG_THREADS), 0, stream, a);
+    DCN_HIP(hipGetLastError());
+    return DCN_OK;
+}
+
+int dcn_set_add_member(dcn_index *set, const dcn_index *member, uint32_t bit) {
+    DCN_HIP(hipSetDevice(set->device));
+    unsigned long long *d_new = nullptr;
+    DCN_HIP(hipMalloc((void **)&d_new, sizeof(unsigned long long)));
+    hipError_t e = hipMemset(d_new, 0, sizeof(unsigned long long));
+    const dcn_table_view v = set->view();
+    const uint64_t src_slots = member->n_groups * DCN_GROUP_SLOTS;
+    if (e == hipSuccess && src_slots) {
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>((src_slots + 255) / 256, 256 * 16);
+        hipLaunchKernelGGL(set_add_member_kernel, dim3(blocks), dim3(256), 0, 0, set->d_slots, set->d_labels, v.group_shift,
+                           v.group_mask, member->d_slots, src_slots, 1u << bit, d_new);
+        e = hipGetLastError();
+    }
+    unsigned long long h_new = 0;
+    if (e == hipSuccess) e = hipMemcpy(&h_new, d_new, sizeof(h_new), hipMemcpyDeviceToHost);
+    hipFree(d_new);
+    if (e != hipSuccess) return dcn_fail(e == hipErrorOutOfMemory ? DCN_ERR_NOMEM : DCN_ERR_HIP, std::string("index set: ") + hipGetErrorString(e));
+    set->n_keys += h_new;
+    if (member->has_zero) {
+        if (!set->has_zero) set->n_keys += 1;
+        set->has_zero = true;
+        set->zero_label |= 1u << bit;
+    }
+    return DCN_OK;
+}

@@ -1,0 +1,54 @@
+// dcn_classify.h -- labelled index sets and the classification kernels (classify.hip; not part of the public ABI).
+#pragma once
+
+#include "dcn_internal.h"
+
+// A labelled set is a dcn_index whose table has the usual slot layout plus a parallel u32 array of member masks
+// (dcn_index::d_labels).  A probe reads the key's home group exactly as dcn_table_contains_dev does; only a hit reads the
+// 4-byte label at the slot it matched.
+constexpr uint32_t DCN_MAX_SET_MEMBERS = 32;
+
+// classify_units_kernel: one lane per unit, up to DCN_CLS_LANE_HITS distinct hits in LDS; a unit with more dump entries
+// than DCN_CLS_LANE_ENTRIES (or more distinct hits than the lane holds) goes to classify_big_kernel, one workgroup per unit
+// with an LDS hash set of DCN_CLS_SET slots swept in hash partitions (exact for any unit size, no global scratch).
+constexpr uint32_t DCN_CLS_LANES = 128;
+constexpr uint32_t DCN_CLS_LANE_HITS = 32;
+constexpr uint32_t DCN_CLS_LANE_ENTRIES = 64;
+constexpr uint32_t DCN_CLS_BIG_THREADS = 256;
+constexpr uint32_t DCN_CLS_SET = 4096;
+
+struct dcn_classify_args {
+    dcn_table_view table;   // the set's slots
+    const uint32_t *labels; // one mask per slot
+    uint32_t zero_label;
+    uint32_t n_members;
+    // plan + minimizer dump of the batch (scan_kernel<..., DUMP=true>)
+    const dcn_tile *tiles;
+    const uint32_t *n_tiles;
+    const uint64_t *offsets;         // n_reads + 1 base offsets of the batch stream
+    const uint32_t *read_tiles;      // per read: tile count
+    const uint32_t *read_tile_first; // per read: first tile
+    const uint32_t *unit_first_read; // n_units + 1, null: unit == read
+    const uint64_t *dump_hash;
+    const uint8_t *dump_valid;
+    const uint32_t *dump_count; // per tile: entries at [tile's read offset + j * tile_windows, + count)
+    uint32_t tile_windows;
+    uint32_t n_units;
+    uint64_t abs_threshold;
+    double rel_threshold;
+    // outputs (hits / total may be null)
+    uint32_t *match;
+    uint32_t *hits; // n_units * n_members
+    uint32_t *total;
+    // units handed to the workgroup kernel
+    uint32_t *big;
+    uint32_t *n_big;
+    const dcn_status *status;  // bad_offsets: the plan refused the batch, every output is written as zero
+    dcn_batch_report *report;  // receives bad_offsets (reported at the next dcn_ctx_synchronize)
+};
+
+int dcn_launch_classify_units(const dcn_classify_args &a, hipStream_t stream);
+int dcn_launch_classify_big(const dcn_classify_args &a, hipStream_t stream);
+
+// set->d_slots / d_labels allocated and clear: insert every key of `member`, OR-ing (1 << bit) into its label
+int dcn_set_add_member(dcn_index *set, const dcn_index *member, uint32_t bit);

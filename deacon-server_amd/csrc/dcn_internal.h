@@ -65,6 +65,11 @@ struct dcn_index {
     uint64_t n_groups = 0;
     uint64_t *d_slots = nullptr;
     bool has_zero = false;
+    // labelled index set (dcn_index_set_create, classify.hip): one u32 member mask per slot of d_slots, read only at the
+    // slot a probe matched; zero_label is key 0's mask (the counterpart of has_zero).  n_members == 0: a plain index.
+    uint32_t *d_labels = nullptr;
+    uint32_t n_members = 0;
+    uint32_t zero_label = 0;
     dcn_table_view view() const {
         dcn_table_view v;
         v.slots = d_slots;

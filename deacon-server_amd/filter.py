@@ -9,6 +9,7 @@ Names, argument meaning and results follow the Rust items they stand for (paths 
     .filter_batch(...)                  the whole paraseq per-record loop   (local_filter.rs:346-528)
     .stats()                            ProcessingStats                        (local_filter.rs:179-187)
   get_minimizer_hashes_and_positions <- filter_common.rs:211-310
+  IndexSet / Classifier              (no counterpart) several indexes in one table, per-member hits in one pass
   unpaired_should_keep / paired_should_keep <- remote_filter.rs:230-301
 
 Everything here is plumbing: all arithmetic happens in lib/libdeacon_hip.so on the GPU.
@@ -216,6 +217,120 @@ class Index:
     def close(self):
         if getattr(self, "_h", None):
             N.lib().dcn_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class IndexSet:
+    """Labelled index set (dcn_index_set_create): one device table over the union of 1..32 indexes of equal k, w,
+    minimizer rule and device, each key carrying a mask of the members that hold it (bit j = indexes[j]).  The set owns
+    its memory: the member Index objects may be closed afterwards."""
+
+    def __init__(self, indexes):
+        indexes = list(indexes)
+        arr = (C.c_void_p * max(len(indexes), 1))(*[i._h for i in indexes])
+        self._h = C.c_void_p()
+        N.check(N.lib().dcn_index_set_create(arr, len(indexes), C.byref(self._h)))
+        self.device = indexes[0].device
+        n, k, w = C.c_uint32(), C.c_uint8(), C.c_uint8()
+        keys, mem = C.c_uint64(), C.c_uint64()
+        N.check(N.lib().dcn_index_set_info(self._h, C.byref(n), C.byref(k), C.byref(w), C.byref(keys), C.byref(mem)))
+        self.n, self.k, self.w, self.n_keys, self.memory = n.value, k.value, w.value, keys.value, mem.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lib().dcn_index_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Classifier:
+    """Per-member classification of batches against an IndexSet (dcn_classify_batch): for every unit (read, or pair
+    through unit_id) the distinct hits against each member, the minimizer count, and a bit mask of the members whose
+    thresholds the unit meets (the search-mode decision of FilterProcessor against that member alone)."""
+
+    def __init__(self, index_set, abs_threshold=2, rel_threshold=0.01, prefix_length=0, device=None,
+                 max_batch_bases=1 << 26, max_batch_reads=1 << 20):
+        if device is not None and int(device) != index_set.device:
+            raise ValueError(f"the set lives on device {index_set.device}, not {device}")
+        self.index_set = index_set
+        self.abs_threshold = int(abs_threshold)
+        self.rel_threshold = float(rel_threshold)
+        self.prefix_length = int(prefix_length)
+        self.max_batch_bases = int(max_batch_bases)
+        self.max_batch_reads = int(max_batch_reads)
+        self._h = C.c_void_p()
+        N.check(N.lib().dcn_ctx_create(index_set._h, self.max_batch_bases, self.max_batch_reads, C.byref(self._h)))
+
+    def _params(self):
+        return Params(self.abs_threshold, self.rel_threshold, self.prefix_length, 0, 0)
+
+    def classify_batch(self, bases, offsets, unit_id=None):
+        """bases: concatenated ASCII; offsets[n_reads+1]; unit_id groups mates ->
+        (match u32[n_units], hits u32[n_units, n], total u32[n_units])"""
+        bases = _as_u8(bases)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_reads = len(offsets) - 1
+        if unit_id is not None:
+            unit_id = np.ascontiguousarray(unit_id, dtype=np.uint32)
+            n_units = int(unit_id[-1]) + 1 if n_reads else 0
+        else:
+            n_units = n_reads
+        n = self.index_set.n
+        match = np.zeros(max(n_units, 1), np.uint32)
+        hits = np.zeros((max(n_units, 1), n), np.uint32)
+        total = np.zeros(max(n_units, 1), np.uint32)
+        p = self._params()
+        N.check(N.lib().dcn_classify_batch(self._h, self.index_set._h, _ptr(bases) if len(bases) else None,
+                                           _ptr(offsets), _ptr(unit_id), n_reads, C.byref(p), _ptr(match), _ptr(hits),
+                                           _ptr(total)))
+        return match[:n_units], hits[:n_units], total[:n_units]
+
+    def classify_batch_device(self, d_bases, d_offsets, n_reads, n_bases, d_match, d_hits=None, d_total=None,
+                              d_unit_id=None, n_units=None):
+        """Same on device-resident inputs (raw device pointers); asynchronous: synchronize() before reading."""
+        p = self._params()
+        if n_units is None:
+            n_units = n_reads
+        N.check(N.lib().dcn_classify_batch_device(self._h, self.index_set._h, d_bases, d_offsets, d_unit_id, n_reads,
+                                                  n_bases, n_units, C.byref(p), d_match, d_hits, d_total))
+
+    def synchronize(self):
+        N.check(N.lib().dcn_ctx_synchronize(self._h))
+
+    @property
+    def stream(self):
+        return N.lib().dcn_ctx_stream(self._h)
+
+    def stats(self):
+        c = (C.c_uint64 * N.N_STATS)()
+        N.check(N.lib().dcn_ctx_stats(self._h, c))
+        return dict(zip(N.STAT_NAMES, list(c)))
+
+    def set_profiling(self, enable=True):
+        N.check(N.lib().dcn_ctx_set_profiling(self._h, 1 if enable else 0))
+
+    def profile(self):
+        """(stage_ms, n_batches): for classify calls the stages are pack, plan, scan (minimizer dump), and the two
+        classification kernels in the 'distinct' (one lane per unit) and 'finish' (one workgroup per large unit) slots"""
+        ms = (C.c_double * N.N_STAGES)()
+        n = C.c_uint64()
+        N.check(N.lib().dcn_ctx_profile(self._h, ms, C.byref(n)))
+        return dict(zip(N.STAGE_NAMES, list(ms))), n.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lib().dcn_ctx_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -66,9 +66,10 @@ enum {
 /* ABI version of this header.  MAJOR changes whenever the signature of an exported function or the layout of a struct
  * changes (a binding built against another major must refuse to run: its calls would pass the wrong arguments), MINOR
  * when entry points are added.  History: 0.x = the headers before versioning (dcn_pack_ascii took four arguments there);
- * 1.0 = dcn_pack_ascii(bases, n_bases, packed, invmask, saw_newline); 1.1 = dcn_abi_version, dcn_comm_* / dcn_stats_allreduce_rccl. */
+ * 1.0 = dcn_pack_ascii(bases, n_bases, packed, invmask, saw_newline); 1.1 = dcn_abi_version, dcn_comm_* / dcn_stats_allreduce_rccl;
+ * 1.2 = dcn_index_set_* / dcn_classify_batch*. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 1
+#define DCN_ABI_MINOR 2
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -293,6 +294,40 @@ int dcn_minimizer_hashes_batch(dcn_ctx *ctx, const uint8_t *bases, const uint64_
  * Host pointers; hits/total may be NULL.  prefix_length of params is ignored here. */
 int dcn_should_keep_hashes(dcn_ctx *ctx, const uint64_t *hashes, const uint64_t *hash_offsets, uint32_t n_units,
                            const dcn_params *params, uint8_t *keep, uint32_t *hits, uint32_t *total);
+
+/* ---- classification against several indexes in one pass ------------------------------------------------
+ * (no reference counterpart: the reference filters against one index, and index::union drops which input a key came
+ * from.)  A labelled index set is ONE device table over the union of 1..32 member indexes -- same k, w, minimizer rule
+ * and device, else DCN_ERR_ARG as for dcn_index_union -- in which every key carries a u32 mask: bit j = the key is in
+ * members[j].  A probe reads the key's home group exactly as the filter does; only a hit reads the 4-byte mask.  The set
+ * is built on the device from the members' tables (no key crosses to the host), sized for the sum of their keys, and owns
+ * its memory: the members may be destroyed afterwards.
+ * A set is a dcn_index: every dcn_index_* call that reads an index (keys, header, memory, contains, write_file, union,
+ * clone, a context) sees the union of its members.  dcn_index_set_destroy and dcn_index_destroy are the same call. */
+int dcn_index_set_create(const dcn_index *const *members, uint32_t n, dcn_index **out);
+void dcn_index_set_destroy(dcn_index *set);
+/* member count, k, w, distinct keys of the union, device bytes of slots + masks; DCN_ERR_ARG for an index that is not a set */
+int dcn_index_set_info(const dcn_index *set, uint32_t *n_members, uint8_t *k, uint8_t *w, uint64_t *n_keys,
+                       uint64_t *table_bytes);
+
+/* Classify one batch against every member of `set` at once.  Inputs as for dcn_filter_batch (a unit is a read, or a
+ * pair through unit_id; params->prefix_length applies; params->deplete is ignored).  Per unit u, with n members:
+ *   total[u]          minimizer count of the unit, as dcn_filter_batch's total (may be NULL)
+ *   hits[u * n + j]   DISTINCT minimizer hashes of the unit that are in member j: what a counting dcn_filter_batch on a
+ *                     context over member j alone returns as hits (may be NULL)
+ *   match[u]          bit j = dcn_decide(hits[u*n+j], total[u], abs, rel, deplete = 0): the unit meets the thresholds
+ *                     against member j
+ * The context's index must have the set's k, w, minimizer rule and device (the set itself may be the context's index);
+ * refused while batches are in flight.  The six counters of the context are left unchanged.  A unit of any length is
+ * counted exactly (no DCN_ERR_CAPACITY).  Blocking. */
+int dcn_classify_batch(dcn_ctx *ctx, const dcn_index *set, const uint8_t *bases, const uint64_t *offsets,
+                       const uint32_t *unit_id, uint32_t n_reads, const dcn_params *params, uint32_t *match,
+                       uint32_t *hits, uint32_t *total);
+/* The same on DEVICE pointers, enqueued on the context's stream (n_bases / n_units and the validation of d_offsets /
+ * d_unit_id as for dcn_filter_batch_device): dcn_ctx_synchronize waits for it and reports a bad batch. */
+int dcn_classify_batch_device(dcn_ctx *ctx, const dcn_index *set, const uint8_t *d_bases, const uint64_t *d_offsets,
+                              const uint32_t *d_unit_id, uint32_t n_reads, uint64_t n_bases, uint32_t n_units,
+                              const dcn_params *params, uint32_t *d_match, uint32_t *d_hits, uint32_t *d_total);
 
 /* ---- counters: ProcessingStats (src/local_filter.rs:179-187, merged at :388-396) -------------------------- */
 

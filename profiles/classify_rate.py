@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""Classification against N indexes in one pass (dcn_classify_batch_device) against N separate counting filter passes
+(dcn_filter_batch_device with hits and totals) on the same device-resident batch: BASELINE configs[1]'s shape (10 M x
+150 bp, half drawn from a 64 Mbp host genome, as bench.py).  Members: a panhuman-sized member 0 (bench.py's index: the host
+genome's minimizers + mix64 keys up to 409.9 M) and N - 1 members of 50 M keys (every (j+1)-th host key + mix64 keys of a
+range of their own), so that host reads hit several members.  For N = 1, 2, 4, 8: the set's device memory and build time,
+then classify and the N filter passes timed alternately (wall clock around enqueue + synchronize, best and median of REPS),
+and one profiled classify call for the stage split (pack, plan, dump scan, lane kernel, workgroup kernel).
+usage: python profiles/classify_rate.py [reads]"""
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, ".")
+import bench as B  # noqa: E402
+import deacon_server_amd as dcn  # noqa: E402
+
+REPS = 5
+reads = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
+dev = torch.device("cuda", 0)
+genome = B.make_host_genome(64_000_000, 3, dev)
+member0, keys0, host_keys, _, build0 = B.build_index(genome, B.PANHUMAN_KEYS, 0)
+del keys0
+batch = B.make_batches("short", genome, reads, 5, dev, rotate=1)[0]
+n_reads, n_bases = batch.n_reads, batch.n_bases
+print(f"batch: {n_reads:,} reads, {n_bases / 1e6:.1f} Mbp, device-resident ASCII; member 0: {member0.n_keys:,} keys "
+      f"({member0.table_bytes / 1e9:.1f} GB, built in {build0:.1f} s)", flush=True)
+
+members = [member0]
+for j in range(1, 8):
+    t0 = time.time()
+    hk = host_keys[::j + 1]
+    rnd = B.mix64_device((1 << 40) + (j << 32), 50_000_000 - len(hk), dev).cpu().numpy().view(np.uint64)
+    members.append(dcn.Index.from_keys(np.concatenate([hk, rnd]), B.K, B.W))
+    print(f"member {j}: {members[-1].n_keys:,} keys ({len(hk):,} host), {members[-1].table_bytes / 1e9:.1f} GB, "
+          f"built in {time.time() - t0:.1f} s", flush=True)
+
+procs = []  # one counting context per member, created once
+for m in members:
+    procs.append(dcn.FilterProcessor(m, max_batch_bases=n_bases, max_batch_reads=n_reads))
+d_hits = torch.zeros(n_reads, dtype=torch.int32, device=dev)
+d_total = torch.zeros(n_reads, dtype=torch.int32, device=dev)
+
+
+def filter_pass(n):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for p in procs[:n]:
+        p.filter_batch_device(batch.d_bases.data_ptr(), batch.d_offsets.data_ptr(), n_reads, n_bases,
+                              batch.d_keep.data_ptr(), d_hits.data_ptr(), d_total.data_ptr())
+        p.synchronize()
+    return time.perf_counter() - t0
+
+
+rows = []
+for n in (1, 2, 4, 8):
+    t0 = time.time()
+    s = dcn.IndexSet(members[:n])
+    set_build = time.time() - t0
+    clf = dcn.Classifier(s, max_batch_bases=n_bases, max_batch_reads=n_reads)
+    d_m = torch.zeros(n_reads, dtype=torch.int32, device=dev)
+    d_h = torch.zeros(n_reads * n, dtype=torch.int32, device=dev)
+    d_t = torch.zeros(n_reads, dtype=torch.int32, device=dev)
+
+    def classify_pass():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        clf.classify_batch_device(batch.d_bases.data_ptr(), batch.d_offsets.data_ptr(), n_reads, n_bases, d_m.data_ptr(),
+                                  d_h.data_ptr(), d_t.data_ptr())
+        clf.synchronize()
+        return time.perf_counter() - t0
+
+    classify_pass()
+    filter_pass(n)
+    tc, tf = [], []
+    for _ in range(REPS):
+        tc.append(classify_pass())
+        tf.append(filter_pass(n))
+    clf.set_profiling(True)
+    classify_pass()
+    stages, _ = clf.profile()
+    clf.set_profiling(False)
+    # consistency: member 0's column equals the last counting pass over member 0
+    procs[0].filter_batch_device(batch.d_bases.data_ptr(), batch.d_offsets.data_ptr(), n_reads, n_bases,
+                                 batch.d_keep.data_ptr(), d_hits.data_ptr(), d_total.data_ptr())
+    procs[0].synchronize()
+    same = bool(torch.equal(d_h.view(n_reads, n)[:, 0], d_hits) and torch.equal(d_t, d_total))
+    matched = [int(((d_m >> j) & 1).sum()) for j in range(n)]
+    r = {"n": n, "set_keys": s.n_keys, "set_gb": s.memory / 1e9, "set_build_s": set_build,
+         "classify_ms_best": min(tc) * 1e3, "classify_ms_median": statistics.median(tc) * 1e3,
+         "filter_n_ms_best": min(tf) * 1e3, "filter_n_ms_median": statistics.median(tf) * 1e3,
+         "stages_ms": {k: round(v, 3) for k, v in stages.items()}, "member0_column_equals_filter": same,
+         "units_matched": matched}
+    r["classify_mbps"] = n_bases / (r["classify_ms_median"] / 1e3) / 1e6
+    r["filter_n_mbps"] = n_bases / (r["filter_n_ms_median"] / 1e3) / 1e6
+    r["speedup_vs_n_filters"] = r["filter_n_ms_median"] / r["classify_ms_median"]
+    rows.append(r)
+    print(f"N={n}: set {s.n_keys:,} keys, {r['set_gb']:.1f} GB (slots + masks), built in {set_build:.1f} s | classify "
+          f"{r['classify_ms_median']:.2f} ms median ({r['classify_ms_best']:.2f} best) = {r['classify_mbps']:,.0f} Mbp/s | "
+          f"{n} counting filter passes {r['filter_n_ms_median']:.2f} ms median ({r['filter_n_ms_best']:.2f} best) = "
+          f"{r['filter_n_mbps']:,.0f} Mbp/s | {r['speedup_vs_n_filters']:.2f}x | stages (ms) {r['stages_ms']} | "
+          f"member 0 column == filter: {same} | units matched per member {matched}", flush=True)
+    clf.close()
+    s.close()
+    del d_m, d_h, d_t
+    torch.cuda.empty_cache()
+
+t1 = rows[0]["classify_ms_median"]
+print("summary: " + "; ".join(f"N={r['n']}: {r['classify_ms_median'] / t1:.2f}x the time of N=1, "
+                              f"{r['speedup_vs_n_filters']:.2f}x faster than {r['n']} filter passes" for r in rows), flush=True)
