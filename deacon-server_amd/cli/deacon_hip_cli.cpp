@@ -2960,7 +2960,11 @@ int run_classify(const ClassifyArgs &a) {
         dcn_index_destroy(m.p);
         m.p = nullptr;
     }
-    uint64_t max_bases = 64ull << 20;
+    uint64_t batch_bases = 32ull << 20, max_bases = 64ull << 20;
+    if (const char *e = std::getenv("DCN_CLI_CLASSIFY_BATCH_BASES")) { // test hook: many batches, records past the context
+        batch_bases = (uint64_t)std::max(64, std::atoi(e));
+        max_bases = 2 * batch_bases;
+    }
     const uint32_t max_reads = 1u << 20;
     dcn_ctx *ctx = nullptr;
     deacon::check(dcn_ctx_create(set.p, max_bases, max_reads, &ctx));
@@ -3040,7 +3044,6 @@ int run_classify(const ClassifyArgs &a) {
         }
         b.clear();
     };
-    const uint64_t batch_bases = 32ull << 20;
     const uint32_t batch_reads = max_reads - 2;
     for (;;) {
         if (!r1.next(b)) {

@@ -228,7 +228,7 @@ __global__ __launch_bounds__(DCN_CLS_BIG_THREADS) void classify_big_kernel(dcn_c
                 if (tid == 0) s_fill = 0;
                 __syncthreads();
                 DCN_CLS_FOR_ENTRIES({
-                    if (P > 1 && __umulhi((uint32_t)((h * 0x9E3779B97F4A7C15ull) >> 32), P) != p) continue;
+                    if (P > 1 && dcn_cls_partition(h, P) != p) continue;
                     uint32_t m = set_label(a, h);
                     if (!m) continue;
                     bool fresh = false;

@@ -17,6 +17,16 @@ constexpr uint32_t DCN_CLS_LANE_ENTRIES = 64;
 constexpr uint32_t DCN_CLS_BIG_THREADS = 256;
 constexpr uint32_t DCN_CLS_SET = 4096;
 
+// classify_big_kernel's hash partition of key h among P: the top 32 bits of a 64-bit multiplicative mix, scaled to [0, P)
+__host__ __device__ inline uint32_t dcn_cls_partition(uint64_t h, uint32_t P) {
+    const uint32_t x = (uint32_t)((h * 0x9E3779B97F4A7C15ull) >> 32);
+#ifdef __HIP_DEVICE_COMPILE__
+    return __umulhi(x, P);
+#else
+    return (uint32_t)(((uint64_t)x * P) >> 32);
+#endif
+}
+
 struct dcn_classify_args {
     dcn_table_view table;   // the set's slots
     const uint32_t *labels; // one mask per slot
