@@ -119,10 +119,14 @@ _SIGNATURES = {
     "dcn_classify_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(Params), _vp, _vp, _vp]),
     "dcn_classify_batch_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32,
                                             C.POINTER(Params), _vp, _vp, _vp]),
+    "dcn_index_set_coverage_enable": (C.c_int, [_vp, C.c_int]),
+    "dcn_index_set_coverage_reset": (C.c_int, [_vp]),
+    "dcn_index_set_coverage": (C.c_int, [_vp, _vp, _vp]),
+    "dcn_index_set_coverage_keys": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, _u64p]),
 }
 
 _lib = None
-ABI = (1, 2)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 3)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

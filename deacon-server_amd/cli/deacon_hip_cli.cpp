@@ -8,6 +8,7 @@
 //   deacon-hip filter <index> [input|-] [input2|-] [-o out] [-O out2] [-a 2] [-r 0.01] [-p 0] [-d] [-R]
 //                     [-s summary.json] [-t threads] [--compression-level 2] [--debug] [-q]
 //   deacon-hip classify -x <index> [-x <index>...] [input|-] [input2] [-a 2] [-r 0.01] [-p 0] [--per-read out.tsv|-]
+//                       [--coverage]
 //                     [-s summary.json] [-q]
 //
 // Flags, defaults, stderr messages and the JSON summary follow src/main.rs:24-234, src/local_filter.rs:575-824 and
@@ -2929,6 +2930,7 @@ struct ClassifyArgs {
     std::vector<std::string> indexes;
     std::string input = "-", input2, per_read, summary;
     bool has_input2 = false, has_per_read = false, has_summary = false, quiet = false;
+    bool coverage = false; // --coverage: distinct keys of each index the input touched (dcn_index_set_coverage)
     unsigned abs_threshold = 2;
     double rel_threshold = 0.01;
     size_t prefix_length = 0;
@@ -2960,6 +2962,8 @@ int run_classify(const ClassifyArgs &a) {
         dcn_index_destroy(m.p);
         m.p = nullptr;
     }
+    // the marks live with the set: contexts recreated for long records below keep adding to them
+    if (a.coverage) deacon::check(dcn_index_set_coverage_enable(set.p, 1));
     uint64_t batch_bases = 32ull << 20, max_bases = 64ull << 20;
     if (const char *e = std::getenv("DCN_CLI_CLASSIFY_BATCH_BASES")) { // test hook: many batches, records past the context
         batch_bases = (uint64_t)std::max(64, std::atoi(e));
@@ -3063,10 +3067,23 @@ int run_classify(const ClassifyArgs &a) {
     else if (tsv) std::fflush(tsv);
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
     auto prop = [](uint64_t x, uint64_t y) { return y ? (double)x / (double)y : 0.0; };
+    std::vector<uint64_t> observed(n, 0), set_keys(n, 0);
+    if (a.coverage) {
+        deacon::check(dcn_index_set_coverage(set.p, observed.data(), set_keys.data()));
+        for (uint32_t j = 0; j < n; ++j)
+            if (set_keys[j] != mkeys[j])
+                std::fprintf(stderr, "warning: the set holds %llu keys of %s, its index file %llu\n",
+                             (unsigned long long)set_keys[j], stems[j].c_str(), (unsigned long long)mkeys[j]);
+    }
     if (!a.quiet) {
         for (uint32_t j = 0; j < n; ++j)
             std::fprintf(stderr, "%s: %llu/%llu (%.3f%%) sequences matched\n", stems[j].c_str(), (unsigned long long)seqs_m[j],
                          (unsigned long long)seqs_in, prop(seqs_m[j], seqs_in) * 100.0);
+        if (a.coverage)
+            for (uint32_t j = 0; j < n; ++j)
+                std::fprintf(stderr, "%s: %llu/%llu (%.3f%%) index minimizers observed\n", stems[j].c_str(),
+                             (unsigned long long)observed[j], (unsigned long long)set_keys[j],
+                             prop(observed[j], set_keys[j]) * 100.0);
         std::fprintf(stderr, "Classified %llu sequences (%llu bp) against %u indexes in %s\n", (unsigned long long)seqs_in,
                      (unsigned long long)bp_in, n, fmt_duration(secs).c_str());
     }
@@ -3082,10 +3099,16 @@ int run_classify(const ClassifyArgs &a) {
             js += (j ? ",\n    {" : "\n    {");
             js += "\"path\": " + json_str(a.indexes[j]) + ", \"name\": " + json_str(stems[j]);
             std::snprintf(buf, sizeof buf, ", \"k\": %u, \"w\": %u, \"keys\": %llu, \"seqs_matched\": %llu, "
-                                           "\"seqs_matched_proportion\": %.17g, \"bp_matched\": %llu, \"bp_matched_proportion\": %.17g}",
-                          (unsigned)mk[j], (unsigned)mw[j], (unsigned long long)mkeys[j], (unsigned long long)seqs_m[j],
-                          prop(seqs_m[j], seqs_in), (unsigned long long)bp_m[j], prop(bp_m[j], bp_in));
+                                           "\"seqs_matched_proportion\": %.17g, \"bp_matched\": %llu, \"bp_matched_proportion\": %.17g",
+                          (unsigned)mk[j], (unsigned)mw[j], (unsigned long long)(a.coverage ? set_keys[j] : mkeys[j]),
+                          (unsigned long long)seqs_m[j], prop(seqs_m[j], seqs_in), (unsigned long long)bp_m[j], prop(bp_m[j], bp_in));
             js += buf;
+            if (a.coverage) {
+                std::snprintf(buf, sizeof buf, ", \"keys_observed\": %llu, \"keys_observed_proportion\": %.17g",
+                              (unsigned long long)observed[j], prop(observed[j], set_keys[j]));
+                js += buf;
+            }
+            js += "}";
         }
         js += "\n  ]\n}\n";
         FILE *f = std::fopen(a.summary.c_str(), "w");
@@ -3176,6 +3199,7 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "  -r, --rel-threshold <F>        Minimum relative proportion (0.0-1.0) of minimizer hits for a match [default: 0.01]\n"
                "  -p, --prefix-length <N>        Search only the first N nucleotides per sequence (0 = entire sequence) [default: 0]\n"
                "      --per-read <PATH>          One TSV row per record or pair (- for stdout): id, length, minimizers, hits per index, matched\n"
+               "      --coverage                 Also report how many distinct minimizers of each index the input observed\n"
                "  -s, --summary <SUMMARY>        Path to JSON summary output file\n"
                "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
                "  -q, --quiet                    Suppress progress reporting\n"
@@ -3310,6 +3334,7 @@ int main(int argc, char **argv) {
                 else if (s == "-p" || s == "--prefix-length") a.prefix_length = (size_t)std::atoll(need(++i).c_str());
                 else if (s == "--per-read") a.per_read = need(++i), a.has_per_read = true;
                 else if (s == "-s" || s == "--summary") a.summary = need(++i), a.has_summary = true;
+                else if (s == "--coverage") a.coverage = true;
                 else if (s == "-t" || s == "--threads") ++i;
                 else if (s == "-q" || s == "--quiet") a.quiet = true;
                 else if (s.size() > 1 && s[0] == '-' && s != "-") die("unexpected argument '" + s + "'");

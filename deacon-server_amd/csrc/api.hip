@@ -312,6 +312,8 @@ extern "C" int dcn_index_clone(const dcn_index *index, int device, dcn_index **o
     idx->d_labels = nullptr; // a replica of a labelled set is a plain index over the union of its members
     idx->n_members = 0;
     idx->zero_label = 0;
+    idx->d_cov = nullptr; // ... without coverage
+    idx->cov_words = 0;
     const uint64_t bytes = idx->n_groups * DCN_GROUP_SLOTS * sizeof(uint64_t);
     // Another GPU: the keys cross the link, not the table (a tenth of the bytes at the default 8 slots per key; dcn_table_clone_by_keys).
     // The same GPU: a device-to-device copy of the table at HBM's pace.  DCN_CLONE_BY_KEYS=1 / DCN_CLONE_BY_COPY=1 force one form
@@ -361,6 +363,7 @@ extern "C" void dcn_index_destroy(dcn_index *index) {
     hipSetDevice(index->device);
     if (index->d_slots) hipFree(index->d_slots);
     if (index->d_labels) hipFree(index->d_labels);
+    if (index->d_cov) hipFree(index->d_cov);
     delete index;
 }
 
@@ -2547,6 +2550,144 @@ extern "C" int dcn_index_set_info(const dcn_index *set, uint32_t *n_members, uin
     return DCN_OK;
 }
 
+// ---- coverage (classify.hip's COV kernels and sweeps) ---------------------------------------------------------------
+namespace {
+int check_coverage(const dcn_index *set) {
+    DCN_TRY(check_set(set));
+    if (!set->d_cov) return dcn_fail(DCN_ERR_ARG, "coverage is not enabled on this set (dcn_index_set_coverage_enable)");
+    return DCN_OK;
+}
+
+int hip_fail(hipError_t e, const char *what) {
+    return dcn_fail(e == hipErrorOutOfMemory ? DCN_ERR_NOMEM : DCN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// counts[0..n) of a coverage_count pass (all_slots: every occupied slot; else the marked ones), key 0 not included
+int coverage_counts(const dcn_index *set, bool all_slots, uint64_t *counts) {
+    unsigned long long *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, DCN_MAX_SET_MEMBERS * sizeof(unsigned long long));
+    if (e != hipSuccess) return hip_fail(e, "coverage");
+    int rc = DCN_OK;
+    e = hipMemset(d, 0, DCN_MAX_SET_MEMBERS * sizeof(unsigned long long));
+    if (e == hipSuccess) rc = dcn_coverage_count(set, all_slots, d, 0);
+    unsigned long long h[DCN_MAX_SET_MEMBERS] = {};
+    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
+    hipFree(d);
+    if (rc != DCN_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "coverage");
+    for (uint32_t j = 0; j < set->n_members; ++j) counts[j] = h[j];
+    return DCN_OK;
+}
+
+bool zero_observed(const dcn_index *set, int *rc) {
+    uint32_t w = 0;
+    const hipError_t e = hipMemcpy(&w, set->d_cov + set->cov_words, sizeof(w), hipMemcpyDeviceToHost);
+    *rc = e == hipSuccess ? DCN_OK : hip_fail(e, "coverage");
+    return (w & 1u) != 0;
+}
+} // namespace
+
+extern "C" int dcn_index_set_coverage_enable(dcn_index *set, int enable) {
+    DCN_TRY(check_set(set));
+    DCN_HIP(hipSetDevice(set->device));
+    if (!enable) {
+        if (set->d_cov) hipFree(set->d_cov);
+        set->d_cov = nullptr;
+        set->cov_words = 0;
+        return DCN_OK;
+    }
+    if (set->d_cov) return DCN_OK; // already on: the marks stay
+    const uint64_t words = (set->n_groups * DCN_GROUP_SLOTS + 31) / 32;
+    uint32_t *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, (words + 1) * sizeof(uint32_t));
+    if (e != hipSuccess) return hip_fail(e, "coverage bitmap");
+    e = hipMemset(d, 0, (words + 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        hipFree(d);
+        return hip_fail(e, "coverage bitmap");
+    }
+    set->d_cov = d;
+    set->cov_words = words;
+    uint64_t keys[DCN_MAX_SET_MEMBERS] = {};
+    int rc = coverage_counts(set, true, keys);
+    if (rc != DCN_OK) {
+        dcn_index_set_coverage_enable(set, 0);
+        return rc;
+    }
+    for (uint32_t j = 0; j < set->n_members; ++j)
+        set->cov_keys[j] = keys[j] + (set->has_zero && ((set->zero_label >> j) & 1u) ? 1 : 0);
+    return DCN_OK;
+}
+
+extern "C" int dcn_index_set_coverage_reset(dcn_index *set) {
+    DCN_TRY(check_coverage(set));
+    DCN_HIP(hipSetDevice(set->device));
+    DCN_HIP(hipMemset(set->d_cov, 0, (set->cov_words + 1) * sizeof(uint32_t)));
+    DCN_HIP(hipDeviceSynchronize());
+    return DCN_OK;
+}
+
+extern "C" int dcn_index_set_coverage(const dcn_index *set, uint64_t *observed, uint64_t *keys) {
+    DCN_TRY(check_coverage(set));
+    if (!observed || !keys) return dcn_fail(DCN_ERR_ARG, "observed/keys is NULL");
+    DCN_HIP(hipSetDevice(set->device));
+    uint64_t obs[DCN_MAX_SET_MEMBERS] = {};
+    DCN_TRY(coverage_counts(set, false, obs));
+    int rc = DCN_OK;
+    const bool zero = zero_observed(set, &rc);
+    DCN_TRY(rc);
+    for (uint32_t j = 0; j < set->n_members; ++j) {
+        observed[j] = obs[j] + (zero && ((set->zero_label >> j) & 1u) ? 1 : 0);
+        keys[j] = set->cov_keys[j];
+    }
+    return DCN_OK;
+}
+
+extern "C" int dcn_index_set_coverage_keys(const dcn_index *set, uint32_t member, uint64_t *out, uint64_t capacity,
+                                           uint64_t *n) {
+    DCN_TRY(check_coverage(set));
+    if (!n) return dcn_fail(DCN_ERR_ARG, "n is NULL");
+    *n = 0;
+    if (member != UINT32_MAX && member >= set->n_members)
+        return dcn_fail(DCN_ERR_ARG, "member " + std::to_string(member) + " out of range: the set has " +
+                                         std::to_string(set->n_members) + " members");
+    if (!out && capacity > 0) return dcn_fail(DCN_ERR_ARG, "out is NULL");
+    const uint32_t mask = member == UINT32_MAX ? ~0u : 1u << member;
+    DCN_HIP(hipSetDevice(set->device));
+    int rc = DCN_OK;
+    const bool zero = zero_observed(set, &rc) && (set->zero_label & mask);
+    DCN_TRY(rc);
+    unsigned long long *d_n = nullptr;
+    uint64_t *d_out = nullptr;
+    hipError_t e = hipMalloc((void **)&d_n, sizeof(unsigned long long));
+    unsigned long long count = 0;
+    if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) rc = dcn_coverage_count_mask(set, mask, d_n, 0);
+    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(&count, d_n, sizeof(count), hipMemcpyDeviceToHost);
+    const uint64_t total = count + (zero ? 1 : 0);
+    if (e == hipSuccess && rc == DCN_OK && total <= capacity && count > 0) {
+        e = hipMalloc((void **)&d_out, count * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof(unsigned long long));
+        if (e == hipSuccess) rc = dcn_coverage_collect(set, mask, d_out, count, d_n, 0);
+        unsigned long long written = 0;
+        if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(&written, d_n, sizeof(written), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && rc == DCN_OK && written != count)
+            rc = dcn_fail(DCN_ERR_INTERNAL, "coverage keys: the bitmap changed between the count and the copy (a classify call in flight?)");
+        if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(out, d_out, count * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    }
+    if (d_out) hipFree(d_out);
+    hipFree(d_n);
+    if (rc != DCN_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "coverage keys");
+    *n = total;
+    if (total > capacity)
+        return dcn_fail(DCN_ERR_CAPACITY, "coverage keys: " + std::to_string(total) + " observed keys, capacity " +
+                                              std::to_string(capacity));
+    if (zero) out[count] = 0;
+    return DCN_OK;
+}
+
 namespace {
 int classify_check(dcn_ctx *ctx, const dcn_index *set, const dcn_params *params) {
     if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
@@ -2674,6 +2815,8 @@ int classify_enqueue(dcn_ctx *c, const dcn_index *set, const uint8_t *d_ascii, c
     ca.n_big = c->d_cls_n_big;
     ca.status = c->d_status;
     ca.report = c->d_report;
+    ca.cov_bits = set->d_cov; // null: the kernels without coverage
+    ca.cov_zero = set->d_cov ? set->d_cov + set->cov_words : nullptr;
     DCN_TRY(dcn_launch_classify_units(ca, st));
     DCN_PROF_MARK(DCN_STAGE_DISTINCT);
     DCN_TRY(dcn_launch_classify_big(ca, st));

@@ -14,6 +14,9 @@
 //   classify_big_kernel    one workgroup per listed unit: the same counts with an LDS hash set, in hash partitions
 //                          sized so that each fits the set (more partitions if one overflows): exact for any unit size,
 //                          without global scratch.
+// Both take COV: with a coverage bitmap on the set (dcn_index_set_coverage_enable), every hit a unit counts as fresh
+// also sets its slot's bit; the COV = false instantiations are the kernels without coverage, instruction for instruction.
+// The coverage sweeps (dcn_index_set_coverage*) count and list the marked slots per member.
 #include "dcn_classify.h"
 #include "dcn_probe.h"
 
@@ -66,6 +69,20 @@ __device__ inline uint32_t set_label(const dcn_classify_args &a, uint64_t key) {
     return set_label_from(a, key, g, dcn_load_group(a.table, g));
 }
 
+// coverage: the bitmap word and bit of slot `at` (~0 = key 0, whose word is its own)
+__device__ inline uint32_t *cov_word(const dcn_classify_args &a, uint64_t at) {
+    return at == ~0ull ? a.cov_zero : a.cov_bits + (at >> 5);
+}
+__device__ inline uint32_t cov_bit(uint64_t at) { return at == ~0ull ? 1u : 1u << (at & 31); }
+// test, then set: `seen` is a plain load of the word; the atomic is issued only for a bit that was clear there (a key
+// that repeats across the batch's units -- most of them on host-heavy input -- costs a load and no atomic).  A stale
+// `seen` only costs a redundant OR, and OR is idempotent: a unit marked twice (the lane kernel's hand-off of an `over`
+// unit to the workgroup kernel, a partition retry there) marks what it marked once.
+__device__ inline void cov_mark(const dcn_classify_args &a, uint64_t at, uint32_t seen) {
+    const uint32_t bit = cov_bit(at);
+    if (!(seen & bit)) atomicOr(cov_word(a, at), bit);
+}
+
 __device__ inline void unit_reads(const dcn_classify_args &a, uint32_t u, uint32_t *r0, uint32_t *r1) {
     *r0 = a.unit_first_read ? a.unit_first_read[u] : u;
     *r1 = a.unit_first_read ? a.unit_first_read[u + 1] : u + 1;
@@ -76,6 +93,7 @@ __device__ inline void write_unit(const dcn_classify_args &a, uint32_t u, uint32
     a.match[u] = match;
 }
 
+template <bool COV>
 __global__ __launch_bounds__(DCN_CLS_LANES) void classify_units_kernel(dcn_classify_args a) {
     __shared__ uint64_t s_hash[DCN_CLS_LANE_HITS][DCN_CLS_LANES];
     __shared__ uint8_t s_cnt[DCN_MAX_SET_MEMBERS][DCN_CLS_LANES];
@@ -124,6 +142,12 @@ __global__ __launch_bounds__(DCN_CLS_LANES) void classify_units_kernel(dcn_class
         for (uint32_t i = 0; i < 4; ++i) at[i] = (i < nb && hb[i] != 0) ? set_find_slot(a, hb[i], gi[i], gr[i]) : ~0ull;
 #pragma unroll
         for (uint32_t i = 0; i < 4; ++i) m[i] = at[i] != ~0ull ? a.labels[at[i]] : (i < nb && hb[i] == 0 ? a.zero_label : 0u);
+        // COV: the bitmap words of the hits among them, loaded together (key 0 hits with at == ~0: its own word)
+        uint32_t seen[4];
+        if constexpr (COV) {
+#pragma unroll
+            for (uint32_t i = 0; i < 4; ++i) seen[i] = (i < nb && m[i]) ? *cov_word(a, at[i]) : ~0u;
+        }
 #pragma unroll
         for (uint32_t i = 0; i < 4; ++i) {
             if (i >= nb || over || !m[i]) continue;
@@ -136,6 +160,7 @@ __global__ __launch_bounds__(DCN_CLS_LANES) void classify_units_kernel(dcn_class
                 continue;
             }
             s_hash[nh++][lane] = h;
+            if constexpr (COV) cov_mark(a, at[i], seen[i]);
             for (uint32_t mm = m[i]; mm; mm &= mm - 1) s_cnt[__ffs(mm) - 1][lane]++;
         }
         nb = 0;
@@ -196,6 +221,22 @@ __global__ __launch_bounds__(DCN_CLS_LANES) void classify_units_kernel(dcn_class
         }                                                                                                          \
     }
 
+// COV: the member mask of h through set_find_slot, whose slot (~0 for key 0 or a miss) *at receives; else set_label
+template <bool COV>
+__device__ inline uint32_t big_label(const dcn_classify_args &a, uint64_t h, uint64_t *at) {
+    if constexpr (COV) {
+        *at = ~0ull;
+        if (h == 0) return a.zero_label;
+        const uint32_t g = dcn_group_of(h, a.table.group_shift, a.table.group_mask);
+        *at = set_find_slot(a, h, g, dcn_load_group(a.table, g));
+        return *at != ~0ull ? a.labels[*at] : 0u;
+    } else {
+        (void)at;
+        return set_label(a, h);
+    }
+}
+
+template <bool COV>
 __global__ __launch_bounds__(DCN_CLS_BIG_THREADS) void classify_big_kernel(dcn_classify_args a) {
     __shared__ unsigned long long s_set[DCN_CLS_SET];
     __shared__ uint32_t s_cnt[DCN_MAX_SET_MEMBERS];
@@ -229,7 +270,8 @@ __global__ __launch_bounds__(DCN_CLS_BIG_THREADS) void classify_big_kernel(dcn_c
                 __syncthreads();
                 DCN_CLS_FOR_ENTRIES({
                     if (P > 1 && dcn_cls_partition(h, P) != p) continue;
-                    uint32_t m = set_label(a, h);
+                    uint64_t at;
+                    uint32_t m = big_label<COV>(a, h, &at);
                     if (!m) continue;
                     bool fresh = false;
                     if (h == 0) {
@@ -257,6 +299,7 @@ __global__ __launch_bounds__(DCN_CLS_BIG_THREADS) void classify_big_kernel(dcn_c
                         }
                     }
                     if (fresh) {
+                        if constexpr (COV) cov_mark(a, at, *cov_word(a, at));
                         while (m) {
                             atomicAdd(&s_cnt[__ffs(m) - 1], 1u);
                             m &= m - 1;
@@ -282,6 +325,112 @@ __global__ __launch_bounds__(DCN_CLS_BIG_THREADS) void classify_big_kernel(dcn_c
     }
 }
 #undef DCN_CLS_FOR_ENTRIES
+
+// ---- coverage sweeps ---------------------------------------------------------------------------------------------
+constexpr uint32_t DCN_COV_THREADS = 256;
+
+// lane j of the wave (j < n) adds the wave's count of labels with bit j: one ballot per member (a bit-slice of the 64
+// lanes' labels), its popcount kept by the lane of that member
+__device__ inline void cov_tally(uint32_t L, uint32_t n, uint32_t lane, unsigned long long *mine) {
+    if (!__ballot(L != 0)) return;
+#pragma unroll
+    for (uint32_t j = 0; j < DCN_MAX_SET_MEMBERS; ++j) {
+        if (j < n) {
+            const unsigned long long b = __ballot((L >> j) & 1u);
+            if (lane == j) *mine += __popcll(b);
+        }
+    }
+}
+
+// per member j: counts[j] += marked slots (ALL: occupied slots) whose label has bit j.  Grid-stride in wave-uniform
+// steps over bitmap words (ALL: over slots); one LDS add per member per wave, one global add per member per workgroup.
+template <bool ALL>
+__global__ __launch_bounds__(DCN_COV_THREADS) void coverage_count_kernel(const uint32_t *bits, uint64_t n_words,
+                                                                         const uint32_t *labels, uint64_t n_slots,
+                                                                         uint32_t n, unsigned long long *counts) {
+    __shared__ unsigned long long s_cnt[DCN_MAX_SET_MEMBERS];
+    const uint32_t tid = threadIdx.x, lane = tid & (DCN_WAVE - 1);
+    if (tid < DCN_MAX_SET_MEMBERS) s_cnt[tid] = 0;
+    __syncthreads();
+    unsigned long long mine = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * DCN_COV_THREADS;
+    const uint64_t end = ALL ? n_slots : n_words;
+    for (uint64_t w0 = (uint64_t)blockIdx.x * DCN_COV_THREADS + (tid - lane); w0 < end; w0 += stride) {
+        const uint64_t i = w0 + lane;
+        if constexpr (ALL) {
+            cov_tally(i < n_slots ? labels[i] : 0u, n, lane, &mine);
+        } else {
+            uint32_t word = i < n_words ? bits[i] : 0u;
+            while (__ballot(word != 0)) {
+                uint32_t L = 0;
+                if (word) {
+                    L = labels[i * 32 + (__ffs(word) - 1)];
+                    word &= word - 1;
+                }
+                cov_tally(L, n, lane, &mine);
+            }
+        }
+    }
+    if (lane < n && mine) atomicAdd(&s_cnt[lane], mine);
+    __syncthreads();
+    if (tid < n && s_cnt[tid]) atomicAdd(&counts[tid], s_cnt[tid]);
+}
+
+// marked slots whose label meets `mask`: counted (out == null: *n_out += the count) or written to out[*n_out ...] with
+// one returning atomicAdd per wave (out holds cap keys: a position at or past cap is not written)
+__global__ __launch_bounds__(DCN_COV_THREADS) void coverage_keys_kernel(const uint32_t *bits, uint64_t n_words,
+                                                                        const uint32_t *labels, const uint64_t *slots,
+                                                                        uint32_t mask, uint64_t *out, uint64_t cap,
+                                                                        unsigned long long *n_out) {
+    __shared__ unsigned long long s_n;
+    const uint32_t tid = threadIdx.x, lane = tid & (DCN_WAVE - 1);
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    unsigned long long mine = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * DCN_COV_THREADS;
+    for (uint64_t w0 = (uint64_t)blockIdx.x * DCN_COV_THREADS + (tid - lane); w0 < n_words; w0 += stride) {
+        const uint64_t i = w0 + lane;
+        const uint32_t word = i < n_words ? bits[i] : 0u;
+        uint32_t c = 0;
+        for (uint32_t b = word; b; b &= b - 1)
+            if (labels[i * 32 + (__ffs(b) - 1)] & mask) ++c;
+        if (!out) {
+            mine += c;
+            continue;
+        }
+        // the wave's exclusive prefix of c, its total, and one atomicAdd by lane 0 for the wave's range of out
+        uint32_t incl = c;
+        for (uint32_t d = 1; d < DCN_WAVE; d <<= 1) {
+            const uint32_t v = __shfl_up(incl, d);
+            if (lane >= d) incl += v;
+        }
+        const uint32_t wave_total = __shfl(incl, DCN_WAVE - 1);
+        if (!wave_total) continue;
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(n_out, (unsigned long long)wave_total);
+        base = __shfl(base, 0);
+        uint64_t pos = base + (incl - c);
+        for (uint32_t b = word; b; b &= b - 1) {
+            const uint64_t s = i * 32 + (__ffs(b) - 1);
+            if (labels[s] & mask) {
+                if (pos < cap) out[pos] = slots[s];
+                ++pos;
+            }
+        }
+    }
+    if (!out) {
+        if (mine) atomicAdd(&s_n, mine);
+        __syncthreads();
+        if (tid == 0 && s_n) atomicAdd(n_out, s_n);
+    }
+}
+
+uint32_t cov_blocks(uint64_t items) {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + DCN_COV_THREADS - 1) / DCN_COV_THREADS,
+                                                             (uint64_t)std::max(cus, 1) * 8));
+}
 
 // insert-or-OR: every key of a member's slot array into the set, its bit into the label of the slot that holds it
 __global__ void set_add_member_kernel(uint64_t *slots, uint32_t *labels, uint32_t shift, uint32_t mask, const uint64_t *src,
@@ -325,7 +474,10 @@ int dcn_launch_classify_units(const dcn_classify_args &a, hipStream_t stream) {
     if (a.n_units == 0) return DCN_OK;
     if (a.n_members == 0 || a.n_members > DCN_MAX_SET_MEMBERS) return dcn_fail(DCN_ERR_INTERNAL, "classify: member count");
     const uint32_t blocks = (a.n_units + DCN_CLS_LANES - 1) / DCN_CLS_LANES;
-    hipLaunchKernelGGL(classify_units_kernel, dim3(blocks), dim3(DCN_CLS_LANES), 0, stream, a);
+    if (a.cov_bits)
+        hipLaunchKernelGGL(classify_units_kernel<true>, dim3(blocks), dim3(DCN_CLS_LANES), 0, stream, a);
+    else
+        hipLaunchKernelGGL(classify_units_kernel<false>, dim3(blocks), dim3(DCN_CLS_LANES), 0, stream, a);
     DCN_HIP(hipGetLastError());
     return DCN_OK;
 }
@@ -336,7 +488,37 @@ int dcn_launch_classify_big(const dcn_classify_args &a, hipStream_t stream) {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const uint32_t blocks = std::min<uint32_t>(a.n_units, (uint32_t)std::max(cus, 1) * 4);
-    hipLaunchKernelGGL(classify_big_kernel, dim3(blocks), dim3(DCN_CLS_BIG_THREADS), 0, stream, a);
+    if (a.cov_bits)
+        hipLaunchKernelGGL(classify_big_kernel<true>, dim3(blocks), dim3(DCN_CLS_BIG_THREADS), 0, stream, a);
+    else
+        hipLaunchKernelGGL(classify_big_kernel<false>, dim3(blocks), dim3(DCN_CLS_BIG_THREADS), 0, stream, a);
+    DCN_HIP(hipGetLastError());
+    return DCN_OK;
+}
+
+int dcn_coverage_count(const dcn_index *set, bool all_slots, unsigned long long *d_counts, hipStream_t stream) {
+    const uint64_t n_slots = set->n_groups * DCN_GROUP_SLOTS;
+    if (all_slots)
+        hipLaunchKernelGGL(coverage_count_kernel<true>, dim3(cov_blocks(n_slots)), dim3(DCN_COV_THREADS), 0, stream,
+                           set->d_cov, set->cov_words, set->d_labels, n_slots, set->n_members, d_counts);
+    else
+        hipLaunchKernelGGL(coverage_count_kernel<false>, dim3(cov_blocks(set->cov_words)), dim3(DCN_COV_THREADS), 0, stream,
+                           set->d_cov, set->cov_words, set->d_labels, n_slots, set->n_members, d_counts);
+    DCN_HIP(hipGetLastError());
+    return DCN_OK;
+}
+
+int dcn_coverage_count_mask(const dcn_index *set, uint32_t mask, unsigned long long *d_n, hipStream_t stream) {
+    hipLaunchKernelGGL(coverage_keys_kernel, dim3(cov_blocks(set->cov_words)), dim3(DCN_COV_THREADS), 0, stream, set->d_cov,
+                       set->cov_words, set->d_labels, set->d_slots, mask, nullptr, 0, d_n);
+    DCN_HIP(hipGetLastError());
+    return DCN_OK;
+}
+
+int dcn_coverage_collect(const dcn_index *set, uint32_t mask, uint64_t *d_out, uint64_t cap, unsigned long long *d_n,
+                         hipStream_t stream) {
+    hipLaunchKernelGGL(coverage_keys_kernel, dim3(cov_blocks(set->cov_words)), dim3(DCN_COV_THREADS), 0, stream, set->d_cov,
+                       set->cov_words, set->d_labels, set->d_slots, mask, d_out, cap, d_n);
     DCN_HIP(hipGetLastError());
     return DCN_OK;
 }

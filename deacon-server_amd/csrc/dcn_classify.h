@@ -55,10 +55,23 @@ struct dcn_classify_args {
     uint32_t *n_big;
     const dcn_status *status;  // bad_offsets: the plan refused the batch, every output is written as zero
     dcn_batch_report *report;  // receives bad_offsets (reported at the next dcn_ctx_synchronize)
+    // coverage (dcn_index_set_coverage_enable; null = off, the COV = false kernels): bit s of the bitmap = slot s's key
+    // was among a unit's counted minimizers; key 0, which has no slot, has a word of its own (bit 0)
+    uint32_t *cov_bits;
+    uint32_t *cov_zero;
 };
 
 int dcn_launch_classify_units(const dcn_classify_args &a, hipStream_t stream);
 int dcn_launch_classify_big(const dcn_classify_args &a, hipStream_t stream);
+
+// coverage sweeps of a set with a bitmap (dcn_index::d_cov): per member j, observed[j] += marked slots whose label has
+// bit j (keys[j] += occupied slots whose label has bit j, when all_slots); key 0 is left to the caller
+int dcn_coverage_count(const dcn_index *set, bool all_slots, unsigned long long *d_counts, hipStream_t stream);
+// *d_n += the marked slots whose label meets `mask` (any bit); collect writes their keys to d_out (cap entries, sized by
+// a count pass) in no particular order, *d_n counting from 0.  Key 0 is left to the caller.
+int dcn_coverage_count_mask(const dcn_index *set, uint32_t mask, unsigned long long *d_n, hipStream_t stream);
+int dcn_coverage_collect(const dcn_index *set, uint32_t mask, uint64_t *d_out, uint64_t cap, unsigned long long *d_n,
+                         hipStream_t stream);
 
 // set->d_slots / d_labels allocated and clear: insert every key of `member`, OR-ing (1 << bit) into its label
 int dcn_set_add_member(dcn_index *set, const dcn_index *member, uint32_t bit);

@@ -70,6 +70,11 @@ struct dcn_index {
     uint32_t *d_labels = nullptr;
     uint32_t n_members = 0;
     uint32_t zero_label = 0;
+    // coverage of a set (dcn_index_set_coverage_enable, classify.hip): cov_words u32 words of one bit per slot, then key
+    // 0's word; cov_keys[j] = distinct keys of member j in the set, counted once at enable (the set never changes)
+    uint32_t *d_cov = nullptr;
+    uint64_t cov_words = 0;
+    uint64_t cov_keys[32] = {};
     dcn_table_view view() const {
         dcn_table_view v;
         v.slots = d_slots;

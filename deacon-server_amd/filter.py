@@ -242,6 +242,36 @@ class IndexSet:
         N.check(N.lib().dcn_index_set_info(self._h, C.byref(n), C.byref(k), C.byref(w), C.byref(keys), C.byref(mem)))
         self.n, self.k, self.w, self.n_keys, self.memory = n.value, k.value, w.value, keys.value, mem.value
 
+    # ---- coverage (dcn_index_set_coverage*): distinct keys of each member observed by classify calls on this set ----
+    def enable_coverage(self, on=True):
+        """Allocate a zeroed observed-bitmap (on) or free it (off); every later classify call against the set, from
+        any Classifier, marks the set's keys among its units' counted minimizers.  Enabling twice keeps the marks."""
+        N.check(N.lib().dcn_index_set_coverage_enable(self._h, 1 if on else 0))
+
+    def reset_coverage(self):
+        N.check(N.lib().dcn_index_set_coverage_reset(self._h))
+
+    def coverage(self):
+        """(observed, keys): np.uint64[n] each -- keys[j] distinct keys of member j in the set, observed[j] how many of
+        them were marked.  Device-form batches must have been synchronized first."""
+        observed = np.zeros(self.n, np.uint64)
+        keys = np.zeros(self.n, np.uint64)
+        N.check(N.lib().dcn_index_set_coverage(self._h, _ptr(observed), _ptr(keys)))
+        return observed, keys
+
+    def observed_keys(self, member=None):
+        """the observed keys of member `member` (None: of any member), np.uint64 in no particular order"""
+        m = 0xFFFFFFFF if member is None else int(member)
+        if not 0 <= m <= 0xFFFFFFFF:
+            raise ValueError(f"member {member} out of range")
+        n = C.c_uint64()
+        rc = N.lib().dcn_index_set_coverage_keys(self._h, m, None, 0, C.byref(n))
+        if rc != N.DCN_ERR_CAPACITY:
+            N.check(rc)
+        out = np.zeros(max(n.value, 1), np.uint64)
+        N.check(N.lib().dcn_index_set_coverage_keys(self._h, m, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
+
     def close(self):
         if getattr(self, "_h", None):
             N.lib().dcn_index_set_destroy(self._h)

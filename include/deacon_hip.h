@@ -67,9 +67,9 @@ enum {
  * changes (a binding built against another major must refuse to run: its calls would pass the wrong arguments), MINOR
  * when entry points are added.  History: 0.x = the headers before versioning (dcn_pack_ascii took four arguments there);
  * 1.0 = dcn_pack_ascii(bases, n_bases, packed, invmask, saw_newline); 1.1 = dcn_abi_version, dcn_comm_* / dcn_stats_allreduce_rccl;
- * 1.2 = dcn_index_set_* / dcn_classify_batch*. */
+ * 1.2 = dcn_index_set_* / dcn_classify_batch*; 1.3 = dcn_index_set_coverage*. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 2
+#define DCN_ABI_MINOR 3
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -328,6 +328,32 @@ int dcn_classify_batch(dcn_ctx *ctx, const dcn_index *set, const uint8_t *bases,
 int dcn_classify_batch_device(dcn_ctx *ctx, const dcn_index *set, const uint8_t *d_bases, const uint64_t *d_offsets,
                               const uint32_t *d_unit_id, uint32_t n_reads, uint64_t n_bases, uint32_t n_units,
                               const dcn_params *params, uint32_t *d_match, uint32_t *d_hits, uint32_t *d_total);
+
+/* ---- coverage: which keys of each member a run of classify calls observed --------------------------------------
+ * (no reference counterpart.)  Breadth next to match counts: how many DISTINCT keys of each member the whole input
+ * touched.  After coverage is enabled on a set, every dcn_classify_batch / dcn_classify_batch_device call against that
+ * set, from any context, marks keys: key K is OBSERVED when some unit of such a call has K among the minimizer hashes
+ * counted in its total[u] -- after params->prefix_length and the ACGT filter -- and K is in the set.  That is exactly the
+ * union over units of the hashes behind hits[u*n+j], whether or not the unit matched anything.  The observed keys of
+ * member j are the observed keys whose mask has bit j.  Marks accumulate until dcn_index_set_coverage_reset or disable;
+ * a batch the plan refuses (bad offsets) marks nothing.  Key 0 has a mark of its own.
+ * The state (one bit per slot of the set's table, 1/64 of its slot bytes) belongs to the set: every context on the set's
+ * device marks the same bits.  dcn_index_set_create allocates none, dcn_index_set_info / dcn_index_memory do not count
+ * it, a dcn_index_clone of the set has none, dcn_index_destroy frees it.
+ * The reads below are blocking and order after nothing: the caller has waited for its classify calls first (the host
+ * form returns complete; the device form needs dcn_ctx_synchronize).  Every call returns DCN_ERR_ARG for an index that
+ * is not a set, and the reset, read and keys calls for a set without coverage. */
+/* allocate (enable != 0) a zeroed observed-bitmap for the set, or free it (0); not while classify calls on the set are
+ * in flight.  Enabling a set that has coverage keeps its marks. */
+int dcn_index_set_coverage_enable(dcn_index *set, int enable);
+/* clear every mark */
+int dcn_index_set_coverage_reset(dcn_index *set);
+/* n_members entries each: keys[j] = distinct keys of member j held by the set, observed[j] = how many of them are
+ * marked.  Neither may be NULL. */
+int dcn_index_set_coverage(const dcn_index *set, uint64_t *observed, uint64_t *keys);
+/* observed keys of member `member` (UINT32_MAX = of any member), arbitrary order; *n = count; DCN_ERR_CAPACITY if
+ * capacity < count (out may be NULL with capacity 0: *n still receives the count) */
+int dcn_index_set_coverage_keys(const dcn_index *set, uint32_t member, uint64_t *out, uint64_t capacity, uint64_t *n);
 
 /* ---- counters: ProcessingStats (src/local_filter.rs:179-187, merged at :388-396) -------------------------- */
 

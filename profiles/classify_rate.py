@@ -6,7 +6,11 @@ genome's minimizers + mix64 keys up to 409.9 M) and N - 1 members of 50 M keys (
 range of their own), so that host reads hit several members.  For N = 1, 2, 4, 8: the set's device memory and build time,
 then classify and the N filter passes timed alternately (wall clock around enqueue + synchronize, best and median of REPS),
 and one profiled classify call for the stage split (pack, plan, dump scan, lane kernel, workgroup kernel).
-usage: python profiles/classify_rate.py [reads]"""
+--coverage: for N = 1 and 8 only, classify with coverage off, then on (dcn_index_set_coverage_enable) right after a reset
+(every key the batch hits is seen first: test-loads and atomics) and again (every key already marked: test-loads only),
+timed alternately; the enable cost (bitmap + keys sweep), the read-out sweeps (coverage(), observed_keys()) and the stage
+split with coverage on.
+usage: python profiles/classify_rate.py [reads] [--coverage]"""
 import statistics
 import sys
 import time
@@ -19,7 +23,9 @@ import bench as B  # noqa: E402
 import deacon_server_amd as dcn  # noqa: E402
 
 REPS = 5
-reads = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
+COVERAGE = "--coverage" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a != "--coverage"]
+reads = int(args[0]) if args else 10_000_000
 dev = torch.device("cuda", 0)
 genome = B.make_host_genome(64_000_000, 3, dev)
 member0, keys0, host_keys, _, build0 = B.build_index(genome, B.PANHUMAN_KEYS, 0)
@@ -55,8 +61,54 @@ def filter_pass(n):
     return time.perf_counter() - t0
 
 
+def coverage_leg(n, s, clf, classify_pass):
+    """coverage off / on after a reset / on with every key marked, alternately; then the sweeps and the stage split"""
+    t_off, t_cold, t_warm, t_enable = [], [], [], []
+    for _ in range(REPS):
+        t_off.append(classify_pass())
+        t0 = time.perf_counter()
+        s.enable_coverage()
+        t_enable.append(time.perf_counter() - t0)
+        t_cold.append(classify_pass())
+        t_warm.append(classify_pass())
+        s.enable_coverage(False)
+    s.enable_coverage()
+    classify_pass()
+    t0 = time.perf_counter()
+    observed, keys = s.coverage()
+    t_cov = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    any_keys = s.observed_keys()
+    t_keys = time.perf_counter() - t0
+    clf.set_profiling(True)
+    s.reset_coverage()
+    classify_pass()
+    cold_stages, _ = clf.profile()
+    clf.set_profiling(False)
+    clf.set_profiling(True)
+    classify_pass()
+    warm_stages, _ = clf.profile()
+    clf.set_profiling(False)
+    s.enable_coverage(False)
+    med = lambda t: statistics.median(t) * 1e3  # noqa: E731
+    r = {"n": n, "off_ms_median": med(t_off), "cold_ms_median": med(t_cold), "warm_ms_median": med(t_warm),
+         "off_ms_best": min(t_off) * 1e3, "cold_ms_best": min(t_cold) * 1e3, "warm_ms_best": min(t_warm) * 1e3,
+         "enable_ms_median": med(t_enable), "coverage_sweep_ms": t_cov * 1e3, "observed_keys_ms": t_keys * 1e3,
+         "observed": observed.tolist(), "keys": keys.tolist(), "observed_any": len(any_keys),
+         "cold_stages_ms": {k: round(v, 3) for k, v in cold_stages.items()},
+         "warm_stages_ms": {k: round(v, 3) for k, v in warm_stages.items()}}
+    print(f"coverage N={n}: classify off {r['off_ms_median']:.2f} ms median ({r['off_ms_best']:.2f} best) | on, after reset "
+          f"{r['cold_ms_median']:.2f} ms ({r['cold_ms_best']:.2f}) = {r['cold_ms_median'] / r['off_ms_median']:.2f}x | on, "
+          f"keys marked {r['warm_ms_median']:.2f} ms ({r['warm_ms_best']:.2f}) = {r['warm_ms_median'] / r['off_ms_median']:.2f}x"
+          f" | enable {r['enable_ms_median']:.1f} ms | coverage() {r['coverage_sweep_ms']:.1f} ms | observed_keys() "
+          f"{r['observed_keys_ms']:.1f} ms for {r['observed_any']:,} keys | observed/keys per member "
+          f"{list(zip(r['observed'], r['keys']))} | stages (ms) after reset {r['cold_stages_ms']} | keys marked "
+          f"{r['warm_stages_ms']}", flush=True)
+    return r
+
+
 rows = []
-for n in (1, 2, 4, 8):
+for n in ((1, 8) if COVERAGE else (1, 2, 4, 8)):
     t0 = time.time()
     s = dcn.IndexSet(members[:n])
     set_build = time.time() - t0
@@ -98,6 +150,8 @@ for n in (1, 2, 4, 8):
     r["filter_n_mbps"] = n_bases / (r["filter_n_ms_median"] / 1e3) / 1e6
     r["speedup_vs_n_filters"] = r["filter_n_ms_median"] / r["classify_ms_median"]
     rows.append(r)
+    if COVERAGE:
+        r["coverage"] = coverage_leg(n, s, clf, classify_pass)
     print(f"N={n}: set {s.n_keys:,} keys, {r['set_gb']:.1f} GB (slots + masks), built in {set_build:.1f} s | classify "
           f"{r['classify_ms_median']:.2f} ms median ({r['classify_ms_best']:.2f} best) = {r['classify_mbps']:,.0f} Mbp/s | "
           f"{n} counting filter passes {r['filter_n_ms_median']:.2f} ms median ({r['filter_n_ms_best']:.2f} best) = "
@@ -111,3 +165,8 @@ for n in (1, 2, 4, 8):
 t1 = rows[0]["classify_ms_median"]
 print("summary: " + "; ".join(f"N={r['n']}: {r['classify_ms_median'] / t1:.2f}x the time of N=1, "
                               f"{r['speedup_vs_n_filters']:.2f}x faster than {r['n']} filter passes" for r in rows), flush=True)
+if COVERAGE:
+    print("coverage summary: " + "; ".join(
+        f"N={r['n']}: on/off {r['coverage']['cold_ms_median'] / r['coverage']['off_ms_median']:.2f}x after reset, "
+        f"{r['coverage']['warm_ms_median'] / r['coverage']['off_ms_median']:.2f}x with keys marked, sweep "
+        f"{r['coverage']['coverage_sweep_ms']:.1f} ms" for r in rows), flush=True)
