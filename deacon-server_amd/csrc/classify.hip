@@ -100,7 +100,7 @@ __global__ __launch_bounds__(DCN_CLS_LANES) void classify_units_kernel(dcn_class
     const uint32_t lane = threadIdx.x, u = blockIdx.x * DCN_CLS_LANES + lane;
     if (u >= a.n_units) return;
     const uint32_t n = a.n_members;
-    if (a.status->bad_offsets) { // tiles and read ranges are not looked at (api.hip reports DCN_ERR_ARG)
+    if (a.status->bad_offsets) { // tiles and read ranges are not looked at (ctx.hip reports DCN_ERR_ARG)
         if (u == 0) a.report->bad_offsets = 1;
         write_unit(a, u, 0, 0);
         if (a.hits)

@@ -1,0 +1,357 @@
+// classify_api.hip -- the C ABI of labelled index sets: creation, per-member coverage, and classification of a batch
+// against a set (the kernels are in classify.hip; the batch runs pack -> plan -> scan in dump mode on a filter context).
+#include "dcn_ctx.h"
+#include "dcn_classify.h"
+
+#include <cstring>
+
+using namespace dcn_impl;
+
+namespace {
+int check_set(const dcn_index *set) {
+    if (!set) return dcn_fail(DCN_ERR_ARG, "set is NULL");
+    if (set->n_members == 0 || !set->d_labels) return dcn_fail(DCN_ERR_ARG, "index is not a labelled set (dcn_index_set_create)");
+    return DCN_OK;
+}
+} // namespace
+
+extern "C" int dcn_index_set_create(const dcn_index *const *members, uint32_t n, dcn_index **out) {
+    if (!out) return dcn_fail(DCN_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (!members) return dcn_fail(DCN_ERR_ARG, "members is NULL");
+    if (n == 0 || n > DCN_MAX_SET_MEMBERS)
+        return dcn_fail(DCN_ERR_ARG, "an index set has 1 to 32 members, not " + std::to_string(n));
+    uint64_t sum = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!members[i]) return dcn_fail(DCN_ERR_ARG, "member index " + std::to_string(i) + " is NULL");
+        int rc = same_params(members[0], members[i]);
+        if (rc != DCN_OK) return rc;
+        sum += members[i]->n_keys; // worst case, as union sizes its table
+    }
+    dcn_index *set = new (std::nothrow) dcn_index();
+    if (!set) return dcn_fail(DCN_ERR_NOMEM, "host allocation failed");
+    set->device = members[0]->device;
+    set->variant = members[0]->variant;
+    set->k = members[0]->k;
+    set->w = members[0]->w;
+    int rc = dcn_table_alloc(set, std::max<uint64_t>(sum, 16));
+    if (rc == DCN_OK) {
+        const uint64_t n_slots = set->n_groups * DCN_GROUP_SLOTS;
+        hipError_t e = hipMalloc((void **)&set->d_labels, n_slots * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(set->d_labels, 0, n_slots * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e != hipSuccess)
+            rc = dcn_fail(e == hipErrorOutOfMemory ? DCN_ERR_NOMEM : DCN_ERR_HIP, std::string("index set labels: ") + hipGetErrorString(e));
+    }
+    set->n_members = n;
+    for (uint32_t i = 0; i < n && rc == DCN_OK; ++i) rc = dcn_set_add_member(set, members[i], i);
+    if (rc != DCN_OK) {
+        dcn_index_destroy(set);
+        return rc;
+    }
+    *out = set;
+    return DCN_OK;
+}
+
+extern "C" void dcn_index_set_destroy(dcn_index *set) { dcn_index_destroy(set); }
+
+extern "C" int dcn_index_set_info(const dcn_index *set, uint32_t *n_members, uint8_t *k, uint8_t *w, uint64_t *n_keys,
+                                  uint64_t *table_bytes) {
+    DCN_TRY(check_set(set));
+    if (n_members) *n_members = set->n_members;
+    if (k) *k = set->k;
+    if (w) *w = set->w;
+    if (n_keys) *n_keys = set->n_keys;
+    if (table_bytes) *table_bytes = set->n_groups * DCN_GROUP_SLOTS * (sizeof(uint64_t) + sizeof(uint32_t));
+    return DCN_OK;
+}
+
+// ---- coverage (classify.hip's COV kernels and sweeps) ---------------------------------------------------------------
+namespace {
+int check_coverage(const dcn_index *set) {
+    DCN_TRY(check_set(set));
+    if (!set->d_cov) return dcn_fail(DCN_ERR_ARG, "coverage is not enabled on this set (dcn_index_set_coverage_enable)");
+    return DCN_OK;
+}
+
+int hip_fail(hipError_t e, const char *what) {
+    return dcn_fail(e == hipErrorOutOfMemory ? DCN_ERR_NOMEM : DCN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// counts[0..n) of a coverage_count pass (all_slots: every occupied slot; else the marked ones), key 0 not included
+int coverage_counts(const dcn_index *set, bool all_slots, uint64_t *counts) {
+    unsigned long long *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, DCN_MAX_SET_MEMBERS * sizeof(unsigned long long));
+    if (e != hipSuccess) return hip_fail(e, "coverage");
+    int rc = DCN_OK;
+    e = hipMemset(d, 0, DCN_MAX_SET_MEMBERS * sizeof(unsigned long long));
+    if (e == hipSuccess) rc = dcn_coverage_count(set, all_slots, d, 0);
+    unsigned long long h[DCN_MAX_SET_MEMBERS] = {};
+    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
+    hipFree(d);
+    if (rc != DCN_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "coverage");
+    for (uint32_t j = 0; j < set->n_members; ++j) counts[j] = h[j];
+    return DCN_OK;
+}
+
+bool zero_observed(const dcn_index *set, int *rc) {
+    uint32_t w = 0;
+    const hipError_t e = hipMemcpy(&w, set->d_cov + set->cov_words, sizeof(w), hipMemcpyDeviceToHost);
+    *rc = e == hipSuccess ? DCN_OK : hip_fail(e, "coverage");
+    return (w & 1u) != 0;
+}
+} // namespace
+
+extern "C" int dcn_index_set_coverage_enable(dcn_index *set, int enable) {
+    DCN_TRY(check_set(set));
+    DCN_HIP(hipSetDevice(set->device));
+    if (!enable) {
+        if (set->d_cov) hipFree(set->d_cov);
+        set->d_cov = nullptr;
+        set->cov_words = 0;
+        return DCN_OK;
+    }
+    if (set->d_cov) return DCN_OK; // already on: the marks stay
+    const uint64_t words = (set->n_groups * DCN_GROUP_SLOTS + 31) / 32;
+    uint32_t *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, (words + 1) * sizeof(uint32_t));
+    if (e != hipSuccess) return hip_fail(e, "coverage bitmap");
+    e = hipMemset(d, 0, (words + 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        hipFree(d);
+        return hip_fail(e, "coverage bitmap");
+    }
+    set->d_cov = d;
+    set->cov_words = words;
+    uint64_t keys[DCN_MAX_SET_MEMBERS] = {};
+    int rc = coverage_counts(set, true, keys);
+    if (rc != DCN_OK) {
+        dcn_index_set_coverage_enable(set, 0);
+        return rc;
+    }
+    for (uint32_t j = 0; j < set->n_members; ++j)
+        set->cov_keys[j] = keys[j] + (set->has_zero && ((set->zero_label >> j) & 1u) ? 1 : 0);
+    return DCN_OK;
+}
+
+extern "C" int dcn_index_set_coverage_reset(dcn_index *set) {
+    DCN_TRY(check_coverage(set));
+    DCN_HIP(hipSetDevice(set->device));
+    DCN_HIP(hipMemset(set->d_cov, 0, (set->cov_words + 1) * sizeof(uint32_t)));
+    DCN_HIP(hipDeviceSynchronize());
+    return DCN_OK;
+}
+
+extern "C" int dcn_index_set_coverage(const dcn_index *set, uint64_t *observed, uint64_t *keys) {
+    DCN_TRY(check_coverage(set));
+    if (!observed || !keys) return dcn_fail(DCN_ERR_ARG, "observed/keys is NULL");
+    DCN_HIP(hipSetDevice(set->device));
+    uint64_t obs[DCN_MAX_SET_MEMBERS] = {};
+    DCN_TRY(coverage_counts(set, false, obs));
+    int rc = DCN_OK;
+    const bool zero = zero_observed(set, &rc);
+    DCN_TRY(rc);
+    for (uint32_t j = 0; j < set->n_members; ++j) {
+        observed[j] = obs[j] + (zero && ((set->zero_label >> j) & 1u) ? 1 : 0);
+        keys[j] = set->cov_keys[j];
+    }
+    return DCN_OK;
+}
+
+extern "C" int dcn_index_set_coverage_keys(const dcn_index *set, uint32_t member, uint64_t *out, uint64_t capacity,
+                                           uint64_t *n) {
+    DCN_TRY(check_coverage(set));
+    if (!n) return dcn_fail(DCN_ERR_ARG, "n is NULL");
+    *n = 0;
+    if (member != UINT32_MAX && member >= set->n_members)
+        return dcn_fail(DCN_ERR_ARG, "member " + std::to_string(member) + " out of range: the set has " +
+                                         std::to_string(set->n_members) + " members");
+    if (!out && capacity > 0) return dcn_fail(DCN_ERR_ARG, "out is NULL");
+    const uint32_t mask = member == UINT32_MAX ? ~0u : 1u << member;
+    DCN_HIP(hipSetDevice(set->device));
+    int rc = DCN_OK;
+    const bool zero = zero_observed(set, &rc) && (set->zero_label & mask);
+    DCN_TRY(rc);
+    unsigned long long *d_n = nullptr;
+    uint64_t *d_out = nullptr;
+    hipError_t e = hipMalloc((void **)&d_n, sizeof(unsigned long long));
+    unsigned long long count = 0;
+    if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) rc = dcn_coverage_count_mask(set, mask, d_n, 0);
+    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(&count, d_n, sizeof(count), hipMemcpyDeviceToHost);
+    const uint64_t total = count + (zero ? 1 : 0);
+    if (e == hipSuccess && rc == DCN_OK && total <= capacity && count > 0) {
+        e = hipMalloc((void **)&d_out, count * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof(unsigned long long));
+        if (e == hipSuccess) rc = dcn_coverage_collect(set, mask, d_out, count, d_n, 0);
+        unsigned long long written = 0;
+        if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(&written, d_n, sizeof(written), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && rc == DCN_OK && written != count)
+            rc = dcn_fail(DCN_ERR_INTERNAL, "coverage keys: the bitmap changed between the count and the copy (a classify call in flight?)");
+        if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(out, d_out, count * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    }
+    if (d_out) hipFree(d_out);
+    hipFree(d_n);
+    if (rc != DCN_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "coverage keys");
+    *n = total;
+    if (total > capacity)
+        return dcn_fail(DCN_ERR_CAPACITY, "coverage keys: " + std::to_string(total) + " observed keys, capacity " +
+                                              std::to_string(capacity));
+    if (zero) out[count] = 0;
+    return DCN_OK;
+}
+
+namespace {
+int classify_check(dcn_ctx *ctx, const dcn_index *set, const dcn_params *params) {
+    if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
+    DCN_TRY(check_set(set));
+    DCN_TRY(check_params(params));
+    const dcn_index *ix = ctx->index;
+    if (ix->k != set->k || ix->w != set->w)
+        return dcn_fail(DCN_ERR_ARG, "the context's index (k=" + std::to_string((int)ix->k) + ", w=" + std::to_string((int)ix->w) +
+                                         ") and the set (k=" + std::to_string((int)set->k) + ", w=" + std::to_string((int)set->w) +
+                                         ") differ");
+    if (ix->device != set->device) return dcn_fail(DCN_ERR_ARG, "the context and the set live on different devices");
+    if (ix->variant != set->variant)
+        return dcn_fail(DCN_ERR_ARG, "the context's index and the set were created under different minimizer rules");
+    return check_idle(ctx);
+}
+
+// the lazily allocated buffers of classification: the dump arrays, the work list and (host form) the outputs
+int classify_buffers(dcn_ctx *c, uint32_t n_members, bool host_outputs) {
+    DCN_TRY(ensure_dump_buffers(c));
+    if (!c->d_cls_big) {
+        DCN_TRY(dev_alloc(&c->d_cls_big, c->max_reads, "classify work list"));
+        DCN_TRY(dev_alloc(&c->d_cls_n_big, 1, "classify work list length"));
+    }
+    if (host_outputs) {
+        if (!c->d_cls_match) {
+            DCN_TRY(dev_alloc(&c->d_cls_match, c->max_reads, "classify match"));
+            DCN_TRY(dev_alloc(&c->d_cls_total, c->max_reads, "classify total"));
+        }
+        if (c->cls_hits_members < n_members) {
+            if (c->d_cls_hits) hipFree(c->d_cls_hits);
+            c->d_cls_hits = nullptr;
+            c->cls_hits_members = 0;
+            DCN_TRY(dev_alloc(&c->d_cls_hits, (uint64_t)c->max_reads * n_members, "classify hits"));
+            c->cls_hits_members = n_members;
+        }
+    }
+    return DCN_OK;
+}
+
+// pack -> plan -> scan (minimizer dump) -> classification kernels, on the context's stream; the batch's inputs are
+// device pointers (the host form has staged them into the context's buffers).  Leaves the six counters alone.
+int classify_enqueue(dcn_ctx *c, const dcn_index *set, const uint8_t *d_ascii, const uint64_t *d_offsets,
+                     const uint32_t *d_unit_id, uint32_t n_reads, uint64_t n_bases, uint32_t n_units,
+                     const dcn_params *params, uint32_t *d_match, uint32_t *d_hits, uint32_t *d_total) {
+    hipStream_t st = c->stream;
+    DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
+    DCN_HIP(hipMemsetAsync(c->d_cls_n_big, 0, sizeof(uint32_t), st));
+    int prof_slot = -1;
+    DCN_TRY(prof_begin(c, &prof_slot));
+    DCN_TRY(dcn_launch_pack(d_ascii, 0, n_bases, c->d_packed + DCN_FRONT_PAD, c->d_invmask + DCN_FRONT_PAD, c->d_status, st));
+    DCN_PROF_MARK(DCN_STAGE_PACK);
+    dcn_plan_args pa = plan_args(c, set, d_ascii, d_offsets, d_unit_id, n_reads, n_units, params->prefix_length);
+    pa.read_tiles = c->d_read_tiles;
+    pa.read_tile_first = c->d_read_tile_first;
+    pa.stream_bases = n_bases; // the device form's offsets have not been seen by the host: the plan kernel checks them
+    pa.check_offsets = 1;
+    pa.max_tiles = c->max_tiles;
+    DCN_TRY(dcn_launch_plan(pa, st));
+    DCN_PROF_MARK(DCN_STAGE_PLAN);
+    dcn_scan_args sa = dump_scan_args(c, set, n_bases);
+    sa.dump_abs = 1; // (positions are not looked at)
+    DCN_TRY(dcn_launch_scan(sa, tile_bound(c, n_reads, n_bases), true, st));
+    DCN_PROF_MARK(DCN_STAGE_SCAN);
+    dcn_classify_args ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.table = set->view();
+    ca.labels = set->d_labels;
+    ca.zero_label = set->zero_label;
+    ca.n_members = set->n_members;
+    ca.tiles = c->d_tiles;
+    ca.n_tiles = &c->d_status->n_tiles;
+    ca.offsets = d_offsets;
+    ca.read_tiles = c->d_read_tiles;
+    ca.read_tile_first = c->d_read_tile_first;
+    ca.unit_first_read = d_unit_id ? c->d_unit_first_read : nullptr;
+    ca.dump_hash = c->d_dump_hash;
+    ca.dump_valid = c->d_dump_valid;
+    ca.dump_count = c->d_dump_count;
+    ca.tile_windows = c->tile_windows;
+    ca.n_units = n_units;
+    ca.abs_threshold = params->abs_threshold;
+    ca.rel_threshold = params->rel_threshold;
+    ca.match = d_match;
+    ca.hits = d_hits;
+    ca.total = d_total;
+    ca.big = c->d_cls_big;
+    ca.n_big = c->d_cls_n_big;
+    ca.status = c->d_status;
+    ca.report = c->d_report;
+    ca.cov_bits = set->d_cov; // null: the kernels without coverage
+    ca.cov_zero = set->d_cov ? set->d_cov + set->cov_words : nullptr;
+    DCN_TRY(dcn_launch_classify_units(ca, st));
+    DCN_PROF_MARK(DCN_STAGE_DISTINCT);
+    DCN_TRY(dcn_launch_classify_big(ca, st));
+    DCN_PROF_MARK(DCN_STAGE_FINISH);
+    if (prof_slot >= 0) c->prof_used[prof_slot] = true;
+    // a later device-pointer filter batch packs one batch ahead into these packed buffers on its own stream, after the
+    // events below: they now stand after this run
+    if (c->pack_ahead_state == 1) {
+        DCN_HIP(hipEventRecord(c->plan_done, st));
+        for (int i = 0; i < 2; ++i) DCN_HIP(hipEventRecord(c->buf_free[i], st));
+    }
+    c->batch_pending = true; // dcn_ctx_synchronize reports what the plan kernel found wrong with the batch
+    return DCN_OK;
+}
+} // namespace
+
+extern "C" int dcn_classify_batch(dcn_ctx *ctx, const dcn_index *set, const uint8_t *bases, const uint64_t *offsets,
+                                  const uint32_t *unit_id, uint32_t n_reads, const dcn_params *params, uint32_t *match,
+                                  uint32_t *hits, uint32_t *total) {
+    DCN_TRY(classify_check(ctx, set, params));
+    if (n_reads == 0) return DCN_OK;
+    if (!offsets || !match) return dcn_fail(DCN_ERR_ARG, "offsets/match is NULL");
+    DCN_TRY(validate_host_batch(ctx, offsets, n_reads));
+    uint32_t n_units = n_reads;
+    if (unit_id) {
+        if (unit_id[0] != 0) return dcn_fail(DCN_ERR_ARG, "unit_id[0] must be 0");
+        for (uint32_t r = 1; r < n_reads; ++r)
+            if (unit_id[r] != unit_id[r - 1] && unit_id[r] != unit_id[r - 1] + 1)
+                return dcn_fail(DCN_ERR_ARG, "unit_id must be non-decreasing in steps of 0 or 1");
+        n_units = unit_id[n_reads - 1] + 1;
+    }
+    const uint64_t n_bases = offsets[n_reads];
+    if (n_bases > 0 && !bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
+    dcn_ctx *c = ctx;
+    DCN_HIP(hipSetDevice(c->device));
+    DCN_TRY(classify_buffers(c, set->n_members, true));
+    DCN_TRY(stage_batch(c, bases, n_bases, offsets, n_reads, unit_id));
+    DCN_TRY(classify_enqueue(c, set, c->d_ascii, c->d_offsets, unit_id ? c->d_unit_id : nullptr, n_reads, n_bases, n_units,
+                             params, c->d_cls_match, c->d_cls_hits, c->d_cls_total));
+    DCN_TRY(sync_and_check(c, nullptr));
+    DCN_HIP(hipMemcpy(match, c->d_cls_match, (uint64_t)n_units * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (hits)
+        DCN_HIP(hipMemcpy(hits, c->d_cls_hits, (uint64_t)n_units * set->n_members * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (total) DCN_HIP(hipMemcpy(total, c->d_cls_total, (uint64_t)n_units * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return DCN_OK;
+}
+
+extern "C" int dcn_classify_batch_device(dcn_ctx *ctx, const dcn_index *set, const uint8_t *d_bases,
+                                         const uint64_t *d_offsets, const uint32_t *d_unit_id, uint32_t n_reads,
+                                         uint64_t n_bases, uint32_t n_units, const dcn_params *params, uint32_t *d_match,
+                                         uint32_t *d_hits, uint32_t *d_total) {
+    DCN_TRY(classify_check(ctx, set, params));
+    if (n_reads == 0) return DCN_OK;
+    if (!d_bases || !d_offsets || !d_match) return dcn_fail(DCN_ERR_ARG, "d_bases/d_offsets/d_match is NULL");
+    DCN_TRY(check_device_batch(ctx, n_reads, n_bases, n_units, d_unit_id));
+    DCN_HIP(hipSetDevice(ctx->device));
+    DCN_TRY(classify_buffers(ctx, set->n_members, false));
+    return classify_enqueue(ctx, set, d_bases, d_offsets, d_unit_id, n_reads, n_bases, n_units, params, d_match, d_hits,
+                            d_total);
+}

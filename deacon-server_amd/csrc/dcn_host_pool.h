@@ -1,5 +1,5 @@
 // The library's host-side thread pool (plain C++: no HIP in here, so tests/cpp/host_pool_test.cpp can put it under
-// ThreadSanitizer on the CPU).  Included by api.hip only.
+// ThreadSanitizer on the CPU).  Included by api.hip, ctx.hip and host_batch.hip.
 #pragma once
 #include <algorithm>
 #include <atomic>

@@ -198,7 +198,7 @@ struct dcn_scan_args {
     uint32_t nt_combine_xor; // 0: fw + rc, 1: fw ^ rc
 };
 
-// ---- kernels launched by api.hip -------------------------------------------------------------------
+// ---- kernels launched by ctx.hip, dump.hip and classify_api.hip ------------------------------------
 // packs bases [base_begin, base_end) of the stream (whole 32-base groups; bytes at or past base_end read as 'A');
 // status (may be null) receives any_newline
 int dcn_launch_pack(const uint8_t *d_ascii, uint64_t base_begin, uint64_t base_end, uint32_t *d_packed,

@@ -29,7 +29,7 @@ struct dcn_plan_args {
     uint32_t check_offsets;     // 1: a read whose offsets are decreasing or beyond the stream is planned as empty and reported
                                 // (status->bad_offsets) instead of being followed outside the batch's buffers
     const uint32_t *newline_flag; // null: status->any_newline; else the word the pack kernel of this batch wrote (it may have
-                                  // run ahead of the batch's own status words: api.hip, pack one batch ahead)
+                                  // run ahead of the batch's own status words: ctx.hip, pack one batch ahead)
 };
 
 struct dcn_distinct_args {

@@ -110,7 +110,7 @@ bool have_avx512() {
 } // namespace
 
 // whether this host packs with the AVX-512 form (about 1.7 x the AVX2 + pext form's rate on a whole socket share): the host
-// entry points then pack page-locked ASCII on the host too instead of sending it as it is (api.hip)
+// entry points then pack page-locked ASCII on the host too instead of sending it as it is (host_batch.hip)
 bool dcn_host_pack_is_wide() { return have_avx2() && have_avx512(); }
 
 // Packs the 32-base groups [g0, g1) of the stream `ascii` (n_bases bytes; bytes at or past n_bases count as 'A',

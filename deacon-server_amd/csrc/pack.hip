@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ a
 }
 
 
-// The same for a batch that is packed BESIDE another kernel's waves (api.hip packs batch i+1 while the scan kernel of batch i
+// The same for a batch that is packed BESIDE another kernel's waves (ctx.hip packs batch i+1 while the scan kernel of batch i
 // runs): the scan kernel holds 4 waves x 120 VGPRs of a SIMD's 512, so only a wave of <= 32 VGPRs fits next to them.  Each
 // thread packs 16 bases (one uint4 in, one packed word and half a mask word out), one-wave workgroups, whole 16-base pieces
 // of a 16-byte-aligned stream only (dcn_launch_pack_beside leaves the rest to the general kernel).
@@ -158,7 +158,7 @@ int dcn_launch_pack(const uint8_t *d_ascii, uint64_t base_begin, uint64_t base_e
     const uint64_t g_first = base_begin / 32, n_bases = base_end;
     uint64_t n_chunks = (base_end + 31) / 32 - g_first;
     // block_threads = 64: one-wave workgroups, which fit into any single wave slot another kernel's waves leave behind
-    // (api.hip packs the next batch beside the running scan kernel); 256 otherwise
+    // (ctx.hip packs the next batch beside the running scan kernel); 256 otherwise
     const uint32_t bt = block_threads == 64 ? 64u : 256u;
     uint32_t blocks = (uint32_t)((n_chunks + bt - 1) / bt);
     if (blocks > 256 * 32 * (256 / bt)) blocks = 256 * 32 * (256 / bt);

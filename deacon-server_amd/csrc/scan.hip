@@ -177,7 +177,7 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
     extern __shared__ __align__(16) uint2 dyn_ring[]; // only for W == 0: [w][64] (lkey, rkey); VAR: [w][64] of two u64 keys
 
     const int lane = threadIdx.x;
-    // (bad_offsets: the plan kernel refused the batch's offsets -- api.hip reports it at the next synchronize; its tiles are not looked at)
+    // (bad_offsets: the plan kernel refused the batch's offsets -- ctx.hip reports it at the next synchronize; its tiles are not looked at)
     const uint32_t NT = a.status->bad_offsets ? 0u : *a.n_tiles;
     const uint32_t wave_first = blockIdx.x * DCN_WAVE;
     if (wave_first >= NT) return;
@@ -239,7 +239,7 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
         // A unit's run of the record array starts at the slot of its first window in this wave and may grow up to the slot of
         // its last: with one slot per 2^rec_shift windows it holds that many times fewer hits than the unit has windows
         // here, which real sequence never fills (one minimizer per ~8 windows) -- a run that would is refused and the
-        // batch comes back with one slot per window (api.hip).
+        // batch comes back with one slot per window (ctx.hip).
         // (a read's last tile -- the only kind that can be a few windows short of a slot -- also owns the l-1 positions
         // behind its last window, where no window of this read or of the next one starts)
         const uint32_t head_lane = 63u - (uint32_t)__clzll(head_mask & ((2ull << lane) - 1));
@@ -570,7 +570,7 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
                 // the unit's first tile in this wave and holds sh.ucap entries, one per 2^rec_shift windows of the unit's
                 // tiles here: it cannot reach another run, and with rec_shift > 0 it CAN fill up (homopolymers and short-
                 // period repeats give a hit every window or two) -- then status->run_overflow is raised and the host runs
-                // the batch again with one slot per window (api.hip, grow_run_slots).  Hits fill it from the front in item order.  No global
+                // the batch again with one slot per window (ctx.hip, grow_run_slots).  Hits fill it from the front in item order.  No global
                 // atomics: the running length lives in LDS, and since items are in flat order the hits of one unit
                 // sit in adjacent lanes of a round.  plan.hip's distinct pass reads the runs back (coalesced).
                 // A zero hash (0 marks an empty set slot there) is flagged per unit instead of counted there.

@@ -1,4 +1,4 @@
-"""The seams of classification (classify.hip, api.hip's classify entry points, `deacon-hip classify`) that random reads
+"""The seams of classification (classify.hip, classify_api.hip's entry points, `deacon-hip classify`) that random reads
 do not reach: the lane kernel's entry and hit limits at their exact edges, the workgroup kernel's fill-limit retry, member
 labels in displaced slots of a crowded set, every minimizer rule, one context through many different calls, a set used as
 a plain index, and the command line over many batches.  Every comparison is exact.

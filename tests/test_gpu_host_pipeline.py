@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(autouse=True, params=["lean", "three-streams"])
 def submission_form(request, monkeypatch):
     """every test of this file twice: batches of up to 16 Mbp that fit one chunk are submitted on ONE stream in their plain
-    form (64-bit offsets, whole mask words; api.hip submit_impl, `lean`), larger or chunked ones with copies, kernels and result
+    form (64-bit offsets, whole mask words; host_batch.hip submit_impl, `lean`), larger or chunked ones with copies, kernels and result
     copies on three streams; DCN_LEAN_MAX_BASES=0 sends everything the second way, so that narrow offsets, the sparse mask and
     the events between the streams are tested at test sizes too"""
     if request.param == "three-streams":
@@ -527,7 +527,7 @@ def test_contexts_on_several_threads_pack_side_by_side(oracle, dcn, genome, inde
 
 def test_device_pointer_batches_queued_back_to_back(oracle, dcn, genome, index_pair, monkeypatch):
     """Round 4: on the device-pointer API the pack kernel of batch i+1 can run on a side stream, into a second packed buffer,
-    while the kernels of batch i run (csrc/api.hip, ensure_pack_ahead; DCN_PACK_AHEAD=1 -- off by default, it bought nothing).  Nine batches of three different shapes -- sizes that
+    while the kernels of batch i run (csrc/ctx.hip, ensure_pack_ahead; DCN_PACK_AHEAD=1 -- off by default, it bought nothing).  Nine batches of three different shapes -- sizes that
     differ by 4 x, reads with N and trailing newlines (the pack kernel's newline flag travels with its buffer), pairs -- are
     queued without a synchronize in between, each with result arrays of its own; every one must give the oracle's
     results.  Then the same in the default order (packed in line), and with per-stage profiling on (which packs in line too)."""
