@@ -42,6 +42,16 @@ class Params(C.Structure):
     ]
 
 
+class LocateParams(C.Structure):
+    _fields_ = [
+        ("max_gap", C.c_uint32),
+        ("min_hits", C.c_uint32),
+        ("member_mask", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("prefix_length", C.c_uint64),
+    ]
+
+
 def build(force=False, jobs=6):
     """Compile every HIP source for gfx950 into lib/libdeacon_hip.so (hipcc cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -123,10 +133,11 @@ _SIGNATURES = {
     "dcn_index_set_coverage_reset": (C.c_int, [_vp]),
     "dcn_index_set_coverage": (C.c_int, [_vp, _vp, _vp]),
     "dcn_index_set_coverage_keys": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, _u64p]),
+    "dcn_locate_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64]),
 }
 
 _lib = None
-ABI = (1, 3)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 4)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

@@ -7,6 +7,7 @@
 //   deacon-hip index diff  <first.idx> <second.idx | fastx> [-k K -w W] [-o out.idx]
 //   deacon-hip filter <index> [input|-] [input2|-] [-o out] [-O out2] [-a 2] [-r 0.01] [-p 0] [-d] [-R]
 //                     [-s summary.json] [-t threads] [--compression-level 2] [--debug] [-q]
+//   deacon-hip mask -x <index> [-x <index>...] [input|-] [-o masked.fastq] [--bed hits.bed] [--soft] [-g N] [-a 2] [-p 0] [-s summary.json]
 //   deacon-hip classify -x <index> [-x <index>...] [input|-] [input2] [-a 2] [-r 0.01] [-p 0] [--per-read out.tsv|-]
 //                       [--coverage]
 //                     [-s summary.json] [-q]
@@ -3119,11 +3120,197 @@ int run_classify(const ClassifyArgs &a) {
     return 0;
 }
 
+// `deacon-hip mask`: where in each record the index (or which of several indexes) matched, by the same minimizer hits the
+// filter counts (dcn_locate_batch; the definition of a segment is in include/deacon_hip.h), and the records with those
+// stretches replaced by N or lower-cased.  No reference counterpart.  Mates are independent here: one input.
+struct MaskArgs {
+    std::vector<std::string> indexes;
+    std::string input = "-", output, bed, summary;
+    bool has_input = false, has_output = false, has_bed = false, has_summary = false, quiet = false, soft = false;
+    long max_gap = -1;  // -1: 2*w - 1
+    unsigned min_hits = 2;
+    size_t prefix_length = 0;
+};
+
+int run_mask(const MaskArgs &a) {
+    const auto start = std::chrono::steady_clock::now();
+    if (a.indexes.empty()) die("the following required arguments were not provided: -x <INDEX>");
+    if (a.indexes.size() > 32) die("mask takes at most 32 indexes");
+    if (!a.has_output && !a.has_bed && !a.has_summary) die("nothing to write: give at least one of -o <OUTPUT>, --bed <BED>, -s <SUMMARY>");
+    const uint32_t n = (uint32_t)a.indexes.size();
+    std::vector<RawIndex> members(n);
+    std::vector<const dcn_index *> mp(n);
+    uint8_t k = 0, w = 0;
+    for (uint32_t j = 0; j < n; ++j) {
+        deacon::check(dcn_index_from_file(a.indexes[j].c_str(), 0, &members[j].p));
+        mp[j] = members[j].p;
+    }
+    deacon::check(dcn_index_header(members[0].p, &k, &w, nullptr));
+    // one index is probed as it is (every label is 1); several become a labelled set, as classify builds it
+    RawIndex set;
+    if (n > 1) {
+        deacon::check(dcn_index_set_create(mp.data(), n, &set.p));
+        for (auto &m : members) {
+            dcn_index_destroy(m.p);
+            m.p = nullptr;
+        }
+    }
+    const dcn_index *target = n > 1 ? set.p : members[0].p;
+    uint64_t batch_bases = 32ull << 20, max_bases = 64ull << 20;
+    if (const char *e = std::getenv("DCN_CLI_LOCATE_BATCH_BASES")) { // test hook: many batches, records past the context
+        batch_bases = (uint64_t)std::max(64, std::atoi(e));
+        max_bases = 2 * batch_bases;
+    }
+    const uint32_t max_reads = 1u << 20;
+    dcn_ctx *ctx = nullptr;
+    deacon::check(dcn_ctx_create(target, max_bases, max_reads, &ctx));
+    struct CtxGuard {
+        dcn_ctx **c;
+        ~CtxGuard() {
+            if (*c) dcn_ctx_destroy(*c);
+        }
+    } guard{&ctx};
+    dcn_locate_params prm = {};
+    prm.max_gap = a.max_gap < 0 ? 2u * w - 1u : (uint32_t)a.max_gap;
+    prm.min_hits = a.min_hits;
+    prm.member_mask = 0xFFFFFFFFu;
+    prm.prefix_length = a.prefix_length;
+
+    std::vector<std::string> stems(n);
+    for (uint32_t j = 0; j < n; ++j) stems[j] = index_stem(a.indexes[j]);
+    std::unique_ptr<Output> out;
+    if (a.has_output) out.reset(new Output(a.output, 2));
+    FILE *bed = nullptr;
+    if (a.has_bed) {
+        bed = a.bed == "-" ? stdout : std::fopen(a.bed.c_str(), "w");
+        if (!bed) die("cannot open " + a.bed + " for writing");
+    }
+    FastxReader rd(a.input);
+    uint64_t reads_in = 0, bases_in = 0, reads_hit = 0, n_segments = 0, masked = 0;
+    std::vector<uint64_t> seg_m(n, 0), bp_m(n, 0);
+    Batch b;
+    std::vector<uint64_t> seg_off;
+    std::vector<dcn_segment> segs(1u << 16);
+    std::vector<char> text;
+    std::string rows;
+    auto run_batch = [&]() {
+        const uint32_t n_reads = (uint32_t)b.recs.size();
+        if (n_reads == 0) return;
+        const uint64_t nb = b.offsets.back();
+        if (nb > max_bases) { // a record longer than the context's batch: a context of its size
+            dcn_ctx_destroy(ctx);
+            ctx = nullptr;
+            max_bases = nb;
+            deacon::check(dcn_ctx_create(target, max_bases, max_reads, &ctx));
+        }
+        seg_off.assign((size_t)n_reads + 1, 0);
+        int rc = dcn_locate_batch(ctx, target, b.bases.data(), b.offsets.data(), n_reads, &prm, seg_off.data(), segs.data(), segs.size());
+        if (rc == DCN_ERR_CAPACITY && seg_off[n_reads] > segs.size()) { // the count came back: once more with room for it
+            segs.resize(seg_off[n_reads]);
+            rc = dcn_locate_batch(ctx, target, b.bases.data(), b.offsets.data(), n_reads, &prm, seg_off.data(), segs.data(), segs.size());
+        }
+        deacon::check(rc);
+        text.clear();
+        rows.clear();
+        for (uint32_t r = 0; r < n_reads; ++r) {
+            const Rec &rec = b.recs[r];
+            const char *id = b.chars() + rec.id_off;
+            const uint64_t s0 = seg_off[r], s1 = seg_off[r + 1];
+            ++reads_in;
+            bases_in += rec.seq_len;
+            reads_hit += s1 > s0;
+            n_segments += s1 - s0;
+            size_t id_len = 0;
+            while (id_len < rec.id_len && id[id_len] != ' ' && id[id_len] != '\t') ++id_len;
+            size_t seq_at = 0;
+            if (out) {
+                text.push_back(rec.qual_off == NO_QUAL ? '>' : '@');
+                text.insert(text.end(), id, id + rec.id_len);
+                text.push_back('\n');
+                seq_at = text.size();
+                const char *seq = b.seq_ptr(rec);
+                text.insert(text.end(), seq, seq + rec.seq_len);
+                text.push_back('\n');
+                if (rec.qual_off != NO_QUAL) {
+                    text.push_back('+');
+                    text.push_back('\n');
+                    text.insert(text.end(), b.chars() + rec.qual_off, b.chars() + rec.qual_off + rec.seq_len);
+                    text.push_back('\n');
+                }
+            }
+            for (uint64_t q = s0; q < s1; ++q) {
+                const dcn_segment &sg = segs[q];
+                const uint32_t end = std::min(sg.end, rec.seq_len);
+                masked += end - sg.start;
+                for (uint32_t j = 0; j < n; ++j)
+                    if (sg.members >> j & 1u) seg_m[j] += 1, bp_m[j] += end - sg.start;
+                if (out)
+                    for (uint32_t i = sg.start; i < end; ++i) {
+                        char &c = text[seq_at + i];
+                        c = a.soft ? (char)std::tolower((unsigned char)c) : 'N';
+                    }
+                if (bed) {
+                    rows.append(id, id_len);
+                    rows += '\t' + std::to_string(sg.start) + '\t' + std::to_string(end) + '\t' + std::to_string(sg.n_hits) + '\t';
+                    bool any = false;
+                    for (uint32_t j = 0; j < n; ++j)
+                        if (sg.members >> j & 1u) {
+                            if (any) rows += ',';
+                            rows += stems[j];
+                            any = true;
+                        }
+                    rows += '\n';
+                }
+            }
+        }
+        if (out) out->write(text);
+        if (bed) std::fwrite(rows.data(), 1, rows.size(), bed);
+        b.clear();
+    };
+    const uint32_t batch_reads = max_reads - 2;
+    while (rd.next(b))
+        if (b.offsets.back() >= batch_bases || b.recs.size() >= batch_reads) run_batch();
+    run_batch();
+    if (out) out->close();
+    if (bed && bed != stdout) std::fclose(bed);
+    else if (bed) std::fflush(bed);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+    if (!a.quiet)
+        std::fprintf(stderr, "Masked %llu bp in %llu segments of %llu/%llu sequences (%llu bp) in %s\n", (unsigned long long)masked,
+                     (unsigned long long)n_segments, (unsigned long long)reads_hit, (unsigned long long)reads_in,
+                     (unsigned long long)bases_in, fmt_duration(secs).c_str());
+    if (a.has_summary) {
+        std::string js = "{\n  \"version\": " + json_str(std::string("deacon-hip ") + VERSION) + ",\n  \"input\": " + json_str(a.input);
+        char buf[512];
+        std::snprintf(buf, sizeof buf, ",\n  \"k\": %u,\n  \"w\": %u,\n  \"max_gap\": %u,\n  \"min_hits\": %u,\n  \"prefix_length\": %zu,\n"
+                                       "  \"soft\": %s,\n  \"reads\": %llu,\n  \"bases\": %llu,\n  \"reads_with_segments\": %llu,\n"
+                                       "  \"segments\": %llu,\n  \"masked_bases\": %llu,\n  \"time\": %.17g,\n  \"indexes\": [",
+                      (unsigned)k, (unsigned)w, prm.max_gap, prm.min_hits, a.prefix_length, a.soft ? "true" : "false",
+                      (unsigned long long)reads_in, (unsigned long long)bases_in, (unsigned long long)reads_hit,
+                      (unsigned long long)n_segments, (unsigned long long)masked, secs);
+        js += buf;
+        for (uint32_t j = 0; j < n; ++j) {
+            js += (j ? ",\n    {" : "\n    {");
+            js += "\"path\": " + json_str(a.indexes[j]) + ", \"name\": " + json_str(stems[j]);
+            std::snprintf(buf, sizeof buf, ", \"segments\": %llu, \"masked_bases\": %llu}", (unsigned long long)seg_m[j],
+                          (unsigned long long)bp_m[j]);
+            js += buf;
+        }
+        js += "\n  ]\n}\n";
+        FILE *f = std::fopen(a.summary.c_str(), "w");
+        if (!f) die("cannot open " + a.summary + " for writing");
+        std::fwrite(js.data(), 1, js.size(), f);
+        std::fclose(f);
+    }
+    return 0;
+}
+
 void usage() {
     std::fprintf(stderr,
                  "Usage: deacon-hip <COMMAND>\n\nCommands:\n  index   Build and compose minimizer indexes (build, info, union, diff)\n"
                  "  filter  Keep or discard DNA fastx records with sufficient minimizer hits to an index\n"
                  "  classify  Report which of several indexes each record (or pair) matches, in one pass\n"
+                 "  mask    Report where in each record an index matched, and mask those stretches\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -3204,6 +3391,24 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
                "  -q, --quiet                    Suppress progress reporting\n"
                "  -h, --help                     Print help\n";
+    else if (sub == "mask")
+        text = "Report where in each record an index (or which of several) matched, and replace those stretches by N\n\n"
+               "Usage: deacon-hip mask -x <INDEX> [-x <INDEX>...] [OPTIONS] [INPUT]\n\n"
+               "Arguments:\n"
+               "  [INPUT]   Optional path to fastx file (or - for stdin; gz, bgzf, zst, xz and bz2 found by content) [default: -]\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Path to a minimizer index file; repeat for up to 32 indexes (same k and w)\n"
+               "  -o, --output <OUTPUT>          Every record, in input order, its matched stretches masked (- for stdout; .gz, .zst and .xz by extension)\n"
+               "      --bed <BED>                One line per matched stretch: id, start, end (0-based, half-open), hits, index names\n"
+               "      --soft                     Lower-case the matched stretches instead of replacing them by N\n"
+               "  -g, --max-gap <N>              Join hits whose k-mers are at most N bases apart [default: 2*w - 1]\n"
+               "  -a, --min-hits <N>             Minimum number of minimizer hits in a stretch [default: 2]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per sequence (0 = entire sequence) [default: 0]\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
+               "  -h, --help                     Print help\n\n"
+               "At least one of -o, --bed and -s is required.  Mates are independent here: one input.\n";
     else if (sub == "index build")
         text = "Index minimizers contained within a fastx file\n\n"
                "Usage: deacon-hip index build [OPTIONS] <INPUT>\n\n"
@@ -3344,6 +3549,34 @@ int main(int argc, char **argv) {
             if (pos.size() > 1) a.input2 = pos[1], a.has_input2 = true;
             if (pos.size() > 2) die("unexpected argument '" + pos[2] + "'");
             return run_classify(a);
+        }
+        if (args[0] == "mask") {
+            MaskArgs a;
+            std::vector<std::string> pos;
+            for (size_t i = 1; i < args.size(); ++i) {
+                const std::string &s = args[i];
+                if (s == "-x" || s == "--index") a.indexes.push_back(need(++i));
+                else if (s == "-o" || s == "--output") a.output = need(++i), a.has_output = true;
+                else if (s == "--bed") a.bed = need(++i), a.has_bed = true;
+                else if (s == "--soft") a.soft = true;
+                else if (s == "-g" || s == "--max-gap") {
+                    const long long v = std::atoll(need(++i).c_str());
+                    if (v < 0 || v > 0xFFFFFFFFll) die("invalid value for --max-gap: must be 0..4294967295");
+                    a.max_gap = (long)v;
+                } else if (s == "-a" || s == "--min-hits") {
+                    const long v = std::atol(need(++i).c_str());
+                    if (v < 1 || v > 65535) die("invalid value for --min-hits: must be 1..65535");
+                    a.min_hits = (unsigned)v;
+                } else if (s == "-p" || s == "--prefix-length") a.prefix_length = (size_t)std::atoll(need(++i).c_str());
+                else if (s == "-s" || s == "--summary") a.summary = need(++i), a.has_summary = true;
+                else if (s == "-t" || s == "--threads") ++i;
+                else if (s == "-q" || s == "--quiet") a.quiet = true;
+                else if (s.size() > 1 && s[0] == '-' && s != "-") die("unexpected argument '" + s + "'");
+                else pos.push_back(s);
+            }
+            if (pos.size() > 0) a.input = pos[0];
+            if (pos.size() > 1) die("mask takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[1] + "')");
+            return run_mask(a);
         }
         if (args[0] == "cat" && args.size() >= 2) {  // hidden: the input side alone (format found by content, decoded to stdout; no GPU)
             Input in(args[1]);

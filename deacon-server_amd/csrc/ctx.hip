@@ -75,7 +75,9 @@ static void free_ctx(dcn_ctx *c) {
                    c->d_keep, c->d_unit_state, c->d_hits, c->d_total, c->d_unit_scratch, c->d_caps,
                    c->d_set_off, c->d_tile_hits, c->d_pending, c->d_big, c->d_rec_hash, c->d_set_slots, c->d_status, c->d_report, c->d_dump_hash,
                    c->d_dump_pos, c->d_dump_count, c->d_dump_valid, c->d_tile_read_pos,
-                   c->d_cls_big, c->d_cls_n_big, c->d_cls_match, c->d_cls_hits, c->d_cls_total};
+                   c->d_cls_big, c->d_cls_n_big, c->d_cls_match, c->d_cls_hits, c->d_cls_total,
+                   c->d_loc_bits, c->d_loc_labels, c->d_loc_counts, c->d_loc_big, c->d_loc_n_big, c->d_loc_block_sums,
+                   c->d_loc_seg_offsets, c->d_loc_segs};
     for (void *p : dev)
         if (p && !((char *)p >= c->d_slab && (char *)p < c->d_slab + c->slab_bytes)) hipFree(p);
     if (c->d_slab) hipFree(c->d_slab);

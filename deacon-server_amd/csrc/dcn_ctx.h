@@ -1,6 +1,7 @@
 // dcn_ctx.h -- the filter context and what the files that implement the C ABI's host side share (internal, like
 // dcn_internal.h): api.hip (errors, indexes), ctx.hip (context, device-pointer batches, the stage builders),
-// host_batch.hip (submit / wait), dump.hip (minimizer dump, hash seam, index build), classify_api.hip (index sets).
+// host_batch.hip (submit / wait), dump.hip (minimizer dump, hash seam, index build), classify_api.hip (index sets),
+// locate_api.hip (segments).
 #pragma once
 
 #include "dcn_internal.h"
@@ -132,6 +133,14 @@ struct dcn_ctx {
     uint32_t *d_cls_big = nullptr, *d_cls_n_big = nullptr;
     uint32_t *d_cls_match = nullptr, *d_cls_hits = nullptr, *d_cls_total = nullptr;
     uint32_t cls_hits_members = 0;
+    // locate buffers (lazy, first dcn_locate_batch): the hit bitmap (a bit per base), the labels of the hits (a word per
+    // base, only once the index of a call is a set), per-read counts / offsets with the scan's block sums, the work list
+    // of the wave kernel, and the segment buffer (loc_seg_cap entries, grown to the largest count)
+    uint32_t *d_loc_bits = nullptr, *d_loc_labels = nullptr, *d_loc_counts = nullptr, *d_loc_big = nullptr, *d_loc_n_big = nullptr;
+    unsigned long long *d_loc_block_sums = nullptr;
+    uint64_t *d_loc_seg_offsets = nullptr;
+    dcn_segment *d_loc_segs = nullptr;
+    uint64_t loc_seg_cap = 0;
     // deferred state of the last enqueued device-API batch
     bool batch_pending = false;
     bool lean = false; // a small host batch is being submitted: copies and result copies go on `stream` itself (submit_impl)

@@ -10,6 +10,7 @@ Names, argument meaning and results follow the Rust items they stand for (paths 
     .stats()                            ProcessingStats                        (local_filter.rs:179-187)
   get_minimizer_hashes_and_positions <- filter_common.rs:211-310
   IndexSet / Classifier              (no counterpart) several indexes in one table, per-member hits in one pass
+  Locator                            (no counterpart) where in each read an index or a set matched: segments
   unpaired_should_keep / paired_should_keep <- remote_filter.rs:230-301
 
 Everything here is plumbing: all arithmetic happens in lib/libdeacon_hip.so on the GPU.
@@ -353,6 +354,81 @@ class Classifier:
     def profile(self):
         """(stage_ms, n_batches): for classify calls the stages are pack, plan, scan (minimizer dump), and the two
         classification kernels in the 'distinct' (one lane per unit) and 'finish' (one workgroup per large unit) slots"""
+        ms = (C.c_double * N.N_STAGES)()
+        n = C.c_uint64()
+        N.check(N.lib().dcn_ctx_profile(self._h, ms, C.byref(n)))
+        return dict(zip(N.STAGE_NAMES, list(ms))), n.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lib().dcn_ctx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# numpy view of dcn_segment (16 bytes)
+SEGMENT_DTYPE = np.dtype([("start", np.uint32), ("end", np.uint32), ("n_hits", np.uint32), ("members", np.uint32)])
+
+
+class Locator:
+    """Where in each read an Index or an IndexSet matched (dcn_locate_batch; the definition of a segment is in
+    include/deacon_hip.h): per read, the half-open [start, end) stretches its hit minimizer k-mers cover once hits at most
+    max_gap bases apart are joined, with the number of hit positions and the OR of their member labels.
+    max_gap=None is the derived default 2*w - 1; member_mask selects members of a set (ignored for a plain index)."""
+
+    def __init__(self, index, max_gap=None, min_hits=1, prefix_length=0, member_mask=0xFFFFFFFF,
+                 max_batch_bases=1 << 26, max_batch_reads=1 << 20):
+        self.index = index
+        w = index.w if hasattr(index, "w") else index.window_size  # (IndexSet / Index)
+        self.max_gap = 2 * int(w) - 1 if max_gap is None else int(max_gap)
+        self.min_hits = int(min_hits)
+        self.prefix_length = int(prefix_length)
+        self.member_mask = int(member_mask)
+        self.max_batch_bases = int(max_batch_bases)
+        self.max_batch_reads = int(max_batch_reads)
+        self._h = C.c_void_p()
+        N.check(N.lib().dcn_ctx_create(index._h, self.max_batch_bases, self.max_batch_reads, C.byref(self._h)))
+
+    def _params(self):
+        return N.LocateParams(self.max_gap, self.min_hits, self.member_mask, 0, self.prefix_length)
+
+    def locate_batch(self, bases, offsets):
+        """bases: concatenated ASCII; offsets[n_reads+1] -> (seg_offsets u64[n_reads+1], segs SEGMENT_DTYPE[]): read r
+        owns segs[seg_offsets[r]:seg_offsets[r+1]], ascending by start."""
+        bases = _as_u8(bases)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_reads = len(offsets) - 1
+        seg_offsets = np.zeros(n_reads + 1, np.uint64)
+        p = self._params()
+        cap = getattr(self, "_last_total", 0)
+        segs = np.zeros(max(cap, 1), SEGMENT_DTYPE)
+        for _ in range(2):  # the second call has the capacity the first one asked for
+            rc = N.lib().dcn_locate_batch(self._h, self.index._h, _ptr(bases) if len(bases) else None, _ptr(offsets),
+                                          n_reads, C.byref(p), _ptr(seg_offsets), _ptr(segs) if cap else None, cap)
+            if rc != N.DCN_ERR_CAPACITY:
+                break
+            cap = int(seg_offsets[n_reads])
+            segs = np.zeros(cap, SEGMENT_DTYPE)
+        N.check(rc)
+        self._last_total = int(seg_offsets[n_reads])
+        return seg_offsets, segs[:int(seg_offsets[n_reads])]
+
+    def stats(self):
+        c = (C.c_uint64 * N.N_STATS)()
+        N.check(N.lib().dcn_ctx_stats(self._h, c))
+        return dict(zip(N.STAT_NAMES, list(c)))
+
+    def set_profiling(self, enable=True):
+        N.check(N.lib().dcn_ctx_set_profiling(self._h, 1 if enable else 0))
+
+    def profile(self):
+        """(stage_ms, n_batches): pack, plan, scan (minimizer dump), the probe sweep that marks hits in the 'distinct' slot
+        and the segment passes (count, scan over reads, write) in the 'finish' slot"""
         ms = (C.c_double * N.N_STAGES)()
         n = C.c_uint64()
         N.check(N.lib().dcn_ctx_profile(self._h, ms, C.byref(n)))

@@ -67,9 +67,9 @@ enum {
  * changes (a binding built against another major must refuse to run: its calls would pass the wrong arguments), MINOR
  * when entry points are added.  History: 0.x = the headers before versioning (dcn_pack_ascii took four arguments there);
  * 1.0 = dcn_pack_ascii(bases, n_bases, packed, invmask, saw_newline); 1.1 = dcn_abi_version, dcn_comm_* / dcn_stats_allreduce_rccl;
- * 1.2 = dcn_index_set_* / dcn_classify_batch*; 1.3 = dcn_index_set_coverage*. */
+ * 1.2 = dcn_index_set_* / dcn_classify_batch*; 1.3 = dcn_index_set_coverage*; 1.4 = dcn_locate_batch. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 3
+#define DCN_ABI_MINOR 4
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -354,6 +354,52 @@ int dcn_index_set_coverage(const dcn_index *set, uint64_t *observed, uint64_t *k
 /* observed keys of member `member` (UINT32_MAX = of any member), arbitrary order; *n = count; DCN_ERR_CAPACITY if
  * capacity < count (out may be NULL with capacity 0: *n still receives the count) */
 int dcn_index_set_coverage_keys(const dcn_index *set, uint32_t member, uint64_t *out, uint64_t capacity, uint64_t *n);
+
+/* ---- locate: where in each read the index matched ----------------------------------------------------------
+ * (no reference counterpart: the reference answers one verdict per record.)  Segments of every read of a host batch,
+ * from the same probes the filter and the classifier make.  THE DEFINITION, per read (mates are independent here:
+ * there is no unit_id), with the index's k and w:
+ *   1. (hashes, positions) = what get_minimizer_hashes_and_positions yields for the read (src/filter_common.rs:211-310;
+ *      here dcn_minimizer_hashes_batch): after the len < k rule, the prefix cut, the stripped trailing newline and the
+ *      ACGT filter of positions.
+ *   2. A position p is a HIT when its hash is in the index.  On a labelled set its label is the key's member mask and it
+ *      is a hit when label & member_mask != 0; on a plain index the label is 1 and member_mask is ignored.  Positions
+ *      may repeat in the list; a position is one k-mer, has one hash and one label, and counts once.
+ *   3. Walk the distinct hit positions in ascending order.  A hit at p extends the current segment when
+ *      p <= segment.end + max_gap, else it starts a new one.  start = the segment's first hit position, end = its last
+ *      hit position + k (half-open, in bases of the read as given), n_hits = its distinct hit positions, members = OR of
+ *      their labels.
+ *   4. Segments with n_hits < min_hits are dropped (after merging: dropping never splits or joins anything).
+ *   5. A read's segments are reported in ascending start; they are disjoint and more than max_gap apart.
+ * max_gap = 2*w - 1 is the derived default of the layers above (an isolated substituted base leaves at most 2w - 1
+ * bases between the minimizer k-mers on its two sides, so that gap joins them and claims nothing larger); with w <= k
+ * the hits inside an exactly matching stretch overlap or abut, so max_gap = 0 already yields one segment there. */
+typedef struct dcn_locate_params {
+    uint32_t max_gap;       /* bases a segment may bridge between the end of one hit k-mer and the start of the next */
+    uint32_t min_hits;      /* >= 1: segments with fewer distinct hit positions are dropped */
+    uint32_t member_mask;   /* labelled set: only hits whose label meets this mask; ignored for a plain index */
+    uint32_t reserved;      /* must be 0 */
+    uint64_t prefix_length; /* 0 = whole read, else only the first prefix_length bases */
+} dcn_locate_params;
+typedef struct dcn_segment {
+    uint32_t start, end, n_hits, members;
+} dcn_segment; /* 16 bytes */
+
+/*   index        a plain index or a labelled set with the k, w, minimizer rule and device of the context's index
+ *   params       a dcn_locate_params; min_hits == 0 or reserved != 0 is DCN_ERR_ARG
+ *   seg_offsets  n_reads+1 entries: read r owns segs[seg_offsets[r] .. seg_offsets[r+1])
+ *   segs         an array of dcn_segment
+ *   capacity     entries available in segs; on DCN_ERR_CAPACITY seg_offsets[] is complete, seg_offsets[n_reads] is the
+ *                size needed and segs is not written (segs may be NULL with capacity 0 to ask for the count only)
+ * (params and segs are declared void *: every prototype of this header uses only scalar and handle types, which is
+ * what lets bindings be generated and checked from it; a C caller passes its dcn_locate_params * / dcn_segment * as is.)
+ * Host pointers, blocking, batch limits as for dcn_classify_batch; refused while batches are in flight; the six
+ * counters of the context are left unchanged.  Device memory, allocated on the first call and freed with the context:
+ * max_batch_bases / 8 bytes of hit bitmap, 4 * max_batch_bases bytes of labels when the index is a set, 16 bytes per
+ * read of counts and offsets, and a segment buffer grown to the largest batch's count.  dcn_ctx_set_profiling covers it:
+ * pack, plan, scan (minimizer dump), DISTINCT = the probe sweep that marks hits, FINISH = the segment passes. */
+int dcn_locate_batch(dcn_ctx *ctx, const dcn_index *index, const uint8_t *bases, const uint64_t *offsets,
+                     uint32_t n_reads, const void *params, uint64_t *seg_offsets, void *segs, uint64_t capacity);
 
 /* ---- counters: ProcessingStats (src/local_filter.rs:179-187, merged at :388-396) -------------------------- */
 
