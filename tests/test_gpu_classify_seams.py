@@ -29,7 +29,7 @@ LANE_ENTRIES = 64                 # DCN_CLS_LANE_ENTRIES (dcn_classify.h)
 HALF, FULL = 2048, 3072           # classify_big_kernel: entries per partition aimed at, fill limit of its LDS set
 
 
-def _group_slots():
+def group_slots():
     text = open(os.path.join(ROOT, "deacon-server_amd", "csrc", "dcn_internal.h")).read()
     return int(re.search(r"#define DCN_GROUP_SLOTS (\d+)", text).group(1))
 
@@ -247,14 +247,11 @@ def test_constructed_units_at_the_kernels_limits(oracle, dcn, k):
 
 
 # ---- member labels under displacement --------------------------------------------------------------------------------
-def test_member_labels_in_displaced_slots(oracle, dcn, monkeypatch):
-    """At 2 slots per key the set is about half full.  Member 0 fills the home group of every target hash and the group
-    after it, so the targets (held by members 1 and 2) sit two or more groups away; some home groups are the last one,
-    whose chains wrap to group 0.  Some fillers are in member 2 too (their labels are ORed into slots member 0 placed),
-    and some read hashes in the same groups are in no member: their lookups walk the same chains and find nothing."""
-    monkeypatch.setenv("DCN_TABLE_SLOTS_PER_KEY", "2")
+def displaced_members(oracle):
+    """The construction of test_member_labels_in_displaced_slots, for a table built under DCN_TABLE_SLOTS_PER_KEY=2:
+    (k, the table's groups, the three members' key arrays, the target home groups, the single-window reads)."""
     k = 31
-    S = _group_slots()
+    S = group_slots()
     G = 2048 // S                      # a 2 048-slot table: the member key counts sum to 509..1020
     pool = Pool(oracle, k, 24_000, 7)
     rng = np.random.default_rng(8)
@@ -285,13 +282,24 @@ def test_member_labels_in_displaced_slots(oracle, dcn, monkeypatch):
     while rule * S < n_sum * 2 + 8:
         rule <<= 1
     assert rule == G
-    members = [np.array(sorted(m), np.uint64) for m in (m0, m1, m2)]
+    rng.shuffle(reads)
+    return k, G, [np.array(sorted(m), np.uint64) for m in (m0, m1, m2)], targets, reads
+
+
+def test_member_labels_in_displaced_slots(oracle, dcn, monkeypatch):
+    """At 2 slots per key the set is about half full.  Member 0 fills the home group of every target hash and the group
+    after it, so the targets (held by members 1 and 2) sit two or more groups away; some home groups are the last one,
+    whose chains wrap to group 0.  Some fillers are in member 2 too (their labels are ORed into slots member 0 placed),
+    and some read hashes in the same groups are in no member: their lookups walk the same chains and find nothing."""
+    monkeypatch.setenv("DCN_TABLE_SLOTS_PER_KEY", "2")
+    S = group_slots()
+    k, G, members, targets, reads = displaced_members(oracle)
+    m0, m1, m2 = (set(m.tolist()) for m in members)
     ol = [oracle.Index(m, k, W) for m in members]
     s = dcn.IndexSet([dcn.Index.from_keys(m, k, W) for m in members])
     assert s.memory % 12 == 0 and s.memory // 12 == G * S  # 8 bytes of key and 4 of label per slot
     assert s.n_keys == len(m0 | m1 | m2)
     assert len(m0 | m1 | m2) * 2 > G * S * 0.85  # about half full
-    rng.shuffle(reads)
     clf = dcn.Classifier(s, abs_threshold=1, rel_threshold=0.0, max_batch_bases=1 << 20, max_batch_reads=1 << 13)
     _, hits, _ = check(oracle, clf, ol, reads)  # one read per unit: the lane path
     assert [int((hits[:, j] > 0).sum()) for j in range(3)] == [len(targets), 2 * len(targets), 2 * len(targets)]
