@@ -86,6 +86,7 @@ _SIGNATURES = {
     "dcn_index_keys": (C.c_int, [_vp, _vp, C.c_uint64, _u64p]),
     "dcn_index_union": (C.c_int, [C.POINTER(_vp), C.c_uint32, C.POINTER(_vp)]),
     "dcn_index_diff": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "dcn_index_intersect": (C.c_int, [C.POINTER(_vp), C.c_uint32, C.POINTER(_vp)]),
     "dcn_index_write_file": (C.c_int, [_vp, C.c_char_p]),
     "dcn_index_header": (C.c_int, [_vp, _u8p, _u8p, _u64p]),
     "dcn_index_contains": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
@@ -133,11 +134,14 @@ _SIGNATURES = {
     "dcn_index_set_coverage_reset": (C.c_int, [_vp]),
     "dcn_index_set_coverage": (C.c_int, [_vp, _vp, _vp]),
     "dcn_index_set_coverage_keys": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, _u64p]),
+    "dcn_index_set_select": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p,
+                                       C.POINTER(_vp)]),
+    "dcn_index_set_overlap": (C.c_int, [_vp, _vp, _vp, _vp]),
     "dcn_locate_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64]),
 }
 
 _lib = None
-ABI = (1, 4)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 5)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

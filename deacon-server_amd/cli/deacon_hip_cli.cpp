@@ -5,6 +5,10 @@
 //   deacon-hip index info  <index>
 //   deacon-hip index union <index>... [-o out.idx]
 //   deacon-hip index diff  <first.idx> <second.idx | fastx> [-k K -w W] [-o out.idx]
+//   deacon-hip index intersect <index>... [-o out.idx]
+//   deacon-hip index compare <index>... [-s summary.json]
+//   deacon-hip index select -x <index> [-x <index>...] [--all LIST] [--any LIST] [--none LIST] [--min-members N]
+//                           [--max-members N] [-o out.idx]
 //   deacon-hip filter <index> [input|-] [input2|-] [-o out] [-O out2] [-a 2] [-r 0.01] [-p 0] [-d] [-R]
 //                     [-s summary.json] [-t threads] [--compression-level 2] [--debug] [-q]
 //   deacon-hip mask -x <index> [-x <index>...] [input|-] [-o masked.fastq] [--bed hits.bed] [--soft] [-g N] [-a 2] [-p 0] [-s summary.json]
@@ -2924,6 +2928,153 @@ int run_index_diff(const std::string &first, const std::string &second, int k_op
     return 0;
 }
 
+// A n B n ... (dcn_index_intersect; no reference counterpart: the reference composes with union and diff)
+int run_index_intersect(const std::vector<std::string> &inputs, const std::string &output) {
+    auto start = std::chrono::steady_clock::now();
+    if (inputs.empty()) die("index intersect needs at least one <INDEX>");
+    std::vector<RawIndex> idx(inputs.size());
+    std::vector<const dcn_index *> ptrs;
+    for (size_t i = 0; i < inputs.size(); ++i) {
+        deacon::check(dcn_index_from_file(inputs[i].c_str(), 0, &idx[i].p));
+        uint64_t n = 0;
+        dcn_index_header(idx[i].p, nullptr, nullptr, &n);
+        std::fprintf(stderr, "Index %zu: %llu minimizers\n", i + 1, (unsigned long long)n);
+        ptrs.push_back(idx[i].p);
+    }
+    RawIndex out;
+    deacon::check(dcn_index_intersect(ptrs.data(), (uint32_t)ptrs.size(), &out.p));
+    uint64_t n = 0;
+    dcn_index_header(out.p, nullptr, nullptr, &n);
+    std::fprintf(stderr, "Intersection: %llu minimizers from %zu indexes\n", (unsigned long long)n, inputs.size());
+    write_index(out.p, output);
+    std::fprintf(stderr, "Completed intersect operation in %s\n",
+                 fmt_duration(std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count()).c_str());
+    return 0;
+}
+
+// the labelled set over index files, as `classify` builds it; the members' own tables go back at once
+void load_index_set(const std::vector<std::string> &paths, RawIndex &set) {
+    std::vector<RawIndex> members(paths.size());
+    std::vector<const dcn_index *> mp(paths.size());
+    for (size_t j = 0; j < paths.size(); ++j) {
+        deacon::check(dcn_index_from_file(paths[j].c_str(), 0, &members[j].p));
+        mp[j] = members[j].p;
+    }
+    deacon::check(dcn_index_set_create(mp.data(), (uint32_t)mp.size(), &set.p));
+}
+
+// `deacon-hip index compare`: how much 2..32 indexes share (dcn_index_set_overlap).  stdout: a TSV of shared counts, a
+// blank line, and the same shape holding containment shared[i][j] / keys[i]
+int run_index_compare(const std::vector<std::string> &inputs, const std::string &summary) {
+    if (inputs.size() < 2 || inputs.size() > 32) die("index compare takes 2 to 32 indexes, not " + std::to_string(inputs.size()));
+    const size_t n = inputs.size();
+    RawIndex set;
+    load_index_set(inputs, set);
+    uint8_t k = 0, w = 0;
+    uint64_t n_union = 0;
+    deacon::check(dcn_index_header(set.p, &k, &w, &n_union));
+    std::vector<uint64_t> shared(n * n), exclusive(n), by_count(n);
+    deacon::check(dcn_index_set_overlap(set.p, shared.data(), exclusive.data(), by_count.data()));
+    auto keys = [&](size_t i) { return shared[i * n + i]; };
+    auto ratio = [](uint64_t a, uint64_t b) { return b ? (double)a / (double)b : 0.0; };
+    for (int block = 0; block < 2; ++block) {
+        std::string text = block ? "\nindex\tkeys\texclusive" : "index\tkeys\texclusive";
+        for (auto &p : inputs) text += "\t" + p;
+        text += "\n";
+        char buf[64];
+        for (size_t i = 0; i < n; ++i) {
+            text += inputs[i] + "\t" + std::to_string(keys(i)) + "\t" + std::to_string(exclusive[i]);
+            for (size_t j = 0; j < n; ++j) {
+                if (block) {
+                    if (keys(i)) std::snprintf(buf, sizeof buf, "\t%.6f", ratio(shared[i * n + j], keys(i)));
+                    else std::snprintf(buf, sizeof buf, "\t0");
+                    text += buf;
+                } else {
+                    text += "\t" + std::to_string(shared[i * n + j]);
+                }
+            }
+            text += "\n";
+        }
+        std::fwrite(text.data(), 1, text.size(), stdout);
+    }
+    if (!summary.empty()) {
+        char buf[64];
+        std::string js = "{\n  \"version\": " + json_str(std::string("deacon-hip ") + VERSION) + ",\n  \"k\": " + std::to_string((int)k) +
+                         ",\n  \"w\": " + std::to_string((int)w) + ",\n  \"union\": " + std::to_string(n_union) + ",\n  \"members\": [";
+        for (size_t i = 0; i < n; ++i)
+            js += std::string(i ? "," : "") + "\n    {\"path\": " + json_str(inputs[i]) + ", \"keys\": " + std::to_string(keys(i)) +
+                  ", \"exclusive\": " + std::to_string(exclusive[i]) + "}";
+        js += "\n  ],\n  \"shared\": [";
+        for (size_t i = 0; i < n; ++i) {
+            js += std::string(i ? "," : "") + "\n    [";
+            for (size_t j = 0; j < n; ++j) js += (j ? ", " : "") + std::to_string(shared[i * n + j]);
+            js += "]";
+        }
+        js += "\n  ],\n  \"jaccard\": [";
+        for (size_t i = 0; i < n; ++i) {
+            js += std::string(i ? "," : "") + "\n    [";
+            for (size_t j = 0; j < n; ++j) {
+                std::snprintf(buf, sizeof buf, "%s%.17g", j ? ", " : "", ratio(shared[i * n + j], keys(i) + keys(j) - shared[i * n + j]));
+                js += buf;
+            }
+            js += "]";
+        }
+        js += "\n  ],\n  \"by_count\": [";
+        for (size_t c = 0; c < n; ++c) js += (c ? ", " : "") + std::to_string(by_count[c]);
+        js += "]\n}\n";
+        FILE *f = std::fopen(summary.c_str(), "w");
+        if (!f) die("cannot open " + summary + " for writing");
+        std::fwrite(js.data(), 1, js.size(), f);
+        std::fclose(f);
+    }
+    return 0;
+}
+
+// a LIST of `index select`: comma-separated 0-based positions of the -x options -> a member mask
+uint32_t parse_member_list(const std::string &opt, const std::string &list, size_t n_indexes) {
+    uint32_t mask = 0;
+    std::stringstream ss(list);
+    std::string item;
+    bool any = false;
+    while (std::getline(ss, item, ',')) {
+        if (item.empty() || item.size() > 2 || item.find_first_not_of("0123456789") != std::string::npos)
+            die("invalid value '" + list + "' for " + opt + ": a comma-separated list of 0-based index positions");
+        const unsigned j = (unsigned)std::atoi(item.c_str());
+        if (j >= n_indexes) die("invalid value '" + list + "' for " + opt + ": position " + item + ", but " + std::to_string(n_indexes) + " -x given");
+        mask |= 1u << j;
+        any = true;
+    }
+    if (!any || list.back() == ',') die("invalid value '" + list + "' for " + opt + ": a comma-separated list of 0-based index positions");
+    return mask;
+}
+
+struct SelectArgs {
+    std::vector<std::string> indexes;
+    std::string all_of, any_of, none_of, output = "-";
+    unsigned min_members = 0, max_members = 0;
+};
+
+// `deacon-hip index select`: the keys of several indexes chosen by which of them hold each (dcn_index_set_select)
+int run_index_select(const SelectArgs &a) {
+    auto start = std::chrono::steady_clock::now();
+    if (a.indexes.empty()) die("the following required arguments were not provided: -x <INDEX>");
+    if (a.indexes.size() > 32) die("index select takes at most 32 indexes");
+    const uint32_t all_of = a.all_of.empty() ? 0 : parse_member_list("--all", a.all_of, a.indexes.size());
+    const uint32_t any_of = a.any_of.empty() ? 0 : parse_member_list("--any", a.any_of, a.indexes.size());
+    const uint32_t none_of = a.none_of.empty() ? 0 : parse_member_list("--none", a.none_of, a.indexes.size());
+    if (a.max_members && a.min_members > a.max_members) die("--min-members is larger than --max-members");
+    RawIndex set, out;
+    load_index_set(a.indexes, set);
+    uint64_t n_union = 0, n = 0;
+    deacon::check(dcn_index_header(set.p, nullptr, nullptr, &n_union));
+    deacon::check(dcn_index_set_select(set.p, all_of, any_of, none_of, a.min_members, a.max_members, &n, &out.p));
+    std::fprintf(stderr, "Selected %llu of %llu minimizers\n", (unsigned long long)n, (unsigned long long)n_union);
+    write_index(out.p, a.output);
+    std::fprintf(stderr, "Completed select operation in %s\n",
+                 fmt_duration(std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count()).c_str());
+    return 0;
+}
+
 // `deacon-hip classify`: which of up to 32 indexes each read (or pair) matches, from one pass over the input against one
 // labelled index set (dcn_index_set_create / dcn_classify_batch).  No reference counterpart: its nearest is N runs of
 // `deacon filter` in search mode, one per index -- a unit matches index j exactly when that run would keep it.
@@ -3307,7 +3458,7 @@ int run_mask(const MaskArgs &a) {
 
 void usage() {
     std::fprintf(stderr,
-                 "Usage: deacon-hip <COMMAND>\n\nCommands:\n  index   Build and compose minimizer indexes (build, info, union, diff)\n"
+                 "Usage: deacon-hip <COMMAND>\n\nCommands:\n  index   Build and compose minimizer indexes (build, info, union, diff, intersect, compare, select)\n"
                  "  filter  Keep or discard DNA fastx records with sufficient minimizer hits to an index\n"
                  "  classify  Report which of several indexes each record (or pair) matches, in one pass\n"
                  "  mask    Report where in each record an index matched, and mask those stretches\n"
@@ -3443,6 +3594,35 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "  -w, --window-size <W>    Window size (required if second argument is FASTX file)\n"
                "  -o, --output <OUTPUT>    Path to output file (- for stdout) [default: -]\n"
                "  -h, --help               Print help\n";
+    else if (sub == "index intersect")
+        text = "Keep the minimizers present in every index (A n B...)\n\n"
+               "Usage: deacon-hip index intersect [OPTIONS] <INPUTS>...\n\n"
+               "Arguments:\n  <INPUTS>...  Path(s) to one or more index file(s)\n\n"
+               "Options:\n"
+               "  -o, --output <OUTPUT>      Path to output file (- for stdout) [default: -]\n"
+               "  -h, --help                 Print help\n";
+    else if (sub == "index compare")
+        text = "Report how many minimizers 2 to 32 indexes share, pair by pair\n\n"
+               "Usage: deacon-hip index compare [OPTIONS] <INPUTS>...\n\n"
+               "Arguments:\n  <INPUTS>...  Paths to 2 to 32 index files (same k and w)\n\n"
+               "Options:\n"
+               "  -s, --summary <SUMMARY>    Path to JSON summary output file (k, w, union, members, shared, jaccard, by_count)\n"
+               "  -h, --help                 Print help\n\n"
+               "stdout: one TSV row per index (index, keys, exclusive, then the minimizers shared with each index), a blank line,\n"
+               "and the same rows holding containment: shared / keys of the row's index.\n";
+    else if (sub == "index select")
+        text = "Keep the minimizers of several indexes chosen by which of the indexes hold them\n\n"
+               "Usage: deacon-hip index select -x <INDEX> [-x <INDEX>...] [OPTIONS]\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>        Path to a minimizer index file; repeat for up to 32 indexes (same k and w)\n"
+               "      --all <LIST>           Keep minimizers held by every index of LIST (comma-separated 0-based positions of the -x options)\n"
+               "      --any <LIST>           Keep minimizers held by at least one index of LIST\n"
+               "      --none <LIST>          Keep minimizers held by no index of LIST\n"
+               "      --min-members <N>      Keep minimizers held by at least N of the indexes [default: 1]\n"
+               "      --max-members <N>      Keep minimizers held by at most N of the indexes (0 = no bound) [default: 0]\n"
+               "  -o, --output <OUTPUT>      Path to output file (- for stdout) [default: -]\n"
+               "  -h, --help                 Print help\n\n"
+               "Minimizers only the first index holds: --all 0 --max-members 1.  The core held by at least m indexes: --min-members m.\n";
     else if (sub == "index")
         text = "Build and compose minimizer indexes\n\n"
                "Usage: deacon-hip index <COMMAND>\n\n"
@@ -3450,7 +3630,10 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "  build  Index minimizers contained within a fastx file\n"
                "  info   Show index information\n"
                "  union  Combine multiple minimizer indexes (A u B...)\n"
-               "  diff   Subtract minimizers in one index from another (A - B)\n";
+               "  diff   Subtract minimizers in one index from another (A - B)\n"
+               "  intersect  Keep the minimizers present in every index (A n B...)\n"
+               "  compare    Report how many minimizers 2 to 32 indexes share, pair by pair\n"
+               "  select     Keep the minimizers of several indexes chosen by which of the indexes hold them\n";
     if (!text) return false;
     std::fputs(text, stdout);
     return true;
@@ -3773,6 +3956,37 @@ int main(int argc, char **argv) {
             if (args[1] == "union") return run_index_union(pos, output);
             if (pos.size() != 2) die("index diff needs <FIRST> <SECOND>");
             return run_index_diff(pos[0], pos[1], k_opt, w_opt, output);
+        }
+        if (args[0] == "index" && args.size() >= 2 && (args[1] == "intersect" || args[1] == "compare")) {
+            std::vector<std::string> pos;
+            std::string output = "-", summary;
+            for (size_t i = 2; i < args.size(); ++i) {
+                const std::string &s = args[i];
+                if (args[1] == "intersect" && (s == "-o" || s == "--output")) output = need(++i);
+                else if (args[1] == "compare" && (s == "-s" || s == "--summary")) summary = need(++i);
+                else if (s.size() > 1 && s[0] == '-') die("unexpected argument '" + s + "'");
+                else pos.push_back(s);
+            }
+            return args[1] == "intersect" ? run_index_intersect(pos, output) : run_index_compare(pos, summary);
+        }
+        if (args[0] == "index" && args.size() >= 2 && args[1] == "select") {
+            SelectArgs a;
+            auto list = [&](size_t i) -> const std::string & {  // (an empty LIST is a mistake, not an option left out)
+                if (need(i).empty()) die("invalid value '' for " + args[i - 1] + ": a comma-separated list of 0-based index positions");
+                return args[i];
+            };
+            for (size_t i = 2; i < args.size(); ++i) {
+                const std::string &s = args[i];
+                if (s == "-x" || s == "--index") a.indexes.push_back(need(++i));
+                else if (s == "--all") a.all_of = list(++i);
+                else if (s == "--any") a.any_of = list(++i);
+                else if (s == "--none") a.none_of = list(++i);
+                else if (s == "--min-members") a.min_members = (unsigned)std::max(0, std::atoi(need(++i).c_str()));
+                else if (s == "--max-members") a.max_members = (unsigned)std::max(0, std::atoi(need(++i).c_str()));
+                else if (s == "-o" || s == "--output") a.output = need(++i);
+                else die("unexpected argument '" + s + "'");
+            }
+            return run_index_select(a);
         }
         usage();
         return 2;

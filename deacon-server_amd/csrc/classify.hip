@@ -19,6 +19,7 @@
 // The coverage sweeps (dcn_index_set_coverage*) count and list the marked slots per member.
 #include "dcn_classify.h"
 #include "dcn_probe.h"
+#include "dcn_table_insert.h"
 
 #include <algorithm>
 
@@ -440,30 +441,7 @@ __global__ void set_add_member_kernel(uint64_t *slots, uint32_t *labels, uint32_
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < src_slots; i += stride) {
         const uint64_t key = src[i];
         if (key == 0) continue;
-        uint32_t g = dcn_group_of(key, shift, mask);
-        for (;;) {
-            unsigned long long *grp = (unsigned long long *)(slots + (uint64_t)g * DCN_GROUP_SLOTS);
-            int at = -1;
-            for (int s = 0; s < DCN_GROUP_SLOTS && at < 0; ++s) {
-                unsigned long long cur = __hip_atomic_load(&grp[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (cur == key) {
-                    at = s;
-                } else if (cur == 0) {
-                    unsigned long long old = atomicCAS(&grp[s], 0ull, (unsigned long long)key);
-                    if (old == 0) {
-                        fresh++;
-                        at = s;
-                    } else if (old == key) {
-                        at = s;
-                    }
-                }
-            }
-            if (at >= 0) {
-                atomicOr(&labels[(uint64_t)g * DCN_GROUP_SLOTS + at], bit);
-                break;
-            }
-            g = (g + 1) & mask;
-        }
+        atomicOr(&labels[dcn_table_insert_dev(slots, shift, mask, key, &fresh)], bit);
     }
     if (fresh) atomicAdd(n_new, fresh);
 }

@@ -7,13 +7,11 @@
 
 using namespace dcn_impl;
 
-namespace {
-int check_set(const dcn_index *set) {
+int dcn_impl::check_set(const dcn_index *set) {
     if (!set) return dcn_fail(DCN_ERR_ARG, "set is NULL");
     if (set->n_members == 0 || !set->d_labels) return dcn_fail(DCN_ERR_ARG, "index is not a labelled set (dcn_index_set_create)");
     return DCN_OK;
 }
-} // namespace
 
 extern "C" int dcn_index_set_create(const dcn_index *const *members, uint32_t n, dcn_index **out) {
     if (!out) return dcn_fail(DCN_ERR_ARG, "out is NULL");

@@ -210,6 +210,9 @@ struct BatchView {
 // ---- api.hip ----
 int same_params(const dcn_index *a, const dcn_index *b); // k, w, device and minimizer rule agree (else DCN_ERR_ARG)
 
+// ---- classify_api.hip ----
+int check_set(const dcn_index *set); // not NULL and a labelled set (else DCN_ERR_ARG)
+
 // ---- ctx.hip: context plumbing ----
 int alloc_records(dcn_ctx *c, uint64_t n_records);
 void free_slot_buffers(dcn_slot &sl);

@@ -6,6 +6,7 @@
 // probing group by group.  One probe = one aligned group read inside one 64-byte HBM sector.
 #include "dcn_internal.h"
 #include "dcn_probe.h"
+#include "dcn_table_insert.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -719,26 +720,7 @@ __global__ void table_copy_filtered_kernel(uint64_t *dst, uint32_t dst_shift, ui
         uint64_t key = src[i];
         if (key == 0) continue;
         if (minus.slots && dcn_table_contains_dev(minus, key)) continue;
-        uint32_t g = dcn_group_of(key, dst_shift, dst_mask);
-        bool done = false;
-        while (!done) {
-            unsigned long long *grp = (unsigned long long *)(dst + (uint64_t)g * DCN_GROUP_SLOTS);
-            for (int s = 0; s < DCN_GROUP_SLOTS && !done; ++s) {
-                unsigned long long cur = __hip_atomic_load(&grp[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (cur == key) {
-                    done = true;
-                } else if (cur == 0) {
-                    unsigned long long old = atomicCAS(&grp[s], 0ull, (unsigned long long)key);
-                    if (old == 0) {
-                        fresh++;
-                        done = true;
-                    } else if (old == key) {
-                        done = true;
-                    }
-                }
-            }
-            g = (g + 1) & dst_mask;
-        }
+        dcn_table_insert_dev(dst, dst_shift, dst_mask, key, &fresh);
     }
     if (fresh) atomicAdd(n_new, fresh);
 }

@@ -162,6 +162,16 @@ class Index:
         N.check(N.lib().dcn_index_union(arr, len(indexes), C.byref(h)))
         return cls(h, indexes[0].device)
 
+    @classmethod
+    def intersect(cls, indexes):
+        """The minimizers present in every one of `indexes` (dcn_index_intersect; no reference counterpart): same k, w,
+        minimizer rule and device, any number of them; the result is sized for its own key count."""
+        indexes = list(indexes)
+        arr = (C.c_void_p * max(len(indexes), 1))(*[i._h for i in indexes])
+        h = C.c_void_p()
+        N.check(N.lib().dcn_index_intersect(arr, len(indexes), C.byref(h)))
+        return cls(h, indexes[0].device)
+
     def clone(self, device):
         """Replica on another (or the same) device, copied device to device (dcn_index_clone)."""
         h = C.c_void_p()
@@ -272,6 +282,45 @@ class IndexSet:
         out = np.zeros(max(n.value, 1), np.uint64)
         N.check(N.lib().dcn_index_set_coverage_keys(self._h, m, _ptr(out), len(out), C.byref(n)))
         return out[:n.value]
+
+    # ---- set algebra on the member masks (dcn_index_set_select / dcn_index_set_overlap) ----
+    def __len__(self):
+        return self.n_keys
+
+    def _mask(self, members):
+        """a member mask given as an int, or as an iterable of member numbers"""
+        if isinstance(members, (int, np.integer)):
+            m = int(members)
+        else:
+            m = 0
+            for j in members:
+                if not 0 <= int(j) < 32:
+                    raise ValueError(f"member {j} out of range")
+                m |= 1 << int(j)
+        if not 0 <= m <= 0xFFFFFFFF:
+            raise ValueError(f"member mask {members} out of range")
+        return m
+
+    def select(self, all_of=0, any_of=0, none_of=0, min_members=0, max_members=0, count_only=False):
+        """The keys whose member mask L holds every member of all_of, some member of any_of (if given), none of none_of,
+        and min_members <= popcount(L) <= max_members (0 = no bound): a new plain Index sized for them, or their number
+        with count_only.  Masks are ints (bit j = member j) or iterables of member numbers.  The member-specific keys of
+        member j: select(all_of=[j], max_members=1); the core held by at least m members: select(min_members=m)."""
+        n = C.c_uint64()
+        h = C.c_void_p()
+        N.check(N.lib().dcn_index_set_select(self._h, self._mask(all_of), self._mask(any_of), self._mask(none_of),
+                                             int(min_members), int(max_members), C.byref(n),
+                                             None if count_only else C.byref(h)))
+        return n.value if count_only else Index(h, self.device)
+
+    def overlap(self):
+        """How much the members share: {"shared": u64[n, n] (keys in members i and j; the diagonal is each member's key
+        count), "exclusive": u64[n] (keys in member j alone), "by_count": u64[n] (keys held by exactly c + 1 members)}."""
+        shared = np.zeros((self.n, self.n), np.uint64)
+        exclusive = np.zeros(self.n, np.uint64)
+        by_count = np.zeros(self.n, np.uint64)
+        N.check(N.lib().dcn_index_set_overlap(self._h, _ptr(shared), _ptr(exclusive), _ptr(by_count)))
+        return {"shared": shared, "exclusive": exclusive, "by_count": by_count}
 
     def close(self):
         if getattr(self, "_h", None):

@@ -67,9 +67,10 @@ enum {
  * changes (a binding built against another major must refuse to run: its calls would pass the wrong arguments), MINOR
  * when entry points are added.  History: 0.x = the headers before versioning (dcn_pack_ascii took four arguments there);
  * 1.0 = dcn_pack_ascii(bases, n_bases, packed, invmask, saw_newline); 1.1 = dcn_abi_version, dcn_comm_* / dcn_stats_allreduce_rccl;
- * 1.2 = dcn_index_set_* / dcn_classify_batch*; 1.3 = dcn_index_set_coverage*; 1.4 = dcn_locate_batch. */
+ * 1.2 = dcn_index_set_* / dcn_classify_batch*; 1.3 = dcn_index_set_coverage*; 1.4 = dcn_locate_batch;
+ * 1.5 = dcn_index_set_select / _overlap, dcn_index_intersect. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 4
+#define DCN_ABI_MINOR 5
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -126,6 +127,13 @@ int dcn_index_union(const dcn_index *const *inputs, uint32_t n, dcn_index **out)
 
 /* Set difference first \ second: index::diff (src/index.rs:421-536); k and w must match (:478-490). */
 int dcn_index_diff(const dcn_index *first, const dcn_index *second, dcn_index **out);
+
+/* Set intersection of n >= 1 indexes on the same device: the keys present in EVERY input (no reference counterpart: the
+ * reference composes indexes with union and diff only, and A n B took two diffs and two intermediate indexes).  The
+ * refusals on k, w, minimizer rule and device are dcn_index_union's; a labelled set counts as the union of its members.
+ * Any n works: the smallest input is swept once and its keys probed in the others.  The result's table is sized for its
+ * own key count, not for the inputs'; an empty intersection is a valid index with 0 keys. */
+int dcn_index_intersect(const dcn_index *const *inputs, uint32_t n, dcn_index **out);
 
 /* Header fields and the number of DISTINCT keys (what `deacon index info` prints, src/index.rs:539-560). */
 int dcn_index_header(const dcn_index *index, uint8_t *k, uint8_t *w, uint64_t *n_keys);
@@ -309,6 +317,28 @@ void dcn_index_set_destroy(dcn_index *set);
 /* member count, k, w, distinct keys of the union, device bytes of slots + masks; DCN_ERR_ARG for an index that is not a set */
 int dcn_index_set_info(const dcn_index *set, uint32_t *n_members, uint8_t *k, uint8_t *w, uint64_t *n_keys,
                        uint64_t *table_bytes);
+
+/* ---- set algebra on a labelled set: its member masks answer every membership question about its keys ------------
+ * (no reference counterpart.)  Both calls are blocking sweeps over the set's masks on its device, leave the set -- its
+ * coverage marks included -- as it is, and return DCN_ERR_ARG for an index that is not a set.  Key 0 takes part.
+ *
+ * Keys of a labelled set chosen by their member mask L (c = popcount(L)):
+ *   (L & all_of) == all_of  &&  (any_of == 0 || (L & any_of) != 0)  &&  (L & none_of) == 0
+ *   && min_members <= c <= max_members
+ * -> a new PLAIN index (k, w, minimizer rule and device of the set; neither masks nor coverage), sized for exactly the
+ * selected keys.  max_members == 0: no upper bound; min_members == 0 behaves as 1 (every key of a set is in at least one
+ * member).  *n_selected (may be NULL) receives the count.  out == NULL: count only, nothing is allocated.
+ * DCN_ERR_ARG: a mask with a bit at or above the set's member count, min_members > max_members != 0, out and n_selected
+ * both NULL.  A well-formed predicate that nothing satisfies (all_of & none_of != 0, say) is no error: the result is a
+ * valid index with 0 keys.  Recipes: the keys only member j holds = all_of 1 << j, max_members 1; the core held by at
+ * least m members = min_members m. */
+int dcn_index_set_select(const dcn_index *set, uint32_t all_of, uint32_t any_of, uint32_t none_of, uint32_t min_members,
+                         uint32_t max_members, uint64_t *n_selected, dcn_index **out);
+/* How much the members share.  n = the set's member count; any output may be NULL, but not all three.
+ *   shared[i*n + j]  keys whose mask has bits i and j (symmetric; shared[j*n + j] = keys of member j in the set)
+ *   exclusive[j]     keys whose mask is exactly 1 << j
+ *   by_count[c-1]    keys held by exactly c members, c = 1..n (sums to the set's key count) */
+int dcn_index_set_overlap(const dcn_index *set, uint64_t *shared, uint64_t *exclusive, uint64_t *by_count);
 
 /* Classify one batch against every member of `set` at once.  Inputs as for dcn_filter_batch (a unit is a read, or a
  * pair through unit_id; params->prefix_length applies; params->deplete is ignored).  Per unit u, with n members:

@@ -108,6 +108,14 @@ class Index {
         check(dcn_index_contains(h_, hashes.data(), hashes.size(), out.data()));
         return std::vector<bool>(out.begin(), out.end());
     }
+    // the minimizers present in every input (dcn_index_intersect; the reference composes with union and diff only)
+    static Index intersect(const std::vector<const Index *> &inputs) {
+        std::vector<const dcn_index *> raw;
+        for (const Index *i : inputs) raw.push_back(i ? i->h_ : nullptr);
+        dcn_index *h = nullptr;
+        check(dcn_index_intersect(raw.data(), (uint32_t)raw.size(), &h));
+        return Index(h);
+    }
     // replica on another (or the same) device, copied device to device: the reference shares ONE set between its
     // workers (local_filter.rs:630-631); a multi-GPU host loads it once and clones it
     Index clone(int device) const {
