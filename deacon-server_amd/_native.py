@@ -134,6 +134,11 @@ _SIGNATURES = {
     "dcn_index_set_coverage_reset": (C.c_int, [_vp]),
     "dcn_index_set_coverage": (C.c_int, [_vp, _vp, _vp]),
     "dcn_index_set_coverage_keys": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, _u64p]),
+    "dcn_index_set_depth_enable": (C.c_int, [_vp, C.c_int]),
+    "dcn_index_set_depth_reset": (C.c_int, [_vp]),
+    "dcn_index_set_depth_stats": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "dcn_index_set_depth_hist": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp]),
+    "dcn_index_set_depth_keys": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint64, _u64p]),
     "dcn_index_set_select": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p,
                                        C.POINTER(_vp)]),
     "dcn_index_set_overlap": (C.c_int, [_vp, _vp, _vp, _vp]),
@@ -141,7 +146,7 @@ _SIGNATURES = {
 }
 
 _lib = None
-ABI = (1, 5)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 6)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

@@ -13,7 +13,7 @@
 //                     [-s summary.json] [-t threads] [--compression-level 2] [--debug] [-q]
 //   deacon-hip mask -x <index> [-x <index>...] [input|-] [-o masked.fastq] [--bed hits.bed] [--soft] [-g N] [-a 2] [-p 0] [-s summary.json]
 //   deacon-hip classify -x <index> [-x <index>...] [input|-] [input2] [-a 2] [-r 0.01] [-p 0] [--per-read out.tsv|-]
-//                       [--coverage]
+//                       [--coverage] [--depth] [--depth-hist hist.tsv]
 //                     [-s summary.json] [-q]
 //
 // Flags, defaults, stderr messages and the JSON summary follow src/main.rs:24-234, src/local_filter.rs:575-824 and
@@ -3083,6 +3083,9 @@ struct ClassifyArgs {
     std::string input = "-", input2, per_read, summary;
     bool has_input2 = false, has_per_read = false, has_summary = false, quiet = false;
     bool coverage = false; // --coverage: distinct keys of each index the input touched (dcn_index_set_coverage)
+    bool depth = false;    // --depth: how often the input touched them (dcn_index_set_depth_*)
+    std::string depth_hist;
+    bool has_depth_hist = false;
     unsigned abs_threshold = 2;
     double rel_threshold = 0.01;
     size_t prefix_length = 0;
@@ -3116,6 +3119,7 @@ int run_classify(const ClassifyArgs &a) {
     }
     // the marks live with the set: contexts recreated for long records below keep adding to them
     if (a.coverage) deacon::check(dcn_index_set_coverage_enable(set.p, 1));
+    if (a.depth) deacon::check(dcn_index_set_depth_enable(set.p, 1)); // (and so do the depth counters)
     uint64_t batch_bases = 32ull << 20, max_bases = 64ull << 20;
     if (const char *e = std::getenv("DCN_CLI_CLASSIFY_BATCH_BASES")) { // test hook: many batches, records past the context
         batch_bases = (uint64_t)std::max(64, std::atoi(e));
@@ -3227,6 +3231,49 @@ int run_classify(const ClassifyArgs &a) {
                 std::fprintf(stderr, "warning: the set holds %llu keys of %s, its index file %llu\n",
                              (unsigned long long)set_keys[j], stems[j].c_str(), (unsigned long long)mkeys[j]);
     }
+    // depth per index: the three tallies, and mean and median over the observed keys (the median from a histogram of
+    // 4096 bins: the mean of the two middle keys' depths, or ">=4095" when the upper one lies in the last bin)
+    std::vector<uint64_t> d_observed(n, 0), d_sum(n, 0), d_saturated(n, 0);
+    std::vector<std::string> d_median(n, "0");
+    if (a.depth) {
+        deacon::check(dcn_index_set_depth_stats(set.p, d_observed.data(), d_sum.data(), d_saturated.data()));
+        const uint32_t bins = 4096;
+        std::vector<uint64_t> h(bins);
+        for (uint32_t j = 0; j < n; ++j) {
+            deacon::check(dcn_index_set_depth_hist(set.p, j, bins, h.data()));
+            uint64_t seen = 0;
+            for (uint32_t d = 1; d < bins; ++d) seen += h[d];
+            if (!seen) continue;
+            const uint64_t r_lo = (seen - 1) / 2, r_hi = seen / 2; // 0-based ranks of the middle keys
+            uint32_t lo = 0, hi = 0;
+            uint64_t below = 0;
+            for (uint32_t d = 1; d < bins; ++d) {
+                if (r_lo >= below && r_lo < below + h[d]) lo = d;
+                if (r_hi >= below && r_hi < below + h[d]) hi = d;
+                below += h[d];
+            }
+            char mb[64];
+            if (hi == bins - 1) std::snprintf(mb, sizeof mb, "\">=%u\"", bins - 1);
+            else std::snprintf(mb, sizeof mb, "%.17g", (lo + hi) / 2.0);
+            d_median[j] = mb;
+        }
+    }
+    if (a.has_depth_hist) {
+        FILE *f = std::fopen(a.depth_hist.c_str(), "w");
+        if (!f) die("cannot open " + a.depth_hist + " for writing");
+        std::fputs("index\tdepth\tkeys\n", f);
+        const uint32_t bins = 256;
+        std::vector<uint64_t> h(bins);
+        for (uint32_t j = 0; j < n; ++j) {
+            deacon::check(dcn_index_set_depth_hist(set.p, j, bins, h.data()));
+            for (uint32_t d = 0; d < bins; ++d) {
+                if (!h[d]) continue;
+                if (d == bins - 1) std::fprintf(f, "%s\t>=%u\t%llu\n", stems[j].c_str(), d, (unsigned long long)h[d]);
+                else std::fprintf(f, "%s\t%u\t%llu\n", stems[j].c_str(), d, (unsigned long long)h[d]);
+            }
+        }
+        std::fclose(f);
+    }
     if (!a.quiet) {
         for (uint32_t j = 0; j < n; ++j)
             std::fprintf(stderr, "%s: %llu/%llu (%.3f%%) sequences matched\n", stems[j].c_str(), (unsigned long long)seqs_m[j],
@@ -3236,6 +3283,11 @@ int run_classify(const ClassifyArgs &a) {
                 std::fprintf(stderr, "%s: %llu/%llu (%.3f%%) index minimizers observed\n", stems[j].c_str(),
                              (unsigned long long)observed[j], (unsigned long long)set_keys[j],
                              prop(observed[j], set_keys[j]) * 100.0);
+        if (a.depth)
+            for (uint32_t j = 0; j < n; ++j)
+                std::fprintf(stderr, "%s: depth mean %.2f, median %s over %llu index minimizers seen (%llu saturated)\n",
+                             stems[j].c_str(), prop(d_sum[j], d_observed[j]), d_median[j].c_str(),
+                             (unsigned long long)d_observed[j], (unsigned long long)d_saturated[j]);
         std::fprintf(stderr, "Classified %llu sequences (%llu bp) against %u indexes in %s\n", (unsigned long long)seqs_in,
                      (unsigned long long)bp_in, n, fmt_duration(secs).c_str());
     }
@@ -3258,6 +3310,13 @@ int run_classify(const ClassifyArgs &a) {
             if (a.coverage) {
                 std::snprintf(buf, sizeof buf, ", \"keys_observed\": %llu, \"keys_observed_proportion\": %.17g",
                               (unsigned long long)observed[j], prop(observed[j], set_keys[j]));
+                js += buf;
+            }
+            if (a.depth) {
+                std::snprintf(buf, sizeof buf, ", \"depth\": {\"observed\": %llu, \"sum\": %llu, \"mean\": %.17g, \"median\": %s, "
+                                               "\"saturated\": %llu}",
+                              (unsigned long long)d_observed[j], (unsigned long long)d_sum[j], prop(d_sum[j], d_observed[j]),
+                              d_median[j].c_str(), (unsigned long long)d_saturated[j]);
                 js += buf;
             }
             js += "}";
@@ -3538,6 +3597,10 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "  -p, --prefix-length <N>        Search only the first N nucleotides per sequence (0 = entire sequence) [default: 0]\n"
                "      --per-read <PATH>          One TSV row per record or pair (- for stdout): id, length, minimizers, hits per index, matched\n"
                "      --coverage                 Also report how many distinct minimizers of each index the input observed\n"
+               "      --depth                    Also report how often: per index the observed minimizers, the sum, mean and median\n"
+               "                                 of their occurrence counts (each saturating at 65535; median \">=4095\" past that)\n"
+               "      --depth-hist <PATH>        TSV of index, depth, keys: minimizers of each index by occurrence count, 256 bins\n"
+               "                                 (depth 0 = not observed, the last row \">=255\"; non-empty bins only; implies --depth)\n"
                "  -s, --summary <SUMMARY>        Path to JSON summary output file\n"
                "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
                "  -q, --quiet                    Suppress progress reporting\n"
@@ -3723,6 +3786,8 @@ int main(int argc, char **argv) {
                 else if (s == "--per-read") a.per_read = need(++i), a.has_per_read = true;
                 else if (s == "-s" || s == "--summary") a.summary = need(++i), a.has_summary = true;
                 else if (s == "--coverage") a.coverage = true;
+                else if (s == "--depth") a.depth = true;
+                else if (s == "--depth-hist") a.depth_hist = need(++i), a.has_depth_hist = true, a.depth = true;
                 else if (s == "-t" || s == "--threads") ++i;
                 else if (s == "-q" || s == "--quiet") a.quiet = true;
                 else if (s.size() > 1 && s[0] == '-' && s != "-") die("unexpected argument '" + s + "'");

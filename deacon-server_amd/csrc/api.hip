@@ -434,6 +434,8 @@ extern "C" int dcn_index_clone(const dcn_index *index, int device, dcn_index **o
     idx->zero_label = 0;
     idx->d_cov = nullptr; // ... without coverage
     idx->cov_words = 0;
+    idx->d_depth = nullptr; // ... and without depth counters
+    idx->depth_words = 0;
     const uint64_t bytes = idx->n_groups * DCN_GROUP_SLOTS * sizeof(uint64_t);
     // Another GPU: the keys cross the link, not the table (a tenth of the bytes at the default 8 slots per key; dcn_table_clone_by_keys).
     // The same GPU: a device-to-device copy of the table at HBM's pace.  DCN_CLONE_BY_KEYS=1 / DCN_CLONE_BY_COPY=1 force one form
@@ -484,6 +486,7 @@ extern "C" void dcn_index_destroy(dcn_index *index) {
     if (index->d_slots) hipFree(index->d_slots);
     if (index->d_labels) hipFree(index->d_labels);
     if (index->d_cov) hipFree(index->d_cov);
+    if (index->d_depth) hipFree(index->d_depth);
     delete index;
 }
 

@@ -46,22 +46,9 @@ __device__ inline uint32_t set_label_from(const dcn_classify_args &a, uint64_t k
     }
 }
 
-// slot index of `key` (non-zero) in the set, ~0 when it is in no member
+// slot index of `key` (non-zero) in the set, ~0 when it is in no member (the walk is dcn_probe.h's, shared with depth.hip)
 __device__ inline uint64_t set_find_slot(const dcn_classify_args &a, uint64_t key, uint32_t g, dcn_group grp) {
-    for (;;) {
-        const uint64_t s0 = (uint64_t)g * DCN_GROUP_SLOTS;
-        if (grp.a.x == key) return s0;
-        if (grp.a.y == key) return s0 + 1;
-#if DCN_GROUP_SLOTS == 4
-        if (grp.b.x == key) return s0 + 2;
-        if (grp.b.y == key) return s0 + 3;
-        if (grp.a.x == 0 || grp.a.y == 0 || grp.b.x == 0 || grp.b.y == 0) return ~0ull;
-#else
-        if (grp.a.x == 0 || grp.a.y == 0) return ~0ull;
-#endif
-        g = (g + 1) & a.table.group_mask;
-        grp = dcn_load_group(a.table, g);
-    }
+    return dcn_table_find_slot(a.table, key, g, grp);
 }
 
 __device__ inline uint32_t set_label(const dcn_classify_args &a, uint64_t key) {

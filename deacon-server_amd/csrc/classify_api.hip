@@ -2,6 +2,7 @@
 // against a set (the kernels are in classify.hip; the batch runs pack -> plan -> scan in dump mode on a filter context).
 #include "dcn_ctx.h"
 #include "dcn_classify.h"
+#include "dcn_depth.h"
 
 #include <cstring>
 
@@ -72,23 +73,11 @@ int check_coverage(const dcn_index *set) {
     return DCN_OK;
 }
 
-int hip_fail(hipError_t e, const char *what) {
-    return dcn_fail(e == hipErrorOutOfMemory ? DCN_ERR_NOMEM : DCN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 // counts[0..n) of a coverage_count pass (all_slots: every occupied slot; else the marked ones), key 0 not included
 int coverage_counts(const dcn_index *set, bool all_slots, uint64_t *counts) {
-    unsigned long long *d = nullptr;
-    hipError_t e = hipMalloc((void **)&d, DCN_MAX_SET_MEMBERS * sizeof(unsigned long long));
-    if (e != hipSuccess) return hip_fail(e, "coverage");
-    int rc = DCN_OK;
-    e = hipMemset(d, 0, DCN_MAX_SET_MEMBERS * sizeof(unsigned long long));
-    if (e == hipSuccess) rc = dcn_coverage_count(set, all_slots, d, 0);
     unsigned long long h[DCN_MAX_SET_MEMBERS] = {};
-    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-    hipFree(d);
-    if (rc != DCN_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "coverage");
+    DCN_TRY(dcn_device_tally(DCN_MAX_SET_MEMBERS, h, "coverage",
+                             [&](unsigned long long *d) { return dcn_coverage_count(set, all_slots, d, 0); }));
     for (uint32_t j = 0; j < set->n_members; ++j) counts[j] = h[j];
     return DCN_OK;
 }
@@ -96,7 +85,7 @@ int coverage_counts(const dcn_index *set, bool all_slots, uint64_t *counts) {
 bool zero_observed(const dcn_index *set, int *rc) {
     uint32_t w = 0;
     const hipError_t e = hipMemcpy(&w, set->d_cov + set->cov_words, sizeof(w), hipMemcpyDeviceToHost);
-    *rc = e == hipSuccess ? DCN_OK : hip_fail(e, "coverage");
+    *rc = e == hipSuccess ? DCN_OK : dcn_hip_fail(e, "coverage");
     return (w & 1u) != 0;
 }
 } // namespace
@@ -114,12 +103,12 @@ extern "C" int dcn_index_set_coverage_enable(dcn_index *set, int enable) {
     const uint64_t words = (set->n_groups * DCN_GROUP_SLOTS + 31) / 32;
     uint32_t *d = nullptr;
     hipError_t e = hipMalloc((void **)&d, (words + 1) * sizeof(uint32_t));
-    if (e != hipSuccess) return hip_fail(e, "coverage bitmap");
+    if (e != hipSuccess) return dcn_hip_fail(e, "coverage bitmap");
     e = hipMemset(d, 0, (words + 1) * sizeof(uint32_t));
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) {
         hipFree(d);
-        return hip_fail(e, "coverage bitmap");
+        return dcn_hip_fail(e, "coverage bitmap");
     }
     set->d_cov = d;
     set->cov_words = words;
@@ -193,7 +182,7 @@ extern "C" int dcn_index_set_coverage_keys(const dcn_index *set, uint32_t member
     if (d_out) hipFree(d_out);
     hipFree(d_n);
     if (rc != DCN_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "coverage keys");
+    if (e != hipSuccess) return dcn_hip_fail(e, "coverage keys");
     *n = total;
     if (total > capacity)
         return dcn_fail(DCN_ERR_CAPACITY, "coverage keys: " + std::to_string(total) + " observed keys, capacity " +
@@ -219,8 +208,11 @@ int classify_check(dcn_ctx *ctx, const dcn_index *set, const dcn_params *params)
 }
 
 // the lazily allocated buffers of classification: the dump arrays, the work list and (host form) the outputs
-int classify_buffers(dcn_ctx *c, uint32_t n_members, bool host_outputs) {
+int classify_buffers(dcn_ctx *c, const dcn_index *set, bool host_outputs) {
+    const uint32_t n_members = set->n_members;
     DCN_TRY(ensure_dump_buffers(c));
+    // depth: the batch's position bitmap (locate's, which allocates it the same way)
+    if (set->d_depth && !c->d_loc_bits) DCN_TRY(dev_alloc(&c->d_loc_bits, (c->max_bases + 31) / 32 + 1, "position bitmap"));
     if (!c->d_cls_big) {
         DCN_TRY(dev_alloc(&c->d_cls_big, c->max_reads, "classify work list"));
         DCN_TRY(dev_alloc(&c->d_cls_n_big, 1, "classify work list length"));
@@ -262,9 +254,28 @@ int classify_enqueue(dcn_ctx *c, const dcn_index *set, const uint8_t *d_ascii, c
     DCN_TRY(dcn_launch_plan(pa, st));
     DCN_PROF_MARK(DCN_STAGE_PLAN);
     dcn_scan_args sa = dump_scan_args(c, set, n_bases);
-    sa.dump_abs = 1; // (positions are not looked at)
+    sa.dump_abs = 1; // (the classification kernels do not look at positions; the depth sweep does)
     DCN_TRY(dcn_launch_scan(sa, tile_bound(c, n_reads, n_bases), true, st));
     DCN_PROF_MARK(DCN_STAGE_SCAN);
+    if (set->d_depth) { // the counting sweep of depth.hip, timed with the lane kernel (no stage of its own: DCN_N_STAGES is ABI)
+        DCN_HIP(hipMemsetAsync(c->d_loc_bits, 0, ((n_bases + 31) / 32 + 1) * sizeof(uint32_t), st));
+        dcn_depth_args da;
+        memset(&da, 0, sizeof(da));
+        da.table = set->view();
+        da.tiles = c->d_tiles;
+        da.n_tiles = &c->d_status->n_tiles;
+        da.dump_hash = c->d_dump_hash;
+        da.dump_valid = c->d_dump_valid;
+        da.dump_pos = c->d_dump_pos;
+        da.dump_count = c->d_dump_count;
+        da.max_tiles = tile_bound(c, n_reads, n_bases);
+        da.n_bases = n_bases;
+        da.status = c->d_status;
+        da.bits = c->d_loc_bits;
+        da.depth = set->d_depth;
+        da.depth_zero = set->has_zero ? set->d_depth + set->depth_words : nullptr;
+        DCN_TRY(dcn_launch_depth_count(da, st));
+    }
     dcn_classify_args ca;
     memset(&ca, 0, sizeof(ca));
     ca.table = set->view();
@@ -328,7 +339,7 @@ extern "C" int dcn_classify_batch(dcn_ctx *ctx, const dcn_index *set, const uint
     if (n_bases > 0 && !bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
     dcn_ctx *c = ctx;
     DCN_HIP(hipSetDevice(c->device));
-    DCN_TRY(classify_buffers(c, set->n_members, true));
+    DCN_TRY(classify_buffers(c, set, true));
     DCN_TRY(stage_batch(c, bases, n_bases, offsets, n_reads, unit_id));
     DCN_TRY(classify_enqueue(c, set, c->d_ascii, c->d_offsets, unit_id ? c->d_unit_id : nullptr, n_reads, n_bases, n_units,
                              params, c->d_cls_match, c->d_cls_hits, c->d_cls_total));
@@ -349,7 +360,7 @@ extern "C" int dcn_classify_batch_device(dcn_ctx *ctx, const dcn_index *set, con
     if (!d_bases || !d_offsets || !d_match) return dcn_fail(DCN_ERR_ARG, "d_bases/d_offsets/d_match is NULL");
     DCN_TRY(check_device_batch(ctx, n_reads, n_bases, n_units, d_unit_id));
     DCN_HIP(hipSetDevice(ctx->device));
-    DCN_TRY(classify_buffers(ctx, set->n_members, false));
+    DCN_TRY(classify_buffers(ctx, set, false));
     return classify_enqueue(ctx, set, d_bases, d_offsets, d_unit_id, n_reads, n_bases, n_units, params, d_match, d_hits,
                             d_total);
 }

@@ -22,6 +22,27 @@ int dcn_fail(int code, const std::string &msg);
                             std::string(#expr) + ": " + hipGetErrorString(_e));                    \
     } while (0)
 
+// a failed HIP call of the read-outs, as an error code with `what` in front of HIP's message
+inline int dcn_hip_fail(hipError_t e, const char *what) {
+    return dcn_fail(e == hipErrorOutOfMemory ? DCN_ERR_NOMEM : DCN_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// `count` zeroed unsigned long longs on the device, `sweep(d)` run on them, then copied back into h: the tallies of the
+// coverage and depth read-outs
+template <typename F>
+int dcn_device_tally(uint64_t count, unsigned long long *h, const char *what, F sweep) {
+    unsigned long long *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, count * sizeof(unsigned long long));
+    if (e != hipSuccess) return dcn_hip_fail(e, what);
+    int rc = DCN_OK;
+    e = hipMemset(d, 0, count * sizeof(unsigned long long));
+    if (e == hipSuccess) rc = sweep(d);
+    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(h, d, count * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    hipFree(d);
+    if (rc != DCN_OK) return rc;
+    return e == hipSuccess ? DCN_OK : dcn_hip_fail(e, what);
+}
+
 // memcpy on the host pool's threads (api.hip): large copies into memory nobody has touched yet are first-touch bound on one thread
 void dcn_host_parallel_copy(void *dst, const void *src, size_t n);
 
@@ -75,6 +96,11 @@ struct dcn_index {
     uint32_t *d_cov = nullptr;
     uint64_t cov_words = 0;
     uint64_t cov_keys[32] = {};
+    // depth of a set (dcn_index_set_depth_enable, depth.hip): how often each key occurred among the counted minimizers.
+    // depth_words u32 words of two saturating 16-bit counters each (slot s: word s >> 1, half s & 1), then key 0's word.
+    // 2 B per slot: 8 GiB at the panhuman-sized set (2^31 groups of 2 slots).
+    uint32_t *d_depth = nullptr;
+    uint64_t depth_words = 0;
     dcn_table_view view() const {
         dcn_table_view v;
         v.slots = d_slots;

@@ -51,6 +51,25 @@ __device__ inline bool dcn_table_contains_dev(const dcn_table_view &t, uint64_t 
     }
 }
 
+// slot index of `key` (non-zero) whose home group g has been loaded into grp, ~0 when the table does not hold it (the
+// classification kernels' walk: a caller with several probes in flight loads their home groups first)
+__device__ inline uint64_t dcn_table_find_slot(const dcn_table_view &t, uint64_t key, uint32_t g, dcn_group grp) {
+    for (;;) {
+        const uint64_t s0 = (uint64_t)g * DCN_GROUP_SLOTS;
+        if (grp.a.x == key) return s0;
+        if (grp.a.y == key) return s0 + 1;
+#if DCN_GROUP_SLOTS == 4
+        if (grp.b.x == key) return s0 + 2;
+        if (grp.b.y == key) return s0 + 3;
+        if (grp.a.x == 0 || grp.a.y == 0 || grp.b.x == 0 || grp.b.y == 0) return ~0ull;
+#else
+        if (grp.a.x == 0 || grp.a.y == 0) return ~0ull;
+#endif
+        g = (g + 1) & t.group_mask;
+        grp = dcn_load_group(t, g);
+    }
+}
+
 // ---- XXH3-64, seed 0, 8-byte and 16-byte inputs (xxh3_64(&kmer.to_le_bytes()),
 //      src/filter_common.rs:296,305) -------------------------------------------------------------------
 __device__ inline uint64_t dcn_rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }

@@ -29,8 +29,9 @@ int locate_check(dcn_ctx *ctx, const dcn_index *index, const dcn_locate_params *
 
 int locate_buffers(dcn_ctx *c, bool labelled) {
     DCN_TRY(ensure_dump_buffers(c));
-    if (!c->d_loc_bits) {
-        DCN_TRY(dev_alloc(&c->d_loc_bits, (c->max_bases + 31) / 32 + 1, "locate hit bitmap"));
+    // (the bitmap alone may be there already: a classify call against a set with depth counters uses it too)
+    if (!c->d_loc_bits) DCN_TRY(dev_alloc(&c->d_loc_bits, (c->max_bases + 31) / 32 + 1, "locate hit bitmap"));
+    if (!c->d_loc_counts) {
         DCN_TRY(dev_alloc(&c->d_loc_counts, c->max_reads, "locate counts"));
         DCN_TRY(dev_alloc(&c->d_loc_block_sums, (uint64_t)c->max_reads / DCN_LOC_SCAN_BLOCK + 1, "locate block sums"));
         DCN_TRY(dev_alloc(&c->d_loc_seg_offsets, (uint64_t)c->max_reads + 1, "locate segment offsets"));

@@ -283,6 +283,47 @@ class IndexSet:
         N.check(N.lib().dcn_index_set_coverage_keys(self._h, m, _ptr(out), len(out), C.byref(n)))
         return out[:n.value]
 
+    # ---- depth (dcn_index_set_depth_*): how often each key occurred among the minimizers classify calls counted ----
+    def enable_depth(self, on=True):
+        """Allocate zeroed 16-bit counters, one per slot (on), or free them (off); every later classify call against the
+        set, from any Classifier, adds its occurrences (saturating at 65,535).  Enabling twice keeps the counts."""
+        N.check(N.lib().dcn_index_set_depth_enable(self._h, 1 if on else 0))
+
+    def reset_depth(self):
+        N.check(N.lib().dcn_index_set_depth_reset(self._h))
+
+    def depth_stats(self):
+        """{"observed", "sum", "saturated"}: np.uint64[n] each, over member j's keys -- keys with depth > 0, the sum of
+        their depths, keys at 65,535.  Device-form batches must have been synchronized first."""
+        out = {name: np.zeros(self.n, np.uint64) for name in ("observed", "sum", "saturated")}
+        N.check(N.lib().dcn_index_set_depth_stats(self._h, _ptr(out["observed"]), _ptr(out["sum"]), _ptr(out["saturated"])))
+        return out
+
+    def depth_hist(self, member=None, n_bins=256):
+        """np.uint64[n_bins]: keys of member `member` (None: of any member) by depth, the last bin holding every depth
+        >= n_bins - 1 and bin 0 the unobserved keys"""
+        m = 0xFFFFFFFF if member is None else int(member)
+        if not 0 <= m <= 0xFFFFFFFF or not 0 <= int(n_bins) <= 0xFFFFFFFF:
+            raise ValueError(f"member {member} / n_bins {n_bins} out of range")
+        hist = np.zeros(max(int(n_bins), 1), np.uint64)
+        N.check(N.lib().dcn_index_set_depth_hist(self._h, m, int(n_bins), _ptr(hist)))
+        return hist
+
+    def depth_keys(self, member=None):
+        """(keys np.uint64, depths np.uint32) of the keys of member `member` (None: of any member) with depth > 0, in no
+        particular order"""
+        m = 0xFFFFFFFF if member is None else int(member)
+        if not 0 <= m <= 0xFFFFFFFF:
+            raise ValueError(f"member {member} out of range")
+        n = C.c_uint64()
+        rc = N.lib().dcn_index_set_depth_keys(self._h, m, None, None, 0, C.byref(n))
+        if rc != N.DCN_ERR_CAPACITY:
+            N.check(rc)
+        keys = np.zeros(max(n.value, 1), np.uint64)
+        depths = np.zeros(max(n.value, 1), np.uint32)
+        N.check(N.lib().dcn_index_set_depth_keys(self._h, m, _ptr(keys), _ptr(depths), len(keys), C.byref(n)))
+        return keys[:n.value], depths[:n.value]
+
     # ---- set algebra on the member masks (dcn_index_set_select / dcn_index_set_overlap) ----
     def __len__(self):
         return self.n_keys

@@ -68,9 +68,10 @@ enum {
  * when entry points are added.  History: 0.x = the headers before versioning (dcn_pack_ascii took four arguments there);
  * 1.0 = dcn_pack_ascii(bases, n_bases, packed, invmask, saw_newline); 1.1 = dcn_abi_version, dcn_comm_* / dcn_stats_allreduce_rccl;
  * 1.2 = dcn_index_set_* / dcn_classify_batch*; 1.3 = dcn_index_set_coverage*; 1.4 = dcn_locate_batch;
- * 1.5 = dcn_index_set_select / _overlap, dcn_index_intersect. */
+ * 1.5 = dcn_index_set_select / _overlap, dcn_index_intersect;
+ * 1.6 = dcn_index_set_depth_enable / _reset / _stats / _hist / _keys. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 5
+#define DCN_ABI_MINOR 6
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -384,6 +385,38 @@ int dcn_index_set_coverage(const dcn_index *set, uint64_t *observed, uint64_t *k
 /* observed keys of member `member` (UINT32_MAX = of any member), arbitrary order; *n = count; DCN_ERR_CAPACITY if
  * capacity < count (out may be NULL with capacity 0: *n still receives the count) */
 int dcn_index_set_coverage_keys(const dcn_index *set, uint32_t member, uint64_t *out, uint64_t capacity, uint64_t *n);
+
+/* ---- depth: how often each key of a set occurred in the input ------------------------------------------------------
+ * (no reference counterpart.)  Coverage says that a member's keys were touched; depth says how often.  An OCCURRENCE is
+ * one (read, position) pair of a batch whose minimizer k-mer is counted in its unit's total[u] -- after
+ * params->prefix_length and the ACGT filter, each position of a read once, mates of a pair independently.  The DEPTH of
+ * key K is the number of occurrences whose hash is K, over all dcn_classify_batch / dcn_classify_batch_device calls
+ * against the set, from any context, since depth was enabled or last reset.  It is held per slot of the set's table as a
+ * 16-bit counter that SATURATES at 65,535; it does not depend on the thresholds, on match[], or on the unit's size; a
+ * batch the plan refuses (bad offsets) counts nothing.  Depth and coverage are independent (either, both or neither);
+ * with both on over the same calls a key has depth > 0 exactly when it is observed.  Key 0 has a counter of its own.
+ * The state costs 2 bytes per slot of the set's table (1/4 of its slot bytes: 8 GiB for a set of 2^32 slots) and belongs
+ * to the set like the coverage bitmap: dcn_index_set_create allocates none, dcn_index_set_info / dcn_index_memory do not
+ * count it, a dcn_index_clone has none, dcn_index_destroy frees it.  A context that classifies against a set with depth
+ * also holds max_batch_bases / 8 bytes of position bitmap (shared with dcn_locate_batch).
+ * The reads below are blocking and order after nothing: the caller has waited for its classify calls first.  Every call
+ * returns DCN_ERR_ARG -- before any device work -- for an index that is not a set, a NULL output, a member at or above
+ * the set's member count (UINT32_MAX = any member), n_bins outside 2..4096, and (all but enable) a set without depth. */
+/* allocate (enable != 0) zeroed counters for the set, or free them (0); not while classify calls on the set are in
+ * flight.  Enabling a set that has depth keeps its counts.  DCN_ERR_NOMEM leaves the set as it was. */
+int dcn_index_set_depth_enable(dcn_index *set, int enable);
+/* zero every counter */
+int dcn_index_set_depth_reset(dcn_index *set);
+/* n_members entries each, over the keys of member j: observed[j] = keys with depth > 0, sum[j] = the sum of their depths
+ * (saturated counters add 65,535), saturated[j] = keys at 65,535 */
+int dcn_index_set_depth_stats(const dcn_index *set, uint64_t *observed, uint64_t *sum, uint64_t *saturated);
+/* hist[min(depth, n_bins - 1)] = keys of member `member` (UINT32_MAX: of any member) at that depth, n_bins entries,
+ * 2 <= n_bins <= 4096; hist[0] = its unobserved keys, so the entries sum to the member's key count */
+int dcn_index_set_depth_hist(const dcn_index *set, uint32_t member, uint32_t n_bins, uint64_t *hist);
+/* (key, depth) of every key of member `member` (UINT32_MAX: any) with depth > 0, arbitrary order; *n = count;
+ * DCN_ERR_CAPACITY if capacity < count (keys / depths may be NULL with capacity 0: *n still receives the count) */
+int dcn_index_set_depth_keys(const dcn_index *set, uint32_t member, uint64_t *keys, uint32_t *depths, uint64_t capacity,
+                             uint64_t *n);
 
 /* ---- locate: where in each read the index matched ----------------------------------------------------------
  * (no reference counterpart: the reference answers one verdict per record.)  Segments of every read of a host batch,
