@@ -142,11 +142,18 @@ _SIGNATURES = {
     "dcn_index_set_select": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p,
                                        C.POINTER(_vp)]),
     "dcn_index_set_overlap": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "dcn_index_builder_create": (C.c_int, [C.c_uint8, C.c_uint8, C.c_float, C.c_uint64, C.c_int, C.POINTER(_vp)]),
+    "dcn_index_builder_add": (C.c_int, [_vp, _vp, _vp, C.c_uint32]),
+    "dcn_index_builder_info": (C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p]),
+    "dcn_index_builder_hist": (C.c_int, [_vp, C.c_uint32, _vp]),
+    "dcn_index_builder_counts": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u64p]),
+    "dcn_index_builder_finish": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _u64p, C.POINTER(_vp)]),
+    "dcn_index_builder_destroy": (None, [_vp]),
     "dcn_locate_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64]),
 }
 
 _lib = None
-ABI = (1, 6)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 7)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

@@ -2,6 +2,7 @@
 // repository accelerates:
 //
 //   deacon-hip index build <fastx> [-k 31] [-w 15] [-o out.idx] [-c capacity_millions] [-e entropy] [-q]
+//                          [--min-count N] [--max-count N] [--count-hist FILE]
 //   deacon-hip index info  <index>
 //   deacon-hip index union <index>... [-o out.idx]
 //   deacon-hip index diff  <first.idx> <second.idx | fastx> [-k K -w W] [-o out.idx]
@@ -2839,6 +2840,72 @@ int run_index_build(const std::string &input, unsigned k, unsigned w, const std:
     return 0;
 }
 
+// `index build` with --min-count / --max-count / --count-hist: the input goes through the record reader batch by batch into a
+// counting builder (dcn_index_builder_*), and the index written is the builder's selection by count
+int run_index_build_counted(const std::string &input, unsigned k, unsigned w, const std::string &output, float entropy, bool quiet, uint32_t min_count, uint32_t max_count, const std::string &count_hist) {
+    auto start = std::chrono::steady_clock::now();
+    // (-c is a pre-allocation hint the plain build caps by the input's size; here the input is not known in advance and the
+    // builder's table grows as needed, so the flag is accepted and not used)
+    std::fprintf(stderr, "Deacon-hip v%s; mode: build; input: single; options: capacity=as needed, min_count=%u, max_count=%u\n", VERSION,
+                 std::max(min_count, 1u), max_count);
+    if ((k + w - 1) % 2 == 0)
+        die("Constraint violated: k + w - 1 must be odd (k=" + std::to_string(k) + ", w=" + std::to_string(w) + ")");
+    std::fprintf(stderr, "Building index (k=%u, w=%u)\n", k, w);
+    uint64_t batch_bases = 256ull << 20;
+    if (const char *e = std::getenv("DCN_CLI_BUILD_BATCH_BASES")) batch_bases = (uint64_t)std::max(64, std::atoi(e)); // test hook: many batches
+    const size_t batch_reads = 1u << 22;
+    deacon::IndexBuilder builder((uint8_t)k, (uint8_t)w, entropy, 0, 0);
+    FastxReader rd(input);
+    Batch b;
+    uint64_t n_seqs = 0;
+    auto run_batch = [&]() {
+        if (b.recs.empty()) return;
+        builder.add(b.bases.data(), b.offsets.data(), (uint32_t)b.recs.size());
+        n_seqs += b.recs.size();
+        b.clear();
+    };
+    while (rd.next(b)) {
+        if (!quiet) {
+            const Rec &r = b.recs.back();
+            std::fprintf(stderr, "  %.*s (%ubp)\n", (int)r.id_len, b.chars() + r.id_off, r.seq_len);
+        }
+        if (b.offsets.back() >= batch_bases || b.recs.size() >= batch_reads) run_batch();
+    }
+    run_batch();
+    const deacon::IndexBuilder::Info info = builder.info();
+    const uint32_t lo = std::max(min_count, 1u);
+    const uint64_t below = lo > 1 ? builder.count(1, lo - 1) : 0, above = max_count && max_count < 65535 ? builder.count(max_count + 1, 0) : 0;
+    deacon::Index idx = builder.finish(lo, max_count);
+    std::fprintf(stderr, "Counted %llu minimizers (%llu occurrences) from %llu sequence(s) (%llubp): kept %llu, dropped %llu below --min-count, %llu above --max-count\n",
+                 (unsigned long long)info.n_keys, (unsigned long long)info.n_occurrences, (unsigned long long)n_seqs,
+                 (unsigned long long)info.n_bases, (unsigned long long)idx.len(), (unsigned long long)below, (unsigned long long)above);
+    if (!count_hist.empty()) {
+        const std::vector<uint64_t> h = builder.hist(4096);
+        // bins 1..4094 are exact; the tail comes from the exported counts only when some key reaches it
+        std::vector<uint64_t> tail;
+        if (h[4095]) {
+            std::vector<uint64_t> keys(info.n_keys);
+            std::vector<uint32_t> counts(info.n_keys);
+            uint64_t n = 0;
+            deacon::check(dcn_index_builder_counts(builder.raw(), keys.data(), counts.data(), info.n_keys, &n));
+            tail.assign(65536, 0);
+            for (uint64_t i = 0; i < n; ++i)
+                if (counts[i] >= 4095) tail[counts[i]]++;
+        }
+        FILE *f = count_hist == "-" ? stdout : std::fopen(count_hist.c_str(), "w");
+        if (!f) die("cannot open " + count_hist + " for writing");
+        for (uint32_t c = 1; c < 4095; ++c)
+            if (h[c]) std::fprintf(f, "%u\t%llu\n", c, (unsigned long long)h[c]);
+        for (size_t c = 4095; c < tail.size(); ++c)
+            if (tail[c]) std::fprintf(f, "%zu\t%llu\n", c, (unsigned long long)tail[c]);
+        if (std::ferror(f) || (f != stdout ? std::fclose(f) : std::fflush(f)) != 0) die("Failed to write the count histogram: " + count_hist);
+    }
+    deacon::check(dcn_index_write_file(idx.raw(), (output == "-" ? std::string("/dev/stdout") : output).c_str()));
+    std::fprintf(stderr, "Completed in %s\n",
+                 fmt_duration(std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count()).c_str());
+    return 0;
+}
+
 int run_index_info(const std::string &path) {
     auto start = std::chrono::steady_clock::now();
     deacon::Index idx = deacon::Index::load(path);
@@ -3635,7 +3702,16 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "  -t, --threads <THREADS>        Accepted for compatibility (the scan runs on the GPU)\n"
                "  -q, --quiet                    Suppress sequence header output\n"
                "  -e, --entropy-threshold <F>    Minimum scaled entropy threshold for k-mer filtering (0.0-1.0) [default: 0.0]\n"
-               "  -h, --help                     Print help\n";
+               "      --min-count <N>            Keep only minimizers that occur at least N times in the input (1-65535): for an\n"
+               "                                 index built from reads, 2 drops the keys that sequencing errors mint\n"
+               "      --max-count <N>            Keep only minimizers that occur at most N times (1-65535): drops repeats\n"
+               "      --count-hist <FILE>        Write the histogram of occurrences as count<TAB>keys lines (- for stdout; the\n"
+               "                                 last line, 65535, holds every key that occurred at least that often)\n"
+               "  -h, --help                     Print help\n\n"
+               "With any of the last three the input is read batch by batch (host memory is bounded by the batch, not by the\n"
+               "input) and occurrences are counted on the GPU: distinct (sequence, position) pairs of the minimizers the index\n"
+               "side selects.  --count-hist alone keeps every minimizer.  -c is accepted and not used then: the table grows\n"
+               "as needed.\n";
     else if (sub == "index info")
         text = "Show index information\n\nUsage: deacon-hip index info <INDEX>\n\nArguments:\n  <INDEX>  Path to index file\n";
     else if (sub == "index union")
@@ -3987,7 +4063,16 @@ int main(int argc, char **argv) {
             unsigned k = deacon::DEFAULT_KMER_LENGTH, w = deacon::DEFAULT_WINDOW_SIZE;
             size_t cap = 400;
             float entropy = 0.0f;
-            bool quiet = false;
+            bool quiet = false, counted = false;
+            uint32_t min_count = 0, max_count = 0;
+            std::string count_hist;
+            auto count_arg = [&](const std::string &name, const std::string &v) {
+                char *end = nullptr;
+                const long n = std::strtol(v.c_str(), &end, 10);
+                if (v.empty() || *end || n < 1 || n > 65535) die("invalid value '" + v + "' for " + name + ": 1 to 65535");
+                counted = true;
+                return (uint32_t)n;
+            };
             for (size_t i = 2; i < args.size(); ++i) {
                 const std::string &s = args[i];
                 if (s == "-k") k = (unsigned)std::atoi(need(++i).c_str());
@@ -3997,11 +4082,16 @@ int main(int argc, char **argv) {
                 else if (s == "-t" || s == "--threads") ++i;
                 else if (s == "-q" || s == "--quiet") quiet = true;
                 else if (s == "-e" || s == "--entropy-threshold") entropy = (float)std::atof(need(++i).c_str());
+                else if (s == "--min-count") min_count = count_arg(s, need(++i));
+                else if (s == "--max-count") max_count = count_arg(s, need(++i));
+                else if (s == "--count-hist") count_hist = need(++i), counted = true;
                 else if (s.size() > 1 && s[0] == '-') die("unexpected argument '" + s + "'");
                 else input = s;
             }
             if (input.empty()) die("the following required arguments were not provided: <INPUT>");
             if (k < 1 || k > 57) die("invalid value for -k: 1..=57");
+            if (max_count && min_count > max_count) die("--min-count " + std::to_string(min_count) + " is above --max-count " + std::to_string(max_count));
+            if (counted) return run_index_build_counted(input, k, w, output, entropy, quiet, min_count, max_count, count_hist);
             return run_index_build(input, k, w, output, cap, entropy, quiet);
         }
         if (args[0] == "index" && args.size() >= 3 && args[1] == "info") return run_index_info(args[2]);

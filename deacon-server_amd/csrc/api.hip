@@ -58,7 +58,7 @@ extern "C" int dcn_device_count(int *count) {
 // ----------------------------------------------------------------------------------------------------
 int dcn_read_index_file(const char *path, uint8_t *k, uint8_t *w, std::vector<uint64_t> *keys); // index_file.cpp
 
-static int check_kw(uint8_t k, uint8_t w) {
+int dcn_impl::check_kw(uint8_t k, uint8_t w) {
     if (k < 1 || k > 56) return dcn_fail(DCN_ERR_ARG, "k must be in 1..=56 (src/filter_common.rs:269-272)");
     if (w < 1) return dcn_fail(DCN_ERR_ARG, "w must be >= 1");
     if (((uint32_t)k + w - 1) % 2 == 0)
@@ -70,6 +70,8 @@ static int check_kw(uint8_t k, uint8_t w) {
         return dcn_fail(DCN_ERR_ARG, "minimizer variant: w <= 128 under a non-default rule (dcn_set_minimizer_variant)");
     return DCN_OK;
 }
+
+using dcn_impl::check_kw;
 
 // the end of every entry point that makes an index: hand it over, or release it with the error
 static int publish_index(int rc, dcn_index *idx, dcn_index **out) {

@@ -8,6 +8,7 @@
 #include "dcn_plan.h"
 
 #include <algorithm>
+#include <functional>
 #include <vector>
 
 // One pipeline step of a host batch: reads [r0, r1) = units [u0, u1) = bases [b0, b1) of the batch stream.
@@ -209,6 +210,23 @@ struct BatchView {
 
 // ---- api.hip ----
 int same_params(const dcn_index *a, const dcn_index *b); // k, w, device and minimizer rule agree (else DCN_ERR_ARG)
+int check_kw(uint8_t k, uint8_t w);                      // the k / w rule every index is made under (else DCN_ERR_ARG)
+
+// ---- dump.hip: the chunk loop both index builds share ----
+constexpr uint32_t DCN_BUILD_MAX_PIECES = 1u << 16;
+uint64_t build_chunk_bases(); // 2^27, or DCN_BUILD_CHUNK_BASES (>= 4096)
+using build_sweep_fn = std::function<int(uint64_t nb, bool continues)>;
+// DCN_INDEX_TIMING: where a build's time goes, one stderr line when it ends.  Host seconds here; the device stages come
+// from the context's stage events (dcn_ctx_profile), the sweep -- reserve included -- in the DISTINCT slot.
+struct build_times {
+    double front_end_s = 0, staging_s = 0, growth_s = 0, finish_s = 0, finish_table_s = 0;
+};
+double build_now(); // seconds on a steady clock
+int build_timing_begin(dcn_ctx *c); // (turns the context's stage events on)
+int build_times_print(const char *which, dcn_ctx *c, const build_times &t);
+// times: null, or a build that runs under build_timing_begin (staging is then waited for, chunk by chunk)
+int build_run_chunks(dcn_ctx *c, const dcn_index *idx, const uint8_t *bases, const uint64_t *offsets, uint32_t n_seqs,
+                     uint64_t chunk_bases, const build_sweep_fn &sweep, build_times *times = nullptr);
 
 // ---- classify_api.hip ----
 int check_set(const dcn_index *set); // not NULL and a labelled set (else DCN_ERR_ARG)

@@ -12,6 +12,19 @@ constexpr uint32_t DCN_DEPTH_TILE_LANES = 16; // lanes per tile of the counting 
 constexpr uint32_t DCN_DEPTH_MAX = 0xFFFFu;
 constexpr uint32_t DCN_DEPTH_MAX_BINS = 4096;
 
+// +1 on the 16-bit half at `shift` of *word, saturating at DCN_DEPTH_MAX and never carrying into the other half.  A
+// saturated counter costs a load and no atomic: a key that thousands of lanes hit at once issues at most 65,535 successful
+// compare-and-swaps per reset.
+__device__ inline void dcn_depth_add(uint32_t *word, uint32_t shift) {
+    uint32_t cur = __atomic_load_n(word, __ATOMIC_RELAXED);
+    for (;;) {
+        if (((cur >> shift) & DCN_DEPTH_MAX) == DCN_DEPTH_MAX) return;
+        const uint32_t old = atomicCAS(word, cur, cur + (1u << shift));
+        if (old == cur) return;
+        cur = old;
+    }
+}
+
 // the counting sweep over the minimizer dump of a batch (scan_kernel<..., DUMP = true> with dump_abs = 1)
 struct dcn_depth_args {
     dcn_table_view table; // the set's slots

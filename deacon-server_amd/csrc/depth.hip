@@ -21,19 +21,6 @@
 
 namespace {
 
-// +1 on the 16-bit half at `shift` of *word, saturating at DCN_DEPTH_MAX and never carrying into the other half.  A
-// saturated counter costs a load and no atomic: a key that thousands of lanes hit at once issues at most 65,535 successful
-// compare-and-swaps per reset.
-__device__ inline void depth_add(uint32_t *word, uint32_t shift) {
-    uint32_t cur = __atomic_load_n(word, __ATOMIC_RELAXED);
-    for (;;) {
-        if (((cur >> shift) & DCN_DEPTH_MAX) == DCN_DEPTH_MAX) return;
-        const uint32_t old = atomicCAS(word, cur, cur + (1u << shift));
-        if (old == cur) return;
-        cur = old;
-    }
-}
-
 __global__ __launch_bounds__(DCN_DEPTH_THREADS) void depth_count_kernel(dcn_depth_args a) {
     if (a.status->bad_offsets) return; // the scan looked at no tile: the dump is not this batch's
     const uint64_t gid = (uint64_t)blockIdx.x * DCN_DEPTH_THREADS + threadIdx.x;
@@ -69,7 +56,7 @@ __global__ __launch_bounds__(DCN_DEPTH_THREADS) void depth_count_kernel(dcn_dept
         const uint32_t bit = 1u << (p & 31);
         if (*pw & bit) continue;                // (bits are only ever set during the sweep: a set bit seen is set)
         if (atomicOr(pw, bit) & bit) continue;  // another entry of this position was first
-        depth_add(word, shift);
+        dcn_depth_add(word, shift);
     }
 }
 

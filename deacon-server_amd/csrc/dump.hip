@@ -2,6 +2,8 @@
 // the minimizer dump (parity / debugging seam), the server's hash seam and the GPU index build.
 #include "dcn_ctx.h"
 
+#include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <vector>
 
@@ -150,86 +152,148 @@ extern "C" int dcn_should_keep_hashes(dcn_ctx *ctx, const uint64_t *hashes, cons
 // ----------------------------------------------------------------------------------------------------
 // index build (f1): chunks of sequence pieces -> pack (index-side codes) -> plan -> scan in dump mode -> insert
 // ----------------------------------------------------------------------------------------------------
-int dcn_build_index_impl(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seqs, float entropy_threshold,
-                         dcn_index *idx) {
-    if (n_seqs == 0) return DCN_OK;
-    if (offsets[0] != 0) return dcn_fail(DCN_ERR_ARG, "offsets[0] must be 0");
-    const uint32_t k = idx->k, l = (uint32_t)idx->k + idx->w - 1;
-    // a piece is a range of one sequence; a sequence longer than the chunk is cut into pieces overlapping by
-    // l-1 bases, which yields every window exactly once (an extra duplicate at a seam merges in the set)
+uint64_t dcn_impl::build_chunk_bases() {
     uint64_t chunk_bases = 1ull << 27;
     if (const char *cb = getenv("DCN_BUILD_CHUNK_BASES")) {
         long long v = atoll(cb);
         if (v >= 4096) chunk_bases = (uint64_t)v;
     }
-    const uint32_t max_pieces = 1u << 16;
-    dcn_ctx *c = nullptr;
-    DCN_TRY(dcn_ctx_create(idx, chunk_bases, max_pieces, &c));
-    int rc = DCN_OK;
-    auto body = [&]() -> int {
-        DCN_TRY(ensure_dump_buffers(c));
-        std::vector<uint64_t> p_off;   // offsets of the pieces inside the chunk buffer
-        std::vector<const uint8_t *> p_src;
-        std::vector<uint64_t> p_len;
-        auto run_chunk = [&]() -> int {
-            if (p_len.empty()) return DCN_OK;
-            uint32_t np = (uint32_t)p_len.size();
-            p_off.assign(np + 1, 0);
-            for (uint32_t i = 0; i < np; ++i) p_off[i + 1] = p_off[i] + p_len[i];
-            uint64_t nb = p_off[np];
-            for (uint32_t i = 0; i < np; ++i)
-                DCN_TRY(staged_h2d(c, c->d_ascii + p_off[i], p_src[i], p_len[i]));
-            DCN_TRY(staged_h2d(c, c->d_offsets, p_off.data(), (uint64_t)(np + 1) * sizeof(uint64_t)));
-            DCN_TRY(stage_done(c));
-            hipStream_t st = c->stream;
-            DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
-            DCN_HIP(hipMemsetAsync(c->d_dump_valid, 0, nb + 2, st));
-            // no status word for the pack (a newline is not looked for), the index side's code table
-            DCN_TRY(dcn_launch_pack(c->d_ascii, 0, nb, c->d_packed + DCN_FRONT_PAD, c->d_invmask + DCN_FRONT_PAD, nullptr, st,
-                                    /*index_side=*/true));
-            // (check_offsets stays 0: the pieces' offsets were made right here)
-            dcn_plan_args pa = plan_args(c, idx, c->d_ascii, c->d_offsets, nullptr, np, np, 0);
-            pa.read_tiles = c->d_read_tiles;
-            pa.read_tile_first = c->d_read_tile_first;
-            DCN_TRY(dcn_launch_plan(pa, st));
-            dcn_scan_args sa = dump_scan_args(c, idx, nb);
-            sa.dump_abs = 1; // positions in the chunk: dcn_table_insert_dump reads the bases around them
-            DCN_TRY(dcn_launch_scan(sa, tile_bound(c, np, nb), true, st));
-            uint64_t n_valid = 0;
-            DCN_TRY(dcn_table_count_valid(c->d_dump_valid, nb, &n_valid, st));
-            DCN_TRY(dcn_table_reserve(idx, idx->n_keys + n_valid));
-            DCN_TRY(dcn_table_insert_dump(idx, c->d_dump_hash, c->d_dump_valid, c->d_dump_pos, nb, c->d_ascii,
-                                          entropy_threshold, st));
-            p_src.clear();
-            p_len.clear();
-            return DCN_OK;
-        };
-        uint64_t used = 0;
-        for (uint32_t sidx = 0; sidx < n_seqs; ++sidx) {
-            if (offsets[sidx + 1] < offsets[sidx]) return dcn_fail(DCN_ERR_ARG, "offsets must be non-decreasing");
-            const uint8_t *seq = bases + offsets[sidx];
-            uint64_t len = offsets[sidx + 1] - offsets[sidx];
-            if (len < k || len < l) continue; // src/minimizers.rs:135; fewer than l bases have no window
-            uint64_t a = 0;
-            while (a + l <= len) {
-                uint64_t room = chunk_bases - used;
-                if (room < l || p_len.size() >= max_pieces) {
-                    DCN_TRY(run_chunk());
-                    used = 0;
-                    room = chunk_bases;
-                }
-                uint64_t take = std::min<uint64_t>(room, len - a);
-                if (take > 0xFFFFFF00ull) take = 0xFFFFFF00ull;
-                p_src.push_back(seq + a);
-                p_len.push_back(take);
-                used += take;
-                if (a + take >= len) break;
-                a += take - (l - 1); // next piece starts l-1 bases before the cut
-            }
+    return chunk_bases;
+}
+
+// DCN_INDEX_TIMING (dcn_ctx.h)
+double dcn_impl::build_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+int dcn_impl::build_timing_begin(dcn_ctx *c) { return dcn_ctx_set_profiling(c, 1); }
+
+int dcn_impl::build_times_print(const char *which, dcn_ctx *c, const build_times &t) {
+    double ms[DCN_N_STAGES] = {};
+    uint64_t chunks = 0;
+    DCN_TRY(dcn_ctx_profile(c, ms, &chunks));
+    fprintf(stderr,
+            "index build timing (%s): front end made %.3f s; %llu chunks: staging %.3f s, pack %.1f ms, plan %.1f ms, "
+            "scan %.1f ms, sweep %.1f ms (of it growth %.3f s); finish %.3f s (of it its table made %.3f s)\n",
+            which, t.front_end_s, (unsigned long long)chunks, t.staging_s, ms[DCN_STAGE_PACK], ms[DCN_STAGE_PLAN],
+            ms[DCN_STAGE_SCAN], ms[DCN_STAGE_DISTINCT], t.growth_s, t.finish_s, t.finish_table_s);
+    return DCN_OK;
+}
+
+// The front end of both index builds on a dump-mode context of chunk_bases bases and DCN_BUILD_MAX_PIECES reads: after
+// each chunk's scan, sweep(nb, continues) sees the chunk's dump (nb bases; dump_abs = 1) on c->stream.  `continues`: the
+// chunk's first piece continues the piece that ended the chunk before it (the same sequence, l-1 bases further back).
+int dcn_impl::build_run_chunks(dcn_ctx *c, const dcn_index *idx, const uint8_t *bases, const uint64_t *offsets, uint32_t n_seqs,
+                               uint64_t chunk_bases, const build_sweep_fn &sweep, build_times *times) {
+    if (n_seqs == 0) return DCN_OK;
+    if (offsets[0] != 0) return dcn_fail(DCN_ERR_ARG, "offsets[0] must be 0");
+    const uint32_t k = idx->k, l = (uint32_t)idx->k + idx->w - 1;
+    // a piece is a range of one sequence; a sequence longer than the chunk is cut into pieces overlapping by
+    // l-1 bases, which yields every window exactly once (an extra duplicate at a seam merges in the set)
+    const uint32_t max_pieces = DCN_BUILD_MAX_PIECES;
+    DCN_TRY(ensure_dump_buffers(c));
+    std::vector<uint64_t> p_off;   // offsets of the pieces inside the chunk buffer
+    std::vector<const uint8_t *> p_src;
+    std::vector<uint64_t> p_len;
+    bool continues = false;
+    auto run_chunk = [&]() -> int {
+        if (p_len.empty()) return DCN_OK;
+        uint32_t np = (uint32_t)p_len.size();
+        p_off.assign(np + 1, 0);
+        for (uint32_t i = 0; i < np; ++i) p_off[i + 1] = p_off[i] + p_len[i];
+        uint64_t nb = p_off[np];
+        const double t_stage = times ? build_now() : 0.0;
+        // pieces that follow each other in the caller's memory (the reads of a batch) cross as one copy: one copy per
+        // 150-base read was the whole build of a read set
+        for (uint32_t i = 0; i < np;) {
+            uint32_t j = i + 1;
+            while (j < np && p_src[j] == p_src[j - 1] + p_len[j - 1]) ++j;
+            DCN_TRY(staged_h2d(c, c->d_ascii + p_off[i], p_src[i], p_off[j] - p_off[i]));
+            i = j;
         }
-        return run_chunk();
+        DCN_TRY(staged_h2d(c, c->d_offsets, p_off.data(), (uint64_t)(np + 1) * sizeof(uint64_t)));
+        DCN_TRY(stage_done(c));
+        if (times) {
+            DCN_HIP(hipEventSynchronize(c->copy_done));
+            times->staging_s += build_now() - t_stage;
+        }
+        hipStream_t st = c->stream;
+        int prof_slot = -1;
+        DCN_TRY(prof_begin(c, &prof_slot));
+        DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
+        DCN_HIP(hipMemsetAsync(c->d_dump_valid, 0, nb + 2, st));
+        // no status word for the pack (a newline is not looked for), the index side's code table
+        DCN_TRY(dcn_launch_pack(c->d_ascii, 0, nb, c->d_packed + DCN_FRONT_PAD, c->d_invmask + DCN_FRONT_PAD, nullptr, st,
+                                /*index_side=*/true));
+        DCN_PROF_MARK(DCN_STAGE_PACK);
+        // (check_offsets stays 0: the pieces' offsets were made right here)
+        dcn_plan_args pa = plan_args(c, idx, c->d_ascii, c->d_offsets, nullptr, np, np, 0);
+        pa.read_tiles = c->d_read_tiles;
+        pa.read_tile_first = c->d_read_tile_first;
+        DCN_TRY(dcn_launch_plan(pa, st));
+        DCN_PROF_MARK(DCN_STAGE_PLAN);
+        dcn_scan_args sa = dump_scan_args(c, idx, nb);
+        sa.dump_abs = 1; // positions in the chunk: the sweeps read the bases around them
+        DCN_TRY(dcn_launch_scan(sa, tile_bound(c, np, nb), true, st));
+        DCN_PROF_MARK(DCN_STAGE_SCAN);
+        DCN_TRY(sweep(nb, continues));
+        DCN_PROF_MARK(DCN_STAGE_DISTINCT); // (the sweep's slot; nothing follows it)
+        DCN_PROF_MARK(DCN_STAGE_FINISH);
+        if (prof_slot >= 0) c->prof_used[prof_slot] = true;
+        p_src.clear();
+        p_len.clear();
+        return DCN_OK;
     };
-    rc = body();
+    uint64_t used = 0;
+    for (uint32_t sidx = 0; sidx < n_seqs; ++sidx) {
+        if (offsets[sidx + 1] < offsets[sidx]) return dcn_fail(DCN_ERR_ARG, "offsets must be non-decreasing");
+        const uint8_t *seq = bases + offsets[sidx];
+        uint64_t len = offsets[sidx + 1] - offsets[sidx];
+        if (len < k || len < l) continue; // src/minimizers.rs:135; fewer than l bases have no window
+        uint64_t a = 0;
+        while (a + l <= len) {
+            uint64_t room = chunk_bases - used;
+            if (room < l || p_len.size() >= max_pieces) {
+                DCN_TRY(run_chunk());
+                continues = a > 0; // (a cut piece fills its chunk: the piece at a > 0 that opens a chunk continues it)
+                used = 0;
+                room = chunk_bases;
+            }
+            uint64_t take = std::min<uint64_t>(room, len - a);
+            if (take > 0xFFFFFF00ull) take = 0xFFFFFF00ull;
+            p_src.push_back(seq + a);
+            p_len.push_back(take);
+            used += take;
+            if (a + take >= len) break;
+            a += take - (l - 1); // next piece starts l-1 bases before the cut
+        }
+    }
+    return run_chunk();
+}
+
+int dcn_build_index_impl(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seqs, float entropy_threshold,
+                         dcn_index *idx) {
+    if (n_seqs == 0) return DCN_OK;
+    const uint64_t chunk_bases = build_chunk_bases();
+    const bool timing = getenv("DCN_INDEX_TIMING") != nullptr;
+    build_times times;
+    dcn_ctx *c = nullptr;
+    double t0 = build_now();
+    DCN_TRY(dcn_ctx_create(idx, chunk_bases, DCN_BUILD_MAX_PIECES, &c));
+    times.front_end_s = build_now() - t0;
+    int rc = timing ? build_timing_begin(c) : DCN_OK;
+    if (rc == DCN_OK)
+        rc = build_run_chunks(c, idx, bases, offsets, n_seqs, chunk_bases, [&](uint64_t nb, bool) -> int {
+            uint64_t n_valid = 0;
+            DCN_TRY(dcn_table_count_valid(c->d_dump_valid, nb, &n_valid, c->stream));
+            const double t_grow = build_now();
+            DCN_TRY(dcn_table_reserve(idx, idx->n_keys + n_valid));
+            times.growth_s += build_now() - t_grow;
+            return dcn_table_insert_dump(idx, c->d_dump_hash, c->d_dump_valid, c->d_dump_pos, nb, c->d_ascii, entropy_threshold,
+                                         c->stream);
+        }, timing ? &times : nullptr);
+    // (the events are read before the context goes; what freeing it costs is printed by itself)
+    if (timing && rc == DCN_OK) rc = build_times_print("plain", c, times);
+    t0 = build_now();
     dcn_ctx_destroy(c);
+    if (timing) fprintf(stderr, "index build timing (plain): front end freed %.3f s\n", build_now() - t0);
     return rc;
 }

@@ -6,6 +6,7 @@
 // probing group by group.  One probe = one aligned group read inside one 64-byte HBM sector.
 #include "dcn_internal.h"
 #include "dcn_probe.h"
+#include "dcn_entropy.h"
 #include "dcn_table_insert.h"
 
 #include <algorithm>
@@ -338,30 +339,6 @@ int dcn_table_contains_device(const dcn_index *idx, const uint64_t *d_keys, uint
 // ----------------------------------------------------------------------------------------------------
 namespace {
 
-// p * log2(p) for p = count/total, computed on the HOST in f32 exactly as calculate_scaled_entropy does
-// (src/minimizers.rs:110-116), so the device only subtracts table entries in the reference's order
-constexpr int ENT_MAX = 57;
-__device__ float g_plogp[ENT_MAX][ENT_MAX];
-
-__device__ inline float scaled_entropy_dev(const uint8_t *kmer, uint32_t k) { // src/minimizers.rs:73-121
-    if (k < 10) return 1.0f;
-    uint32_t cnt[4] = {0, 0, 0, 0};
-    uint32_t total = 0;
-    for (uint32_t i = 0; i < k; ++i) {
-        uint32_t c = kmer[i] | 0x20u;
-        int j = c == 'a' ? 0 : c == 'c' ? 1 : c == 'g' ? 2 : c == 't' ? 3 : -1;
-        if (j >= 0) {
-            cnt[j]++;
-            total++;
-        }
-    }
-    if (total == 0) return 1.0f;
-    float entropy = 0.0f;
-    for (int j = 0; j < 4; ++j)
-        if (cnt[j] > 0) entropy = __fsub_rn(entropy, g_plogp[total][cnt[j]]);
-    return __fdiv_rn(entropy, 2.0f);
-}
-
 __global__ void insert_dump_kernel(uint64_t *slots, uint32_t group_shift, uint32_t group_mask, const uint64_t *hash,
                                    const uint8_t *valid, const uint32_t *abs_pos, uint64_t n, const uint8_t *ascii,
                                    uint32_t k, float entropy_threshold, unsigned long long *n_new, uint32_t *has_zero) {
@@ -536,16 +513,9 @@ int dcn_table_count_valid(const uint8_t *d_valid, uint64_t n, uint64_t *count, h
 int dcn_table_insert_dump(dcn_index *idx, const uint64_t *d_hash, const uint8_t *d_valid, const uint32_t *d_abs_pos,
                           uint64_t n_slots, const uint8_t *d_ascii, float entropy_threshold, hipStream_t stream) {
     if (n_slots == 0) return DCN_OK;
-    static bool table_ready = false; // the p*log2(p) table is the same for every build
-    if (entropy_threshold != 0.0f && !table_ready) {
-        static float host_tab[ENT_MAX][ENT_MAX];
-        for (int t = 1; t < ENT_MAX; ++t)
-            for (int c = 1; c <= t; ++c) {
-                float p = (float)c / (float)t;
-                host_tab[t][c] = p * log2f(p);
-            }
-        DCN_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_plogp), host_tab, sizeof(host_tab)));
-        table_ready = true;
+    if (entropy_threshold != 0.0f) {
+        const int ent_rc = dcn_entropy_table_ready();
+        if (ent_rc != DCN_OK) return ent_rc;
     }
     unsigned long long *d_new = nullptr;
     uint32_t *d_zero = nullptr;

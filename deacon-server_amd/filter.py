@@ -9,6 +9,7 @@ Names, argument meaning and results follow the Rust items they stand for (paths 
     .filter_batch(...)                  the whole paraseq per-record loop   (local_filter.rs:346-528)
     .stats()                            ProcessingStats                        (local_filter.rs:179-187)
   get_minimizer_hashes_and_positions <- filter_common.rs:211-310
+  IndexBuilder                       (no counterpart) an index built call by call that counts its keys' occurrences
   IndexSet / Classifier              (no counterpart) several indexes in one table, per-member hits in one pass
   Locator                            (no counterpart) where in each read an index or a set matched: segments
   unpaired_should_keep / paired_should_keep <- remote_filter.rs:230-301
@@ -228,6 +229,82 @@ class Index:
     def close(self):
         if getattr(self, "_h", None):
             N.lib().dcn_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class IndexBuilder:
+    """An index built over several calls that counts how often each key occurs (dcn_index_builder_*; no reference
+    counterpart).  add() takes sequences batch by batch -- the index-side rule of Index.build, an occurrence being a distinct
+    (sequence, position) pair -- and finish() hands out plain indexes by count: min_count for indexes built from reads,
+    max_count for repeat-aware ones.  Counts are 16 bits and saturate at 65,535.  Not thread-safe."""
+
+    def __init__(self, kmer_length=DEFAULT_KMER_LENGTH, window_size=DEFAULT_WINDOW_SIZE, entropy_threshold=0.0,
+                 capacity_keys=0, device=0):
+        for name, v, hi in (("kmer_length", kmer_length, 255), ("window_size", window_size, 255),
+                            ("capacity_keys", capacity_keys, (1 << 64) - 1)):
+            if not 0 <= int(v) <= hi:
+                raise ValueError(f"{name} {v} out of range")
+        self._h = C.c_void_p()
+        self.device = int(device)
+        self.kmer_length, self.window_size = int(kmer_length), int(window_size)
+        N.check(N.lib().dcn_index_builder_create(int(kmer_length), int(window_size), float(entropy_threshold),
+                                                 int(capacity_keys), int(device), C.byref(self._h)))
+
+    def add(self, seqs):
+        """count and insert the index-side minimizers of every sequence of `seqs` (bytes-like each)"""
+        seqs = list(seqs)
+        bases, offsets = concat_reads(seqs)
+        N.check(N.lib().dcn_index_builder_add(self._h, _ptr(bases) if len(bases) else None, _ptr(offsets), len(seqs)))
+
+    def info(self):
+        """{"n_keys", "n_occurrences" (the true number, not the saturated sum), "n_bases", "device_bytes"}"""
+        v = [C.c_uint64() for _ in range(4)]
+        N.check(N.lib().dcn_index_builder_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("n_keys", "n_occurrences", "n_bases", "device_bytes"), (x.value for x in v)))
+
+    def __len__(self):
+        return self.info()["n_keys"]
+
+    def hist(self, n_bins=256):
+        """np.uint64[n_bins]: keys by count, the last bin holding every count >= n_bins - 1; bin 0 is always 0"""
+        if not 0 <= int(n_bins) <= 0xFFFFFFFF:
+            raise ValueError(f"n_bins {n_bins} out of range")
+        hist = np.zeros(max(int(n_bins), 1), np.uint64)
+        N.check(N.lib().dcn_index_builder_hist(self._h, int(n_bins), _ptr(hist)))
+        return hist
+
+    def counts(self):
+        """(keys np.uint64, counts np.uint32) of every key, in no particular order"""
+        n = C.c_uint64()
+        rc = N.lib().dcn_index_builder_counts(self._h, None, None, 0, C.byref(n))
+        if rc != N.DCN_ERR_CAPACITY:
+            N.check(rc)
+        keys = np.zeros(max(n.value, 1), np.uint64)
+        counts = np.zeros(max(n.value, 1), np.uint32)
+        N.check(N.lib().dcn_index_builder_counts(self._h, _ptr(keys), _ptr(counts), len(keys), C.byref(n)))
+        return keys[:n.value], counts[:n.value]
+
+    def finish(self, min_count=1, max_count=0, count_only=False):
+        """The keys with min_count <= count <= max_count (0 = no upper bound): a new plain Index sized for them, or their
+        number with count_only.  The builder stays as it is: finish again with other bounds, or add more."""
+        for name, v in (("min_count", min_count), ("max_count", max_count)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} {v} out of range")
+        n = C.c_uint64()
+        h = C.c_void_p()
+        N.check(N.lib().dcn_index_builder_finish(self._h, int(min_count), int(max_count), C.byref(n),
+                                                 None if count_only else C.byref(h)))
+        return n.value if count_only else Index(h, self.device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lib().dcn_index_builder_destroy(self._h)
             self._h = None
 
     def __del__(self):

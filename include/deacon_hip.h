@@ -69,9 +69,10 @@ enum {
  * 1.0 = dcn_pack_ascii(bases, n_bases, packed, invmask, saw_newline); 1.1 = dcn_abi_version, dcn_comm_* / dcn_stats_allreduce_rccl;
  * 1.2 = dcn_index_set_* / dcn_classify_batch*; 1.3 = dcn_index_set_coverage*; 1.4 = dcn_locate_batch;
  * 1.5 = dcn_index_set_select / _overlap, dcn_index_intersect;
- * 1.6 = dcn_index_set_depth_enable / _reset / _stats / _hist / _keys. */
+ * 1.6 = dcn_index_set_depth_enable / _reset / _stats / _hist / _keys;
+ * 1.7 = dcn_index_builder_create / _add / _info / _hist / _counts / _finish / _destroy. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 6
+#define DCN_ABI_MINOR 7
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -417,6 +418,56 @@ int dcn_index_set_depth_hist(const dcn_index *set, uint32_t member, uint32_t n_b
  * DCN_ERR_CAPACITY if capacity < count (keys / depths may be NULL with capacity 0: *n still receives the count) */
 int dcn_index_set_depth_keys(const dcn_index *set, uint32_t member, uint64_t *keys, uint32_t *depths, uint64_t capacity,
                              uint64_t *n);
+
+/* ---- index builder: add sequences call by call, keep keys by how often they occur ------------------------------------
+ * (no reference counterpart: index::build reads one input whole and its set keeps no multiplicity.)  A builder is a
+ * device table that lives across calls and counts as it inserts; dcn_index_builder_finish hands out plain indexes chosen
+ * by count: a minimum for indexes built from reads (every sequencing error mints a key that occurs once), a maximum for
+ * repeat-aware indexes.  THE DEFINITION: for every sequence given to dcn_index_builder_add, take the list that
+ * fill_minimizer_hashes walks (src/minimizers.rs:125-191), which is what dcn_index_build inserts: IUPAC codes
+ * canonicalised before the scan, positions whose k-mer has a non-ACGT byte in the ORIGINAL bytes dropped, the entropy
+ * floor applied, sequences shorter than k or k+w-1 contributing nothing.  An OCCURRENCE is a distinct (sequence, position)
+ * pair of that list.  The COUNT of key K is the number of occurrences whose hash is K, over all add calls since create.
+ * It is held per slot of the table as a 16-bit counter that SATURATES at 65,535; key 0 has a counter of its own.  The count
+ * does not depend on how the sequences are split over calls, nor on how a long sequence is cut into pieces inside the
+ * library (pieces of a chunk's size that overlap by k+w-2 bases: a position of an overlap is counted once).
+ * Device memory: 8 + 2 bytes per slot of the builder's table (sized and grown by dcn_index_memory's rule: a power-of-two
+ * number of 16-byte groups, at least four slots per key), and from the first add on one dump-mode context for chunks of
+ * 2^27 bases (DCN_BUILD_CHUNK_BASES, as dcn_index_build; about 18 bytes per base of a chunk) plus chunk / 8 bytes of
+ * position bitmap.  Growth holds the old and the new table for a moment, as dcn_index_build's does.
+ * A builder is NOT thread-safe; all calls are blocking.  Argument errors (the k / w rule and entropy range of
+ * dcn_index_build, NULLs, bad bounds, bad n_bins) return DCN_ERR_ARG before any device work.  After an add that failed
+ * the counts are unspecified: destroy the builder.
+ * (The handle is declared void * in the prototypes: every prototype of this header uses only scalar types and the handle
+ * types its bindings are generated and checked against; a C caller keeps a dcn_index_builder * and passes it as is,
+ * with (void **)&builder for create.) */
+typedef struct dcn_index_builder dcn_index_builder;
+/* k, w, entropy_threshold, capacity_keys (a pre-allocation hint; 0 = grow as needed) and device as for dcn_index_build; the
+ * minimizer rule in force is captured here, as by every index */
+int dcn_index_builder_create(uint8_t k, uint8_t w, float entropy_threshold, uint64_t capacity_keys, int device, void **out);
+/* bases / offsets: concatenated sequences and n_seqs+1 byte offsets in host memory, as for dcn_index_build; any number of
+ * calls, each with whole sequences */
+int dcn_index_builder_add(void *builder, const uint8_t *bases, const uint64_t *offsets, uint32_t n_seqs);
+/* any output may be NULL: distinct keys so far; occurrences so far (the true number as a u64, not the saturated sum);
+ * bases of all sequences given to add; device bytes of table, counters and position bitmap (not the context's buffers) */
+int dcn_index_builder_info(const void *builder, uint64_t *n_keys, uint64_t *n_occurrences, uint64_t *n_bases,
+                           uint64_t *device_bytes);
+/* hist[min(count, n_bins - 1)] = keys with that count, n_bins entries, 2 <= n_bins <= 4096, as dcn_index_set_depth_hist;
+ * hist[0] is always 0 (a key of the builder occurred), the entries sum to n_keys */
+int dcn_index_builder_hist(const void *builder, uint32_t n_bins, uint64_t *hist);
+/* (key, count) of every key, arbitrary order; *n = n_keys; DCN_ERR_CAPACITY if capacity < n_keys (keys / counts may be
+ * NULL with capacity 0: *n still receives the count), as dcn_index_set_depth_keys */
+int dcn_index_builder_counts(const void *builder, uint64_t *keys, uint32_t *counts, uint64_t capacity, uint64_t *n);
+/* The keys with min_count <= count <= max_count -> a new PLAIN index with the builder's k, w, device and the minimizer
+ * rule captured at create, sized for exactly the selected keys.  max_count == 0: no upper bound; min_count == 0 behaves as
+ * 1; a saturated key counts as 65,535 in both comparisons.  *n_selected (may be NULL) receives the count; out == NULL:
+ * count only, nothing is allocated.  DCN_ERR_ARG: min_count > max_count != 0, either bound above 65,535, out and
+ * n_selected both NULL.  The builder stays as it is: finish may be called again with other bounds, and add may follow
+ * it.  An empty result is a valid index with 0 keys.  With bounds (1, 0) the key set equals that of dcn_index_build on
+ * the same sequences. */
+int dcn_index_builder_finish(const void *builder, uint32_t min_count, uint32_t max_count, uint64_t *n_selected,
+                             dcn_index **out);
+void dcn_index_builder_destroy(void *builder);
 
 /* ---- locate: where in each read the index matched ----------------------------------------------------------
  * (no reference counterpart: the reference answers one verdict per record.)  Segments of every read of a host batch,

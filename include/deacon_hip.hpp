@@ -136,12 +136,60 @@ class Index {
     const dcn_index *raw() const { return h_; }
 
   private:
+    friend class IndexBuilder;
     explicit Index(dcn_index *h) : h_(h) {}
     void reset() {
         if (h_) dcn_index_destroy(h_);
         h_ = nullptr;
     }
     dcn_index *h_ = nullptr;
+};
+
+// An index built over several calls that counts how often each key occurs (dcn_index_builder_*; no reference
+// counterpart): add() takes sequences batch by batch, finish() hands out plain indexes by count.
+class IndexBuilder {
+  public:
+    struct Info {
+        uint64_t n_keys = 0, n_occurrences = 0, n_bases = 0, device_bytes = 0;
+    };
+    explicit IndexBuilder(uint8_t kmer_length = DEFAULT_KMER_LENGTH, uint8_t window_size = DEFAULT_WINDOW_SIZE,
+                          float entropy_threshold = 0.0f, uint64_t capacity_keys = 0, int device = 0) {
+        check(dcn_index_builder_create(kmer_length, window_size, entropy_threshold, capacity_keys, device, &h_));
+    }
+    IndexBuilder(const IndexBuilder &) = delete;
+    IndexBuilder &operator=(const IndexBuilder &) = delete;
+    ~IndexBuilder() {
+        if (h_) dcn_index_builder_destroy(h_);
+    }
+    // concatenated sequences and n_seqs + 1 byte offsets, as dcn_index_build takes them
+    void add(const uint8_t *bases, const uint64_t *offsets, uint32_t n_seqs) {
+        check(dcn_index_builder_add(h_, bases, offsets, n_seqs));
+    }
+    Info info() const {
+        Info i;
+        check(dcn_index_builder_info(h_, &i.n_keys, &i.n_occurrences, &i.n_bases, &i.device_bytes));
+        return i;
+    }
+    std::vector<uint64_t> hist(uint32_t n_bins = 256) const {  // keys by count; the last bin holds every count >= n_bins - 1
+        std::vector<uint64_t> h(n_bins);
+        check(dcn_index_builder_hist(h_, n_bins, h.data()));
+        return h;
+    }
+    uint64_t count(uint32_t min_count, uint32_t max_count = 0) const {  // how many keys finish() would keep
+        uint64_t n = 0;
+        check(dcn_index_builder_finish(h_, min_count, max_count, &n, nullptr));
+        return n;
+    }
+    // the keys with min_count <= count <= max_count (0: no upper bound); the builder stays as it is
+    Index finish(uint32_t min_count = 1, uint32_t max_count = 0) const {
+        dcn_index *h = nullptr;
+        check(dcn_index_builder_finish(h_, min_count, max_count, nullptr, &h));
+        return Index(h);
+    }
+    void *raw() const { return h_; }
+
+  private:
+    void *h_ = nullptr;
 };
 
 struct FilterConfig {  // the decision-relevant fields of lib.rs:39-87 with their defaults (lib.rs:90-109)
