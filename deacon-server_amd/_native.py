@@ -52,6 +52,26 @@ class LocateParams(C.Structure):
     ]
 
 
+class TrackParams(C.Structure):
+    _fields_ = [
+        ("bin_bases", C.c_uint32),
+        ("member_mask", C.c_uint32),
+        ("depth_cap", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("prefix_length", C.c_uint64),
+    ]
+
+
+class TrackBin(C.Structure):
+    _fields_ = [
+        ("n_positions", C.c_uint32),
+        ("n_keys", C.c_uint32),
+        ("n_observed", C.c_uint32),
+        ("max_depth", C.c_uint32),
+        ("sum_depth", C.c_uint64),
+    ]
+
+
 def build(force=False, jobs=6):
     """Compile every HIP source for gfx950 into lib/libdeacon_hip.so (hipcc cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -150,10 +170,11 @@ _SIGNATURES = {
     "dcn_index_builder_finish": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _u64p, C.POINTER(_vp)]),
     "dcn_index_builder_destroy": (None, [_vp]),
     "dcn_locate_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64]),
+    "dcn_depth_track_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64]),
 }
 
 _lib = None
-ABI = (1, 7)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 8)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

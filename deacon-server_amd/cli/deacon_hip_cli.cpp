@@ -15,6 +15,7 @@
 //   deacon-hip mask -x <index> [-x <index>...] [input|-] [-o masked.fastq] [--bed hits.bed] [--soft] [-g N] [-a 2] [-p 0] [-s summary.json]
 //   deacon-hip classify -x <index> [-x <index>...] [input|-] [input2] [-a 2] [-r 0.01] [-p 0] [--per-read out.tsv|-]
 //                       [--coverage] [--depth] [--depth-hist hist.tsv]
+//                       [--track ref.fasta] [--track-out track.tsv] [--track-bin 1000] [--track-cap 0]
 //                     [-s summary.json] [-q]
 //
 // Flags, defaults, stderr messages and the JSON summary follow src/main.rs:24-234, src/local_filter.rs:575-824 and
@@ -3153,6 +3154,10 @@ struct ClassifyArgs {
     bool depth = false;    // --depth: how often the input touched them (dcn_index_set_depth_*)
     std::string depth_hist;
     bool has_depth_hist = false;
+    // --track: after the last read batch, the depth counters binned along the records of a reference (dcn_depth_track_batch)
+    std::string track_ref, track_out = "-";
+    bool has_track = false;
+    uint32_t track_bin = 1000, track_cap = 0;
     unsigned abs_threshold = 2;
     double rel_threshold = 0.01;
     size_t prefix_length = 0;
@@ -3288,6 +3293,79 @@ int run_classify(const ClassifyArgs &a) {
     run_batch();
     if (tsv && tsv != stdout) std::fclose(tsv);
     else if (tsv) std::fflush(tsv);
+    // --track: the records of the reference against the counters the reads left, one block of lines per index (a header
+    // line, then record, start, end and the bin's figures; mean = sum_depth / n_keys).  The whole records are tracked:
+    // --prefix-length is the reads'.
+    std::vector<uint64_t> t_bins(n, 0), t_bins_obs(n, 0), t_sum(n, 0), t_keys(n, 0);
+    if (a.has_track) {
+        std::vector<std::string> block(n);
+        for (uint32_t j = 0; j < n; ++j)
+            block[j] = "# " + stems[j] + "\trecord\tstart\tend\tn_positions\tn_keys\tn_observed\tsum_depth\tmax_depth\tmean\n";
+        FastxReader rt(a.track_ref);
+        Batch tb;
+        std::vector<uint64_t> bin_off;
+        std::vector<dcn_track_bin> tbins;
+        char num[160];
+        auto track_batch = [&]() {
+            const uint32_t n_reads = (uint32_t)tb.recs.size();
+            if (n_reads == 0) return;
+            const uint64_t nb = tb.offsets.back();
+            if (nb > max_bases) { // a record longer than the context's batch: a context of its size
+                dcn_ctx_destroy(ctx);
+                ctx = nullptr;
+                max_bases = nb;
+                deacon::check(dcn_ctx_create(set.p, max_bases, max_reads, &ctx));
+            }
+            bin_off.assign((size_t)n_reads + 1, 0);
+            for (uint32_t j = 0; j < n; ++j) {
+                dcn_track_params tp = {};
+                tp.bin_bases = a.track_bin;
+                tp.member_mask = 1u << j;
+                tp.depth_cap = a.track_cap;
+                int rc = dcn_depth_track_batch(ctx, set.p, tb.bases.data(), tb.offsets.data(), n_reads, &tp, bin_off.data(),
+                                               tbins.data(), tbins.size());
+                if (rc == DCN_ERR_CAPACITY && bin_off[n_reads] > tbins.size()) { // the count came back: once more with room
+                    tbins.resize(bin_off[n_reads]);
+                    rc = dcn_depth_track_batch(ctx, set.p, tb.bases.data(), tb.offsets.data(), n_reads, &tp, bin_off.data(),
+                                               tbins.data(), tbins.size());
+                }
+                deacon::check(rc);
+                for (uint32_t r = 0; r < n_reads; ++r) {
+                    const Rec &rec = tb.recs[r];
+                    const char *id = tb.chars() + rec.id_off;
+                    size_t id_len = 0;
+                    while (id_len < rec.id_len && id[id_len] != ' ' && id[id_len] != '\t') ++id_len;
+                    for (uint64_t q = bin_off[r]; q < bin_off[r + 1]; ++q) {
+                        const dcn_track_bin &tbn = tbins[q];
+                        const uint64_t b0 = (q - bin_off[r]) * (uint64_t)a.track_bin;
+                        const uint64_t b1 = a.track_bin ? std::min<uint64_t>(b0 + a.track_bin, rec.seq_len) : rec.seq_len;
+                        block[j].append(id, id_len);
+                        int len = std::snprintf(num, sizeof num, "\t%llu\t%llu\t%u\t%u\t%u\t%llu\t%u\t", (unsigned long long)b0,
+                                                (unsigned long long)b1, tbn.n_positions, tbn.n_keys, tbn.n_observed,
+                                                (unsigned long long)tbn.sum_depth, tbn.max_depth);
+                        block[j].append(num, (size_t)len);
+                        if (tbn.n_keys) {
+                            len = std::snprintf(num, sizeof num, "%.4f\n", (double)tbn.sum_depth / (double)tbn.n_keys);
+                            block[j].append(num, (size_t)len);
+                        } else block[j] += "0\n";
+                        t_bins[j] += 1;
+                        t_bins_obs[j] += tbn.n_observed > 0;
+                        t_sum[j] += tbn.sum_depth;
+                        t_keys[j] += tbn.n_keys;
+                    }
+                }
+            }
+            tb.clear();
+        };
+        while (rt.next(tb))
+            if (tb.offsets.back() >= batch_bases || tb.recs.size() >= batch_reads) track_batch();
+        track_batch();
+        FILE *f = a.track_out == "-" ? stdout : std::fopen(a.track_out.c_str(), "w");
+        if (!f) die("cannot open " + a.track_out + " for writing");
+        for (uint32_t j = 0; j < n; ++j) std::fwrite(block[j].data(), 1, block[j].size(), f);
+        if (f != stdout) std::fclose(f);
+        else std::fflush(f);
+    }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
     auto prop = [](uint64_t x, uint64_t y) { return y ? (double)x / (double)y : 0.0; };
     std::vector<uint64_t> observed(n, 0), set_keys(n, 0);
@@ -3388,7 +3466,21 @@ int run_classify(const ClassifyArgs &a) {
             }
             js += "}";
         }
-        js += "\n  ]\n}\n";
+        js += "\n  ]";
+        if (a.has_track) {
+            js += ",\n  \"track\": {\"reference\": " + json_str(a.track_ref);
+            std::snprintf(buf, sizeof buf, ", \"bin_bases\": %u, \"depth_cap\": %u, \"indexes\": [", a.track_bin, a.track_cap);
+            js += buf;
+            for (uint32_t j = 0; j < n; ++j) {
+                js += std::string(j ? "," : "") + "\n    {\"name\": " + json_str(stems[j]);
+                std::snprintf(buf, sizeof buf, ", \"bins\": %llu, \"bins_observed\": %llu, \"sum_depth\": %llu, \"n_keys\": %llu}",
+                              (unsigned long long)t_bins[j], (unsigned long long)t_bins_obs[j], (unsigned long long)t_sum[j],
+                              (unsigned long long)t_keys[j]);
+                js += buf;
+            }
+            js += "\n  ]}";
+        }
+        js += "\n}\n";
         FILE *f = std::fopen(a.summary.c_str(), "w");
         if (!f) die("cannot open " + a.summary + " for writing");
         std::fwrite(js.data(), 1, js.size(), f);
@@ -3668,6 +3760,12 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "                                 of their occurrence counts (each saturating at 65535; median \">=4095\" past that)\n"
                "      --depth-hist <PATH>        TSV of index, depth, keys: minimizers of each index by occurrence count, 256 bins\n"
                "                                 (depth 0 = not observed, the last row \">=255\"; non-empty bins only; implies --depth)\n"
+               "      --track <FASTX>            After the last read, bin the occurrence counts along the records of this reference:\n"
+               "                                 per index a header line, then record, start, end, n_positions, n_keys, n_observed,\n"
+               "                                 sum_depth, max_depth, mean (= sum_depth / n_keys) for every bin (implies --depth)\n"
+               "      --track-out <PATH>         Where the track lines go [default: - (stdout)]\n"
+               "      --track-bin <N>            Bases per bin (0 = one bin per record) [default: 1000]\n"
+               "      --track-cap <N>            Count each minimizer's occurrences as at most N (0 = as counted) [default: 0]\n"
                "  -s, --summary <SUMMARY>        Path to JSON summary output file\n"
                "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
                "  -q, --quiet                    Suppress progress reporting\n"
@@ -3864,6 +3962,17 @@ int main(int argc, char **argv) {
                 else if (s == "--coverage") a.coverage = true;
                 else if (s == "--depth") a.depth = true;
                 else if (s == "--depth-hist") a.depth_hist = need(++i), a.has_depth_hist = true, a.depth = true;
+                else if (s == "--track") a.track_ref = need(++i), a.has_track = true, a.depth = true;
+                else if (s == "--track-out") a.track_out = need(++i);
+                else if (s == "--track-bin") {
+                    long long v = std::atoll(need(++i).c_str());
+                    if (v < 0 || v > 0xFFFFFFFFll) die("invalid value for --track-bin");
+                    a.track_bin = (uint32_t)v;
+                } else if (s == "--track-cap") {
+                    long v = std::atol(need(++i).c_str());
+                    if (v < 0 || v > 65535) die("invalid value for --track-cap: must be 0..65535");
+                    a.track_cap = (uint32_t)v;
+                }
                 else if (s == "-t" || s == "--threads") ++i;
                 else if (s == "-q" || s == "--quiet") a.quiet = true;
                 else if (s.size() > 1 && s[0] == '-' && s != "-") die("unexpected argument '" + s + "'");

@@ -1,7 +1,7 @@
 // dcn_ctx.h -- the filter context and what the files that implement the C ABI's host side share (internal, like
 // dcn_internal.h): api.hip (errors, indexes), ctx.hip (context, device-pointer batches, the stage builders),
 // host_batch.hip (submit / wait), dump.hip (minimizer dump, hash seam, index build), classify_api.hip (index sets),
-// locate_api.hip (segments).
+// locate_api.hip (segments), track_api.hip (depth tracks).
 #pragma once
 
 #include "dcn_internal.h"
@@ -142,6 +142,11 @@ struct dcn_ctx {
     uint64_t *d_loc_seg_offsets = nullptr;
     dcn_segment *d_loc_segs = nullptr;
     uint64_t loc_seg_cap = 0;
+    // depth track buffers (lazy, first dcn_depth_track_batch): per-read bin and piece offsets, computed on the host, and
+    // the bins (trk_bin_cap entries, grown to the largest batch's count).  The bitmap and the word per base are locate's.
+    uint64_t *d_trk_bin_offsets = nullptr, *d_trk_piece_offsets = nullptr;
+    dcn_track_bin *d_trk_bins = nullptr;
+    uint64_t trk_bin_cap = 0;
     // deferred state of the last enqueued device-API batch
     bool batch_pending = false;
     bool lean = false; // a small host batch is being submitted: copies and result copies go on `stream` itself (submit_impl)

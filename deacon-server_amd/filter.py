@@ -12,6 +12,7 @@ Names, argument meaning and results follow the Rust items they stand for (paths 
   IndexBuilder                       (no counterpart) an index built call by call that counts its keys' occurrences
   IndexSet / Classifier              (no counterpart) several indexes in one table, per-member hits in one pass
   Locator                            (no counterpart) where in each read an index or a set matched: segments
+  DepthTracker                       (no counterpart) a set's depth counters binned along each sequence of a batch
   unpaired_should_keep / paired_should_keep <- remote_filter.rs:230-301
 
 Everything here is plumbing: all arithmetic happens in lib/libdeacon_hip.so on the GPU.
@@ -596,6 +597,91 @@ class Locator:
     def profile(self):
         """(stage_ms, n_batches): pack, plan, scan (minimizer dump), the probe sweep that marks hits in the 'distinct' slot
         and the segment passes (count, scan over reads, write) in the 'finish' slot"""
+        ms = (C.c_double * N.N_STAGES)()
+        n = C.c_uint64()
+        N.check(N.lib().dcn_ctx_profile(self._h, ms, C.byref(n)))
+        return dict(zip(N.STAGE_NAMES, list(ms))), n.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lib().dcn_ctx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# numpy view of dcn_track_bin (24 bytes)
+TRACK_BIN_DTYPE = np.dtype([("n_positions", np.uint32), ("n_keys", np.uint32), ("n_observed", np.uint32),
+                            ("max_depth", np.uint32), ("sum_depth", np.uint64)])
+
+
+class DepthTracker:
+    """Depth tracks (dcn_depth_track_batch; the definition of a bin is in include/deacon_hip.h): for every sequence of a
+    batch, bins of bin_bases bases (0: one bin per sequence), each with the number of minimizer positions that start in
+    it, how many of them are keys of the chosen members, how many of those the classify calls on the set have seen, and
+    the sum and the maximum of their depth counters (each capped at depth_cap when that is not 0).  The set has depth
+    enabled; its counters are read, never changed.  member=None: every member; an int or an iterable selects members."""
+
+    def __init__(self, index_set, max_batch_bases=1 << 26, max_batch_reads=1 << 20, bin_bases=1000, member=None,
+                 depth_cap=0, prefix_length=0):
+        self.index_set = index_set
+        self.bin_bases = int(bin_bases)
+        if member is None:
+            self.member_mask = (1 << index_set.n) - 1
+        elif isinstance(member, (int, np.integer)):
+            if int(member) < 0:
+                raise ValueError(f"member {member} out of range")
+            self.member_mask = 1 << int(member)
+        else:
+            self.member_mask = index_set._mask(member)
+        self.depth_cap = int(depth_cap)
+        self.prefix_length = int(prefix_length)
+        if not (0 <= self.bin_bases <= 0xFFFFFFFF and 0 <= self.member_mask <= 0xFFFFFFFF and 0 <= self.depth_cap <= 0xFFFFFFFF):
+            raise ValueError("bin_bases / member / depth_cap out of range")
+        self.max_batch_bases = int(max_batch_bases)
+        self.max_batch_reads = int(max_batch_reads)
+        self._h = C.c_void_p()
+        N.check(N.lib().dcn_ctx_create(index_set._h, self.max_batch_bases, self.max_batch_reads, C.byref(self._h)))
+
+    def _params(self):
+        return N.TrackParams(self.bin_bases, self.member_mask, self.depth_cap, 0, self.prefix_length)
+
+    def track_batch(self, bases, offsets):
+        """bases: concatenated ASCII; offsets[n_reads+1] -> (bin_offsets u64[n_reads+1], bins TRACK_BIN_DTYPE[]): read r
+        owns bins[bin_offsets[r]:bin_offsets[r+1]], bin b of it covers its bases [b * bin_bases, (b + 1) * bin_bases)."""
+        bases = _as_u8(bases)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_reads = len(offsets) - 1
+        bin_offsets = np.zeros(n_reads + 1, np.uint64)
+        p = self._params()
+        rc = N.lib().dcn_depth_track_batch(self._h, self.index_set._h, _ptr(bases) if len(bases) else None, _ptr(offsets),
+                                           n_reads, C.byref(p), _ptr(bin_offsets), None, 0)  # the count: no device work
+        if rc != N.DCN_ERR_CAPACITY:
+            N.check(rc)
+            return bin_offsets, np.zeros(0, TRACK_BIN_DTYPE)
+        total = int(bin_offsets[n_reads])
+        bins = np.zeros(total, TRACK_BIN_DTYPE)
+        N.check(N.lib().dcn_depth_track_batch(self._h, self.index_set._h, _ptr(bases) if len(bases) else None,
+                                              _ptr(offsets), n_reads, C.byref(p), _ptr(bin_offsets), _ptr(bins), total))
+        return bin_offsets, bins
+
+    def track(self, seqs):
+        """the tracks of a list of sequences: one TRACK_BIN_DTYPE array per sequence"""
+        seqs = list(seqs)
+        bases, offsets = concat_reads(seqs)
+        bo, bins = self.track_batch(bases, offsets)
+        return [bins[int(bo[r]):int(bo[r + 1])] for r in range(len(seqs))]
+
+    def set_profiling(self, enable=True):
+        N.check(N.lib().dcn_ctx_set_profiling(self._h, 1 if enable else 0))
+
+    def profile(self):
+        """(stage_ms, n_batches): pack, plan, scan (minimizer dump), the probe sweep that marks positions and reads the
+        counters in the 'distinct' slot and the reduction into bins in the 'finish' slot"""
         ms = (C.c_double * N.N_STAGES)()
         n = C.c_uint64()
         N.check(N.lib().dcn_ctx_profile(self._h, ms, C.byref(n)))

@@ -70,9 +70,10 @@ enum {
  * 1.2 = dcn_index_set_* / dcn_classify_batch*; 1.3 = dcn_index_set_coverage*; 1.4 = dcn_locate_batch;
  * 1.5 = dcn_index_set_select / _overlap, dcn_index_intersect;
  * 1.6 = dcn_index_set_depth_enable / _reset / _stats / _hist / _keys;
- * 1.7 = dcn_index_builder_create / _add / _info / _hist / _counts / _finish / _destroy. */
+ * 1.7 = dcn_index_builder_create / _add / _info / _hist / _counts / _finish / _destroy;
+ * 1.8 = dcn_depth_track_batch. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 7
+#define DCN_ABI_MINOR 8
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -514,6 +515,54 @@ typedef struct dcn_segment {
  * pack, plan, scan (minimizer dump), DISTINCT = the probe sweep that marks hits, FINISH = the segment passes. */
 int dcn_locate_batch(dcn_ctx *ctx, const dcn_index *index, const uint8_t *bases, const uint64_t *offsets,
                      uint32_t n_reads, const void *params, uint64_t *seg_offsets, void *segs, uint64_t capacity);
+
+/* ---- depth tracks: a set's depth counters, binned along a sequence ------------------------------------------------------
+ * (no reference counterpart.)  Depth says how often each key occurred in the sample; a track says where on a sequence --
+ * a reference record, or a read -- those keys lie and how deep the sample covered each stretch of it.  It READS a set's
+ * depth state and never changes it.  THE DEFINITION, per read r of the batch (mates are independent here: there is no
+ * unit_id), with the set's k and w:
+ *   1. (hashes, positions) = what get_minimizer_hashes_and_positions yields for the read (src/filter_common.rs:211-310;
+ *      here dcn_minimizer_hashes_batch): after the len < k rule, the prefix cut, the stripped trailing newline and the
+ *      ACGT filter of positions.  A position the list repeats counts once; it has one hash.
+ *   2. Bins.  With bin_bases = B > 0 read r owns ceil(len_r / B) bins (len_r: the read as given, so none for an empty
+ *      read); bin b covers bases [b*B, min((b+1)*B, len_r)) and a position p belongs to bin p / B, by where its k-mer
+ *      starts.  With B == 0 every read owns exactly one bin, an empty read too.  Bins past a prefix cut exist and are
+ *      all zero.
+ *   3. Per bin, over its distinct positions: n_positions = how many there are; n_keys = those whose hash is in the set
+ *      with label & member_mask != 0; n_observed = those of n_keys whose depth is > 0; sum_depth = the sum over n_keys of
+ *      d and max_depth = the maximum of d, where d = depth when depth_cap == 0, else min(depth, depth_cap).  A
+ *      saturated counter contributes 65,535.  Key 0 uses its own counter word.
+ *   4. Nothing depends on thresholds, on earlier track calls, or on how the library cuts the work. */
+typedef struct dcn_track_params {
+    uint32_t bin_bases;     /* 0: one bin per read */
+    uint32_t member_mask;   /* keys whose label meets it; 0 is DCN_ERR_ARG */
+    uint32_t depth_cap;     /* 0: none; else 1..65535: each depth counts as min(depth, cap) */
+    uint32_t reserved;      /* must be 0 */
+    uint64_t prefix_length; /* 0 = whole read, else only the first prefix_length bases */
+} dcn_track_params; /* 24 bytes */
+typedef struct dcn_track_bin {
+    uint32_t n_positions, n_keys, n_observed, max_depth;
+    uint64_t sum_depth;
+} dcn_track_bin; /* 24 bytes */
+
+/*   set          a labelled set with depth enabled and the k, w, minimizer rule and device of the context's index
+ *   params       a dcn_track_params
+ *   bin_offsets  n_reads+1 entries, always complete: read r owns bins[bin_offsets[r] .. bin_offsets[r+1])
+ *   bins         an array of dcn_track_bin
+ *   capacity     entries available in bins; on DCN_ERR_CAPACITY bin_offsets[n_reads] is the size needed and bins is not
+ *                written (bins may be NULL with capacity 0 to ask for the count only).  bin_offsets follows from offsets
+ *                alone: the capacity is checked before anything is enqueued.
+ * (params and bins are declared void * for the reason given at dcn_locate_batch.)  Host pointers, blocking, batch limits
+ * as for dcn_classify_batch; refused while batches are in flight; the six counters of the context are left unchanged.
+ * DCN_ERR_ARG, before any device work: NULLs, reserved != 0, member_mask == 0 or with a bit at or above the set's member
+ * count, depth_cap > 65535, an index that is not a labelled set, a set without depth.  The caller has waited for the
+ * classify calls whose counts it wants to see.  Device memory, allocated on the first call and freed with the context:
+ * max_batch_bases / 8 bytes of position bitmap and 4 * max_batch_bases bytes of values (both shared with
+ * dcn_locate_batch), 16 bytes per read of offsets, and a bin buffer grown to the largest batch's count.
+ * dcn_ctx_set_profiling covers it: pack, plan, scan (minimizer dump), DISTINCT = the probe sweep that marks positions and
+ * reads the counters, FINISH = the reduction into bins. */
+int dcn_depth_track_batch(dcn_ctx *ctx, const dcn_index *set, const uint8_t *bases, const uint64_t *offsets,
+                          uint32_t n_reads, const void *params, uint64_t *bin_offsets, void *bins, uint64_t capacity);
 
 /* ---- counters: ProcessingStats (src/local_filter.rs:179-187, merged at :388-396) -------------------------- */
 
