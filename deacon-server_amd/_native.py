@@ -72,6 +72,30 @@ class TrackBin(C.Structure):
     ]
 
 
+class PlaceParams(C.Structure):
+    _fields_ = [
+        ("band_bases", C.c_uint32),
+        ("min_votes", C.c_uint32),
+        ("prefix_length", C.c_uint64),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class Placement(C.Structure):
+    _fields_ = [
+        ("record", C.c_uint32),
+        ("reverse", C.c_uint32),
+        ("votes", C.c_uint32),
+        ("n_anchors", C.c_uint32),
+        ("n_positions", C.c_uint32),
+        ("read_start", C.c_uint32),
+        ("read_end", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("ref_start", C.c_uint64),
+        ("ref_end", C.c_uint64),
+    ]
+
+
 def build(force=False, jobs=6):
     """Compile every HIP source for gfx950 into lib/libdeacon_hip.so (hipcc cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -171,10 +195,15 @@ _SIGNATURES = {
     "dcn_index_builder_destroy": (None, [_vp]),
     "dcn_locate_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64]),
     "dcn_depth_track_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64]),
+    "dcn_anchor_map_create": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "dcn_anchor_map_add": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _u32p]),
+    "dcn_anchor_map_info": (C.c_int, [_vp, _u32p, _u64p, _u64p, _u64p]),
+    "dcn_anchor_map_anchors": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _u64p]),
+    "dcn_place_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp]),
 }
 
 _lib = None
-ABI = (1, 8)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 9)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

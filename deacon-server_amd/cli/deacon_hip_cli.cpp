@@ -3674,12 +3674,173 @@ int run_mask(const MaskArgs &a) {
     return 0;
 }
 
+// ---- place: which record of a reference each read came from, where, on which strand ------------------------------------
+struct PlaceArgs {
+    std::string ref, input = "-", index, output = "-", summary;
+    bool has_index = false, has_summary = false, quiet = false;
+    unsigned k = 31, w = 15, band = 256, min_votes = 2;
+    size_t prefix_length = 0;
+};
+
+int run_place(const PlaceArgs &a) {
+    const auto start = std::chrono::steady_clock::now();
+    if (a.ref.empty()) die("the following required arguments were not provided: <REF>");
+    // the reference, whole: its records are the map's records, and without -x its minimizers are the map's keys
+    Batch ref;
+    {
+        FastxReader rd(a.ref);
+        while (rd.next(ref)) {
+        }
+    }
+    const uint32_t n_records = (uint32_t)ref.recs.size();
+    if (n_records == 0) die("no records in " + a.ref);
+    RawIndex keys, map;
+    if (a.has_index) deacon::check(dcn_index_from_file(a.index.c_str(), 0, &keys.p));
+    else
+        deacon::check(dcn_index_build(ref.bases.data(), ref.offsets.data(), n_records, (uint8_t)a.k, (uint8_t)a.w, 0.0f,
+                                      ref.bases.size() / 4 + 1024, 0, &keys.p));
+    uint8_t k = 0, w = 0;
+    deacon::check(dcn_index_header(keys.p, &k, &w, nullptr));
+    deacon::check(dcn_anchor_map_create(keys.p, &map.p));
+    dcn_index_destroy(keys.p);
+    keys.p = nullptr;
+    uint64_t batch_bases = 32ull << 20, max_bases = 64ull << 20;
+    if (const char *e = std::getenv("DCN_CLI_PLACE_BATCH_BASES")) { // test hook: many batches, records past the context
+        batch_bases = (uint64_t)std::max(64, std::atoi(e));
+        max_bases = 2 * batch_bases;
+    }
+    const uint32_t max_reads = 1u << 20;
+    dcn_ctx *ctx = nullptr;
+    deacon::check(dcn_ctx_create(map.p, max_bases, max_reads, &ctx));
+    struct CtxGuard {
+        dcn_ctx **c;
+        ~CtxGuard() {
+            if (*c) dcn_ctx_destroy(*c);
+        }
+    } guard{&ctx};
+    auto fit = [&](uint64_t nb) { // a record longer than the context's batch: a context of its size
+        if (nb <= max_bases) return;
+        dcn_ctx_destroy(ctx);
+        ctx = nullptr;
+        max_bases = nb;
+        deacon::check(dcn_ctx_create(map.p, max_bases, max_reads, &ctx));
+    };
+    const uint32_t batch_reads = max_reads - 2;
+    // the records, batch by batch: whole records, offsets rebased to the batch
+    std::vector<uint64_t> off;
+    for (uint32_t r0 = 0; r0 < n_records;) {
+        uint32_t r1 = r0 + 1;
+        while (r1 < n_records && ref.offsets[r1] - ref.offsets[r0] < batch_bases && r1 - r0 < batch_reads) ++r1;
+        off.assign((size_t)(r1 - r0) + 1, 0);
+        for (uint32_t r = r0; r <= r1; ++r) off[r - r0] = ref.offsets[r] - ref.offsets[r0];
+        fit(off.back());
+        uint32_t first = 0;
+        deacon::check(dcn_anchor_map_add(map.p, ctx, ref.bases.data() + ref.offsets[r0], off.data(), r1 - r0, &first));
+        if (first != r0) die("place: record numbering out of step");
+        r0 = r1;
+    }
+    uint32_t m_records = 0;
+    uint64_t m_keys = 0, m_anchors = 0, m_repeats = 0;
+    deacon::check(dcn_anchor_map_info(map.p, &m_records, &m_keys, &m_anchors, &m_repeats));
+    std::vector<std::string> names(n_records);
+    std::vector<uint32_t> lens(n_records);
+    for (uint32_t r = 0; r < n_records; ++r) {
+        const Rec &rec = ref.recs[r];
+        const char *id = ref.chars() + rec.id_off;
+        size_t n = 0;
+        while (n < rec.id_len && id[n] != ' ' && id[n] != '\t') ++n;
+        names[r].assign(id, n);
+        lens[r] = rec.seq_len;
+    }
+    { // the sequences are on the device's side of things now: only names and lengths are needed from here on
+        Batch none;
+        std::swap(ref, none);
+    }
+    if (!a.quiet)
+        std::fprintf(stderr, "Anchor map: %u records, %llu keys, %llu anchors, %llu repeats (k=%u, w=%u)\n", m_records,
+                     (unsigned long long)m_keys, (unsigned long long)m_anchors, (unsigned long long)m_repeats, (unsigned)k, (unsigned)w);
+
+    dcn_place_params prm = {};
+    prm.band_bases = a.band;
+    prm.min_votes = a.min_votes;
+    prm.prefix_length = a.prefix_length;
+    FILE *out = a.output == "-" ? stdout : std::fopen(a.output.c_str(), "w");
+    if (!out) die("cannot open " + a.output + " for writing");
+    FastxReader rd(a.input);
+    uint64_t reads_in = 0, placed = 0, strand[2] = {0, 0};
+    std::vector<uint64_t> per_record(n_records, 0);
+    Batch b;
+    std::vector<dcn_placement> pl;
+    std::string rows;
+    auto run_batch = [&]() {
+        const uint32_t n_reads = (uint32_t)b.recs.size();
+        if (n_reads == 0) return;
+        fit(b.offsets.back());
+        pl.resize(n_reads);
+        deacon::check(dcn_place_batch(ctx, map.p, b.bases.data(), b.offsets.data(), n_reads, &prm, pl.data()));
+        rows.clear();
+        for (uint32_t r = 0; r < n_reads; ++r) {
+            const Rec &rec = b.recs[r];
+            const char *id = b.chars() + rec.id_off;
+            size_t id_len = 0;
+            while (id_len < rec.id_len && id[id_len] != ' ' && id[id_len] != '\t') ++id_len;
+            const dcn_placement &p = pl[r];
+            const bool is = p.record != UINT32_MAX;
+            ++reads_in;
+            if (is) ++placed, ++strand[p.reverse & 1u], ++per_record[p.record];
+            rows.append(id, id_len);
+            rows += '\t' + std::to_string(rec.seq_len) + '\t' + std::to_string(p.read_start) + '\t' + std::to_string(p.read_end) + '\t';
+            rows += is ? (p.reverse ? "-" : "+") : "*";
+            rows += '\t' + (is ? names[p.record] : std::string("*")) + '\t' + std::to_string(is ? lens[p.record] : 0u) + '\t' +
+                    std::to_string(p.ref_start) + '\t' + std::to_string(p.ref_end) + '\t' + std::to_string(p.votes) + '\t' +
+                    std::to_string(p.n_anchors) + '\t' + std::to_string(p.n_positions) + '\n';
+        }
+        std::fwrite(rows.data(), 1, rows.size(), out);
+        b.clear();
+    };
+    while (rd.next(b))
+        if (b.offsets.back() >= batch_bases || b.recs.size() >= batch_reads) run_batch();
+    run_batch();
+    if (out != stdout) std::fclose(out);
+    else std::fflush(out);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+    if (!a.quiet)
+        std::fprintf(stderr, "Placed %llu of %llu reads (%llu +, %llu -) in %s\n", (unsigned long long)placed,
+                     (unsigned long long)reads_in, (unsigned long long)strand[0], (unsigned long long)strand[1], fmt_duration(secs).c_str());
+    if (a.has_summary) {
+        std::string js = "{\n  \"version\": " + json_str(std::string("deacon-hip ") + VERSION) + ",\n  \"reference\": " + json_str(a.ref) +
+                         ",\n  \"input\": " + json_str(a.input);
+        char buf[512];
+        std::snprintf(buf, sizeof buf, ",\n  \"k\": %u,\n  \"w\": %u,\n  \"band_bases\": %u,\n  \"min_votes\": %u,\n  \"prefix_length\": %zu,\n"
+                                       "  \"records\": %u,\n  \"keys\": %llu,\n  \"anchors\": %llu,\n  \"repeats\": %llu,\n"
+                                       "  \"reads\": %llu,\n  \"placed\": %llu,\n  \"placed_by_strand\": {\"+\": %llu, \"-\": %llu},\n"
+                                       "  \"time\": %.17g,\n  \"placed_by_record\": [",
+                      (unsigned)k, (unsigned)w, a.band, a.min_votes, a.prefix_length, m_records, (unsigned long long)m_keys,
+                      (unsigned long long)m_anchors, (unsigned long long)m_repeats, (unsigned long long)reads_in,
+                      (unsigned long long)placed, (unsigned long long)strand[0], (unsigned long long)strand[1], secs);
+        js += buf;
+        for (uint32_t r = 0; r < n_records; ++r) {
+            js += (r ? ",\n    {" : "\n    {");
+            js += "\"name\": " + json_str(names[r]);
+            std::snprintf(buf, sizeof buf, ", \"length\": %u, \"placed\": %llu}", lens[r], (unsigned long long)per_record[r]);
+            js += buf;
+        }
+        js += "\n  ]\n}\n";
+        FILE *f = std::fopen(a.summary.c_str(), "w");
+        if (!f) die("cannot open " + a.summary + " for writing");
+        std::fwrite(js.data(), 1, js.size(), f);
+        std::fclose(f);
+    }
+    return 0;
+}
+
 void usage() {
     std::fprintf(stderr,
                  "Usage: deacon-hip <COMMAND>\n\nCommands:\n  index   Build and compose minimizer indexes (build, info, union, diff, intersect, compare, select)\n"
                  "  filter  Keep or discard DNA fastx records with sufficient minimizer hits to an index\n"
                  "  classify  Report which of several indexes each record (or pair) matches, in one pass\n"
                  "  mask    Report where in each record an index matched, and mask those stretches\n"
+                 "  place   Report which record of a reference each read came from, where, and on which strand\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -3788,6 +3949,29 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "  -q, --quiet                    Suppress progress reporting\n"
                "  -h, --help                     Print help\n\n"
                "At least one of -o, --bed and -s is required.  Mates are independent here: one input.\n";
+    else if (sub == "place")
+        text = "Report which record of a reference each read came from, at which coordinate, on which strand\n\n"
+               "Usage: deacon-hip place [OPTIONS] <REF> [READS]\n\n"
+               "Arguments:\n"
+               "  <REF>     Path to the reference fastx file: its records are numbered and named in file order\n"
+               "  [READS]   Optional path to fastx file (or - for stdin; gz, bgzf, zst, xz and bz2 found by content) [default: -]\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Keys that may anchor: a minimizer index file, whose k and w are used\n"
+               "                                 [default: the minimizers of <REF> at -k / -w]\n"
+               "  -k <K>                         K-mer length without -x [default: 31]\n"
+               "  -w <W>                         Minimizer window size without -x [default: 15]\n"
+               "  -o, --output <OUTPUT>          One tab-separated line per read, in input order (- for stdout) [default: -]:\n"
+               "                                 name len read_start read_end strand record_name record_len ref_start ref_end\n"
+               "                                 votes n_anchors n_positions; an unplaced read has * for strand and record name\n"
+               "      --band <N>                 Width of a diagonal band in bases [default: 256, a convention]\n"
+               "  -a, --min-votes <N>            Minimum number of anchor hits in the best cell [default: 2, as filter's -a]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per read (0 = entire read) [default: 0]\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
+               "  -h, --help                     Print help\n\n"
+               "A key that occurs at exactly one place of <REF> is an anchor; keys that occur at several never vote.\n"
+               "Mates are independent here: one input.\n";
     else if (sub == "index build")
         text = "Index minimizers contained within a fastx file\n\n"
                "Usage: deacon-hip index build [OPTIONS] <INPUT>\n\n"
@@ -4010,6 +4194,36 @@ int main(int argc, char **argv) {
             if (pos.size() > 0) a.input = pos[0];
             if (pos.size() > 1) die("mask takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[1] + "')");
             return run_mask(a);
+        }
+        if (args[0] == "place") {
+            PlaceArgs a;
+            std::vector<std::string> pos;
+            auto number = [&](const std::string &v, const char *flag, long long lo, long long hi) {
+                char *end = nullptr;
+                const long long x = std::strtoll(v.c_str(), &end, 10);
+                if (v.empty() || *end || x < lo || x > hi)
+                    die(std::string("invalid value for ") + flag + ": must be " + std::to_string(lo) + ".." + std::to_string(hi));
+                return x;
+            };
+            for (size_t i = 1; i < args.size(); ++i) {
+                const std::string &s = args[i];
+                if (s == "-x" || s == "--index") a.index = need(++i), a.has_index = true;
+                else if (s == "-k") a.k = (unsigned)number(need(++i), "-k", 1, 56);
+                else if (s == "-w") a.w = (unsigned)number(need(++i), "-w", 1, 255);
+                else if (s == "-o" || s == "--output") a.output = need(++i);
+                else if (s == "--band") a.band = (unsigned)number(need(++i), "--band", 1, 0xFFFFFFFFll);
+                else if (s == "-a" || s == "--min-votes") a.min_votes = (unsigned)number(need(++i), "--min-votes", 1, 0xFFFFFFFFll);
+                else if (s == "-p" || s == "--prefix-length") a.prefix_length = (size_t)number(need(++i), "--prefix-length", 0, 0x7FFFFFFFFFFFFFFFll);
+                else if (s == "-s" || s == "--summary") a.summary = need(++i), a.has_summary = true;
+                else if (s == "-t" || s == "--threads") ++i;
+                else if (s == "-q" || s == "--quiet") a.quiet = true;
+                else if (s.size() > 1 && s[0] == '-' && s != "-") die("unexpected argument '" + s + "'");
+                else pos.push_back(s);
+            }
+            if (pos.size() > 0) a.ref = pos[0];
+            if (pos.size() > 1) a.input = pos[1];
+            if (pos.size() > 2) die("place takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[2] + "')");
+            return run_place(a);
         }
         if (args[0] == "cat" && args.size() >= 2) {  // hidden: the input side alone (format found by content, decoded to stdout; no GPU)
             Input in(args[1]);

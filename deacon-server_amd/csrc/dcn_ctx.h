@@ -1,7 +1,7 @@
 // dcn_ctx.h -- the filter context and what the files that implement the C ABI's host side share (internal, like
 // dcn_internal.h): api.hip (errors, indexes), ctx.hip (context, device-pointer batches, the stage builders),
 // host_batch.hip (submit / wait), dump.hip (minimizer dump, hash seam, index build), classify_api.hip (index sets),
-// locate_api.hip (segments), track_api.hip (depth tracks).
+// locate_api.hip (segments), track_api.hip (depth tracks), place_api.hip (anchor maps, placement).
 #pragma once
 
 #include "dcn_internal.h"
@@ -147,6 +147,11 @@ struct dcn_ctx {
     uint64_t *d_trk_bin_offsets = nullptr, *d_trk_piece_offsets = nullptr;
     dcn_track_bin *d_trk_bins = nullptr;
     uint64_t trk_bin_cap = 0;
+    // placement buffers (lazy, first dcn_place_batch): the anchor bitmap, one word per base (dcn_place.h), the work list
+    // of the workgroup kernel with its length, and the placements.  The position bitmap is locate's.
+    uint64_t *d_plc_words = nullptr;
+    uint32_t *d_plc_abits = nullptr, *d_plc_big = nullptr, *d_plc_n_big = nullptr;
+    dcn_placement *d_plc_out = nullptr;
     // deferred state of the last enqueued device-API batch
     bool batch_pending = false;
     bool lean = false; // a small host batch is being submitted: copies and result copies go on `stream` itself (submit_impl)

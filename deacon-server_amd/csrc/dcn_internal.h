@@ -101,6 +101,10 @@ struct dcn_index {
     // 2 B per slot: 8 GiB at the panhuman-sized set (2^31 groups of 2 slots).
     uint32_t *d_depth = nullptr;
     uint64_t depth_words = 0;
+    // anchor map (dcn_anchor_map_create, place.hip): one 64-bit word per slot, then key 0's word (layout in dcn_place.h);
+    // anchor_records = records added so far.  Null: not a map.
+    uint64_t *d_anchor = nullptr;
+    uint32_t anchor_records = 0;
     dcn_table_view view() const {
         dcn_table_view v;
         v.slots = d_slots;

@@ -1,0 +1,257 @@
+// place_api.hip -- the C ABI of anchor maps (dcn_anchor_map_*) and dcn_place_batch (kernels in place.hip; both batch
+// calls run locate's front end, pack -> plan -> scan in dump mode, on a filter context).
+#include "dcn_ctx.h"
+#include "dcn_place.h"
+
+#include <cstdlib>
+#include <cstring>
+
+using namespace dcn_impl;
+
+static_assert(sizeof(dcn_place_params) == 24 && sizeof(dcn_placement) == 48, "place structs are ABI");
+
+namespace {
+int check_map(const dcn_index *map) {
+    if (!map) return dcn_fail(DCN_ERR_ARG, "map is NULL");
+    if (!map->d_anchor) return dcn_fail(DCN_ERR_ARG, "the index is not an anchor map (dcn_anchor_map_create)");
+    return DCN_OK;
+}
+
+// the context's index reads sequences as the map does, on the map's device; the context is idle
+int check_ctx(const dcn_ctx *ctx, const dcn_index *map) {
+    const dcn_index *ix = ctx->index;
+    if (ix->k != map->k || ix->w != map->w)
+        return dcn_fail(DCN_ERR_ARG, "the context's index (k=" + std::to_string((int)ix->k) + ", w=" + std::to_string((int)ix->w) +
+                                         ") and the map (k=" + std::to_string((int)map->k) + ", w=" + std::to_string((int)map->w) +
+                                         ") differ");
+    if (ix->device != map->device) return dcn_fail(DCN_ERR_ARG, "the context and the map live on different devices");
+    if (ix->variant != map->variant)
+        return dcn_fail(DCN_ERR_ARG, "the context's index and the map were created under different minimizer rules");
+    return check_idle(ctx);
+}
+
+// a test hook of the vote: `name` as a number within [lo, hi], else `dflt`
+uint32_t env_u32(const char *name, uint32_t dflt, uint32_t lo, uint32_t hi) {
+    const char *s = std::getenv(name);
+    if (!s || !*s) return dflt;
+    const unsigned long long v = std::strtoull(s, nullptr, 10);
+    return (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>(v, lo), hi);
+}
+
+// pack -> plan -> dump scan of a staged batch on the context's stream, and the fields of `pa` that describe its dump
+int front_end(dcn_ctx *c, const dcn_index *map, uint32_t n_reads, uint64_t n_bases, uint64_t prefix_length, int prof_slot,
+              dcn_place_args *pa) {
+    hipStream_t st = c->stream;
+    DCN_TRY(dcn_launch_pack(c->d_ascii, 0, n_bases, c->d_packed + DCN_FRONT_PAD, c->d_invmask + DCN_FRONT_PAD, c->d_status, st));
+    DCN_PROF_MARK(DCN_STAGE_PACK);
+    // (check_offsets stays 0: validate_host_batch has walked the offsets on the host)
+    dcn_plan_args pl = plan_args(c, map, c->d_ascii, c->d_offsets, nullptr, n_reads, n_reads, prefix_length);
+    pl.read_tiles = c->d_read_tiles;
+    pl.read_tile_first = c->d_read_tile_first;
+    DCN_TRY(dcn_launch_plan(pl, st));
+    DCN_PROF_MARK(DCN_STAGE_PLAN);
+    dcn_scan_args sa = dump_scan_args(c, map, n_bases);
+    sa.dump_abs = 1;
+    const uint32_t max_tiles = tile_bound(c, n_reads, n_bases);
+    DCN_TRY(dcn_launch_scan(sa, max_tiles, true, st));
+    DCN_PROF_MARK(DCN_STAGE_SCAN);
+    memset(pa, 0, sizeof(*pa));
+    pa->table = map->view();
+    pa->anchor = map->d_anchor;
+    pa->n_slots = map->n_groups * DCN_GROUP_SLOTS;
+    pa->k = map->k;
+    pa->packed = c->d_packed + DCN_FRONT_PAD;
+    pa->status = c->d_status;
+    pa->tiles = c->d_tiles;
+    pa->n_tiles = &c->d_status->n_tiles;
+    pa->dump_hash = c->d_dump_hash;
+    pa->dump_valid = c->d_dump_valid;
+    pa->dump_pos = c->d_dump_pos;
+    pa->dump_count = c->d_dump_count;
+    pa->max_tiles = max_tiles;
+    pa->n_bases = n_bases;
+    pa->offsets = c->d_offsets;
+    pa->n_reads = n_reads;
+    return DCN_OK;
+}
+
+// what follows the last kernel of a batch call: the events a later device-pointer filter batch waits for, then the wait
+int finish_run(dcn_ctx *c, int prof_slot) {
+    if (prof_slot >= 0) c->prof_used[prof_slot] = true;
+    // a later device-pointer filter batch packs one batch ahead into these packed buffers on its own stream, after the
+    // events below: they now stand after this run
+    if (c->pack_ahead_state == 1) {
+        DCN_HIP(hipEventRecord(c->plan_done, c->stream));
+        for (int i = 0; i < 2; ++i) DCN_HIP(hipEventRecord(c->buf_free[i], c->stream));
+    }
+    return sync_and_check(c, nullptr);
+}
+} // namespace
+
+extern "C" int dcn_anchor_map_create(const dcn_index *index, dcn_index **out) {
+    if (!out) return dcn_fail(DCN_ERR_ARG, "out is NULL");
+    *out = nullptr;
+    if (!index) return dcn_fail(DCN_ERR_ARG, "index is NULL");
+    dcn_index *map = nullptr;
+    DCN_TRY(dcn_index_clone(index, index->device, &map)); // (a plain index over the keys, on the same device)
+    const uint64_t words = map->n_groups * DCN_GROUP_SLOTS + 1;
+    uint64_t *d = nullptr;
+    hipError_t e = hipSetDevice(map->device);
+    if (e == hipSuccess) e = hipMalloc((void **)&d, words * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMemset(d, 0, words * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        if (d) hipFree(d);
+        dcn_index_destroy(map);
+        return dcn_hip_fail(e, "anchor words");
+    }
+    map->d_anchor = d;
+    map->anchor_records = 0;
+    *out = map;
+    return DCN_OK;
+}
+
+extern "C" int dcn_anchor_map_add(dcn_index *map, dcn_ctx *ctx, const uint8_t *bases, const uint64_t *offsets,
+                                  uint32_t n_records, uint32_t *first_record) {
+    DCN_TRY(check_map(map));
+    if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
+    DCN_TRY(check_ctx(ctx, map));
+    if (first_record) *first_record = map->anchor_records;
+    if (n_records == 0) return DCN_OK;
+    if (!offsets) return dcn_fail(DCN_ERR_ARG, "offsets is NULL");
+    if ((uint64_t)map->anchor_records + n_records > DCN_ANCHOR_MAX_RECORDS)
+        return dcn_fail(DCN_ERR_ARG, "an anchor map holds at most 2^31 - 1 records");
+    DCN_TRY(validate_host_batch(ctx, offsets, n_records));
+    for (uint32_t r = 0; r < n_records; ++r)
+        if (offsets[r + 1] - offsets[r] > DCN_ANCHOR_MAX_RECORD_BASES)
+            return dcn_fail(DCN_ERR_ARG, "a record of an anchor map has at most 2^32 - 1 bases");
+    const uint64_t n_bases = offsets[n_records];
+    if (n_bases > 0 && !bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
+    dcn_ctx *c = ctx;
+    DCN_HIP(hipSetDevice(c->device));
+    DCN_TRY(ensure_dump_buffers(c));
+    DCN_TRY(stage_batch(c, bases, n_bases, offsets, n_records, nullptr));
+    hipStream_t st = c->stream;
+    DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
+    int prof_slot = -1;
+    DCN_TRY(prof_begin(c, &prof_slot));
+    dcn_place_args pa;
+    DCN_TRY(front_end(c, map, n_records, n_bases, 0, prof_slot, &pa));
+    pa.first_record = map->anchor_records;
+    DCN_TRY(dcn_launch_anchor_add(pa, st));
+    DCN_PROF_MARK(DCN_STAGE_DISTINCT);
+    DCN_PROF_MARK(DCN_STAGE_FINISH);
+    DCN_TRY(finish_run(c, prof_slot));
+    map->anchor_records += n_records;
+    return DCN_OK;
+}
+
+extern "C" int dcn_anchor_map_info(const dcn_index *map, uint32_t *n_records, uint64_t *n_keys, uint64_t *n_anchors,
+                                   uint64_t *n_repeats) {
+    DCN_TRY(check_map(map));
+    DCN_HIP(hipSetDevice(map->device));
+    unsigned long long h[2] = {};
+    if (n_anchors || n_repeats)
+        DCN_TRY(dcn_device_tally(2, h, "anchor map info", [&](unsigned long long *d) { return dcn_anchor_tally(map, d, 0); }));
+    if (n_records) *n_records = map->anchor_records;
+    if (n_keys) *n_keys = map->n_keys;
+    if (n_anchors) *n_anchors = h[0];
+    if (n_repeats) *n_repeats = h[1];
+    return DCN_OK;
+}
+
+extern "C" int dcn_anchor_map_anchors(const dcn_index *map, uint64_t *keys, uint32_t *records, uint32_t *positions,
+                                      uint64_t capacity, uint64_t *n) {
+    DCN_TRY(check_map(map));
+    if (!n) return dcn_fail(DCN_ERR_ARG, "n is NULL");
+    *n = 0;
+    if ((!keys || !records || !positions) && capacity > 0) return dcn_fail(DCN_ERR_ARG, "keys/records/positions is NULL");
+    DCN_HIP(hipSetDevice(map->device));
+    unsigned long long h[2] = {};
+    DCN_TRY(dcn_device_tally(2, h, "anchors", [&](unsigned long long *d) { return dcn_anchor_tally(map, d, 0); }));
+    const uint64_t total = h[0];
+    *n = total;
+    if (total > capacity)
+        return dcn_fail(DCN_ERR_CAPACITY, "anchors: " + std::to_string(total) + " anchors, capacity " + std::to_string(capacity));
+    if (total == 0) return DCN_OK;
+    unsigned long long *d_n = nullptr;
+    uint64_t *d_keys = nullptr;
+    uint32_t *d_rec = nullptr, *d_pos = nullptr;
+    int rc = DCN_OK;
+    unsigned long long written = 0;
+    hipError_t e = hipMalloc((void **)&d_n, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_keys, total * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_rec, total * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_pos, total * sizeof(uint32_t));
+    if (e == hipSuccess) rc = dcn_anchor_export(map, d_keys, d_rec, d_pos, total, d_n, 0);
+    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(&written, d_n, sizeof(written), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == DCN_OK && written != total)
+        rc = dcn_fail(DCN_ERR_INTERNAL, "anchors: the map changed between the count and the copy (an add call in flight?)");
+    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(keys, d_keys, total * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(records, d_rec, total * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(positions, d_pos, total * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (d_keys) hipFree(d_keys);
+    if (d_rec) hipFree(d_rec);
+    if (d_pos) hipFree(d_pos);
+    if (d_n) hipFree(d_n);
+    if (rc != DCN_OK) return rc;
+    return e == hipSuccess ? DCN_OK : dcn_hip_fail(e, "anchors");
+}
+
+extern "C" int dcn_place_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets,
+                               uint32_t n_reads, const void *params, void *placements) {
+    const dcn_place_params *prm = static_cast<const dcn_place_params *>(params);
+    // (the parameters first: what is wrong with them does not depend on the context or the map)
+    if (!prm) return dcn_fail(DCN_ERR_ARG, "params is NULL");
+    if (prm->reserved[0] != 0 || prm->reserved[1] != 0) return dcn_fail(DCN_ERR_ARG, "params.reserved must be 0");
+    if (prm->band_bases == 0) return dcn_fail(DCN_ERR_ARG, "params.band_bases must be at least 1");
+    if (prm->min_votes == 0) return dcn_fail(DCN_ERR_ARG, "params.min_votes must be at least 1");
+    if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
+    DCN_TRY(check_map(map));
+    DCN_TRY(check_ctx(ctx, map));
+    if (n_reads == 0) return DCN_OK;
+    if (!offsets) return dcn_fail(DCN_ERR_ARG, "offsets is NULL");
+    if (!placements) return dcn_fail(DCN_ERR_ARG, "placements is NULL");
+    DCN_TRY(validate_host_batch(ctx, offsets, n_reads)); // (a read of 2^32 bases or more is refused here)
+    const uint64_t n_bases = offsets[n_reads];
+    if (n_bases > 0 && !bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
+    dcn_ctx *c = ctx;
+    DCN_HIP(hipSetDevice(c->device));
+    DCN_TRY(ensure_dump_buffers(c));
+    if (!c->d_loc_bits) DCN_TRY(dev_alloc(&c->d_loc_bits, (c->max_bases + 31) / 32 + 1, "position bitmap"));
+    if (!c->d_plc_abits) DCN_TRY(dev_alloc(&c->d_plc_abits, (c->max_bases + 31) / 32 + 1, "anchor bitmap"));
+    if (!c->d_plc_words) DCN_TRY(dev_alloc(&c->d_plc_words, c->max_bases + 2, "placement words"));
+    if (!c->d_plc_big) DCN_TRY(dev_alloc(&c->d_plc_big, c->max_reads, "placement work list"));
+    if (!c->d_plc_n_big) DCN_TRY(dev_alloc(&c->d_plc_n_big, 1, "placement work list length"));
+    if (!c->d_plc_out) DCN_TRY(dev_alloc(&c->d_plc_out, c->max_reads, "placements"));
+    DCN_TRY(stage_batch(c, bases, n_bases, offsets, n_reads, nullptr));
+    hipStream_t st = c->stream;
+    DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
+    DCN_HIP(hipMemsetAsync(c->d_loc_bits, 0, ((n_bases + 31) / 32 + 1) * sizeof(uint32_t), st));
+    DCN_HIP(hipMemsetAsync(c->d_plc_abits, 0, ((n_bases + 31) / 32 + 1) * sizeof(uint32_t), st));
+    DCN_HIP(hipMemsetAsync(c->d_plc_n_big, 0, sizeof(uint32_t), st));
+    int prof_slot = -1;
+    DCN_TRY(prof_begin(c, &prof_slot));
+    dcn_place_args pa;
+    DCN_TRY(front_end(c, map, n_reads, n_bases, prm->prefix_length, prof_slot, &pa));
+    pa.band = prm->band_bases;
+    pa.min_votes = prm->min_votes;
+    pa.lane_bases = env_u32("DCN_PLACE_LANE_BASES", DCN_PLC_LANE_BASES, 0, 0xFFFFFFFFu);
+    pa.lds_cells = env_u32("DCN_PLACE_LDS_CELLS", DCN_PLC_LDS_CELLS, DCN_PLC_LDS_CELLS_MIN, DCN_PLC_LDS_CELLS);
+    // (the offsets are the host's: whether any read takes the workgroup path is known before the launch)
+    for (uint32_t r = 0; r < n_reads && !pa.any_big; ++r) pa.any_big = offsets[r + 1] - offsets[r] > pa.lane_bases ? 1u : 0u;
+    pa.bits = c->d_loc_bits;
+    pa.abits = c->d_plc_abits;
+    pa.words = c->d_plc_words;
+    pa.big = c->d_plc_big;
+    pa.n_big = c->d_plc_n_big;
+    pa.out = c->d_plc_out;
+    DCN_TRY(dcn_launch_place_mark(pa, st));
+    DCN_PROF_MARK(DCN_STAGE_DISTINCT);
+    DCN_TRY(dcn_launch_place_vote(pa, st));
+    DCN_PROF_MARK(DCN_STAGE_FINISH);
+    DCN_TRY(finish_run(c, prof_slot));
+    DCN_HIP(hipMemcpy(placements, c->d_plc_out, (uint64_t)n_reads * sizeof(dcn_placement), hipMemcpyDeviceToHost));
+    return DCN_OK;
+}

@@ -699,6 +699,140 @@ class DepthTracker:
             pass
 
 
+# numpy view of dcn_placement (48 bytes)
+PLACEMENT_DTYPE = np.dtype([("record", np.uint32), ("reverse", np.uint32), ("votes", np.uint32), ("n_anchors", np.uint32),
+                            ("n_positions", np.uint32), ("read_start", np.uint32), ("read_end", np.uint32),
+                            ("reserved", np.uint32), ("ref_start", np.uint64), ("ref_end", np.uint64)])
+UNPLACED = 0xFFFFFFFF
+
+
+class AnchorMap(Index):
+    """An index whose slots know where on a reference their key lies (dcn_anchor_map_*; the definition of an anchor is in
+    include/deacon_hip.h): a copy of `index`'s keys (the source may be closed afterwards) with one word per slot.  Records
+    are numbered in the order they are added; a key that occurs at exactly one (record, position) of them is an anchor, one
+    that occurs at several is a repeat and never votes.  It is an Index: contexts can be created over it, clone() gives a
+    plain Index without the words."""
+
+    def __init__(self, index):
+        h = C.c_void_p()
+        N.check(N.lib().dcn_anchor_map_create(index._h, C.byref(h)))
+        super().__init__(h, index.device)
+        self._ctx = C.c_void_p()
+        self._ctx_bases = self._ctx_reads = 0
+
+    def clone(self, device):
+        h = C.c_void_p()
+        N.check(N.lib().dcn_index_clone(self._h, int(device), C.byref(h)))
+        return Index(h, int(device))
+
+    def _context(self, n_bases, n_reads):
+        """a context of the map's own, made on the first add and re-made larger for a longer batch"""
+        if self._ctx and n_bases <= self._ctx_bases and n_reads <= self._ctx_reads:
+            return self._ctx
+        if self._ctx:
+            N.lib().dcn_ctx_destroy(self._ctx)
+            self._ctx = C.c_void_p()
+        bases, reads = max(int(n_bases), self._ctx_bases, 1 << 20), max(int(n_reads), self._ctx_reads, 1 << 10)
+        N.check(N.lib().dcn_ctx_create(self._h, bases, reads, C.byref(self._ctx)))
+        self._ctx_bases, self._ctx_reads = bases, reads
+        return self._ctx
+
+    def add(self, bases, offsets):
+        """bases: concatenated ASCII; offsets[n_records+1] -> the number of the batch's first record"""
+        bases = _as_u8(bases)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        first = C.c_uint32()
+        ctx = self._context(int(offsets[-1]) if n > 0 else 0, n)
+        N.check(N.lib().dcn_anchor_map_add(self._h, ctx, _ptr(bases) if len(bases) else None, _ptr(offsets), n, C.byref(first)))
+        return first.value
+
+    def add_records(self, records):
+        bases, offsets = concat_reads(list(records))
+        return self.add(bases, offsets)
+
+    def info(self):
+        """{records, keys, anchors, repeats}"""
+        r, k, a, p = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        N.check(N.lib().dcn_anchor_map_info(self._h, C.byref(r), C.byref(k), C.byref(a), C.byref(p)))
+        return {"records": r.value, "keys": k.value, "anchors": a.value, "repeats": p.value}
+
+    def anchors(self):
+        """(keys u64[], records u32[], positions u32[]) of the anchors, in arbitrary order"""
+        n = C.c_uint64()
+        rc = N.lib().dcn_anchor_map_anchors(self._h, None, None, None, 0, C.byref(n))
+        if rc != N.DCN_ERR_CAPACITY:
+            N.check(rc)
+        cap = int(n.value)
+        keys, rec, pos = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32)
+        N.check(N.lib().dcn_anchor_map_anchors(self._h, _ptr(keys), _ptr(rec), _ptr(pos), cap, C.byref(n)))
+        return keys[:cap], rec[:cap], pos[:cap]
+
+    def close(self):
+        if getattr(self, "_ctx", None):
+            N.lib().dcn_ctx_destroy(self._ctx)
+            self._ctx = None
+        super().close()
+
+
+class Placer:
+    """Where on the reference each read lands (dcn_place_batch; the definition of a placement is in
+    include/deacon_hip.h): a read's anchor hits vote on a diagonal band of band_bases bases; the best cell, with at least
+    min_votes votes, gives the record, the strand and the extents on the read and on the record.  band_bases = 256 and
+    min_votes = 2 are conventions (the 2 is the filter's -a 2), not measured optima."""
+
+    def __init__(self, anchor_map, max_batch_bases=1 << 26, max_batch_reads=1 << 20, band_bases=256, min_votes=2,
+                 prefix_length=0):
+        self.anchor_map = anchor_map
+        self.band_bases = int(band_bases)
+        self.min_votes = int(min_votes)
+        self.prefix_length = int(prefix_length)
+        self.max_batch_bases = int(max_batch_bases)
+        self.max_batch_reads = int(max_batch_reads)
+        self._h = C.c_void_p()
+        N.check(N.lib().dcn_ctx_create(anchor_map._h, self.max_batch_bases, self.max_batch_reads, C.byref(self._h)))
+
+    def _params(self):
+        return N.PlaceParams(self.band_bases, self.min_votes, self.prefix_length, (C.c_uint32 * 2)(0, 0))
+
+    def place_batch(self, bases, offsets):
+        """bases: concatenated ASCII; offsets[n_reads+1] -> PLACEMENT_DTYPE[n_reads]"""
+        bases = _as_u8(bases)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_reads = len(offsets) - 1
+        out = np.zeros(max(n_reads, 1), PLACEMENT_DTYPE)
+        p = self._params()
+        N.check(N.lib().dcn_place_batch(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None, _ptr(offsets),
+                                        n_reads, C.byref(p), _ptr(out)))
+        return out[:n_reads]
+
+    def place(self, reads):
+        bases, offsets = concat_reads(list(reads))
+        return self.place_batch(bases, offsets)
+
+    def set_profiling(self, enable=True):
+        N.check(N.lib().dcn_ctx_set_profiling(self._h, 1 if enable else 0))
+
+    def profile(self):
+        """(stage_ms, n_batches): pack, plan, scan (minimizer dump), the probe sweep that marks positions and stores their
+        anchors in the 'distinct' slot and the vote in the 'finish' slot"""
+        ms = (C.c_double * N.N_STAGES)()
+        n = C.c_uint64()
+        N.check(N.lib().dcn_ctx_profile(self._h, ms, C.byref(n)))
+        return dict(zip(N.STAGE_NAMES, list(ms))), n.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lib().dcn_ctx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class FilterProcessor:
     """One pipeline context bound to an index: decides keep/drop for units (reads or pairs)."""
 

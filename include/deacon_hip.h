@@ -71,9 +71,10 @@ enum {
  * 1.5 = dcn_index_set_select / _overlap, dcn_index_intersect;
  * 1.6 = dcn_index_set_depth_enable / _reset / _stats / _hist / _keys;
  * 1.7 = dcn_index_builder_create / _add / _info / _hist / _counts / _finish / _destroy;
- * 1.8 = dcn_depth_track_batch. */
+ * 1.8 = dcn_depth_track_batch;
+ * 1.9 = dcn_anchor_map_create / _add / _info / _anchors, dcn_place_batch. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 8
+#define DCN_ABI_MINOR 9
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -563,6 +564,92 @@ typedef struct dcn_track_bin {
  * reads the counters, FINISH = the reduction into bins. */
 int dcn_depth_track_batch(dcn_ctx *ctx, const dcn_index *set, const uint8_t *bases, const uint64_t *offsets,
                           uint32_t n_reads, const void *params, uint64_t *bin_offsets, void *bins, uint64_t capacity);
+
+/* ---- place: which record of a reference, at which coordinate, on which strand (ABI 1.9) -----------------------------
+ * (no reference counterpart.)  Two parts: an ANCHOR MAP, a dcn_index whose slots know where on a reference their key
+ * lies, and dcn_place_batch, in which a read's anchor hits vote on a diagonal.
+ *
+ * THE DEFINITION OF AN ANCHOR.  Records are numbered 0, 1, ... in the order they are added, over all dcn_anchor_map_add
+ * calls.  The occurrence list of record R is the distinct positions P of get_minimizer_hashes_and_positions(record, k,
+ * w, prefix_length = 0) (src/filter_common.rs:211-310: after the len < k rule, the stripped trailing newline and the ACGT
+ * filter; the filter-side list, the one depth tracks use), each with its hash.  An occurrence whose hash is not a key of
+ * the map is ignored.  A key of the map is an ANCHOR when, over everything added so far, exactly one (R, P) has its
+ * hash; the anchor carries one strand bit: whether the forward k-mer at (R, P) is the canonical one (kmer <=
+ * revcomp(kmer) as the packed values the k-mer hash compares: the hash is taken of the smaller one).  A key with two
+ * or more distinct occurrences is a REPEAT and never votes; a key with none is UNSEEN.  The state does not depend on the
+ * order of records within a call, on how the library cuts a record, or on how many calls the records were spread over.
+ * Limits: at most 2^31 - 1 records, a record of at most 2^32 - 1 bases.
+ *
+ * An anchor map is a copy of an index's slot table (it owns its memory; the source may be destroyed) with one 64-bit
+ * word per slot beside it (8 bytes per slot, which dcn_index_memory does not count).  It is a dcn_index: a context can
+ * be created over it and every call that reads an index sees its keys; dcn_index_clone of it gives a plain index
+ * without the words; dcn_index_destroy frees everything.  The table never grows: the caller chooses which keys may
+ * anchor by what it builds the map from (the reference's own index, that index minus a host, the member-specific keys
+ * of a set).  Every call below returns DCN_ERR_ARG for an index that is not a map. */
+int dcn_anchor_map_create(const dcn_index *index, dcn_index **out);
+/* Add n_records records (host pointers, offsets[n_records + 1], blocking).  ctx: an idle context whose index has the
+ * map's k, w, minimizer rule and device (the map itself may be that index); batch limits as for dcn_classify_batch.
+ * Whole records are used.  *first_record (may be NULL) receives the number of the batch's first record.  DCN_ERR_ARG
+ * before any device work when the records would exceed the limits above.  A batch that is refused adds nothing and
+ * does not advance the record count. */
+int dcn_anchor_map_add(dcn_index *map, dcn_ctx *ctx, const uint8_t *bases, const uint64_t *offsets,
+                       uint32_t n_records, uint32_t *first_record);
+/* Records added, keys of the map, and how many of them are anchors and repeats (a blocking sweep; outputs may be NULL). */
+int dcn_anchor_map_info(const dcn_index *map, uint32_t *n_records, uint64_t *n_keys, uint64_t *n_anchors,
+                        uint64_t *n_repeats);
+/* The anchors, in arbitrary order (a blocking sweep).  *n is always the number there is; DCN_ERR_CAPACITY when that is
+ * more than capacity, and nothing is written then (capacity 0 with NULL arrays asks for the count). */
+int dcn_anchor_map_anchors(const dcn_index *map, uint64_t *keys, uint32_t *records, uint32_t *positions,
+                           uint64_t capacity, uint64_t *n);
+
+/* THE DEFINITION OF A PLACEMENT.  Mates are independent (no unit_id).  Per read of length len (the read as given), with
+ * the map's k and w, band_bases = W:
+ *   1. (hashes, positions) = what get_minimizer_hashes_and_positions yields for the read: after the len < k rule, the
+ *      prefix cut, the stripped trailing newline and the ACGT filter.  A position the list repeats counts once;
+ *      n_positions = the number of distinct positions.
+ *   2. A position q is an ANCHOR HIT when its hash is an anchor of the map, at (R, P); n_anchors = how many there are.
+ *      Its orientation o is '+' when the read's k-mer at q and the record's k-mer at P are canonical on the same side
+ *      (both strand bits equal; equivalently the two k-mers' texts are equal -- a k-mer that is its own reverse
+ *      complement counts as '+'), else '-' (the read's k-mer is the reverse complement).
+ *   3. Its diagonal is D = P - q + len for '+' and D = P + q for '-' (non-negative, 64 bits).  A read cut from the
+ *      record's forward strand at a has D = a + len at every hit, the reverse complement of that cut D = a + len - k.
+ *   4. The hit votes for the two cells (R, o, j) with j = D / W and j = D / W + 1: cell j collects the diagonals in
+ *      [(j-1)*W, (j+1)*W), so any group of hits whose diagonals differ by less than W shares a cell.
+ *   5. The best cell has the most votes; ties go to the smallest (R, o, j), '+' before '-'.
+ *   6. With votes >= min_votes the read is placed: record = R, reverse = (o == '-'), votes, and over the best cell's
+ *      hits read_start = min q, read_end = max q + k, ref_start = min P, ref_end = max P + k.
+ *   7. Otherwise record = UINT32_MAX and every field but n_anchors and n_positions is 0.
+ *   8. Nothing depends on thresholds of the filter, on earlier calls, or on how the library cuts the work.  Integers only.
+ * n_anchors - votes is the number of anchor hits the placement does not explain (a chimera shows there); no second-best
+ * cell is reported.  band_bases = 256 and min_votes = 2 are the conventions of the layers above (the 2 is the filter's
+ * -a 2), not measured optima. */
+typedef struct dcn_place_params {
+    uint32_t band_bases;    /* W >= 1: width of a diagonal band */
+    uint32_t min_votes;     /* >= 1: a read whose best cell has fewer votes is unplaced */
+    uint64_t prefix_length; /* 0 = whole read */
+    uint32_t reserved[2];   /* must be 0 */
+} dcn_place_params; /* 24 bytes */
+typedef struct dcn_placement {
+    uint32_t record;  /* UINT32_MAX: unplaced */
+    uint32_t reverse; /* 0 | 1 */
+    uint32_t votes, n_anchors, n_positions;
+    uint32_t read_start, read_end; /* bases of the read as given, half-open */
+    uint32_t reserved;             /* 0 */
+    uint64_t ref_start, ref_end;   /* bases of the record, half-open */
+} dcn_placement; /* 48 bytes */
+
+/*   map         an anchor map with the k, w, minimizer rule and device of the context's index
+ *   params      a dcn_place_params
+ *   placements  n_reads entries of dcn_placement
+ * (params and placements are declared void * for the reason given at dcn_locate_batch.)  Host pointers, blocking, batch
+ * limits as for dcn_classify_batch; refused while batches are in flight; the six counters of the context are left
+ * unchanged.  DCN_ERR_ARG, before any device work: NULLs, reserved != 0, band_bases == 0, min_votes == 0, an index that
+ * is not a map.  Device memory, allocated on the first call and freed with the context: max_batch_bases / 8 bytes of
+ * position bitmap (shared with dcn_locate_batch), as much again for the anchor bitmap, 8 * max_batch_bases bytes of one
+ * word per base (12 GB for a context of 1.5 Gbp; written only where a position is an anchor hit), and 52 bytes per read.  dcn_ctx_set_profiling covers it: pack, plan, scan (minimizer dump), DISTINCT = the
+ * probe sweep that marks positions and stores the anchor of each anchor hit, FINISH = the vote. */
+int dcn_place_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets,
+                    uint32_t n_reads, const void *params, void *placements);
 
 /* ---- counters: ProcessingStats (src/local_filter.rs:179-187, merged at :388-396) -------------------------- */
 
