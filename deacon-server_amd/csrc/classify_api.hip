@@ -1,5 +1,5 @@
 // classify_api.hip -- the C ABI of labelled index sets: creation, per-member coverage, and classification of a batch
-// against a set (the kernels are in classify.hip; the batch runs pack -> plan -> scan in dump mode on a filter context).
+// against a set (the kernels are in classify.hip; the batch runs the dump front end of ctx.hip on a filter context).
 #include "dcn_ctx.h"
 #include "dcn_classify.h"
 #include "dcn_depth.h"
@@ -34,14 +34,7 @@ extern "C" int dcn_index_set_create(const dcn_index *const *members, uint32_t n,
     set->k = members[0]->k;
     set->w = members[0]->w;
     int rc = dcn_table_alloc(set, std::max<uint64_t>(sum, 16));
-    if (rc == DCN_OK) {
-        const uint64_t n_slots = set->n_groups * DCN_GROUP_SLOTS;
-        hipError_t e = hipMalloc((void **)&set->d_labels, n_slots * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemset(set->d_labels, 0, n_slots * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess)
-            rc = dcn_fail(e == hipErrorOutOfMemory ? DCN_ERR_NOMEM : DCN_ERR_HIP, std::string("index set labels: ") + hipGetErrorString(e));
-    }
+    if (rc == DCN_OK) rc = dev_alloc_zeroed(&set->d_labels, set->n_groups * DCN_GROUP_SLOTS, "index set labels");
     set->n_members = n;
     for (uint32_t i = 0; i < n && rc == DCN_OK; ++i) rc = dcn_set_add_member(set, members[i], i);
     if (rc != DCN_OK) {
@@ -101,16 +94,7 @@ extern "C" int dcn_index_set_coverage_enable(dcn_index *set, int enable) {
     }
     if (set->d_cov) return DCN_OK; // already on: the marks stay
     const uint64_t words = (set->n_groups * DCN_GROUP_SLOTS + 31) / 32;
-    uint32_t *d = nullptr;
-    hipError_t e = hipMalloc((void **)&d, (words + 1) * sizeof(uint32_t));
-    if (e != hipSuccess) return dcn_hip_fail(e, "coverage bitmap");
-    e = hipMemset(d, 0, (words + 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        hipFree(d);
-        return dcn_hip_fail(e, "coverage bitmap");
-    }
-    set->d_cov = d;
+    DCN_TRY(dev_alloc_zeroed(&set->d_cov, words + 1, "coverage bitmap"));
     set->cov_words = words;
     uint64_t keys[DCN_MAX_SET_MEMBERS] = {};
     int rc = coverage_counts(set, true, keys);
@@ -161,32 +145,29 @@ extern "C" int dcn_index_set_coverage_keys(const dcn_index *set, uint32_t member
     int rc = DCN_OK;
     const bool zero = zero_observed(set, &rc) && (set->zero_label & mask);
     DCN_TRY(rc);
-    unsigned long long *d_n = nullptr;
-    uint64_t *d_out = nullptr;
-    hipError_t e = hipMalloc((void **)&d_n, sizeof(unsigned long long));
+    const char *what = "coverage keys";
+    DevMem d_n, d_out;
+    DCN_TRY(d_n.alloc(sizeof(unsigned long long), true, what));
+    DCN_TRY(dcn_coverage_count_mask(set, mask, d_n.as<unsigned long long>(), 0));
     unsigned long long count = 0;
-    if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof(unsigned long long));
-    if (e == hipSuccess) rc = dcn_coverage_count_mask(set, mask, d_n, 0);
-    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(&count, d_n, sizeof(count), hipMemcpyDeviceToHost);
+    DCN_TRY(read_count(d_n, what, &count));
     const uint64_t total = count + (zero ? 1 : 0);
-    if (e == hipSuccess && rc == DCN_OK && total <= capacity && count > 0) {
-        e = hipMalloc((void **)&d_out, count * sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof(unsigned long long));
-        if (e == hipSuccess) rc = dcn_coverage_collect(set, mask, d_out, count, d_n, 0);
-        unsigned long long written = 0;
-        if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(&written, d_n, sizeof(written), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rc == DCN_OK && written != count)
-            rc = dcn_fail(DCN_ERR_INTERNAL, "coverage keys: the bitmap changed between the count and the copy (a classify call in flight?)");
-        if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(out, d_out, count * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    }
-    if (d_out) hipFree(d_out);
-    hipFree(d_n);
-    if (rc != DCN_OK) return rc;
-    if (e != hipSuccess) return dcn_hip_fail(e, "coverage keys");
-    *n = total;
-    if (total > capacity)
+    if (total > capacity) {
+        *n = total;
         return dcn_fail(DCN_ERR_CAPACITY, "coverage keys: " + std::to_string(total) + " observed keys, capacity " +
                                               std::to_string(capacity));
+    }
+    if (count > 0) {
+        DCN_TRY(d_out.alloc(count * sizeof(uint64_t), false, what));
+        DCN_TRY(d_n.clear(what));
+        DCN_TRY(dcn_coverage_collect(set, mask, d_out.as<uint64_t>(), count, d_n.as<unsigned long long>(), 0));
+        unsigned long long written = 0;
+        DCN_TRY(read_count(d_n, what, &written));
+        if (written != count)
+            return dcn_fail(DCN_ERR_INTERNAL, "coverage keys: the bitmap changed between the count and the copy (a classify call in flight?)");
+        DCN_TRY(d_out.read(out, count * sizeof(uint64_t), what));
+    }
+    *n = total;
     if (zero) out[count] = 0;
     return DCN_OK;
 }
@@ -196,23 +177,14 @@ int classify_check(dcn_ctx *ctx, const dcn_index *set, const dcn_params *params)
     if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
     DCN_TRY(check_set(set));
     DCN_TRY(check_params(params));
-    const dcn_index *ix = ctx->index;
-    if (ix->k != set->k || ix->w != set->w)
-        return dcn_fail(DCN_ERR_ARG, "the context's index (k=" + std::to_string((int)ix->k) + ", w=" + std::to_string((int)ix->w) +
-                                         ") and the set (k=" + std::to_string((int)set->k) + ", w=" + std::to_string((int)set->w) +
-                                         ") differ");
-    if (ix->device != set->device) return dcn_fail(DCN_ERR_ARG, "the context and the set live on different devices");
-    if (ix->variant != set->variant)
-        return dcn_fail(DCN_ERR_ARG, "the context's index and the set were created under different minimizer rules");
-    return check_idle(ctx);
+    return check_ctx_matches(ctx, set, "the set");
 }
 
 // the lazily allocated buffers of classification: the dump arrays, the work list and (host form) the outputs
 int classify_buffers(dcn_ctx *c, const dcn_index *set, bool host_outputs) {
     const uint32_t n_members = set->n_members;
     DCN_TRY(ensure_dump_buffers(c));
-    // depth: the batch's position bitmap (locate's, which allocates it the same way)
-    if (set->d_depth && !c->d_loc_bits) DCN_TRY(dev_alloc(&c->d_loc_bits, (c->max_bases + 31) / 32 + 1, "position bitmap"));
+    if (set->d_depth) DCN_TRY(ensure_position_bitmap(c)); // (the counting sweep's)
     if (!c->d_cls_big) {
         DCN_TRY(dev_alloc(&c->d_cls_big, c->max_reads, "classify work list"));
         DCN_TRY(dev_alloc(&c->d_cls_n_big, 1, "classify work list length"));
@@ -242,34 +214,17 @@ int classify_enqueue(dcn_ctx *c, const dcn_index *set, const uint8_t *d_ascii, c
     DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
     DCN_HIP(hipMemsetAsync(c->d_cls_n_big, 0, sizeof(uint32_t), st));
     int prof_slot = -1;
-    DCN_TRY(prof_begin(c, &prof_slot));
-    DCN_TRY(dcn_launch_pack(d_ascii, 0, n_bases, c->d_packed + DCN_FRONT_PAD, c->d_invmask + DCN_FRONT_PAD, c->d_status, st));
-    DCN_PROF_MARK(DCN_STAGE_PACK);
-    dcn_plan_args pa = plan_args(c, set, d_ascii, d_offsets, d_unit_id, n_reads, n_units, params->prefix_length);
-    pa.read_tiles = c->d_read_tiles;
-    pa.read_tile_first = c->d_read_tile_first;
-    pa.stream_bases = n_bases; // the device form's offsets have not been seen by the host: the plan kernel checks them
-    pa.check_offsets = 1;
-    pa.max_tiles = c->max_tiles;
-    DCN_TRY(dcn_launch_plan(pa, st));
-    DCN_PROF_MARK(DCN_STAGE_PLAN);
-    dcn_scan_args sa = dump_scan_args(c, set, n_bases);
-    sa.dump_abs = 1; // (the classification kernels do not look at positions; the depth sweep does)
-    DCN_TRY(dcn_launch_scan(sa, tile_bound(c, n_reads, n_bases), true, st));
-    DCN_PROF_MARK(DCN_STAGE_SCAN);
+    dcn_dump_view dump;
+    // (the device form's offsets have not been seen by the host: the plan kernel checks them.  The classification
+    // kernels do not look at the dump's positions; the depth sweep does.)
+    DCN_TRY(dump_front_end(c, set, d_ascii, d_offsets, d_unit_id, n_reads, n_units, n_bases, params->prefix_length, true,
+                           &prof_slot, &dump));
     if (set->d_depth) { // the counting sweep of depth.hip, timed with the lane kernel (no stage of its own: DCN_N_STAGES is ABI)
         DCN_HIP(hipMemsetAsync(c->d_loc_bits, 0, ((n_bases + 31) / 32 + 1) * sizeof(uint32_t), st));
         dcn_depth_args da;
         memset(&da, 0, sizeof(da));
         da.table = set->view();
-        da.tiles = c->d_tiles;
-        da.n_tiles = &c->d_status->n_tiles;
-        da.dump_hash = c->d_dump_hash;
-        da.dump_valid = c->d_dump_valid;
-        da.dump_pos = c->d_dump_pos;
-        da.dump_count = c->d_dump_count;
-        da.max_tiles = tile_bound(c, n_reads, n_bases);
-        da.n_bases = n_bases;
+        da.dump = dump;
         da.status = c->d_status;
         da.bits = c->d_loc_bits;
         da.depth = set->d_depth;
@@ -282,15 +237,15 @@ int classify_enqueue(dcn_ctx *c, const dcn_index *set, const uint8_t *d_ascii, c
     ca.labels = set->d_labels;
     ca.zero_label = set->zero_label;
     ca.n_members = set->n_members;
-    ca.tiles = c->d_tiles;
-    ca.n_tiles = &c->d_status->n_tiles;
+    ca.tiles = dump.tiles;
+    ca.n_tiles = dump.n_tiles;
     ca.offsets = d_offsets;
     ca.read_tiles = c->d_read_tiles;
     ca.read_tile_first = c->d_read_tile_first;
     ca.unit_first_read = d_unit_id ? c->d_unit_first_read : nullptr;
-    ca.dump_hash = c->d_dump_hash;
-    ca.dump_valid = c->d_dump_valid;
-    ca.dump_count = c->d_dump_count;
+    ca.dump_hash = dump.hash;
+    ca.dump_valid = dump.valid;
+    ca.dump_count = dump.count;
     ca.tile_windows = c->tile_windows;
     ca.n_units = n_units;
     ca.abs_threshold = params->abs_threshold;
@@ -308,13 +263,7 @@ int classify_enqueue(dcn_ctx *c, const dcn_index *set, const uint8_t *d_ascii, c
     DCN_PROF_MARK(DCN_STAGE_DISTINCT);
     DCN_TRY(dcn_launch_classify_big(ca, st));
     DCN_PROF_MARK(DCN_STAGE_FINISH);
-    if (prof_slot >= 0) c->prof_used[prof_slot] = true;
-    // a later device-pointer filter batch packs one batch ahead into these packed buffers on its own stream, after the
-    // events below: they now stand after this run
-    if (c->pack_ahead_state == 1) {
-        DCN_HIP(hipEventRecord(c->plan_done, st));
-        for (int i = 0; i < 2; ++i) DCN_HIP(hipEventRecord(c->buf_free[i], st));
-    }
+    DCN_TRY(record_run_end(c, prof_slot));
     c->batch_pending = true; // dcn_ctx_synchronize reports what the plan kernel found wrong with the batch
     return DCN_OK;
 }

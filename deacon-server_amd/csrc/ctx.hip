@@ -429,6 +429,19 @@ int check_idle(const dcn_ctx *c) {
     return DCN_OK;
 }
 
+int check_ctx_matches(const dcn_ctx *c, const dcn_index *other, const char *noun) {
+    const dcn_index *ix = c->index;
+    const std::string n = noun;
+    if (ix->k != other->k || ix->w != other->w)
+        return dcn_fail(DCN_ERR_ARG, "the context's index (k=" + std::to_string((int)ix->k) + ", w=" + std::to_string((int)ix->w) +
+                                         ") and " + n + " (k=" + std::to_string((int)other->k) + ", w=" + std::to_string((int)other->w) +
+                                         ") differ");
+    if (ix->device != other->device) return dcn_fail(DCN_ERR_ARG, "the context and " + n + " live on different devices");
+    if (ix->variant != other->variant)
+        return dcn_fail(DCN_ERR_ARG, "the context's index and " + n + " were created under different minimizer rules");
+    return check_idle(c);
+}
+
 int check_device_batch(const dcn_ctx *c, uint32_t n_reads, uint64_t n_bases, uint32_t n_units, const uint32_t *d_unit_id) {
     if (n_reads > c->max_reads) return dcn_fail(DCN_ERR_CAPACITY, "n_reads exceeds the context's max_batch_reads");
     if (n_bases > c->max_bases) return dcn_fail(DCN_ERR_CAPACITY, "n_bases exceeds the context's max_batch_bases");
@@ -462,6 +475,16 @@ int ensure_dump_buffers(dcn_ctx *c) {
     DCN_TRY(dev_alloc(&c->d_dump_valid, c->max_bases + 2, "dump_valid"));
     DCN_TRY(dev_alloc(&c->d_dump_count, c->max_tiles, "dump_count"));
     return DCN_OK;
+}
+
+int ensure_position_bitmap(dcn_ctx *c) {
+    if (c->d_loc_bits) return DCN_OK;
+    return dev_alloc(&c->d_loc_bits, (c->max_bases + 31) / 32 + 1, "position bitmap");
+}
+
+int ensure_position_words(dcn_ctx *c) {
+    if (c->d_loc_labels) return DCN_OK;
+    return dev_alloc(&c->d_loc_labels, c->max_bases + 2, "position words");
 }
 
 UnitScratch unit_scratch(const dcn_ctx *c) {
@@ -533,6 +556,63 @@ dcn_scan_args dump_scan_args(const dcn_ctx *c, const dcn_index *index, uint64_t 
 
 uint32_t tile_bound(const dcn_ctx *c, uint32_t n_reads, uint64_t n_bases) {
     return (uint32_t)std::min<uint64_t>((uint64_t)n_reads + n_bases / c->tile_windows + 1, c->max_tiles);
+}
+
+dcn_dump_view dump_view(const dcn_ctx *c, uint32_t max_tiles, uint64_t n_bases) {
+    dcn_dump_view v = {};
+    v.tiles = c->d_tiles;
+    v.n_tiles = &c->d_status->n_tiles;
+    v.hash = c->d_dump_hash;
+    v.valid = c->d_dump_valid;
+    v.pos = c->d_dump_pos;
+    v.count = c->d_dump_count;
+    v.max_tiles = max_tiles;
+    v.n_bases = n_bases;
+    return v;
+}
+
+int dump_front_end(dcn_ctx *c, const dcn_index *index, const uint8_t *d_ascii, const uint64_t *d_offsets,
+                   const uint32_t *d_unit_id, uint32_t n_reads, uint32_t n_units, uint64_t n_bases, uint64_t prefix_length,
+                   bool plan_checks_offsets, int *prof_slot_out, dcn_dump_view *view) {
+    hipStream_t st = c->stream;
+    int prof_slot = -1;
+    DCN_TRY(prof_begin(c, &prof_slot));
+    *prof_slot_out = prof_slot;
+    DCN_TRY(dcn_launch_pack(d_ascii, 0, n_bases, c->d_packed + DCN_FRONT_PAD, c->d_invmask + DCN_FRONT_PAD, c->d_status, st));
+    DCN_PROF_MARK(DCN_STAGE_PACK);
+    dcn_plan_args pa = plan_args(c, index, d_ascii, d_offsets, d_unit_id, n_reads, n_units, prefix_length);
+    pa.read_tiles = c->d_read_tiles;
+    pa.read_tile_first = c->d_read_tile_first;
+    if (plan_checks_offsets) { // (else check_offsets stays 0: validate_host_batch has walked the offsets on the host)
+        pa.stream_bases = n_bases;
+        pa.check_offsets = 1;
+        pa.max_tiles = c->max_tiles;
+    }
+    DCN_TRY(dcn_launch_plan(pa, st));
+    DCN_PROF_MARK(DCN_STAGE_PLAN);
+    dcn_scan_args sa = dump_scan_args(c, index, n_bases);
+    sa.dump_abs = 1;
+    const uint32_t max_tiles = tile_bound(c, n_reads, n_bases);
+    DCN_TRY(dcn_launch_scan(sa, max_tiles, true, st));
+    DCN_PROF_MARK(DCN_STAGE_SCAN);
+    *view = dump_view(c, max_tiles, n_bases);
+    return DCN_OK;
+}
+
+int record_run_end(dcn_ctx *c, int prof_slot) {
+    if (prof_slot >= 0) c->prof_used[prof_slot] = true;
+    // a later device-pointer filter batch packs one batch ahead into these packed buffers on its own stream, after the
+    // events below: they now stand after this run
+    if (c->pack_ahead_state == 1) {
+        DCN_HIP(hipEventRecord(c->plan_done, c->stream));
+        for (int i = 0; i < 2; ++i) DCN_HIP(hipEventRecord(c->buf_free[i], c->stream));
+    }
+    return DCN_OK;
+}
+
+int finish_run(dcn_ctx *c, int prof_slot) {
+    DCN_TRY(record_run_end(c, prof_slot));
+    return sync_and_check(c, nullptr);
 }
 
 dcn_distinct_args distinct_args(const dcn_ctx *c, uint32_t n_units, const dcn_params *params, const uint64_t *rec_hash,

@@ -1,9 +1,12 @@
 // dcn_ctx.h -- the filter context and what the files that implement the C ABI's host side share (internal, like
-// dcn_internal.h): api.hip (errors, indexes), ctx.hip (context, device-pointer batches, the stage builders),
-// host_batch.hip (submit / wait), dump.hip (minimizer dump, hash seam, index build), classify_api.hip (index sets),
-// locate_api.hip (segments), track_api.hip (depth tracks), place_api.hip (anchor maps, placement).
+// dcn_internal.h): api.hip (errors, indexes), ctx.hip (context, device-pointer batches, the stage builders, the dump
+// front end and the tail of a batch call), host_batch.hip (submit / wait), dump.hip (minimizer dump, hash seam, index
+// build), and the dump's consumers, which all run dump_front_end .. finish_run of ctx.hip around kernels that sweep
+// the dump as dcn_dump_sweep.h says: classify_api.hip (index sets; depth counters with depth_api.hip), locate_api.hip
+// (segments), track_api.hip (depth tracks), place_api.hip (anchor maps, placement).
 #pragma once
 
+#include "dcn_dump_sweep.h"
 #include "dcn_internal.h"
 #include "dcn_plan.h"
 
@@ -134,21 +137,24 @@ struct dcn_ctx {
     uint32_t *d_cls_big = nullptr, *d_cls_n_big = nullptr;
     uint32_t *d_cls_match = nullptr, *d_cls_hits = nullptr, *d_cls_total = nullptr;
     uint32_t cls_hits_members = 0;
-    // locate buffers (lazy, first dcn_locate_batch): the hit bitmap (a bit per base), the labels of the hits (a word per
-    // base, only once the index of a call is a set), per-read counts / offsets with the scan's block sums, the work list
+    // what the dump's consumers mark positions in (lazy: ensure_position_bitmap / ensure_position_words): a bit per base
+    // (locate's hits, the positions of track, place and the depth sweep) and a word per base (locate's labels on a set,
+    // track's values)
+    uint32_t *d_loc_bits = nullptr, *d_loc_labels = nullptr;
+    // locate buffers (lazy, first dcn_locate_batch): per-read counts / offsets with the scan's block sums, the work list
     // of the wave kernel, and the segment buffer (loc_seg_cap entries, grown to the largest count)
-    uint32_t *d_loc_bits = nullptr, *d_loc_labels = nullptr, *d_loc_counts = nullptr, *d_loc_big = nullptr, *d_loc_n_big = nullptr;
+    uint32_t *d_loc_counts = nullptr, *d_loc_big = nullptr, *d_loc_n_big = nullptr;
     unsigned long long *d_loc_block_sums = nullptr;
     uint64_t *d_loc_seg_offsets = nullptr;
     dcn_segment *d_loc_segs = nullptr;
     uint64_t loc_seg_cap = 0;
     // depth track buffers (lazy, first dcn_depth_track_batch): per-read bin and piece offsets, computed on the host, and
-    // the bins (trk_bin_cap entries, grown to the largest batch's count).  The bitmap and the word per base are locate's.
+    // the bins (trk_bin_cap entries, grown to the largest batch's count)
     uint64_t *d_trk_bin_offsets = nullptr, *d_trk_piece_offsets = nullptr;
     dcn_track_bin *d_trk_bins = nullptr;
     uint64_t trk_bin_cap = 0;
     // placement buffers (lazy, first dcn_place_batch): the anchor bitmap, one word per base (dcn_place.h), the work list
-    // of the workgroup kernel with its length, and the placements.  The position bitmap is locate's.
+    // of the workgroup kernel with its length, and the placements
     uint64_t *d_plc_words = nullptr;
     uint32_t *d_plc_abits = nullptr, *d_plc_big = nullptr, *d_plc_n_big = nullptr;
     dcn_placement *d_plc_out = nullptr;
@@ -197,6 +203,51 @@ int dev_alloc(T **p, uint64_t count, const char *what) {
     }
     return DCN_OK;
 }
+
+// `count` zeroed T on the current device, there when the call returns (state that lives with an index: a set's labels,
+// coverage bits and depth counters, a map's words); *p is null when it fails
+template <typename T>
+int dev_alloc_zeroed(T **p, uint64_t count, const char *what) {
+    *p = nullptr;
+    T *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, count * sizeof(T));
+    if (e == hipSuccess) e = hipMemset(d, 0, count * sizeof(T));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        if (d) hipFree(d);
+        return dcn_hip_fail(e, what);
+    }
+    *p = d;
+    return DCN_OK;
+}
+
+// device scratch that goes back on every way out
+struct DevMem {
+    void *p = nullptr;
+    ~DevMem() {
+        if (p) hipFree(p);
+    }
+    int alloc(uint64_t bytes, bool zero, const char *what) {
+        hipError_t e = hipMalloc(&p, std::max<uint64_t>(bytes, 8));
+        if (e == hipSuccess && zero) e = hipMemset(p, 0, std::max<uint64_t>(bytes, 8));
+        return e == hipSuccess ? DCN_OK : dcn_hip_fail(e, what);
+    }
+    int clear(const char *what) { // the first 8 bytes: a counter between two sweeps
+        const hipError_t e = hipMemset(p, 0, 8);
+        return e == hipSuccess ? DCN_OK : dcn_hip_fail(e, what);
+    }
+    int read(void *h, uint64_t bytes, const char *what) const { // (the copy waits for the null stream)
+        const hipError_t e = hipMemcpy(h, p, bytes, hipMemcpyDeviceToHost);
+        return e == hipSuccess ? DCN_OK : dcn_hip_fail(e, what);
+    }
+    template <typename T>
+    T *as() const {
+        return (T *)p;
+    }
+};
+
+// the counter of a sweep, after the sweep
+inline int read_count(const DevMem &d_n, const char *what, unsigned long long *n) { return d_n.read(n, sizeof(*n), what); }
 
 inline uint64_t packed_words(uint64_t max_bases) { return DCN_FRONT_PAD + 2 * ((max_bases + 31) / 32) + DCN_TAIL_PAD; }
 inline uint64_t mask_words(uint64_t max_bases) { return DCN_FRONT_PAD + (max_bases + 31) / 32 + DCN_TAIL_PAD; }
@@ -256,6 +307,9 @@ int slots_busy(const dcn_ctx *c);
 
 // ---- ctx.hip: argument checks shared by entry points (codes and messages are what callers see) ----
 int check_idle(const dcn_ctx *c); // no host batch in a slot, no device-pointer batch since the last synchronize
+// the context's index reads sequences as `other` does (k, w, minimizer rule), on its device, and the context is idle;
+// `noun` names `other` in the messages ("the set", "the map")
+int check_ctx_matches(const dcn_ctx *c, const dcn_index *other, const char *noun);
 int check_device_batch(const dcn_ctx *c, uint32_t n_reads, uint64_t n_bases, uint32_t n_units, const uint32_t *d_unit_id);
 // offsets[0] == 0, non-decreasing, no entry over 2^32: `noun` names the array, `too_long` is that last message whole
 int check_offsets_walk(const uint64_t *offsets, uint32_t n, const char *noun, const char *too_long);
@@ -265,6 +319,8 @@ int validate_host_batch(const dcn_ctx *c, const uint64_t *offsets, uint32_t n_re
 // ---- ctx.hip: one builder per stage.  Each writes the fields every caller sets alike; what differs between callers
 // is set at the call site, and a field a caller leaves out stays zero. ----
 int ensure_dump_buffers(dcn_ctx *c); // the four arrays of a dump-mode scan, allocated on first use
+int ensure_position_bitmap(dcn_ctx *c); // d_loc_bits: a bit per base of the largest batch (+ a word), on first use
+int ensure_position_words(dcn_ctx *c);  // d_loc_labels: a word per base, on first use
 struct UnitScratch { // d_unit_scratch, max_reads words each
     uint32_t *g_total, *g_hitcnt, *g_distinct, *g_zero;
 };
@@ -280,6 +336,21 @@ dcn_plan_args plan_args(const dcn_ctx *c, const dcn_index *index, const uint8_t 
 // a scan of the context's packed stream in dump mode; left to the caller: tile_read_pos, dump_abs
 dcn_scan_args dump_scan_args(const dcn_ctx *c, const dcn_index *index, uint64_t n_bases);
 uint32_t tile_bound(const dcn_ctx *c, uint32_t n_reads, uint64_t n_bases); // launch bound of a scan: tiles the plan can cut
+// the plan and the dump that a dump-mode scan of the context leaves, as the kernels of dcn_dump_sweep.h take them
+dcn_dump_view dump_view(const dcn_ctx *c, uint32_t max_tiles, uint64_t n_bases);
+
+// ---- ctx.hip: a batch call that consumes the minimizer dump (classify, depth, locate, track, anchor add, place) ----
+// Begins the run's profile slot (*prof_slot, -1: none) and enqueues pack -> plan -> scan in dump mode with batch-absolute
+// positions on c->stream; *view is what the scan leaves.  The batch is device memory; d_unit_id may be null.
+// plan_checks_offsets: the host has not walked the offsets, the plan kernel does (classification).
+int dump_front_end(dcn_ctx *c, const dcn_index *index, const uint8_t *d_ascii, const uint64_t *d_offsets,
+                   const uint32_t *d_unit_id, uint32_t n_reads, uint32_t n_units, uint64_t n_bases, uint64_t prefix_length,
+                   bool plan_checks_offsets, int *prof_slot, dcn_dump_view *view);
+// what follows the last kernel of such a call: the profile slot is in use, and the events a later device-pointer filter
+// batch waits for stand after this run ...
+int record_run_end(dcn_ctx *c, int prof_slot);
+// ... then the wait, and what the device reported
+int finish_run(dcn_ctx *c, int prof_slot);
 dcn_distinct_args distinct_args(const dcn_ctx *c, uint32_t n_units, const dcn_params *params, const uint64_t *rec_hash,
                                 uint32_t rec_shift, uint32_t *g_total_or_null);
 dcn_finish_args finish_args(const dcn_ctx *c, uint32_t n_units, const dcn_params *params, const uint32_t *unit_first_read,

@@ -5,10 +5,9 @@
 // key 0, which has no slot.  A counter saturates at 65,535.  2 B per slot: 8 GiB at the panhuman-sized set.
 #pragma once
 
-#include "dcn_internal.h"
+#include "dcn_dump_sweep.h"
 
-constexpr uint32_t DCN_DEPTH_THREADS = 256;
-constexpr uint32_t DCN_DEPTH_TILE_LANES = 16; // lanes per tile of the counting sweep, as locate's mark kernel
+constexpr uint32_t DCN_DEPTH_THREADS = 256; // (the read-out sweeps; the counting sweep's geometry is dcn_dump_sweep.h's)
 constexpr uint32_t DCN_DEPTH_MAX = 0xFFFFu;
 constexpr uint32_t DCN_DEPTH_MAX_BINS = 4096;
 
@@ -25,17 +24,10 @@ __device__ inline void dcn_depth_add(uint32_t *word, uint32_t shift) {
     }
 }
 
-// the counting sweep over the minimizer dump of a batch (scan_kernel<..., DUMP = true> with dump_abs = 1)
+// the counting sweep over the minimizer dump of a batch
 struct dcn_depth_args {
     dcn_table_view table; // the set's slots
-    const dcn_tile *tiles;
-    const uint32_t *n_tiles;
-    const uint64_t *dump_hash;
-    const uint8_t *dump_valid;
-    const uint32_t *dump_pos;   // low 32 bits of the minimizer's base index in the batch stream
-    const uint32_t *dump_count; // per tile: entries at [scan_start + carry, + count)
-    uint32_t max_tiles;         // launch bound
-    uint64_t n_bases;
+    dcn_dump_view dump;
     const dcn_status *status; // bad_offsets: the plan refused the batch, nothing is counted
     uint32_t *bits;           // one bit per base of the batch stream, zero before the sweep: a position counts once
     uint32_t *depth;          // the set's counters

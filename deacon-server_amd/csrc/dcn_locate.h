@@ -1,12 +1,10 @@
 // dcn_locate.h -- the kernels behind dcn_locate_batch (locate.hip; not part of the public ABI).
 #pragma once
 
-#include "dcn_internal.h"
+#include "dcn_dump_sweep.h"
 
-// mark: DCN_LOC_TILE_LANES lanes walk one tile's dump entries (a short read's tile has ~14, a full tile of 256 windows
-// ~32), so a wave sweeps four tiles with coalesced loads and 64 probes in flight.
+// (the mark kernel is a dump sweep: its geometry is dcn_dump_sweep.h's)
 constexpr uint32_t DCN_LOC_THREADS = 256;
-constexpr uint32_t DCN_LOC_TILE_LANES = 16;
 // segments: a read of at most this many bases is walked by one lane, bit by bit; a longer one by one wave, a bitmap word
 // per lane, which needs every word to hold hits of one segment only: k + max_gap >= 31 (else every read takes the lane path)
 constexpr uint32_t DCN_LOC_LANE_BASES = 1024;
@@ -19,15 +17,7 @@ struct dcn_locate_args {
     const uint32_t *labels; // one member mask per slot (a labelled set); null: a plain index, every hit's label is 1
     uint32_t zero_label;    // key 0's mask (plain index: has_zero)
     uint32_t member_mask;   // ~0 for a plain index
-    // plan + minimizer dump of the batch (scan_kernel<..., DUMP = true> with dump_abs = 1)
-    const dcn_tile *tiles;
-    const uint32_t *n_tiles;
-    const uint64_t *dump_hash;
-    const uint8_t *dump_valid;
-    const uint32_t *dump_pos;   // low 32 bits of the minimizer's base index in the batch stream
-    const uint32_t *dump_count; // per tile: entries at [scan_start + carry, + count)
-    uint32_t max_tiles;         // launch bound of the mark kernel
-    uint64_t n_bases;
+    dcn_dump_view dump;
     const uint64_t *offsets; // n_reads + 1
     uint32_t n_reads;
     uint32_t k;

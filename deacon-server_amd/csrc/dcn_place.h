@@ -2,11 +2,10 @@
 // part of the public ABI).
 #pragma once
 
-#include "dcn_internal.h"
+#include "dcn_dump_sweep.h"
 
-// mark sweeps: DCN_PLC_TILE_LANES lanes walk one tile's dump entries, as locate's and track's mark kernels
+// (the add and mark kernels are dump sweeps: their geometry is dcn_dump_sweep.h's)
 constexpr uint32_t DCN_PLC_THREADS = 256;
-constexpr uint32_t DCN_PLC_TILE_LANES = 16;
 
 // The word of a slot of an anchor map (dcn_index::d_anchor; key 0's word follows the slots' words):
 //   DCN_ANCHOR_EMPTY   no occurrence of the key among the records added so far
@@ -46,15 +45,7 @@ struct dcn_place_args {
     uint32_t first_record;  // add: record number of read 0 of the batch
     const uint32_t *packed; // 2-bit stream of the batch (offset by DCN_FRONT_PAD words)
     const dcn_status *status;
-    // plan + minimizer dump of the batch (scan_kernel<..., DUMP = true> with dump_abs = 1)
-    const dcn_tile *tiles;
-    const uint32_t *n_tiles;
-    const uint64_t *dump_hash;
-    const uint8_t *dump_valid;
-    const uint32_t *dump_pos;
-    const uint32_t *dump_count;
-    uint32_t max_tiles;
-    uint64_t n_bases;
+    dcn_dump_view dump;
     const uint64_t *offsets; // n_reads + 1
     uint32_t n_reads;
     // placement

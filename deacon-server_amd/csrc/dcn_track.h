@@ -2,11 +2,10 @@
 #pragma once
 
 #include "dcn_depth.h"
-#include "dcn_internal.h"
+#include "dcn_dump_sweep.h"
 
-// mark: DCN_TRK_TILE_LANES lanes walk one tile's dump entries, as locate's mark kernel and the depth counting sweep
+// (the mark kernel is a dump sweep: its geometry is dcn_dump_sweep.h's)
 constexpr uint32_t DCN_TRK_THREADS = 256;
-constexpr uint32_t DCN_TRK_TILE_LANES = 16;
 // value[p] of a marked position p: 0 = its hash is no key under the mask, else DCN_TRK_KEY | depth (capped)
 constexpr uint32_t DCN_TRK_KEY = 0x10000u;
 // reduce: a read whose widest bin (min(bin_bases, its length); its length when bin_bases == 0) has at most this many
@@ -26,15 +25,7 @@ struct dcn_track_args {
     const uint32_t *depth;      // the set's counters: read, never written
     const uint32_t *depth_zero; // key 0's word (null: key 0 is not in the set)
     uint32_t depth_cap;         // 0: none
-    // plan + minimizer dump of the batch (scan_kernel<..., DUMP = true> with dump_abs = 1)
-    const dcn_tile *tiles;
-    const uint32_t *n_tiles;
-    const uint64_t *dump_hash;
-    const uint8_t *dump_valid;
-    const uint32_t *dump_pos;   // low 32 bits of the minimizer's base index in the batch stream
-    const uint32_t *dump_count; // per tile: entries at [scan_start + carry, + count)
-    uint32_t max_tiles;         // launch bound of the mark kernel
-    uint64_t n_bases;
+    dcn_dump_view dump;
     const uint64_t *offsets; // n_reads + 1
     uint32_t n_reads;
     uint32_t bin_bases;            // 0: one bin per read

@@ -1,12 +1,11 @@
 // depth.hip -- how often each key of a labelled set occurred among the minimizers classify calls counted
 // (dcn_index_set_depth_*; the definition is in include/deacon_hip.h, the layout in dcn_depth.h).
 //
-// Runs behind the front end of classification (pack -> plan -> scan in dump mode with batch-absolute positions), beside
-// the classification kernels and without touching them:
-//   depth_count_kernel  a flat sweep over the dump entries, DCN_DEPTH_TILE_LANES lanes per tile, shaped like
-//                       locate_mark_kernel: find the entry's slot (dcn_table_find_slot); on a hit claim the entry's
-//                       position in the batch's position bitmap (test, then atomicOr: the lane that finds the bit clear
-//                       owns the position) and add 1 to the slot's 16-bit counter, saturating.  The dump may hold a
+// Runs behind the dump front end (dump_front_end, ctx.hip: pack -> plan -> scan in dump mode with batch-absolute
+// positions), beside the classification kernels and without touching them:
+//   depth_count_kernel  the flat sweep over the dump entries (dcn_dump_sweep.h): find the entry's slot
+//                       (dcn_table_find_slot); on a hit claim the entry's position in the batch's position bitmap
+//                       (dcn_bit_claim) and add 1 to the slot's 16-bit counter, saturating.  The dump may hold a
 //                       position more than once (two windows of a read can choose the same k-mer with another between
 //                       them; the classification totals count both), an occurrence is a (read, position) pair: hence
 //                       the bitmap rather than a count of entries.
@@ -21,43 +20,26 @@
 
 namespace {
 
-__global__ __launch_bounds__(DCN_DEPTH_THREADS) void depth_count_kernel(dcn_depth_args a) {
+__global__ __launch_bounds__(DCN_SWEEP_THREADS) void depth_count_kernel(dcn_depth_args a) {
     if (a.status->bad_offsets) return; // the scan looked at no tile: the dump is not this batch's
-    const uint64_t gid = (uint64_t)blockIdx.x * DCN_DEPTH_THREADS + threadIdx.x;
-    const uint64_t tile = gid / DCN_DEPTH_TILE_LANES;
-    const uint32_t sub = (uint32_t)(gid % DCN_DEPTH_TILE_LANES);
-    if (tile >= *a.n_tiles) return;
-    const dcn_tile t = a.tiles[tile];
-    const uint64_t base = t.scan_start + t.carry();
-    if (base >= a.n_bases) return;
-    // (an entry's slot is at or before its window's first base: never past the stream)
-    const uint32_t cnt = (uint32_t)min((uint64_t)a.dump_count[tile], a.n_bases - base);
-    for (uint32_t e = sub; e < cnt; e += DCN_DEPTH_TILE_LANES) {
-        const uint64_t s = base + e;
-        if (!a.dump_valid[s]) continue;
-        const uint64_t h = a.dump_hash[s];
+    dcn_for_dump_entries(a.dump, [&](uint64_t s) {
+        const uint64_t h = a.dump.hash[s];
         uint32_t *word;
         uint32_t shift = 0;
         if (h == 0) {
-            if (!a.depth_zero) continue;
+            if (!a.depth_zero) return;
             word = a.depth_zero;
         } else {
             const uint32_t g = dcn_group_of(h, a.table.group_shift, a.table.group_mask);
             const uint64_t at = dcn_table_find_slot(a.table, h, g, dcn_load_group(a.table, g));
-            if (at == ~0ull) continue;
+            if (at == ~0ull) return;
             word = a.depth + (at >> 1);
             shift = (uint32_t)(at & 1) * 16;
         }
-        // the minimizer of a window lies at or after the window's start, which is at or after its slot: the low 32 bits
-        // of the position and the slot give the position
-        const uint64_t p = s + (uint32_t)(a.dump_pos[s] - (uint32_t)s);
-        if (p >= a.n_bases) continue;
-        uint32_t *pw = a.bits + (p >> 5);
-        const uint32_t bit = 1u << (p & 31);
-        if (*pw & bit) continue;                // (bits are only ever set during the sweep: a set bit seen is set)
-        if (atomicOr(pw, bit) & bit) continue;  // another entry of this position was first
-        dcn_depth_add(word, shift);
-    }
+        const uint64_t p = dcn_dump_position(a.dump, s);
+        if (p >= a.dump.n_bases) return;
+        if (dcn_bit_claim(a.bits, p)) dcn_depth_add(word, shift);
+    });
 }
 
 // ---- sweeps -------------------------------------------------------------------------------------------------------
@@ -205,13 +187,7 @@ uint32_t depth_blocks(uint64_t n_slots) {
 } // namespace
 
 int dcn_launch_depth_count(const dcn_depth_args &a, hipStream_t stream) {
-    if (a.max_tiles == 0) return DCN_OK;
-    const uint64_t threads = (uint64_t)a.max_tiles * DCN_DEPTH_TILE_LANES;
-    const uint64_t blocks = (threads + DCN_DEPTH_THREADS - 1) / DCN_DEPTH_THREADS;
-    if (blocks > 0x7FFFFFFFull) return dcn_fail(DCN_ERR_INTERNAL, "depth: tile count");
-    hipLaunchKernelGGL(depth_count_kernel, dim3((uint32_t)blocks), dim3(DCN_DEPTH_THREADS), 0, stream, a);
-    DCN_HIP(hipGetLastError());
-    return DCN_OK;
+    return dcn_launch_dump_sweep(depth_count_kernel, a, "depth: tile count", stream);
 }
 
 int dcn_depth_stats(const dcn_index *set, unsigned long long *d_out, hipStream_t stream) {

@@ -44,16 +44,7 @@ extern "C" int dcn_index_set_depth_enable(dcn_index *set, int enable) {
     }
     if (set->d_depth) return DCN_OK; // already on: the counts stay
     const uint64_t words = (set->n_groups * DCN_GROUP_SLOTS + 1) / 2;
-    uint32_t *d = nullptr;
-    hipError_t e = hipMalloc((void **)&d, (words + 1) * sizeof(uint32_t));
-    if (e != hipSuccess) return dcn_hip_fail(e, "depth counters"); // (the set is as it was)
-    e = hipMemset(d, 0, (words + 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        hipFree(d);
-        return dcn_hip_fail(e, "depth counters");
-    }
-    set->d_depth = d;
+    DCN_TRY(dev_alloc_zeroed(&set->d_depth, words + 1, "depth counters")); // (on failure the set is as it was)
     set->depth_words = words;
     return DCN_OK;
 }
@@ -113,37 +104,31 @@ extern "C" int dcn_index_set_depth_keys(const dcn_index *set, uint32_t member, u
     uint32_t d0 = 0;
     DCN_TRY(zero_depth(set, &d0));
     const bool zero = d0 && (set->zero_label & mask);
-    unsigned long long *d_n = nullptr;
-    uint64_t *d_keys = nullptr;
-    uint32_t *d_depths = nullptr;
-    int rc = DCN_OK;
-    hipError_t e = hipMalloc((void **)&d_n, sizeof(unsigned long long));
+    const char *what = "depth keys";
+    DevMem d_n, d_keys, d_depths;
+    DCN_TRY(d_n.alloc(sizeof(unsigned long long), true, what));
+    DCN_TRY(dcn_depth_keys(set, mask, nullptr, nullptr, 0, d_n.as<unsigned long long>(), 0));
     unsigned long long count = 0;
-    if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof(unsigned long long));
-    if (e == hipSuccess) rc = dcn_depth_keys(set, mask, nullptr, nullptr, 0, d_n, 0);
-    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(&count, d_n, sizeof(count), hipMemcpyDeviceToHost);
+    DCN_TRY(read_count(d_n, what, &count));
     const uint64_t total = count + (zero ? 1 : 0);
-    if (e == hipSuccess && rc == DCN_OK && total <= capacity && count > 0) {
-        e = hipMalloc((void **)&d_keys, count * sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_depths, count * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof(unsigned long long));
-        if (e == hipSuccess) rc = dcn_depth_keys(set, mask, d_keys, d_depths, count, d_n, 0);
-        unsigned long long written = 0;
-        if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(&written, d_n, sizeof(written), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rc == DCN_OK && written != count)
-            rc = dcn_fail(DCN_ERR_INTERNAL, "depth keys: the counters changed between the count and the copy (a classify call in flight?)");
-        if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(keys, d_keys, count * sizeof(uint64_t), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(depths, d_depths, count * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    }
-    if (d_keys) hipFree(d_keys);
-    if (d_depths) hipFree(d_depths);
-    if (d_n) hipFree(d_n);
-    if (rc != DCN_OK) return rc;
-    if (e != hipSuccess) return dcn_hip_fail(e, "depth keys");
-    *n = total;
-    if (total > capacity)
+    if (total > capacity) {
+        *n = total;
         return dcn_fail(DCN_ERR_CAPACITY, "depth keys: " + std::to_string(total) + " observed keys, capacity " +
                                               std::to_string(capacity));
+    }
+    if (count > 0) {
+        DCN_TRY(d_keys.alloc(count * sizeof(uint64_t), false, what));
+        DCN_TRY(d_depths.alloc(count * sizeof(uint32_t), false, what));
+        DCN_TRY(d_n.clear(what));
+        DCN_TRY(dcn_depth_keys(set, mask, d_keys.as<uint64_t>(), d_depths.as<uint32_t>(), count, d_n.as<unsigned long long>(), 0));
+        unsigned long long written = 0;
+        DCN_TRY(read_count(d_n, what, &written));
+        if (written != count)
+            return dcn_fail(DCN_ERR_INTERNAL, "depth keys: the counters changed between the count and the copy (a classify call in flight?)");
+        DCN_TRY(d_keys.read(keys, count * sizeof(uint64_t), what));
+        DCN_TRY(d_depths.read(depths, count * sizeof(uint32_t), what));
+    }
+    *n = total;
     if (zero) {
         keys[count] = 0;
         depths[count] = d0;

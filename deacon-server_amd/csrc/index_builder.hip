@@ -4,8 +4,8 @@
 // Runs behind the index side's front end (pack with the index-side codes -> plan -> scan in dump mode with chunk-absolute
 // positions), where the plain build runs insert_dump_kernel:
 //   builder_count_kernel  a flat grid-stride sweep over all slots of dump_valid, as insert_dump_kernel.  Per valid entry that
-//                         passes the entropy floor: claim the entry's position in the chunk's position bitmap (test, then
-//                         atomicOr: the lane that finds the bit clear owns the position), make the key a member
+//                         passes the entropy floor: claim the entry's position in the chunk's position bitmap
+//                         (dcn_bit_claim, dcn_dump_sweep.h), make the key a member
 //                         (dcn_table_insert_dev gives the slot) and add 1 to the slot's 16-bit counter, saturating.  The dump
 //                         may hold a position more than once (two windows can choose the same k-mer with another between
 //                         them; two pieces of a cut sequence can choose the same k-mer of their overlap): an occurrence is a
@@ -44,10 +44,7 @@ __global__ __launch_bounds__(DCN_BUILDER_THREADS) void builder_count_kernel(dcn_
         const uint64_t p = a.dump_pos[i];
         if (p + a.k > a.n_bases) continue; // (a k-mer of the chunk lies inside it)
         if (a.entropy_threshold != 0.0f && scaled_entropy_dev(a.ascii + p, a.k) < a.entropy_threshold) continue;
-        uint32_t *pw = a.bits + (p >> 5);
-        const uint32_t bit = 1u << (p & 31);
-        if (*pw & bit) continue;               // (bits are only ever set during the sweep: a set bit seen is set)
-        if (atomicOr(pw, bit) & bit) continue; // another entry of this position was first
+        if (!dcn_bit_claim(a.bits, p)) continue;
         ++occ;
         const uint64_t key = a.dump_hash[i];
         if (key == 0) {

@@ -1,9 +1,10 @@
 // locate.hip -- where in each read the index matched (dcn_locate_batch; the definition is in include/deacon_hip.h).
 //
-// Runs behind the front end of classification (pack -> plan -> scan in dump mode with batch-absolute positions):
-//   locate_mark_kernel      a flat sweep over the dump entries, DCN_LOC_TILE_LANES lanes per tile: probe the table (for a
+// Runs behind the dump front end (dump_front_end, ctx.hip: pack -> plan -> scan in dump mode with batch-absolute
+// positions):
+//   locate_mark_kernel      the flat sweep over the dump entries (dcn_dump_sweep.h): probe the table (for a
 //                           set: read the label of the slot that matched) and, on a hit that passes member_mask, set bit
-//                           `position` of the batch's hit bitmap (test, then atomicOr) and, for a set, store the label at
+//                           `position` of the batch's hit bitmap (dcn_bit_mark) and, for a set, store the label at
 //                           label_scratch[position].  No per-read state: a position that several windows emitted is one
 //                           bit, which is the "counts once" of the definition.
 //   locate_segments_kernel  read r's segments from its slice [offsets[r], offsets[r+1]) of the bitmap.  A hit starts a
@@ -42,38 +43,15 @@ __device__ inline uint32_t loc_label(const dcn_locate_args &a, uint64_t key) {
     }
 }
 
-__global__ __launch_bounds__(DCN_LOC_THREADS) void locate_mark_kernel(dcn_locate_args a) {
-    const uint64_t gid = (uint64_t)blockIdx.x * DCN_LOC_THREADS + threadIdx.x;
-    const uint64_t tile = gid / DCN_LOC_TILE_LANES;
-    const uint32_t sub = (uint32_t)(gid % DCN_LOC_TILE_LANES);
-    if (tile >= *a.n_tiles) return;
-    const dcn_tile t = a.tiles[tile];
-    const uint64_t base = t.scan_start + t.carry();
-    if (base >= a.n_bases) return;
-    // (an entry's slot is at or before its window's first base: never past the stream)
-    const uint32_t cnt = (uint32_t)min((uint64_t)a.dump_count[tile], a.n_bases - base);
-    for (uint32_t e = sub; e < cnt; e += DCN_LOC_TILE_LANES) {
-        const uint64_t s = base + e;
-        if (!a.dump_valid[s]) continue;
-        const uint32_t L = loc_label(a, a.dump_hash[s]) & a.member_mask;
-        if (!L) continue;
-        // the minimizer of a window lies at or after the window's start, which is at or after its slot: the low 32 bits
-        // of the position and the slot give the position
-        const uint64_t p = s + (uint32_t)(a.dump_pos[s] - (uint32_t)s);
-        if (p >= a.n_bases) continue;
-        uint32_t *word = a.bits + (p >> 5);
-        const uint32_t bit = 1u << (p & 31);
-        if (!(*word & bit)) atomicOr(word, bit);
+__global__ __launch_bounds__(DCN_SWEEP_THREADS) void locate_mark_kernel(dcn_locate_args a) {
+    dcn_for_dump_entries(a.dump, [&](uint64_t s) {
+        const uint32_t L = loc_label(a, a.dump.hash[s]) & a.member_mask;
+        if (!L) return;
+        const uint64_t p = dcn_dump_position(a.dump, s);
+        if (p >= a.dump.n_bases) return;
+        dcn_bit_mark(a.bits, p);
         if (a.labels) a.label_scratch[p] = L; // (windows that share a position share its hash: the same value)
-    }
-}
-
-// word wi of the bitmap, cut to the bits of [o0, o1)
-__device__ inline uint32_t loc_word(const dcn_locate_args &a, uint64_t wi, uint64_t o0, uint64_t o1) {
-    uint32_t word = a.bits[wi];
-    if (wi == (o0 >> 5)) word &= ~0u << (o0 & 31);
-    if (wi == (o1 >> 5)) word &= ~(~0u << (o1 & 31)); // (o1 a multiple of 32: its word is past the read and not loaded)
-    return word;
+    });
 }
 
 __device__ inline uint32_t loc_word_labels(const dcn_locate_args &a, uint64_t wi, uint32_t word) {
@@ -117,7 +95,7 @@ __global__ __launch_bounds__(DCN_LOC_THREADS) void locate_segments_kernel(dcn_lo
     uint32_t start = 0, last = 0, cnt = 0, lab = 0;
     if (o1 > o0) {
         for (uint64_t wi = o0 >> 5; wi <= ((o1 - 1) >> 5); ++wi) {
-            for (uint32_t word = loc_word(a, wi, o0, o1); word; word &= word - 1) {
+            for (uint32_t word = dcn_bits_cut(a.bits, wi, o0, o1); word; word &= word - 1) {
                 const uint64_t q = wi * 32 + (__ffs(word) - 1);
                 const uint32_t p = (uint32_t)(q - o0), L = a.labels ? a.label_scratch[q] : 1u;
                 if (open && p - last <= a.join) {
@@ -155,7 +133,7 @@ __global__ __launch_bounds__(DCN_LOC_THREADS) void locate_segments_wave_kernel(d
         uint32_t c_start = 0, c_last = 0, c_cnt = 0, c_lab = 0;
         for (uint64_t wb = o0 >> 5; wb <= w1; wb += DCN_WAVE) {
             const uint64_t wi = wb + lane;
-            const uint32_t word = wi <= w1 ? loc_word(a, wi, o0, o1) : 0u;
+            const uint32_t word = wi <= w1 ? dcn_bits_cut(a.bits, wi, o0, o1) : 0u;
             const bool ne = word != 0;
             const uint32_t f = ne ? (uint32_t)(wi * 32 + (__ffs(word) - 1) - o0) : 0u;
             const uint32_t l = ne ? (uint32_t)(wi * 32 + (31 - __clz(word)) - o0) : 0u;
@@ -291,13 +269,7 @@ uint32_t loc_wave_blocks(uint32_t n_reads) {
 } // namespace
 
 int dcn_launch_locate_mark(const dcn_locate_args &a, hipStream_t stream) {
-    if (a.max_tiles == 0) return DCN_OK;
-    const uint64_t threads = (uint64_t)a.max_tiles * DCN_LOC_TILE_LANES;
-    const uint64_t blocks = (threads + DCN_LOC_THREADS - 1) / DCN_LOC_THREADS;
-    if (blocks > 0x7FFFFFFFull) return dcn_fail(DCN_ERR_INTERNAL, "locate: tile count");
-    hipLaunchKernelGGL(locate_mark_kernel, dim3((uint32_t)blocks), dim3(DCN_LOC_THREADS), 0, stream, a);
-    DCN_HIP(hipGetLastError());
-    return DCN_OK;
+    return dcn_launch_dump_sweep(locate_mark_kernel, a, "locate: tile count", stream);
 }
 
 int dcn_launch_locate_count(const dcn_locate_args &a, hipStream_t stream) {

@@ -1,5 +1,5 @@
 // locate_api.hip -- the C ABI of dcn_locate_batch: the segments of every read of a host batch (kernels in locate.hip;
-// the batch runs pack -> plan -> scan in dump mode on a filter context, as classification does).
+// the batch runs the dump front end of ctx.hip on a filter context).
 #include "dcn_ctx.h"
 #include "dcn_locate.h"
 
@@ -16,21 +16,12 @@ int locate_check(dcn_ctx *ctx, const dcn_index *index, const dcn_locate_params *
     if (!seg_offsets) return dcn_fail(DCN_ERR_ARG, "seg_offsets is NULL");
     if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
     if (!index) return dcn_fail(DCN_ERR_ARG, "index is NULL");
-    const dcn_index *ix = ctx->index;
-    if (ix->k != index->k || ix->w != index->w)
-        return dcn_fail(DCN_ERR_ARG, "the context's index (k=" + std::to_string((int)ix->k) + ", w=" + std::to_string((int)ix->w) +
-                                         ") and the set (k=" + std::to_string((int)index->k) + ", w=" + std::to_string((int)index->w) +
-                                         ") differ");
-    if (ix->device != index->device) return dcn_fail(DCN_ERR_ARG, "the context and the set live on different devices");
-    if (ix->variant != index->variant)
-        return dcn_fail(DCN_ERR_ARG, "the context's index and the set were created under different minimizer rules");
-    return check_idle(ctx);
+    return check_ctx_matches(ctx, index, "the set"); // (also where `index` is a plain index: the messages are ABI)
 }
 
 int locate_buffers(dcn_ctx *c, bool labelled) {
     DCN_TRY(ensure_dump_buffers(c));
-    // (the bitmap alone may be there already: a classify call against a set with depth counters uses it too)
-    if (!c->d_loc_bits) DCN_TRY(dev_alloc(&c->d_loc_bits, (c->max_bases + 31) / 32 + 1, "locate hit bitmap"));
+    DCN_TRY(ensure_position_bitmap(c));
     if (!c->d_loc_counts) {
         DCN_TRY(dev_alloc(&c->d_loc_counts, c->max_reads, "locate counts"));
         DCN_TRY(dev_alloc(&c->d_loc_block_sums, (uint64_t)c->max_reads / DCN_LOC_SCAN_BLOCK + 1, "locate block sums"));
@@ -38,7 +29,7 @@ int locate_buffers(dcn_ctx *c, bool labelled) {
         DCN_TRY(dev_alloc(&c->d_loc_big, c->max_reads, "locate work list"));
         DCN_TRY(dev_alloc(&c->d_loc_n_big, 1, "locate work list length"));
     }
-    if (labelled && !c->d_loc_labels) DCN_TRY(dev_alloc(&c->d_loc_labels, c->max_bases + 2, "locate labels"));
+    if (labelled) DCN_TRY(ensure_position_words(c));
     return DCN_OK;
 }
 
@@ -75,34 +66,14 @@ extern "C" int dcn_locate_batch(dcn_ctx *ctx, const dcn_index *index, const uint
     DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
     DCN_HIP(hipMemsetAsync(c->d_loc_bits, 0, ((n_bases + 31) / 32 + 1) * sizeof(uint32_t), st));
     int prof_slot = -1;
-    DCN_TRY(prof_begin(c, &prof_slot));
-    DCN_TRY(dcn_launch_pack(c->d_ascii, 0, n_bases, c->d_packed + DCN_FRONT_PAD, c->d_invmask + DCN_FRONT_PAD, c->d_status, st));
-    DCN_PROF_MARK(DCN_STAGE_PACK);
-    // (check_offsets stays 0: validate_host_batch has walked the offsets on the host)
-    dcn_plan_args pa = plan_args(c, index, c->d_ascii, c->d_offsets, nullptr, n_reads, n_reads, prm->prefix_length);
-    pa.read_tiles = c->d_read_tiles;
-    pa.read_tile_first = c->d_read_tile_first;
-    DCN_TRY(dcn_launch_plan(pa, st));
-    DCN_PROF_MARK(DCN_STAGE_PLAN);
-    dcn_scan_args sa = dump_scan_args(c, index, n_bases);
-    sa.dump_abs = 1;
-    const uint32_t max_tiles = tile_bound(c, n_reads, n_bases);
-    DCN_TRY(dcn_launch_scan(sa, max_tiles, true, st));
-    DCN_PROF_MARK(DCN_STAGE_SCAN);
     dcn_locate_args la;
     memset(&la, 0, sizeof(la));
+    DCN_TRY(dump_front_end(c, index, c->d_ascii, c->d_offsets, nullptr, n_reads, n_reads, n_bases, prm->prefix_length, false,
+                           &prof_slot, &la.dump));
     la.table = index->view();
     la.labels = labelled ? index->d_labels : nullptr;
     la.zero_label = labelled ? index->zero_label : (index->has_zero ? 1u : 0u);
     la.member_mask = labelled ? prm->member_mask : ~0u;
-    la.tiles = c->d_tiles;
-    la.n_tiles = &c->d_status->n_tiles;
-    la.dump_hash = c->d_dump_hash;
-    la.dump_valid = c->d_dump_valid;
-    la.dump_pos = c->d_dump_pos;
-    la.dump_count = c->d_dump_count;
-    la.max_tiles = max_tiles;
-    la.n_bases = n_bases;
     la.offsets = c->d_offsets;
     la.n_reads = n_reads;
     la.k = index->k;
@@ -124,14 +95,7 @@ extern "C" int dcn_locate_batch(dcn_ctx *ctx, const dcn_index *index, const uint
     DCN_TRY(dcn_launch_locate_count(la, st));
     DCN_TRY(dcn_launch_locate_write(la, st));
     DCN_PROF_MARK(DCN_STAGE_FINISH);
-    if (prof_slot >= 0) c->prof_used[prof_slot] = true;
-    // a later device-pointer filter batch packs one batch ahead into these packed buffers on its own stream, after the
-    // events below: they now stand after this run
-    if (c->pack_ahead_state == 1) {
-        DCN_HIP(hipEventRecord(c->plan_done, st));
-        for (int i = 0; i < 2; ++i) DCN_HIP(hipEventRecord(c->buf_free[i], st));
-    }
-    DCN_TRY(sync_and_check(c, nullptr));
+    DCN_TRY(finish_run(c, prof_slot));
     DCN_HIP(hipMemcpy(seg_offsets, c->d_loc_seg_offsets, ((uint64_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
     const uint64_t total = seg_offsets[n_reads];
     if (total > capacity)

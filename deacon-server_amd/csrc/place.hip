@@ -1,10 +1,10 @@
 // place.hip -- anchor maps (dcn_anchor_map_*) and placement (dcn_place_batch); the definitions are in
 // include/deacon_hip.h, the word layouts in dcn_place.h.
 //
-// Both run behind the front end of locate (pack -> plan -> scan in dump mode with batch-absolute positions):
-//   place_sweep_kernel<true>  (add) a flat sweep over the dump entries, DCN_PLC_TILE_LANES lanes per tile, shaped like
-//                         locate_mark_kernel: a valid entry whose hash is a key of the map computes (record, position,
-//                         strand bit) and moves the slot's word EMPTY -> value -> REPEAT: atomicCAS(EMPTY, v) sets it, an
+// Both run behind the dump front end (dump_front_end, ctx.hip: pack -> plan -> scan in dump mode with batch-absolute
+// positions):
+//   place_sweep_kernel<true>  (add) the flat sweep over the dump entries (dcn_dump_sweep.h): a valid entry whose hash
+//                         is a key of the map computes (record, position, strand bit) and moves the slot's word EMPTY -> value -> REPEAT: atomicCAS(EMPTY, v) sets it, an
 //                         old word that is neither EMPTY nor v makes the lane store REPEAT (an atomicMax: REPEAT is the
 //                         largest word).  The same (record, position) emitted twice is the same v: one occurrence.
 //   anchor_tally_kernel / anchor_export_kernel
@@ -51,17 +51,6 @@ __device__ inline uint32_t plc_strand(const uint32_t *packed, uint64_t p, uint32
     return (hi < bhi || (hi == bhi && lo <= blo)) ? 1u : 0u;
 }
 
-// the read that owns base p of the stream: the last r with off[r] <= p (p < off[n])
-__device__ inline uint32_t plc_owner(const uint64_t *off, uint32_t n, uint64_t p) {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (off[mid] <= p) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // the word of the key `h` in the map (null: not a key)
 __device__ inline uint64_t *plc_word_of(const dcn_place_args &a, uint64_t h) {
     if (h == 0) return a.table.has_zero ? a.anchor + a.n_slots : nullptr;
@@ -71,30 +60,17 @@ __device__ inline uint64_t *plc_word_of(const dcn_place_args &a, uint64_t h) {
 }
 
 template <bool ADD>
-__global__ __launch_bounds__(DCN_PLC_THREADS) void place_sweep_kernel(dcn_place_args a) {
+__global__ __launch_bounds__(DCN_SWEEP_THREADS) void place_sweep_kernel(dcn_place_args a) {
     if (a.status->bad_offsets) return; // the scan looked at no tile: the dump is not this batch's
-    const uint64_t gid = (uint64_t)blockIdx.x * DCN_PLC_THREADS + threadIdx.x;
-    const uint64_t tile = gid / DCN_PLC_TILE_LANES;
-    const uint32_t sub = (uint32_t)(gid % DCN_PLC_TILE_LANES);
-    if (tile >= *a.n_tiles) return;
-    const dcn_tile t = a.tiles[tile];
-    const uint64_t base = t.scan_start + t.carry();
-    if (base >= a.n_bases) return;
-    // (an entry's slot is at or before its window's first base: never past the stream)
-    const uint32_t cnt = (uint32_t)min((uint64_t)a.dump_count[tile], a.n_bases - base);
-    for (uint32_t e = sub; e < cnt; e += DCN_PLC_TILE_LANES) {
-        const uint64_t s = base + e;
-        if (!a.dump_valid[s]) continue;
-        // the minimizer of a window lies at or after the window's start, which is at or after its slot: the low 32 bits
-        // of the position and the slot give the position
-        const uint64_t p = s + (uint32_t)(a.dump_pos[s] - (uint32_t)s);
-        if (p >= a.n_bases) continue;
-        uint64_t *word = plc_word_of(a, a.dump_hash[s]);
+    dcn_for_dump_entries(a.dump, [&](uint64_t s) {
+        const uint64_t p = dcn_dump_position(a.dump, s);
+        if (p >= a.dump.n_bases) return;
+        uint64_t *word = plc_word_of(a, a.dump.hash[s]);
         if (ADD) {
-            if (!word) continue;
-            const uint32_t r = plc_owner(a.offsets, a.n_reads, p);
+            if (!word) return;
+            const uint32_t r = dcn_owner_of(a.offsets, a.n_reads, p);
             const uint64_t v = dcn_anchor_word(a.first_record + r, (uint32_t)(p - a.offsets[r]), plc_strand(a.packed, p, a.k));
-            if (*word == DCN_ANCHOR_REPEAT) continue; // (a word never leaves REPEAT)
+            if (*word == DCN_ANCHOR_REPEAT) return; // (a word never leaves REPEAT)
             const uint64_t old = atomicCAS(reinterpret_cast<unsigned long long *>(word), (unsigned long long)DCN_ANCHOR_EMPTY,
                                            (unsigned long long)v);
             if (old != DCN_ANCHOR_EMPTY && old != v && old != DCN_ANCHOR_REPEAT)
@@ -105,16 +81,13 @@ __global__ __launch_bounds__(DCN_PLC_THREADS) void place_sweep_kernel(dcn_place_
                 const uint64_t w = *word;
                 if (dcn_anchor_is_value(w)) v = w ^ (uint64_t)plc_strand(a.packed, p, a.k);
             }
-            uint32_t *bw = a.bits + (p >> 5);
-            const uint32_t bit = 1u << (p & 31);
-            if (!(*bw & bit)) atomicOr(bw, bit);
+            dcn_bit_mark(a.bits, p);
             if (v) { // (windows that share a position share its hash: the same word)
-                uint32_t *aw = a.abits + (p >> 5);
-                if (!(*aw & bit)) atomicOr(aw, bit);
+                dcn_bit_mark(a.abits, p);
                 a.words[p] = v;
             }
         }
-    }
+    });
 }
 
 // ---- sweeps over a map's words ------------------------------------------------------------------------------------
@@ -163,14 +136,6 @@ __global__ __launch_bounds__(DCN_PLC_THREADS) void anchor_export_kernel(const ui
 }
 
 // ---- vote ---------------------------------------------------------------------------------------------------------
-// word wi of the bitmap, cut to the bits of [b0, b1)
-__device__ inline uint32_t plc_bits(const uint32_t *bits, uint64_t wi, uint64_t b0, uint64_t b1) {
-    uint32_t word = bits[wi];
-    if (wi == (b0 >> 5)) word &= ~0u << (b0 & 31);
-    if (wi == (b1 >> 5)) word &= ~(~0u << (b1 & 31)); // (b1 a multiple of 32: its word is past the range and not loaded)
-    return word;
-}
-
 // an anchor hit of a read: the word of base p = o0 + q of a read of len bases
 struct plc_hit {
     uint32_t rec1; // record + 1
@@ -239,13 +204,13 @@ __global__ __launch_bounds__(DCN_PLC_THREADS) void place_lane_kernel(dcn_place_a
     if (len > 0) {
         const uint64_t w0 = o0 >> 5, w1 = (o1 - 1) >> 5;
         for (uint64_t wi = w0; wi <= w1; ++wi) { // the two counts first
-            n_positions += __popc(plc_bits(a.bits, wi, o0, o1));
-            n_anchors += __popc(plc_bits(a.abits, wi, o0, o1));
+            n_positions += __popc(dcn_bits_cut(a.bits, wi, o0, o1));
+            n_anchors += __popc(dcn_bits_cut(a.abits, wi, o0, o1));
         }
         // A cell that holds every anchor hit of the read ends the search: a cell that holds them all holds the hit it was
         // found from, h, so it is one of h's two cells, and both have been compared (the common case: a read of one place).
         for (uint64_t wi = w0; wi <= w1 && best.votes < n_anchors; ++wi) {
-            uint32_t word = plc_bits(a.abits, wi, o0, o1);
+            uint32_t word = dcn_bits_cut(a.abits, wi, o0, o1);
             for (; word && best.votes < n_anchors; word &= word - 1) {
                 const uint64_t p = wi * 32 + (__ffs(word) - 1);
                 const uint64_t v = a.words[p];
@@ -255,7 +220,7 @@ __global__ __launch_bounds__(DCN_PLC_THREADS) void place_lane_kernel(dcn_place_a
                 uint32_t c_lo = 0, c_hi = 0;
                 plc_extent x_lo, x_hi;
                 for (uint64_t vi = w0; vi <= w1; ++vi) {
-                    uint32_t inner = plc_bits(a.abits, vi, o0, o1);
+                    uint32_t inner = dcn_bits_cut(a.abits, vi, o0, o1);
                     for (; inner; inner &= inner - 1) {
                         const uint64_t p2 = vi * 32 + (__ffs(inner) - 1);
                         const uint64_t v2 = a.words[p2];
@@ -326,7 +291,7 @@ __global__ __launch_bounds__(DCN_PLC_THREADS) void place_big_kernel(dcn_place_ar
                 }
                 __syncthreads();
                 for (uint64_t wi = w0 + tid; wi <= w1; wi += DCN_PLC_THREADS) {
-                    uint32_t word = plc_bits(a.abits, wi, o0, o1);
+                    uint32_t word = dcn_bits_cut(a.abits, wi, o0, o1);
                     for (; word; word &= word - 1) {
                         const uint64_t p = wi * 32 + (__ffs(word) - 1);
                         const uint64_t v = a.words[p];
@@ -400,8 +365,8 @@ __global__ __launch_bounds__(DCN_PLC_THREADS) void place_big_kernel(dcn_place_ar
         uint32_t n_anchors = 0, n_positions = 0;
         plc_extent x;
         for (uint64_t wi = w0 + tid; wi <= w1; wi += DCN_PLC_THREADS) {
-            n_positions += __popc(plc_bits(a.bits, wi, o0, o1));
-            uint32_t word = plc_bits(a.abits, wi, o0, o1);
+            n_positions += __popc(dcn_bits_cut(a.bits, wi, o0, o1));
+            uint32_t word = dcn_bits_cut(a.abits, wi, o0, o1);
             n_anchors += __popc(word);
             for (; word; word &= word - 1) {
                 const uint64_t p = wi * 32 + (__ffs(word) - 1);
@@ -437,21 +402,14 @@ uint32_t plc_sweep_blocks(uint64_t n) {
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + DCN_PLC_THREADS - 1) / DCN_PLC_THREADS, (uint64_t)plc_cus() * 8));
 }
 
-template <bool ADD>
-int plc_launch_sweep(const dcn_place_args &a, hipStream_t stream) {
-    if (a.max_tiles == 0) return DCN_OK;
-    const uint64_t threads = (uint64_t)a.max_tiles * DCN_PLC_TILE_LANES;
-    const uint64_t blocks = (threads + DCN_PLC_THREADS - 1) / DCN_PLC_THREADS;
-    if (blocks > 0x7FFFFFFFull) return dcn_fail(DCN_ERR_INTERNAL, "place: tile count");
-    hipLaunchKernelGGL(place_sweep_kernel<ADD>, dim3((uint32_t)blocks), dim3(DCN_PLC_THREADS), 0, stream, a);
-    DCN_HIP(hipGetLastError());
-    return DCN_OK;
-}
-
 } // namespace
 
-int dcn_launch_anchor_add(const dcn_place_args &a, hipStream_t stream) { return plc_launch_sweep<true>(a, stream); }
-int dcn_launch_place_mark(const dcn_place_args &a, hipStream_t stream) { return plc_launch_sweep<false>(a, stream); }
+int dcn_launch_anchor_add(const dcn_place_args &a, hipStream_t stream) {
+    return dcn_launch_dump_sweep(place_sweep_kernel<true>, a, "place: tile count", stream);
+}
+int dcn_launch_place_mark(const dcn_place_args &a, hipStream_t stream) {
+    return dcn_launch_dump_sweep(place_sweep_kernel<false>, a, "place: tile count", stream);
+}
 
 int dcn_anchor_tally(const dcn_index *map, unsigned long long *d_tally, hipStream_t stream) {
     const uint64_t n_words = map->n_groups * DCN_GROUP_SLOTS + 1;

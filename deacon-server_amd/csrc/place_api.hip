@@ -1,5 +1,5 @@
 // place_api.hip -- the C ABI of anchor maps (dcn_anchor_map_*) and dcn_place_batch (kernels in place.hip; both batch
-// calls run locate's front end, pack -> plan -> scan in dump mode, on a filter context).
+// calls run the dump front end of ctx.hip on a filter context).
 #include "dcn_ctx.h"
 #include "dcn_place.h"
 
@@ -17,19 +17,6 @@ int check_map(const dcn_index *map) {
     return DCN_OK;
 }
 
-// the context's index reads sequences as the map does, on the map's device; the context is idle
-int check_ctx(const dcn_ctx *ctx, const dcn_index *map) {
-    const dcn_index *ix = ctx->index;
-    if (ix->k != map->k || ix->w != map->w)
-        return dcn_fail(DCN_ERR_ARG, "the context's index (k=" + std::to_string((int)ix->k) + ", w=" + std::to_string((int)ix->w) +
-                                         ") and the map (k=" + std::to_string((int)map->k) + ", w=" + std::to_string((int)map->w) +
-                                         ") differ");
-    if (ix->device != map->device) return dcn_fail(DCN_ERR_ARG, "the context and the map live on different devices");
-    if (ix->variant != map->variant)
-        return dcn_fail(DCN_ERR_ARG, "the context's index and the map were created under different minimizer rules");
-    return check_idle(ctx);
-}
-
 // a test hook of the vote: `name` as a number within [lo, hi], else `dflt`
 uint32_t env_u32(const char *name, uint32_t dflt, uint32_t lo, uint32_t hi) {
     const char *s = std::getenv(name);
@@ -38,53 +25,21 @@ uint32_t env_u32(const char *name, uint32_t dflt, uint32_t lo, uint32_t hi) {
     return (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>(v, lo), hi);
 }
 
-// pack -> plan -> dump scan of a staged batch on the context's stream, and the fields of `pa` that describe its dump
-int front_end(dcn_ctx *c, const dcn_index *map, uint32_t n_reads, uint64_t n_bases, uint64_t prefix_length, int prof_slot,
+// the dump front end over a staged batch, and the fields of `pa` that both sweeps read
+int front_end(dcn_ctx *c, const dcn_index *map, uint32_t n_reads, uint64_t n_bases, uint64_t prefix_length, int *prof_slot,
               dcn_place_args *pa) {
-    hipStream_t st = c->stream;
-    DCN_TRY(dcn_launch_pack(c->d_ascii, 0, n_bases, c->d_packed + DCN_FRONT_PAD, c->d_invmask + DCN_FRONT_PAD, c->d_status, st));
-    DCN_PROF_MARK(DCN_STAGE_PACK);
-    // (check_offsets stays 0: validate_host_batch has walked the offsets on the host)
-    dcn_plan_args pl = plan_args(c, map, c->d_ascii, c->d_offsets, nullptr, n_reads, n_reads, prefix_length);
-    pl.read_tiles = c->d_read_tiles;
-    pl.read_tile_first = c->d_read_tile_first;
-    DCN_TRY(dcn_launch_plan(pl, st));
-    DCN_PROF_MARK(DCN_STAGE_PLAN);
-    dcn_scan_args sa = dump_scan_args(c, map, n_bases);
-    sa.dump_abs = 1;
-    const uint32_t max_tiles = tile_bound(c, n_reads, n_bases);
-    DCN_TRY(dcn_launch_scan(sa, max_tiles, true, st));
-    DCN_PROF_MARK(DCN_STAGE_SCAN);
     memset(pa, 0, sizeof(*pa));
+    DCN_TRY(dump_front_end(c, map, c->d_ascii, c->d_offsets, nullptr, n_reads, n_reads, n_bases, prefix_length, false, prof_slot,
+                           &pa->dump));
     pa->table = map->view();
     pa->anchor = map->d_anchor;
     pa->n_slots = map->n_groups * DCN_GROUP_SLOTS;
     pa->k = map->k;
     pa->packed = c->d_packed + DCN_FRONT_PAD;
     pa->status = c->d_status;
-    pa->tiles = c->d_tiles;
-    pa->n_tiles = &c->d_status->n_tiles;
-    pa->dump_hash = c->d_dump_hash;
-    pa->dump_valid = c->d_dump_valid;
-    pa->dump_pos = c->d_dump_pos;
-    pa->dump_count = c->d_dump_count;
-    pa->max_tiles = max_tiles;
-    pa->n_bases = n_bases;
     pa->offsets = c->d_offsets;
     pa->n_reads = n_reads;
     return DCN_OK;
-}
-
-// what follows the last kernel of a batch call: the events a later device-pointer filter batch waits for, then the wait
-int finish_run(dcn_ctx *c, int prof_slot) {
-    if (prof_slot >= 0) c->prof_used[prof_slot] = true;
-    // a later device-pointer filter batch packs one batch ahead into these packed buffers on its own stream, after the
-    // events below: they now stand after this run
-    if (c->pack_ahead_state == 1) {
-        DCN_HIP(hipEventRecord(c->plan_done, c->stream));
-        for (int i = 0; i < 2; ++i) DCN_HIP(hipEventRecord(c->buf_free[i], c->stream));
-    }
-    return sync_and_check(c, nullptr);
 }
 } // namespace
 
@@ -95,17 +50,12 @@ extern "C" int dcn_anchor_map_create(const dcn_index *index, dcn_index **out) {
     dcn_index *map = nullptr;
     DCN_TRY(dcn_index_clone(index, index->device, &map)); // (a plain index over the keys, on the same device)
     const uint64_t words = map->n_groups * DCN_GROUP_SLOTS + 1;
-    uint64_t *d = nullptr;
-    hipError_t e = hipSetDevice(map->device);
-    if (e == hipSuccess) e = hipMalloc((void **)&d, words * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMemset(d, 0, words * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        if (d) hipFree(d);
+    const hipError_t e = hipSetDevice(map->device);
+    const int rc = e == hipSuccess ? dev_alloc_zeroed(&map->d_anchor, words, "anchor words") : dcn_hip_fail(e, "anchor words");
+    if (rc != DCN_OK) {
         dcn_index_destroy(map);
-        return dcn_hip_fail(e, "anchor words");
+        return rc;
     }
-    map->d_anchor = d;
     map->anchor_records = 0;
     *out = map;
     return DCN_OK;
@@ -115,7 +65,7 @@ extern "C" int dcn_anchor_map_add(dcn_index *map, dcn_ctx *ctx, const uint8_t *b
                                   uint32_t n_records, uint32_t *first_record) {
     DCN_TRY(check_map(map));
     if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
-    DCN_TRY(check_ctx(ctx, map));
+    DCN_TRY(check_ctx_matches(ctx, map, "the map"));
     if (first_record) *first_record = map->anchor_records;
     if (n_records == 0) return DCN_OK;
     if (!offsets) return dcn_fail(DCN_ERR_ARG, "offsets is NULL");
@@ -134,9 +84,8 @@ extern "C" int dcn_anchor_map_add(dcn_index *map, dcn_ctx *ctx, const uint8_t *b
     hipStream_t st = c->stream;
     DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
     int prof_slot = -1;
-    DCN_TRY(prof_begin(c, &prof_slot));
     dcn_place_args pa;
-    DCN_TRY(front_end(c, map, n_records, n_bases, 0, prof_slot, &pa));
+    DCN_TRY(front_end(c, map, n_records, n_bases, 0, &prof_slot, &pa));
     pa.first_record = map->anchor_records;
     DCN_TRY(dcn_launch_anchor_add(pa, st));
     DCN_PROF_MARK(DCN_STAGE_DISTINCT);
@@ -174,29 +123,21 @@ extern "C" int dcn_anchor_map_anchors(const dcn_index *map, uint64_t *keys, uint
     if (total > capacity)
         return dcn_fail(DCN_ERR_CAPACITY, "anchors: " + std::to_string(total) + " anchors, capacity " + std::to_string(capacity));
     if (total == 0) return DCN_OK;
-    unsigned long long *d_n = nullptr;
-    uint64_t *d_keys = nullptr;
-    uint32_t *d_rec = nullptr, *d_pos = nullptr;
-    int rc = DCN_OK;
+    const char *what = "anchors";
+    DevMem d_n, d_keys, d_rec, d_pos;
+    DCN_TRY(d_n.alloc(sizeof(unsigned long long), true, what));
+    DCN_TRY(d_keys.alloc(total * sizeof(uint64_t), false, what));
+    DCN_TRY(d_rec.alloc(total * sizeof(uint32_t), false, what));
+    DCN_TRY(d_pos.alloc(total * sizeof(uint32_t), false, what));
+    DCN_TRY(dcn_anchor_export(map, d_keys.as<uint64_t>(), d_rec.as<uint32_t>(), d_pos.as<uint32_t>(), total,
+                              d_n.as<unsigned long long>(), 0));
     unsigned long long written = 0;
-    hipError_t e = hipMalloc((void **)&d_n, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(d_n, 0, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_keys, total * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_rec, total * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_pos, total * sizeof(uint32_t));
-    if (e == hipSuccess) rc = dcn_anchor_export(map, d_keys, d_rec, d_pos, total, d_n, 0);
-    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(&written, d_n, sizeof(written), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == DCN_OK && written != total)
-        rc = dcn_fail(DCN_ERR_INTERNAL, "anchors: the map changed between the count and the copy (an add call in flight?)");
-    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(keys, d_keys, total * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(records, d_rec, total * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == DCN_OK) e = hipMemcpy(positions, d_pos, total * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (d_keys) hipFree(d_keys);
-    if (d_rec) hipFree(d_rec);
-    if (d_pos) hipFree(d_pos);
-    if (d_n) hipFree(d_n);
-    if (rc != DCN_OK) return rc;
-    return e == hipSuccess ? DCN_OK : dcn_hip_fail(e, "anchors");
+    DCN_TRY(read_count(d_n, what, &written));
+    if (written != total)
+        return dcn_fail(DCN_ERR_INTERNAL, "anchors: the map changed between the count and the copy (an add call in flight?)");
+    DCN_TRY(d_keys.read(keys, total * sizeof(uint64_t), what));
+    DCN_TRY(d_rec.read(records, total * sizeof(uint32_t), what));
+    return d_pos.read(positions, total * sizeof(uint32_t), what);
 }
 
 extern "C" int dcn_place_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets,
@@ -209,7 +150,7 @@ extern "C" int dcn_place_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t
     if (prm->min_votes == 0) return dcn_fail(DCN_ERR_ARG, "params.min_votes must be at least 1");
     if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
     DCN_TRY(check_map(map));
-    DCN_TRY(check_ctx(ctx, map));
+    DCN_TRY(check_ctx_matches(ctx, map, "the map"));
     if (n_reads == 0) return DCN_OK;
     if (!offsets) return dcn_fail(DCN_ERR_ARG, "offsets is NULL");
     if (!placements) return dcn_fail(DCN_ERR_ARG, "placements is NULL");
@@ -219,7 +160,7 @@ extern "C" int dcn_place_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t
     dcn_ctx *c = ctx;
     DCN_HIP(hipSetDevice(c->device));
     DCN_TRY(ensure_dump_buffers(c));
-    if (!c->d_loc_bits) DCN_TRY(dev_alloc(&c->d_loc_bits, (c->max_bases + 31) / 32 + 1, "position bitmap"));
+    DCN_TRY(ensure_position_bitmap(c));
     if (!c->d_plc_abits) DCN_TRY(dev_alloc(&c->d_plc_abits, (c->max_bases + 31) / 32 + 1, "anchor bitmap"));
     if (!c->d_plc_words) DCN_TRY(dev_alloc(&c->d_plc_words, c->max_bases + 2, "placement words"));
     if (!c->d_plc_big) DCN_TRY(dev_alloc(&c->d_plc_big, c->max_reads, "placement work list"));
@@ -232,9 +173,8 @@ extern "C" int dcn_place_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t
     DCN_HIP(hipMemsetAsync(c->d_plc_abits, 0, ((n_bases + 31) / 32 + 1) * sizeof(uint32_t), st));
     DCN_HIP(hipMemsetAsync(c->d_plc_n_big, 0, sizeof(uint32_t), st));
     int prof_slot = -1;
-    DCN_TRY(prof_begin(c, &prof_slot));
     dcn_place_args pa;
-    DCN_TRY(front_end(c, map, n_reads, n_bases, prm->prefix_length, prof_slot, &pa));
+    DCN_TRY(front_end(c, map, n_reads, n_bases, prm->prefix_length, &prof_slot, &pa));
     pa.band = prm->band_bases;
     pa.min_votes = prm->min_votes;
     pa.lane_bases = env_u32("DCN_PLACE_LANE_BASES", DCN_PLC_LANE_BASES, 0, 0xFFFFFFFFu);

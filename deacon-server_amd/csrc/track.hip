@@ -1,10 +1,11 @@
 // track.hip -- depth tracks: per bin of every read, a summary of the set's depth counters at the read's minimizer
 // positions (dcn_depth_track_batch; the definition is in include/deacon_hip.h).
 //
-// Runs behind the front end of locate (pack -> plan -> scan in dump mode with batch-absolute positions):
-//   track_mark_kernel    a flat sweep over the dump entries, DCN_TRK_TILE_LANES lanes per tile, shaped like
-//                        locate_mark_kernel: every valid entry sets bit `position` of the batch's position bitmap (test,
-//                        then atomicOr), finds its slot (dcn_table_find_slot) and stores value[position] = 0 when the hash
+// Runs behind the dump front end (dump_front_end, ctx.hip: pack -> plan -> scan in dump mode with batch-absolute
+// positions):
+//   track_mark_kernel    the flat sweep over the dump entries (dcn_dump_sweep.h): every valid entry sets bit
+//                        `position` of the batch's position bitmap (dcn_bit_mark), finds its slot
+//                        (dcn_table_find_slot) and stores value[position] = 0 when the hash
 //                        is no key under the mask, else DCN_TRK_KEY | the slot's counter (capped).  Entries that repeat a
 //                        position store the same word.  Nothing of the set is written.
 //   track_bins_kernel    one lane per bin: a bin of a read of the lane path (dcn_track.h) is walked word by word, the first
@@ -19,24 +20,11 @@
 
 namespace {
 
-__global__ __launch_bounds__(DCN_TRK_THREADS) void track_mark_kernel(dcn_track_args a) {
-    const uint64_t gid = (uint64_t)blockIdx.x * DCN_TRK_THREADS + threadIdx.x;
-    const uint64_t tile = gid / DCN_TRK_TILE_LANES;
-    const uint32_t sub = (uint32_t)(gid % DCN_TRK_TILE_LANES);
-    if (tile >= *a.n_tiles) return;
-    const dcn_tile t = a.tiles[tile];
-    const uint64_t base = t.scan_start + t.carry();
-    if (base >= a.n_bases) return;
-    // (an entry's slot is at or before its window's first base: never past the stream)
-    const uint32_t cnt = (uint32_t)min((uint64_t)a.dump_count[tile], a.n_bases - base);
-    for (uint32_t e = sub; e < cnt; e += DCN_TRK_TILE_LANES) {
-        const uint64_t s = base + e;
-        if (!a.dump_valid[s]) continue;
-        // the minimizer of a window lies at or after the window's start, which is at or after its slot: the low 32 bits
-        // of the position and the slot give the position
-        const uint64_t p = s + (uint32_t)(a.dump_pos[s] - (uint32_t)s);
-        if (p >= a.n_bases) continue;
-        const uint64_t h = a.dump_hash[s];
+__global__ __launch_bounds__(DCN_SWEEP_THREADS) void track_mark_kernel(dcn_track_args a) {
+    dcn_for_dump_entries(a.dump, [&](uint64_t s) {
+        const uint64_t p = dcn_dump_position(a.dump, s);
+        if (p >= a.dump.n_bases) return;
+        const uint64_t h = a.dump.hash[s];
         uint32_t v = 0;
         if (h == 0) {
             if (a.depth_zero && (a.zero_label & a.member_mask)) v = DCN_TRK_KEY | (*a.depth_zero & DCN_DEPTH_MAX);
@@ -47,30 +35,9 @@ __global__ __launch_bounds__(DCN_TRK_THREADS) void track_mark_kernel(dcn_track_a
                 v = DCN_TRK_KEY | ((a.depth[at >> 1] >> ((uint32_t)(at & 1) * 16)) & DCN_DEPTH_MAX);
         }
         if (v && a.depth_cap) v = DCN_TRK_KEY | min(v & DCN_DEPTH_MAX, a.depth_cap);
-        uint32_t *word = a.bits + (p >> 5);
-        const uint32_t bit = 1u << (p & 31);
-        if (!(*word & bit)) atomicOr(word, bit);
+        dcn_bit_mark(a.bits, p);
         a.value[p] = v; // (windows that share a position share its hash: the same value)
-    }
-}
-
-// the read that owns item i of a prefix array off[0 .. n]: the last r with off[r] <= i (i < off[n])
-__device__ inline uint32_t trk_owner(const uint64_t *off, uint32_t n, uint64_t i) {
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (off[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// word wi of the bitmap, cut to the bits of [b0, b1)
-__device__ inline uint32_t trk_word(const dcn_track_args &a, uint64_t wi, uint64_t b0, uint64_t b1) {
-    uint32_t word = a.bits[wi];
-    if (wi == (b0 >> 5)) word &= ~0u << (b0 & 31);
-    if (wi == (b1 >> 5)) word &= ~(~0u << (b1 & 31)); // (b1 a multiple of 32: its word is past the range and not loaded)
-    return word;
+    });
 }
 
 struct trk_acc {
@@ -94,13 +61,13 @@ __device__ inline void trk_add_word(const dcn_track_args &a, uint64_t wi, uint32
 __global__ __launch_bounds__(DCN_TRK_THREADS) void track_bins_kernel(dcn_track_args a) {
     const uint64_t i = (uint64_t)blockIdx.x * DCN_TRK_THREADS + threadIdx.x;
     if (i >= a.n_bins) return;
-    const uint32_t r = trk_owner(a.bin_offsets, a.n_reads, i);
+    const uint32_t r = dcn_owner_of(a.bin_offsets, a.n_reads, i);
     const uint64_t o0 = a.offsets[r], o1 = a.offsets[r + 1];
     const uint64_t bw = dcn_track_bin_width(o1 - o0, a.bin_bases);
     trk_acc c;
     if (bw <= DCN_TRK_LANE_BASES && bw > 0) { // (a wider bin is zeroed here and filled by its pieces)
         const uint64_t b0 = o0 + (i - a.bin_offsets[r]) * bw, b1 = min(b0 + bw, o1);
-        for (uint64_t wi = b0 >> 5; wi <= ((b1 - 1) >> 5); ++wi) trk_add_word(a, wi, trk_word(a, wi, b0, b1), c);
+        for (uint64_t wi = b0 >> 5; wi <= ((b1 - 1) >> 5); ++wi) trk_add_word(a, wi, dcn_bits_cut(a.bits, wi, b0, b1), c);
     }
     dcn_track_bin out;
     out.n_positions = c.n_pos;
@@ -116,7 +83,7 @@ __global__ __launch_bounds__(DCN_TRK_THREADS) void track_pieces_kernel(dcn_track
     const uint32_t lane = threadIdx.x & (DCN_WAVE - 1);
     const uint32_t waves = DCN_TRK_THREADS / DCN_WAVE;
     for (uint64_t q = (uint64_t)blockIdx.x * waves + threadIdx.x / DCN_WAVE; q < a.n_pieces; q += (uint64_t)gridDim.x * waves) {
-        const uint32_t r = trk_owner(a.piece_offsets, a.n_reads, q);
+        const uint32_t r = dcn_owner_of(a.piece_offsets, a.n_reads, q);
         const uint64_t o0 = a.offsets[r], o1 = a.offsets[r + 1];
         const uint64_t bw = dcn_track_bin_width(o1 - o0, a.bin_bases); // (> DCN_TRK_LANE_BASES: the read has pieces)
         const uint64_t per_bin = (bw + DCN_TRK_PIECE_BASES - 1) / DCN_TRK_PIECE_BASES;
@@ -130,7 +97,7 @@ __global__ __launch_bounds__(DCN_TRK_THREADS) void track_pieces_kernel(dcn_track
         trk_acc c;
         for (uint64_t wb = p0 >> 5; wb <= w1; wb += DCN_WAVE) {
             const uint64_t wi = wb + lane;
-            if (wi <= w1) trk_add_word(a, wi, trk_word(a, wi, p0, p1), c);
+            if (wi <= w1) trk_add_word(a, wi, dcn_bits_cut(a.bits, wi, p0, p1), c);
         }
         for (uint32_t d = DCN_WAVE / 2; d; d >>= 1) {
             c.n_pos += __shfl_xor(c.n_pos, d);
@@ -162,13 +129,7 @@ uint32_t trk_piece_blocks(uint64_t n_pieces) {
 } // namespace
 
 int dcn_launch_track_mark(const dcn_track_args &a, hipStream_t stream) {
-    if (a.max_tiles == 0) return DCN_OK;
-    const uint64_t threads = (uint64_t)a.max_tiles * DCN_TRK_TILE_LANES;
-    const uint64_t blocks = (threads + DCN_TRK_THREADS - 1) / DCN_TRK_THREADS;
-    if (blocks > 0x7FFFFFFFull) return dcn_fail(DCN_ERR_INTERNAL, "track: tile count");
-    hipLaunchKernelGGL(track_mark_kernel, dim3((uint32_t)blocks), dim3(DCN_TRK_THREADS), 0, stream, a);
-    DCN_HIP(hipGetLastError());
-    return DCN_OK;
+    return dcn_launch_dump_sweep(track_mark_kernel, a, "track: tile count", stream);
 }
 
 int dcn_launch_track_reduce(const dcn_track_args &a, hipStream_t stream) {

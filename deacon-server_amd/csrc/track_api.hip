@@ -1,5 +1,5 @@
 // track_api.hip -- the C ABI of dcn_depth_track_batch: the depth track of every read of a host batch (kernels in
-// track.hip; the batch runs locate's front end, pack -> plan -> scan in dump mode, on a filter context).
+// track.hip; the batch runs the dump front end of ctx.hip on a filter context).
 #include "dcn_ctx.h"
 #include "dcn_track.h"
 
@@ -24,22 +24,13 @@ int track_check(dcn_ctx *ctx, const dcn_index *set, const dcn_track_params *p, c
     if (set->n_members < 32 && (p->member_mask >> set->n_members) != 0)
         return dcn_fail(DCN_ERR_ARG, "params.member_mask has a bit at or above the set's member count (" +
                                          std::to_string(set->n_members) + ")");
-    const dcn_index *ix = ctx->index;
-    if (ix->k != set->k || ix->w != set->w)
-        return dcn_fail(DCN_ERR_ARG, "the context's index (k=" + std::to_string((int)ix->k) + ", w=" + std::to_string((int)ix->w) +
-                                         ") and the set (k=" + std::to_string((int)set->k) + ", w=" + std::to_string((int)set->w) +
-                                         ") differ");
-    if (ix->device != set->device) return dcn_fail(DCN_ERR_ARG, "the context and the set live on different devices");
-    if (ix->variant != set->variant)
-        return dcn_fail(DCN_ERR_ARG, "the context's index and the set were created under different minimizer rules");
-    return check_idle(ctx);
+    return check_ctx_matches(ctx, set, "the set");
 }
 
 int track_buffers(dcn_ctx *c) {
     DCN_TRY(ensure_dump_buffers(c));
-    // (either may be there already: classify with depth and locate use the bitmap, locate on a set the word per base)
-    if (!c->d_loc_bits) DCN_TRY(dev_alloc(&c->d_loc_bits, (c->max_bases + 31) / 32 + 1, "position bitmap"));
-    if (!c->d_loc_labels) DCN_TRY(dev_alloc(&c->d_loc_labels, c->max_bases + 2, "track values"));
+    DCN_TRY(ensure_position_bitmap(c));
+    DCN_TRY(ensure_position_words(c));
     if (!c->d_trk_bin_offsets) {
         DCN_TRY(dev_alloc(&c->d_trk_bin_offsets, (uint64_t)c->max_reads + 1, "track bin offsets"));
         DCN_TRY(dev_alloc(&c->d_trk_piece_offsets, (uint64_t)c->max_reads + 1, "track piece offsets"));
@@ -94,22 +85,10 @@ extern "C" int dcn_depth_track_batch(dcn_ctx *ctx, const dcn_index *set, const u
     DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
     DCN_HIP(hipMemsetAsync(c->d_loc_bits, 0, ((n_bases + 31) / 32 + 1) * sizeof(uint32_t), st));
     int prof_slot = -1;
-    DCN_TRY(prof_begin(c, &prof_slot));
-    DCN_TRY(dcn_launch_pack(c->d_ascii, 0, n_bases, c->d_packed + DCN_FRONT_PAD, c->d_invmask + DCN_FRONT_PAD, c->d_status, st));
-    DCN_PROF_MARK(DCN_STAGE_PACK);
-    // (check_offsets stays 0: validate_host_batch has walked the offsets on the host)
-    dcn_plan_args pa = plan_args(c, set, c->d_ascii, c->d_offsets, nullptr, n_reads, n_reads, prm->prefix_length);
-    pa.read_tiles = c->d_read_tiles;
-    pa.read_tile_first = c->d_read_tile_first;
-    DCN_TRY(dcn_launch_plan(pa, st));
-    DCN_PROF_MARK(DCN_STAGE_PLAN);
-    dcn_scan_args sa = dump_scan_args(c, set, n_bases);
-    sa.dump_abs = 1;
-    const uint32_t max_tiles = tile_bound(c, n_reads, n_bases);
-    DCN_TRY(dcn_launch_scan(sa, max_tiles, true, st));
-    DCN_PROF_MARK(DCN_STAGE_SCAN);
     dcn_track_args ta;
     memset(&ta, 0, sizeof(ta));
+    DCN_TRY(dump_front_end(c, set, c->d_ascii, c->d_offsets, nullptr, n_reads, n_reads, n_bases, prm->prefix_length, false,
+                           &prof_slot, &ta.dump));
     ta.table = set->view();
     ta.labels = set->d_labels;
     ta.zero_label = set->zero_label;
@@ -117,14 +96,6 @@ extern "C" int dcn_depth_track_batch(dcn_ctx *ctx, const dcn_index *set, const u
     ta.depth = set->d_depth;
     ta.depth_zero = set->has_zero ? set->d_depth + set->depth_words : nullptr;
     ta.depth_cap = prm->depth_cap;
-    ta.tiles = c->d_tiles;
-    ta.n_tiles = &c->d_status->n_tiles;
-    ta.dump_hash = c->d_dump_hash;
-    ta.dump_valid = c->d_dump_valid;
-    ta.dump_pos = c->d_dump_pos;
-    ta.dump_count = c->d_dump_count;
-    ta.max_tiles = max_tiles;
-    ta.n_bases = n_bases;
     ta.offsets = c->d_offsets;
     ta.n_reads = n_reads;
     ta.bin_bases = prm->bin_bases;
@@ -139,14 +110,7 @@ extern "C" int dcn_depth_track_batch(dcn_ctx *ctx, const dcn_index *set, const u
     DCN_PROF_MARK(DCN_STAGE_DISTINCT);
     DCN_TRY(dcn_launch_track_reduce(ta, st));
     DCN_PROF_MARK(DCN_STAGE_FINISH);
-    if (prof_slot >= 0) c->prof_used[prof_slot] = true;
-    // a later device-pointer filter batch packs one batch ahead into these packed buffers on its own stream, after the
-    // events below: they now stand after this run
-    if (c->pack_ahead_state == 1) {
-        DCN_HIP(hipEventRecord(c->plan_done, st));
-        for (int i = 0; i < 2; ++i) DCN_HIP(hipEventRecord(c->buf_free[i], st));
-    }
-    DCN_TRY(sync_and_check(c, nullptr));
+    DCN_TRY(finish_run(c, prof_slot));
     DCN_HIP(hipMemcpy(bins, c->d_trk_bins, total * sizeof(dcn_track_bin), hipMemcpyDeviceToHost));
     return DCN_OK;
 }
