@@ -2841,10 +2841,165 @@ int run_index_build(const std::string &input, unsigned k, unsigned w, const std:
     return 0;
 }
 
+// ---- what the tools below share: each piece of a batch tool, written once ---------------------------------------------
+struct RawIndex {  // owns a dcn_index*
+    dcn_index *p = nullptr;
+    ~RawIndex() {
+        if (p) dcn_index_destroy(p);
+    }
+};
+
+struct Stopwatch {
+    std::chrono::steady_clock::time_point start = std::chrono::steady_clock::now();
+    double seconds() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count(); }
+};
+
+// printf onto the end of a string, sized by the text itself
+__attribute__((format(printf, 2, 3))) void appendf(std::string &s, const char *fmt, ...) {
+    va_list ap, again;
+    va_start(ap, fmt);
+    va_copy(again, ap);
+    const int n = std::vsnprintf(nullptr, 0, fmt, ap);
+    va_end(ap);
+    const size_t at = s.size();
+    s.resize(at + (size_t)std::max(n, 0) + 1);
+    std::vsnprintf(&s[at], s.size() - at, fmt, again);
+    va_end(again);
+    s.resize(s.size() - 1);
+}
+
+std::string summary_head() { return "{\n  \"version\": " + json_str(std::string("deacon-hip ") + VERSION); }
+
+// a text output: PATH, or stdout for `-` where the option says so
+struct TextOut {
+    FILE *f = nullptr;
+    TextOut() = default;
+    TextOut(const std::string &path, bool dash_is_stdout) { open(path, dash_is_stdout); }
+    void open(const std::string &path, bool dash_is_stdout) {
+        f = dash_is_stdout && path == "-" ? stdout : std::fopen(path.c_str(), "w");
+        if (!f) die("cannot open " + path + " for writing");
+    }
+    explicit operator bool() const { return f != nullptr; }
+    void write(const std::string &s) { std::fwrite(s.data(), 1, s.size(), f); }
+    int finish() {  // closed, or flushed when it is stdout; nothing when it was never opened
+        FILE *g = f;
+        f = nullptr;
+        return !g ? 0 : g != stdout ? std::fclose(g) : std::fflush(g);
+    }
+};
+
+void write_text_file(const std::string &path, const std::string &text) {  // the -s summaries: `-` is a file name here
+    TextOut out(path, false);
+    out.write(text);
+    out.finish();
+}
+
+// the name of a record up to its first blank or tab
+std::string_view id_token(const Batch &b, const Rec &r) {
+    const char *id = b.chars() + r.id_off;
+    size_t n = 0;
+    while (n < r.id_len && id[n] != ' ' && id[n] != '\t') ++n;
+    return {id, n};
+}
+
+// the names of a member mask's members, comma-joined, onto the end of s; false when the mask has none of them
+bool append_members(std::string &s, uint32_t mask, const std::vector<std::string> &names) {
+    bool any = false;
+    for (size_t j = 0; j < names.size(); ++j)
+        if (mask >> j & 1u) {
+            if (any) s += ',';
+            s += names[j];
+            any = true;
+        }
+    return any;
+}
+
+// an ABI call that fills v and says how many items there are when v is too small: call(data, capacity, count) -> rc
+template <typename T, typename F>
+void with_room(std::vector<T> &v, F call) {
+    uint64_t count = 0;
+    int rc = call(v.data(), v.size(), count);
+    if (rc == DCN_ERR_CAPACITY && count > v.size()) {  // the count came back: once more with room for it
+        v.resize(count);
+        rc = call(v.data(), v.size(), count);
+    }
+    deacon::check(rc);
+}
+
+// bases that fill a batch and bases a context holds, or what the test hook `hook` says (many batches, records past the context)
+struct BatchSize {
+    uint64_t batch_bases, max_bases;
+};
+BatchSize batch_size(const char *hook, uint64_t batch_bases = 32ull << 20) {
+    if (const char *e = std::getenv(hook)) batch_bases = (uint64_t)std::max(64, std::atoi(e));
+    return {batch_bases, 2 * batch_bases};
+}
+
+// a dcn_ctx over `index`, and the one place where one is made and unmade
+struct Context {
+    dcn_ctx *p = nullptr;
+    const dcn_index *index;
+    uint64_t max_bases;
+    uint32_t max_reads;
+    Context(const dcn_index *index_, uint64_t max_bases_, uint32_t max_reads_ = 1u << 20)
+        : index(index_), max_bases(max_bases_), max_reads(max_reads_) {
+        deacon::check(dcn_ctx_create(index, max_bases, max_reads, &p));
+    }
+    Context(const Context &) = delete;
+    Context &operator=(const Context &) = delete;
+    ~Context() {
+        if (p) dcn_ctx_destroy(p);
+    }
+    uint32_t batch_reads() const { return max_reads - 2; }
+    void fit(uint64_t n_bases) {  // a record longer than the context's batch: a context of its size
+        if (n_bases <= max_bases) return;
+        dcn_ctx_destroy(p);
+        p = nullptr;
+        max_bases = n_bases;
+        deacon::check(dcn_ctx_create(index, max_bases, max_reads, &p));
+    }
+};
+
+// records from next(b) until it says false; run() for every full batch and for the last partial one, never for an empty one
+template <typename Next, typename Run>
+void for_each_batch(Next next, Batch &b, uint64_t batch_bases, size_t batch_reads, Run run) {
+    auto flush = [&] {
+        if (!b.recs.empty()) run();
+        b.clear();
+    };
+    while (next(b))
+        if (b.offsets.back() >= batch_bases || b.recs.size() >= batch_reads) flush();
+    flush();
+}
+template <typename Run>
+void for_each_batch(FastxReader &rd, Batch &b, uint64_t batch_bases, size_t batch_reads, Run run) {
+    for_each_batch([&rd](Batch &into) { return rd.next(into); }, b, batch_bases, batch_reads, run);
+}
+
+// index files, loaded: the owned members, pointers to them in order, and each one's k, w and key count
+struct Members {
+    std::vector<RawIndex> idx;
+    std::vector<const dcn_index *> ptrs;
+    std::vector<uint8_t> k, w;
+    std::vector<uint64_t> keys;
+};
+Members load_indexes(const std::vector<std::string> &paths, bool announce = false) {
+    const size_t n = paths.size();
+    Members m{std::vector<RawIndex>(n), std::vector<const dcn_index *>(n), std::vector<uint8_t>(n), std::vector<uint8_t>(n),
+              std::vector<uint64_t>(n)};
+    for (size_t j = 0; j < n; ++j) {
+        deacon::check(dcn_index_from_file(paths[j].c_str(), 0, &m.idx[j].p));
+        deacon::check(dcn_index_header(m.idx[j].p, &m.k[j], &m.w[j], &m.keys[j]));
+        if (announce) std::fprintf(stderr, "Index %zu: %llu minimizers\n", j + 1, (unsigned long long)m.keys[j]);
+        m.ptrs[j] = m.idx[j].p;
+    }
+    return m;
+}
+
 // `index build` with --min-count / --max-count / --count-hist: the input goes through the record reader batch by batch into a
 // counting builder (dcn_index_builder_*), and the index written is the builder's selection by count
 int run_index_build_counted(const std::string &input, unsigned k, unsigned w, const std::string &output, float entropy, bool quiet, uint32_t min_count, uint32_t max_count, const std::string &count_hist) {
-    auto start = std::chrono::steady_clock::now();
+    const Stopwatch watch;
     // (-c is a pre-allocation hint the plain build caps by the input's size; here the input is not known in advance and the
     // builder's table grows as needed, so the flag is accepted and not used)
     std::fprintf(stderr, "Deacon-hip v%s; mode: build; input: single; options: capacity=as needed, min_count=%u, max_count=%u\n", VERSION,
@@ -2852,27 +3007,24 @@ int run_index_build_counted(const std::string &input, unsigned k, unsigned w, co
     if ((k + w - 1) % 2 == 0)
         die("Constraint violated: k + w - 1 must be odd (k=" + std::to_string(k) + ", w=" + std::to_string(w) + ")");
     std::fprintf(stderr, "Building index (k=%u, w=%u)\n", k, w);
-    uint64_t batch_bases = 256ull << 20;
-    if (const char *e = std::getenv("DCN_CLI_BUILD_BATCH_BASES")) batch_bases = (uint64_t)std::max(64, std::atoi(e)); // test hook: many batches
+    const uint64_t batch_bases = batch_size("DCN_CLI_BUILD_BATCH_BASES", 256ull << 20).batch_bases;  // (no context here)
     const size_t batch_reads = 1u << 22;
     deacon::IndexBuilder builder((uint8_t)k, (uint8_t)w, entropy, 0, 0);
     FastxReader rd(input);
     Batch b;
     uint64_t n_seqs = 0;
-    auto run_batch = [&]() {
-        if (b.recs.empty()) return;
+    auto next = [&](Batch &into) {  // the record's line as it arrives, not per batch
+        if (!rd.next(into)) return false;
+        if (!quiet) {
+            const Rec &r = into.recs.back();
+            std::fprintf(stderr, "  %.*s (%ubp)\n", (int)r.id_len, into.chars() + r.id_off, r.seq_len);
+        }
+        return true;
+    };
+    for_each_batch(next, b, batch_bases, batch_reads, [&] {
         builder.add(b.bases.data(), b.offsets.data(), (uint32_t)b.recs.size());
         n_seqs += b.recs.size();
-        b.clear();
-    };
-    while (rd.next(b)) {
-        if (!quiet) {
-            const Rec &r = b.recs.back();
-            std::fprintf(stderr, "  %.*s (%ubp)\n", (int)r.id_len, b.chars() + r.id_off, r.seq_len);
-        }
-        if (b.offsets.back() >= batch_bases || b.recs.size() >= batch_reads) run_batch();
-    }
-    run_batch();
+    });
     const deacon::IndexBuilder::Info info = builder.info();
     const uint32_t lo = std::max(min_count, 1u);
     const uint64_t below = lo > 1 ? builder.count(1, lo - 1) : 0, above = max_count && max_count < 65535 ? builder.count(max_count + 1, 0) : 0;
@@ -2893,29 +3045,26 @@ int run_index_build_counted(const std::string &input, unsigned k, unsigned w, co
             for (uint64_t i = 0; i < n; ++i)
                 if (counts[i] >= 4095) tail[counts[i]]++;
         }
-        FILE *f = count_hist == "-" ? stdout : std::fopen(count_hist.c_str(), "w");
-        if (!f) die("cannot open " + count_hist + " for writing");
+        TextOut out(count_hist, true);
         for (uint32_t c = 1; c < 4095; ++c)
-            if (h[c]) std::fprintf(f, "%u\t%llu\n", c, (unsigned long long)h[c]);
+            if (h[c]) std::fprintf(out.f, "%u\t%llu\n", c, (unsigned long long)h[c]);
         for (size_t c = 4095; c < tail.size(); ++c)
-            if (tail[c]) std::fprintf(f, "%zu\t%llu\n", c, (unsigned long long)tail[c]);
-        if (std::ferror(f) || (f != stdout ? std::fclose(f) : std::fflush(f)) != 0) die("Failed to write the count histogram: " + count_hist);
+            if (tail[c]) std::fprintf(out.f, "%zu\t%llu\n", c, (unsigned long long)tail[c]);
+        if (std::ferror(out.f) || out.finish() != 0) die("Failed to write the count histogram: " + count_hist);
     }
     deacon::check(dcn_index_write_file(idx.raw(), (output == "-" ? std::string("/dev/stdout") : output).c_str()));
-    std::fprintf(stderr, "Completed in %s\n",
-                 fmt_duration(std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count()).c_str());
+    std::fprintf(stderr, "Completed in %s\n", fmt_duration(watch.seconds()).c_str());
     return 0;
 }
 
 int run_index_info(const std::string &path) {
-    auto start = std::chrono::steady_clock::now();
+    const Stopwatch watch;
     deacon::Index idx = deacon::Index::load(path);
     auto hd = idx.header();
     std::fprintf(stderr, "Index information:\n  Format version: %u\n  K-mer length (k): %u\n  Window size (w): %u\n"
                          "  Distinct minimizer count: %llu\n",
                  hd.format_version, hd.kmer_length, hd.window_size, (unsigned long long)idx.len());
-    std::fprintf(stderr, "Retrieved index info in %s\n",
-                 fmt_duration(std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count()).c_str());
+    std::fprintf(stderr, "Retrieved index info in %s\n", fmt_duration(watch.seconds()).c_str());
     return 0;
 }
 
@@ -2924,40 +3073,36 @@ void write_index(dcn_index *raw, const std::string &output) {
     deacon::check(dcn_index_write_file(raw, path.c_str()));
 }
 
-struct RawIndex {  // owns a dcn_index*
-    dcn_index *p = nullptr;
-    ~RawIndex() {
-        if (p) dcn_index_destroy(p);
-    }
-};
+// the n-ary compositions: `combine` over every input, with the two words of its stderr lines that differ
+int run_index_combine(const std::vector<std::string> &inputs, const std::string &output,
+                      int (*combine)(const dcn_index *const *, uint32_t, dcn_index **), const char *title, const char *word) {
+    const Stopwatch watch;
+    const Members m = load_indexes(inputs, true);
+    RawIndex out;
+    deacon::check(combine(m.ptrs.data(), (uint32_t)m.ptrs.size(), &out.p));
+    uint64_t n = 0;
+    dcn_index_header(out.p, nullptr, nullptr, &n);
+    std::fprintf(stderr, "%s: %llu minimizers from %zu indexes\n", title, (unsigned long long)n, inputs.size());
+    write_index(out.p, output);
+    std::fprintf(stderr, "Completed %s operation in %s\n", word, fmt_duration(watch.seconds()).c_str());
+    return 0;
+}
 
 // index::union (src/index.rs:563-664)
 int run_index_union(const std::vector<std::string> &inputs, const std::string &output) {
-    auto start = std::chrono::steady_clock::now();
-    std::vector<RawIndex> idx(inputs.size());
-    std::vector<const dcn_index *> ptrs;
-    for (size_t i = 0; i < inputs.size(); ++i) {
-        deacon::check(dcn_index_from_file(inputs[i].c_str(), 0, &idx[i].p));
-        uint64_t n = 0;
-        dcn_index_header(idx[i].p, nullptr, nullptr, &n);
-        std::fprintf(stderr, "Index %zu: %llu minimizers\n", i + 1, (unsigned long long)n);
-        ptrs.push_back(idx[i].p);
-    }
-    RawIndex out;
-    deacon::check(dcn_index_union(ptrs.data(), (uint32_t)ptrs.size(), &out.p));
-    uint64_t n = 0;
-    dcn_index_header(out.p, nullptr, nullptr, &n);
-    std::fprintf(stderr, "Union: %llu minimizers from %zu indexes\n", (unsigned long long)n, inputs.size());
-    write_index(out.p, output);
-    std::fprintf(stderr, "Completed union operation in %s\n",
-                 fmt_duration(std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count()).c_str());
-    return 0;
+    return run_index_combine(inputs, output, dcn_index_union, "Union", "union");
+}
+
+// A n B n ... (dcn_index_intersect; no reference counterpart: the reference composes with union and diff)
+int run_index_intersect(const std::vector<std::string> &inputs, const std::string &output) {
+    if (inputs.empty()) die("index intersect needs at least one <INDEX>");
+    return run_index_combine(inputs, output, dcn_index_intersect, "Intersection", "intersect");
 }
 
 // index::diff (src/index.rs:421-536): second is an index file, or a FASTX file when -k/-w are given or when it does
 // not parse as an index (then the first index's k, w are used)
 int run_index_diff(const std::string &first, const std::string &second, int k_opt, int w_opt, const std::string &output) {
-    auto start = std::chrono::steady_clock::now();
+    const Stopwatch watch;
     RawIndex a, b, out;
     deacon::check(dcn_index_from_file(first.c_str(), 0, &a.p));
     uint8_t k = 0, w = 0;
@@ -2991,44 +3136,14 @@ int run_index_diff(const std::string &first, const std::string &second, int k_op
     dcn_index_header(out.p, nullptr, nullptr, &n);
     std::fprintf(stderr, "Removed %llu minimizers, %llu remaining\n", (unsigned long long)(na - n), (unsigned long long)n);
     write_index(out.p, output);
-    std::fprintf(stderr, "Completed difference operation in %s\n",
-                 fmt_duration(std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count()).c_str());
-    return 0;
-}
-
-// A n B n ... (dcn_index_intersect; no reference counterpart: the reference composes with union and diff)
-int run_index_intersect(const std::vector<std::string> &inputs, const std::string &output) {
-    auto start = std::chrono::steady_clock::now();
-    if (inputs.empty()) die("index intersect needs at least one <INDEX>");
-    std::vector<RawIndex> idx(inputs.size());
-    std::vector<const dcn_index *> ptrs;
-    for (size_t i = 0; i < inputs.size(); ++i) {
-        deacon::check(dcn_index_from_file(inputs[i].c_str(), 0, &idx[i].p));
-        uint64_t n = 0;
-        dcn_index_header(idx[i].p, nullptr, nullptr, &n);
-        std::fprintf(stderr, "Index %zu: %llu minimizers\n", i + 1, (unsigned long long)n);
-        ptrs.push_back(idx[i].p);
-    }
-    RawIndex out;
-    deacon::check(dcn_index_intersect(ptrs.data(), (uint32_t)ptrs.size(), &out.p));
-    uint64_t n = 0;
-    dcn_index_header(out.p, nullptr, nullptr, &n);
-    std::fprintf(stderr, "Intersection: %llu minimizers from %zu indexes\n", (unsigned long long)n, inputs.size());
-    write_index(out.p, output);
-    std::fprintf(stderr, "Completed intersect operation in %s\n",
-                 fmt_duration(std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count()).c_str());
+    std::fprintf(stderr, "Completed difference operation in %s\n", fmt_duration(watch.seconds()).c_str());
     return 0;
 }
 
 // the labelled set over index files, as `classify` builds it; the members' own tables go back at once
 void load_index_set(const std::vector<std::string> &paths, RawIndex &set) {
-    std::vector<RawIndex> members(paths.size());
-    std::vector<const dcn_index *> mp(paths.size());
-    for (size_t j = 0; j < paths.size(); ++j) {
-        deacon::check(dcn_index_from_file(paths[j].c_str(), 0, &members[j].p));
-        mp[j] = members[j].p;
-    }
-    deacon::check(dcn_index_set_create(mp.data(), (uint32_t)mp.size(), &set.p));
+    const Members m = load_indexes(paths);
+    deacon::check(dcn_index_set_create(m.ptrs.data(), (uint32_t)m.ptrs.size(), &set.p));
 }
 
 // `deacon-hip index compare`: how much 2..32 indexes share (dcn_index_set_overlap).  stdout: a TSV of shared counts, a
@@ -3049,26 +3164,20 @@ int run_index_compare(const std::vector<std::string> &inputs, const std::string 
         std::string text = block ? "\nindex\tkeys\texclusive" : "index\tkeys\texclusive";
         for (auto &p : inputs) text += "\t" + p;
         text += "\n";
-        char buf[64];
         for (size_t i = 0; i < n; ++i) {
             text += inputs[i] + "\t" + std::to_string(keys(i)) + "\t" + std::to_string(exclusive[i]);
             for (size_t j = 0; j < n; ++j) {
-                if (block) {
-                    if (keys(i)) std::snprintf(buf, sizeof buf, "\t%.6f", ratio(shared[i * n + j], keys(i)));
-                    else std::snprintf(buf, sizeof buf, "\t0");
-                    text += buf;
-                } else {
-                    text += "\t" + std::to_string(shared[i * n + j]);
-                }
+                if (!block) text += "\t" + std::to_string(shared[i * n + j]);
+                else if (keys(i)) appendf(text, "\t%.6f", ratio(shared[i * n + j], keys(i)));
+                else text += "\t0";
             }
             text += "\n";
         }
         std::fwrite(text.data(), 1, text.size(), stdout);
     }
     if (!summary.empty()) {
-        char buf[64];
-        std::string js = "{\n  \"version\": " + json_str(std::string("deacon-hip ") + VERSION) + ",\n  \"k\": " + std::to_string((int)k) +
-                         ",\n  \"w\": " + std::to_string((int)w) + ",\n  \"union\": " + std::to_string(n_union) + ",\n  \"members\": [";
+        std::string js = summary_head() + ",\n  \"k\": " + std::to_string((int)k) + ",\n  \"w\": " + std::to_string((int)w) +
+                         ",\n  \"union\": " + std::to_string(n_union) + ",\n  \"members\": [";
         for (size_t i = 0; i < n; ++i)
             js += std::string(i ? "," : "") + "\n    {\"path\": " + json_str(inputs[i]) + ", \"keys\": " + std::to_string(keys(i)) +
                   ", \"exclusive\": " + std::to_string(exclusive[i]) + "}";
@@ -3081,19 +3190,14 @@ int run_index_compare(const std::vector<std::string> &inputs, const std::string 
         js += "\n  ],\n  \"jaccard\": [";
         for (size_t i = 0; i < n; ++i) {
             js += std::string(i ? "," : "") + "\n    [";
-            for (size_t j = 0; j < n; ++j) {
-                std::snprintf(buf, sizeof buf, "%s%.17g", j ? ", " : "", ratio(shared[i * n + j], keys(i) + keys(j) - shared[i * n + j]));
-                js += buf;
-            }
+            for (size_t j = 0; j < n; ++j)
+                appendf(js, "%s%.17g", j ? ", " : "", ratio(shared[i * n + j], keys(i) + keys(j) - shared[i * n + j]));
             js += "]";
         }
         js += "\n  ],\n  \"by_count\": [";
         for (size_t c = 0; c < n; ++c) js += (c ? ", " : "") + std::to_string(by_count[c]);
         js += "]\n}\n";
-        FILE *f = std::fopen(summary.c_str(), "w");
-        if (!f) die("cannot open " + summary + " for writing");
-        std::fwrite(js.data(), 1, js.size(), f);
-        std::fclose(f);
+        write_text_file(summary, js);
     }
     return 0;
 }
@@ -3124,7 +3228,7 @@ struct SelectArgs {
 
 // `deacon-hip index select`: the keys of several indexes chosen by which of them hold each (dcn_index_set_select)
 int run_index_select(const SelectArgs &a) {
-    auto start = std::chrono::steady_clock::now();
+    const Stopwatch watch;
     if (a.indexes.empty()) die("the following required arguments were not provided: -x <INDEX>");
     if (a.indexes.size() > 32) die("index select takes at most 32 indexes");
     const uint32_t all_of = a.all_of.empty() ? 0 : parse_member_list("--all", a.all_of, a.indexes.size());
@@ -3138,8 +3242,7 @@ int run_index_select(const SelectArgs &a) {
     deacon::check(dcn_index_set_select(set.p, all_of, any_of, none_of, a.min_members, a.max_members, &n, &out.p));
     std::fprintf(stderr, "Selected %llu of %llu minimizers\n", (unsigned long long)n, (unsigned long long)n_union);
     write_index(out.p, a.output);
-    std::fprintf(stderr, "Completed select operation in %s\n",
-                 fmt_duration(std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count()).c_str());
+    std::fprintf(stderr, "Completed select operation in %s\n", fmt_duration(watch.seconds()).c_str());
     return 0;
 }
 
@@ -3170,42 +3273,22 @@ std::string index_stem(const std::string &path) {
 }
 
 int run_classify(const ClassifyArgs &a) {
-    const auto start = std::chrono::steady_clock::now();
+    const Stopwatch watch;
     if (a.indexes.empty()) die("the following required arguments were not provided: -x <INDEX>");
     if (a.indexes.size() > 32) die("classify takes at most 32 indexes");
     const uint32_t n = (uint32_t)a.indexes.size();
-    std::vector<RawIndex> members(n);
-    std::vector<const dcn_index *> mp(n);
-    std::vector<uint8_t> mk(n), mw(n);
-    std::vector<uint64_t> mkeys(n);
-    for (uint32_t j = 0; j < n; ++j) {
-        deacon::check(dcn_index_from_file(a.indexes[j].c_str(), 0, &members[j].p));
-        deacon::check(dcn_index_header(members[j].p, &mk[j], &mw[j], &mkeys[j]));
-        mp[j] = members[j].p;
-    }
+    Members members = load_indexes(a.indexes);
+    const std::vector<uint8_t> &mk = members.k, &mw = members.w;
+    const std::vector<uint64_t> &mkeys = members.keys;
     RawIndex set;
-    deacon::check(dcn_index_set_create(mp.data(), n, &set.p));
-    for (auto &m : members) { // the set holds its own table: the members' memory goes back at once
-        dcn_index_destroy(m.p);
-        m.p = nullptr;
-    }
+    deacon::check(dcn_index_set_create(members.ptrs.data(), n, &set.p));
+    members.idx.clear();  // the set holds its own table: the members' memory goes back at once
     // the marks live with the set: contexts recreated for long records below keep adding to them
     if (a.coverage) deacon::check(dcn_index_set_coverage_enable(set.p, 1));
     if (a.depth) deacon::check(dcn_index_set_depth_enable(set.p, 1)); // (and so do the depth counters)
-    uint64_t batch_bases = 32ull << 20, max_bases = 64ull << 20;
-    if (const char *e = std::getenv("DCN_CLI_CLASSIFY_BATCH_BASES")) { // test hook: many batches, records past the context
-        batch_bases = (uint64_t)std::max(64, std::atoi(e));
-        max_bases = 2 * batch_bases;
-    }
-    const uint32_t max_reads = 1u << 20;
-    dcn_ctx *ctx = nullptr;
-    deacon::check(dcn_ctx_create(set.p, max_bases, max_reads, &ctx));
-    struct CtxGuard {
-        dcn_ctx **c;
-        ~CtxGuard() {
-            if (*c) dcn_ctx_destroy(*c);
-        }
-    } guard{&ctx};
+    const BatchSize size = batch_size("DCN_CLI_CLASSIFY_BATCH_BASES");
+    const uint64_t batch_bases = size.batch_bases;
+    Context ctx(set.p, size.max_bases);
     dcn_params prm = {};
     prm.abs_threshold = a.abs_threshold;
     prm.rel_threshold = a.rel_threshold;
@@ -3213,13 +3296,12 @@ int run_classify(const ClassifyArgs &a) {
 
     std::vector<std::string> stems(n);
     for (uint32_t j = 0; j < n; ++j) stems[j] = index_stem(a.indexes[j]);
-    FILE *tsv = nullptr;
+    TextOut tsv;
     if (a.has_per_read) {
-        tsv = a.per_read == "-" ? stdout : std::fopen(a.per_read.c_str(), "w");
-        if (!tsv) die("cannot open " + a.per_read + " for writing");
-        std::fputs("id\tlength\tminimizers", tsv);
-        for (auto &st : stems) std::fprintf(tsv, "\thits:%s", st.c_str());
-        std::fputs("\tmatched\n", tsv);
+        tsv.open(a.per_read, true);
+        std::fputs("id\tlength\tminimizers", tsv.f);
+        for (auto &st : stems) std::fprintf(tsv.f, "\thits:%s", st.c_str());
+        std::fputs("\tmatched\n", tsv.f);
     }
     FastxReader r1(a.input);
     std::unique_ptr<FastxReader> r2;
@@ -3229,21 +3311,27 @@ int run_classify(const ClassifyArgs &a) {
     std::vector<uint64_t> seqs_m(n, 0), bp_m(n, 0);
     Batch b;
     std::vector<uint32_t> match, hits, total;
-    auto run_batch = [&]() {
-        const uint32_t n_reads = (uint32_t)b.recs.size();
-        if (n_reads == 0) return;
-        const uint64_t nb = b.offsets.back();
-        if (nb > max_bases) { // a record longer than the context's batch: a context of its size
-            dcn_ctx_destroy(ctx);
-            ctx = nullptr;
-            max_bases = nb;
-            deacon::check(dcn_ctx_create(set.p, max_bases, max_reads, &ctx));
+    auto next = [&](Batch &into) {  // a record, or with a second input a pair: one unit of two records
+        if (!r1.next(into)) {
+            if (r2 && r2->next(into)) die("the second input has more records than the first");
+            return false;
         }
+        if (r2) {
+            if (!r2->next(into)) die("the first input has more records than the second");
+            const uint32_t u = (uint32_t)(into.recs.size() / 2 - 1);
+            into.unit_id.push_back(u);
+            into.unit_id.push_back(u);
+        }
+        return true;
+    };
+    for_each_batch(next, b, batch_bases, ctx.batch_reads(), [&] {
+        const uint32_t n_reads = (uint32_t)b.recs.size();
+        ctx.fit(b.offsets.back());
         const uint32_t n_units = paired ? n_reads / 2 : n_reads;
         match.assign(n_units, 0);
         hits.assign((size_t)n_units * n, 0);
         total.assign(n_units, 0);
-        deacon::check(dcn_classify_batch(ctx, set.p, b.bases.data(), b.offsets.data(), paired ? b.unit_id.data() : nullptr,
+        deacon::check(dcn_classify_batch(ctx.p, set.p, b.bases.data(), b.offsets.data(), paired ? b.unit_id.data() : nullptr,
                                          n_reads, &prm, match.data(), hits.data(), total.data()));
         const uint32_t per = paired ? 2 : 1;
         std::string row;
@@ -3255,44 +3343,16 @@ int run_classify(const ClassifyArgs &a) {
             for (uint32_t j = 0; j < n; ++j)
                 if (match[u] >> j & 1u) seqs_m[j] += per, bp_m[j] += len;
             if (!tsv) continue;
-            const Rec &r = b.recs[u * per];
-            const char *id = b.chars() + r.id_off;
-            size_t id_len = 0;
-            while (id_len < r.id_len && id[id_len] != ' ' && id[id_len] != '\t') ++id_len;
-            row.assign(id, id_len);
+            row = id_token(b, b.recs[u * per]);
             row += '\t' + std::to_string(len) + '\t' + std::to_string(total[u]);
             for (uint32_t j = 0; j < n; ++j) row += '\t' + std::to_string(hits[(size_t)u * n + j]);
             row += '\t';
-            bool any = false;
-            for (uint32_t j = 0; j < n; ++j)
-                if (match[u] >> j & 1u) {
-                    if (any) row += ',';
-                    row += stems[j];
-                    any = true;
-                }
-            if (!any) row += '-';
+            if (!append_members(row, match[u], stems)) row += '-';
             row += '\n';
-            std::fwrite(row.data(), 1, row.size(), tsv);
+            tsv.write(row);
         }
-        b.clear();
-    };
-    const uint32_t batch_reads = max_reads - 2;
-    for (;;) {
-        if (!r1.next(b)) {
-            if (r2 && r2->next(b)) die("the second input has more records than the first");
-            break;
-        }
-        if (r2) {
-            if (!r2->next(b)) die("the first input has more records than the second");
-            const uint32_t u = (uint32_t)(b.recs.size() / 2 - 1);
-            b.unit_id.push_back(u);
-            b.unit_id.push_back(u);
-        }
-        if (b.offsets.back() >= batch_bases || b.recs.size() >= batch_reads) run_batch();
-    }
-    run_batch();
-    if (tsv && tsv != stdout) std::fclose(tsv);
-    else if (tsv) std::fflush(tsv);
+    });
+    tsv.finish();
     // --track: the records of the reference against the counters the reads left, one block of lines per index (a header
     // line, then record, start, end and the bin's figures; mean = sum_depth / n_keys).  The whole records are tracked:
     // --prefix-length is the reads'.
@@ -3306,40 +3366,29 @@ int run_classify(const ClassifyArgs &a) {
         std::vector<uint64_t> bin_off;
         std::vector<dcn_track_bin> tbins;
         char num[160];
-        auto track_batch = [&]() {
+        for_each_batch(rt, tb, batch_bases, ctx.batch_reads(), [&] {
             const uint32_t n_reads = (uint32_t)tb.recs.size();
-            if (n_reads == 0) return;
-            const uint64_t nb = tb.offsets.back();
-            if (nb > max_bases) { // a record longer than the context's batch: a context of its size
-                dcn_ctx_destroy(ctx);
-                ctx = nullptr;
-                max_bases = nb;
-                deacon::check(dcn_ctx_create(set.p, max_bases, max_reads, &ctx));
-            }
+            ctx.fit(tb.offsets.back());
             bin_off.assign((size_t)n_reads + 1, 0);
             for (uint32_t j = 0; j < n; ++j) {
                 dcn_track_params tp = {};
                 tp.bin_bases = a.track_bin;
                 tp.member_mask = 1u << j;
                 tp.depth_cap = a.track_cap;
-                int rc = dcn_depth_track_batch(ctx, set.p, tb.bases.data(), tb.offsets.data(), n_reads, &tp, bin_off.data(),
-                                               tbins.data(), tbins.size());
-                if (rc == DCN_ERR_CAPACITY && bin_off[n_reads] > tbins.size()) { // the count came back: once more with room
-                    tbins.resize(bin_off[n_reads]);
-                    rc = dcn_depth_track_batch(ctx, set.p, tb.bases.data(), tb.offsets.data(), n_reads, &tp, bin_off.data(),
-                                               tbins.data(), tbins.size());
-                }
-                deacon::check(rc);
+                with_room(tbins, [&](dcn_track_bin *bins, size_t room, uint64_t &count) {
+                    const int rc = dcn_depth_track_batch(ctx.p, set.p, tb.bases.data(), tb.offsets.data(), n_reads, &tp, bin_off.data(),
+                                                         bins, room);
+                    count = bin_off[n_reads];
+                    return rc;
+                });
                 for (uint32_t r = 0; r < n_reads; ++r) {
                     const Rec &rec = tb.recs[r];
-                    const char *id = tb.chars() + rec.id_off;
-                    size_t id_len = 0;
-                    while (id_len < rec.id_len && id[id_len] != ' ' && id[id_len] != '\t') ++id_len;
+                    const std::string_view id = id_token(tb, rec);
                     for (uint64_t q = bin_off[r]; q < bin_off[r + 1]; ++q) {
                         const dcn_track_bin &tbn = tbins[q];
                         const uint64_t b0 = (q - bin_off[r]) * (uint64_t)a.track_bin;
                         const uint64_t b1 = a.track_bin ? std::min<uint64_t>(b0 + a.track_bin, rec.seq_len) : rec.seq_len;
-                        block[j].append(id, id_len);
+                        block[j].append(id);
                         int len = std::snprintf(num, sizeof num, "\t%llu\t%llu\t%u\t%u\t%u\t%llu\t%u\t", (unsigned long long)b0,
                                                 (unsigned long long)b1, tbn.n_positions, tbn.n_keys, tbn.n_observed,
                                                 (unsigned long long)tbn.sum_depth, tbn.max_depth);
@@ -3355,18 +3404,12 @@ int run_classify(const ClassifyArgs &a) {
                     }
                 }
             }
-            tb.clear();
-        };
-        while (rt.next(tb))
-            if (tb.offsets.back() >= batch_bases || tb.recs.size() >= batch_reads) track_batch();
-        track_batch();
-        FILE *f = a.track_out == "-" ? stdout : std::fopen(a.track_out.c_str(), "w");
-        if (!f) die("cannot open " + a.track_out + " for writing");
-        for (uint32_t j = 0; j < n; ++j) std::fwrite(block[j].data(), 1, block[j].size(), f);
-        if (f != stdout) std::fclose(f);
-        else std::fflush(f);
+        });
+        TextOut out(a.track_out, true);
+        for (uint32_t j = 0; j < n; ++j) out.write(block[j]);
+        out.finish();
     }
-    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+    const double secs = watch.seconds();
     auto prop = [](uint64_t x, uint64_t y) { return y ? (double)x / (double)y : 0.0; };
     std::vector<uint64_t> observed(n, 0), set_keys(n, 0);
     if (a.coverage) {
@@ -3397,27 +3440,25 @@ int run_classify(const ClassifyArgs &a) {
                 if (r_hi >= below && r_hi < below + h[d]) hi = d;
                 below += h[d];
             }
-            char mb[64];
-            if (hi == bins - 1) std::snprintf(mb, sizeof mb, "\">=%u\"", bins - 1);
-            else std::snprintf(mb, sizeof mb, "%.17g", (lo + hi) / 2.0);
-            d_median[j] = mb;
+            d_median[j].clear();
+            if (hi == bins - 1) appendf(d_median[j], "\">=%u\"", bins - 1);
+            else appendf(d_median[j], "%.17g", (lo + hi) / 2.0);
         }
     }
     if (a.has_depth_hist) {
-        FILE *f = std::fopen(a.depth_hist.c_str(), "w");
-        if (!f) die("cannot open " + a.depth_hist + " for writing");
-        std::fputs("index\tdepth\tkeys\n", f);
+        TextOut out(a.depth_hist, false);  // (`-` is a file name here)
+        std::fputs("index\tdepth\tkeys\n", out.f);
         const uint32_t bins = 256;
         std::vector<uint64_t> h(bins);
         for (uint32_t j = 0; j < n; ++j) {
             deacon::check(dcn_index_set_depth_hist(set.p, j, bins, h.data()));
             for (uint32_t d = 0; d < bins; ++d) {
                 if (!h[d]) continue;
-                if (d == bins - 1) std::fprintf(f, "%s\t>=%u\t%llu\n", stems[j].c_str(), d, (unsigned long long)h[d]);
-                else std::fprintf(f, "%s\t%u\t%llu\n", stems[j].c_str(), d, (unsigned long long)h[d]);
+                if (d == bins - 1) std::fprintf(out.f, "%s\t>=%u\t%llu\n", stems[j].c_str(), d, (unsigned long long)h[d]);
+                else std::fprintf(out.f, "%s\t%u\t%llu\n", stems[j].c_str(), d, (unsigned long long)h[d]);
             }
         }
-        std::fclose(f);
+        out.finish();
     }
     if (!a.quiet) {
         for (uint32_t j = 0; j < n; ++j)
@@ -3437,54 +3478,41 @@ int run_classify(const ClassifyArgs &a) {
                      (unsigned long long)bp_in, n, fmt_duration(secs).c_str());
     }
     if (a.has_summary) {
-        std::string js = "{\n  \"version\": " + json_str(std::string("deacon-hip ") + VERSION) + ",\n  \"input\": " +
-                         json_str(a.input) + ",\n  \"input2\": " + (a.has_input2 ? json_str(a.input2) : std::string("null"));
-        char buf[512];
-        std::snprintf(buf, sizeof buf, ",\n  \"abs_threshold\": %u,\n  \"rel_threshold\": %.17g,\n  \"prefix_length\": %zu,\n"
-                                       "  \"seqs_in\": %llu,\n  \"bp_in\": %llu,\n  \"time\": %.17g,\n  \"indexes\": [",
-                      a.abs_threshold, a.rel_threshold, a.prefix_length, (unsigned long long)seqs_in, (unsigned long long)bp_in, secs);
-        js += buf;
+        std::string js = summary_head() + ",\n  \"input\": " + json_str(a.input) + ",\n  \"input2\": " +
+                         (a.has_input2 ? json_str(a.input2) : std::string("null"));
+        appendf(js, ",\n  \"abs_threshold\": %u,\n  \"rel_threshold\": %.17g,\n  \"prefix_length\": %zu,\n"
+                    "  \"seqs_in\": %llu,\n  \"bp_in\": %llu,\n  \"time\": %.17g,\n  \"indexes\": [",
+                a.abs_threshold, a.rel_threshold, a.prefix_length, (unsigned long long)seqs_in, (unsigned long long)bp_in, secs);
         for (uint32_t j = 0; j < n; ++j) {
             js += (j ? ",\n    {" : "\n    {");
             js += "\"path\": " + json_str(a.indexes[j]) + ", \"name\": " + json_str(stems[j]);
-            std::snprintf(buf, sizeof buf, ", \"k\": %u, \"w\": %u, \"keys\": %llu, \"seqs_matched\": %llu, "
-                                           "\"seqs_matched_proportion\": %.17g, \"bp_matched\": %llu, \"bp_matched_proportion\": %.17g",
-                          (unsigned)mk[j], (unsigned)mw[j], (unsigned long long)(a.coverage ? set_keys[j] : mkeys[j]),
-                          (unsigned long long)seqs_m[j], prop(seqs_m[j], seqs_in), (unsigned long long)bp_m[j], prop(bp_m[j], bp_in));
-            js += buf;
-            if (a.coverage) {
-                std::snprintf(buf, sizeof buf, ", \"keys_observed\": %llu, \"keys_observed_proportion\": %.17g",
-                              (unsigned long long)observed[j], prop(observed[j], set_keys[j]));
-                js += buf;
-            }
-            if (a.depth) {
-                std::snprintf(buf, sizeof buf, ", \"depth\": {\"observed\": %llu, \"sum\": %llu, \"mean\": %.17g, \"median\": %s, "
-                                               "\"saturated\": %llu}",
-                              (unsigned long long)d_observed[j], (unsigned long long)d_sum[j], prop(d_sum[j], d_observed[j]),
-                              d_median[j].c_str(), (unsigned long long)d_saturated[j]);
-                js += buf;
-            }
+            appendf(js, ", \"k\": %u, \"w\": %u, \"keys\": %llu, \"seqs_matched\": %llu, "
+                        "\"seqs_matched_proportion\": %.17g, \"bp_matched\": %llu, \"bp_matched_proportion\": %.17g",
+                    (unsigned)mk[j], (unsigned)mw[j], (unsigned long long)(a.coverage ? set_keys[j] : mkeys[j]),
+                    (unsigned long long)seqs_m[j], prop(seqs_m[j], seqs_in), (unsigned long long)bp_m[j], prop(bp_m[j], bp_in));
+            if (a.coverage)
+                appendf(js, ", \"keys_observed\": %llu, \"keys_observed_proportion\": %.17g", (unsigned long long)observed[j],
+                        prop(observed[j], set_keys[j]));
+            if (a.depth)
+                appendf(js, ", \"depth\": {\"observed\": %llu, \"sum\": %llu, \"mean\": %.17g, \"median\": %s, \"saturated\": %llu}",
+                        (unsigned long long)d_observed[j], (unsigned long long)d_sum[j], prop(d_sum[j], d_observed[j]),
+                        d_median[j].c_str(), (unsigned long long)d_saturated[j]);
             js += "}";
         }
         js += "\n  ]";
         if (a.has_track) {
             js += ",\n  \"track\": {\"reference\": " + json_str(a.track_ref);
-            std::snprintf(buf, sizeof buf, ", \"bin_bases\": %u, \"depth_cap\": %u, \"indexes\": [", a.track_bin, a.track_cap);
-            js += buf;
+            appendf(js, ", \"bin_bases\": %u, \"depth_cap\": %u, \"indexes\": [", a.track_bin, a.track_cap);
             for (uint32_t j = 0; j < n; ++j) {
                 js += std::string(j ? "," : "") + "\n    {\"name\": " + json_str(stems[j]);
-                std::snprintf(buf, sizeof buf, ", \"bins\": %llu, \"bins_observed\": %llu, \"sum_depth\": %llu, \"n_keys\": %llu}",
-                              (unsigned long long)t_bins[j], (unsigned long long)t_bins_obs[j], (unsigned long long)t_sum[j],
-                              (unsigned long long)t_keys[j]);
-                js += buf;
+                appendf(js, ", \"bins\": %llu, \"bins_observed\": %llu, \"sum_depth\": %llu, \"n_keys\": %llu}",
+                        (unsigned long long)t_bins[j], (unsigned long long)t_bins_obs[j], (unsigned long long)t_sum[j],
+                        (unsigned long long)t_keys[j]);
             }
             js += "\n  ]}";
         }
         js += "\n}\n";
-        FILE *f = std::fopen(a.summary.c_str(), "w");
-        if (!f) die("cannot open " + a.summary + " for writing");
-        std::fwrite(js.data(), 1, js.size(), f);
-        std::fclose(f);
+        write_text_file(a.summary, js);
     }
     return 0;
 }
@@ -3502,43 +3530,23 @@ struct MaskArgs {
 };
 
 int run_mask(const MaskArgs &a) {
-    const auto start = std::chrono::steady_clock::now();
+    const Stopwatch watch;
     if (a.indexes.empty()) die("the following required arguments were not provided: -x <INDEX>");
     if (a.indexes.size() > 32) die("mask takes at most 32 indexes");
     if (!a.has_output && !a.has_bed && !a.has_summary) die("nothing to write: give at least one of -o <OUTPUT>, --bed <BED>, -s <SUMMARY>");
     const uint32_t n = (uint32_t)a.indexes.size();
-    std::vector<RawIndex> members(n);
-    std::vector<const dcn_index *> mp(n);
-    uint8_t k = 0, w = 0;
-    for (uint32_t j = 0; j < n; ++j) {
-        deacon::check(dcn_index_from_file(a.indexes[j].c_str(), 0, &members[j].p));
-        mp[j] = members[j].p;
-    }
-    deacon::check(dcn_index_header(members[0].p, &k, &w, nullptr));
+    Members members = load_indexes(a.indexes);
+    const uint8_t k = members.k[0], w = members.w[0];
     // one index is probed as it is (every label is 1); several become a labelled set, as classify builds it
     RawIndex set;
     if (n > 1) {
-        deacon::check(dcn_index_set_create(mp.data(), n, &set.p));
-        for (auto &m : members) {
-            dcn_index_destroy(m.p);
-            m.p = nullptr;
-        }
+        deacon::check(dcn_index_set_create(members.ptrs.data(), n, &set.p));
+        members.idx.clear();
     }
-    const dcn_index *target = n > 1 ? set.p : members[0].p;
-    uint64_t batch_bases = 32ull << 20, max_bases = 64ull << 20;
-    if (const char *e = std::getenv("DCN_CLI_LOCATE_BATCH_BASES")) { // test hook: many batches, records past the context
-        batch_bases = (uint64_t)std::max(64, std::atoi(e));
-        max_bases = 2 * batch_bases;
-    }
-    const uint32_t max_reads = 1u << 20;
-    dcn_ctx *ctx = nullptr;
-    deacon::check(dcn_ctx_create(target, max_bases, max_reads, &ctx));
-    struct CtxGuard {
-        dcn_ctx **c;
-        ~CtxGuard() {
-            if (*c) dcn_ctx_destroy(*c);
-        }
-    } guard{&ctx};
+    const dcn_index *target = n > 1 ? set.p : members.idx[0].p;
+    const BatchSize size = batch_size("DCN_CLI_LOCATE_BATCH_BASES");
+    const uint64_t batch_bases = size.batch_bases;
+    Context ctx(target, size.max_bases);
     dcn_locate_params prm = {};
     prm.max_gap = a.max_gap < 0 ? 2u * w - 1u : (uint32_t)a.max_gap;
     prm.min_hits = a.min_hits;
@@ -3549,11 +3557,8 @@ int run_mask(const MaskArgs &a) {
     for (uint32_t j = 0; j < n; ++j) stems[j] = index_stem(a.indexes[j]);
     std::unique_ptr<Output> out;
     if (a.has_output) out.reset(new Output(a.output, 2));
-    FILE *bed = nullptr;
-    if (a.has_bed) {
-        bed = a.bed == "-" ? stdout : std::fopen(a.bed.c_str(), "w");
-        if (!bed) die("cannot open " + a.bed + " for writing");
-    }
+    TextOut bed;
+    if (a.has_bed) bed.open(a.bed, true);
     FastxReader rd(a.input);
     uint64_t reads_in = 0, bases_in = 0, reads_hit = 0, n_segments = 0, masked = 0;
     std::vector<uint64_t> seg_m(n, 0), bp_m(n, 0);
@@ -3562,23 +3567,15 @@ int run_mask(const MaskArgs &a) {
     std::vector<dcn_segment> segs(1u << 16);
     std::vector<char> text;
     std::string rows;
-    auto run_batch = [&]() {
+    for_each_batch(rd, b, batch_bases, ctx.batch_reads(), [&] {
         const uint32_t n_reads = (uint32_t)b.recs.size();
-        if (n_reads == 0) return;
-        const uint64_t nb = b.offsets.back();
-        if (nb > max_bases) { // a record longer than the context's batch: a context of its size
-            dcn_ctx_destroy(ctx);
-            ctx = nullptr;
-            max_bases = nb;
-            deacon::check(dcn_ctx_create(target, max_bases, max_reads, &ctx));
-        }
+        ctx.fit(b.offsets.back());
         seg_off.assign((size_t)n_reads + 1, 0);
-        int rc = dcn_locate_batch(ctx, target, b.bases.data(), b.offsets.data(), n_reads, &prm, seg_off.data(), segs.data(), segs.size());
-        if (rc == DCN_ERR_CAPACITY && seg_off[n_reads] > segs.size()) { // the count came back: once more with room for it
-            segs.resize(seg_off[n_reads]);
-            rc = dcn_locate_batch(ctx, target, b.bases.data(), b.offsets.data(), n_reads, &prm, seg_off.data(), segs.data(), segs.size());
-        }
-        deacon::check(rc);
+        with_room(segs, [&](dcn_segment *into, size_t room, uint64_t &count) {
+            const int rc = dcn_locate_batch(ctx.p, target, b.bases.data(), b.offsets.data(), n_reads, &prm, seg_off.data(), into, room);
+            count = seg_off[n_reads];
+            return rc;
+        });
         text.clear();
         rows.clear();
         for (uint32_t r = 0; r < n_reads; ++r) {
@@ -3589,8 +3586,7 @@ int run_mask(const MaskArgs &a) {
             bases_in += rec.seq_len;
             reads_hit += s1 > s0;
             n_segments += s1 - s0;
-            size_t id_len = 0;
-            while (id_len < rec.id_len && id[id_len] != ' ' && id[id_len] != '\t') ++id_len;
+            const std::string_view name = id_token(b, rec);
             size_t seq_at = 0;
             if (out) {
                 text.push_back(rec.qual_off == NO_QUAL ? '>' : '@');
@@ -3619,57 +3615,38 @@ int run_mask(const MaskArgs &a) {
                         c = a.soft ? (char)std::tolower((unsigned char)c) : 'N';
                     }
                 if (bed) {
-                    rows.append(id, id_len);
+                    rows.append(name);
                     rows += '\t' + std::to_string(sg.start) + '\t' + std::to_string(end) + '\t' + std::to_string(sg.n_hits) + '\t';
-                    bool any = false;
-                    for (uint32_t j = 0; j < n; ++j)
-                        if (sg.members >> j & 1u) {
-                            if (any) rows += ',';
-                            rows += stems[j];
-                            any = true;
-                        }
+                    append_members(rows, sg.members, stems);
                     rows += '\n';
                 }
             }
         }
         if (out) out->write(text);
-        if (bed) std::fwrite(rows.data(), 1, rows.size(), bed);
-        b.clear();
-    };
-    const uint32_t batch_reads = max_reads - 2;
-    while (rd.next(b))
-        if (b.offsets.back() >= batch_bases || b.recs.size() >= batch_reads) run_batch();
-    run_batch();
+        if (bed) bed.write(rows);
+    });
     if (out) out->close();
-    if (bed && bed != stdout) std::fclose(bed);
-    else if (bed) std::fflush(bed);
-    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+    bed.finish();
+    const double secs = watch.seconds();
     if (!a.quiet)
         std::fprintf(stderr, "Masked %llu bp in %llu segments of %llu/%llu sequences (%llu bp) in %s\n", (unsigned long long)masked,
                      (unsigned long long)n_segments, (unsigned long long)reads_hit, (unsigned long long)reads_in,
                      (unsigned long long)bases_in, fmt_duration(secs).c_str());
     if (a.has_summary) {
-        std::string js = "{\n  \"version\": " + json_str(std::string("deacon-hip ") + VERSION) + ",\n  \"input\": " + json_str(a.input);
-        char buf[512];
-        std::snprintf(buf, sizeof buf, ",\n  \"k\": %u,\n  \"w\": %u,\n  \"max_gap\": %u,\n  \"min_hits\": %u,\n  \"prefix_length\": %zu,\n"
-                                       "  \"soft\": %s,\n  \"reads\": %llu,\n  \"bases\": %llu,\n  \"reads_with_segments\": %llu,\n"
-                                       "  \"segments\": %llu,\n  \"masked_bases\": %llu,\n  \"time\": %.17g,\n  \"indexes\": [",
-                      (unsigned)k, (unsigned)w, prm.max_gap, prm.min_hits, a.prefix_length, a.soft ? "true" : "false",
-                      (unsigned long long)reads_in, (unsigned long long)bases_in, (unsigned long long)reads_hit,
-                      (unsigned long long)n_segments, (unsigned long long)masked, secs);
-        js += buf;
+        std::string js = summary_head() + ",\n  \"input\": " + json_str(a.input);
+        appendf(js, ",\n  \"k\": %u,\n  \"w\": %u,\n  \"max_gap\": %u,\n  \"min_hits\": %u,\n  \"prefix_length\": %zu,\n"
+                    "  \"soft\": %s,\n  \"reads\": %llu,\n  \"bases\": %llu,\n  \"reads_with_segments\": %llu,\n"
+                    "  \"segments\": %llu,\n  \"masked_bases\": %llu,\n  \"time\": %.17g,\n  \"indexes\": [",
+                (unsigned)k, (unsigned)w, prm.max_gap, prm.min_hits, a.prefix_length, a.soft ? "true" : "false",
+                (unsigned long long)reads_in, (unsigned long long)bases_in, (unsigned long long)reads_hit,
+                (unsigned long long)n_segments, (unsigned long long)masked, secs);
         for (uint32_t j = 0; j < n; ++j) {
             js += (j ? ",\n    {" : "\n    {");
             js += "\"path\": " + json_str(a.indexes[j]) + ", \"name\": " + json_str(stems[j]);
-            std::snprintf(buf, sizeof buf, ", \"segments\": %llu, \"masked_bases\": %llu}", (unsigned long long)seg_m[j],
-                          (unsigned long long)bp_m[j]);
-            js += buf;
+            appendf(js, ", \"segments\": %llu, \"masked_bases\": %llu}", (unsigned long long)seg_m[j], (unsigned long long)bp_m[j]);
         }
         js += "\n  ]\n}\n";
-        FILE *f = std::fopen(a.summary.c_str(), "w");
-        if (!f) die("cannot open " + a.summary + " for writing");
-        std::fwrite(js.data(), 1, js.size(), f);
-        std::fclose(f);
+        write_text_file(a.summary, js);
     }
     return 0;
 }
@@ -3683,7 +3660,7 @@ struct PlaceArgs {
 };
 
 int run_place(const PlaceArgs &a) {
-    const auto start = std::chrono::steady_clock::now();
+    const Stopwatch watch;
     if (a.ref.empty()) die("the following required arguments were not provided: <REF>");
     // the reference, whole: its records are the map's records, and without -x its minimizers are the map's keys
     Batch ref;
@@ -3704,28 +3681,10 @@ int run_place(const PlaceArgs &a) {
     deacon::check(dcn_anchor_map_create(keys.p, &map.p));
     dcn_index_destroy(keys.p);
     keys.p = nullptr;
-    uint64_t batch_bases = 32ull << 20, max_bases = 64ull << 20;
-    if (const char *e = std::getenv("DCN_CLI_PLACE_BATCH_BASES")) { // test hook: many batches, records past the context
-        batch_bases = (uint64_t)std::max(64, std::atoi(e));
-        max_bases = 2 * batch_bases;
-    }
-    const uint32_t max_reads = 1u << 20;
-    dcn_ctx *ctx = nullptr;
-    deacon::check(dcn_ctx_create(map.p, max_bases, max_reads, &ctx));
-    struct CtxGuard {
-        dcn_ctx **c;
-        ~CtxGuard() {
-            if (*c) dcn_ctx_destroy(*c);
-        }
-    } guard{&ctx};
-    auto fit = [&](uint64_t nb) { // a record longer than the context's batch: a context of its size
-        if (nb <= max_bases) return;
-        dcn_ctx_destroy(ctx);
-        ctx = nullptr;
-        max_bases = nb;
-        deacon::check(dcn_ctx_create(map.p, max_bases, max_reads, &ctx));
-    };
-    const uint32_t batch_reads = max_reads - 2;
+    const BatchSize size = batch_size("DCN_CLI_PLACE_BATCH_BASES");
+    const uint64_t batch_bases = size.batch_bases;
+    Context ctx(map.p, size.max_bases);
+    const uint32_t batch_reads = ctx.batch_reads();
     // the records, batch by batch: whole records, offsets rebased to the batch
     std::vector<uint64_t> off;
     for (uint32_t r0 = 0; r0 < n_records;) {
@@ -3733,9 +3692,9 @@ int run_place(const PlaceArgs &a) {
         while (r1 < n_records && ref.offsets[r1] - ref.offsets[r0] < batch_bases && r1 - r0 < batch_reads) ++r1;
         off.assign((size_t)(r1 - r0) + 1, 0);
         for (uint32_t r = r0; r <= r1; ++r) off[r - r0] = ref.offsets[r] - ref.offsets[r0];
-        fit(off.back());
+        ctx.fit(off.back());
         uint32_t first = 0;
-        deacon::check(dcn_anchor_map_add(map.p, ctx, ref.bases.data() + ref.offsets[r0], off.data(), r1 - r0, &first));
+        deacon::check(dcn_anchor_map_add(map.p, ctx.p, ref.bases.data() + ref.offsets[r0], off.data(), r1 - r0, &first));
         if (first != r0) die("place: record numbering out of step");
         r0 = r1;
     }
@@ -3745,12 +3704,8 @@ int run_place(const PlaceArgs &a) {
     std::vector<std::string> names(n_records);
     std::vector<uint32_t> lens(n_records);
     for (uint32_t r = 0; r < n_records; ++r) {
-        const Rec &rec = ref.recs[r];
-        const char *id = ref.chars() + rec.id_off;
-        size_t n = 0;
-        while (n < rec.id_len && id[n] != ' ' && id[n] != '\t') ++n;
-        names[r].assign(id, n);
-        lens[r] = rec.seq_len;
+        names[r] = id_token(ref, ref.recs[r]);
+        lens[r] = ref.recs[r].seq_len;
     }
     { // the sequences are on the device's side of things now: only names and lengths are needed from here on
         Batch none;
@@ -3764,72 +3719,55 @@ int run_place(const PlaceArgs &a) {
     prm.band_bases = a.band;
     prm.min_votes = a.min_votes;
     prm.prefix_length = a.prefix_length;
-    FILE *out = a.output == "-" ? stdout : std::fopen(a.output.c_str(), "w");
-    if (!out) die("cannot open " + a.output + " for writing");
+    TextOut out(a.output, true);
     FastxReader rd(a.input);
     uint64_t reads_in = 0, placed = 0, strand[2] = {0, 0};
     std::vector<uint64_t> per_record(n_records, 0);
     Batch b;
     std::vector<dcn_placement> pl;
     std::string rows;
-    auto run_batch = [&]() {
+    for_each_batch(rd, b, batch_bases, batch_reads, [&] {
         const uint32_t n_reads = (uint32_t)b.recs.size();
-        if (n_reads == 0) return;
-        fit(b.offsets.back());
+        ctx.fit(b.offsets.back());
         pl.resize(n_reads);
-        deacon::check(dcn_place_batch(ctx, map.p, b.bases.data(), b.offsets.data(), n_reads, &prm, pl.data()));
+        deacon::check(dcn_place_batch(ctx.p, map.p, b.bases.data(), b.offsets.data(), n_reads, &prm, pl.data()));
         rows.clear();
         for (uint32_t r = 0; r < n_reads; ++r) {
             const Rec &rec = b.recs[r];
-            const char *id = b.chars() + rec.id_off;
-            size_t id_len = 0;
-            while (id_len < rec.id_len && id[id_len] != ' ' && id[id_len] != '\t') ++id_len;
             const dcn_placement &p = pl[r];
             const bool is = p.record != UINT32_MAX;
             ++reads_in;
             if (is) ++placed, ++strand[p.reverse & 1u], ++per_record[p.record];
-            rows.append(id, id_len);
+            rows.append(id_token(b, rec));
             rows += '\t' + std::to_string(rec.seq_len) + '\t' + std::to_string(p.read_start) + '\t' + std::to_string(p.read_end) + '\t';
             rows += is ? (p.reverse ? "-" : "+") : "*";
             rows += '\t' + (is ? names[p.record] : std::string("*")) + '\t' + std::to_string(is ? lens[p.record] : 0u) + '\t' +
                     std::to_string(p.ref_start) + '\t' + std::to_string(p.ref_end) + '\t' + std::to_string(p.votes) + '\t' +
                     std::to_string(p.n_anchors) + '\t' + std::to_string(p.n_positions) + '\n';
         }
-        std::fwrite(rows.data(), 1, rows.size(), out);
-        b.clear();
-    };
-    while (rd.next(b))
-        if (b.offsets.back() >= batch_bases || b.recs.size() >= batch_reads) run_batch();
-    run_batch();
-    if (out != stdout) std::fclose(out);
-    else std::fflush(out);
-    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
+        out.write(rows);
+    });
+    out.finish();
+    const double secs = watch.seconds();
     if (!a.quiet)
         std::fprintf(stderr, "Placed %llu of %llu reads (%llu +, %llu -) in %s\n", (unsigned long long)placed,
                      (unsigned long long)reads_in, (unsigned long long)strand[0], (unsigned long long)strand[1], fmt_duration(secs).c_str());
     if (a.has_summary) {
-        std::string js = "{\n  \"version\": " + json_str(std::string("deacon-hip ") + VERSION) + ",\n  \"reference\": " + json_str(a.ref) +
-                         ",\n  \"input\": " + json_str(a.input);
-        char buf[512];
-        std::snprintf(buf, sizeof buf, ",\n  \"k\": %u,\n  \"w\": %u,\n  \"band_bases\": %u,\n  \"min_votes\": %u,\n  \"prefix_length\": %zu,\n"
-                                       "  \"records\": %u,\n  \"keys\": %llu,\n  \"anchors\": %llu,\n  \"repeats\": %llu,\n"
-                                       "  \"reads\": %llu,\n  \"placed\": %llu,\n  \"placed_by_strand\": {\"+\": %llu, \"-\": %llu},\n"
-                                       "  \"time\": %.17g,\n  \"placed_by_record\": [",
-                      (unsigned)k, (unsigned)w, a.band, a.min_votes, a.prefix_length, m_records, (unsigned long long)m_keys,
-                      (unsigned long long)m_anchors, (unsigned long long)m_repeats, (unsigned long long)reads_in,
-                      (unsigned long long)placed, (unsigned long long)strand[0], (unsigned long long)strand[1], secs);
-        js += buf;
+        std::string js = summary_head() + ",\n  \"reference\": " + json_str(a.ref) + ",\n  \"input\": " + json_str(a.input);
+        appendf(js, ",\n  \"k\": %u,\n  \"w\": %u,\n  \"band_bases\": %u,\n  \"min_votes\": %u,\n  \"prefix_length\": %zu,\n"
+                    "  \"records\": %u,\n  \"keys\": %llu,\n  \"anchors\": %llu,\n  \"repeats\": %llu,\n"
+                    "  \"reads\": %llu,\n  \"placed\": %llu,\n  \"placed_by_strand\": {\"+\": %llu, \"-\": %llu},\n"
+                    "  \"time\": %.17g,\n  \"placed_by_record\": [",
+                (unsigned)k, (unsigned)w, a.band, a.min_votes, a.prefix_length, m_records, (unsigned long long)m_keys,
+                (unsigned long long)m_anchors, (unsigned long long)m_repeats, (unsigned long long)reads_in,
+                (unsigned long long)placed, (unsigned long long)strand[0], (unsigned long long)strand[1], secs);
         for (uint32_t r = 0; r < n_records; ++r) {
             js += (r ? ",\n    {" : "\n    {");
             js += "\"name\": " + json_str(names[r]);
-            std::snprintf(buf, sizeof buf, ", \"length\": %u, \"placed\": %llu}", lens[r], (unsigned long long)per_record[r]);
-            js += buf;
+            appendf(js, ", \"length\": %u, \"placed\": %llu}", lens[r], (unsigned long long)per_record[r]);
         }
         js += "\n  ]\n}\n";
-        FILE *f = std::fopen(a.summary.c_str(), "w");
-        if (!f) die("cannot open " + a.summary + " for writing");
-        std::fwrite(js.data(), 1, js.size(), f);
-        std::fclose(f);
+        write_text_file(a.summary, js);
     }
     return 0;
 }

@@ -52,6 +52,57 @@ def concat_reads(reads):
     return bases, offsets
 
 
+def _batch(bases, offsets):
+    """a batch as the ABI takes it -> (bases u8[], offsets u64[n_reads+1], n_reads)"""
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    return _as_u8(bases), offsets, len(offsets) - 1
+
+
+class _Context:
+    """Owner of one dcn_ctx, `_h`, over an index, a set or an anchor map: what Classifier, Locator, DepthTracker, Placer and
+    FilterProcessor share, and what an AnchorMap holds for its adds."""
+
+    def __init__(self, target_handle, max_batch_bases=1 << 26, max_batch_reads=1 << 20):
+        self.max_batch_bases = int(max_batch_bases)
+        self.max_batch_reads = int(max_batch_reads)
+        self._h = C.c_void_p()
+        N.check(N.lib().dcn_ctx_create(target_handle, self.max_batch_bases, self.max_batch_reads, C.byref(self._h)))
+
+    def synchronize(self):
+        N.check(N.lib().dcn_ctx_synchronize(self._h))
+
+    @property
+    def stream(self):
+        return N.lib().dcn_ctx_stream(self._h)
+
+    def stats(self):
+        c = (C.c_uint64 * N.N_STATS)()
+        N.check(N.lib().dcn_ctx_stats(self._h, c))
+        return dict(zip(N.STAT_NAMES, (int(x) for x in c)))
+
+    def set_profiling(self, enable=True):
+        N.check(N.lib().dcn_ctx_set_profiling(self._h, 1 if enable else 0))
+
+    def profile(self):
+        """-> ({stage: accumulated device ms}, batches measured); HIP events on the context's stream.  What the 'distinct'
+        and 'finish' slots hold depends on the call: see the class."""
+        ms = (C.c_double * N.N_STAGES)()
+        n = C.c_uint64()
+        N.check(N.lib().dcn_ctx_profile(self._h, ms, C.byref(n)))
+        return dict(zip(N.STAGE_NAMES, (float(x) for x in ms))), int(n.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lib().dcn_ctx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def pack_ascii(bases, allow_newline=False):
     """Concatenated ASCII -> (packed u32[2*ceil(n/32)], invmask u32[ceil(n/32)]) in the layout
     dcn_filter_batch_packed takes (PackedSeqVec::from_ascii + the mask loop, filter_common.rs:238-258).
@@ -453,10 +504,12 @@ class IndexSet:
             pass
 
 
-class Classifier:
+class Classifier(_Context):
     """Per-member classification of batches against an IndexSet (dcn_classify_batch): for every unit (read, or pair
     through unit_id) the distinct hits against each member, the minimizer count, and a bit mask of the members whose
-    thresholds the unit meets (the search-mode decision of FilterProcessor against that member alone)."""
+    thresholds the unit meets (the search-mode decision of FilterProcessor against that member alone).
+    profile(): for classify calls the stages are pack, plan, scan (minimizer dump), and the two classification kernels in
+    the 'distinct' (one lane per unit) and 'finish' (one workgroup per large unit) slots."""
 
     def __init__(self, index_set, abs_threshold=2, rel_threshold=0.01, prefix_length=0, device=None,
                  max_batch_bases=1 << 26, max_batch_reads=1 << 20):
@@ -466,10 +519,7 @@ class Classifier:
         self.abs_threshold = int(abs_threshold)
         self.rel_threshold = float(rel_threshold)
         self.prefix_length = int(prefix_length)
-        self.max_batch_bases = int(max_batch_bases)
-        self.max_batch_reads = int(max_batch_reads)
-        self._h = C.c_void_p()
-        N.check(N.lib().dcn_ctx_create(index_set._h, self.max_batch_bases, self.max_batch_reads, C.byref(self._h)))
+        super().__init__(index_set._h, max_batch_bases, max_batch_reads)
 
     def _params(self):
         return Params(self.abs_threshold, self.rel_threshold, self.prefix_length, 0, 0)
@@ -477,9 +527,7 @@ class Classifier:
     def classify_batch(self, bases, offsets, unit_id=None):
         """bases: concatenated ASCII; offsets[n_reads+1]; unit_id groups mates ->
         (match u32[n_units], hits u32[n_units, n], total u32[n_units])"""
-        bases = _as_u8(bases)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n_reads = len(offsets) - 1
+        bases, offsets, n_reads = _batch(bases, offsets)
         if unit_id is not None:
             unit_id = np.ascontiguousarray(unit_id, dtype=np.uint32)
             n_units = int(unit_id[-1]) + 1 if n_reads else 0
@@ -504,50 +552,18 @@ class Classifier:
         N.check(N.lib().dcn_classify_batch_device(self._h, self.index_set._h, d_bases, d_offsets, d_unit_id, n_reads,
                                                   n_bases, n_units, C.byref(p), d_match, d_hits, d_total))
 
-    def synchronize(self):
-        N.check(N.lib().dcn_ctx_synchronize(self._h))
-
-    @property
-    def stream(self):
-        return N.lib().dcn_ctx_stream(self._h)
-
-    def stats(self):
-        c = (C.c_uint64 * N.N_STATS)()
-        N.check(N.lib().dcn_ctx_stats(self._h, c))
-        return dict(zip(N.STAT_NAMES, list(c)))
-
-    def set_profiling(self, enable=True):
-        N.check(N.lib().dcn_ctx_set_profiling(self._h, 1 if enable else 0))
-
-    def profile(self):
-        """(stage_ms, n_batches): for classify calls the stages are pack, plan, scan (minimizer dump), and the two
-        classification kernels in the 'distinct' (one lane per unit) and 'finish' (one workgroup per large unit) slots"""
-        ms = (C.c_double * N.N_STAGES)()
-        n = C.c_uint64()
-        N.check(N.lib().dcn_ctx_profile(self._h, ms, C.byref(n)))
-        return dict(zip(N.STAGE_NAMES, list(ms))), n.value
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lib().dcn_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # numpy view of dcn_segment (16 bytes)
 SEGMENT_DTYPE = np.dtype([("start", np.uint32), ("end", np.uint32), ("n_hits", np.uint32), ("members", np.uint32)])
 
 
-class Locator:
+class Locator(_Context):
     """Where in each read an Index or an IndexSet matched (dcn_locate_batch; the definition of a segment is in
     include/deacon_hip.h): per read, the half-open [start, end) stretches its hit minimizer k-mers cover once hits at most
     max_gap bases apart are joined, with the number of hit positions and the OR of their member labels.
-    max_gap=None is the derived default 2*w - 1; member_mask selects members of a set (ignored for a plain index)."""
+    max_gap=None is the derived default 2*w - 1; member_mask selects members of a set (ignored for a plain index).
+    profile(): pack, plan, scan (minimizer dump), the probe sweep that marks hits in the 'distinct' slot and the segment
+    passes (count, scan over reads, write) in the 'finish' slot."""
 
     def __init__(self, index, max_gap=None, min_hits=1, prefix_length=0, member_mask=0xFFFFFFFF,
                  max_batch_bases=1 << 26, max_batch_reads=1 << 20):
@@ -557,10 +573,7 @@ class Locator:
         self.min_hits = int(min_hits)
         self.prefix_length = int(prefix_length)
         self.member_mask = int(member_mask)
-        self.max_batch_bases = int(max_batch_bases)
-        self.max_batch_reads = int(max_batch_reads)
-        self._h = C.c_void_p()
-        N.check(N.lib().dcn_ctx_create(index._h, self.max_batch_bases, self.max_batch_reads, C.byref(self._h)))
+        super().__init__(index._h, max_batch_bases, max_batch_reads)
 
     def _params(self):
         return N.LocateParams(self.max_gap, self.min_hits, self.member_mask, 0, self.prefix_length)
@@ -568,9 +581,7 @@ class Locator:
     def locate_batch(self, bases, offsets):
         """bases: concatenated ASCII; offsets[n_reads+1] -> (seg_offsets u64[n_reads+1], segs SEGMENT_DTYPE[]): read r
         owns segs[seg_offsets[r]:seg_offsets[r+1]], ascending by start."""
-        bases = _as_u8(bases)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n_reads = len(offsets) - 1
+        bases, offsets, n_reads = _batch(bases, offsets)
         seg_offsets = np.zeros(n_reads + 1, np.uint64)
         p = self._params()
         cap = getattr(self, "_last_total", 0)
@@ -586,45 +597,20 @@ class Locator:
         self._last_total = int(seg_offsets[n_reads])
         return seg_offsets, segs[:int(seg_offsets[n_reads])]
 
-    def stats(self):
-        c = (C.c_uint64 * N.N_STATS)()
-        N.check(N.lib().dcn_ctx_stats(self._h, c))
-        return dict(zip(N.STAT_NAMES, list(c)))
-
-    def set_profiling(self, enable=True):
-        N.check(N.lib().dcn_ctx_set_profiling(self._h, 1 if enable else 0))
-
-    def profile(self):
-        """(stage_ms, n_batches): pack, plan, scan (minimizer dump), the probe sweep that marks hits in the 'distinct' slot
-        and the segment passes (count, scan over reads, write) in the 'finish' slot"""
-        ms = (C.c_double * N.N_STAGES)()
-        n = C.c_uint64()
-        N.check(N.lib().dcn_ctx_profile(self._h, ms, C.byref(n)))
-        return dict(zip(N.STAGE_NAMES, list(ms))), n.value
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lib().dcn_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # numpy view of dcn_track_bin (24 bytes)
 TRACK_BIN_DTYPE = np.dtype([("n_positions", np.uint32), ("n_keys", np.uint32), ("n_observed", np.uint32),
                             ("max_depth", np.uint32), ("sum_depth", np.uint64)])
 
 
-class DepthTracker:
+class DepthTracker(_Context):
     """Depth tracks (dcn_depth_track_batch; the definition of a bin is in include/deacon_hip.h): for every sequence of a
     batch, bins of bin_bases bases (0: one bin per sequence), each with the number of minimizer positions that start in
     it, how many of them are keys of the chosen members, how many of those the classify calls on the set have seen, and
     the sum and the maximum of their depth counters (each capped at depth_cap when that is not 0).  The set has depth
-    enabled; its counters are read, never changed.  member=None: every member; an int or an iterable selects members."""
+    enabled; its counters are read, never changed.  member=None: every member; an int or an iterable selects members.
+    profile(): pack, plan, scan (minimizer dump), the probe sweep that marks positions and reads the counters in the
+    'distinct' slot and the reduction into bins in the 'finish' slot."""
 
     def __init__(self, index_set, max_batch_bases=1 << 26, max_batch_reads=1 << 20, bin_bases=1000, member=None,
                  depth_cap=0, prefix_length=0):
@@ -642,10 +628,7 @@ class DepthTracker:
         self.prefix_length = int(prefix_length)
         if not (0 <= self.bin_bases <= 0xFFFFFFFF and 0 <= self.member_mask <= 0xFFFFFFFF and 0 <= self.depth_cap <= 0xFFFFFFFF):
             raise ValueError("bin_bases / member / depth_cap out of range")
-        self.max_batch_bases = int(max_batch_bases)
-        self.max_batch_reads = int(max_batch_reads)
-        self._h = C.c_void_p()
-        N.check(N.lib().dcn_ctx_create(index_set._h, self.max_batch_bases, self.max_batch_reads, C.byref(self._h)))
+        super().__init__(index_set._h, max_batch_bases, max_batch_reads)
 
     def _params(self):
         return N.TrackParams(self.bin_bases, self.member_mask, self.depth_cap, 0, self.prefix_length)
@@ -653,9 +636,7 @@ class DepthTracker:
     def track_batch(self, bases, offsets):
         """bases: concatenated ASCII; offsets[n_reads+1] -> (bin_offsets u64[n_reads+1], bins TRACK_BIN_DTYPE[]): read r
         owns bins[bin_offsets[r]:bin_offsets[r+1]], bin b of it covers its bases [b * bin_bases, (b + 1) * bin_bases)."""
-        bases = _as_u8(bases)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n_reads = len(offsets) - 1
+        bases, offsets, n_reads = _batch(bases, offsets)
         bin_offsets = np.zeros(n_reads + 1, np.uint64)
         p = self._params()
         rc = N.lib().dcn_depth_track_batch(self._h, self.index_set._h, _ptr(bases) if len(bases) else None, _ptr(offsets),
@@ -676,28 +657,6 @@ class DepthTracker:
         bo, bins = self.track_batch(bases, offsets)
         return [bins[int(bo[r]):int(bo[r + 1])] for r in range(len(seqs))]
 
-    def set_profiling(self, enable=True):
-        N.check(N.lib().dcn_ctx_set_profiling(self._h, 1 if enable else 0))
-
-    def profile(self):
-        """(stage_ms, n_batches): pack, plan, scan (minimizer dump), the probe sweep that marks positions and reads the
-        counters in the 'distinct' slot and the reduction into bins in the 'finish' slot"""
-        ms = (C.c_double * N.N_STAGES)()
-        n = C.c_uint64()
-        N.check(N.lib().dcn_ctx_profile(self._h, ms, C.byref(n)))
-        return dict(zip(N.STAGE_NAMES, list(ms))), n.value
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lib().dcn_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # numpy view of dcn_placement (48 bytes)
 PLACEMENT_DTYPE = np.dtype([("record", np.uint32), ("reverse", np.uint32), ("votes", np.uint32), ("n_anchors", np.uint32),
@@ -717,8 +676,7 @@ class AnchorMap(Index):
         h = C.c_void_p()
         N.check(N.lib().dcn_anchor_map_create(index._h, C.byref(h)))
         super().__init__(h, index.device)
-        self._ctx = C.c_void_p()
-        self._ctx_bases = self._ctx_reads = 0
+        self._ctx = None
 
     def clone(self, device):
         h = C.c_void_p()
@@ -727,24 +685,20 @@ class AnchorMap(Index):
 
     def _context(self, n_bases, n_reads):
         """a context of the map's own, made on the first add and re-made larger for a longer batch"""
-        if self._ctx and n_bases <= self._ctx_bases and n_reads <= self._ctx_reads:
+        have_bases, have_reads = (self._ctx.max_batch_bases, self._ctx.max_batch_reads) if self._ctx else (0, 0)
+        if self._ctx and n_bases <= have_bases and n_reads <= have_reads:
             return self._ctx
         if self._ctx:
-            N.lib().dcn_ctx_destroy(self._ctx)
-            self._ctx = C.c_void_p()
-        bases, reads = max(int(n_bases), self._ctx_bases, 1 << 20), max(int(n_reads), self._ctx_reads, 1 << 10)
-        N.check(N.lib().dcn_ctx_create(self._h, bases, reads, C.byref(self._ctx)))
-        self._ctx_bases, self._ctx_reads = bases, reads
+            self._ctx.close()
+        self._ctx = _Context(self._h, max(int(n_bases), have_bases, 1 << 20), max(int(n_reads), have_reads, 1 << 10))
         return self._ctx
 
     def add(self, bases, offsets):
         """bases: concatenated ASCII; offsets[n_records+1] -> the number of the batch's first record"""
-        bases = _as_u8(bases)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n = len(offsets) - 1
+        bases, offsets, n = _batch(bases, offsets)
         first = C.c_uint32()
         ctx = self._context(int(offsets[-1]) if n > 0 else 0, n)
-        N.check(N.lib().dcn_anchor_map_add(self._h, ctx, _ptr(bases) if len(bases) else None, _ptr(offsets), n, C.byref(first)))
+        N.check(N.lib().dcn_anchor_map_add(self._h, ctx._h, _ptr(bases) if len(bases) else None, _ptr(offsets), n, C.byref(first)))
         return first.value
 
     def add_records(self, records):
@@ -770,16 +724,18 @@ class AnchorMap(Index):
 
     def close(self):
         if getattr(self, "_ctx", None):
-            N.lib().dcn_ctx_destroy(self._ctx)
+            self._ctx.close()
             self._ctx = None
         super().close()
 
 
-class Placer:
+class Placer(_Context):
     """Where on the reference each read lands (dcn_place_batch; the definition of a placement is in
     include/deacon_hip.h): a read's anchor hits vote on a diagonal band of band_bases bases; the best cell, with at least
     min_votes votes, gives the record, the strand and the extents on the read and on the record.  band_bases = 256 and
-    min_votes = 2 are conventions (the 2 is the filter's -a 2), not measured optima."""
+    min_votes = 2 are conventions (the 2 is the filter's -a 2), not measured optima.
+    profile(): pack, plan, scan (minimizer dump), the probe sweep that marks positions and stores their anchors in the
+    'distinct' slot and the vote in the 'finish' slot."""
 
     def __init__(self, anchor_map, max_batch_bases=1 << 26, max_batch_reads=1 << 20, band_bases=256, min_votes=2,
                  prefix_length=0):
@@ -787,19 +743,14 @@ class Placer:
         self.band_bases = int(band_bases)
         self.min_votes = int(min_votes)
         self.prefix_length = int(prefix_length)
-        self.max_batch_bases = int(max_batch_bases)
-        self.max_batch_reads = int(max_batch_reads)
-        self._h = C.c_void_p()
-        N.check(N.lib().dcn_ctx_create(anchor_map._h, self.max_batch_bases, self.max_batch_reads, C.byref(self._h)))
+        super().__init__(anchor_map._h, max_batch_bases, max_batch_reads)
 
     def _params(self):
         return N.PlaceParams(self.band_bases, self.min_votes, self.prefix_length, (C.c_uint32 * 2)(0, 0))
 
     def place_batch(self, bases, offsets):
         """bases: concatenated ASCII; offsets[n_reads+1] -> PLACEMENT_DTYPE[n_reads]"""
-        bases = _as_u8(bases)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n_reads = len(offsets) - 1
+        bases, offsets, n_reads = _batch(bases, offsets)
         out = np.zeros(max(n_reads, 1), PLACEMENT_DTYPE)
         p = self._params()
         N.check(N.lib().dcn_place_batch(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None, _ptr(offsets),
@@ -810,30 +761,8 @@ class Placer:
         bases, offsets = concat_reads(list(reads))
         return self.place_batch(bases, offsets)
 
-    def set_profiling(self, enable=True):
-        N.check(N.lib().dcn_ctx_set_profiling(self._h, 1 if enable else 0))
 
-    def profile(self):
-        """(stage_ms, n_batches): pack, plan, scan (minimizer dump), the probe sweep that marks positions and stores their
-        anchors in the 'distinct' slot and the vote in the 'finish' slot"""
-        ms = (C.c_double * N.N_STAGES)()
-        n = C.c_uint64()
-        N.check(N.lib().dcn_ctx_profile(self._h, ms, C.byref(n)))
-        return dict(zip(N.STAGE_NAMES, list(ms))), n.value
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lib().dcn_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class FilterProcessor:
+class FilterProcessor(_Context):
     """One pipeline context bound to an index: decides keep/drop for units (reads or pairs)."""
 
     def __init__(self, index, abs_threshold=2, rel_threshold=0.01, prefix_length=0, deplete=False,
@@ -843,10 +772,7 @@ class FilterProcessor:
         self.rel_threshold = float(rel_threshold)
         self.prefix_length = int(prefix_length)
         self.deplete = bool(deplete)
-        self.max_batch_bases = int(max_batch_bases)
-        self.max_batch_reads = int(max_batch_reads)
-        self._h = C.c_void_p()
-        N.check(N.lib().dcn_ctx_create(index._h, self.max_batch_bases, self.max_batch_reads, C.byref(self._h)))
+        super().__init__(index._h, max_batch_bases, max_batch_reads)
 
     # -- parameters -----------------------------------------------------------------------------------
     def _params(self):
@@ -857,9 +783,7 @@ class FilterProcessor:
         """bases: concatenated ASCII; offsets[n_reads+1]; unit_id groups mates -> (keep bool[], hits, total).
         counts=False asks for the decisions only (returns just keep): the kernels may then stop probing a read once
         its decision is fixed, which is what `deacon filter` needs outside --debug."""
-        bases = _as_u8(bases)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n_reads = len(offsets) - 1
+        bases, offsets, n_reads = _batch(bases, offsets)
         if unit_id is not None:
             unit_id = np.ascontiguousarray(unit_id, dtype=np.uint32)
             n_units = int(unit_id[-1]) + 1 if n_reads else 0
@@ -891,8 +815,7 @@ class FilterProcessor:
     def submit(self, bases, offsets, unit_id=None, counts=True, out=None):
         """dcn_filter_batch_submit: returns a PendingBatch; up to two may be in flight per processor.
         out = (keep u8[], hits u32[] | None, total u32[] | None) lets the caller supply (page-locked) result arrays."""
-        bases = _as_u8(bases)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        bases, offsets, _ = _batch(bases, offsets)
         if unit_id is not None:
             unit_id = np.ascontiguousarray(unit_id, dtype=np.uint32)
         n_reads, n_units, keep, hits, total = self._outputs(offsets, unit_id, counts, out)
@@ -941,15 +864,8 @@ class FilterProcessor:
         N.check(N.lib().dcn_filter_batch_device(self._h, d_bases, d_offsets, d_unit_id, n_reads, n_bases, n_units,
                                                 C.byref(p), d_keep, d_hits, d_total))
 
-    def synchronize(self):
-        N.check(N.lib().dcn_ctx_synchronize(self._h))
-
     def reserve_records(self, n_records):
         N.check(N.lib().dcn_ctx_reserve_records(self._h, int(n_records)))
-
-    @property
-    def stream(self):
-        return N.lib().dcn_ctx_stream(self._h)
 
     # -- the per-read seam of the reference ----------------------------------------------------------------
     def should_keep_sequence(self, seq):
@@ -961,24 +877,12 @@ class FilterProcessor:
         return bool(keep[0]), int(hits[0]), int(total[0])
 
     # -- counters -------------------------------------------------------------------------------------------
-    def stats(self):
-        c = (C.c_uint64 * N.N_STATS)()
-        N.check(N.lib().dcn_ctx_stats(self._h, c))
-        return dict(zip(N.STAT_NAMES, (int(x) for x in c)))
-
     def reset_stats(self):
         N.check(N.lib().dcn_ctx_reset_stats(self._h))
 
     def set_profiling(self, enable=True):
         """True / 1: every stage; 2: the scan stage only (cheaper: two events per batch); False / 0: off"""
         N.check(N.lib().dcn_ctx_set_profiling(self._h, 2 if enable == 2 else (1 if enable else 0)))
-
-    def profile(self):
-        """-> ({stage: accumulated device ms}, batches measured); HIP events on the context's stream."""
-        ms = (C.c_double * N.N_STAGES)()
-        n = C.c_uint64()
-        N.check(N.lib().dcn_ctx_profile(self._h, ms, C.byref(n)))
-        return dict(zip(N.STAGE_NAMES, (float(x) for x in ms))), int(n.value)
 
     def summary(self, elapsed_seconds):
         """The numeric fields of FilterSummary (filter_common.rs:11-38; filled at local_filter.rs:780-821)."""
@@ -1005,9 +909,7 @@ class FilterProcessor:
     # -- minimizers (parity seam) ------------------------------------------------------------------------------
     def minimizer_hashes_batch(self, bases, offsets, prefix_length=None):
         """-> (out_offsets u64[n+1], hashes u64[], positions u32[]) for every read of the batch."""
-        bases = _as_u8(bases)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n_reads = len(offsets) - 1
+        bases, offsets, n_reads = _batch(bases, offsets)
         pl = self.prefix_length if prefix_length is None else int(prefix_length)
         out_off = np.zeros(n_reads + 1, np.uint64)
         cap = max(int(len(bases)), 1)
@@ -1029,17 +931,6 @@ class FilterProcessor:
         N.check(N.lib().dcn_should_keep_hashes(self._h, _ptr(hashes) if len(hashes) else None, _ptr(hash_offsets),
                                                n_units, C.byref(p), _ptr(keep), _ptr(hits), _ptr(total)))
         return keep[:n_units].astype(bool), hits[:n_units], total[:n_units]
-
-    def close(self):
-        if getattr(self, "_h", None):
-            N.lib().dcn_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def stats_allreduce(processors):

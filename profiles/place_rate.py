@@ -31,19 +31,15 @@ amap = dcn.AnchorMap(index)
 amap.add_records([host[:1_000_000]])  # (untimed: makes the map's context; a map of its own below is the one timed)
 amap.close()
 amap = dcn.AnchorMap(index)
-amap._context(len(host), 1)
-N, C = dcn._native, __import__("ctypes")
-N.check(N.lib().dcn_ctx_set_profiling(amap._ctx, 1))
+amap._context(len(host), 1).set_profiling(True)
 t0 = time.perf_counter()
 amap.add_records([host])
 add_s = time.perf_counter() - t0
-ms = (C.c_double * N.N_STAGES)()
-nb = C.c_uint64()
-N.check(N.lib().dcn_ctx_profile(amap._ctx, ms, C.byref(nb)))
+ms, _ = amap._ctx.profile()
 info = amap.info()
 print(f"map: {info} over {index.n_keys:,} keys ({index.table_bytes / 1e9:.2f} GB of table, {index.table_bytes / 1e9:.2f} GB of words) | "
       f"dcn_anchor_map_add of the 64 Mbp record: {add_s * 1e3:.1f} ms wall, stages (ms) "
-      f"{dict(zip(N.STAGE_NAMES, (round(float(x), 3) for x in ms)))} (distinct = the anchor sweep)", flush=True)
+      f"{ {k: round(v, 3) for k, v in ms.items()} } (distinct = the anchor sweep)", flush=True)
 
 
 def timed(fn):

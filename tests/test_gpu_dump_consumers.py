@@ -171,3 +171,67 @@ def test_every_consumer_on_one_context(oracle, dcn, world, order, pack_ahead, mo
         clf.close()
         amap.close()
         s.close()
+
+
+STATS = {"total_seqs", "filtered_seqs", "total_bp", "output_bp", "filtered_bp", "output_seq_counter"}
+STAGES = {"pack", "plan", "scan", "distinct", "finish"}
+
+
+def test_context_owners(oracle, dcn):
+    """The five classes that are a context and the AnchorMap that holds one: stats() and profile() keep their keys, close()
+    twice is harmless and leaves `_h` None; the map's context is re-created once for a batch longer than it, and kept for a
+    shorter one after"""
+    rng = np.random.default_rng(813)
+    alpha = np.frombuffer(b"ACGT", np.uint8)
+    genome = alpha[rng.integers(0, 4, 1500)].tobytes()
+    keys = oracle.Index.build([genome], k=K, w=W).keys()
+    assert 50 < len(keys) < 400
+    index = dcn.Index.from_keys(keys, K, W)
+    s = dcn.IndexSet([index])
+    s.enable_depth()
+    amap = dcn.AnchorMap(index)
+    b, o = oracle.concat_reads([genome[100:300], genome[700:900]])
+    small = dict(max_batch_bases=1 << 12, max_batch_reads=1 << 4)
+    owners = [(dcn.FilterProcessor(index, **small), lambda x: x.filter_batch(b, o)),
+              (dcn.Classifier(s, **small), lambda x: x.classify_batch(b, o)),
+              (dcn.Locator(index, **small), lambda x: x.locate_batch(b, o)),
+              (dcn.DepthTracker(s, **small), lambda x: x.track_batch(b, o)),
+              (dcn.Placer(amap, **small), lambda x: x.place_batch(b, o))]
+    try:
+        # the map: no context before the first add; the floor of 1 Mi bases / 1 Ki reads; grow only
+        assert amap._ctx is None
+        assert amap.add(b, o) == 0
+        first = amap._ctx
+        assert (first.max_batch_bases, first.max_batch_reads) == (1 << 20, 1 << 10) and first._h
+        long_record = alpha[rng.integers(0, 4, 2_000_000)].tobytes()
+        assert amap.add_records([long_record]) == 2
+        second = amap._ctx
+        assert second is not first and first._h is None and second._h
+        assert (second.max_batch_bases, second.max_batch_reads) == (2_000_000, 1 << 10)
+        handle = second._h.value
+        assert amap.add(b, o) == 3
+        assert amap._ctx is second and second._h.value == handle and second.max_batch_bases == 2_000_000
+        assert amap.info()["records"] == 5
+        for obj, call in owners:
+            assert (obj.max_batch_bases, obj.max_batch_reads) == (1 << 12, 1 << 4)
+            obj.set_profiling(True)
+            call(obj)
+            obj.synchronize()
+            stage_ms, n_batches = obj.profile()
+            assert set(stage_ms) == STAGES and all(isinstance(v, float) for v in stage_ms.values()), type(obj)
+            assert isinstance(n_batches, int) and n_batches >= 1, type(obj)
+            st = obj.stats()
+            assert set(st) == STATS and all(isinstance(v, int) for v in st.values()), type(obj)
+            obj.close()
+            assert obj._h is None
+            obj.close()
+            assert obj._h is None
+        amap.close()
+        assert amap._ctx is None and amap._h is None and second._h is None
+        amap.close()
+    finally:
+        for obj, _ in owners:
+            obj.close()
+        amap.close()
+        s.close()
+        index.close()
