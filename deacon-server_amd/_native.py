@@ -96,6 +96,28 @@ class Placement(C.Structure):
     ]
 
 
+class PlaceSplitParams(C.Structure):
+    _fields_ = [
+        ("band_bases", C.c_uint32),
+        ("min_votes", C.c_uint32),
+        ("prefix_length", C.c_uint64),
+        ("max_placements", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+
+class SplitPlacement(C.Structure):
+    _fields_ = Placement._fields_ + [
+        ("rank", C.c_uint32),
+        ("n_placed", C.c_uint32),
+        ("rival_votes", C.c_uint32),
+        ("mapq", C.c_uint32),
+    ]
+
+
+PLACE_SPLIT_MAX = 8  # DCN_PLACE_SPLIT_MAX
+
+
 def build(force=False, jobs=6):
     """Compile every HIP source for gfx950 into lib/libdeacon_hip.so (hipcc cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -200,10 +222,11 @@ _SIGNATURES = {
     "dcn_anchor_map_info": (C.c_int, [_vp, _u32p, _u64p, _u64p, _u64p]),
     "dcn_anchor_map_anchors": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _u64p]),
     "dcn_place_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp]),
+    "dcn_place_split_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp]),
 }
 
 _lib = None
-ABI = (1, 9)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 10)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

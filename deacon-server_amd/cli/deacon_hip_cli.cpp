@@ -3659,32 +3659,45 @@ struct PlaceArgs {
     size_t prefix_length = 0;
 };
 
-int run_place(const PlaceArgs &a) {
-    const Stopwatch watch;
-    if (a.ref.empty()) die("the following required arguments were not provided: <REF>");
-    // the reference, whole: its records are the map's records, and without -x its minimizers are the map's keys
+// The reference of `place` and `map`, whole: its records are the map's records, and without -x its minimizers are the
+// map's keys.  What is left of it afterwards: the map, a context over it, and the records' names and lengths.
+struct AnchorRef {
+    RawIndex map;
+    std::unique_ptr<Context> ctx;  // (after the map: destroyed before it)
+    uint64_t batch_bases = 0;
+    uint32_t batch_reads = 0, n_records = 0, m_records = 0;
+    uint64_t m_keys = 0, m_anchors = 0, m_repeats = 0;
+    uint8_t k = 0, w = 0;
+    std::vector<std::string> names;
+    std::vector<uint32_t> lens;
+};
+
+void load_anchor_ref(AnchorRef &R, const std::string &ref_path, bool has_index, const std::string &index, unsigned k_arg,
+                     unsigned w_arg, const char *batch_hook, bool quiet) {
+    if (ref_path.empty()) die("the following required arguments were not provided: <REF>");
     Batch ref;
     {
-        FastxReader rd(a.ref);
+        FastxReader rd(ref_path);
         while (rd.next(ref)) {
         }
     }
-    const uint32_t n_records = (uint32_t)ref.recs.size();
-    if (n_records == 0) die("no records in " + a.ref);
-    RawIndex keys, map;
-    if (a.has_index) deacon::check(dcn_index_from_file(a.index.c_str(), 0, &keys.p));
+    const uint32_t n_records = R.n_records = (uint32_t)ref.recs.size();
+    if (n_records == 0) die("no records in " + ref_path);
+    RawIndex keys;
+    RawIndex &map = R.map;
+    if (has_index) deacon::check(dcn_index_from_file(index.c_str(), 0, &keys.p));
     else
-        deacon::check(dcn_index_build(ref.bases.data(), ref.offsets.data(), n_records, (uint8_t)a.k, (uint8_t)a.w, 0.0f,
+        deacon::check(dcn_index_build(ref.bases.data(), ref.offsets.data(), n_records, (uint8_t)k_arg, (uint8_t)w_arg, 0.0f,
                                       ref.bases.size() / 4 + 1024, 0, &keys.p));
-    uint8_t k = 0, w = 0;
-    deacon::check(dcn_index_header(keys.p, &k, &w, nullptr));
+    deacon::check(dcn_index_header(keys.p, &R.k, &R.w, nullptr));
     deacon::check(dcn_anchor_map_create(keys.p, &map.p));
     dcn_index_destroy(keys.p);
     keys.p = nullptr;
-    const BatchSize size = batch_size("DCN_CLI_PLACE_BATCH_BASES");
-    const uint64_t batch_bases = size.batch_bases;
-    Context ctx(map.p, size.max_bases);
-    const uint32_t batch_reads = ctx.batch_reads();
+    const BatchSize size = batch_size(batch_hook);
+    const uint64_t batch_bases = R.batch_bases = size.batch_bases;
+    R.ctx.reset(new Context(map.p, size.max_bases));
+    Context &ctx = *R.ctx;
+    const uint32_t batch_reads = R.batch_reads = ctx.batch_reads();
     // the records, batch by batch: whole records, offsets rebased to the batch
     std::vector<uint64_t> off;
     for (uint32_t r0 = 0; r0 < n_records;) {
@@ -3698,22 +3711,32 @@ int run_place(const PlaceArgs &a) {
         if (first != r0) die("place: record numbering out of step");
         r0 = r1;
     }
-    uint32_t m_records = 0;
-    uint64_t m_keys = 0, m_anchors = 0, m_repeats = 0;
-    deacon::check(dcn_anchor_map_info(map.p, &m_records, &m_keys, &m_anchors, &m_repeats));
-    std::vector<std::string> names(n_records);
-    std::vector<uint32_t> lens(n_records);
+    deacon::check(dcn_anchor_map_info(map.p, &R.m_records, &R.m_keys, &R.m_anchors, &R.m_repeats));
+    R.names.resize(n_records);
+    R.lens.resize(n_records);
     for (uint32_t r = 0; r < n_records; ++r) {
-        names[r] = id_token(ref, ref.recs[r]);
-        lens[r] = ref.recs[r].seq_len;
+        R.names[r] = id_token(ref, ref.recs[r]);
+        R.lens[r] = ref.recs[r].seq_len;
     }
-    { // the sequences are on the device's side of things now: only names and lengths are needed from here on
-        Batch none;
-        std::swap(ref, none);
-    }
-    if (!a.quiet)
-        std::fprintf(stderr, "Anchor map: %u records, %llu keys, %llu anchors, %llu repeats (k=%u, w=%u)\n", m_records,
-                     (unsigned long long)m_keys, (unsigned long long)m_anchors, (unsigned long long)m_repeats, (unsigned)k, (unsigned)w);
+    // (the sequences are on the device's side of things now: only names and lengths are needed from here on)
+    if (!quiet)
+        std::fprintf(stderr, "Anchor map: %u records, %llu keys, %llu anchors, %llu repeats (k=%u, w=%u)\n", R.m_records,
+                     (unsigned long long)R.m_keys, (unsigned long long)R.m_anchors, (unsigned long long)R.m_repeats,
+                     (unsigned)R.k, (unsigned)R.w);
+}
+
+int run_place(const PlaceArgs &a) {
+    const Stopwatch watch;
+    AnchorRef R;
+    load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, "DCN_CLI_PLACE_BATCH_BASES", a.quiet);
+    RawIndex &map = R.map;
+    Context &ctx = *R.ctx;
+    const uint64_t batch_bases = R.batch_bases;
+    const uint32_t batch_reads = R.batch_reads, n_records = R.n_records, m_records = R.m_records;
+    const uint64_t m_keys = R.m_keys, m_anchors = R.m_anchors, m_repeats = R.m_repeats;
+    const uint8_t k = R.k, w = R.w;
+    const std::vector<std::string> &names = R.names;
+    const std::vector<uint32_t> &lens = R.lens;
 
     dcn_place_params prm = {};
     prm.band_bases = a.band;
@@ -3772,6 +3795,102 @@ int run_place(const PlaceArgs &a) {
     return 0;
 }
 
+// ---- map: up to N placements per read with rival votes and a quality, as PAF ------------------------------------------
+struct MapArgs {
+    std::string ref, input = "-", index, output = "-", summary;
+    bool has_index = false, has_summary = false, quiet = false;
+    unsigned k = 31, w = 15, band = 256, min_votes = 2, max_placements = 4;
+    size_t prefix_length = 0;
+};
+
+// one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
+// hits of the read), ns (positions of the read)
+void append_paf(std::string &rows, const std::string &read_name, uint32_t read_len, const dcn_split_placement &p,
+                const std::string &record_name, uint32_t record_len, uint32_t k) {
+    const uint64_t on_read = p.read_end - p.read_start, on_ref = p.ref_end - p.ref_start;
+    const uint64_t matches = std::min<uint64_t>((uint64_t)p.votes * k, on_read);
+    rows.append(read_name);
+    rows += '\t' + std::to_string(read_len) + '\t' + std::to_string(p.read_start) + '\t' + std::to_string(p.read_end) + '\t';
+    rows += p.reverse ? '-' : '+';
+    rows += '\t' + record_name + '\t' + std::to_string(record_len) + '\t' + std::to_string(p.ref_start) + '\t' +
+            std::to_string(p.ref_end) + '\t' + std::to_string(matches) + '\t' + std::to_string(std::max(on_read, on_ref)) + '\t' +
+            std::to_string(p.mapq);
+    rows += "\tcm:i:" + std::to_string(p.votes) + "\trk:i:" + std::to_string(p.rank) + "\tnp:i:" + std::to_string(p.n_placed) +
+            "\trv:i:" + std::to_string(p.rival_votes) + "\tna:i:" + std::to_string(p.n_anchors) + "\tns:i:" +
+            std::to_string(p.n_positions) + '\n';
+}
+
+int run_map(const MapArgs &a) {
+    const Stopwatch watch;
+    AnchorRef R;
+    load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, "DCN_CLI_MAP_BATCH_BASES", a.quiet);
+    Context &ctx = *R.ctx;
+    dcn_place_split_params prm = {};
+    prm.band_bases = a.band;
+    prm.min_votes = a.min_votes;
+    prm.prefix_length = a.prefix_length;
+    prm.max_placements = a.max_placements;
+    TextOut out(a.output, true);
+    FastxReader rd(a.input);
+    uint64_t reads_in = 0, placed = 0, split_reads = 0, placements = 0, mapq60 = 0, mapq0 = 0;
+    std::vector<uint64_t> per_record(R.n_records, 0);
+    Batch b;
+    std::vector<uint64_t> place_off;
+    std::vector<dcn_split_placement> pl;
+    std::string rows;
+    for_each_batch(rd, b, R.batch_bases, R.batch_reads, [&] {
+        const uint32_t n_reads = (uint32_t)b.recs.size();
+        ctx.fit(b.offsets.back());
+        place_off.assign((size_t)n_reads + 1, 0);
+        pl.resize((size_t)n_reads * a.max_placements);  // (never more than max_placements per read)
+        deacon::check(dcn_place_split_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &prm, place_off.data(),
+                                            pl.data(), pl.size(), nullptr));
+        rows.clear();
+        for (uint32_t r = 0; r < n_reads; ++r) {
+            const Rec &rec = b.recs[r];
+            const uint64_t p0 = place_off[r], p1 = place_off[r + 1];
+            ++reads_in;
+            if (p1 > p0) ++placed;
+            if (p1 > p0 + 1) ++split_reads;
+            placements += p1 - p0;
+            const std::string name(p1 > p0 ? id_token(b, rec) : std::string_view());
+            for (uint64_t q = p0; q < p1; ++q) {
+                const dcn_split_placement &p = pl[q];
+                ++per_record[p.record];
+                mapq60 += p.mapq == 60, mapq0 += p.mapq == 0;
+                append_paf(rows, name, rec.seq_len, p, R.names[p.record], R.lens[p.record], R.k);
+            }
+        }
+        out.write(rows);
+    });
+    out.finish();
+    const double secs = watch.seconds();
+    if (!a.quiet)
+        std::fprintf(stderr, "Mapped %llu of %llu reads in %llu placements (%llu reads with two or more) in %s\n",
+                     (unsigned long long)placed, (unsigned long long)reads_in, (unsigned long long)placements,
+                     (unsigned long long)split_reads, fmt_duration(secs).c_str());
+    if (a.has_summary) {
+        std::string js = summary_head() + ",\n  \"reference\": " + json_str(a.ref) + ",\n  \"input\": " + json_str(a.input);
+        appendf(js, ",\n  \"k\": %u,\n  \"w\": %u,\n  \"band_bases\": %u,\n  \"min_votes\": %u,\n  \"prefix_length\": %zu,\n"
+                    "  \"records\": %u,\n  \"keys\": %llu,\n  \"anchors\": %llu,\n  \"repeats\": %llu,\n"
+                    "  \"reads\": %llu,\n  \"placed\": %llu,\n  \"max_placements\": %u,\n  \"placements\": %llu,\n"
+                    "  \"split_reads\": %llu,\n  \"mapq60\": %llu,\n  \"mapq0\": %llu,\n"
+                    "  \"time\": %.17g,\n  \"placements_by_record\": [",
+                (unsigned)R.k, (unsigned)R.w, a.band, a.min_votes, a.prefix_length, R.m_records, (unsigned long long)R.m_keys,
+                (unsigned long long)R.m_anchors, (unsigned long long)R.m_repeats, (unsigned long long)reads_in,
+                (unsigned long long)placed, a.max_placements, (unsigned long long)placements, (unsigned long long)split_reads,
+                (unsigned long long)mapq60, (unsigned long long)mapq0, secs);
+        for (uint32_t r = 0; r < R.n_records; ++r) {
+            js += (r ? ",\n    {" : "\n    {");
+            js += "\"name\": " + json_str(R.names[r]);
+            appendf(js, ", \"length\": %u, \"placements\": %llu}", R.lens[r], (unsigned long long)per_record[r]);
+        }
+        js += "\n  ]\n}\n";
+        write_text_file(a.summary, js);
+    }
+    return 0;
+}
+
 void usage() {
     std::fprintf(stderr,
                  "Usage: deacon-hip <COMMAND>\n\nCommands:\n  index   Build and compose minimizer indexes (build, info, union, diff, intersect, compare, select)\n"
@@ -3779,6 +3898,7 @@ void usage() {
                  "  classify  Report which of several indexes each record (or pair) matches, in one pass\n"
                  "  mask    Report where in each record an index matched, and mask those stretches\n"
                  "  place   Report which record of a reference each read came from, where, and on which strand\n"
+                 "  map     Report up to N placements per read on a reference, each with a mapping quality, as PAF\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -3909,6 +4029,36 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "  -q, --quiet                    Suppress progress reporting\n"
                "  -h, --help                     Print help\n\n"
                "A key that occurs at exactly one place of <REF> is an anchor; keys that occur at several never vote.\n"
+               "Mates are independent here: one input.\n";
+    else if (sub == "map")
+        text = "Report up to N placements of each read on a reference, with rival votes and a mapping quality, as PAF\n\n"
+               "Usage: deacon-hip map [OPTIONS] <REF> [READS]\n\n"
+               "Arguments:\n"
+               "  <REF>     Path to the reference fastx file: its records are numbered and named in file order\n"
+               "  [READS]   Optional path to fastx file (or - for stdin; gz, bgzf, zst, xz and bz2 found by content) [default: -]\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Keys that may anchor: a minimizer index file, whose k and w are used\n"
+               "                                 [default: the minimizers of <REF> at -k / -w]\n"
+               "  -k <K>                         K-mer length without -x [default: 31]\n"
+               "  -w <W>                         Minimizer window size without -x [default: 15]\n"
+               "  -o, --output <OUTPUT>          PAF, one line per placement, reads in input order, ranks ascending, no line\n"
+               "                                 for an unplaced read (- for stdout) [default: -].  Column 10 is\n"
+               "                                 min(votes * k, read_end - read_start), column 11 the longer of the two\n"
+               "                                 extents, column 12 the mapping quality; tags: cm votes, rk rank, np placements\n"
+               "                                 of the read, rv rival votes, na anchor hits and ns positions of the read\n"
+               "  -N, --max-placements <N>       Placements per read, each from the anchor hits no earlier one explained (1..8)\n"
+               "                                 [default: 4]\n"
+               "      --band <N>                 Width of a diagonal band in bases [default: 256, a convention]\n"
+               "  -a, --min-votes <N>            Minimum number of anchor hits in a placement's cell [default: 2, as filter's -a,\n"
+               "                                 a convention]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per read (0 = entire read) [default: 0]\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
+               "  -h, --help                     Print help\n\n"
+               "A key that occurs at exactly one place of <REF> is an anchor; keys that occur at several never vote.\n"
+               "The mapping quality is 60 * (votes - rival votes) / votes, where the rival is the strongest other cell on the\n"
+               "same stretch of the read (0 when it is as strong): a convention, not a calibrated probability.\n"
                "Mates are independent here: one input.\n";
     else if (sub == "index build")
         text = "Index minimizers contained within a fastx file\n\n"
@@ -4162,6 +4312,37 @@ int main(int argc, char **argv) {
             if (pos.size() > 1) a.input = pos[1];
             if (pos.size() > 2) die("place takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[2] + "')");
             return run_place(a);
+        }
+        if (args[0] == "map") {
+            MapArgs a;
+            std::vector<std::string> pos;
+            auto number = [&](const std::string &v, const char *flag, long long lo, long long hi) {
+                char *end = nullptr;
+                const long long x = std::strtoll(v.c_str(), &end, 10);
+                if (v.empty() || *end || x < lo || x > hi)
+                    die(std::string("invalid value for ") + flag + ": must be " + std::to_string(lo) + ".." + std::to_string(hi));
+                return x;
+            };
+            for (size_t i = 1; i < args.size(); ++i) {
+                const std::string &s = args[i];
+                if (s == "-x" || s == "--index") a.index = need(++i), a.has_index = true;
+                else if (s == "-k") a.k = (unsigned)number(need(++i), "-k", 1, 56);
+                else if (s == "-w") a.w = (unsigned)number(need(++i), "-w", 1, 255);
+                else if (s == "-o" || s == "--output") a.output = need(++i);
+                else if (s == "-N" || s == "--max-placements") a.max_placements = (unsigned)number(need(++i), "-N", 1, DCN_PLACE_SPLIT_MAX);
+                else if (s == "--band") a.band = (unsigned)number(need(++i), "--band", 1, 0xFFFFFFFFll);
+                else if (s == "-a" || s == "--min-votes") a.min_votes = (unsigned)number(need(++i), "--min-votes", 1, 0xFFFFFFFFll);
+                else if (s == "-p" || s == "--prefix-length") a.prefix_length = (size_t)number(need(++i), "--prefix-length", 0, 0x7FFFFFFFFFFFFFFFll);
+                else if (s == "-s" || s == "--summary") a.summary = need(++i), a.has_summary = true;
+                else if (s == "-t" || s == "--threads") ++i;
+                else if (s == "-q" || s == "--quiet") a.quiet = true;
+                else if (s.size() > 1 && s[0] == '-' && s != "-") die("unexpected argument '" + s + "'");
+                else pos.push_back(s);
+            }
+            if (pos.size() > 0) a.ref = pos[0];
+            if (pos.size() > 1) a.input = pos[1];
+            if (pos.size() > 2) die("map takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[2] + "')");
+            return run_map(a);
         }
         if (args[0] == "cat" && args.size() >= 2) {  // hidden: the input side alone (format found by content, decoded to stdout; no GPU)
             Input in(args[1]);

@@ -78,7 +78,9 @@ static void free_ctx(dcn_ctx *c) {
                    c->d_cls_big, c->d_cls_n_big, c->d_cls_match, c->d_cls_hits, c->d_cls_total,
                    c->d_loc_bits, c->d_loc_labels, c->d_loc_counts, c->d_loc_big, c->d_loc_n_big, c->d_loc_block_sums,
                    c->d_loc_seg_offsets, c->d_loc_segs, c->d_trk_bin_offsets, c->d_trk_piece_offsets, c->d_trk_bins,
-                   c->d_plc_words, c->d_plc_abits, c->d_plc_big, c->d_plc_n_big, c->d_plc_out};
+                   c->d_plc_words, c->d_plc_abits, c->d_plc_big, c->d_plc_n_big, c->d_plc_out,
+                   c->d_pls_rbits, c->d_pls_n_rounds, c->d_pls_read_counts, c->d_pls_counts, c->d_pls_block_sums,
+                   c->d_pls_offsets, c->d_pls_rounds, c->d_pls_out};
     for (void *p : dev)
         if (p && !((char *)p >= c->d_slab && (char *)p < c->d_slab + c->slab_bytes)) hipFree(p);
     if (c->d_slab) hipFree(c->d_slab);

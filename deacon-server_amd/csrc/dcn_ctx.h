@@ -14,6 +14,8 @@
 #include <functional>
 #include <vector>
 
+struct dcn_split_round; // (dcn_place.h)
+
 // One pipeline step of a host batch: reads [r0, r1) = units [u0, u1) = bases [b0, b1) of the batch stream.
 // groups [g0, g1) of the invalid-base mask that crossed the link as their non-zero words only: n (group, word) pairs at
 // pairs_off of the slot's pair buffer; the range is cleared and the pairs scattered in front of the chunk's kernels
@@ -158,6 +160,15 @@ struct dcn_ctx {
     uint64_t *d_plc_words = nullptr;
     uint32_t *d_plc_abits = nullptr, *d_plc_big = nullptr, *d_plc_n_big = nullptr;
     dcn_placement *d_plc_out = nullptr;
+    // split placement buffers (lazy, first dcn_place_split_batch; dcn_place.h): the copy of the anchor bitmap that the
+    // rounds clear, per read the round count, the two counts, the placement count and the CSR offsets with the scan's
+    // block sums; the rounds and the rows grow to the largest n_reads * (max_placements + 1) and n_reads * max_placements
+    uint32_t *d_pls_rbits = nullptr, *d_pls_n_rounds = nullptr, *d_pls_read_counts = nullptr, *d_pls_counts = nullptr;
+    unsigned long long *d_pls_block_sums = nullptr;
+    uint64_t *d_pls_offsets = nullptr;
+    dcn_split_round *d_pls_rounds = nullptr;
+    dcn_split_placement *d_pls_out = nullptr;
+    uint64_t pls_round_cap = 0, pls_out_cap = 0;
     // deferred state of the last enqueued device-API batch
     bool batch_pending = false;
     bool lean = false; // a small host batch is being submitted: copies and result copies go on `stream` itself (submit_impl)

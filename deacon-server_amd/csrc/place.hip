@@ -136,41 +136,6 @@ __global__ __launch_bounds__(DCN_PLC_THREADS) void anchor_export_kernel(const ui
 }
 
 // ---- vote ---------------------------------------------------------------------------------------------------------
-// an anchor hit of a read: the word of base p = o0 + q of a read of len bases
-struct plc_hit {
-    uint32_t rec1; // record + 1
-    uint32_t o;    // 0: '+', 1: '-'
-    uint32_t q, P;
-    uint64_t j;    // D / W: the hit votes for cells j and j + 1 of (record, o)
-};
-__device__ inline plc_hit plc_decode(uint64_t w, uint32_t q, uint64_t len, uint32_t band) {
-    plc_hit h;
-    h.rec1 = (uint32_t)(w >> 33);
-    h.o = (uint32_t)(w & 1);
-    h.q = q;
-    h.P = dcn_anchor_position(w);
-    const uint64_t D = h.o ? (uint64_t)h.P + q : (uint64_t)h.P + len - q;
-    h.j = D / band;
-    return h;
-}
-
-// a cell and its votes; better(): more votes, then the smaller (record, o, j)
-struct plc_cell {
-    uint32_t votes, rec1, o;
-    uint64_t j;
-};
-__device__ inline plc_cell plc_no_cell() { return plc_cell{0, 0, 0, 0}; }
-__device__ inline bool plc_better(uint32_t votes, uint32_t rec1, uint32_t o, uint64_t j, const plc_cell &b) {
-    if (votes != b.votes) return votes > b.votes;
-    if (rec1 != b.rec1) return rec1 < b.rec1;
-    if (o != b.o) return o < b.o;
-    return j < b.j;
-}
-
-struct plc_extent {
-    uint32_t q0 = ~0u, q1 = 0, P0 = ~0u, P1 = 0;
-};
-
 __device__ inline void plc_write(const dcn_place_args &a, uint32_t r, const plc_cell &best, const plc_extent &x,
                                  uint32_t n_anchors, uint32_t n_positions) {
     dcn_placement out;
@@ -250,14 +215,6 @@ __global__ __launch_bounds__(DCN_PLC_THREADS) void place_lane_kernel(dcn_place_a
         }
     }
     plc_write(a, (uint32_t)r, best, bx, n_anchors, n_positions);
-}
-
-__device__ inline uint64_t plc_mix(uint64_t x) {
-    x ^= x >> 33;
-    x *= 0xFF51AFD7ED558CCDull;
-    x ^= x >> 33;
-    x *= 0xC4CEB9FE1A85EC53ull;
-    return x ^ (x >> 33);
 }
 
 // one workgroup per listed read

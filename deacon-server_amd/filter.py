@@ -663,6 +663,9 @@ PLACEMENT_DTYPE = np.dtype([("record", np.uint32), ("reverse", np.uint32), ("vot
                             ("n_positions", np.uint32), ("read_start", np.uint32), ("read_end", np.uint32),
                             ("reserved", np.uint32), ("ref_start", np.uint64), ("ref_end", np.uint64)])
 UNPLACED = 0xFFFFFFFF
+# numpy view of dcn_split_placement (64 bytes): the fields of dcn_placement, then rank, n_placed, rival_votes, mapq
+SPLIT_PLACEMENT_DTYPE = np.dtype(PLACEMENT_DTYPE.descr + [("rank", np.uint32), ("n_placed", np.uint32),
+                                                          ("rival_votes", np.uint32), ("mapq", np.uint32)])
 
 
 class AnchorMap(Index):
@@ -735,7 +738,8 @@ class Placer(_Context):
     min_votes votes, gives the record, the strand and the extents on the read and on the record.  band_bases = 256 and
     min_votes = 2 are conventions (the 2 is the filter's -a 2), not measured optima.
     profile(): pack, plan, scan (minimizer dump), the probe sweep that marks positions and stores their anchors in the
-    'distinct' slot and the vote in the 'finish' slot."""
+    'distinct' slot and the vote in the 'finish' slot.  place_split_batch / place_split report up to max_placements
+    placements per read with rival votes and a quality (dcn_place_split_batch); one Placer serves both kinds of call."""
 
     def __init__(self, anchor_map, max_batch_bases=1 << 26, max_batch_reads=1 << 20, band_bases=256, min_votes=2,
                  prefix_length=0):
@@ -760,6 +764,33 @@ class Placer(_Context):
     def place(self, reads):
         bases, offsets = concat_reads(list(reads))
         return self.place_batch(bases, offsets)
+
+    def place_split_batch(self, bases, offsets, max_placements=4, capacity=None):
+        """Up to max_placements (1..8) placements per read, each from the anchor hits that no earlier one explained, with
+        the votes of the strongest competing cell on the same stretch of the read and mapq = 60 * (votes - rival_votes)
+        // votes (a convention, not a calibrated probability; dcn_place_split_batch, the definition is in
+        include/deacon_hip.h).  bases: concatenated ASCII; offsets[n_reads+1] -> (place_offsets u64[n_reads+1],
+        SPLIT_PLACEMENT_DTYPE[place_offsets[-1]], read_counts u32[n_reads, 2]): read r owns
+        placements[place_offsets[r]:place_offsets[r+1]], ranks ascending, and read_counts[r] = (n_anchors, n_positions)
+        also where it owns nothing.  capacity=None sizes the rows by n_reads * max_placements, which always suffices;
+        a smaller capacity raises DeaconHipError(DCN_ERR_CAPACITY) when the batch has more."""
+        bases, offsets, n_reads = _batch(bases, offsets)
+        cap = n_reads * int(max_placements) if capacity is None else int(capacity)
+        place_offsets = np.zeros(n_reads + 1, np.uint64)
+        out = np.zeros(max(cap, 1), SPLIT_PLACEMENT_DTYPE)
+        counts = np.zeros((max(n_reads, 1), 2), np.uint32)
+        p = N.PlaceSplitParams(self.band_bases, self.min_votes, self.prefix_length, int(max_placements), (C.c_uint32 * 3)(0, 0, 0))
+        N.check(N.lib().dcn_place_split_batch(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None, _ptr(offsets),
+                                              n_reads, C.byref(p), _ptr(place_offsets), _ptr(out) if cap else None, cap,
+                                              _ptr(counts)))
+        return place_offsets, out[:int(place_offsets[n_reads])], counts[:n_reads]
+
+    def place_split(self, reads, max_placements=4):
+        """-> per read the SPLIT_PLACEMENT_DTYPE rows it owns (none for an unplaced read)"""
+        reads = list(reads)
+        bases, offsets = concat_reads(reads)
+        po, rows, _ = self.place_split_batch(bases, offsets, max_placements)
+        return [rows[int(po[r]):int(po[r + 1])] for r in range(len(reads))]
 
 
 class FilterProcessor(_Context):

@@ -72,9 +72,10 @@ enum {
  * 1.6 = dcn_index_set_depth_enable / _reset / _stats / _hist / _keys;
  * 1.7 = dcn_index_builder_create / _add / _info / _hist / _counts / _finish / _destroy;
  * 1.8 = dcn_depth_track_batch;
- * 1.9 = dcn_anchor_map_create / _add / _info / _anchors, dcn_place_batch. */
+ * 1.9 = dcn_anchor_map_create / _add / _info / _anchors, dcn_place_batch.
+ * 1.10 = dcn_place_split_batch. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 9
+#define DCN_ABI_MINOR 10
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -621,7 +622,7 @@ int dcn_anchor_map_anchors(const dcn_index *map, uint64_t *keys, uint32_t *recor
  *   7. Otherwise record = UINT32_MAX and every field but n_anchors and n_positions is 0.
  *   8. Nothing depends on thresholds of the filter, on earlier calls, or on how the library cuts the work.  Integers only.
  * n_anchors - votes is the number of anchor hits the placement does not explain (a chimera shows there); no second-best
- * cell is reported.  band_bases = 256 and min_votes = 2 are the conventions of the layers above (the 2 is the filter's
+ * cell is reported (dcn_place_split_batch below reports further placements, a rival and a quality).  band_bases = 256 and min_votes = 2 are the conventions of the layers above (the 2 is the filter's
  * -a 2), not measured optima. */
 typedef struct dcn_place_params {
     uint32_t band_bases;    /* W >= 1: width of a diagonal band */
@@ -650,6 +651,68 @@ typedef struct dcn_placement {
  * probe sweep that marks positions and stores the anchor of each anchor hit, FINISH = the vote. */
 int dcn_place_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets,
                     uint32_t n_reads, const void *params, void *placements);
+
+/* ---- split placements: several per read, each with its rival and a quality (ABI 1.10) -------------------------------
+ * THE DEFINITION OF A SPLIT PLACEMENT.  Steps 1-4 are those of THE DEFINITION OF A PLACEMENT (positions, anchor hits,
+ * orientation, diagonal D, the two cells D / W and D / W + 1 of a hit).  With N = max_placements:
+ *   1. ROUNDS.  H_0 = the read's anchor hits.  In round t = 0, 1, ...: cells are counted over H_t only; C_t is the best
+ *      cell by rule 5 above (most votes, ties to the smallest (R, o, j), '+' before '-') and v_t its votes; H_{t+1} is
+ *      H_t without the hits of C_t, those with its (R, o) and D / W in {j - 1, j}.  Rounds end when H_t is empty or after
+ *      round t = N; that last round is computed and never reported.  v_t never rises: a cell's count over H_{t+1}, a
+ *      subset of H_t, is at most its count over H_t, which is at most v_t.
+ *   2. REPORTED are the rounds t < N with v_t >= min_votes (a prefix of the rounds, by the above).  Each carries record,
+ *      reverse, votes, read_start/_end and ref_start/_end exactly as rule 6 defines them, over the hits of C_t in H_t;
+ *      rank = t; n_placed = how many the read has; and the read's n_anchors and n_positions.
+ *   3. RIVAL.  The read interval of a computed round, reported or not, is [min q, max q + k) over its cell's hits.  Two
+ *      intervals intersect when max(starts) < min(ends): touching is not intersecting.  rival_votes of placement t is
+ *      the largest v_u over all computed rounds u != t whose interval intersects t's; 0 when there is none.
+ *   4. QUALITY.  mapq = 0 when rival_votes >= votes, else 60 * (votes - rival_votes) / votes by integer division: 0 .. 60.
+ *      It is a convention, like band_bases = 256 and min_votes = 2, and NOT a calibrated probability.
+ *   5. Integers only.  Nothing depends on tiles, on which kernel places a read, on partitions of the count, or on how
+ *      a batch is cut.  Round 0 is dcn_place_batch's placement: max_placements = 1 reports that placement and its rival.
+ * Two parts of a chimera that do not overlap on the read each get mapq 60; a weaker cell on the same stretch of the read
+ * as a stronger one gets 0. */
+#define DCN_PLACE_SPLIT_MAX 8
+typedef struct dcn_place_split_params {
+    uint32_t band_bases, min_votes; /* as dcn_place_params */
+    uint64_t prefix_length;
+    uint32_t max_placements;        /* 1 .. DCN_PLACE_SPLIT_MAX */
+    uint32_t reserved[3];           /* must be 0 */
+} dcn_place_split_params; /* 32 bytes */
+typedef struct dcn_split_placement {
+    /* the 48 bytes of dcn_placement, field for field */
+    uint32_t record;
+    uint32_t reverse;
+    uint32_t votes, n_anchors, n_positions;
+    uint32_t read_start, read_end;
+    uint32_t reserved; /* 0 */
+    uint64_t ref_start, ref_end;
+    /* then */
+    uint32_t rank, n_placed, rival_votes, mapq;
+} dcn_split_placement; /* 64 bytes */
+
+/*   map            as for dcn_place_batch
+ *   params         a dcn_place_split_params
+ *   place_offsets  n_reads + 1 entries: read r owns placements[place_offsets[r] .. place_offsets[r + 1]), ranks
+ *                  ascending; an unplaced read owns nothing
+ *   placements     capacity entries of dcn_split_placement
+ *   read_counts    NULL, or 2 * n_reads entries: n_anchors and n_positions of every read, unplaced ones included; filled
+ *                  whenever place_offsets is
+ * (params and placements are declared void * for the reason given at dcn_locate_batch.)  DCN_ERR_CAPACITY follows the
+ * contract stated at dcn_locate_batch: the offsets are complete, the total is place_offsets[n_reads], no placement is
+ * written, and NULL with capacity 0 asks for the count.  Host pointers, blocking, batch limits as for
+ * dcn_classify_batch; refused while batches are in flight; the six counters of the context are left unchanged.
+ * DCN_ERR_ARG, before any device work: NULLs, reserved != 0, band_bases == 0, min_votes == 0, max_placements 0 or above
+ * DCN_PLACE_SPLIT_MAX, an index that is not a map.  Device memory, allocated on the first call and freed with the
+ * context: what dcn_place_batch states per base (shared with it, all but its 48 bytes per read of placements), one more
+ * max_batch_bases / 8 bytes for the copy of the anchor bitmap that the rounds clear, and per read 28 bytes of counts
+ * and offsets, for the max_batch_reads of the context, plus 32 * (max_placements + 1) bytes of rounds and
+ * 64 * max_placements bytes of rows, for the largest batch so far (444 bytes per read at max_placements = 4).
+ * dcn_ctx_set_profiling covers it: pack, plan, scan (minimizer dump), DISTINCT = the mark sweep of dcn_place_batch,
+ * FINISH = the vote and the compaction into rows. */
+int dcn_place_split_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets,
+                          uint32_t n_reads, const void *params, uint64_t *place_offsets, void *placements,
+                          uint64_t capacity, uint32_t *read_counts);
 
 /* ---- counters: ProcessingStats (src/local_filter.rs:179-187, merged at :388-396) -------------------------- */
 
