@@ -118,6 +118,29 @@ class SplitPlacement(C.Structure):
 PLACE_SPLIT_MAX = 8  # DCN_PLACE_SPLIT_MAX
 
 
+class PlacePairParams(C.Structure):
+    _fields_ = [
+        ("band_bases", C.c_uint32),
+        ("min_votes", C.c_uint32),
+        ("prefix_length", C.c_uint64),
+        ("max_placements", C.c_uint32),
+        ("max_insert", C.c_uint32),
+        ("hist_bin_bases", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+
+class PairPlacement(C.Structure):
+    _fields_ = SplitPlacement._fields_ + [
+        ("flags", C.c_uint32),
+        ("pair_votes", C.c_uint32),
+        ("tlen", C.c_int64),
+    ]
+
+
+PAIR_HIST_BINS = 256  # DCN_PAIR_HIST_BINS
+
+
 def build(force=False, jobs=6):
     """Compile every HIP source for gfx950 into lib/libdeacon_hip.so (hipcc cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -223,10 +246,11 @@ _SIGNATURES = {
     "dcn_anchor_map_anchors": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _u64p]),
     "dcn_place_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp]),
     "dcn_place_split_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "dcn_place_pair_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
 }
 
 _lib = None
-ABI = (1, 10)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 11)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

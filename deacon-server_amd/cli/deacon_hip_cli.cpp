@@ -3891,6 +3891,130 @@ int run_map(const MapArgs &a) {
     return 0;
 }
 
+// ---- map-pairs: the two mates of a pair placed jointly, as PAF with pair tags -------------------------------------------
+struct MapPairsArgs {
+    std::string ref, input, input2, index, output = "-", summary, insert_hist;
+    bool has_input = false, has_input2 = false, has_index = false, has_summary = false, has_insert_hist = false, quiet = false;
+    unsigned k = 31, w = 15, band = 256, min_votes = 2, max_placements = 4, max_insert = 1000, insert_bin = 8;
+    size_t prefix_length = 0;
+};
+
+int run_map_pairs(const MapPairsArgs &a) {
+    const Stopwatch watch;
+    if (a.ref.empty()) die("the following required arguments were not provided: <REF>");
+    if (!a.has_input) die("the following required arguments were not provided: <READS1>");
+    AnchorRef R;
+    load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, "DCN_CLI_MAPPAIRS_BATCH_BASES", a.quiet);
+    Context &ctx = *R.ctx;
+    dcn_place_pair_params prm = {};
+    prm.band_bases = a.band;
+    prm.min_votes = a.min_votes;
+    prm.prefix_length = a.prefix_length;
+    prm.max_placements = a.max_placements;
+    prm.max_insert = a.max_insert;
+    prm.hist_bin_bases = a.insert_bin;
+    TextOut out(a.output, true);
+    FastxReader r1(a.input);
+    std::unique_ptr<FastxReader> r2;
+    if (a.has_input2) r2.reset(new FastxReader(a.input2));
+    uint64_t pairs = 0, placed = 0, proper = 0, rescued = 0, both_not_proper = 0, one_placed = 0, neither = 0, mapq60 = 0, mapq0 = 0;
+    std::vector<uint64_t> per_record(R.n_records, 0), hist(DCN_PAIR_HIST_BINS, 0), batch_hist(DCN_PAIR_HIST_BINS, 0);
+    Batch b;
+    std::vector<dcn_pair_placement> pl;
+    std::string rows;
+    auto next = [&](Batch &into) {  // one pair: two records, from the two inputs in step or from the one, interleaved
+        if (!r1.next(into)) {
+            if (r2 && r2->next(into)) die("the second input has more records than the first");
+            return false;
+        }
+        if (r2) {
+            if (!r2->next(into)) die("the first input has more records than the second");
+        } else if (!r1.next(into)) die("Paired input ended with an unpaired record");
+        return true;
+    };
+    for_each_batch(next, b, R.batch_bases, R.batch_reads, [&] {
+        const uint32_t n_reads = (uint32_t)b.recs.size();  // (even: a pair is never cut)
+        ctx.fit(b.offsets.back());
+        pl.resize(n_reads);
+        deacon::check(dcn_place_pair_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &prm, pl.data(), batch_hist.data()));
+        for (size_t i = 0; i < hist.size(); ++i) hist[i] += batch_hist[i];  // (the call overwrites its histogram)
+        rows.clear();
+        for (uint32_t u = 0; u < n_reads / 2; ++u) {
+            const dcn_pair_placement &p1 = pl[2 * u], &p2 = pl[2 * u + 1];
+            const bool is1 = p1.record != UINT32_MAX, is2 = p2.record != UINT32_MAX;
+            ++pairs;
+            if (p1.flags & DCN_PAIR_PROPER) ++proper;
+            else if (is1 && is2) ++both_not_proper;
+            else if (is1 || is2) ++one_placed;
+            else ++neither;
+            for (uint32_t m = 0; m < 2; ++m) {
+                const dcn_pair_placement &p = pl[2 * u + m];
+                if (p.record == UINT32_MAX) continue;
+                const Rec &rec = b.recs[2 * u + m];
+                ++placed, ++per_record[p.record];
+                rescued += (p.flags & DCN_PAIR_RESCUED) != 0;
+                mapq60 += p.mapq == 60, mapq0 += p.mapq == 0;
+                dcn_split_placement sp;  // (the first 64 bytes of a pair row, field for field)
+                std::memcpy(&sp, &p, sizeof sp);
+                append_paf(rows, std::string(id_token(b, rec)), rec.seq_len, sp, R.names[p.record], R.lens[p.record], R.k);
+                rows.pop_back();
+                rows += "\tmt:i:" + std::to_string(m + 1) + "\tpr:i:" + std::to_string(p.flags & DCN_PAIR_PROPER ? 1 : 0) + "\trs:i:" +
+                        std::to_string(p.flags & DCN_PAIR_RESCUED ? 1 : 0) + "\tpv:i:" + std::to_string(p.pair_votes) + "\ttl:i:" +
+                        std::to_string((long long)p.tlen) + '\n';
+            }
+        }
+        out.write(rows);
+    });
+    out.finish();
+    // the bin that holds the median proper pair: the first at which the running count reaches half of them
+    long long median_bin = -1;
+    for (uint64_t i = 0, run = 0; i < hist.size() && proper > 0; ++i) {
+        run += hist[i];
+        if (run * 2 >= proper) {
+            median_bin = (long long)i;
+            break;
+        }
+    }
+    if (a.has_insert_hist) {
+        std::string tsv = "bin_start\tbin_end\tpairs\n";
+        for (uint64_t i = 0; i < hist.size(); ++i) {
+            if (!hist[i]) continue;
+            tsv += std::to_string(i * a.insert_bin) + '\t' + (i + 1 == hist.size() ? std::string("inf") : std::to_string((i + 1) * a.insert_bin)) +
+                   '\t' + std::to_string(hist[i]) + '\n';
+        }
+        write_text_file(a.insert_hist, tsv);
+    }
+    const double secs = watch.seconds();
+    if (!a.quiet)
+        std::fprintf(stderr, "Mapped %llu pairs: %llu proper (%llu mates rescued), %llu with both mates placed apart, %llu with one, %llu with none in %s\n",
+                     (unsigned long long)pairs, (unsigned long long)proper, (unsigned long long)rescued, (unsigned long long)both_not_proper,
+                     (unsigned long long)one_placed, (unsigned long long)neither, fmt_duration(secs).c_str());
+    if (a.has_summary) {
+        std::string js = summary_head() + ",\n  \"reference\": " + json_str(a.ref) + ",\n  \"input\": " + json_str(a.input);
+        if (a.has_input2) js += ",\n  \"input2\": " + json_str(a.input2);
+        appendf(js, ",\n  \"k\": %u,\n  \"w\": %u,\n  \"band_bases\": %u,\n  \"min_votes\": %u,\n  \"prefix_length\": %zu,\n"
+                    "  \"records\": %u,\n  \"keys\": %llu,\n  \"anchors\": %llu,\n  \"repeats\": %llu,\n"
+                    "  \"reads\": %llu,\n  \"placed\": %llu,\n  \"max_placements\": %u,\n  \"max_insert\": %u,\n  \"pairs\": %llu,\n"
+                    "  \"proper\": %llu,\n  \"rescued_mates\": %llu,\n  \"both_placed_not_proper\": %llu,\n  \"one_mate_placed\": %llu,\n"
+                    "  \"neither_placed\": %llu,\n  \"mapq60\": %llu,\n  \"mapq0\": %llu,\n  \"insert_median_bin_start\": ",
+                (unsigned)R.k, (unsigned)R.w, a.band, a.min_votes, a.prefix_length, R.m_records, (unsigned long long)R.m_keys,
+                (unsigned long long)R.m_anchors, (unsigned long long)R.m_repeats, (unsigned long long)(2 * pairs),
+                (unsigned long long)placed, a.max_placements, a.max_insert, (unsigned long long)pairs, (unsigned long long)proper,
+                (unsigned long long)rescued, (unsigned long long)both_not_proper, (unsigned long long)one_placed,
+                (unsigned long long)neither, (unsigned long long)mapq60, (unsigned long long)mapq0);
+        js += median_bin < 0 ? std::string("null") : std::to_string((unsigned long long)median_bin * a.insert_bin);
+        appendf(js, ",\n  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
+        for (uint32_t r = 0; r < R.n_records; ++r) {
+            js += (r ? ",\n    {" : "\n    {");
+            js += "\"name\": " + json_str(R.names[r]);
+            appendf(js, ", \"length\": %u, \"placements\": %llu}", R.lens[r], (unsigned long long)per_record[r]);
+        }
+        js += "\n  ]\n}\n";
+        write_text_file(a.summary, js);
+    }
+    return 0;
+}
+
 void usage() {
     std::fprintf(stderr,
                  "Usage: deacon-hip <COMMAND>\n\nCommands:\n  index   Build and compose minimizer indexes (build, info, union, diff, intersect, compare, select)\n"
@@ -3899,6 +4023,7 @@ void usage() {
                  "  mask    Report where in each record an index matched, and mask those stretches\n"
                  "  place   Report which record of a reference each read came from, where, and on which strand\n"
                  "  map     Report up to N placements per read on a reference, each with a mapping quality, as PAF\n"
+                 "  map-pairs  Place the two mates of each pair jointly: proper pairs, rescued mates, insert sizes, as PAF\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -4060,6 +4185,43 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "The mapping quality is 60 * (votes - rival votes) / votes, where the rival is the strongest other cell on the\n"
                "same stretch of the read (0 when it is as strong): a convention, not a calibrated probability.\n"
                "Mates are independent here: one input.\n";
+    else if (sub == "map-pairs")
+        text = "Place the two mates of each pair jointly on a reference: proper pairs, rescued mates and insert sizes, as PAF\n\n"
+               "Usage: deacon-hip map-pairs [OPTIONS] <REF> <READS1> [READS2]\n\n"
+               "Arguments:\n"
+               "  <REF>     Path to the reference fastx file: its records are numbered and named in file order\n"
+               "  <READS1>  Path to fastx file of mate 1, or without [READS2] of interleaved mates (or - for stdin; gz, bgzf, zst,\n"
+               "            xz and bz2 found by content)\n"
+               "  [READS2]  Optional path to fastx file of mate 2, read in step with <READS1>\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Keys that may anchor: a minimizer index file, whose k and w are used\n"
+               "                                 [default: the minimizers of <REF> at -k / -w]\n"
+               "  -k <K>                         K-mer length without -x [default: 31]\n"
+               "  -w <W>                         Minimizer window size without -x [default: 15]\n"
+               "  -o, --output <OUTPUT>          PAF, one line per placed mate, pairs in input order, mate 1 before mate 2, no\n"
+               "                                 line for an unplaced mate (- for stdout) [default: -].  Columns 1-12 and the\n"
+               "                                 tags cm rk np rv na ns as in map; then mt mate (1 | 2), pr proper pair (0 | 1),\n"
+               "                                 rs rescued (0 | 1), pv paired votes, tl template length (signed; 0: not proper)\n"
+               "  -N, --max-placements <N>       Candidate placements per mate, each from the anchor hits no earlier one\n"
+               "                                 explained (1..8) [default: 4]\n"
+               "  -I, --max-insert <N>           Longest template of a proper pair in bases [default: 1000, a convention]\n"
+               "      --insert-hist <FILE>       TSV of bin_start, bin_end, pairs: the proper pairs by template length, non-empty\n"
+               "                                 bins only; the last of the 256 bins is open-ended (bin_end inf)\n"
+               "      --insert-bin <N>           Bases per bin of the insert histogram [default: 8, a convention]\n"
+               "      --band <N>                 Width of a diagonal band in bases [default: 256, a convention]\n"
+               "  -a, --min-votes <N>            Minimum number of anchor hits for a mate to stand on its own [default: 2, as\n"
+               "                                 filter's -a, a convention]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per read (0 = entire read) [default: 0]\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
+               "  -h, --help                     Print help\n\n"
+               "A key that occurs at exactly one place of <REF> is an anchor; keys that occur at several never vote.\n"
+               "Concordant: a placement of each mate on one record, on opposite strands, the forward one beginning before the reverse one ends, the template at most -I bases, one of the two with -a votes.\n"
+               "Proper: the concordant combination with the most votes is reported (ties: mate 1's lower rank, then mate 2's) and a mate of it below -a votes is rescued; without one each mate is mapped as map -N 1 maps it.\n"
+               "Paired votes of a placement: its votes plus the most votes of a placement of the other mate that is concordant with it.\n"
+               "Quality: 60 * (paired votes - rival) / paired votes, the rival being the most paired votes of another cell on the same stretch of the read (0 when it is as strong).\n"
+               "The quality and -I are conventions, not a calibrated probability and not a measured optimum.\n";
     else if (sub == "index build")
         text = "Index minimizers contained within a fastx file\n\n"
                "Usage: deacon-hip index build [OPTIONS] <INPUT>\n\n"
@@ -4343,6 +4505,41 @@ int main(int argc, char **argv) {
             if (pos.size() > 1) a.input = pos[1];
             if (pos.size() > 2) die("map takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[2] + "')");
             return run_map(a);
+        }
+        if (args[0] == "map-pairs") {
+            MapPairsArgs a;
+            std::vector<std::string> pos;
+            auto number = [&](const std::string &v, const char *flag, long long lo, long long hi) {
+                char *end = nullptr;
+                const long long x = std::strtoll(v.c_str(), &end, 10);
+                if (v.empty() || *end || x < lo || x > hi)
+                    die(std::string("invalid value for ") + flag + ": must be " + std::to_string(lo) + ".." + std::to_string(hi));
+                return x;
+            };
+            for (size_t i = 1; i < args.size(); ++i) {
+                const std::string &s = args[i];
+                if (s == "-x" || s == "--index") a.index = need(++i), a.has_index = true;
+                else if (s == "-k") a.k = (unsigned)number(need(++i), "-k", 1, 56);
+                else if (s == "-w") a.w = (unsigned)number(need(++i), "-w", 1, 255);
+                else if (s == "-o" || s == "--output") a.output = need(++i);
+                else if (s == "-N" || s == "--max-placements") a.max_placements = (unsigned)number(need(++i), "-N", 1, DCN_PLACE_SPLIT_MAX);
+                else if (s == "-I" || s == "--max-insert") a.max_insert = (unsigned)number(need(++i), "--max-insert", 1, 0xFFFFFFFFll);
+                else if (s == "--insert-hist") a.insert_hist = need(++i), a.has_insert_hist = true;
+                else if (s == "--insert-bin") a.insert_bin = (unsigned)number(need(++i), "--insert-bin", 1, 0xFFFFFFFFll);
+                else if (s == "--band") a.band = (unsigned)number(need(++i), "--band", 1, 0xFFFFFFFFll);
+                else if (s == "-a" || s == "--min-votes") a.min_votes = (unsigned)number(need(++i), "--min-votes", 1, 0xFFFFFFFFll);
+                else if (s == "-p" || s == "--prefix-length") a.prefix_length = (size_t)number(need(++i), "--prefix-length", 0, 0x7FFFFFFFFFFFFFFFll);
+                else if (s == "-s" || s == "--summary") a.summary = need(++i), a.has_summary = true;
+                else if (s == "-t" || s == "--threads") ++i;
+                else if (s == "-q" || s == "--quiet") a.quiet = true;
+                else if (s.size() > 1 && s[0] == '-' && s != "-") die("unexpected argument '" + s + "'");
+                else pos.push_back(s);
+            }
+            if (pos.size() > 0) a.ref = pos[0];
+            if (pos.size() > 1) a.input = pos[1], a.has_input = true;
+            if (pos.size() > 2) a.input2 = pos[2], a.has_input2 = true;
+            if (pos.size() > 3) die("unexpected argument '" + pos[3] + "'");
+            return run_map_pairs(a);
         }
         if (args[0] == "cat" && args.size() >= 2) {  // hidden: the input side alone (format found by content, decoded to stdout; no GPU)
             Input in(args[1]);

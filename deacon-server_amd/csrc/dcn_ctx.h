@@ -169,6 +169,9 @@ struct dcn_ctx {
     dcn_split_round *d_pls_rounds = nullptr;
     dcn_split_placement *d_pls_out = nullptr;
     uint64_t pls_round_cap = 0, pls_out_cap = 0;
+    // paired placement buffers (lazy, first dcn_place_pair_batch): one row per read and the insert histogram
+    dcn_pair_placement *d_ppr_out = nullptr;
+    unsigned long long *d_ppr_hist = nullptr;
     // deferred state of the last enqueued device-API batch
     bool batch_pending = false;
     bool lean = false; // a small host batch is being submitted: copies and result copies go on `stream` itself (submit_impl)

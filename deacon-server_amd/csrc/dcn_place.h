@@ -1,5 +1,5 @@
-// dcn_place.h -- anchor maps and placement: the kernels behind dcn_anchor_map_*, dcn_place_batch (place.hip) and
-// dcn_place_split_batch (place_split.hip); not part of the public ABI.
+// dcn_place.h -- anchor maps and placement: the kernels behind dcn_anchor_map_*, dcn_place_batch (place.hip),
+// dcn_place_split_batch (place_split.hip) and dcn_place_pair_batch (place_pair.hip); not part of the public ABI.
 #pragma once
 
 #include "dcn_dump_sweep.h"
@@ -142,6 +142,26 @@ struct dcn_place_split_args {
 constexpr uint32_t DCN_PLS_SCAN_ITEMS = 8;
 constexpr uint32_t DCN_PLS_SCAN_BLOCK = DCN_PLC_THREADS * DCN_PLS_SCAN_ITEMS;
 
-// rounds per read (lane and workgroup form, the switch and the work list of dcn_launch_place_vote) -> counts ->
-// place_offsets (exclusive scan, place_offsets[n_reads] = the total) -> out; *p.n_big is zero before
+// rounds per read (lane and workgroup form, the switch and the work list of dcn_launch_place_vote) -> rounds, n_rounds,
+// counts, read_counts; *p.n_big is zero before
+int dcn_launch_place_split_rounds(const dcn_place_split_args &s, hipStream_t stream);
+// the CSR tail: counts -> place_offsets (exclusive scan, place_offsets[n_reads] = the total) -> out
+int dcn_launch_place_split_rows(const dcn_place_split_args &s, hipStream_t stream);
+// both, in that order on the one stream
 int dcn_launch_place_split_vote(const dcn_place_split_args &s, hipStream_t stream);
+
+// ---- paired placements (dcn_place_pair_batch, place_pair.hip) ------------------------------------------------------
+// A consumer of the rounds beside place_split_write_kernel: one lane per pair reads the two mates' computed rounds
+// (reads 2u and 2u + 1) where the round launcher left them and writes both rows of "THE DEFINITION OF A PAIRED
+// PLACEMENT".
+struct dcn_place_pair_args {
+    const dcn_split_round *rounds; // n_reads * (max_placements + 1)
+    const uint32_t *n_rounds;      // per read: computed rounds
+    const uint32_t *read_counts;   // per read: n_anchors, n_positions
+    const uint32_t *counts;        // per read: n_placed of the split call
+    uint32_t n_pairs;
+    uint32_t max_placements, k, min_votes, max_insert, hist_bin_bases;
+    dcn_pair_placement *out;       // 2 * n_pairs
+    unsigned long long *hist;      // DCN_PAIR_HIST_BINS counters, zero before; NULL: no histogram
+};
+int dcn_launch_place_pair(const dcn_place_pair_args &a, hipStream_t stream);

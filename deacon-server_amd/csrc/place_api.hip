@@ -1,5 +1,6 @@
-// place_api.hip -- the C ABI of anchor maps (dcn_anchor_map_*), dcn_place_batch and dcn_place_split_batch (kernels in
-// place.hip and place_split.hip; the batch calls run the dump front end of ctx.hip on a filter context).
+// place_api.hip -- the C ABI of anchor maps (dcn_anchor_map_*), dcn_place_batch, dcn_place_split_batch and
+// dcn_place_pair_batch (kernels in place.hip, place_split.hip and place_pair.hip; the batch calls run the dump front
+// end of ctx.hip on a filter context).
 #include "dcn_ctx.h"
 #include "dcn_place.h"
 
@@ -11,6 +12,7 @@ using namespace dcn_impl;
 static_assert(sizeof(dcn_place_params) == 24 && sizeof(dcn_placement) == 48, "place structs are ABI");
 static_assert(sizeof(dcn_place_split_params) == 32 && sizeof(dcn_split_placement) == 64 && sizeof(dcn_split_round) == 32,
               "split place structs are ABI");
+static_assert(sizeof(dcn_place_pair_params) == 40 && sizeof(dcn_pair_placement) == 80, "pair place structs are ABI");
 
 namespace {
 int check_map(const dcn_index *map) {
@@ -210,6 +212,69 @@ int grow(T **buf, uint64_t *cap, uint64_t need, const char *what) {
     *cap = need;
     return DCN_OK;
 }
+
+// What dcn_place_split_batch and dcn_place_pair_batch do before the rounds: the buffers of the context (`rows`: those of
+// the CSR tail too), the staged batch, the dump front end, the mark sweep (DISTINCT ends behind it) and the copy of the
+// anchor bitmap that the rounds clear.  `sa` is ready for dcn_launch_place_split_rounds / _rows.
+int split_prepare(dcn_ctx *c, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                  uint64_t n_bases, uint32_t band_bases, uint32_t min_votes, uint64_t prefix_length, uint32_t N, bool rows,
+                  int *prof_slot_out, dcn_place_split_args *sa_out) {
+    DCN_HIP(hipSetDevice(c->device));
+    DCN_TRY(ensure_dump_buffers(c));
+    DCN_TRY(ensure_position_bitmap(c));
+    const uint64_t bitmap_words = (c->max_bases + 31) / 32 + 1;
+    if (!c->d_plc_abits) DCN_TRY(dev_alloc(&c->d_plc_abits, bitmap_words, "anchor bitmap"));
+    if (!c->d_plc_words) DCN_TRY(dev_alloc(&c->d_plc_words, c->max_bases + 2, "placement words"));
+    if (!c->d_plc_big) DCN_TRY(dev_alloc(&c->d_plc_big, c->max_reads, "placement work list"));
+    if (!c->d_plc_n_big) DCN_TRY(dev_alloc(&c->d_plc_n_big, 1, "placement work list length"));
+    if (!c->d_pls_rbits) DCN_TRY(dev_alloc(&c->d_pls_rbits, bitmap_words, "remaining anchor bitmap"));
+    if (!c->d_pls_n_rounds) DCN_TRY(dev_alloc(&c->d_pls_n_rounds, c->max_reads, "placement round counts"));
+    if (!c->d_pls_read_counts) DCN_TRY(dev_alloc(&c->d_pls_read_counts, (uint64_t)c->max_reads * 2, "placement read counts"));
+    if (!c->d_pls_counts) DCN_TRY(dev_alloc(&c->d_pls_counts, c->max_reads, "placement counts"));
+    if (rows) {
+        if (!c->d_pls_block_sums)
+            DCN_TRY(dev_alloc(&c->d_pls_block_sums, (uint64_t)c->max_reads / DCN_PLS_SCAN_BLOCK + 1, "placement block sums"));
+        if (!c->d_pls_offsets) DCN_TRY(dev_alloc(&c->d_pls_offsets, (uint64_t)c->max_reads + 1, "placement offsets"));
+    }
+    DCN_TRY(grow(&c->d_pls_rounds, &c->pls_round_cap, (uint64_t)n_reads * (N + 1), "placement rounds"));
+    if (rows) DCN_TRY(grow(&c->d_pls_out, &c->pls_out_cap, (uint64_t)n_reads * N, "split placements"));
+    DCN_TRY(stage_batch(c, bases, n_bases, offsets, n_reads, nullptr));
+    hipStream_t st = c->stream;
+    const uint64_t batch_words = (n_bases + 31) / 32 + 1;
+    DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
+    DCN_HIP(hipMemsetAsync(c->d_loc_bits, 0, batch_words * sizeof(uint32_t), st));
+    DCN_HIP(hipMemsetAsync(c->d_plc_abits, 0, batch_words * sizeof(uint32_t), st));
+    DCN_HIP(hipMemsetAsync(c->d_plc_n_big, 0, sizeof(uint32_t), st));
+    int prof_slot = -1;
+    dcn_place_split_args &sa = *sa_out;
+    memset(&sa, 0, sizeof(sa));
+    dcn_place_args &pa = sa.p;
+    DCN_TRY(front_end(c, map, n_reads, n_bases, prefix_length, &prof_slot, &pa));
+    *prof_slot_out = prof_slot;
+    pa.band = band_bases;
+    pa.min_votes = min_votes;
+    pa.lane_bases = env_u32("DCN_PLACE_LANE_BASES", DCN_PLC_LANE_BASES, 0, 0xFFFFFFFFu);
+    pa.lds_cells = env_u32("DCN_PLACE_LDS_CELLS", DCN_PLC_LDS_CELLS, DCN_PLC_LDS_CELLS_MIN, DCN_PLC_LDS_CELLS);
+    for (uint32_t r = 0; r < n_reads && !pa.any_big; ++r) pa.any_big = offsets[r + 1] - offsets[r] > pa.lane_bases ? 1u : 0u;
+    pa.bits = c->d_loc_bits;
+    pa.abits = c->d_plc_abits;
+    pa.words = c->d_plc_words;
+    pa.big = c->d_plc_big;
+    pa.n_big = c->d_plc_n_big;
+    sa.rbits = c->d_pls_rbits;
+    sa.max_placements = N;
+    sa.rounds = c->d_pls_rounds;
+    sa.n_rounds = c->d_pls_n_rounds;
+    sa.read_counts = c->d_pls_read_counts;
+    sa.counts = c->d_pls_counts;
+    sa.block_sums = c->d_pls_block_sums;
+    sa.place_offsets = c->d_pls_offsets;
+    sa.out = c->d_pls_out;
+    DCN_TRY(dcn_launch_place_mark(pa, st));
+    DCN_PROF_MARK(DCN_STAGE_DISTINCT);
+    DCN_HIP(hipMemcpyAsync(c->d_pls_rbits, c->d_plc_abits, batch_words * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    return DCN_OK;
+}
 } // namespace
 
 extern "C" int dcn_place_split_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets,
@@ -236,58 +301,11 @@ extern "C" int dcn_place_split_batch(dcn_ctx *ctx, const dcn_index *map, const u
     const uint64_t n_bases = offsets[n_reads];
     if (n_bases > 0 && !bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
     dcn_ctx *c = ctx;
-    const uint32_t N = prm->max_placements;
-    DCN_HIP(hipSetDevice(c->device));
-    DCN_TRY(ensure_dump_buffers(c));
-    DCN_TRY(ensure_position_bitmap(c));
-    const uint64_t bitmap_words = (c->max_bases + 31) / 32 + 1;
-    if (!c->d_plc_abits) DCN_TRY(dev_alloc(&c->d_plc_abits, bitmap_words, "anchor bitmap"));
-    if (!c->d_plc_words) DCN_TRY(dev_alloc(&c->d_plc_words, c->max_bases + 2, "placement words"));
-    if (!c->d_plc_big) DCN_TRY(dev_alloc(&c->d_plc_big, c->max_reads, "placement work list"));
-    if (!c->d_plc_n_big) DCN_TRY(dev_alloc(&c->d_plc_n_big, 1, "placement work list length"));
-    if (!c->d_pls_rbits) DCN_TRY(dev_alloc(&c->d_pls_rbits, bitmap_words, "remaining anchor bitmap"));
-    if (!c->d_pls_n_rounds) DCN_TRY(dev_alloc(&c->d_pls_n_rounds, c->max_reads, "placement round counts"));
-    if (!c->d_pls_read_counts) DCN_TRY(dev_alloc(&c->d_pls_read_counts, (uint64_t)c->max_reads * 2, "placement read counts"));
-    if (!c->d_pls_counts) DCN_TRY(dev_alloc(&c->d_pls_counts, c->max_reads, "placement counts"));
-    if (!c->d_pls_block_sums)
-        DCN_TRY(dev_alloc(&c->d_pls_block_sums, (uint64_t)c->max_reads / DCN_PLS_SCAN_BLOCK + 1, "placement block sums"));
-    if (!c->d_pls_offsets) DCN_TRY(dev_alloc(&c->d_pls_offsets, (uint64_t)c->max_reads + 1, "placement offsets"));
-    DCN_TRY(grow(&c->d_pls_rounds, &c->pls_round_cap, (uint64_t)n_reads * (N + 1), "placement rounds"));
-    DCN_TRY(grow(&c->d_pls_out, &c->pls_out_cap, (uint64_t)n_reads * N, "split placements"));
-    DCN_TRY(stage_batch(c, bases, n_bases, offsets, n_reads, nullptr));
-    hipStream_t st = c->stream;
-    const uint64_t batch_words = (n_bases + 31) / 32 + 1;
-    DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
-    DCN_HIP(hipMemsetAsync(c->d_loc_bits, 0, batch_words * sizeof(uint32_t), st));
-    DCN_HIP(hipMemsetAsync(c->d_plc_abits, 0, batch_words * sizeof(uint32_t), st));
-    DCN_HIP(hipMemsetAsync(c->d_plc_n_big, 0, sizeof(uint32_t), st));
     int prof_slot = -1;
     dcn_place_split_args sa;
-    memset(&sa, 0, sizeof(sa));
-    dcn_place_args &pa = sa.p;
-    DCN_TRY(front_end(c, map, n_reads, n_bases, prm->prefix_length, &prof_slot, &pa));
-    pa.band = prm->band_bases;
-    pa.min_votes = prm->min_votes;
-    pa.lane_bases = env_u32("DCN_PLACE_LANE_BASES", DCN_PLC_LANE_BASES, 0, 0xFFFFFFFFu);
-    pa.lds_cells = env_u32("DCN_PLACE_LDS_CELLS", DCN_PLC_LDS_CELLS, DCN_PLC_LDS_CELLS_MIN, DCN_PLC_LDS_CELLS);
-    for (uint32_t r = 0; r < n_reads && !pa.any_big; ++r) pa.any_big = offsets[r + 1] - offsets[r] > pa.lane_bases ? 1u : 0u;
-    pa.bits = c->d_loc_bits;
-    pa.abits = c->d_plc_abits;
-    pa.words = c->d_plc_words;
-    pa.big = c->d_plc_big;
-    pa.n_big = c->d_plc_n_big;
-    sa.rbits = c->d_pls_rbits;
-    sa.max_placements = N;
-    sa.rounds = c->d_pls_rounds;
-    sa.n_rounds = c->d_pls_n_rounds;
-    sa.read_counts = c->d_pls_read_counts;
-    sa.counts = c->d_pls_counts;
-    sa.block_sums = c->d_pls_block_sums;
-    sa.place_offsets = c->d_pls_offsets;
-    sa.out = c->d_pls_out;
-    DCN_TRY(dcn_launch_place_mark(pa, st));
-    DCN_PROF_MARK(DCN_STAGE_DISTINCT);
-    DCN_HIP(hipMemcpyAsync(c->d_pls_rbits, c->d_plc_abits, batch_words * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    DCN_TRY(split_prepare(c, map, bases, offsets, n_reads, n_bases, prm->band_bases, prm->min_votes, prm->prefix_length,
+                          prm->max_placements, true, &prof_slot, &sa));
+    hipStream_t st = c->stream;
     DCN_TRY(dcn_launch_place_split_vote(sa, st));
     DCN_PROF_MARK(DCN_STAGE_FINISH);
     DCN_TRY(finish_run(c, prof_slot));
@@ -299,5 +317,64 @@ extern "C" int dcn_place_split_batch(dcn_ctx *ctx, const dcn_index *map, const u
         return dcn_fail(DCN_ERR_CAPACITY,
                         "place split: " + std::to_string(total) + " placements, capacity " + std::to_string(capacity));
     if (total) DCN_HIP(hipMemcpy(placements, c->d_pls_out, total * sizeof(dcn_split_placement), hipMemcpyDeviceToHost));
+    return DCN_OK;
+}
+
+extern "C" int dcn_place_pair_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets,
+                                    uint32_t n_reads, const void *params, void *rows, uint64_t *tlen_hist) {
+    const dcn_place_pair_params *prm = static_cast<const dcn_place_pair_params *>(params);
+    // (the parameters first, as in dcn_place_batch)
+    if (!prm) return dcn_fail(DCN_ERR_ARG, "params is NULL");
+    if (prm->reserved[0] != 0 || prm->reserved[1] != 0 || prm->reserved[2] != 0)
+        return dcn_fail(DCN_ERR_ARG, "params.reserved must be 0");
+    if (prm->band_bases == 0) return dcn_fail(DCN_ERR_ARG, "params.band_bases must be at least 1");
+    if (prm->min_votes == 0) return dcn_fail(DCN_ERR_ARG, "params.min_votes must be at least 1");
+    if (prm->max_placements == 0 || prm->max_placements > DCN_PLACE_SPLIT_MAX)
+        return dcn_fail(DCN_ERR_ARG, "params.max_placements must be 1.." + std::to_string(DCN_PLACE_SPLIT_MAX));
+    if (prm->max_insert == 0) return dcn_fail(DCN_ERR_ARG, "params.max_insert must be at least 1");
+    if (prm->hist_bin_bases == 0) return dcn_fail(DCN_ERR_ARG, "params.hist_bin_bases must be at least 1");
+    if (n_reads % 2 != 0) return dcn_fail(DCN_ERR_ARG, "n_reads must be even: reads 2u and 2u + 1 are the mates of pair u");
+    if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
+    DCN_TRY(check_map(map));
+    DCN_TRY(check_ctx_matches(ctx, map, "the map"));
+    if (n_reads == 0) {
+        if (tlen_hist) memset(tlen_hist, 0, DCN_PAIR_HIST_BINS * sizeof(uint64_t));
+        return DCN_OK;
+    }
+    if (!offsets) return dcn_fail(DCN_ERR_ARG, "offsets is NULL");
+    if (!rows) return dcn_fail(DCN_ERR_ARG, "rows is NULL");
+    DCN_TRY(validate_host_batch(ctx, offsets, n_reads));
+    const uint64_t n_bases = offsets[n_reads];
+    if (n_bases > 0 && !bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
+    dcn_ctx *c = ctx;
+    DCN_HIP(hipSetDevice(c->device));
+    if (!c->d_ppr_out) DCN_TRY(dev_alloc(&c->d_ppr_out, c->max_reads, "pair placements"));
+    if (!c->d_ppr_hist) DCN_TRY(dev_alloc(&c->d_ppr_hist, DCN_PAIR_HIST_BINS, "insert histogram"));
+    int prof_slot = -1;
+    dcn_place_split_args sa;
+    DCN_TRY(split_prepare(c, map, bases, offsets, n_reads, n_bases, prm->band_bases, prm->min_votes, prm->prefix_length,
+                          prm->max_placements, false, &prof_slot, &sa));
+    hipStream_t st = c->stream;
+    DCN_TRY(dcn_launch_place_split_rounds(sa, st));
+    dcn_place_pair_args pp;
+    memset(&pp, 0, sizeof(pp));
+    pp.rounds = sa.rounds;
+    pp.n_rounds = sa.n_rounds;
+    pp.read_counts = sa.read_counts;
+    pp.counts = sa.counts;
+    pp.n_pairs = n_reads / 2;
+    pp.max_placements = prm->max_placements;
+    pp.k = map->k;
+    pp.min_votes = prm->min_votes;
+    pp.max_insert = prm->max_insert;
+    pp.hist_bin_bases = prm->hist_bin_bases;
+    pp.out = c->d_ppr_out;
+    pp.hist = tlen_hist ? c->d_ppr_hist : nullptr; // (NULL: the kernel skips its LDS counters)
+    if (tlen_hist) DCN_HIP(hipMemsetAsync(c->d_ppr_hist, 0, DCN_PAIR_HIST_BINS * sizeof(unsigned long long), st));
+    DCN_TRY(dcn_launch_place_pair(pp, st));
+    DCN_PROF_MARK(DCN_STAGE_FINISH);
+    DCN_TRY(finish_run(c, prof_slot));
+    DCN_HIP(hipMemcpy(rows, c->d_ppr_out, (uint64_t)n_reads * sizeof(dcn_pair_placement), hipMemcpyDeviceToHost));
+    if (tlen_hist) DCN_HIP(hipMemcpy(tlen_hist, c->d_ppr_hist, DCN_PAIR_HIST_BINS * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return DCN_OK;
 }

@@ -396,7 +396,8 @@ uint32_t pls_cus() {
 
 } // namespace
 
-int dcn_launch_place_split_vote(const dcn_place_split_args &s, hipStream_t stream) {
+// the rounds (what dcn_place_pair_batch consumes too), then the CSR tail; dcn_launch_place_split_vote is both, in order
+int dcn_launch_place_split_rounds(const dcn_place_split_args &s, hipStream_t stream) {
     const uint32_t n_reads = s.p.n_reads;
     if (n_reads == 0) return DCN_OK;
     const uint32_t blocks = (n_reads + DCN_PLC_THREADS - 1) / DCN_PLC_THREADS;
@@ -407,6 +408,13 @@ int dcn_launch_place_split_vote(const dcn_place_split_args &s, hipStream_t strea
         hipLaunchKernelGGL(place_split_big_kernel, dim3(big_blocks), dim3(DCN_PLC_THREADS), 0, stream, s);
         DCN_HIP(hipGetLastError());
     }
+    return DCN_OK;
+}
+
+int dcn_launch_place_split_rows(const dcn_place_split_args &s, hipStream_t stream) {
+    const uint32_t n_reads = s.p.n_reads;
+    if (n_reads == 0) return DCN_OK;
+    const uint32_t blocks = (n_reads + DCN_PLC_THREADS - 1) / DCN_PLC_THREADS;
     const uint32_t scan_blocks = (n_reads + DCN_PLS_SCAN_BLOCK - 1) / DCN_PLS_SCAN_BLOCK;
     hipLaunchKernelGGL(place_split_scan_sums_kernel, dim3(scan_blocks), dim3(DCN_PLC_THREADS), 0, stream, s);
     hipLaunchKernelGGL(place_split_scan_blocks_kernel, dim3(1), dim3(DCN_PLC_THREADS), 0, stream, s, scan_blocks);
@@ -414,4 +422,9 @@ int dcn_launch_place_split_vote(const dcn_place_split_args &s, hipStream_t strea
     hipLaunchKernelGGL(place_split_write_kernel, dim3(blocks), dim3(DCN_PLC_THREADS), 0, stream, s);
     DCN_HIP(hipGetLastError());
     return DCN_OK;
+}
+
+int dcn_launch_place_split_vote(const dcn_place_split_args &s, hipStream_t stream) {
+    const int rc = dcn_launch_place_split_rounds(s, stream);
+    return rc != DCN_OK ? rc : dcn_launch_place_split_rows(s, stream);
 }

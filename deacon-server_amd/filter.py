@@ -666,6 +666,10 @@ UNPLACED = 0xFFFFFFFF
 # numpy view of dcn_split_placement (64 bytes): the fields of dcn_placement, then rank, n_placed, rival_votes, mapq
 SPLIT_PLACEMENT_DTYPE = np.dtype(PLACEMENT_DTYPE.descr + [("rank", np.uint32), ("n_placed", np.uint32),
                                                           ("rival_votes", np.uint32), ("mapq", np.uint32)])
+# numpy view of dcn_pair_placement (80 bytes): the fields of dcn_split_placement, then flags, pair_votes, tlen
+PAIR_PLACEMENT_DTYPE = np.dtype(SPLIT_PLACEMENT_DTYPE.descr + [("flags", np.uint32), ("pair_votes", np.uint32),
+                                                               ("tlen", np.int64)])
+PAIR_PROPER, PAIR_RESCUED, PAIR_MATE_PLACED = 1, 2, 4  # DCN_PAIR_*: bits of `flags`
 
 
 class AnchorMap(Index):
@@ -739,7 +743,8 @@ class Placer(_Context):
     min_votes = 2 are conventions (the 2 is the filter's -a 2), not measured optima.
     profile(): pack, plan, scan (minimizer dump), the probe sweep that marks positions and stores their anchors in the
     'distinct' slot and the vote in the 'finish' slot.  place_split_batch / place_split report up to max_placements
-    placements per read with rival votes and a quality (dcn_place_split_batch); one Placer serves both kinds of call."""
+    placements per read with rival votes and a quality (dcn_place_split_batch); place_pair_batch / place_pairs place the
+    two mates of a pair jointly (dcn_place_pair_batch); one Placer serves every kind of call alternately."""
 
     def __init__(self, anchor_map, max_batch_bases=1 << 26, max_batch_reads=1 << 20, band_bases=256, min_votes=2,
                  prefix_length=0):
@@ -791,6 +796,32 @@ class Placer(_Context):
         bases, offsets = concat_reads(reads)
         po, rows, _ = self.place_split_batch(bases, offsets, max_placements)
         return [rows[int(po[r]):int(po[r + 1])] for r in range(len(reads))]
+
+    def place_pair_batch(self, bases, offsets, max_placements=4, max_insert=1000, hist_bin_bases=8, want_hist=True):
+        """Reads 2u and 2u + 1 are the mates of pair u, placed jointly (dcn_place_pair_batch; the definition of a paired
+        placement is in include/deacon_hip.h): a combination of one of the first max_placements rounds of each mate is
+        concordant when the two lie on one record on opposite strands, the forward one begins before the reverse one
+        ends and the template is at most max_insert bases; the concordant combination with the most votes makes the
+        pair PROPER, and a mate with a single hit there is RESCUED.  Rival votes and mapq count the partner's votes in
+        (a convention, not a calibrated probability; max_insert = 1000 and hist_bin_bases = 8 are conventions too).
+        -> (PAIR_PLACEMENT_DTYPE[n_reads], one row per read with record == UNPLACED for an unplaced mate,
+        u64[256] of proper pairs by tlen // hist_bin_bases with the last bin open-ended, or None with want_hist=False)"""
+        bases, offsets, n_reads = _batch(bases, offsets)
+        out = np.zeros(max(n_reads, 1), PAIR_PLACEMENT_DTYPE)
+        hist = np.zeros(N.PAIR_HIST_BINS, np.uint64) if want_hist else None
+        p = N.PlacePairParams(self.band_bases, self.min_votes, self.prefix_length, int(max_placements), int(max_insert),
+                              int(hist_bin_bases), (C.c_uint32 * 3)(0, 0, 0))
+        N.check(N.lib().dcn_place_pair_batch(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None, _ptr(offsets),
+                                             n_reads, C.byref(p), _ptr(out), _ptr(hist) if want_hist else None))
+        return out[:n_reads], hist
+
+    def place_pairs(self, reads1, reads2, **kw):
+        """the mates of two lists, interleaved -> place_pair_batch's result"""
+        reads1, reads2 = list(reads1), list(reads2)
+        if len(reads1) != len(reads2):
+            raise ValueError("place_pairs: the two lists must have one mate each per pair")
+        bases, offsets = concat_reads([m for pair in zip(reads1, reads2) for m in pair])
+        return self.place_pair_batch(bases, offsets, **kw)
 
 
 class FilterProcessor(_Context):

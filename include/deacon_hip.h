@@ -73,9 +73,10 @@ enum {
  * 1.7 = dcn_index_builder_create / _add / _info / _hist / _counts / _finish / _destroy;
  * 1.8 = dcn_depth_track_batch;
  * 1.9 = dcn_anchor_map_create / _add / _info / _anchors, dcn_place_batch.
- * 1.10 = dcn_place_split_batch. */
+ * 1.10 = dcn_place_split_batch.
+ * 1.11 = dcn_place_pair_batch. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 10
+#define DCN_ABI_MINOR 11
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -713,6 +714,84 @@ typedef struct dcn_split_placement {
 int dcn_place_split_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets,
                           uint32_t n_reads, const void *params, uint64_t *place_offsets, void *placements,
                           uint64_t capacity, uint32_t *read_counts);
+
+/* ---- paired placements: mates placed jointly, proper pairs, rescue, insert sizes (ABI 1.11) --------------------------
+ * THE DEFINITION OF A PAIRED PLACEMENT.  Pair u is read 2u (mate 1) and read 2u + 1 (mate 2) of the batch: n_reads is
+ * even.  N = max_placements, I = max_insert.  Positions, anchor hits, cells and rounds are exactly those of THE
+ * DEFINITION OF A SPLIT PLACEMENT: rounds 0 .. N are computed per mate, each with its votes, its (R, o), its read
+ * interval [min q, max q + k) and its reference extent [ref_start, ref_end) = [min P, max P + k) of placement rule 6.
+ *   1. CANDIDATES of a mate are its computed rounds t < N, whatever their votes.
+ *   2. CONCORDANT.  A combination (a, b) is a candidate a of mate 1 with a candidate b of mate 2.  It is concordant when
+ *      the two rounds lie on the same record; their orientations differ (call the '+' round F and the '-' round V);
+ *      F.ref_start < V.ref_end (the forward mate begins before the reverse mate ends: touching is not enough, mates
+ *      that overlap fully are fine); T = max(F.ref_end, V.ref_end) - min(F.ref_start, V.ref_start) <= I; and
+ *      max(votes_a, votes_b) >= min_votes (one mate must stand on its own, the other may have a single hit).
+ *   3. CHOSEN is the concordant combination with the largest votes_a + votes_b, ties to the smallest a, then the
+ *      smallest b.  If one exists the pair is PROPER and the mates report rounds a and b.  Otherwise each mate reports
+ *      its round 0 when its votes reach min_votes, and else is unplaced as in placement rule 7: record = UINT32_MAX and
+ *      every field but n_anchors and n_positions is 0 (flags included: an unplaced row carries none).
+ *   4. PAIRED VOTES.  For a computed round t of a mate, pv(t) = votes_t + the most votes of any candidate of the other
+ *      mate that is concordant with t: + 0 when there is none, and + 0 for t = N, which is not a candidate.  Both rows
+ *      of a proper pair so carry pair_votes = votes_a + votes_b.
+ *   5. RIVAL AND QUALITY.  rival_votes of a reported round t is the largest pv(u) over the same mate's computed rounds
+ *      u != t (u up to N) whose read interval intersects t's (split rule 3); 0 when there is none.  mapq = 0 when
+ *      rival_votes >= pv(t), else 60 * (pv(t) - rival_votes) / pv(t) by integer division.  It is a convention, as
+ *      before, and NOT a calibrated probability.  A pair with no concordant combination gives each mate exactly the
+ *      rank-0 row of dcn_place_split_batch, or no row's worth.
+ *   6. FLAGS AND TEMPLATE LENGTH.  flags bit 0 is PROPER; bit 1 is RESCUED: the pair is proper and this mate's reported
+ *      round has votes < min_votes; bit 2 is MATE_PLACED: this row is placed and so is the other mate's.  tlen: in a
+ *      proper pair the mate with the smaller ref_start gets +T, a tie goes to mate 1, and the other mate gets -T;
+ *      otherwise 0.  rank is the reported round's index; pair_votes = pv(rank); n_placed, n_anchors and n_positions are
+ *      dcn_place_split_batch's values for that read.
+ *   7. INSERT HISTOGRAM.  tlen_hist[min(T / hist_bin_bases, DCN_PAIR_HIST_BINS - 1)] counts the proper pairs of this
+ *      call.  The array is overwritten by every call: the caller sums across calls.
+ *   8. Integers only.  Nothing depends on tiles, on which vote kernel served which mate, on LDS partitions or on how a
+ *      batch is cut (as long as no pair is cut).
+ * The orientation library is FR only.  A mate's candidates are its first N rounds: a mate with many stray single hits
+ * may not compute its concordant one (there is no windowed recount around the partner).  max_insert = 1000 and
+ * hist_bin_bases = 8 are conventions of the layers above, like band_bases = 256, not measured optima. */
+#define DCN_PAIR_HIST_BINS 256
+#define DCN_PAIR_PROPER 1u
+#define DCN_PAIR_RESCUED 2u
+#define DCN_PAIR_MATE_PLACED 4u
+typedef struct dcn_place_pair_params {
+    uint32_t band_bases, min_votes; /* as dcn_place_params */
+    uint64_t prefix_length;
+    uint32_t max_placements;        /* 1 .. DCN_PLACE_SPLIT_MAX */
+    uint32_t max_insert;            /* >= 1 */
+    uint32_t hist_bin_bases;        /* >= 1 */
+    uint32_t reserved[3];           /* must be 0 */
+} dcn_place_pair_params; /* 40 bytes */
+typedef struct dcn_pair_placement {
+    /* the 64 bytes of dcn_split_placement, field for field (rival_votes and mapq by rule 5) */
+    uint32_t record;
+    uint32_t reverse;
+    uint32_t votes, n_anchors, n_positions;
+    uint32_t read_start, read_end;
+    uint32_t reserved; /* 0 */
+    uint64_t ref_start, ref_end;
+    uint32_t rank, n_placed, rival_votes, mapq;
+    /* then */
+    uint32_t flags;      /* DCN_PAIR_* */
+    uint32_t pair_votes; /* pv(rank) */
+    int64_t tlen;
+} dcn_pair_placement; /* 80 bytes */
+
+/*   map        as for dcn_place_batch
+ *   params     a dcn_place_pair_params
+ *   rows       n_reads entries of dcn_pair_placement: row 2u is mate 1 of pair u, row 2u + 1 mate 2; unplaced mates
+ *              have a row too (fixed size: no CSR and no DCN_ERR_CAPACITY)
+ *   tlen_hist  NULL, or DCN_PAIR_HIST_BINS entries
+ * (params and rows are declared void * for the reason given at dcn_locate_batch.)  Host pointers, blocking, batch limits
+ * as for dcn_place_split_batch; refused while batches are in flight; the six counters of the context are left
+ * unchanged.  DCN_ERR_ARG, before any device work: NULLs, reserved != 0, band_bases, min_votes, max_insert or
+ * hist_bin_bases == 0, max_placements 0 or above DCN_PLACE_SPLIT_MAX, an odd n_reads, an index that is not a map.
+ * n_reads = 0 succeeds and zeroes the histogram when one is given.  Device memory: what dcn_place_split_batch states
+ * (shared with it, all but its rows), plus 80 bytes per read of max_batch_reads for the rows and 2 KB of histogram.
+ * dcn_ctx_set_profiling covers it: pack, plan, scan (minimizer dump), DISTINCT = the mark sweep, FINISH = the bitmap
+ * copy, the rounds and the pairing. */
+int dcn_place_pair_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets,
+                         uint32_t n_reads, const void *params, void *rows, uint64_t *tlen_hist);
 
 /* ---- counters: ProcessingStats (src/local_filter.rs:179-187, merged at :388-396) -------------------------- */
 
