@@ -414,10 +414,8 @@ __global__ __launch_bounds__(DCN_COV_THREADS) void coverage_keys_kernel(const ui
 }
 
 uint32_t cov_blocks(uint64_t items) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + DCN_COV_THREADS - 1) / DCN_COV_THREADS,
-                                                             (uint64_t)std::max(cus, 1) * 8));
+                                                             (uint64_t)dcn_cu_count() * 8));
 }
 
 // insert-or-OR: every key of a member's slot array into the set, its bit into the label of the slot that holds it
@@ -450,9 +448,7 @@ int dcn_launch_classify_units(const dcn_classify_args &a, hipStream_t stream) {
 int dcn_launch_classify_big(const dcn_classify_args &a, hipStream_t stream) {
     if (a.n_units == 0) return DCN_OK;
     // a grid over the device's CUs (a few workgroups each), looping over the work list whose length is on the device
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const uint32_t blocks = std::min<uint32_t>(a.n_units, (uint32_t)std::max(cus, 1) * 4);
+    const uint32_t blocks = std::min<uint32_t>(a.n_units, dcn_cu_count() * 4);
     if (a.cov_bits)
         hipLaunchKernelGGL(classify_big_kernel<true>, dim3(blocks), dim3(DCN_CLS_BIG_THREADS), 0, stream, a);
     else

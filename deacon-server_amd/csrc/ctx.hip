@@ -20,6 +20,12 @@
 
 using dcn_host::HostPool;
 
+uint32_t dcn_cu_count() {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return (uint32_t)std::max(cus, 1);
+}
+
 namespace dcn_impl {
 
 int alloc_records(dcn_ctx *c, uint64_t n_records) {

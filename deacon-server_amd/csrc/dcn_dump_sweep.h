@@ -81,6 +81,15 @@ __device__ __forceinline__ uint32_t dcn_owner_of(const uint64_t *off, uint32_t n
     return lo;
 }
 
+// per-read counts -> CSR offsets (offsets_scan.hip): offsets[0 .. n] = the exclusive scan of counts[0 .. n), offsets[n] the
+// total; 64-bit offsets from 32-bit counts.  A workgroup scans DCN_SCAN_BLOCK counts (DCN_SCAN_ITEMS per thread), one
+// workgroup the block sums: `block_sums` is scratch of n / DCN_SCAN_BLOCK + 1 words.
+constexpr uint32_t DCN_SCAN_THREADS = 256;
+constexpr uint32_t DCN_SCAN_ITEMS = 8;
+constexpr uint32_t DCN_SCAN_BLOCK = DCN_SCAN_THREADS * DCN_SCAN_ITEMS;
+int dcn_launch_offsets_scan(const uint32_t *counts, uint32_t n, unsigned long long *block_sums, uint64_t *offsets,
+                            hipStream_t stream);
+
 // launches a kernel that sweeps a.dump with dcn_for_dump_entries; `too_many` is the message of a grid past 2^31 blocks
 template <typename Args>
 int dcn_launch_dump_sweep(void (*kernel)(Args), const Args &a, const char *too_many, hipStream_t stream) {

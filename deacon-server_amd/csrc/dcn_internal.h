@@ -43,6 +43,10 @@ int dcn_device_tally(uint64_t count, unsigned long long *h, const char *what, F 
     return e == hipSuccess ? DCN_OK : dcn_hip_fail(e, what);
 }
 
+// compute units of the current device (256 where the runtime does not say; at least 1): what the grids that stride over
+// their work are sized by (ctx.hip)
+uint32_t dcn_cu_count();
+
 // memcpy on the host pool's threads (api.hip): large copies into memory nobody has touched yet are first-touch bound on one thread
 void dcn_host_parallel_copy(void *dst, const void *src, size_t n);
 

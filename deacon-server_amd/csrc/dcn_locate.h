@@ -8,9 +8,6 @@ constexpr uint32_t DCN_LOC_THREADS = 256;
 // segments: a read of at most this many bases is walked by one lane, bit by bit; a longer one by one wave, a bitmap word
 // per lane, which needs every word to hold hits of one segment only: k + max_gap >= 31 (else every read takes the lane path)
 constexpr uint32_t DCN_LOC_LANE_BASES = 1024;
-// the exclusive scan of the per-read counts: reads per workgroup
-constexpr uint32_t DCN_LOC_SCAN_ITEMS = 8;
-constexpr uint32_t DCN_LOC_SCAN_BLOCK = DCN_LOC_THREADS * DCN_LOC_SCAN_ITEMS;
 
 struct dcn_locate_args {
     dcn_table_view table;
@@ -26,7 +23,7 @@ struct dcn_locate_args {
     uint32_t *bits;          // one bit per base of the batch stream, zero before the mark kernel
     uint32_t *label_scratch; // per base: the label of the hit there (sets only; read only where a bit is set)
     uint32_t *counts;        // per read: segments
-    unsigned long long *block_sums; // per DCN_LOC_SCAN_BLOCK reads
+    unsigned long long *block_sums; // scratch of dcn_launch_offsets_scan
     uint64_t *seg_offsets;   // n_reads + 1
     dcn_segment *segs;
     uint64_t seg_cap; // entries of segs: a segment at or past it is not written (the host grows the buffer and writes again)

@@ -1,5 +1,6 @@
-// dcn_place.h -- anchor maps and placement: the kernels behind dcn_anchor_map_*, dcn_place_batch (place.hip),
-// dcn_place_split_batch (place_split.hip) and dcn_place_pair_batch (place_pair.hip); not part of the public ABI.
+// dcn_place.h -- anchor maps and placement: the kernels behind dcn_anchor_map_* and the mark sweep (place.hip), the vote
+// of dcn_place_batch, dcn_place_split_batch and dcn_place_pair_batch (place_vote.hip), and what consumes its rounds: the
+// CSR tail of the split call (place_split.hip) and the pairing (place_pair.hip); not part of the public ABI.
 #pragma once
 
 #include "dcn_dump_sweep.h"
@@ -70,51 +71,7 @@ int dcn_anchor_export(const dcn_index *map, uint64_t *d_keys, uint32_t *d_record
 int dcn_launch_place_mark(const dcn_place_args &a, hipStream_t stream);
 int dcn_launch_place_vote(const dcn_place_args &a, hipStream_t stream);
 
-// ---- what the vote kernels of place.hip and place_split.hip share ---------------------------------------------------
-// an anchor hit of a read: the word of base p = o0 + q of a read of len bases
-struct plc_hit {
-    uint32_t rec1; // record + 1
-    uint32_t o;    // 0: '+', 1: '-'
-    uint32_t q, P;
-    uint64_t j;    // D / W: the hit votes for cells j and j + 1 of (record, o)
-};
-__device__ inline plc_hit plc_decode(uint64_t w, uint32_t q, uint64_t len, uint32_t band) {
-    plc_hit h;
-    h.rec1 = (uint32_t)(w >> 33);
-    h.o = (uint32_t)(w & 1);
-    h.q = q;
-    h.P = dcn_anchor_position(w);
-    const uint64_t D = h.o ? (uint64_t)h.P + q : (uint64_t)h.P + len - q;
-    h.j = D / band;
-    return h;
-}
-
-// a cell and its votes; better(): more votes, then the smaller (record, o, j)
-struct plc_cell {
-    uint32_t votes, rec1, o;
-    uint64_t j;
-};
-__device__ inline plc_cell plc_no_cell() { return plc_cell{0, 0, 0, 0}; }
-__device__ inline bool plc_better(uint32_t votes, uint32_t rec1, uint32_t o, uint64_t j, const plc_cell &b) {
-    if (votes != b.votes) return votes > b.votes;
-    if (rec1 != b.rec1) return rec1 < b.rec1;
-    if (o != b.o) return o < b.o;
-    return j < b.j;
-}
-
-struct plc_extent {
-    uint32_t q0 = ~0u, q1 = 0, P0 = ~0u, P1 = 0;
-};
-
-__device__ inline uint64_t plc_mix(uint64_t x) {
-    x ^= x >> 33;
-    x *= 0xFF51AFD7ED558CCDull;
-    x ^= x >> 33;
-    x *= 0xC4CEB9FE1A85EC53ull;
-    return x ^ (x >> 33);
-}
-
-// ---- split placements (dcn_place_split_batch, place_split.hip) -----------------------------------------------------
+// ---- split placements (dcn_place_split_batch: place_vote.hip, place_split.hip) ------------------------------------
 // The vote runs the rounds of "THE DEFINITION OF A SPLIT PLACEMENT" over a copy of the anchor bitmap, `rbits`: a round
 // counts the cells of the hits whose bit is still set, and clears the bits of the winning cell's hits.  The anchor
 // bitmap itself stays as the mark left it (n_anchors is counted there).  A read's first and last word of the copy are
@@ -134,16 +91,13 @@ struct dcn_place_split_args {
     uint32_t *n_rounds;      // per read: computed rounds
     uint32_t *read_counts;   // per read: n_anchors, n_positions
     uint32_t *counts;        // per read: reported placements
-    unsigned long long *block_sums; // per DCN_PLS_SCAN_BLOCK reads
+    unsigned long long *block_sums; // scratch of dcn_launch_offsets_scan
     uint64_t *place_offsets; // n_reads + 1
     dcn_split_placement *out; // n_reads * N entries: the CSR rows are written at place_offsets
 };
-// the exclusive scan of the per-read counts: reads per workgroup (the form of locate's scan)
-constexpr uint32_t DCN_PLS_SCAN_ITEMS = 8;
-constexpr uint32_t DCN_PLS_SCAN_BLOCK = DCN_PLC_THREADS * DCN_PLS_SCAN_ITEMS;
 
-// rounds per read (lane and workgroup form, the switch and the work list of dcn_launch_place_vote) -> rounds, n_rounds,
-// counts, read_counts; *p.n_big is zero before
+// rounds per read (dcn_launch_place_vote's kernels, switch and work list, instantiated with the clearing bitmap) ->
+// rounds, n_rounds, counts, read_counts; *p.n_big is zero before
 int dcn_launch_place_split_rounds(const dcn_place_split_args &s, hipStream_t stream);
 // the CSR tail: counts -> place_offsets (exclusive scan, place_offsets[n_reads] = the total) -> out
 int dcn_launch_place_split_rows(const dcn_place_split_args &s, hipStream_t stream);

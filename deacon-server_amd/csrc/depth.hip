@@ -177,11 +177,9 @@ __global__ __launch_bounds__(DCN_DEPTH_THREADS) void depth_keys_kernel(const uin
 }
 
 uint32_t depth_blocks(uint64_t n_slots) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const uint64_t quads = (n_slots + 3) / 4;
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((quads + DCN_DEPTH_THREADS - 1) / DCN_DEPTH_THREADS,
-                                                             (uint64_t)std::max(cus, 1) * 8));
+                                                             (uint64_t)dcn_cu_count() * 8));
 }
 
 } // namespace

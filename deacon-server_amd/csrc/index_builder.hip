@@ -192,10 +192,8 @@ __global__ __launch_bounds__(DCN_BUILDER_THREADS) void builder_select_kernel(con
 
 // a grid over the device's CUs, a few workgroups each; the loops stride over the rest
 uint32_t builder_blocks(uint64_t items) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + DCN_BUILDER_THREADS - 1) / DCN_BUILDER_THREADS,
-                                                             (uint64_t)std::max(cus, 1) * 8));
+                                                             (uint64_t)dcn_cu_count() * 8));
 }
 
 // the table as quads: it has a power-of-two number of groups, at least 64, so its slots come in fours

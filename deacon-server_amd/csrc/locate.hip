@@ -9,7 +9,7 @@
 //                           bit, which is the "counts once" of the definition.
 //   locate_segments_kernel  read r's segments from its slice [offsets[r], offsets[r+1]) of the bitmap.  A hit starts a
 //                           segment iff no hit lies in the k + max_gap positions before it.  COUNT pass -> exclusive
-//                           scan over reads -> WRITE pass: reads in order, segments ascending, no sorting and no atomics
+//                           scan over reads (dcn_launch_offsets_scan) -> WRITE pass: reads in order, segments ascending, no sorting and no atomics
 //                           on the output.  One lane walks a short read bit by bit; a long read goes to a work list and
 //                           locate_segments_wave_kernel, a wave per read, a bitmap word per lane: the word's hits are one
 //                           partial segment (k + max_gap >= 31), joined to the previous lane's by a max-scan of the last
@@ -199,71 +199,9 @@ __global__ __launch_bounds__(DCN_LOC_THREADS) void locate_segments_wave_kernel(d
     }
 }
 
-// ---- exclusive scan of counts[0..n) into seg_offsets[0..n], seg_offsets[n] = the total ------------------------------
-__device__ inline uint32_t loc_thread_sum(const dcn_locate_args &a, uint32_t i0) {
-    uint32_t s = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < DCN_LOC_SCAN_ITEMS; ++i)
-        if (i0 + i < a.n_reads) s += a.counts[i0 + i];
-    return s;
-}
-
-// inclusive scan of one value per thread over the workgroup
-__device__ inline uint32_t loc_block_scan(uint32_t v, uint32_t *s_wave) {
-    const uint32_t lane = threadIdx.x & (DCN_WAVE - 1), wave = threadIdx.x / DCN_WAVE;
-    for (uint32_t d = 1; d < DCN_WAVE; d <<= 1) {
-        const uint32_t o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    if (lane == DCN_WAVE - 1) s_wave[wave] = v;
-    __syncthreads();
-    for (uint32_t q = 0; q < wave; ++q) v += s_wave[q];
-    return v;
-}
-
-__global__ __launch_bounds__(DCN_LOC_THREADS) void locate_scan_sums_kernel(dcn_locate_args a) {
-    __shared__ uint32_t s_wave[DCN_LOC_THREADS / DCN_WAVE];
-    const uint32_t i0 = blockIdx.x * DCN_LOC_SCAN_BLOCK + threadIdx.x * DCN_LOC_SCAN_ITEMS;
-    const uint32_t incl = loc_block_scan(loc_thread_sum(a, i0), s_wave);
-    if (threadIdx.x == DCN_LOC_THREADS - 1) a.block_sums[blockIdx.x] = incl;
-}
-
-// one workgroup: block_sums[] -> their exclusive prefix
-__global__ __launch_bounds__(DCN_LOC_THREADS) void locate_scan_blocks_kernel(dcn_locate_args a, uint32_t n_blocks) {
-    __shared__ unsigned long long s_part[DCN_LOC_THREADS];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t per = (n_blocks + DCN_LOC_THREADS - 1) / DCN_LOC_THREADS;
-    const uint32_t b0 = min(tid * per, n_blocks), b1 = min(b0 + per, n_blocks);
-    unsigned long long mine = 0;
-    for (uint32_t b = b0; b < b1; ++b) mine += a.block_sums[b];
-    s_part[tid] = mine;
-    __syncthreads();
-    unsigned long long before = 0;
-    for (uint32_t q = 0; q < tid; ++q) before += s_part[q];
-    for (uint32_t b = b0; b < b1; ++b) {
-        const unsigned long long v = a.block_sums[b];
-        a.block_sums[b] = before;
-        before += v;
-    }
-}
-
-__global__ __launch_bounds__(DCN_LOC_THREADS) void locate_scan_write_kernel(dcn_locate_args a) {
-    __shared__ uint32_t s_wave[DCN_LOC_THREADS / DCN_WAVE];
-    const uint32_t i0 = blockIdx.x * DCN_LOC_SCAN_BLOCK + threadIdx.x * DCN_LOC_SCAN_ITEMS;
-    const uint32_t mine = loc_thread_sum(a, i0);
-    uint64_t at = a.block_sums[blockIdx.x] + (loc_block_scan(mine, s_wave) - mine);
-    if (i0 == 0) a.seg_offsets[0] = 0;
-    for (uint32_t i = 0; i < DCN_LOC_SCAN_ITEMS && i0 + i < a.n_reads; ++i) {
-        at += a.counts[i0 + i];
-        a.seg_offsets[i0 + i + 1] = at;
-    }
-}
-
 uint32_t loc_wave_blocks(uint32_t n_reads) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const uint32_t waves = DCN_LOC_THREADS / DCN_WAVE;
-    return std::max(1u, std::min((n_reads + waves - 1) / waves, (uint32_t)std::max(cus, 1) * 8));
+    return std::max(1u, std::min((n_reads + waves - 1) / waves, dcn_cu_count() * 8));
 }
 
 } // namespace
@@ -278,12 +216,8 @@ int dcn_launch_locate_count(const dcn_locate_args &a, hipStream_t stream) {
     const uint32_t blocks = (a.n_reads + DCN_LOC_THREADS - 1) / DCN_LOC_THREADS;
     hipLaunchKernelGGL(locate_segments_kernel<false>, dim3(blocks), dim3(DCN_LOC_THREADS), 0, stream, a);
     hipLaunchKernelGGL(locate_segments_wave_kernel<false>, dim3(loc_wave_blocks(a.n_reads)), dim3(DCN_LOC_THREADS), 0, stream, a);
-    const uint32_t scan_blocks = (a.n_reads + DCN_LOC_SCAN_BLOCK - 1) / DCN_LOC_SCAN_BLOCK;
-    hipLaunchKernelGGL(locate_scan_sums_kernel, dim3(scan_blocks), dim3(DCN_LOC_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(locate_scan_blocks_kernel, dim3(1), dim3(DCN_LOC_THREADS), 0, stream, a, scan_blocks);
-    hipLaunchKernelGGL(locate_scan_write_kernel, dim3(scan_blocks), dim3(DCN_LOC_THREADS), 0, stream, a);
     DCN_HIP(hipGetLastError());
-    return DCN_OK;
+    return dcn_launch_offsets_scan(a.counts, a.n_reads, a.block_sums, a.seg_offsets, stream);
 }
 
 int dcn_launch_locate_write(const dcn_locate_args &a, hipStream_t stream) {

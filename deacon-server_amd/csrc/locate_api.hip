@@ -24,7 +24,7 @@ int locate_buffers(dcn_ctx *c, bool labelled) {
     DCN_TRY(ensure_position_bitmap(c));
     if (!c->d_loc_counts) {
         DCN_TRY(dev_alloc(&c->d_loc_counts, c->max_reads, "locate counts"));
-        DCN_TRY(dev_alloc(&c->d_loc_block_sums, (uint64_t)c->max_reads / DCN_LOC_SCAN_BLOCK + 1, "locate block sums"));
+        DCN_TRY(dev_alloc(&c->d_loc_block_sums, (uint64_t)c->max_reads / DCN_SCAN_BLOCK + 1, "locate block sums"));
         DCN_TRY(dev_alloc(&c->d_loc_seg_offsets, (uint64_t)c->max_reads + 1, "locate segment offsets"));
         DCN_TRY(dev_alloc(&c->d_loc_big, c->max_reads, "locate work list"));
         DCN_TRY(dev_alloc(&c->d_loc_n_big, 1, "locate work list length"));

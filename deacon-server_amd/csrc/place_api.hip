@@ -1,11 +1,12 @@
 // place_api.hip -- the C ABI of anchor maps (dcn_anchor_map_*), dcn_place_batch, dcn_place_split_batch and
-// dcn_place_pair_batch (kernels in place.hip, place_split.hip and place_pair.hip; the batch calls run the dump front
-// end of ctx.hip on a filter context).
+// dcn_place_pair_batch (kernels in place.hip, place_vote.hip, place_split.hip and place_pair.hip; the batch calls run the
+// dump front end of ctx.hip on a filter context).
 #include "dcn_ctx.h"
 #include "dcn_place.h"
 
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 using namespace dcn_impl;
 
@@ -43,6 +44,129 @@ int front_end(dcn_ctx *c, const dcn_index *map, uint32_t n_reads, uint64_t n_bas
     pa->status = c->d_status;
     pa->offsets = c->d_offsets;
     pa->n_reads = n_reads;
+    return DCN_OK;
+}
+
+// ---- what dcn_place_batch, dcn_place_split_batch and dcn_place_pair_batch share --------------------------------------
+// the parameters every placement call has (max_placements: the split and the pair call)
+template <typename P>
+int check_vote_params(const P *prm) {
+    if (!prm) return dcn_fail(DCN_ERR_ARG, "params is NULL");
+    for (const uint32_t v : prm->reserved)
+        if (v != 0) return dcn_fail(DCN_ERR_ARG, "params.reserved must be 0");
+    if (prm->band_bases == 0) return dcn_fail(DCN_ERR_ARG, "params.band_bases must be at least 1");
+    if (prm->min_votes == 0) return dcn_fail(DCN_ERR_ARG, "params.min_votes must be at least 1");
+    if constexpr (!std::is_same_v<P, dcn_place_params>)
+        if (prm->max_placements == 0 || prm->max_placements > DCN_PLACE_SPLIT_MAX)
+            return dcn_fail(DCN_ERR_ARG, "params.max_placements must be 1.." + std::to_string(DCN_PLACE_SPLIT_MAX));
+    return DCN_OK;
+}
+
+int check_target(const dcn_ctx *ctx, const dcn_index *map) {
+    if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
+    DCN_TRY(check_map(map));
+    return check_ctx_matches(ctx, map, "the map");
+}
+
+// a batch of n_reads > 0 reads; `out_is_null` names the output the call cannot do without (null: it has it)
+int check_batch(const dcn_ctx *ctx, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, const char *out_is_null,
+                uint64_t *n_bases) {
+    if (!offsets) return dcn_fail(DCN_ERR_ARG, "offsets is NULL");
+    if (out_is_null) return dcn_fail(DCN_ERR_ARG, out_is_null);
+    DCN_TRY(validate_host_batch(ctx, offsets, n_reads)); // (a read of 2^32 bases or more is refused here)
+    *n_bases = offsets[n_reads];
+    if (*n_bases > 0 && !bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
+    return DCN_OK;
+}
+
+// a buffer of the context that grows to the largest need so far
+template <typename T>
+int grow(T **buf, uint64_t *cap, uint64_t need, const char *what) {
+    if (need <= *cap) return DCN_OK;
+    if (*buf) hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    DCN_TRY(dev_alloc(buf, need, what));
+    *cap = need;
+    return DCN_OK;
+}
+
+// which buffers a call needs beside those of the mark sweep and the work list
+enum place_mode {
+    PLACE_SINGLE, // the placements; no remaining-hits bitmap, rounds or counts
+    PLACE_SPLIT,  // the rounds' buffers and the CSR tail's
+    PLACE_PAIR,   // the rounds' buffers
+};
+
+// What the three calls do before the vote: the buffers of the context (allocated when a call first needs them), the
+// staged batch, the dump front end, the mark sweep (DISTINCT ends behind it) and, for the rounds, the copy of the anchor
+// bitmap that they clear.  `sa` is ready for dcn_launch_place_vote (sa.p) / dcn_launch_place_split_rounds / _rows.
+template <typename P>
+int place_prepare(dcn_ctx *c, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                  uint64_t n_bases, const P *prm, place_mode mode, int *prof_slot_out, dcn_place_split_args *sa_out) {
+    uint32_t N = 0;
+    if constexpr (!std::is_same_v<P, dcn_place_params>) N = prm->max_placements;
+    DCN_HIP(hipSetDevice(c->device));
+    DCN_TRY(ensure_dump_buffers(c));
+    DCN_TRY(ensure_position_bitmap(c));
+    const uint64_t bitmap_words = (c->max_bases + 31) / 32 + 1;
+    if (!c->d_plc_abits) DCN_TRY(dev_alloc(&c->d_plc_abits, bitmap_words, "anchor bitmap"));
+    if (!c->d_plc_words) DCN_TRY(dev_alloc(&c->d_plc_words, c->max_bases + 2, "placement words"));
+    if (!c->d_plc_big) DCN_TRY(dev_alloc(&c->d_plc_big, c->max_reads, "placement work list"));
+    if (!c->d_plc_n_big) DCN_TRY(dev_alloc(&c->d_plc_n_big, 1, "placement work list length"));
+    if (mode == PLACE_SINGLE) {
+        if (!c->d_plc_out) DCN_TRY(dev_alloc(&c->d_plc_out, c->max_reads, "placements"));
+    } else {
+        if (!c->d_pls_rbits) DCN_TRY(dev_alloc(&c->d_pls_rbits, bitmap_words, "remaining anchor bitmap"));
+        if (!c->d_pls_n_rounds) DCN_TRY(dev_alloc(&c->d_pls_n_rounds, c->max_reads, "placement round counts"));
+        if (!c->d_pls_read_counts) DCN_TRY(dev_alloc(&c->d_pls_read_counts, (uint64_t)c->max_reads * 2, "placement read counts"));
+        if (!c->d_pls_counts) DCN_TRY(dev_alloc(&c->d_pls_counts, c->max_reads, "placement counts"));
+        if (mode == PLACE_SPLIT) {
+            if (!c->d_pls_block_sums)
+                DCN_TRY(dev_alloc(&c->d_pls_block_sums, (uint64_t)c->max_reads / DCN_SCAN_BLOCK + 1, "placement block sums"));
+            if (!c->d_pls_offsets) DCN_TRY(dev_alloc(&c->d_pls_offsets, (uint64_t)c->max_reads + 1, "placement offsets"));
+        }
+        DCN_TRY(grow(&c->d_pls_rounds, &c->pls_round_cap, (uint64_t)n_reads * (N + 1), "placement rounds"));
+        if (mode == PLACE_SPLIT) DCN_TRY(grow(&c->d_pls_out, &c->pls_out_cap, (uint64_t)n_reads * N, "split placements"));
+    }
+    DCN_TRY(stage_batch(c, bases, n_bases, offsets, n_reads, nullptr));
+    hipStream_t st = c->stream;
+    const uint64_t batch_words = (n_bases + 31) / 32 + 1;
+    DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
+    DCN_HIP(hipMemsetAsync(c->d_loc_bits, 0, batch_words * sizeof(uint32_t), st));
+    DCN_HIP(hipMemsetAsync(c->d_plc_abits, 0, batch_words * sizeof(uint32_t), st));
+    DCN_HIP(hipMemsetAsync(c->d_plc_n_big, 0, sizeof(uint32_t), st));
+    int prof_slot = -1;
+    dcn_place_split_args &sa = *sa_out;
+    memset(&sa, 0, sizeof(sa));
+    dcn_place_args &pa = sa.p;
+    DCN_TRY(front_end(c, map, n_reads, n_bases, prm->prefix_length, &prof_slot, &pa));
+    *prof_slot_out = prof_slot;
+    pa.band = prm->band_bases;
+    pa.min_votes = prm->min_votes;
+    pa.lane_bases = env_u32("DCN_PLACE_LANE_BASES", DCN_PLC_LANE_BASES, 0, 0xFFFFFFFFu);
+    pa.lds_cells = env_u32("DCN_PLACE_LDS_CELLS", DCN_PLC_LDS_CELLS, DCN_PLC_LDS_CELLS_MIN, DCN_PLC_LDS_CELLS);
+    // (the offsets are the host's: whether any read takes the workgroup path is known before the launch)
+    for (uint32_t r = 0; r < n_reads && !pa.any_big; ++r) pa.any_big = offsets[r + 1] - offsets[r] > pa.lane_bases ? 1u : 0u;
+    pa.bits = c->d_loc_bits;
+    pa.abits = c->d_plc_abits;
+    pa.words = c->d_plc_words;
+    pa.big = c->d_plc_big;
+    pa.n_big = c->d_plc_n_big;
+    pa.out = c->d_plc_out; // (null unless dcn_place_batch ran on the context; only its vote writes it)
+    sa.rbits = c->d_pls_rbits;
+    sa.max_placements = N;
+    sa.rounds = c->d_pls_rounds;
+    sa.n_rounds = c->d_pls_n_rounds;
+    sa.read_counts = c->d_pls_read_counts;
+    sa.counts = c->d_pls_counts;
+    sa.block_sums = c->d_pls_block_sums;
+    sa.place_offsets = c->d_pls_offsets;
+    sa.out = c->d_pls_out;
+    DCN_TRY(dcn_launch_place_mark(pa, st));
+    DCN_PROF_MARK(DCN_STAGE_DISTINCT);
+    if (mode != PLACE_SINGLE)
+        DCN_HIP(hipMemcpyAsync(c->d_pls_rbits, c->d_plc_abits, batch_words * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     return DCN_OK;
 }
 } // namespace
@@ -148,163 +272,38 @@ extern "C" int dcn_place_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t
                                uint32_t n_reads, const void *params, void *placements) {
     const dcn_place_params *prm = static_cast<const dcn_place_params *>(params);
     // (the parameters first: what is wrong with them does not depend on the context or the map)
-    if (!prm) return dcn_fail(DCN_ERR_ARG, "params is NULL");
-    if (prm->reserved[0] != 0 || prm->reserved[1] != 0) return dcn_fail(DCN_ERR_ARG, "params.reserved must be 0");
-    if (prm->band_bases == 0) return dcn_fail(DCN_ERR_ARG, "params.band_bases must be at least 1");
-    if (prm->min_votes == 0) return dcn_fail(DCN_ERR_ARG, "params.min_votes must be at least 1");
-    if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
-    DCN_TRY(check_map(map));
-    DCN_TRY(check_ctx_matches(ctx, map, "the map"));
+    DCN_TRY(check_vote_params(prm));
+    DCN_TRY(check_target(ctx, map));
     if (n_reads == 0) return DCN_OK;
-    if (!offsets) return dcn_fail(DCN_ERR_ARG, "offsets is NULL");
-    if (!placements) return dcn_fail(DCN_ERR_ARG, "placements is NULL");
-    DCN_TRY(validate_host_batch(ctx, offsets, n_reads)); // (a read of 2^32 bases or more is refused here)
-    const uint64_t n_bases = offsets[n_reads];
-    if (n_bases > 0 && !bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
+    uint64_t n_bases = 0;
+    DCN_TRY(check_batch(ctx, bases, offsets, n_reads, placements ? nullptr : "placements is NULL", &n_bases));
     dcn_ctx *c = ctx;
-    DCN_HIP(hipSetDevice(c->device));
-    DCN_TRY(ensure_dump_buffers(c));
-    DCN_TRY(ensure_position_bitmap(c));
-    if (!c->d_plc_abits) DCN_TRY(dev_alloc(&c->d_plc_abits, (c->max_bases + 31) / 32 + 1, "anchor bitmap"));
-    if (!c->d_plc_words) DCN_TRY(dev_alloc(&c->d_plc_words, c->max_bases + 2, "placement words"));
-    if (!c->d_plc_big) DCN_TRY(dev_alloc(&c->d_plc_big, c->max_reads, "placement work list"));
-    if (!c->d_plc_n_big) DCN_TRY(dev_alloc(&c->d_plc_n_big, 1, "placement work list length"));
-    if (!c->d_plc_out) DCN_TRY(dev_alloc(&c->d_plc_out, c->max_reads, "placements"));
-    DCN_TRY(stage_batch(c, bases, n_bases, offsets, n_reads, nullptr));
-    hipStream_t st = c->stream;
-    DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
-    DCN_HIP(hipMemsetAsync(c->d_loc_bits, 0, ((n_bases + 31) / 32 + 1) * sizeof(uint32_t), st));
-    DCN_HIP(hipMemsetAsync(c->d_plc_abits, 0, ((n_bases + 31) / 32 + 1) * sizeof(uint32_t), st));
-    DCN_HIP(hipMemsetAsync(c->d_plc_n_big, 0, sizeof(uint32_t), st));
     int prof_slot = -1;
-    dcn_place_args pa;
-    DCN_TRY(front_end(c, map, n_reads, n_bases, prm->prefix_length, &prof_slot, &pa));
-    pa.band = prm->band_bases;
-    pa.min_votes = prm->min_votes;
-    pa.lane_bases = env_u32("DCN_PLACE_LANE_BASES", DCN_PLC_LANE_BASES, 0, 0xFFFFFFFFu);
-    pa.lds_cells = env_u32("DCN_PLACE_LDS_CELLS", DCN_PLC_LDS_CELLS, DCN_PLC_LDS_CELLS_MIN, DCN_PLC_LDS_CELLS);
-    // (the offsets are the host's: whether any read takes the workgroup path is known before the launch)
-    for (uint32_t r = 0; r < n_reads && !pa.any_big; ++r) pa.any_big = offsets[r + 1] - offsets[r] > pa.lane_bases ? 1u : 0u;
-    pa.bits = c->d_loc_bits;
-    pa.abits = c->d_plc_abits;
-    pa.words = c->d_plc_words;
-    pa.big = c->d_plc_big;
-    pa.n_big = c->d_plc_n_big;
-    pa.out = c->d_plc_out;
-    DCN_TRY(dcn_launch_place_mark(pa, st));
-    DCN_PROF_MARK(DCN_STAGE_DISTINCT);
-    DCN_TRY(dcn_launch_place_vote(pa, st));
+    dcn_place_split_args sa;
+    DCN_TRY(place_prepare(c, map, bases, offsets, n_reads, n_bases, prm, PLACE_SINGLE, &prof_slot, &sa));
+    hipStream_t st = c->stream;
+    DCN_TRY(dcn_launch_place_vote(sa.p, st));
     DCN_PROF_MARK(DCN_STAGE_FINISH);
     DCN_TRY(finish_run(c, prof_slot));
     DCN_HIP(hipMemcpy(placements, c->d_plc_out, (uint64_t)n_reads * sizeof(dcn_placement), hipMemcpyDeviceToHost));
     return DCN_OK;
 }
 
-namespace {
-// a buffer of the context that grows to the largest need so far
-template <typename T>
-int grow(T **buf, uint64_t *cap, uint64_t need, const char *what) {
-    if (need <= *cap) return DCN_OK;
-    if (*buf) hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    DCN_TRY(dev_alloc(buf, need, what));
-    *cap = need;
-    return DCN_OK;
-}
-
-// What dcn_place_split_batch and dcn_place_pair_batch do before the rounds: the buffers of the context (`rows`: those of
-// the CSR tail too), the staged batch, the dump front end, the mark sweep (DISTINCT ends behind it) and the copy of the
-// anchor bitmap that the rounds clear.  `sa` is ready for dcn_launch_place_split_rounds / _rows.
-int split_prepare(dcn_ctx *c, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
-                  uint64_t n_bases, uint32_t band_bases, uint32_t min_votes, uint64_t prefix_length, uint32_t N, bool rows,
-                  int *prof_slot_out, dcn_place_split_args *sa_out) {
-    DCN_HIP(hipSetDevice(c->device));
-    DCN_TRY(ensure_dump_buffers(c));
-    DCN_TRY(ensure_position_bitmap(c));
-    const uint64_t bitmap_words = (c->max_bases + 31) / 32 + 1;
-    if (!c->d_plc_abits) DCN_TRY(dev_alloc(&c->d_plc_abits, bitmap_words, "anchor bitmap"));
-    if (!c->d_plc_words) DCN_TRY(dev_alloc(&c->d_plc_words, c->max_bases + 2, "placement words"));
-    if (!c->d_plc_big) DCN_TRY(dev_alloc(&c->d_plc_big, c->max_reads, "placement work list"));
-    if (!c->d_plc_n_big) DCN_TRY(dev_alloc(&c->d_plc_n_big, 1, "placement work list length"));
-    if (!c->d_pls_rbits) DCN_TRY(dev_alloc(&c->d_pls_rbits, bitmap_words, "remaining anchor bitmap"));
-    if (!c->d_pls_n_rounds) DCN_TRY(dev_alloc(&c->d_pls_n_rounds, c->max_reads, "placement round counts"));
-    if (!c->d_pls_read_counts) DCN_TRY(dev_alloc(&c->d_pls_read_counts, (uint64_t)c->max_reads * 2, "placement read counts"));
-    if (!c->d_pls_counts) DCN_TRY(dev_alloc(&c->d_pls_counts, c->max_reads, "placement counts"));
-    if (rows) {
-        if (!c->d_pls_block_sums)
-            DCN_TRY(dev_alloc(&c->d_pls_block_sums, (uint64_t)c->max_reads / DCN_PLS_SCAN_BLOCK + 1, "placement block sums"));
-        if (!c->d_pls_offsets) DCN_TRY(dev_alloc(&c->d_pls_offsets, (uint64_t)c->max_reads + 1, "placement offsets"));
-    }
-    DCN_TRY(grow(&c->d_pls_rounds, &c->pls_round_cap, (uint64_t)n_reads * (N + 1), "placement rounds"));
-    if (rows) DCN_TRY(grow(&c->d_pls_out, &c->pls_out_cap, (uint64_t)n_reads * N, "split placements"));
-    DCN_TRY(stage_batch(c, bases, n_bases, offsets, n_reads, nullptr));
-    hipStream_t st = c->stream;
-    const uint64_t batch_words = (n_bases + 31) / 32 + 1;
-    DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st));
-    DCN_HIP(hipMemsetAsync(c->d_loc_bits, 0, batch_words * sizeof(uint32_t), st));
-    DCN_HIP(hipMemsetAsync(c->d_plc_abits, 0, batch_words * sizeof(uint32_t), st));
-    DCN_HIP(hipMemsetAsync(c->d_plc_n_big, 0, sizeof(uint32_t), st));
-    int prof_slot = -1;
-    dcn_place_split_args &sa = *sa_out;
-    memset(&sa, 0, sizeof(sa));
-    dcn_place_args &pa = sa.p;
-    DCN_TRY(front_end(c, map, n_reads, n_bases, prefix_length, &prof_slot, &pa));
-    *prof_slot_out = prof_slot;
-    pa.band = band_bases;
-    pa.min_votes = min_votes;
-    pa.lane_bases = env_u32("DCN_PLACE_LANE_BASES", DCN_PLC_LANE_BASES, 0, 0xFFFFFFFFu);
-    pa.lds_cells = env_u32("DCN_PLACE_LDS_CELLS", DCN_PLC_LDS_CELLS, DCN_PLC_LDS_CELLS_MIN, DCN_PLC_LDS_CELLS);
-    for (uint32_t r = 0; r < n_reads && !pa.any_big; ++r) pa.any_big = offsets[r + 1] - offsets[r] > pa.lane_bases ? 1u : 0u;
-    pa.bits = c->d_loc_bits;
-    pa.abits = c->d_plc_abits;
-    pa.words = c->d_plc_words;
-    pa.big = c->d_plc_big;
-    pa.n_big = c->d_plc_n_big;
-    sa.rbits = c->d_pls_rbits;
-    sa.max_placements = N;
-    sa.rounds = c->d_pls_rounds;
-    sa.n_rounds = c->d_pls_n_rounds;
-    sa.read_counts = c->d_pls_read_counts;
-    sa.counts = c->d_pls_counts;
-    sa.block_sums = c->d_pls_block_sums;
-    sa.place_offsets = c->d_pls_offsets;
-    sa.out = c->d_pls_out;
-    DCN_TRY(dcn_launch_place_mark(pa, st));
-    DCN_PROF_MARK(DCN_STAGE_DISTINCT);
-    DCN_HIP(hipMemcpyAsync(c->d_pls_rbits, c->d_plc_abits, batch_words * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-    return DCN_OK;
-}
-} // namespace
-
 extern "C" int dcn_place_split_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets,
                                      uint32_t n_reads, const void *params, uint64_t *place_offsets, void *placements,
                                      uint64_t capacity, uint32_t *read_counts) {
     const dcn_place_split_params *prm = static_cast<const dcn_place_split_params *>(params);
-    // (the parameters first, as in dcn_place_batch)
-    if (!prm) return dcn_fail(DCN_ERR_ARG, "params is NULL");
-    if (prm->reserved[0] != 0 || prm->reserved[1] != 0 || prm->reserved[2] != 0)
-        return dcn_fail(DCN_ERR_ARG, "params.reserved must be 0");
-    if (prm->band_bases == 0) return dcn_fail(DCN_ERR_ARG, "params.band_bases must be at least 1");
-    if (prm->min_votes == 0) return dcn_fail(DCN_ERR_ARG, "params.min_votes must be at least 1");
-    if (prm->max_placements == 0 || prm->max_placements > DCN_PLACE_SPLIT_MAX)
-        return dcn_fail(DCN_ERR_ARG, "params.max_placements must be 1.." + std::to_string(DCN_PLACE_SPLIT_MAX));
+    DCN_TRY(check_vote_params(prm));
     if (!place_offsets) return dcn_fail(DCN_ERR_ARG, "place_offsets is NULL");
-    if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
-    DCN_TRY(check_map(map));
-    DCN_TRY(check_ctx_matches(ctx, map, "the map"));
+    DCN_TRY(check_target(ctx, map));
     place_offsets[0] = 0;
     if (n_reads == 0) return DCN_OK;
-    if (!offsets) return dcn_fail(DCN_ERR_ARG, "offsets is NULL");
-    if (!placements && capacity > 0) return dcn_fail(DCN_ERR_ARG, "placements is NULL");
-    DCN_TRY(validate_host_batch(ctx, offsets, n_reads));
-    const uint64_t n_bases = offsets[n_reads];
-    if (n_bases > 0 && !bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
+    uint64_t n_bases = 0;
+    DCN_TRY(check_batch(ctx, bases, offsets, n_reads, !placements && capacity > 0 ? "placements is NULL" : nullptr, &n_bases));
     dcn_ctx *c = ctx;
     int prof_slot = -1;
     dcn_place_split_args sa;
-    DCN_TRY(split_prepare(c, map, bases, offsets, n_reads, n_bases, prm->band_bases, prm->min_votes, prm->prefix_length,
-                          prm->max_placements, true, &prof_slot, &sa));
+    DCN_TRY(place_prepare(c, map, bases, offsets, n_reads, n_bases, prm, PLACE_SPLIT, &prof_slot, &sa));
     hipStream_t st = c->stream;
     DCN_TRY(dcn_launch_place_split_vote(sa, st));
     DCN_PROF_MARK(DCN_STAGE_FINISH);
@@ -323,37 +322,24 @@ extern "C" int dcn_place_split_batch(dcn_ctx *ctx, const dcn_index *map, const u
 extern "C" int dcn_place_pair_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets,
                                     uint32_t n_reads, const void *params, void *rows, uint64_t *tlen_hist) {
     const dcn_place_pair_params *prm = static_cast<const dcn_place_pair_params *>(params);
-    // (the parameters first, as in dcn_place_batch)
-    if (!prm) return dcn_fail(DCN_ERR_ARG, "params is NULL");
-    if (prm->reserved[0] != 0 || prm->reserved[1] != 0 || prm->reserved[2] != 0)
-        return dcn_fail(DCN_ERR_ARG, "params.reserved must be 0");
-    if (prm->band_bases == 0) return dcn_fail(DCN_ERR_ARG, "params.band_bases must be at least 1");
-    if (prm->min_votes == 0) return dcn_fail(DCN_ERR_ARG, "params.min_votes must be at least 1");
-    if (prm->max_placements == 0 || prm->max_placements > DCN_PLACE_SPLIT_MAX)
-        return dcn_fail(DCN_ERR_ARG, "params.max_placements must be 1.." + std::to_string(DCN_PLACE_SPLIT_MAX));
+    DCN_TRY(check_vote_params(prm));
     if (prm->max_insert == 0) return dcn_fail(DCN_ERR_ARG, "params.max_insert must be at least 1");
     if (prm->hist_bin_bases == 0) return dcn_fail(DCN_ERR_ARG, "params.hist_bin_bases must be at least 1");
     if (n_reads % 2 != 0) return dcn_fail(DCN_ERR_ARG, "n_reads must be even: reads 2u and 2u + 1 are the mates of pair u");
-    if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
-    DCN_TRY(check_map(map));
-    DCN_TRY(check_ctx_matches(ctx, map, "the map"));
+    DCN_TRY(check_target(ctx, map));
     if (n_reads == 0) {
         if (tlen_hist) memset(tlen_hist, 0, DCN_PAIR_HIST_BINS * sizeof(uint64_t));
         return DCN_OK;
     }
-    if (!offsets) return dcn_fail(DCN_ERR_ARG, "offsets is NULL");
-    if (!rows) return dcn_fail(DCN_ERR_ARG, "rows is NULL");
-    DCN_TRY(validate_host_batch(ctx, offsets, n_reads));
-    const uint64_t n_bases = offsets[n_reads];
-    if (n_bases > 0 && !bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
+    uint64_t n_bases = 0;
+    DCN_TRY(check_batch(ctx, bases, offsets, n_reads, rows ? nullptr : "rows is NULL", &n_bases));
     dcn_ctx *c = ctx;
     DCN_HIP(hipSetDevice(c->device));
     if (!c->d_ppr_out) DCN_TRY(dev_alloc(&c->d_ppr_out, c->max_reads, "pair placements"));
     if (!c->d_ppr_hist) DCN_TRY(dev_alloc(&c->d_ppr_hist, DCN_PAIR_HIST_BINS, "insert histogram"));
     int prof_slot = -1;
     dcn_place_split_args sa;
-    DCN_TRY(split_prepare(c, map, bases, offsets, n_reads, n_bases, prm->band_bases, prm->min_votes, prm->prefix_length,
-                          prm->max_placements, false, &prof_slot, &sa));
+    DCN_TRY(place_prepare(c, map, bases, offsets, n_reads, n_bases, prm, PLACE_PAIR, &prof_slot, &sa));
     hipStream_t st = c->stream;
     DCN_TRY(dcn_launch_place_split_rounds(sa, st));
     dcn_place_pair_args pp;

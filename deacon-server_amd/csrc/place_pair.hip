@@ -1,6 +1,6 @@
 // place_pair.hip -- the pairing of dcn_place_pair_batch: the two mates of a pair placed jointly from the rounds that
-// the vote of place_split.hip computed per mate (the definition is in include/deacon_hip.h, the buffers in dcn_place.h).
-// It runs behind the dump front end, the mark sweep of place.hip and the round launcher of place_split.hip, which are
+// the vote of place_vote.hip computed per mate (the definition is in include/deacon_hip.h, the buffers in dcn_place.h).
+// It runs behind the dump front end, the mark sweep of place.hip and the round launcher of place_vote.hip, which are
 // called as they are.
 //   place_pair_kernel  one lane per pair.  It reads the two mates' round counts and rounds (at most 9 x 32 bytes per
 //                      mate) straight from global memory: no per-lane array exists, so nothing can spill.  The at most

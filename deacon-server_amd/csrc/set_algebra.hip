@@ -136,9 +136,7 @@ __global__ __launch_bounds__(SA_THREADS) void intersect_build_kernel(const uint6
 
 // a grid over the device's CUs, a few workgroups each; the loops stride over the rest
 uint32_t sa_blocks(uint64_t items) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + SA_THREADS - 1) / SA_THREADS, (uint64_t)std::max(cus, 1) * 8));
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + SA_THREADS - 1) / SA_THREADS, (uint64_t)dcn_cu_count() * 8));
 }
 
 // the set's masks as quads: the table has a power-of-two number of groups, at least 64, so its slots come in fours

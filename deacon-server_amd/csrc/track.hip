@@ -120,10 +120,8 @@ __global__ __launch_bounds__(DCN_TRK_THREADS) void track_pieces_kernel(dcn_track
 }
 
 uint32_t trk_piece_blocks(uint64_t n_pieces) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const uint32_t waves = DCN_TRK_THREADS / DCN_WAVE;
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n_pieces + waves - 1) / waves, (uint64_t)std::max(cus, 1) * 8));
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n_pieces + waves - 1) / waves, (uint64_t)dcn_cu_count() * 8));
 }
 
 } // namespace

@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 K = 31
 LANE_BASES = 1024          # DCN_LOC_LANE_BASES: longer reads go to the wave kernel when k + max_gap >= 31
 ITER_WORDS = 64            # bitmap words per iteration of the wave kernel (2,048 bases)
-SCAN_BLOCK = 2048          # DCN_LOC_SCAN_BLOCK: reads per block of the scan over reads
+SCAN_BLOCK = 2048          # DCN_SCAN_BLOCK: reads per block of the scan over reads
 SCAN_THREADS = 256         # DCN_LOC_THREADS: locate_scan_blocks_kernel takes ceil(blocks / 256) blocks per thread
 SEG_BUFFER = 1 << 16       # a context's first device segment buffer (grow_segments)
 MODS = (0, 1, 31)          # o0 mod 32 of the reads under test

@@ -198,6 +198,47 @@ def test_bitmap_words_shared_with_neighbours(oracle, dcn, ref):
         assert sum(len(g) == 2 for g in got) > 250
 
 
+SCAN_BLOCK = 2048  # DCN_SCAN_BLOCK: reads per block of the scan of the per-read counts into place_offsets
+
+
+@pytest.fixture(scope="module")
+def scan_kinds(ref):
+    """four short reads with 0, 1, 2 and 2 placements, each with the model's (rows, read_counts), computed once"""
+    records, model, _ = ref
+    kinds = [random_reads(np.random.default_rng(983), 1, 70, 70)[0],
+             build(records, [(0, hits(30), 0, 0)])[0],
+             build(records, [(0, hits(20), 0, 0), (1, hits(15), 0, 0)])[0],
+             build(records, [(1, hits(25), 0, 1), (0, hits(12), 900, 0)])[0]]
+    want = [SW.place_split(model, r) for r in kinds]
+    assert [len(rows) for rows, _ in want] == [0, 1, 2, 2]
+    return kinds, want
+
+
+@pytest.mark.parametrize("before", (True, False))
+@pytest.mark.parametrize("n_reads", (SCAN_BLOCK - 1, SCAN_BLOCK, SCAN_BLOCK + 1, 2 * SCAN_BLOCK + 1))
+def test_offsets_across_the_scan_blocks(oracle, dcn, ref, scan_kinds, n_reads, before):
+    """13. place_offsets where the scan over reads changes block (2,048 reads each) and at its last, partial block: the
+    placements either all lie before read 2,047, so that every offset from the first block's last read on is the total,
+    or they begin at read 2,047, so that the first block's sum is 0 but for its last read and the later blocks carry
+    the prefix.  Offsets, rows and read_counts are the model's, expanded from one run per distinct read"""
+    kinds, want = scan_kinds
+    edge = SCAN_BLOCK - 1
+    which = [(1 + i % 3 if (i < edge) == before else 0) for i in range(n_reads)]
+    w_off, w_rows, w_counts = [0], [], []
+    for kind in which:
+        w_rows += want[kind][0]
+        w_counts.append(want[kind][1])
+        w_off.append(len(w_rows))
+    assert (w_off[edge] == w_off[-1] and w_off[-1] > 0) if before else (w_off[edge] == 0 and (n_reads == edge or w_off[-1] > 0))
+    b, o = oracle.concat_reads([kinds[kind] for kind in which])
+    p = dcn.Placer(ref[2], max_batch_bases=1 << 20, max_batch_reads=1 << 13)
+    try:
+        got = p.place_split_batch(b, o, max_placements=4)
+    finally:
+        p.close()
+    SW.assert_split(got, (w_off, w_rows, w_counts), (n_reads, before))
+
+
 def run_worker(case, **env):
     p = subprocess.run([sys.executable, WORKER, case], capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
     print(p.stdout, p.stderr)
