@@ -203,6 +203,7 @@ _SIGNATURES = {
     "dcn_filter_batch_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32,
                                           C.POINTER(Params), _vp, _vp, _vp]),
     "dcn_ctx_synchronize": (C.c_int, [_vp]),
+    "dcn_ctx_last_batch_short": (C.c_int, [_vp, _u32p]),
     "dcn_ctx_reserve_records": (C.c_int, [_vp, C.c_uint64]),
     "dcn_ctx_stream": (_vp, [_vp]),
     "dcn_host_alloc": (C.c_int, [C.c_uint64, C.POINTER(_vp)]),
@@ -250,7 +251,7 @@ _SIGNATURES = {
 }
 
 _lib = None
-ABI = (1, 11)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 12)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

@@ -209,6 +209,10 @@ int enqueue_batch(dcn_ctx *c, const BatchView &v, const dcn_params *params, bool
     uint32_t *packed = v.d_packed + DCN_FRONT_PAD, *invmask = v.d_invmask + DCN_FRONT_PAD;
     int ahead_buf = -1;
     const uint32_t *newline_flag = nullptr;
+    bool short_fused = false;
+    static const bool no_early_out = getenv("DCN_NO_EARLY_OUT") != nullptr, no_early_out_pairs = getenv("DCN_NO_EARLY_OUT_PAIRS") != nullptr;
+    // (the decisions-only instantiation of the scan kernel has no short path)
+    const bool decisions_only_call = !v.d_hits && !v.d_total && params->abs_threshold >= 1 && params->abs_threshold <= 4 && !no_early_out;
     // (per-stage profiling wants the stages one after the other on one stream: in line then)
     if (v.d_ascii && pack_ahead && c->profiling != 1 && ensure_pack_ahead(c)) {
         ahead_buf = c->pack_buf;
@@ -229,6 +233,12 @@ int enqueue_batch(dcn_ctx *c, const BatchView &v, const dcn_params *params, bool
         DCN_HIP(hipStreamWaitEvent(st, c->pack_done[ahead_buf], 0));
         newline_flag = &ps->any_newline;
     } else if (v.d_ascii) {
+        // a batch that may be all short reads: the shape kernel decides on the device, and if it says so the pack kernel below
+        // returns at once and the scan kernel packs its own bases (scan.hip, scan_short).  Everything else is the classic path.
+        short_fused = c->short_fused && !v.d_unit_id && params->prefix_length == 0 && v.b0 == 0 && v.b1 == v.stream_bases &&
+                      v.n_reads == v.n_units && c->tile_windows >= dcn_short_lmax() && idx->variant == DCN_VARIANT_DEFAULT &&
+                      dcn_scan_has_short_path(idx->k, idx->w) && !decisions_only_call;
+        if (short_fused) DCN_TRY(dcn_launch_shape(v.d_offsets, v.n_reads, v.stream_bases, dcn_short_lmax(), c->d_status, st));
         DCN_TRY(dcn_launch_pack(v.d_ascii, v.b0, v.b1, packed, invmask, c->d_status, st));
     }
     DCN_PROF_MARK(DCN_STAGE_PACK);
@@ -257,8 +267,7 @@ int enqueue_batch(dcn_ctx *c, const BatchView &v, const dcn_params *params, bool
     // decisions only: largest list length whose required hits still equal abs_threshold (dcn_required_hits is
     // monotone in the total); the scan kernel's lanes then stop at abs_threshold distinct hits (scan.hip)
     sa.early_out_max_items = 0;
-    static const bool no_early_out = getenv("DCN_NO_EARLY_OUT") != nullptr, no_early_out_pairs = getenv("DCN_NO_EARLY_OUT_PAIRS") != nullptr;
-    if (!v.d_hits && !v.d_total && params->abs_threshold >= 1 && params->abs_threshold <= 4 && !no_early_out) {
+    if (decisions_only_call) {
         uint32_t lo = 0, hi = 65535; // required(lo) == abs always holds for lo = 0
         while (lo < hi) {
             uint32_t mid = (lo + hi + 1) / 2;
@@ -281,6 +290,7 @@ int enqueue_batch(dcn_ctx *c, const BatchView &v, const dcn_params *params, bool
     sa.tile_hits = c->d_tile_hits;
     sa.pending = c->d_pending;
     sa.status = c->d_status;
+    sa.ascii = short_fused ? v.d_ascii : nullptr;
     DCN_TRY(dcn_launch_scan(sa, tile_bound(c, n_reads, v.b1 - v.b0), false, st));
     DCN_PROF_MARK(DCN_STAGE_SCAN);
 
@@ -343,6 +353,7 @@ int sync_and_check(dcn_ctx *c, uint64_t *needed_records) {
     if (!c->batch_pending) return DCN_OK;
     c->batch_pending = false;
     DCN_HIP(hipMemcpy(c->h_report, c->d_report, sizeof(dcn_batch_report), hipMemcpyDeviceToHost));
+    c->last_batch_short = c->h_report->short_batch != 0;
     if (c->h_report->bounds) {
         DCN_HIP(hipMemsetAsync(c->d_report, 0, offsetof(dcn_batch_report, stats), c->stream));
         return dcn_fail(DCN_ERR_INTERNAL, "scan kernel: index out of range in phase B (DCN_DEBUG_BOUNDS build)");
@@ -730,6 +741,7 @@ extern "C" int dcn_ctx_create(const dcn_index *index, uint64_t max_batch_bases, 
     // complexity sequence ties its way to a hit in every window or two (leftmost / rightmost alternate); from w <= 7 on
     // (2 / (w + 1) >= 1/4) the context starts with one slot per window instead of finding out in mid-run
     if (index->w <= 7) c->rec_shift = 0;
+    c->short_fused = getenv("DCN_NO_SHORT_FUSED") == nullptr; // (A/B baseline and escape hatch: every batch takes the classic path)
     if (const char *rs = getenv("DCN_REC_SHIFT")) c->rec_shift = (uint32_t)std::min(3, std::max(0, atoi(rs)));
     uint64_t MR = max_batch_reads;
     // DCN_CTX_SLAB=1 (experiment, profiles/placement_order.py): the fixed-size buffers below come out of ONE allocation,
@@ -821,6 +833,12 @@ extern "C" int dcn_ctx_reserve_records(dcn_ctx *ctx, uint64_t n_records) {
     DCN_HIP(hipStreamSynchronize(ctx->stream));
     if (n_records <= ctx->rec_capacity) return DCN_OK;
     return alloc_records(ctx, n_records);
+}
+
+extern "C" int dcn_ctx_last_batch_short(dcn_ctx *ctx, uint32_t *was_short) {
+    if (!ctx || !was_short) return dcn_fail(DCN_ERR_ARG, "ctx/was_short is NULL");
+    *was_short = ctx->last_batch_short ? 1u : 0u;
+    return DCN_OK;
 }
 
 extern "C" int dcn_ctx_synchronize(dcn_ctx *ctx) {

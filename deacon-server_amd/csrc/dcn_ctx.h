@@ -122,6 +122,8 @@ struct dcn_ctx {
     uint64_t rec_capacity = 0;
     uint64_t *d_set_slots = nullptr;
     dcn_status *d_status = nullptr;
+    bool short_fused = true;       // DCN_NO_SHORT_FUSED unset: batches of short unpaired reads are packed inside the scan kernel
+    bool last_batch_short = false; // ... and whether the last batch waited for was one (dcn_ctx_last_batch_short)
     dcn_batch_report *d_report = nullptr; // device-pointer API: counters + sticky overflow since the last synchronize
     dcn_batch_report *h_report = nullptr; // page-locked
     uint64_t host_stats[DCN_N_STATS] = {}; // counters of completed host batches

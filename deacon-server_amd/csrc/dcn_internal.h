@@ -168,6 +168,11 @@ struct dcn_status {
     uint32_t bounds;               // DCN_DEBUG_BOUNDS builds: phase B met an index outside its list / its stream
     uint32_t run_overflow;         // a unit had more hits in one wave than its run of the record array holds (rec_shift > 0)
     uint32_t bad_offsets;          // the plan kernel met offsets[r] > offsets[r+1] or offsets[r+1] > n_bases: those reads were planned as empty
+    uint32_t short_batch;          // the shape kernel (plan.hip) found good offsets and no read above DCN_SHORT_LMAX bases: the pack
+                                   // kernel returns at once and the scan kernel packs its own bases (scan.hip, scan_short)
+    uint32_t shape_bad;            // ... its workgroups' verdicts: a read too long, or an offset out of order or range
+    uint32_t shape_done;           // ... and how many of them have given theirs (the last one writes short_batch)
+    uint32_t reserved_;
     unsigned long long set_cursor; // distinct pass: slots handed out to the global per-unit hash sets
 };
 
@@ -179,7 +184,7 @@ struct dcn_batch_report {
                                            // scratch was too small; bit 1: a run of the record array was (rec_shift > 0)
     uint32_t bounds;                       // DCN_DEBUG_BOUNDS builds only: the scan kernel refused an out-of-range index
     uint32_t bad_offsets;                  // the offsets array was not non-decreasing within [0, n_bases] when the plan kernel read it
-    uint32_t reserved_;
+    uint32_t short_batch;                  // dcn_status::short_batch of the batch whose finish kernel ran last
     unsigned long long need;               // record capacity (set slots / 4) that would have sufficed
     unsigned long long stats[DCN_N_STATS]; // the six ProcessingStats counters
 };
@@ -230,6 +235,8 @@ struct dcn_scan_args {
     uint32_t nt_rot;         // ntHash rotation per base (1)
     uint32_t cmp_mask;       // hash bits that are compared (0xFFFF0000)
     uint32_t nt_combine_xor; // 0: fw + rc, 1: fw ^ rc
+    // short path (scan.hip, scan_short): the batch's ASCII, set only when a shape kernel ran in front of the pack; null otherwise
+    const uint8_t *ascii;
 };
 
 // ---- kernels launched by ctx.hip, dump.hip and classify_api.hip ------------------------------------
@@ -242,6 +249,13 @@ int dcn_launch_pack(const uint8_t *d_ascii, uint64_t base_begin, uint64_t base_e
 int dcn_launch_pack_beside(const uint8_t *d_ascii, uint64_t base_begin, uint64_t base_end, uint32_t *d_packed, uint32_t *d_invmask,
                            dcn_status *status, hipStream_t stream);
 int dcn_launch_scan(const dcn_scan_args &args, uint32_t max_tiles, bool dump, hipStream_t stream);
+// the scan kernel for (k, w) has the short path, which takes batches of reads of at most dcn_short_lmax() bases
+bool dcn_scan_has_short_path(uint32_t k, uint32_t w);
+uint32_t dcn_short_lmax();
+// one pass over the offsets: status->short_batch = 1 iff they are non-decreasing within [0, stream_bases] and no read is
+// longer than lmax bases (plan.hip).  The status words are zero when it runs.
+int dcn_launch_shape(const uint64_t *d_offsets, uint32_t n_reads, uint64_t stream_bases, uint32_t lmax, dcn_status *status,
+                     hipStream_t stream);
 
 int dcn_table_build(dcn_index *idx, const uint64_t *host_keys, uint64_t n);
 int dcn_table_contains(const dcn_index *idx, const uint64_t *host_keys, uint64_t n, uint8_t *out);

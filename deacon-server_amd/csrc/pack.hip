@@ -8,16 +8,11 @@
 // batch is bits [2(i%16), 2(i%16)+2) of packed[i/16] and bit i%32 of invmask[i/32]; no kernel here
 // needs to know where reads begin.  HBM-bound: 1 B/bp read, 0.375 B/bp written.
 #include "dcn_internal.h"
+#include "dcn_pack.h"
 
 #include <algorithm>
 
 namespace {
-
-__device__ inline uint32_t pack4(uint32_t x) {
-    // 4 ASCII bytes -> 8 bits of 2-bit codes (byte 0 in bits 0..1)
-    uint32_t y = (x >> 1) & 0x03030303u;
-    return (y * ((1u << 24) | (1u << 18) | (1u << 12) | (1u << 6))) >> 24;
-}
 
 // index-side code (src/minimizers.rs:24-43 canonicalise_nucleotide, then the same (c >> 1) & 3):
 // A,W -> A=0; T -> T=2; G,R,S,K,D,V -> G=3; everything else (C,Y,M,B,H,N,...) -> C=1; case-insensitive
@@ -36,19 +31,6 @@ __device__ inline uint32_t pack4_index_side(uint32_t x) {
     return out;
 }
 
-__device__ inline uint32_t invalid4(uint32_t x) {
-    // 4 ASCII bytes -> 4 bits, bit j = byte j is not in ACGTacgt.  All four bytes at once: with y = byte | 0x20 and
-    // T = y.bit2 & ~y.bit1 (set for 't' only among a c g t), a valid byte is 0 1 1 T 0 y2 y1 ~T -- bits 1 and 2 are
-    // free (they are the 2-bit code), every other bit is fixed by them.  17 instructions instead of 4 x 10: this
-    // kernel was bound by its compares (12 VALU instructions per base), not by HBM.
-    const uint32_t y = x | 0x20202020u;
-    const uint32_t T = (y >> 2) & ~(y >> 1) & 0x01010101u;
-    const uint32_t expect = 0x60606060u | (T << 4) | (T ^ 0x01010101u);
-    const uint32_t diff = (y & 0xF9F9F9F9u) ^ expect;                       // non-zero byte <=> invalid byte
-    const uint32_t nz = ((diff & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | diff;        // bit 7 of each byte: byte != 0 (no carries across bytes)
-    return (((nz >> 7) & 0x01010101u) * 0x01020408u) >> 24;                 // bits 0,8,16,24 -> bits 0..3
-}
-
 // each thread packs 32 bases: two packed words and one mask word.  Groups [g_first, g_first + n_chunks) of the
 // stream are packed (a chunk of a larger batch starts at any group); bytes at or past n_bases read as 'A'.
 template <bool ALIGNED, bool INDEX_SIDE>
@@ -56,6 +38,8 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ a
                                                    uint32_t *__restrict__ packed,
                                                    uint32_t *__restrict__ invmask, uint64_t g_first, uint64_t n_chunks,
                                                    dcn_status *status) {
+    // a short batch (the shape kernel, plan.hip): the scan kernel packs its own bases, nothing is read here and any_newline stays 0
+    if (!INDEX_SIDE && status && status->short_batch) return;
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     uint32_t nl = 0;
     for (uint64_t t = g_first + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < g_first + n_chunks; t += stride) {
@@ -83,11 +67,11 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ a
         uint32_t p0 = 0, p1 = 0, m = 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            p0 |= (INDEX_SIDE ? pack4_index_side(w[q]) : pack4(w[q])) << (8 * q);
-            p1 |= (INDEX_SIDE ? pack4_index_side(w[q + 4]) : pack4(w[q + 4])) << (8 * q);
+            p0 |= (INDEX_SIDE ? pack4_index_side(w[q]) : dcn_pack4(w[q])) << (8 * q);
+            p1 |= (INDEX_SIDE ? pack4_index_side(w[q + 4]) : dcn_pack4(w[q + 4])) << (8 * q);
         }
 #pragma unroll
-        for (int q = 0; q < 8; ++q) m |= invalid4(w[q]) << (4 * q);
+        for (int q = 0; q < 8; ++q) m |= dcn_invalid4(w[q]) << (4 * q);
         if (!INDEX_SIDE && m) {
             // any '\n' byte in the batch?  It is an invalid byte, so only groups with one are looked at:
             // (x ^ 0x0A..) has a zero byte <=> some byte of x is '\n'
@@ -117,8 +101,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(32))) void pack1
     uint16_t *mask16 = reinterpret_cast<uint16_t *>(invmask);
     for (uint32_t t = h_first + blockIdx.x * 64u + threadIdx.x; t < h_end; t += stride) { // whole 16-base pieces only
         const uint4 a = *reinterpret_cast<const uint4 *>(ascii + (uint64_t)t * 16);
-        const uint32_t p = pack4(a.x) | (pack4(a.y) << 8) | (pack4(a.z) << 16) | (pack4(a.w) << 24);
-        const uint32_t m = invalid4(a.x) | (invalid4(a.y) << 4) | (invalid4(a.z) << 8) | (invalid4(a.w) << 12);
+        const uint32_t p = dcn_pack4(a.x) | (dcn_pack4(a.y) << 8) | (dcn_pack4(a.z) << 16) | (dcn_pack4(a.w) << 24);
+        const uint32_t m = dcn_invalid4(a.x) | (dcn_invalid4(a.y) << 4) | (dcn_invalid4(a.z) << 8) | (dcn_invalid4(a.w) << 12);
         if (m) {
             uint32_t z = a.x ^ 0x0A0A0A0Au;
             nl |= (z - 0x01010101u) & ~z & 0x80808080u;

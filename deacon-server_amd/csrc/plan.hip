@@ -193,6 +193,37 @@ __global__ __launch_bounds__(256) void plan_kernel(dcn_plan_args a) {
     }
 }
 
+// ---- the batch's shape: may the scan kernel pack this batch's bases itself? (scan.hip, scan_short) ----------------------
+// One grid-stride pass over the offsets, in front of the pack kernel.  It checks what plan_kernel's check_offsets checks
+// (bad offsets leave short_batch 0, and the classic path reports them) and that no read is longer than lmax.  The workgroup
+// that gives its verdict last writes the word.
+__global__ __launch_bounds__(256) void shape_kernel(const uint64_t *__restrict__ offsets, uint32_t n_reads, uint64_t stream_bases,
+                                                    uint32_t lmax, dcn_status *status) {
+    bool bad = false;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t r0 = blockIdx.x * blockDim.x + threadIdx.x; r0 < n_reads; r0 += 4 * stride) {
+        uint64_t off[4], end[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t r = r0 + q * stride;
+            off[q] = end[q] = 0;
+            if (r < n_reads && r >= r0) { // (r >= r0: no wrap of the index)
+                off[q] = offsets[r];
+                end[q] = offsets[r + 1];
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bad |= end[q] < off[q] || end[q] > stream_bases || end[q] - off[q] > lmax;
+    }
+    const int any_bad = __syncthreads_or(bad ? 1 : 0);
+    if (threadIdx.x == 0) {
+        if (any_bad) atomicOr(&status->shape_bad, 1u);
+        __threadfence(); // the verdict before the ticket
+        const bool last = atomicAdd(&status->shape_done, 1u) == gridDim.x - 1;
+        if (last && atomicOr(&status->shape_bad, 0u) == 0u) status->short_batch = 1;
+    }
+}
+
 // ---- exact distinct-hit count of the units the scan kernel did not finish ------------------------------------
 // (long reads, pairs cut by a wave boundary, units with more hits than the in-wave ring holds.)  The scan kernel left
 // every such unit's hits as runs in the record array (scan.hip): the run of (wave, unit) starts at slot
@@ -508,6 +539,7 @@ __global__ __launch_bounds__(256) void finish_kernel(dcn_finish_args a) {
         }
     }
     if (a.status->bounds && blockIdx.x == 0 && threadIdx.x == 0) a.report->bounds = a.status->bounds;
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.report->short_batch = a.status->short_batch; // (dcn_ctx_last_batch_short)
     if (a.status->bad_offsets) {
         if (blockIdx.x == 0 && threadIdx.x == 0) a.report->bad_offsets = 1;
         return; // (the counters would be sums over those offsets)
@@ -599,6 +631,14 @@ int dcn_launch_plan(const dcn_plan_args &a, hipStream_t stream) {
         hipLaunchKernelGGL(plan_kernel<8>, dim3((a.n_reads + 2047) / 2048), dim3(256), 0, stream, a);
     else
         hipLaunchKernelGGL(plan_kernel<1>, dim3((a.n_reads + 255) / 256), dim3(256), 0, stream, a);
+    DCN_HIP(hipGetLastError());
+    return DCN_OK;
+}
+
+int dcn_launch_shape(const uint64_t *d_offsets, uint32_t n_reads, uint64_t stream_bases, uint32_t lmax, dcn_status *status,
+                     hipStream_t stream) {
+    hipLaunchKernelGGL(shape_kernel, dim3(blocks_for((n_reads + 3) / 4, 2048)), dim3(256), 0, stream, d_offsets, n_reads, stream_bases,
+                       lmax, status);
     DCN_HIP(hipGetLastError());
     return DCN_OK;
 }

@@ -26,7 +26,10 @@
 #include "dcn_internal.h"
 #include "dcn_probe.h"
 
+#include "dcn_pack.h"
+
 #include <atomic>
+#include <type_traits>
 
 namespace {
 
@@ -126,6 +129,51 @@ struct WaveShared {
     uint8_t lok[DCN_WAVE];              // unit slot is being resolved inside this wave
 };
 
+// The LDS of the short path (scan_short below): a batch of single-tile reads whose ASCII the wave packs itself.  The 2-bit
+// words and mask bits of the wave's reads live in a staging area; a tile-relative position fits a byte, and the three
+// per-slot words of a unit's exported run (its base, its capacity, both functions of the owner lane's tile) are looked up
+// where a run is written instead of being kept here.  Same total as WaveShared, so the waves per CU do not move.
+constexpr int DCN_SHORT_LMAX = 152;   // longest read of a short batch (dcn_launch_shape)
+constexpr int DCN_STAGE_WORDS = 612;  // 16-base words: 64 reads of DCN_SHORT_LMAX bases, a lead-in of w-1, two cut chunks
+constexpr int DCN_LSTRIDE8 = 44;      // u8 entries per list row: DCN_LCAP + 4, 11 dwords
+static_assert(DCN_LSTRIDE8 >= DCN_LCAP + 2 && (DCN_LSTRIDE8 / 4) % 2 == 1 && DCN_LSTRIDE8 % 4 == 0, "odd dword stride");
+static_assert(DCN_STAGE_WORDS % 2 == 0 && 16 * DCN_STAGE_WORDS >= 64 * DCN_SHORT_LMAX + 14 + 30, "one pass per full wave");
+
+struct WaveSharedShort {
+    uint4 tab[16];
+    // phase A over-reads a lane's stream by up to the wave's longest tile plus two blocks (as the classic path does into the
+    // tail pad): behind stage_p that is stage_m and the list, never the end of the struct
+    uint32_t stage_p[DCN_STAGE_WORDS];  // 2-bit codes, 16 bases per word: word x is 16-byte chunk x of the wave's runs
+    union {
+        uint32_t stage_m[DCN_STAGE_WORDS / 2 + 2]; // invalid-base bits, 32 bases per word
+        uint16_t stage_m16[DCN_STAGE_WORDS + 4];   // ... as written: 16 bits per chunk
+    };
+#if DCN_LIST_BY_LANE
+    uint8_t list[DCN_WAVE][DCN_LSTRIDE8];
+#else
+    uint8_t list[DCN_LCAP + 2][DCN_WAVE];
+#endif
+    uint64_t ring_hash[DCN_RCAP];
+    uint32_t total[DCN_WAVE];
+    uint32_t hits[DCN_WAVE];
+    uint32_t items[DCN_WAVE];
+    uint32_t unit_of[DCN_WAVE];
+    uint16_t start[DCN_WAVE + 2];
+    uint8_t hraw[DCN_WAVE];             // (at most DCN_SHORT_LMAX hits)
+    uint8_t uhits[DCN_WAVE];
+    uint8_t local[DCN_WAVE];
+    uint8_t lok[DCN_WAVE];
+};
+static_assert(sizeof(WaveSharedShort) <= 10240 && sizeof(WaveShared) <= 10240, "16 one-wave workgroups per CU of 160 KB");
+
+// what scan_short hands to the scan proper for one lane
+struct ShortLane {
+    int lane;         // threadIdx.x, as a value the compiler takes for one of this pass
+    bool have;        // the lane scans a tile in this pass
+    dcn_tile t;       // ... this one, its window count corrected for a trailing '\n'
+    uint32_t s_local; // position of t.scan_start in the staging area, in bases
+};
+
 #ifndef DCN_EXP
 #define DCN_EXP 0 // experiment bits (timing-only builds, results wrong): 1 = no set probe, 2 = no phase B,
                   // 4 = no list store, 8 = no duplicate compare, 16 = no mask loads,
@@ -170,13 +218,15 @@ struct IntTag {
 // hash bits compared and the fw/rc combination are run-time values and the window keys are 64 bits wide (hash bits
 // above, position below).  Only instantiated for W == 0; the default rules never take it, so the kernels above are
 // the same code with or without it.
-template <int W, bool K128, bool DUMP, bool FAST, bool VAR = false>
-__global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES) void scan_kernel(dcn_scan_args a) {
+// SHORT: the wave was set up by scan_short (below): `sl` holds the lane's tile, and the stream and mask words come from the
+// staging area in `sh` (a WaveSharedShort) at positions relative to it instead of from a.packed / a.invmask.
+template <int W, bool K128, bool DUMP, bool FAST, bool VAR, bool SHORT, class SH>
+__device__ __forceinline__ void scan_body(const dcn_scan_args &a, SH &sh, const ShortLane &sl) {
     static_assert(!VAR || (W == 0 && !FAST), "the variant path is the generic-w counting / dump kernel");
-    __shared__ WaveShared sh;
+    static_assert(!SHORT || (W > 0 && !K128 && !DUMP && !FAST && !VAR), "the short path is a counting kernel of fixed w, k <= 32");
     extern __shared__ __align__(16) uint2 dyn_ring[]; // only for W == 0: [w][64] (lkey, rkey); VAR: [w][64] of two u64 keys
 
-    const int lane = threadIdx.x;
+    const int lane = SHORT ? sl.lane : (int)threadIdx.x;
     // (bad_offsets: the plan kernel refused the batch's offsets -- ctx.hip reports it at the next synchronize; its tiles are not looked at)
     const uint32_t NT = a.status->bad_offsets ? 0u : *a.n_tiles;
     const uint32_t wave_first = blockIdx.x * DCN_WAVE;
@@ -187,8 +237,10 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
 
     // ---- tile descriptors, unit slots -----------------------------------------------------------------
     const uint32_t tile_idx = wave_first + lane;
-    const bool have_tile = tile_idx < NT;
-    dcn_tile t = a.tiles[have_tile ? tile_idx : NT - 1];
+    const bool have_tile = SHORT ? sl.have : tile_idx < NT;
+    dcn_tile t;
+    if constexpr (SHORT) t = sl.t;
+    else t = a.tiles[have_tile ? tile_idx : NT - 1];
     if (!have_tile) t.nwf = 0;
     const uint32_t carry = t.carry();
     const uint32_t nwc = t.n_windows() ? t.n_windows() + carry : 0; // windows this lane evaluates
@@ -199,19 +251,20 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
     // block's range, but the ranges of different blocks are placed in whatever order their cursor atomics ran: a unit
     // of three or more reads cut by a block boundary can meet itself again with the later reads first.  Such a lane
     // starts a new slot (and a new run of the record array: a run may only grow over windows that lie behind it).
-    const bool head = lane == 0 || t.unit != unit_prev || t.scan_start < start_prev;
+    // (SHORT: every tile is a unit of its own, and the lanes of a pass need not start at lane 0: slot = lane)
+    const bool head = SHORT ? have_tile : (lane == 0 || t.unit != unit_prev || t.scan_start < start_prev);
     const unsigned long long head_mask = __ballot(head);
-    const uint32_t uslot = (uint32_t)__popcll(head_mask & ((2ull << lane) - 1)) - 1;
+    const uint32_t uslot = SHORT ? (uint32_t)lane : (uint32_t)__popcll(head_mask & ((2ull << lane) - 1)) - 1;
     sh.total[lane] = 0;
     sh.hits[lane] = 0;
     sh.items[lane] = 0;
     sh.hraw[lane] = 0;
     sh.lok[lane] = 0;
     sh.uhits[lane] = 0;
-    sh.ucap[lane] = 0;
+    if constexpr (!SHORT) sh.ucap[lane] = 0;
     if (head) {
         sh.unit_of[uslot] = t.unit;
-        sh.run_base[uslot] = (t.scan_start + carry) >> a.rec_shift;
+        if constexpr (!SHORT) sh.run_base[uslot] = (t.scan_start + carry) >> a.rec_shift;
         bool loc = false;
         if (!DUMP) {
             if (t.whole_unit()) { // the unit's only tile is this lane's
@@ -235,7 +288,7 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
         sh.tab[lane] = e;
     }
     __syncthreads();
-    if (!DUMP) {
+    if constexpr (!DUMP && !SHORT) {
         // A unit's run of the record array starts at the slot of its first window in this wave and may grow up to the slot of
         // its last: with one slot per 2^rec_shift windows it holds that many times fewer hits than the unit has windows
         // here, which real sequence never fills (one minimizer per ~8 windows) -- a run that would is refused and the
@@ -251,8 +304,31 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
         __syncthreads();
     }
 
-    const uint32_t *packed = a.packed;
-    const int64_t s = (int64_t)t.scan_start;
+    // word i of the 2-bit stream / of the mask
+    auto PK = [&](int64_t i) -> uint32_t {
+        if constexpr (SHORT) return sh.stage_p[(uint32_t)i];
+        else return a.packed[i];
+    };
+    auto MK = [&](uint64_t i) -> uint32_t {
+        if constexpr (SHORT) return sh.stage_m[(uint32_t)i];
+        else return a.invmask[i];
+    };
+    const int64_t s = SHORT ? (int64_t)sl.s_local : (int64_t)t.scan_start;
+    // SHORT: a unit's run of the record array (mid-scan flush, or more hits than the ring holds) is described by its owner
+    // lane's tile, read again where a run is written, which is rare
+    auto run_cap = [&](uint32_t us, uint32_t us_windows) -> uint32_t {
+        if constexpr (SHORT) {
+            const uint64_t first_win = a.tiles[wave_first + us].scan_start;
+            return (uint32_t)(((first_win + us_windows + l - 1) >> a.rec_shift) - (first_win >> a.rec_shift));
+        } else {
+            return sh.ucap[us];
+        }
+    };
+    auto run_slot0 = [&](uint32_t us) -> uint64_t {
+        if constexpr (SHORT) return a.tiles[wave_first + us].scan_start >> a.rec_shift;
+        else return sh.run_base[us];
+    };
+    [[maybe_unused]] const uint64_t p_limit = SHORT ? (uint64_t)16 * DCN_STAGE_WORDS : a.stream_bases; // (DCN_DEBUG_BOUNDS)
 
     // ---- prologue: first k-1 bases (no complete k-mer yet) -------------------------------------------------
     // fw / rc hold the hashes BEFORE the removal of the outgoing base; the removal terms of a step are folded
@@ -263,7 +339,7 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
         const uint32_t sh_in = (uint32_t)(s & 15) * 2;
         uint32_t cur = 0;
         for (uint32_t tt = 0; tt + 1 < k; ++tt) {
-            if ((tt & 15) == 0) cur = __funnelshift_r(packed[q_in + (tt >> 4)], packed[q_in + (tt >> 4) + 1], sh_in);
+            if ((tt & 15) == 0) cur = __funnelshift_r(PK(q_in + (tt >> 4)), PK(q_in + (tt >> 4) + 1), sh_in);
             uint32_t c = (cur >> (2 * (tt & 15))) & 3;
             uint4 e = sh.tab[c];
             fw = rotl32(fw, VAR ? ROT : 1u) ^ e.x;
@@ -347,19 +423,17 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
             it.o_uslot = o_pk & 0xFFu;
             it.p = (uint64_t)(o_s + it.rel);
 #ifdef DCN_DEBUG_BOUNDS
-            if (it.act && it.p + k > a.stream_bases) {
+            if (it.act && it.p + k > p_limit) {
                 a.status->bounds = 2;
                 it.act = false;
                 it.p = 0;
             }
 #endif
             if (it.act) {
-                const uint32_t *mp = a.invmask + (it.p >> 5);
-                const uint32_t *pp = packed + (it.p >> 4);
 #pragma unroll
-                for (int q = 0; q < NMW; ++q) it.mw[q] = mp[q];
+                for (int q = 0; q < NMW; ++q) it.mw[q] = MK((it.p >> 5) + q);
 #pragma unroll
-                for (int q = 0; q < NPW; ++q) it.pw[q] = pp[q];
+                for (int q = 0; q < NPW; ++q) it.pw[q] = PK((int64_t)(it.p >> 4) + q);
             }
         };
         Item cur, nxt;
@@ -423,7 +497,7 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
                 o_uslot[u] = o_pk & 0xFFu;
                 p[u] = (uint64_t)(o_s + rel[u]);
 #ifdef DCN_DEBUG_BOUNDS
-                if (act[u] && p[u] + k > a.stream_bases) { // a minimizer's k-mer lies inside its read, hence inside the stream
+                if (act[u] && p[u] + k > p_limit) { // a minimizer's k-mer lies inside its read, hence inside the stream
                     a.status->bounds = 2;
                     act[u] = false;
                     p[u] = 0;
@@ -433,12 +507,10 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
 #pragma unroll
             for (int u = 0; u < (PIPE ? 0 : U); ++u) {
                 if (act[u]) {
-                    const uint32_t *mp = a.invmask + (p[u] >> 5);
-                    const uint32_t *pp = packed + (p[u] >> 4);
 #pragma unroll
-                    for (int q = 0; q < NMW; ++q) mw[u][q] = (DCN_EXP & 16) ? 0u : mp[q];
+                    for (int q = 0; q < NMW; ++q) mw[u][q] = (DCN_EXP & 16) ? 0u : MK((p[u] >> 5) + q);
 #pragma unroll
-                    for (int q = 0; q < NPW; ++q) pw[u][q] = pp[q];
+                    for (int q = 0; q < NPW; ++q) pw[u][q] = PK((int64_t)(p[u] >> 4) + q);
                 }
             }
             bool valid[U];
@@ -610,10 +682,11 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
                         const uint32_t head_lane = hm ? 63u - (uint32_t)__clzll(hm) : 0u;
                         const uint32_t rank = (uint32_t)__popcll(below) - (uint32_t)__popcll(rb & ((1ull << head_lane) - 1));
                         any_rec = true;
+                        const uint32_t o_windows = SHORT ? __shfl(nwc, lo[u], 64) : 0u; // (outside `rec`: every lane takes part)
                         if (rec) {
                             const uint32_t at = sh.uhits[o_uslot[u]] + rank;
-                            if (at < sh.ucap[o_uslot[u]]) {
-                                if (!(DCN_EXP & 512)) a.rec_hash[sh.run_base[o_uslot[u]] + at] = hash[u];
+                            if (at < run_cap(o_uslot[u], o_windows)) {
+                                if (!(DCN_EXP & 512)) a.rec_hash[run_slot0(o_uslot[u]) + at] = hash[u];
                             } else {
                                 a.status->run_overflow = 1; // (only with rec_shift > 0; the batch is run again)
                             }
@@ -668,9 +741,9 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
     int64_t b_in = 2 * (s + (int64_t)(k - 1)), b_k = 2 * s, b_l = 2 * (s - (int64_t)(w - 1));
     int64_t wi_in = b_in >> 5, wi_k = b_k >> 5, wi_l = b_l >> 5;
     uint32_t so_in = (uint32_t)(b_in & 31), so_k = (uint32_t)(b_k & 31), so_l = (uint32_t)(b_l & 31);
-    uint32_t ra_in = packed[wi_in], rb_in = packed[wi_in + 1];
-    uint32_t ra_k = packed[wi_k], rb_k = packed[wi_k + 1];
-    uint32_t ra_l = packed[wi_l], rb_l = packed[wi_l + 1];
+    uint32_t ra_in = PK(wi_in), rb_in = PK(wi_in + 1);
+    uint32_t ra_k = PK(wi_k), rb_k = PK(wi_k + 1);
+    uint32_t ra_l = PK(wi_l), rb_l = PK(wi_l + 1);
     uint32_t w_in = __funnelshift_r(ra_in, rb_in, so_in);
     uint32_t w_k = __funnelshift_r(ra_k, rb_k, so_k);
     uint32_t w_l = __funnelshift_r(ra_l, rb_l, so_l);
@@ -682,12 +755,12 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
             ra_in = rb_in ^ 0x5A5A5A5Au; rb_in = ra_k + 0x1234567u; ra_k = rb_l; rb_k = ra_l ^ ra_in; ra_l = rb_k; rb_l = rb_in;
             return;
         }
-        ra_in = packed[wi_in]; rb_in = packed[wi_in + 1];
+        ra_in = PK(wi_in); rb_in = PK(wi_in + 1);
         if (DCN_EXP & 64) {
             ra_k = ra_in; rb_k = rb_in; ra_l = ra_in; rb_l = rb_in;
         } else {
-            ra_k = packed[wi_k]; rb_k = packed[wi_k + 1];
-            ra_l = packed[wi_l]; rb_l = packed[wi_l + 1];
+            ra_k = PK(wi_k); rb_k = PK(wi_k + 1);
+            ra_l = PK(wi_l); rb_l = PK(wi_l + 1);
         }
     };
     advance_streams(); // raw words of block 1 in flight
@@ -700,7 +773,7 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
         } else {
             for (uint32_t b = 1; b < w; ++b) {
                 int64_t p = s - (int64_t)b;
-                tg += (packed[p >> 4] >> (2 * (uint32_t)(p & 15) + 1)) & 1u;
+                tg += (PK(p >> 4) >> (2 * (uint32_t)(p & 15) + 1)) & 1u;
             }
         }
     }
@@ -796,7 +869,7 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
                     // FIRST: window 0, always emitted (a carry tile's copy is dropped in phase B);
                     // later blocks: window j-(w-1) >= 1, emitted when in range and different from its predecessor
                     const bool emit = FIRST ? (nwc > 0) : ((j - (w - 1) < nwc) && sel != prev);
-                    if (!(DCN_EXP & 4)) sh.DCN_LIST_AT(lane, cnt) = (uint16_t)sel;
+                    if (!(DCN_EXP & 4)) sh.DCN_LIST_AT(lane, cnt) = (std::remove_reference_t<decltype(sh.list[0][0])>)sel;
                     cnt += emit ? 1u : 0u;
                     prev = sel;
                 }
@@ -856,7 +929,7 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
                 hash = 0;
                 if (actv) {
                     const uint32_t *mp = a.invmask + (p >> 5);
-                    const uint32_t *pp = packed + (p >> 4);
+                    const uint32_t *pp = a.packed + (p >> 4);
                     const uint32_t m0 = mp[0], m1 = mp[1], m2 = K128 ? mp[2] : 0u;
                     uint32_t pw[K128 ? 5 : 3];
 #pragma unroll
@@ -1013,6 +1086,140 @@ __global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES
     }
 }
 
+// ---- the short path: a batch of single-tile reads, packed by the wave that scans them -------------------------------
+// dcn_status::short_batch (the shape kernel, plan.hip): every read of the batch has at most DCN_SHORT_LMAX bases, the pack
+// kernel did not run, and the plan ran without newline knowledge.  The wave's 64 tiles are 64 whole reads.  Tiles follow the
+// stream inside a planning block's range, reads without a tile leave gaps, and the ranges of different blocks lie in any
+// order: the lanes form RUNS of tiles that are (nearly) contiguous in the stream, almost always one.  Each run's ASCII span
+// [first scan_start - (w-1), last read's end) is loaded as whole 16-byte chunks of the address space (the base pointer may
+// have any alignment), packed, and written to the staging area, one 2-bit word and 16 mask bits per chunk; the scan then
+// works on positions relative to the staging area.  Lanes whose runs do not fit the staging area together (many runs: a
+// batch of mostly tile-less reads) are scanned in a further pass of the same code, so any wave is handled.
+template <int W>
+__device__ __forceinline__ void scan_short(const dcn_scan_args &a, WaveSharedShort &sh) {
+    const uint32_t NT = a.status->bad_offsets ? 0u : *a.n_tiles;
+    const uint32_t wave_first = blockIdx.x * DCN_WAVE;
+    if (wave_first >= NT) return;
+    const uint32_t n_have = min(NT - wave_first, (uint32_t)DCN_WAVE);
+    const uint32_t l = a.k + W - 1;
+    const uint64_t n_bases = a.stream_bases;
+    const uint64_t a16 = reinterpret_cast<uintptr_t>(a.ascii) & 15;
+    const uint8_t *abase = a.ascii - a16; // chunk c = the 16 bytes at abase + 16 c; stream base p lies in chunk (a16 + p) >> 4
+
+    // 16 bases of the stream: bytes in front of it read as 0, bytes behind it as 'A' (as pack_kernel packs them)
+    auto load_chunk = [&](int64_t c) -> uint4 {
+        const int64_t b0 = 16 * c - (int64_t)a16;
+        if (b0 >= 0 && (uint64_t)b0 + 16 <= n_bases) return *reinterpret_cast<const uint4 *>(abase + 16 * c);
+        uint32_t v[4] = {0, 0, 0, 0};
+        for (int j = 0; j < 16; ++j) {
+            const int64_t p = b0 + j;
+            const uint32_t byte = p < 0 ? 0u : ((uint64_t)p < n_bases ? (uint32_t)a.ascii[p] : (uint32_t)'A');
+            v[j >> 2] |= byte << (8 * (j & 3));
+        }
+        return make_uint4(v[0], v[1], v[2], v[3]);
+    };
+
+    constexpr int64_t GAP_CHUNKS = 2; // a gap of up to two chunks is staged with its run: cheaper than a run's own lead-in
+    for (uint32_t lo = 0; lo < n_have;) { // wave-uniform; one pass unless the runs outgrow the staging area
+        // The lane's tile and what follows from it are read again in every pass, and the lane number is a fresh value in each:
+        // otherwise everything the scan derives from the lane alone (a dozen masks and LDS addresses) is computed in front
+        // of this loop and held in registers across it, which the scan's phase A has no room for.  Measured on this kernel
+        // (profiles/short_fused_isa.txt): with the empty asm no VGPR spill and no scratch, without it 19 spilled VGPRs and 80 B.
+        int lane = threadIdx.x;
+        asm volatile("" : "+v"(lane));
+        const bool have = (uint32_t)lane < n_have;
+        const dcn_tile t = a.tiles[wave_first + (have ? (uint32_t)lane : n_have - 1)];
+        // the plan knew of no newline: the tile ends where its read ends
+        const uint64_t start = t.scan_start, end = start + t.n_windows() + l - 1;
+        uint32_t nw = t.n_windows();
+        if (have && nw && end <= n_bases && a.ascii[end - 1] == '\n') nw -= 1; // src/filter_common.rs:229; a read left without a
+                                                                               // window keeps its lane and gets total = 0
+        const int64_t cf = ((int64_t)(a16 + start) - (int64_t)(W - 1)) >> 4; // first and last chunk of this lane's span (cf may be -1)
+        const int64_t cl = (int64_t)(a16 + end - 1) >> 4;
+        const int64_t cl_prev = __shfl_up((long long)cl, 1, 64);
+        const uint64_t start_prev = (uint64_t)__shfl_up((long long)start, 1, 64);
+        const bool in = (uint32_t)lane >= lo && have;
+        const bool newrun = (uint32_t)lane == lo || start < start_prev || cf > cl_prev + 1 + GAP_CHUNKS;
+        const int64_t cost64 = newrun ? cl - cf + 1 : cl - cl_prev;
+        const uint32_t cost = in ? (uint32_t)(cost64 > 0 ? cost64 : 0) : 0u;
+        const uint32_t incl = wave_inclusive_scan_u32(cost, lane);
+        // (a single read's span is at most (DCN_SHORT_LMAX + W - 1 + 15) / 16 + 1 chunks: lane `lo` always fits)
+        // (... and a pass always moves on by a lane, whatever the tiles say)
+        const uint32_t hi = max((uint32_t)__popcll(__ballot(have && incl <= (uint32_t)DCN_STAGE_WORDS)), lo + 1);
+        const bool act = in && (uint32_t)lane < hi && incl <= (uint32_t)DCN_STAGE_WORDS;
+        const unsigned long long heads = __ballot(act && newrun);
+        const unsigned long long mine = heads & ((2ull << lane) - 1);
+        const uint32_t head_lane = mine ? 63u - (uint32_t)__clzll(mine) : lo;
+        const uint32_t excl = incl - cost;
+        const uint32_t wb_h = __shfl(excl, head_lane, 64);
+        const int64_t cf_h = __shfl((long long)cf, head_lane, 64);
+        const uint32_t total_words = __shfl(incl, hi - 1, 64);
+        __syncthreads(); // (the previous pass has finished with the staging area)
+        for (unsigned long long rest = heads; rest;) {
+            const int h = __ffsll((long long)rest) - 1;
+            rest &= rest - 1;
+            const uint32_t wb = __shfl(excl, h, 64);
+            const int64_t c0 = __shfl((long long)cf, h, 64);
+            const uint32_t we = rest ? __shfl(excl, __ffsll((long long)rest) - 1, 64) : total_words;
+            for (uint32_t i0 = 0; i0 < we - wb; i0 += 4 * DCN_WAVE) { // four chunks per lane in flight
+                uint4 v[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const uint32_t i = i0 + q * DCN_WAVE + lane;
+                    v[q] = make_uint4(0, 0, 0, 0);
+                    if (i < we - wb) v[q] = load_chunk(c0 + i);
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const uint32_t i = i0 + q * DCN_WAVE + lane;
+                    if (i < we - wb && wb + i < (uint32_t)DCN_STAGE_WORDS) {
+                        sh.stage_p[wb + i] = dcn_pack4(v[q].x) | (dcn_pack4(v[q].y) << 8) | (dcn_pack4(v[q].z) << 16) | (dcn_pack4(v[q].w) << 24);
+                        sh.stage_m16[wb + i] = (uint16_t)(dcn_invalid4(v[q].x) | (dcn_invalid4(v[q].y) << 4) | (dcn_invalid4(v[q].z) << 8) |
+                                                          (dcn_invalid4(v[q].w) << 12));
+                    }
+                }
+            }
+        }
+        ShortLane sl;
+        sl.lane = lane;
+        sl.have = act;
+        sl.t = t;
+        sl.t.nwf = act ? ((t.nwf & 0xC0000000u) | nw) : 0u;
+        // (w-1 <= s_local, s_local + read length <= 16 * DCN_STAGE_WORDS; an idle lane scans nothing, from the area's front)
+        sl.s_local = act ? (uint32_t)((int64_t)(a16 + start) - 16 * cf_h + 16 * (int64_t)wb_h) : 16u;
+        __syncthreads();
+        scan_body<W, false, false, false, false, true>(a, sh, sl);
+        lo = hi;
+    }
+}
+
+#ifndef DCN_SHORT_FUSED
+#define DCN_SHORT_FUSED 1 // 0: no short path in any instantiation (the shape kernel is then never enqueued)
+#endif
+template <int W>
+constexpr bool dcn_scan_has_short = DCN_SHORT_FUSED && DCN_LIST_BY_LANE && !DCN_EXPORT_UNIFORM && W == 15;
+
+// SHORTK: the kernel of the short path, a launch of its own IN FRONT of the classic kernel of the same batch (launch_w): it
+// does nothing unless the shape kernel raised short_batch, and the classic kernel does nothing when it did.  Two kernels
+// because one holding both bodies costs the classic path its register allocation (128 VGPRs and 29 spilled SGPRs instead of
+// 118 and none: long reads' scan 5.3 -> 8.1 ms, profiles/short_fused_ab.txt section 4).  The grid that returns at once is not
+// free: 54 us in the kernel trace at the headline's 156 k workgroups, 21 us for the long-read leg's grid (section 5 there).
+template <int W, bool K128, bool DUMP, bool FAST, bool VAR = false, bool SHORTK = false>
+__global__ __launch_bounds__(DCN_WAVE, FAST ? DCN_MIN_WAVES_FAST : DCN_MIN_WAVES) void scan_kernel(dcn_scan_args a) {
+    if constexpr (SHORTK) {
+        static_assert(dcn_scan_has_short<W> && !K128 && !DUMP && !FAST && !VAR, "the short path is a counting kernel of fixed w, k <= 32");
+        __shared__ WaveSharedShort sh;
+        if (a.status->short_batch) scan_short<W>(a, sh); // wave-uniform
+    } else {
+        __shared__ WaveShared sh;
+        if constexpr (dcn_scan_has_short<W> && !K128 && !DUMP && !FAST && !VAR) {
+            // (a.ascii: only ctx.hip's filter batches set it, and only behind a shape kernel)
+            if (a.ascii && a.status->short_batch) return;
+        }
+        scan_body<W, K128, DUMP, FAST, VAR, false>(a, sh, ShortLane{});
+    }
+}
+
 template <int W, bool VAR = false>
 int launch_w(const dcn_scan_args &args, uint32_t blocks, bool dump, bool k128, size_t dyn, hipStream_t stream) {
 #define DCN_LAUNCH(K128_, DUMP_, FAST_)                                                               \
@@ -1026,6 +1233,10 @@ int launch_w(const dcn_scan_args &args, uint32_t blocks, bool dump, bool k128, s
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(DCN_WAVE), dyn, stream, args);                    \
     } while (0)
     const bool fast = !dump && args.early_out_max_items != 0;
+    if constexpr (dcn_scan_has_short<W> && !VAR) {
+        if (args.ascii && !k128 && !dump && !fast)
+            hipLaunchKernelGGL((scan_kernel<W, false, false, false, false, true>), dim3(blocks), dim3(DCN_WAVE), 0, stream, args);
+    }
     if (k128) {
         if (dump) DCN_LAUNCH(true, true, false);
         else if (fast) DCN_LAUNCH(true, false, true);
@@ -1064,6 +1275,9 @@ int dcn_get_minimizer_variant(uint32_t *nt_rot, uint32_t *cmp_bits, uint32_t *co
     if (combine) *combine = v & 0xFF;
     return DCN_OK;
 }
+
+bool dcn_scan_has_short_path(uint32_t k, uint32_t w) { return k <= 32 && w == 15 && dcn_scan_has_short<15>; }
+uint32_t dcn_short_lmax() { return DCN_SHORT_LMAX; }
 
 int dcn_launch_scan(const dcn_scan_args &args_in, uint32_t max_tiles, bool dump, hipStream_t stream) {
     if (max_tiles == 0) return DCN_OK;

@@ -926,6 +926,14 @@ class FilterProcessor(_Context):
         N.check(N.lib().dcn_filter_batch_device(self._h, d_bases, d_offsets, d_unit_id, n_reads, n_bases, n_units,
                                                 C.byref(p), d_keep, d_hits, d_total))
 
+    def last_batch_short(self):
+        """True when the last batch synchronize() waited for was packed inside the scan kernel (a device batch of short
+        unpaired reads, dcn_ctx_last_batch_short), False when it took the classic pack pass.  Same results either way.  Batches of
+        filter_batch_device only: the host entry points do not change the answer."""
+        v = C.c_uint32()
+        N.check(N.lib().dcn_ctx_last_batch_short(self._h, C.byref(v)))
+        return bool(v.value)
+
     def reserve_records(self, n_records):
         N.check(N.lib().dcn_ctx_reserve_records(self._h, int(n_records)))
 

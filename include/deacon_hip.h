@@ -74,9 +74,10 @@ enum {
  * 1.8 = dcn_depth_track_batch;
  * 1.9 = dcn_anchor_map_create / _add / _info / _anchors, dcn_place_batch.
  * 1.10 = dcn_place_split_batch.
- * 1.11 = dcn_place_pair_batch. */
+ * 1.11 = dcn_place_pair_batch.
+ * 1.12 = dcn_ctx_last_batch_short. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 11
+#define DCN_ABI_MINOR 12
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -280,6 +281,14 @@ int dcn_filter_batch_device(dcn_ctx *ctx, const uint8_t *d_bases, const uint64_t
  * d_offsets / d_unit_id of some batch since the previous synchronize inconsistent (see above); outputs and counters
  * of those batches are undefined, the context itself stays usable (reported once). */
 int dcn_ctx_synchronize(dcn_ctx *ctx);
+
+/* Which path the last batch that dcn_ctx_synchronize() waited for took (ABI 1.12): *was_short = 1 when the device found it
+ * to be a batch of short unpaired reads (device-resident ASCII, no unit ids, no prefix, every read at most 152 bases) and
+ * packed its bases inside the scan kernel instead of in a pack pass of its own, 0 for the classic path.  The results are
+ * the same either way; DCN_NO_SHORT_FUSED=1 in the environment when the context is created keeps every batch on the
+ * classic path.  Only batches of dcn_filter_batch_device are reported: the host entry points wait for their batches
+ * themselves and leave the answer as it was. */
+int dcn_ctx_last_batch_short(dcn_ctx *ctx, uint32_t *was_short);
 
 /* Grow the scratch that holds (unit, hash) hit records of units spanning several tiles (long reads). */
 int dcn_ctx_reserve_records(dcn_ctx *ctx, uint64_t n_records);
