@@ -141,6 +141,20 @@ class PairPlacement(C.Structure):
 PAIR_HIST_BINS = 256  # DCN_PAIR_HIST_BINS
 
 
+class VerifyParams(C.Structure):
+    _fields_ = [
+        ("max_edits", C.c_uint32),
+        ("max_permille", C.c_uint32),
+        ("row_stride", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+VERIFY_MAX_EDITS = 1023  # DCN_VERIFY_MAX_EDITS
+VERIFY_OVER = 0xFFFFFFFE  # DCN_VERIFY_OVER
+VERIFY_UNPLACED = 0xFFFFFFFF  # DCN_VERIFY_UNPLACED
+
+
 def build(force=False, jobs=6):
     """Compile every HIP source for gfx950 into lib/libdeacon_hip.so (hipcc cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -248,10 +262,13 @@ _SIGNATURES = {
     "dcn_place_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp]),
     "dcn_place_split_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp]),
     "dcn_place_pair_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "dcn_anchor_map_keep_bases": (C.c_int, [_vp]),
+    "dcn_anchor_map_fetch": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
+    "dcn_verify_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp]),
 }
 
 _lib = None
-ABI = (1, 12)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 13)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

@@ -3673,7 +3673,7 @@ struct AnchorRef {
 };
 
 void load_anchor_ref(AnchorRef &R, const std::string &ref_path, bool has_index, const std::string &index, unsigned k_arg,
-                     unsigned w_arg, const char *batch_hook, bool quiet) {
+                     unsigned w_arg, const char *batch_hook, bool quiet, bool keep_bases) {
     if (ref_path.empty()) die("the following required arguments were not provided: <REF>");
     Batch ref;
     {
@@ -3693,6 +3693,7 @@ void load_anchor_ref(AnchorRef &R, const std::string &ref_path, bool has_index, 
     deacon::check(dcn_anchor_map_create(keys.p, &map.p));
     dcn_index_destroy(keys.p);
     keys.p = nullptr;
+    if (keep_bases) deacon::check(dcn_anchor_map_keep_bases(map.p)); // (verify: the records' bases stay on the device)
     const BatchSize size = batch_size(batch_hook);
     const uint64_t batch_bases = R.batch_bases = size.batch_bases;
     R.ctx.reset(new Context(map.p, size.max_bases));
@@ -3728,7 +3729,7 @@ void load_anchor_ref(AnchorRef &R, const std::string &ref_path, bool has_index, 
 int run_place(const PlaceArgs &a) {
     const Stopwatch watch;
     AnchorRef R;
-    load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, "DCN_CLI_PLACE_BATCH_BASES", a.quiet);
+    load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, "DCN_CLI_PLACE_BATCH_BASES", a.quiet, false);
     RawIndex &map = R.map;
     Context &ctx = *R.ctx;
     const uint64_t batch_bases = R.batch_bases;
@@ -3801,14 +3802,20 @@ struct MapArgs {
     bool has_index = false, has_summary = false, quiet = false;
     unsigned k = 31, w = 15, band = 256, min_votes = 2, max_placements = 4;
     size_t prefix_length = 0;
+    // `verify`: map's placements, each compared base by base with the reference (dcn_verify_batch)
+    bool verify = false, verified_only = false;
+    unsigned max_edits = DCN_VERIFY_MAX_EDITS, max_div = 200;
 };
 
 // one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
 // hits of the read), ns (positions of the read)
+// (`verify`: edits = what dcn_verify_batch said of the row, and the line gains ve and, for a verified row, NM, with column
+// 10 = column 11 - NM; map passes DCN_VERIFY_UNPLACED, which no placed row has, and prints what it always did)
 void append_paf(std::string &rows, const std::string &read_name, uint32_t read_len, const dcn_split_placement &p,
-                const std::string &record_name, uint32_t record_len, uint32_t k) {
+                const std::string &record_name, uint32_t record_len, uint32_t k, uint32_t edits = DCN_VERIFY_UNPLACED) {
     const uint64_t on_read = p.read_end - p.read_start, on_ref = p.ref_end - p.ref_start;
-    const uint64_t matches = std::min<uint64_t>((uint64_t)p.votes * k, on_read);
+    const bool verified = edits != DCN_VERIFY_UNPLACED && edits != DCN_VERIFY_OVER;
+    const uint64_t matches = verified ? std::max(on_read, on_ref) - edits : std::min<uint64_t>((uint64_t)p.votes * k, on_read);
     rows.append(read_name);
     rows += '\t' + std::to_string(read_len) + '\t' + std::to_string(p.read_start) + '\t' + std::to_string(p.read_end) + '\t';
     rows += p.reverse ? '-' : '+';
@@ -3817,13 +3824,17 @@ void append_paf(std::string &rows, const std::string &read_name, uint32_t read_l
             std::to_string(p.mapq);
     rows += "\tcm:i:" + std::to_string(p.votes) + "\trk:i:" + std::to_string(p.rank) + "\tnp:i:" + std::to_string(p.n_placed) +
             "\trv:i:" + std::to_string(p.rival_votes) + "\tna:i:" + std::to_string(p.n_anchors) + "\tns:i:" +
-            std::to_string(p.n_positions) + '\n';
+            std::to_string(p.n_positions);
+    if (verified) rows += "\tve:i:1\tNM:i:" + std::to_string(edits);
+    else if (edits == DCN_VERIFY_OVER) rows += "\tve:i:0";
+    rows += '\n';
 }
 
 int run_map(const MapArgs &a) {
     const Stopwatch watch;
     AnchorRef R;
-    load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, "DCN_CLI_MAP_BATCH_BASES", a.quiet);
+    load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, a.verify ? "DCN_CLI_VERIFY_BATCH_BASES" : "DCN_CLI_MAP_BATCH_BASES", a.quiet,
+                    a.verify);
     Context &ctx = *R.ctx;
     dcn_place_split_params prm = {};
     prm.band_bases = a.band;
@@ -3833,10 +3844,16 @@ int run_map(const MapArgs &a) {
     TextOut out(a.output, true);
     FastxReader rd(a.input);
     uint64_t reads_in = 0, placed = 0, split_reads = 0, placements = 0, mapq60 = 0, mapq0 = 0;
+    uint64_t verified = 0, unverified = 0, edits_sum = 0, verified_bases = 0;
+    dcn_verify_params vprm = {};
+    vprm.max_edits = a.max_edits;
+    vprm.max_permille = a.max_div;
+    vprm.row_stride = sizeof(dcn_split_placement);
     std::vector<uint64_t> per_record(R.n_records, 0);
     Batch b;
     std::vector<uint64_t> place_off;
     std::vector<dcn_split_placement> pl;
+    std::vector<uint32_t> edits;
     std::string rows;
     for_each_batch(rd, b, R.batch_bases, R.batch_reads, [&] {
         const uint32_t n_reads = (uint32_t)b.recs.size();
@@ -3845,6 +3862,11 @@ int run_map(const MapArgs &a) {
         pl.resize((size_t)n_reads * a.max_placements);  // (never more than max_placements per read)
         deacon::check(dcn_place_split_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &prm, place_off.data(),
                                             pl.data(), pl.size(), nullptr));
+        if (a.verify) { // the same reads, the rows just placed
+            edits.resize(place_off[n_reads]);
+            deacon::check(dcn_verify_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), pl.data(),
+                                           place_off[n_reads], edits.data()));
+        }
         rows.clear();
         for (uint32_t r = 0; r < n_reads; ++r) {
             const Rec &rec = b.recs[r];
@@ -3858,28 +3880,46 @@ int run_map(const MapArgs &a) {
                 const dcn_split_placement &p = pl[q];
                 ++per_record[p.record];
                 mapq60 += p.mapq == 60, mapq0 += p.mapq == 0;
-                append_paf(rows, name, rec.seq_len, p, R.names[p.record], R.lens[p.record], R.k);
+                if (a.verify) {
+                    if (edits[q] == DCN_VERIFY_OVER) {
+                        ++unverified;
+                        if (a.verified_only) continue;
+                    } else {
+                        ++verified, edits_sum += edits[q];
+                        verified_bases += std::max<uint64_t>(p.read_end - p.read_start, p.ref_end - p.ref_start);
+                    }
+                }
+                append_paf(rows, name, rec.seq_len, p, R.names[p.record], R.lens[p.record], R.k, a.verify ? edits[q] : DCN_VERIFY_UNPLACED);
             }
         }
         out.write(rows);
     });
     out.finish();
     const double secs = watch.seconds();
-    if (!a.quiet)
+    if (!a.quiet) {
+        if (a.verify)
+            std::fprintf(stderr, "Verified %llu of %llu placements (%llu edits over %llu bases)\n", (unsigned long long)verified,
+                         (unsigned long long)placements, (unsigned long long)edits_sum, (unsigned long long)verified_bases);
         std::fprintf(stderr, "Mapped %llu of %llu reads in %llu placements (%llu reads with two or more) in %s\n",
                      (unsigned long long)placed, (unsigned long long)reads_in, (unsigned long long)placements,
                      (unsigned long long)split_reads, fmt_duration(secs).c_str());
+    }
     if (a.has_summary) {
         std::string js = summary_head() + ",\n  \"reference\": " + json_str(a.ref) + ",\n  \"input\": " + json_str(a.input);
         appendf(js, ",\n  \"k\": %u,\n  \"w\": %u,\n  \"band_bases\": %u,\n  \"min_votes\": %u,\n  \"prefix_length\": %zu,\n"
                     "  \"records\": %u,\n  \"keys\": %llu,\n  \"anchors\": %llu,\n  \"repeats\": %llu,\n"
                     "  \"reads\": %llu,\n  \"placed\": %llu,\n  \"max_placements\": %u,\n  \"placements\": %llu,\n"
-                    "  \"split_reads\": %llu,\n  \"mapq60\": %llu,\n  \"mapq0\": %llu,\n"
-                    "  \"time\": %.17g,\n  \"placements_by_record\": [",
+                    "  \"split_reads\": %llu,\n  \"mapq60\": %llu,\n  \"mapq0\": %llu,\n",
                 (unsigned)R.k, (unsigned)R.w, a.band, a.min_votes, a.prefix_length, R.m_records, (unsigned long long)R.m_keys,
                 (unsigned long long)R.m_anchors, (unsigned long long)R.m_repeats, (unsigned long long)reads_in,
                 (unsigned long long)placed, a.max_placements, (unsigned long long)placements, (unsigned long long)split_reads,
-                (unsigned long long)mapq60, (unsigned long long)mapq0, secs);
+                (unsigned long long)mapq60, (unsigned long long)mapq0);
+        if (a.verify)
+            appendf(js, "  \"max_edits\": %u,\n  \"max_permille\": %u,\n  \"verified\": %llu,\n  \"unverified\": %llu,\n"
+                        "  \"edits\": %llu,\n  \"verified_bases\": %llu,\n",
+                    a.max_edits, a.max_div, (unsigned long long)verified, (unsigned long long)unverified, (unsigned long long)edits_sum,
+                    (unsigned long long)verified_bases);
+        appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
         for (uint32_t r = 0; r < R.n_records; ++r) {
             js += (r ? ",\n    {" : "\n    {");
             js += "\"name\": " + json_str(R.names[r]);
@@ -3904,7 +3944,7 @@ int run_map_pairs(const MapPairsArgs &a) {
     if (a.ref.empty()) die("the following required arguments were not provided: <REF>");
     if (!a.has_input) die("the following required arguments were not provided: <READS1>");
     AnchorRef R;
-    load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, "DCN_CLI_MAPPAIRS_BATCH_BASES", a.quiet);
+    load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, "DCN_CLI_MAPPAIRS_BATCH_BASES", a.quiet, false);
     Context &ctx = *R.ctx;
     dcn_place_pair_params prm = {};
     prm.band_bases = a.band;
@@ -4024,6 +4064,7 @@ void usage() {
                  "  place   Report which record of a reference each read came from, where, and on which strand\n"
                  "  map     Report up to N placements per read on a reference, each with a mapping quality, as PAF\n"
                  "  map-pairs  Place the two mates of each pair jointly: proper pairs, rescued mates, insert sizes, as PAF\n"
+                 "  verify  As map, with every placement compared base by base with the reference: edit distance, as PAF\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -4184,6 +4225,42 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "A key that occurs at exactly one place of <REF> is an anchor; keys that occur at several never vote.\n"
                "The mapping quality is 60 * (votes - rival votes) / votes, where the rival is the strongest other cell on the\n"
                "same stretch of the read (0 when it is as strong): a convention, not a calibrated probability.\n"
+               "Mates are independent here: one input.\n";
+    else if (sub == "verify")
+        text = "Report up to N placements of each read on a reference and compare each with the reference base by base, as PAF\n\n"
+               "Usage: deacon-hip verify [OPTIONS] <REF> [READS]\n\n"
+               "Arguments:\n"
+               "  <REF>     Path to the reference fastx file: its records are numbered and named in file order\n"
+               "  [READS]   Optional path to fastx file (or - for stdin; gz, bgzf, zst, xz and bz2 found by content) [default: -]\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Keys that may anchor: a minimizer index file, whose k and w are used\n"
+               "                                 [default: the minimizers of <REF> at -k / -w]\n"
+               "  -k <K>                         K-mer length without -x [default: 31]\n"
+               "  -w <W>                         Minimizer window size without -x [default: 15]\n"
+               "  -o, --output <OUTPUT>          PAF, one line per placement, as map prints it (- for stdout) [default: -], then\n"
+               "                                 ve:i:1 and NM:i:<edits> for a verified placement, ve:i:0 for one over the\n"
+               "                                 threshold.  Column 10 of a verified placement is column 11 - NM: column 11 is\n"
+               "                                 the longer of the two extents, so this is a lower bound on the matching bases\n"
+               "                                 of every optimal alignment.  An unverified placement keeps map's column 10\n"
+               "  -e, --max-edits <N>            Verified means at most N edits (0..1023) [default: 1023, a convention]\n"
+               "      --max-div <N>              ... and at most N per 1000 bases of the longer extent (0..1000) [default: 200,\n"
+               "                                 a convention]\n"
+               "      --verified-only            No line for a placement over the threshold\n"
+               "  -N, --max-placements <N>       Placements per read, each from the anchor hits no earlier one explained (1..8)\n"
+               "                                 [default: 4]\n"
+               "      --band <N>                 Width of a diagonal band in bases [default: 256, a convention]\n"
+               "  -a, --min-votes <N>            Minimum number of anchor hits in a placement's cell [default: 2, as filter's -a,\n"
+               "                                 a convention]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per read (0 = entire read) [default: 0]\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file: map's, and max_edits, max_permille, verified,\n"
+               "                                 unverified, edits and verified_bases (sums over the verified placements)\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
+               "  -h, --help                     Print help\n\n"
+               "Edits: the Levenshtein distance (substitution, insertion, deletion at cost 1 each) of the read's extent, reverse-\n"
+               "complemented on the - strand, and the record's extent, global over both.  A base that is not ACGT (N) matches\n"
+               "nothing.  The threshold is min(-e, longer extent * --max-div / 1000): both are conventions, not measured optima.\n"
+               "Placements, qualities and every other column and tag are map's for the same arguments.\n"
                "Mates are independent here: one input.\n";
     else if (sub == "map-pairs")
         text = "Place the two mates of each pair jointly on a reference: proper pairs, rescued mates and insert sizes, as PAF\n\n"
@@ -4475,8 +4552,9 @@ int main(int argc, char **argv) {
             if (pos.size() > 2) die("place takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[2] + "')");
             return run_place(a);
         }
-        if (args[0] == "map") {
+        if (args[0] == "map" || args[0] == "verify") {
             MapArgs a;
+            a.verify = args[0] == "verify";
             std::vector<std::string> pos;
             auto number = [&](const std::string &v, const char *flag, long long lo, long long hi) {
                 char *end = nullptr;
@@ -4492,6 +4570,9 @@ int main(int argc, char **argv) {
                 else if (s == "-w") a.w = (unsigned)number(need(++i), "-w", 1, 255);
                 else if (s == "-o" || s == "--output") a.output = need(++i);
                 else if (s == "-N" || s == "--max-placements") a.max_placements = (unsigned)number(need(++i), "-N", 1, DCN_PLACE_SPLIT_MAX);
+                else if (a.verify && (s == "-e" || s == "--max-edits")) a.max_edits = (unsigned)number(need(++i), "--max-edits", 0, DCN_VERIFY_MAX_EDITS);
+                else if (a.verify && s == "--max-div") a.max_div = (unsigned)number(need(++i), "--max-div", 0, 1000);
+                else if (a.verify && s == "--verified-only") a.verified_only = true;
                 else if (s == "--band") a.band = (unsigned)number(need(++i), "--band", 1, 0xFFFFFFFFll);
                 else if (s == "-a" || s == "--min-votes") a.min_votes = (unsigned)number(need(++i), "--min-votes", 1, 0xFFFFFFFFll);
                 else if (s == "-p" || s == "--prefix-length") a.prefix_length = (size_t)number(need(++i), "--prefix-length", 0, 0x7FFFFFFFFFFFFFFFll);
@@ -4503,7 +4584,7 @@ int main(int argc, char **argv) {
             }
             if (pos.size() > 0) a.ref = pos[0];
             if (pos.size() > 1) a.input = pos[1];
-            if (pos.size() > 2) die("map takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[2] + "')");
+            if (pos.size() > 2) die(args[0] + " takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[2] + "')");
             return run_map(a);
         }
         if (args[0] == "map-pairs") {

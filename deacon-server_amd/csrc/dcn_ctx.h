@@ -15,6 +15,7 @@
 #include <vector>
 
 struct dcn_split_round; // (dcn_place.h)
+struct dcn_verify_item; // (dcn_verify.h)
 
 // One pipeline step of a host batch: reads [r0, r1) = units [u0, u1) = bases [b0, b1) of the batch stream.
 // groups [g0, g1) of the invalid-base mask that crossed the link as their non-zero words only: n (group, word) pairs at
@@ -174,6 +175,10 @@ struct dcn_ctx {
     // paired placement buffers (lazy, first dcn_place_pair_batch): one row per read and the insert histogram
     dcn_pair_placement *d_ppr_out = nullptr;
     unsigned long long *d_ppr_hist = nullptr;
+    // verify buffers (lazy, first dcn_verify_batch; dcn_verify.h): one item and one result per row, grown to the largest n_rows
+    dcn_verify_item *d_vfy_items = nullptr;
+    uint32_t *d_vfy_out = nullptr;
+    uint64_t vfy_cap = 0;
     // deferred state of the last enqueued device-API batch
     bool batch_pending = false;
     bool lean = false; // a small host batch is being submitted: copies and result copies go on `stream` itself (submit_impl)

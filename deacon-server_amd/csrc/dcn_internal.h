@@ -80,6 +80,9 @@ struct dcn_table_view {
 constexpr uint32_t DCN_VARIANT_DEFAULT = (1u << 16) | (16u << 8) | 0u;
 uint32_t dcn_current_variant();
 
+struct dcn_base_store; // (dcn_verify.h)
+void dcn_base_store_free(dcn_base_store *s);
+
 struct dcn_index {
     // captured when the index is created (built, loaded, merged, cloned): the rule its keys were selected by travels
     // with it, and every context filters by its index's rule whatever the process-wide setting has become since
@@ -109,6 +112,8 @@ struct dcn_index {
     // anchor_records = records added so far.  Null: not a map.
     uint64_t *d_anchor = nullptr;
     uint32_t anchor_records = 0;
+    // ... and the bases of its records (dcn_anchor_map_keep_bases, verify_api.hip).  Null: none are kept.
+    dcn_base_store *store = nullptr;
     dcn_table_view view() const {
         dcn_table_view v;
         v.slots = d_slots;

@@ -3,6 +3,7 @@
 // dump front end of ctx.hip on a filter context).
 #include "dcn_ctx.h"
 #include "dcn_place.h"
+#include "dcn_verify.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -217,8 +218,13 @@ extern "C" int dcn_anchor_map_add(dcn_index *map, dcn_ctx *ctx, const uint8_t *b
     pa.first_record = map->anchor_records;
     DCN_TRY(dcn_launch_anchor_add(pa, st));
     DCN_PROF_MARK(DCN_STAGE_DISTINCT);
+    // kept bases: the front end's packed stream and mask go behind what the store holds, whole words
+    uint64_t store_start = 0;
+    if (map->store)
+        DCN_TRY(dcn_base_store_append(map->store, c->d_packed + DCN_FRONT_PAD, c->d_invmask + DCN_FRONT_PAD, n_bases, st, &store_start));
     DCN_PROF_MARK(DCN_STAGE_FINISH);
     DCN_TRY(finish_run(c, prof_slot));
+    if (map->store) dcn_base_store_commit(map->store, store_start, offsets, n_records);
     map->anchor_records += n_records;
     return DCN_OK;
 }

@@ -1,0 +1,235 @@
+// verify_api.hip -- the C ABI of kept reference bases (dcn_anchor_map_keep_bases, dcn_anchor_map_fetch), the store behind
+// them (dcn_verify.h; dcn_anchor_map_add of place_api.hip appends to it) and dcn_verify_batch (kernel in verify.hip).
+#include "dcn_ctx.h"
+#include "dcn_verify.h"
+
+#include <cstdlib>
+#include <cstring>
+
+using namespace dcn_impl;
+
+static_assert(sizeof(dcn_verify_params) == 16, "verify params are ABI");
+
+namespace {
+int check_map(const dcn_index *map) {
+    if (!map) return dcn_fail(DCN_ERR_ARG, "map is NULL");
+    if (!map->d_anchor) return dcn_fail(DCN_ERR_ARG, "the index is not an anchor map (dcn_anchor_map_create)");
+    return DCN_OK;
+}
+
+int check_store(const dcn_index *map) {
+    DCN_TRY(check_map(map));
+    if (!map->store) return dcn_fail(DCN_ERR_ARG, "the map keeps no bases (dcn_anchor_map_keep_bases before the first add)");
+    return DCN_OK;
+}
+
+// bases the store starts with: DCN_STORE_INITIAL_BASES, or the test hook DCN_ANCHOR_STORE_BASES, read at call time
+uint64_t initial_bases() {
+    const char *s = std::getenv("DCN_ANCHOR_STORE_BASES");
+    const uint64_t v = s && *s ? std::strtoull(s, nullptr, 10) : DCN_STORE_INITIAL_BASES;
+    return std::max<uint64_t>((v + 31) / 32 * 32, 32);
+}
+
+// `cap` bases of store: both arrays with their pads, zeroed, holding the first `used` bases of `s`
+int store_resize(dcn_base_store *s, uint64_t cap) {
+    const uint64_t pw = cap / 16 + DCN_STORE_PAD_WORDS, mw = cap / 32 + DCN_STORE_PAD_WORDS;
+    uint32_t *p = nullptr, *m = nullptr;
+    hipError_t e = hipMalloc((void **)&p, pw * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&m, mw * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(p, 0, pw * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemset(m, 0, mw * sizeof(uint32_t));
+    if (e == hipSuccess && s->used) e = hipMemcpy(p, s->d_packed, s->used / 16 * sizeof(uint32_t), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && s->used) e = hipMemcpy(m, s->d_invmask, s->used / 32 * sizeof(uint32_t), hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize(); // (null-stream work must not be overtaken by the context's stream)
+    if (e != hipSuccess) {
+        if (p) hipFree(p);
+        if (m) hipFree(m);
+        return dcn_hip_fail(e, "kept bases");
+    }
+    if (s->d_packed) hipFree(s->d_packed);
+    if (s->d_invmask) hipFree(s->d_invmask);
+    s->d_packed = p;
+    s->d_invmask = m;
+    s->cap = cap;
+    return DCN_OK;
+}
+} // namespace
+
+void dcn_base_store_free(dcn_base_store *s) {
+    if (!s) return;
+    if (s->d_packed) hipFree(s->d_packed);
+    if (s->d_invmask) hipFree(s->d_invmask);
+    delete s;
+}
+
+int dcn_base_store_append(dcn_base_store *s, const uint32_t *packed, const uint32_t *invmask, uint64_t n_bases, hipStream_t stream,
+                          uint64_t *batch_start) {
+    *batch_start = s->used;
+    const uint64_t groups = (n_bases + 31) / 32, need = s->used + groups * 32;
+    if (need > s->cap) { // geometric: at least twice what there was
+        const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(need, 2 * s->cap), initial_bases());
+        DCN_TRY(store_resize(s, cap));
+    }
+    if (groups == 0) return DCN_OK;
+    // (the pack kernel writes whole 32-base groups: bases behind n_bases are 'A' and valid, and no record reaches them)
+    DCN_HIP(hipMemcpyAsync(s->d_packed + s->used / 16, packed, groups * 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    DCN_HIP(hipMemcpyAsync(s->d_invmask + s->used / 32, invmask, groups * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    return DCN_OK;
+}
+
+void dcn_base_store_commit(dcn_base_store *s, uint64_t batch_start, const uint64_t *offsets, uint32_t n_records) {
+    for (uint32_t r = 0; r < n_records; ++r) {
+        s->rec_start.push_back(batch_start + offsets[r]);
+        s->rec_len.push_back((uint32_t)(offsets[r + 1] - offsets[r]));
+    }
+    s->used = batch_start + (offsets[n_records] + 31) / 32 * 32;
+}
+
+extern "C" int dcn_anchor_map_keep_bases(dcn_index *map) {
+    DCN_TRY(check_map(map));
+    if (map->store) return DCN_OK;
+    if (map->anchor_records != 0)
+        return dcn_fail(DCN_ERR_ARG, "dcn_anchor_map_keep_bases comes before the first dcn_anchor_map_add: the map has records already");
+    map->store = new (std::nothrow) dcn_base_store();
+    if (!map->store) return dcn_fail(DCN_ERR_NOMEM, "host allocation failed");
+    return DCN_OK;
+}
+
+extern "C" int dcn_anchor_map_fetch(const dcn_index *map, uint32_t record, uint64_t start, uint64_t n_bases, uint8_t *out) {
+    DCN_TRY(check_store(map));
+    const dcn_base_store *s = map->store;
+    if (record >= s->rec_len.size())
+        return dcn_fail(DCN_ERR_ARG, "fetch: record " + std::to_string(record) + " of " + std::to_string(s->rec_len.size()) + " added");
+    const uint64_t len = s->rec_len[record];
+    if (start > len || n_bases > len - start)
+        return dcn_fail(DCN_ERR_ARG, "fetch: bases [" + std::to_string(start) + ", " + std::to_string(start) + " + " +
+                                         std::to_string(n_bases) + ") are past the record's " + std::to_string(len) + " bases");
+    if (n_bases == 0) return DCN_OK;
+    if (!out) return dcn_fail(DCN_ERR_ARG, "out is NULL");
+    DCN_HIP(hipSetDevice(map->device));
+    const uint64_t b0 = s->rec_start[record] + start, b1 = b0 + n_bases;
+    const uint64_t pw0 = b0 / 16, pw1 = (b1 + 15) / 16, mw0 = b0 / 32, mw1 = (b1 + 31) / 32;
+    std::vector<uint32_t> p(pw1 - pw0), m(mw1 - mw0);
+    DCN_HIP(hipMemcpy(p.data(), s->d_packed + pw0, p.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    DCN_HIP(hipMemcpy(m.data(), s->d_invmask + mw0, m.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint64_t b = b0; b < b1; ++b) {
+        const uint32_t code = (p[b / 16 - pw0] >> (2 * (b % 16))) & 3u, inv = (m[b / 32 - mw0] >> (b % 32)) & 1u;
+        out[b - b0] = inv ? 'N' : "ACTG"[code];
+    }
+    return DCN_OK;
+}
+
+extern "C" int dcn_verify_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                                const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits) {
+    const dcn_verify_params *prm = static_cast<const dcn_verify_params *>(params);
+    // (the parameters first: what is wrong with them does not depend on the context or the map)
+    if (!prm) return dcn_fail(DCN_ERR_ARG, "params is NULL");
+    if (prm->reserved != 0) return dcn_fail(DCN_ERR_ARG, "params.reserved must be 0");
+    if (prm->max_edits > DCN_VERIFY_MAX_EDITS)
+        return dcn_fail(DCN_ERR_ARG, "params.max_edits must be 0.." + std::to_string(DCN_VERIFY_MAX_EDITS));
+    if (prm->max_permille > 1000) return dcn_fail(DCN_ERR_ARG, "params.max_permille must be 0..1000");
+    if (prm->row_stride < sizeof(dcn_placement) || prm->row_stride % 8 != 0)
+        return dcn_fail(DCN_ERR_ARG, "params.row_stride must be at least 48 and a multiple of 8");
+    if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
+    DCN_TRY(check_store(map));
+    DCN_TRY(check_ctx_matches(ctx, map, "the map"));
+    if (!row_offsets && n_rows != n_reads)
+        return dcn_fail(DCN_ERR_ARG, "without row_offsets row r belongs to read r: n_rows must equal n_reads");
+    if (n_reads == 0) {
+        if (n_rows != 0) return dcn_fail(DCN_ERR_ARG, "row_offsets must end at n_rows");
+        return DCN_OK;
+    }
+    if (!offsets) return dcn_fail(DCN_ERR_ARG, "offsets is NULL");
+    DCN_TRY(validate_host_batch(ctx, offsets, n_reads));
+    const uint64_t n_bases = offsets[n_reads];
+    if (n_bases > 0 && !bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
+    if (row_offsets) {
+        if (row_offsets[0] != 0) return dcn_fail(DCN_ERR_ARG, "row_offsets[0] must be 0");
+        for (uint32_t r = 0; r < n_reads; ++r)
+            if (row_offsets[r + 1] < row_offsets[r]) return dcn_fail(DCN_ERR_ARG, "row_offsets must be non-decreasing");
+        if (row_offsets[n_reads] != n_rows) return dcn_fail(DCN_ERR_ARG, "row_offsets must end at n_rows");
+    }
+    if (n_rows == 0) return DCN_OK;
+    if (!rows) return dcn_fail(DCN_ERR_ARG, "rows is NULL");
+    if (!edits) return dcn_fail(DCN_ERR_ARG, "edits is NULL");
+
+    // every row against its read and its record; what the kernel gets is resolved to stream positions here
+    const dcn_base_store *store = map->store;
+    std::vector<dcn_verify_item> items(n_rows);
+    uint32_t e_max = 0;
+    uint64_t row = 0;
+    for (uint32_t r = 0; r < n_reads; ++r) {
+        const uint64_t row_end = row_offsets ? row_offsets[r + 1] : (uint64_t)r + 1;
+        const uint64_t read_len = offsets[r + 1] - offsets[r];
+        for (; row < row_end; ++row) {
+            dcn_placement p;
+            memcpy(&p, static_cast<const uint8_t *>(rows) + row * prm->row_stride, sizeof(p));
+            dcn_verify_item &it = items[row];
+            memset(&it, 0, sizeof(it));
+            if (p.record == UINT32_MAX) {
+                it.flags = 2u;
+                continue;
+            }
+            // (the message is put together only when a row is wrong: ten million rows are walked here per call)
+            const auto bad = [row](const std::string &what) { return dcn_fail(DCN_ERR_ARG, "row " + std::to_string(row) + ": " + what); };
+            if (p.record >= store->rec_len.size())
+                return bad("record " + std::to_string(p.record) + " of " + std::to_string(store->rec_len.size()) + " added");
+            if (p.reverse > 1) return bad("reverse must be 0 or 1");
+            if (p.read_start > p.read_end) return bad("read_start is behind read_end");
+            if (p.read_end > read_len)
+                return bad("read_end " + std::to_string(p.read_end) + " is past the read's " + std::to_string(read_len) + " bases");
+            if (p.ref_start > p.ref_end) return bad("ref_start is behind ref_end");
+            const uint64_t rec_len = store->rec_len[p.record];
+            if (p.ref_end > rec_len)
+                return bad("ref_end " + std::to_string(p.ref_end) + " is past the record's " + std::to_string(rec_len) + " bases");
+            it.m = p.read_end - p.read_start;
+            it.n = (uint32_t)(p.ref_end - p.ref_start);
+            it.E = (uint32_t)std::min<uint64_t>(prm->max_edits, (uint64_t)std::max(it.m, it.n) * prm->max_permille / 1000);
+            it.flags = p.reverse;
+            it.s_origin = (int64_t)(offsets[r] + (p.reverse ? p.read_end : p.read_start));
+            it.t_origin = (int64_t)(store->rec_start[p.record] + p.ref_start);
+            const uint64_t gap = it.m > it.n ? it.m - it.n : it.n - it.m;
+            if (gap <= it.E) e_max = std::max(e_max, it.E); // (a row whose lengths differ by more is OVER without a wavefront)
+        }
+    }
+
+    dcn_ctx *c = ctx;
+    DCN_HIP(hipSetDevice(c->device));
+    if (n_rows > c->vfy_cap) {
+        if (c->d_vfy_items) hipFree(c->d_vfy_items);
+        if (c->d_vfy_out) hipFree(c->d_vfy_out);
+        c->d_vfy_items = nullptr;
+        c->d_vfy_out = nullptr;
+        c->vfy_cap = 0;
+        DCN_TRY(dev_alloc(&c->d_vfy_items, n_rows, "verify rows"));
+        DCN_TRY(dev_alloc(&c->d_vfy_out, n_rows, "verify edits"));
+        c->vfy_cap = n_rows;
+    }
+    DCN_TRY(staged_h2d(c, c->d_vfy_items, items.data(), n_rows * sizeof(dcn_verify_item)));
+    DCN_TRY(stage_batch(c, bases, n_bases, offsets, n_reads, nullptr));
+    hipStream_t st = c->stream;
+    DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st)); // (short_batch = 0: the pack kernel packs)
+    int prof_slot = -1;
+    DCN_TRY(prof_begin(c, &prof_slot));
+    // the front end up to the packed stream and the invalid mask: no plan, no scan (their slots stay empty)
+    DCN_TRY(dcn_launch_pack(c->d_ascii, 0, n_bases, c->d_packed + DCN_FRONT_PAD, c->d_invmask + DCN_FRONT_PAD, c->d_status, st));
+    DCN_PROF_MARK(DCN_STAGE_PACK);
+    DCN_PROF_MARK(DCN_STAGE_PLAN);
+    DCN_PROF_MARK(DCN_STAGE_SCAN);
+    DCN_PROF_MARK(DCN_STAGE_DISTINCT);
+    dcn_verify_args va;
+    memset(&va, 0, sizeof(va));
+    va.items = c->d_vfy_items;
+    va.n_rows = n_rows;
+    va.s_packed = c->d_packed + DCN_FRONT_PAD;
+    va.s_invmask = c->d_invmask + DCN_FRONT_PAD;
+    va.t_packed = store->d_packed;
+    va.t_invmask = store->d_invmask;
+    va.lds_stride = (2 * e_max + 1 + 3) / 4 * 4;
+    va.out = c->d_vfy_out;
+    DCN_TRY(dcn_launch_verify(va, st));
+    DCN_PROF_MARK(DCN_STAGE_FINISH);
+    DCN_TRY(finish_run(c, prof_slot));
+    DCN_HIP(hipMemcpy(edits, c->d_vfy_out, n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return DCN_OK;
+}

@@ -670,6 +670,7 @@ SPLIT_PLACEMENT_DTYPE = np.dtype(PLACEMENT_DTYPE.descr + [("rank", np.uint32), (
 PAIR_PLACEMENT_DTYPE = np.dtype(SPLIT_PLACEMENT_DTYPE.descr + [("flags", np.uint32), ("pair_votes", np.uint32),
                                                                ("tlen", np.int64)])
 PAIR_PROPER, PAIR_RESCUED, PAIR_MATE_PLACED = 1, 2, 4  # DCN_PAIR_*: bits of `flags`
+VERIFY_OVER, VERIFY_UNPLACED = N.VERIFY_OVER, N.VERIFY_UNPLACED  # DCN_VERIFY_*: what `edits` holds instead of a distance
 
 
 class AnchorMap(Index):
@@ -677,13 +678,23 @@ class AnchorMap(Index):
     include/deacon_hip.h): a copy of `index`'s keys (the source may be closed afterwards) with one word per slot.  Records
     are numbered in the order they are added; a key that occurs at exactly one (record, position) of them is an anchor, one
     that occurs at several is a repeat and never votes.  It is an Index: contexts can be created over it, clone() gives a
-    plain Index without the words."""
+    plain Index without the words.  keep_bases=True also keeps the bases of every record on the device (0.375 B per base;
+    dcn_anchor_map_keep_bases): fetch() cuts a region out, and Placer.verify_batch compares placements base by base."""
 
-    def __init__(self, index):
+    def __init__(self, index, keep_bases=False):
         h = C.c_void_p()
         N.check(N.lib().dcn_anchor_map_create(index._h, C.byref(h)))
         super().__init__(h, index.device)
         self._ctx = None
+        self.keeps_bases = bool(keep_bases)
+        if keep_bases:
+            N.check(N.lib().dcn_anchor_map_keep_bases(self._h))
+
+    def fetch(self, record, start, n):
+        """bases [start, start + n) of a record -> bytes: ACGT, and N for every base that was not in ACGTacgt"""
+        out = np.zeros(max(int(n), 1), np.uint8)
+        N.check(N.lib().dcn_anchor_map_fetch(self._h, int(record), int(start), int(n), _ptr(out)))
+        return out[:int(n)].tobytes()
 
     def clone(self, device):
         h = C.c_void_p()
@@ -814,6 +825,26 @@ class Placer(_Context):
         N.check(N.lib().dcn_place_pair_batch(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None, _ptr(offsets),
                                              n_reads, C.byref(p), _ptr(out), _ptr(hist) if want_hist else None))
         return out[:n_reads], hist
+
+    def verify_batch(self, bases, offsets, rows, row_offsets=None, max_edits=1023, max_permille=200):
+        """The Levenshtein distance of each placement's read interval (reverse-complemented when the row says so) and its
+        record interval, thresholded (dcn_verify_batch; the definition of a verified placement is in
+        include/deacon_hip.h): edits = d when d <= E = min(max_edits, max(m, n) * max_permille // 1000), else VERIFY_OVER;
+        VERIFY_UNPLACED for a row with record == UNPLACED.  The map must keep bases (AnchorMap(index, keep_bases=True)).
+        rows: the rows of place_batch or place_pair_batch (row r belongs to read r), or those of place_split_batch with its
+        place_offsets as row_offsets; the stride is the dtype's item size.  max_edits = 1023 and max_permille = 200 are
+        conventions, not measured optima.  -> np.uint32[n_rows].  profile(): pack in its slot, the verify kernel in
+        'finish'."""
+        bases, offsets, n_reads = _batch(bases, offsets)
+        rows = np.ascontiguousarray(rows)
+        n_rows = len(rows)
+        if row_offsets is not None:
+            row_offsets = np.ascontiguousarray(row_offsets, dtype=np.uint64)
+        edits = np.zeros(max(n_rows, 1), np.uint32)
+        p = N.VerifyParams(int(max_edits), int(max_permille), rows.dtype.itemsize, 0)
+        N.check(N.lib().dcn_verify_batch(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None, _ptr(offsets), n_reads,
+                                         C.byref(p), _ptr(row_offsets), _ptr(rows) if n_rows else None, n_rows, _ptr(edits)))
+        return edits[:n_rows]
 
     def place_pairs(self, reads1, reads2, **kw):
         """the mates of two lists, interleaved -> place_pair_batch's result"""

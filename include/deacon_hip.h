@@ -75,9 +75,10 @@ enum {
  * 1.9 = dcn_anchor_map_create / _add / _info / _anchors, dcn_place_batch.
  * 1.10 = dcn_place_split_batch.
  * 1.11 = dcn_place_pair_batch.
- * 1.12 = dcn_ctx_last_batch_short. */
+ * 1.12 = dcn_ctx_last_batch_short.
+ * 1.13 = dcn_anchor_map_keep_bases / _fetch, dcn_verify_batch. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 12
+#define DCN_ABI_MINOR 13
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -801,6 +802,70 @@ typedef struct dcn_pair_placement {
  * copy, the rounds and the pairing. */
 int dcn_place_pair_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets,
                          uint32_t n_reads, const void *params, void *rows, uint64_t *tlen_hist);
+
+/* ---- verified placements: kept reference bases, edit distance (ABI 1.13) ---------------------------------------------
+ * (no reference counterpart.)  The placement calls above compare minimizers only.  An anchor map that KEEPS BASES holds
+ * its records' bases on the device, and dcn_verify_batch compares each placement's read interval with its record
+ * interval base by base.
+ *
+ * dcn_anchor_map_keep_bases: from then on every dcn_anchor_map_add also appends the batch's 2-bit stream and invalid-base
+ * bits (what the context's front end has packed) to a store the map owns.  It comes before the first add: DCN_ERR_ARG once
+ * the map has records, and for an index that is not a map; calling it again changes nothing.  The store costs 0.375 B per
+ * base of device memory, which dcn_index_memory does not count (like the anchor words); it grows geometrically (the test
+ * hook DCN_ANCHOR_STORE_BASES, read at call time, sets the capacity it starts with); a refused add appends nothing;
+ * dcn_index_clone gives an index without it, dcn_index_destroy frees it.  The lengths of the records stay on the host.  A
+ * map that keeps no bases behaves exactly as before in every call. */
+int dcn_anchor_map_keep_bases(dcn_index *map);
+/* Bases [start, start + n_bases) of a record, as text: ACGT for a valid base (upper case whatever was added), N for every
+ * base that was not in ACGTacgt.  Blocking.  DCN_ERR_ARG for a map that keeps no bases, a record not added yet, or a range
+ * that goes past the record's end. */
+int dcn_anchor_map_fetch(const dcn_index *map, uint32_t record, uint64_t start, uint64_t n_bases, uint8_t *out);
+
+/* THE DEFINITION OF A VERIFIED PLACEMENT.  For a row with record != UINT32_MAX:
+ *   1. S = read[read_start, read_end) of the read as given; when reverse is set, S is its reverse complement.
+ *      T = record[ref_start, ref_end).  m = |S|, n = |T|; either may be 0.
+ *   2. Two bases are EQUAL when both are in ACGTacgt and are the same letter regardless of case.  A base outside that
+ *      alphabet equals nothing, not even itself (it is the pack kernel's invalid bit); the complement of an invalid base
+ *      is invalid.
+ *   3. d = the Levenshtein distance of S and T: substitution, insertion and deletion at cost 1 each, global over both
+ *      whole intervals.
+ *   4. E = min(max_edits, max(m, n) * max_permille / 1000), by integer division.
+ *   5. edits = d when d <= E, else DCN_VERIFY_OVER.
+ *   6. A row with record == UINT32_MAX gets DCN_VERIFY_UNPLACED; its other fields are not looked at.
+ *   7. Integers only.  Nothing depends on the band a kernel uses, on lanes, on LDS sizes or on how a batch is cut.
+ * Global over the extents: both intervals start and end on a k-mer of an anchor hit of the placement's cell, and rule 6 of
+ * placement puts the first and the last hit's diagonals within the cell's range, so |n - m| < 2 W.  The threshold: an
+ * alignment of cost <= E never leaves the diagonals [-E, +E], which makes a banded or wavefront kernel exact, not
+ * approximate.  max_edits = 1023 and max_permille = 200 are the conventions of the layers above, not measured optima. */
+#define DCN_VERIFY_MAX_EDITS 1023u
+#define DCN_VERIFY_OVER 0xFFFFFFFEu
+#define DCN_VERIFY_UNPLACED 0xFFFFFFFFu
+typedef struct dcn_verify_params {
+    uint32_t max_edits;    /* 0 .. DCN_VERIFY_MAX_EDITS */
+    uint32_t max_permille; /* 0 .. 1000 */
+    uint32_t row_stride;   /* bytes from one row to the next: >= 48, a multiple of 8 (48, 64, 80 for the three row types) */
+    uint32_t reserved;     /* must be 0 */
+} dcn_verify_params; /* 16 bytes */
+
+/*   map          an anchor map that keeps bases, with the k, w, minimizer rule and device of the context's index
+ *   params       a dcn_verify_params
+ *   row_offsets  NULL: row r belongs to read r and n_rows == n_reads (dcn_place_batch's and dcn_place_pair_batch's rows);
+ *                else n_reads + 1 entries: read r owns rows[row_offsets[r] .. row_offsets[r + 1]) -- place_offsets as
+ *                dcn_place_split_batch returns it
+ *   rows         n_rows placements, row_stride bytes apart; only the 48 bytes of dcn_placement at the head of each are
+ *                read, which the three row types share field for field
+ *   edits        n_rows entries
+ * (params and rows are declared void * for the reason given at dcn_locate_batch.)  Host pointers, blocking, batch limits
+ * as for dcn_place_batch; refused while batches are in flight; the six counters of the context are left unchanged.
+ * DCN_ERR_ARG, before any device work: NULLs, reserved != 0, max_edits above DCN_VERIFY_MAX_EDITS, max_permille > 1000, a
+ * row_stride below 48 or not a multiple of 8, a map that keeps no bases, row_offsets that do not start at 0, ascend and
+ * end at n_rows, and a placed row with record >= the records added, reverse > 1, read_start > read_end, read_end > the
+ * read's length, ref_start > ref_end or ref_end > the record's length: the message names the first such row.  The kernel
+ * trusts nothing the host has not checked.  The batch is staged and packed again (no plan, no scan), so the call may
+ * follow any placement call on the same context.  Device memory, freed with the context: 36 bytes per row of the largest
+ * call.  dcn_ctx_set_profiling covers it: pack in its slot, the verify kernel in FINISH; plan, scan and DISTINCT are empty. */
+int dcn_verify_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                     const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits);
 
 /* ---- counters: ProcessingStats (src/local_filter.rs:179-187, merged at :388-396) -------------------------- */
 
