@@ -79,7 +79,7 @@ static void free_ctx(dcn_ctx *c) {
     void *dev[] = {c->d_ascii, c->d_offsets, c->d_unit_id, c->d_packed, c->d_invmask,
                    c->d_read_tiles, c->d_read_tile_first, c->d_unit_first_read, c->d_unit_tile_first, c->d_unit_tile_count, c->d_tiles,
                    c->d_keep, c->d_unit_state, c->d_hits, c->d_total, c->d_unit_scratch, c->d_caps,
-                   c->d_set_off, c->d_tile_hits, c->d_pending, c->d_big, c->d_rec_hash, c->d_set_slots, c->d_status, c->d_report, c->d_dump_hash,
+                   c->d_set_off, c->d_tile_hits, c->d_pending, c->d_big, c->d_rec_hash, c->d_set_slots, c->d_status, c->d_wave_kept, c->d_report, c->d_dump_hash,
                    c->d_dump_pos, c->d_dump_count, c->d_dump_valid, c->d_tile_read_pos,
                    c->d_cls_big, c->d_cls_n_big, c->d_cls_match, c->d_cls_hits, c->d_cls_total,
                    c->d_loc_bits, c->d_loc_labels, c->d_loc_counts, c->d_loc_big, c->d_loc_n_big, c->d_loc_block_sums,
@@ -253,6 +253,7 @@ int enqueue_batch(dcn_ctx *c, const BatchView &v, const dcn_params *params, bool
     pa.stream_bases = v.stream_bases;
     pa.check_offsets = 1;
     pa.max_tiles = c->max_tiles;
+    pa.short_armed = short_fused ? 1u : 0u;
     DCN_TRY(dcn_launch_plan(pa, st));
     if (pack_ahead && c->pack_ahead_state == 1) DCN_HIP(hipEventRecord(c->plan_done, st));
     DCN_PROF_MARK(DCN_STAGE_PLAN);
@@ -291,6 +292,9 @@ int enqueue_batch(dcn_ctx *c, const BatchView &v, const dcn_params *params, bool
     sa.pending = c->d_pending;
     sa.status = c->d_status;
     sa.ascii = short_fused ? v.d_ascii : nullptr;
+    sa.offsets = v.d_offsets;
+    sa.n_reads = n_reads;
+    sa.wave_kept = c->d_wave_kept;
     DCN_TRY(dcn_launch_scan(sa, tile_bound(c, n_reads, v.b1 - v.b0), false, st));
     DCN_PROF_MARK(DCN_STAGE_SCAN);
 
@@ -299,8 +303,11 @@ int enqueue_batch(dcn_ctx *c, const BatchView &v, const dcn_params *params, bool
     DCN_TRY(dcn_launch_distinct(da, st));
     DCN_PROF_MARK(DCN_STAGE_DISTINCT);
 
-    const dcn_finish_args fa = finish_args(c, n_units, params, v.d_unit_id ? c->d_unit_first_read : nullptr, v.d_offsets, v.d_keep,
-                                           v.d_hits, v.d_total, v.d_report);
+    dcn_finish_args fa = finish_args(c, n_units, params, v.d_unit_id ? c->d_unit_first_read : nullptr, v.d_offsets, v.d_keep,
+                                     v.d_hits, v.d_total, v.d_report);
+    fa.short_counted = short_fused ? 1u : 0u;
+    fa.pending = c->d_pending;
+    fa.wave_kept = c->d_wave_kept;
     DCN_TRY(dcn_launch_finish(fa, st));
     c->scratch_dirty = false;
     // the next pack into the buffer this batch read may start (a batch packed in line between packed-ahead ones -- per-stage
@@ -787,6 +794,7 @@ extern "C" int dcn_ctx_create(const dcn_index *index, uint64_t max_batch_bases, 
     A(d_big, MR + mt / 64 + 1, "big");
     A(d_rec_hash, (max_batch_bases >> c->rec_shift) + 256, "rec_hash");
     A(d_status, 1, "status");
+    A(d_wave_kept, MR / DCN_WAVE + 1, "wave_kept");
     A(d_report, 1, "report");
 #undef A
     }

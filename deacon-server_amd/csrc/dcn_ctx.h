@@ -123,6 +123,9 @@ struct dcn_ctx {
     uint64_t rec_capacity = 0;
     uint64_t *d_set_slots = nullptr;
     dcn_status *d_status = nullptr;
+    // short batches (scan.hip, scan_short): what each wave of the scan kernel kept, one word per 64 reads (kept reads << 32 |
+    // kept bases); every wave of such a batch writes its word and the finish kernel sums them
+    unsigned long long *d_wave_kept = nullptr;
     bool short_fused = true;       // DCN_NO_SHORT_FUSED unset: batches of short unpaired reads are packed inside the scan kernel
     bool last_batch_short = false; // ... and whether the last batch waited for was one (dcn_ctx_last_batch_short)
     dcn_batch_report *d_report = nullptr; // device-pointer API: counters + sticky overflow since the last synchronize

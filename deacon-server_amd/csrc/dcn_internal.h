@@ -174,7 +174,8 @@ struct dcn_status {
     uint32_t run_overflow;         // a unit had more hits in one wave than its run of the record array holds (rec_shift > 0)
     uint32_t bad_offsets;          // the plan kernel met offsets[r] > offsets[r+1] or offsets[r+1] > n_bases: those reads were planned as empty
     uint32_t short_batch;          // the shape kernel (plan.hip) found good offsets and no read above DCN_SHORT_LMAX bases: the pack
-                                   // kernel returns at once and the scan kernel packs its own bases (scan.hip, scan_short)
+                                   // and plan kernels return at once, the scan kernel takes its reads from the offsets and packs
+                                   // its own bases (scan.hip, scan_short), the finish kernel visits the pending units only
     uint32_t shape_bad;            // ... its workgroups' verdicts: a read too long, or an offset out of order or range
     uint32_t shape_done;           // ... and how many of them have given theirs (the last one writes short_batch)
     uint32_t reserved_;
@@ -197,7 +198,7 @@ struct dcn_batch_report {
 struct dcn_scan_args {
     const uint32_t *packed; // 2-bit stream, already offset by DCN_FRONT_PAD words
     const uint32_t *invmask; // 1 bit per base, same padding (in 32-bit words)
-    const dcn_tile *tiles;
+    dcn_tile *tiles;               // read; the short path writes the tile of a unit it hands to the distinct pass
     const uint32_t *tile_read_pos; // dump mode with read-relative positions: position of scan_start in its read
     const uint32_t *n_tiles; // device-side tile count
     uint32_t *unit_tile_first; // n_units: first tile index of each unit (no entry for whole-unit tiles, see dcn_tile)
@@ -242,6 +243,9 @@ struct dcn_scan_args {
     uint32_t nt_combine_xor; // 0: fw + rc, 1: fw ^ rc
     // short path (scan.hip, scan_short): the batch's ASCII, set only when a shape kernel ran in front of the pack; null otherwise
     const uint8_t *ascii;
+    const uint64_t *offsets; // ... and its reads: lane i of workgroup b of the short kernel is read 64 b + i, no tile is read
+    uint32_t n_reads;
+    unsigned long long *wave_kept; // ... and, per workgroup, what it kept: kept reads << 32 | their bases (dcn_ctx::d_wave_kept)
 };
 
 // ---- kernels launched by ctx.hip, dump.hip and classify_api.hip ------------------------------------

@@ -30,6 +30,8 @@ struct dcn_plan_args {
                                 // (status->bad_offsets) instead of being followed outside the batch's buffers
     const uint32_t *newline_flag; // null: status->any_newline; else the word the pack kernel of this batch wrote (it may have
                                   // run ahead of the batch's own status words: ctx.hip, pack one batch ahead)
+    uint32_t short_armed;         // 1: a shape kernel ran in front (ctx.hip, short_fused); the plan kernel returns at once when it
+                                  // raised status->short_batch
 };
 
 struct dcn_distinct_args {
@@ -71,6 +73,11 @@ struct dcn_finish_args {
     uint32_t *hits, *total;
     dcn_batch_report *report; // counters and the sticky overflow word of the batch this chunk belongs to
     const dcn_status *status;
+    // a batch that may be short (ctx.hip, short_fused): when status->short_batch is up the scan kernel decided every unit but
+    // the pending ones and left what each of its waves kept in wave_kept; the kernel then visits the pending units only
+    uint32_t short_counted;
+    const uint32_t *pending;                // status->n_pending units
+    const unsigned long long *wave_kept;    // one word per 64 units: kept reads << 32 | their bases
 };
 
 struct dcn_probe_hashes_args {

@@ -3,6 +3,7 @@
 #include "dcn_internal.h"
 #include "dcn_plan.h"
 #include "dcn_probe.h"
+#include "dcn_short_lane.h"
 
 #include <algorithm>
 
@@ -11,10 +12,10 @@ namespace {
 // ---- A1: effective sequence -> number of windows (src/filter_common.rs:217-229) -------------------------
 __device__ inline uint32_t effective_windows(const uint8_t *ascii, uint64_t off, uint64_t len, uint64_t prefix,
                                              uint32_t k, uint32_t l) {
-    if (len < k) return 0;                      // :217 -- tested on the full read, before the prefix cut
-    uint64_t n = (prefix > 0 && len > prefix) ? prefix : len; // :222-226
-    if (ascii && n > 0 && ascii[off + n - 1] == '\n') n -= 1; // :229 (ascii == null: no read of the batch ends in one)
-    return n >= l ? (uint32_t)(n - l + 1) : 0;
+    if (len < k) return 0;                      // (dcn_window_count says so too: no byte of such a read is looked at)
+    const uint64_t n = (prefix > 0 && len > prefix) ? prefix : len; // :222-226
+    const bool nl = ascii && n > 0 && ascii[off + n - 1] == '\n'; // (ascii == null: no read of the batch ends in one)
+    return dcn_window_count(len, n, nl, k, l); // the rule itself: dcn_short_lane.h, shared with the scan kernel's short path
 }
 
 __device__ inline void write_tile(const dcn_plan_args &a, uint32_t first, uint32_t j, uint64_t off, uint32_t nwin,
@@ -58,6 +59,9 @@ __global__ __launch_bounds__(256) void plan_kernel(dcn_plan_args a) {
     __shared__ uint32_t s_base;
     __shared__ uint32_t long_reads[PLAN_READS];
     __shared__ uint32_t n_long;
+    // a batch the shape kernel declared short is scanned straight from its offsets (scan.hip, scan_short): a read is a lane,
+    // there is no tile to describe and no cursor to advance (the test pack_kernel makes for its own idle grid)
+    if (a.short_armed && a.status->short_batch) return;
     const uint32_t tid = threadIdx.x;
     const uint32_t block_first = blockIdx.x * PLAN_READS;
     const uint32_t block_end = min(a.n_reads, block_first + PLAN_READS);
@@ -475,7 +479,92 @@ __global__ __launch_bounds__(256) void big_insert_kernel(dcn_distinct_args a) {
 }
 
 // ---- A7/A10: decision for units not resolved by the scan kernel + the six counters ----------------------------
+// sum of v over the workgroup (256 threads), valid in thread 0
+__device__ inline unsigned long long block_sum_u64(unsigned long long v, unsigned long long *red /* [4] */) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    __syncthreads(); // (red free again)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+// A short batch (scan.hip, scan_short): the scan kernel decided every unit it did not put on the work list, wrote keep, hits
+// and total for it and left what each wave kept in wave_kept.  What is left are the pending units, few or none: they are decided
+// here as in the general form below, and the six counters follow from those words, the pending units and two offsets.
+__device__ inline void finish_short(const dcn_finish_args &a) {
+    __shared__ unsigned long long red[4];
+    // The grid was sized for a walk over all units before the batch was known to be short.  The work list and n / 64 words
+    // are little work: a few workgroups do it, so that the counters see a few hundred atomics (one word takes ~88 per
+    // microsecond; with all 1,024 workgroups the kernel took 26 us at 10 M reads, most of it those atomics).
+    constexpr uint32_t SHORT_BLOCKS = 128;
+    if (blockIdx.x >= SHORT_BLOCKS) return;
+    // (an overflowed attempt is enqueued again by the caller: its pending units are still put back to zero, its counts dropped)
+    const bool overflow = a.status->rec_overflow || a.status->run_overflow;
+    const uint32_t NP = a.status->n_pending, stride = min(gridDim.x, SHORT_BLOCKS) * blockDim.x;
+    unsigned long long out_seqs = 0, out_bp = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < NP; i += stride) {
+        const uint32_t u = a.pending[i];
+        const uint32_t tot = a.g_total[u], hc = a.g_distinct[u] + (a.g_zero[u] ? 1u : 0u);
+        a.g_total[u] = 0;
+        a.g_hitcnt[u] = 0;
+        a.g_distinct[u] = 0;
+        a.g_zero[u] = 0;
+        const bool keep = dcn_decide(hc, tot, a.abs_threshold, a.rel_threshold, a.deplete);
+        a.keep[u] = keep ? 1 : 0;
+        if (a.hits) a.hits[u] = hc;
+        if (a.total) a.total[u] = tot;
+        if (keep && a.offsets) {
+            out_seqs += 1;
+            out_bp += a.offsets[u + 1] - a.offsets[u];
+        }
+    }
+    if (!overflow && a.offsets) { // the scan kernel's counts: one word per wave, every one written by this batch's scan
+        const uint32_t n_waves = (a.n_units + DCN_WAVE - 1) / DCN_WAVE;
+        for (uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x; i0 < n_waves; i0 += 4 * stride) {
+            unsigned long long v[4]; // four loads in flight
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) v[q] = (uint64_t)i0 + q * stride < n_waves ? a.wave_kept[i0 + q * stride] : 0ull;
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) {
+                out_seqs += v[q] >> 32;
+                out_bp += v[q] & 0xFFFFFFFFull;
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (a.status->bounds) a.report->bounds = a.status->bounds;
+        a.report->short_batch = 1; // (dcn_ctx_last_batch_short)
+        if (overflow) { // sticky, as below
+            atomicOr(&a.report->overflow, (a.status->rec_overflow ? 1u : 0u) | (a.status->run_overflow ? 2u : 0u));
+            if (a.status->rec_overflow) atomicMax(&a.report->need, (a.status->set_cursor + 3) / 4);
+        }
+    }
+    if (overflow || !a.offsets) return; // (bad_offsets is never up here: the shape kernel found the offsets good)
+    out_seqs = block_sum_u64(out_seqs, red);
+    out_bp = block_sum_u64(out_bp, red);
+    if (threadIdx.x != 0) return;
+    // ProcessingStats, src/local_filter.rs:346-371: every read is a unit; filtered = total - output.  The totals come in with
+    // workgroup 0 and each workgroup takes its share of the output off the filtered counters: sums modulo 2^64, whatever the
+    // order of the workgroups, and exact when the last has added its part (the counters are read after the stream is idle).
+    unsigned long long seqs = 0, bp = 0;
+    if (blockIdx.x == 0) {
+        seqs = a.n_units;
+        bp = a.offsets[a.n_units] - a.offsets[0];
+        atomicAdd(&a.report->stats[DCN_STAT_TOTAL_SEQS], seqs);
+        atomicAdd(&a.report->stats[DCN_STAT_TOTAL_BP], bp);
+    }
+    if (out_seqs) atomicAdd(&a.report->stats[DCN_STAT_OUTPUT_SEQ_COUNTER], out_seqs);
+    if (out_bp) atomicAdd(&a.report->stats[DCN_STAT_OUTPUT_BP], out_bp);
+    if (seqs - out_seqs) atomicAdd(&a.report->stats[DCN_STAT_FILTERED_SEQS], seqs - out_seqs);
+    if (bp - out_bp) atomicAdd(&a.report->stats[DCN_STAT_FILTERED_BP], bp - out_bp);
+}
+
 __global__ __launch_bounds__(256) void finish_kernel(dcn_finish_args a) {
+    if (a.short_counted && a.status->short_batch) { // (uniform over the grid)
+        finish_short(a);
+        return;
+    }
     unsigned long long st[DCN_N_STATS] = {0, 0, 0, 0, 0, 0};
     // grid-stride: few blocks, so the six counters see a few thousand atomics instead of one set per 256 units; four
     // units per thread and step, their loads issued together (the loop is latency-bound: 0.036 -> 0.02 ms at 4 M units)

@@ -27,6 +27,7 @@
 #include "dcn_probe.h"
 
 #include "dcn_pack.h"
+#include "dcn_short_lane.h"
 
 #include <atomic>
 #include <type_traits>
@@ -131,13 +132,13 @@ struct WaveShared {
 
 // The LDS of the short path (scan_short below): a batch of single-tile reads whose ASCII the wave packs itself.  The 2-bit
 // words and mask bits of the wave's reads live in a staging area; a tile-relative position fits a byte, and the three
-// per-slot words of a unit's exported run (its base, its capacity, both functions of the owner lane's tile) are looked up
+// per-slot words of a unit's exported run (its base, its capacity, both functions of the owner lane's read) are looked up
 // where a run is written instead of being kept here.  Same total as WaveShared, so the waves per CU do not move.
 constexpr int DCN_SHORT_LMAX = 152;   // longest read of a short batch (dcn_launch_shape)
-constexpr int DCN_STAGE_WORDS = 612;  // 16-base words: 64 reads of DCN_SHORT_LMAX bases, a lead-in of w-1, two cut chunks
+constexpr int DCN_STAGE_WORDS = 612;  // 16-base words: 64 reads of DCN_SHORT_LMAX bases, a lead-in of w-1, a cut chunk at either end
 constexpr int DCN_LSTRIDE8 = 44;      // u8 entries per list row: DCN_LCAP + 4, 11 dwords
 static_assert(DCN_LSTRIDE8 >= DCN_LCAP + 2 && (DCN_LSTRIDE8 / 4) % 2 == 1 && DCN_LSTRIDE8 % 4 == 0, "odd dword stride");
-static_assert(DCN_STAGE_WORDS % 2 == 0 && 16 * DCN_STAGE_WORDS >= 64 * DCN_SHORT_LMAX + 14 + 30, "one pass per full wave");
+static_assert(DCN_STAGE_WORDS % 2 == 0 && 16 * DCN_STAGE_WORDS >= 64 * DCN_SHORT_LMAX + 14 + 30, "a full wave's span fits");
 
 struct WaveSharedShort {
     uint4 tab[16];
@@ -157,7 +158,8 @@ struct WaveSharedShort {
     uint32_t total[DCN_WAVE];
     uint32_t hits[DCN_WAVE];
     uint32_t items[DCN_WAVE];
-    uint32_t unit_of[DCN_WAVE];
+    uint32_t read_len[DCN_WAVE];        // bytes of the lane's read, for the wave's sum of kept bases (a slot's unit is
+                                        // blockIdx.x * DCN_WAVE + slot here: no unit_of)
     uint16_t start[DCN_WAVE + 2];
     uint8_t hraw[DCN_WAVE];             // (at most DCN_SHORT_LMAX hits)
     uint8_t uhits[DCN_WAVE];
@@ -168,10 +170,9 @@ static_assert(sizeof(WaveSharedShort) <= 10240 && sizeof(WaveShared) <= 10240, "
 
 // what scan_short hands to the scan proper for one lane
 struct ShortLane {
-    int lane;         // threadIdx.x, as a value the compiler takes for one of this pass
-    bool have;        // the lane scans a tile in this pass
-    dcn_tile t;       // ... this one, its window count corrected for a trailing '\n'
-    uint32_t s_local; // position of t.scan_start in the staging area, in bases
+    bool have;        // the lane has a read: read blockIdx.x * DCN_WAVE + lane of the batch
+    uint32_t windows; // ... with this many windows (dcn_short_lane.h; 0: the lane scans nothing)
+    uint32_t s_local; // position of the read's first base in the staging area, in bases
 };
 
 #ifndef DCN_EXP
@@ -218,17 +219,21 @@ struct IntTag {
 // hash bits compared and the fw/rc combination are run-time values and the window keys are 64 bits wide (hash bits
 // above, position below).  Only instantiated for W == 0; the default rules never take it, so the kernels above are
 // the same code with or without it.
-// SHORT: the wave was set up by scan_short (below): `sl` holds the lane's tile, and the stream and mask words come from the
-// staging area in `sh` (a WaveSharedShort) at positions relative to it instead of from a.packed / a.invmask.
+// SHORT: the wave was set up by scan_short (below): lane i has read blockIdx.x * DCN_WAVE + i of the batch, a unit of its own
+// with one tile (`sl`), and the stream and mask words come from the staging area in `sh` (a WaveSharedShort) at positions
+// relative to it instead of from a.packed / a.invmask.  No tile descriptor is read; one is written for a unit handed to the
+// distinct pass, which is rare.
 template <int W, bool K128, bool DUMP, bool FAST, bool VAR, bool SHORT, class SH>
 __device__ __forceinline__ void scan_body(const dcn_scan_args &a, SH &sh, const ShortLane &sl) {
     static_assert(!VAR || (W == 0 && !FAST), "the variant path is the generic-w counting / dump kernel");
     static_assert(!SHORT || (W > 0 && !K128 && !DUMP && !FAST && !VAR), "the short path is a counting kernel of fixed w, k <= 32");
     extern __shared__ __align__(16) uint2 dyn_ring[]; // only for W == 0: [w][64] (lkey, rkey); VAR: [w][64] of two u64 keys
 
-    const int lane = SHORT ? sl.lane : (int)threadIdx.x;
+    const int lane = (int)threadIdx.x;
     // (bad_offsets: the plan kernel refused the batch's offsets -- ctx.hip reports it at the next synchronize; its tiles are not looked at)
-    const uint32_t NT = a.status->bad_offsets ? 0u : *a.n_tiles;
+    uint32_t NT;
+    if constexpr (SHORT) NT = a.n_reads; // (a read is a tile)
+    else NT = a.status->bad_offsets ? 0u : *a.n_tiles;
     const uint32_t wave_first = blockIdx.x * DCN_WAVE;
     if (wave_first >= NT) return;
     const uint32_t k = a.k;
@@ -239,8 +244,13 @@ __device__ __forceinline__ void scan_body(const dcn_scan_args &a, SH &sh, const 
     const uint32_t tile_idx = wave_first + lane;
     const bool have_tile = SHORT ? sl.have : tile_idx < NT;
     dcn_tile t;
-    if constexpr (SHORT) t = sl.t;
-    else t = a.tiles[have_tile ? tile_idx : NT - 1];
+    if constexpr (SHORT) {
+        t.scan_start = 0; // (the read's place in the stream is a.offsets[tile_idx], read again where a run is written)
+        t.unit = tile_idx;
+        t.nwf = sl.windows | (1u << 30);
+    } else {
+        t = a.tiles[have_tile ? tile_idx : NT - 1];
+    }
     if (!have_tile) t.nwf = 0;
     const uint32_t carry = t.carry();
     const uint32_t nwc = t.n_windows() ? t.n_windows() + carry : 0; // windows this lane evaluates
@@ -263,8 +273,10 @@ __device__ __forceinline__ void scan_body(const dcn_scan_args &a, SH &sh, const 
     sh.uhits[lane] = 0;
     if constexpr (!SHORT) sh.ucap[lane] = 0;
     if (head) {
-        sh.unit_of[uslot] = t.unit;
-        if constexpr (!SHORT) sh.run_base[uslot] = (t.scan_start + carry) >> a.rec_shift;
+        if constexpr (!SHORT) {
+            sh.unit_of[uslot] = t.unit;
+            sh.run_base[uslot] = (t.scan_start + carry) >> a.rec_shift;
+        }
         bool loc = false;
         if (!DUMP) {
             if (t.whole_unit()) { // the unit's only tile is this lane's
@@ -314,18 +326,18 @@ __device__ __forceinline__ void scan_body(const dcn_scan_args &a, SH &sh, const 
         else return a.invmask[i];
     };
     const int64_t s = SHORT ? (int64_t)sl.s_local : (int64_t)t.scan_start;
-    // SHORT: a unit's run of the record array (mid-scan flush, or more hits than the ring holds) is described by its owner
-    // lane's tile, read again where a run is written, which is rare
+    // SHORT: a unit's run of the record array (mid-scan flush) starts at its owner lane's read, whose offset is read again
+    // where a run is written, which is rare
     auto run_cap = [&](uint32_t us, uint32_t us_windows) -> uint32_t {
         if constexpr (SHORT) {
-            const uint64_t first_win = a.tiles[wave_first + us].scan_start;
+            const uint64_t first_win = a.offsets[wave_first + us];
             return (uint32_t)(((first_win + us_windows + l - 1) >> a.rec_shift) - (first_win >> a.rec_shift));
         } else {
             return sh.ucap[us];
         }
     };
     auto run_slot0 = [&](uint32_t us) -> uint64_t {
-        if constexpr (SHORT) return a.tiles[wave_first + us].scan_start >> a.rec_shift;
+        if constexpr (SHORT) return a.offsets[wave_first + us] >> a.rec_shift;
         else return sh.run_base[us];
     };
     [[maybe_unused]] const uint64_t p_limit = SHORT ? (uint64_t)16 * DCN_STAGE_WORDS : a.stream_bases; // (DCN_DEBUG_BOUNDS)
@@ -690,7 +702,10 @@ __device__ __forceinline__ void scan_body(const dcn_scan_args &a, SH &sh, const 
                             } else {
                                 a.status->run_overflow = 1; // (only with rec_shift > 0; the batch is run again)
                             }
-                            if (hash[u] == 0) a.g_zero[sh.unit_of[o_uslot[u]]] = 1;
+                            if (hash[u] == 0) {
+                                if constexpr (SHORT) a.g_zero[wave_first + o_uslot[u]] = 1;
+                                else a.g_zero[sh.unit_of[o_uslot[u]]] = 1;
+                            }
                         }
                         if (run_head) { // after every lane of the run has read the old length: one update per run
                             const unsigned long long later = hm_all & ~((2ull << lane) - 1);
@@ -1046,12 +1061,13 @@ __device__ __forceinline__ void scan_body(const dcn_scan_args &a, SH &sh, const 
 
     // ---- units left to the distinct pass: run lengths, hit totals, enrolment ------------------------------------------
     if (any_rec && lane == 0) a.status->any_records = 1;
+    bool enrol = false;
     {
         const bool pending = have_tile && !sh.lok[uslot] && !(DCN_EXP & 1024);
-        bool enrol = false;
         if (pending) {
             const uint32_t th = head ? sh.uhits[uslot] : 0u; // the run hangs on the unit's first tile in this wave
-            a.tile_hits[tile_idx] = th;
+            // (SHORT: the distinct pass looks at the tile of an enrolled unit only, and no other pass at any)
+            if (!SHORT || th) a.tile_hits[tile_idx] = th;
             // one atomic per (wave, unit) with hits; whoever finds the unit's count at zero puts it on the work list
             // (a unit without any hit needs no distinct pass: its count stays 0)
             if (th) enrol = atomicAdd(&a.g_hitcnt[t.unit], th) == 0u;
@@ -1067,43 +1083,60 @@ __device__ __forceinline__ void scan_body(const dcn_scan_args &a, SH &sh, const 
                     a.unit_tile_first[t.unit] = tile_idx;
                     a.unit_tile_count[t.unit] = 1;
                 }
+                if constexpr (SHORT) { // ... and no tile: the distinct pass finds the unit's run through this one
+                    dcn_tile wt = t;
+                    wt.scan_start = a.offsets[tile_idx];
+                    a.tiles[tile_idx] = wt;
+                }
             }
         }
     }
 
     // ---- results of the units this wave owns --------------------------------------------------------------
+    [[maybe_unused]] bool kept = false; // SHORT: this lane wrote a result, and it was "keep"
     if (head && have_tile) {
         uint32_t tot = sh.total[uslot];
-        if (sh.lok[uslot]) {
-            uint32_t hc = sh.hits[uslot];
-            a.keep[t.unit] = dcn_decide(hc, tot, a.abs_threshold, a.rel_threshold, a.deplete) ? 1 : 0;
+        // SHORT: a read lies in this wave alone.  After a mid-scan flush one without a hit is decided here as well, from
+        // its complete total; only a unit on the work list is left to the distinct pass and the finish kernel.
+        if (sh.lok[uslot] || (SHORT && !enrol)) {
+            uint32_t hc = sh.lok[uslot] ? sh.hits[uslot] : 0u;
+            kept = dcn_decide(hc, tot, a.abs_threshold, a.rel_threshold, a.deplete);
+            a.keep[t.unit] = kept ? 1 : 0;
             if (a.hits) a.hits[t.unit] = hc;
             if (a.total) a.total[t.unit] = tot;
-            a.unit_state[t.unit] = 1;
+            if constexpr (!SHORT) a.unit_state[t.unit] = 1; // (SHORT: the finish kernel walks the work list, not the units)
         } else if (tot) {
             atomicAdd(&a.g_total[t.unit], tot);
         }
     }
+    // SHORT: the reads this wave kept and their bases (a trailing newline counts, as in the finish kernel) go into the wave's
+    // word of wave_kept, one plain store; the finish kernel sums the words and adds the pending units.  Every wave writes
+    // its word, so nothing has to be zero beforehand.  The lengths wait in LDS (scan_short): no register lives through the
+    // scan for them.  (Two atomics per wave on 64 counter shards instead of the store: the kernel took 60 to 160 us longer,
+    // more than the finish kernel gave back -- profiles/short_offsets_ab.txt section 3.)
+    if constexpr (SHORT) {
+        const unsigned long long kb = __ballot(kept);
+        uint32_t bp = kept ? sh.read_len[lane] : 0u;
+        bp = wave_last_u32(wave_inclusive_scan_u32(bp, lane));
+        if (lane == 0) a.wave_kept[blockIdx.x] = ((unsigned long long)__popcll(kb) << 32) | bp;
+    }
 }
 
 // ---- the short path: a batch of single-tile reads, packed by the wave that scans them -------------------------------
-// dcn_status::short_batch (the shape kernel, plan.hip): every read of the batch has at most DCN_SHORT_LMAX bases, the pack
-// kernel did not run, and the plan ran without newline knowledge.  The wave's 64 tiles are 64 whole reads.  Tiles follow the
-// stream inside a planning block's range, reads without a tile leave gaps, and the ranges of different blocks lie in any
-// order: the lanes form RUNS of tiles that are (nearly) contiguous in the stream, almost always one.  Each run's ASCII span
-// [first scan_start - (w-1), last read's end) is loaded as whole 16-byte chunks of the address space (the base pointer may
-// have any alignment), packed, and written to the staging area, one 2-bit word and 16 mask bits per chunk; the scan then
-// works on positions relative to the staging area.  Lanes whose runs do not fit the staging area together (many runs: a
-// batch of mostly tile-less reads) are scanned in a further pass of the same code, so any wave is handled.
+// dcn_status::short_batch (the shape kernel, plan.hip): the offsets are non-decreasing inside the stream and every read of
+// the batch has at most DCN_SHORT_LMAX bases; neither the pack nor the plan kernel did anything.  Lane i of workgroup b is
+// read 64 b + i of the batch, with the windows dcn_short_lane.h gives it.  A wave's reads are contiguous in the stream (one
+// offsets array), so their ASCII is ONE span, [offsets[64 b] - (w-1), offsets[min(64 b + 64, n)]): it is loaded as whole
+// 16-byte chunks of the address space (the base pointer may have any alignment), packed, and written to the staging area,
+// one 2-bit word and 16 mask bits per chunk; the scan then works on positions relative to the staging area.  A read
+// without a window keeps its lane, scans nothing and gets its decision (total 0) from the scan body like every other.
 template <int W>
 __device__ __forceinline__ void scan_short(const dcn_scan_args &a, WaveSharedShort &sh) {
-    const uint32_t NT = a.status->bad_offsets ? 0u : *a.n_tiles;
     const uint32_t wave_first = blockIdx.x * DCN_WAVE;
-    if (wave_first >= NT) return;
-    const uint32_t n_have = min(NT - wave_first, (uint32_t)DCN_WAVE);
-    const uint32_t l = a.k + W - 1;
+    if (wave_first >= a.n_reads) return;
+    const uint32_t n_have = min(a.n_reads - wave_first, (uint32_t)DCN_WAVE);
     const uint64_t n_bases = a.stream_bases;
-    const uint64_t a16 = reinterpret_cast<uintptr_t>(a.ascii) & 15;
+    const uint32_t a16 = (uint32_t)(reinterpret_cast<uintptr_t>(a.ascii) & 15);
     const uint8_t *abase = a.ascii - a16; // chunk c = the 16 bytes at abase + 16 c; stream base p lies in chunk (a16 + p) >> 4
 
     // 16 bases of the stream: bytes in front of it read as 0, bytes behind it as 'A' (as pack_kernel packs them)
@@ -1119,78 +1152,45 @@ __device__ __forceinline__ void scan_short(const dcn_scan_args &a, WaveSharedSho
         return make_uint4(v[0], v[1], v[2], v[3]);
     };
 
-    constexpr int64_t GAP_CHUNKS = 2; // a gap of up to two chunks is staged with its run: cheaper than a run's own lead-in
-    for (uint32_t lo = 0; lo < n_have;) { // wave-uniform; one pass unless the runs outgrow the staging area
-        // The lane's tile and what follows from it are read again in every pass, and the lane number is a fresh value in each:
-        // otherwise everything the scan derives from the lane alone (a dozen masks and LDS addresses) is computed in front
-        // of this loop and held in registers across it, which the scan's phase A has no room for.  Measured on this kernel
-        // (profiles/short_fused_isa.txt): with the empty asm no VGPR spill and no scratch, without it 19 spilled VGPRs and 80 B.
-        int lane = threadIdx.x;
-        asm volatile("" : "+v"(lane));
-        const bool have = (uint32_t)lane < n_have;
-        const dcn_tile t = a.tiles[wave_first + (have ? (uint32_t)lane : n_have - 1)];
-        // the plan knew of no newline: the tile ends where its read ends
-        const uint64_t start = t.scan_start, end = start + t.n_windows() + l - 1;
-        uint32_t nw = t.n_windows();
-        if (have && nw && end <= n_bases && a.ascii[end - 1] == '\n') nw -= 1; // src/filter_common.rs:229; a read left without a
-                                                                               // window keeps its lane and gets total = 0
-        const int64_t cf = ((int64_t)(a16 + start) - (int64_t)(W - 1)) >> 4; // first and last chunk of this lane's span (cf may be -1)
-        const int64_t cl = (int64_t)(a16 + end - 1) >> 4;
-        const int64_t cl_prev = __shfl_up((long long)cl, 1, 64);
-        const uint64_t start_prev = (uint64_t)__shfl_up((long long)start, 1, 64);
-        const bool in = (uint32_t)lane >= lo && have;
-        const bool newrun = (uint32_t)lane == lo || start < start_prev || cf > cl_prev + 1 + GAP_CHUNKS;
-        const int64_t cost64 = newrun ? cl - cf + 1 : cl - cl_prev;
-        const uint32_t cost = in ? (uint32_t)(cost64 > 0 ? cost64 : 0) : 0u;
-        const uint32_t incl = wave_inclusive_scan_u32(cost, lane);
-        // (a single read's span is at most (DCN_SHORT_LMAX + W - 1 + 15) / 16 + 1 chunks: lane `lo` always fits)
-        // (... and a pass always moves on by a lane, whatever the tiles say)
-        const uint32_t hi = max((uint32_t)__popcll(__ballot(have && incl <= (uint32_t)DCN_STAGE_WORDS)), lo + 1);
-        const bool act = in && (uint32_t)lane < hi && incl <= (uint32_t)DCN_STAGE_WORDS;
-        const unsigned long long heads = __ballot(act && newrun);
-        const unsigned long long mine = heads & ((2ull << lane) - 1);
-        const uint32_t head_lane = mine ? 63u - (uint32_t)__clzll(mine) : lo;
-        const uint32_t excl = incl - cost;
-        const uint32_t wb_h = __shfl(excl, head_lane, 64);
-        const int64_t cf_h = __shfl((long long)cf, head_lane, 64);
-        const uint32_t total_words = __shfl(incl, hi - 1, 64);
-        __syncthreads(); // (the previous pass has finished with the staging area)
-        for (unsigned long long rest = heads; rest;) {
-            const int h = __ffsll((long long)rest) - 1;
-            rest &= rest - 1;
-            const uint32_t wb = __shfl(excl, h, 64);
-            const int64_t c0 = __shfl((long long)cf, h, 64);
-            const uint32_t we = rest ? __shfl(excl, __ffsll((long long)rest) - 1, 64) : total_words;
-            for (uint32_t i0 = 0; i0 < we - wb; i0 += 4 * DCN_WAVE) { // four chunks per lane in flight
-                uint4 v[4];
+    // (no pass loop around the scan body any more, and with it went the spill that the lane number once caused there:
+    // profiles/short_offsets_isa.txt)
+    const int lane = threadIdx.x;
+    const bool have = (uint32_t)lane < n_have;
+    const uint32_t r = wave_first + (have ? (uint32_t)lane : n_have - 1);
+    const uint64_t off = a.offsets[r], end = a.offsets[r + 1];
+    // src/filter_common.rs:229 (a read below l bases has no window with or without the newline: its byte is not looked at)
+    const bool nl = end - off >= a.k + W - 1 && a.ascii[end - 1] == '\n';
+    const dcn_short_span sp = dcn_short_lane(off, end, nl, a.k, W, a16);
+    // the wave's span: from the first lane's first chunk to the last read's last chunk (c0 may be -1)
+    const int64_t c0 = __shfl((long long)sp.chunk_first, 0, 64);
+    const int64_t c1 = __shfl((long long)sp.chunk_last, (int)n_have - 1, 64);
+    const uint32_t words = (uint32_t)min((int64_t)DCN_STAGE_WORDS, max((int64_t)0, c1 - c0 + 1));
+    for (uint32_t i0 = 0; i0 < words; i0 += 4 * DCN_WAVE) { // four chunks per lane in flight
+        uint4 v[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const uint32_t i = i0 + q * DCN_WAVE + lane;
-                    v[q] = make_uint4(0, 0, 0, 0);
-                    if (i < we - wb) v[q] = load_chunk(c0 + i);
-                }
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t i = i0 + q * DCN_WAVE + lane;
+            v[q] = make_uint4(0, 0, 0, 0);
+            if (i < words) v[q] = load_chunk(c0 + i);
+        }
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const uint32_t i = i0 + q * DCN_WAVE + lane;
-                    if (i < we - wb && wb + i < (uint32_t)DCN_STAGE_WORDS) {
-                        sh.stage_p[wb + i] = dcn_pack4(v[q].x) | (dcn_pack4(v[q].y) << 8) | (dcn_pack4(v[q].z) << 16) | (dcn_pack4(v[q].w) << 24);
-                        sh.stage_m16[wb + i] = (uint16_t)(dcn_invalid4(v[q].x) | (dcn_invalid4(v[q].y) << 4) | (dcn_invalid4(v[q].z) << 8) |
-                                                          (dcn_invalid4(v[q].w) << 12));
-                    }
-                }
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t i = i0 + q * DCN_WAVE + lane;
+            if (i < words) {
+                sh.stage_p[i] = dcn_pack4(v[q].x) | (dcn_pack4(v[q].y) << 8) | (dcn_pack4(v[q].z) << 16) | (dcn_pack4(v[q].w) << 24);
+                sh.stage_m16[i] = (uint16_t)(dcn_invalid4(v[q].x) | (dcn_invalid4(v[q].y) << 4) | (dcn_invalid4(v[q].z) << 8) |
+                                             (dcn_invalid4(v[q].w) << 12));
             }
         }
-        ShortLane sl;
-        sl.lane = lane;
-        sl.have = act;
-        sl.t = t;
-        sl.t.nwf = act ? ((t.nwf & 0xC0000000u) | nw) : 0u;
-        // (w-1 <= s_local, s_local + read length <= 16 * DCN_STAGE_WORDS; an idle lane scans nothing, from the area's front)
-        sl.s_local = act ? (uint32_t)((int64_t)(a16 + start) - 16 * cf_h + 16 * (int64_t)wb_h) : 16u;
-        __syncthreads();
-        scan_body<W, false, false, false, false, true>(a, sh, sl);
-        lo = hi;
     }
+    sh.read_len[lane] = have ? (uint32_t)(end - off) : 0u;
+    ShortLane sl;
+    sl.have = have;
+    sl.windows = have ? sp.windows : 0u;
+    // (w-1 <= s_local, s_local + read length <= 16 * DCN_STAGE_WORDS; an idle lane scans nothing, from the area's front)
+    sl.s_local = have ? (uint32_t)((int64_t)(a16 + off) - 16 * c0) : 16u;
+    __syncthreads();
+    scan_body<W, false, false, false, false, true>(a, sh, sl);
 }
 
 #ifndef DCN_SHORT_FUSED
@@ -1234,8 +1234,10 @@ int launch_w(const dcn_scan_args &args, uint32_t blocks, bool dump, bool k128, s
     } while (0)
     const bool fast = !dump && args.early_out_max_items != 0;
     if constexpr (dcn_scan_has_short<W> && !VAR) {
-        if (args.ascii && !k128 && !dump && !fast)
-            hipLaunchKernelGGL((scan_kernel<W, false, false, false, false, true>), dim3(blocks), dim3(DCN_WAVE), 0, stream, args);
+        // (a read is a lane there: one workgroup per 64 reads, whatever the tile bound of the classic grid is)
+        if (args.ascii && !k128 && !dump && !fast && args.n_reads)
+            hipLaunchKernelGGL((scan_kernel<W, false, false, false, false, true>), dim3((args.n_reads + DCN_WAVE - 1) / DCN_WAVE),
+                               dim3(DCN_WAVE), 0, stream, args);
     }
     if (k128) {
         if (dump) DCN_LAUNCH(true, true, false);
