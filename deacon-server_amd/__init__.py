@@ -5,9 +5,9 @@ from . import _native, client, distributed, server
 from ._native import DeaconHipError, build, declared_symbols
 from .filter import (DEFAULT_KMER_LENGTH, DEFAULT_WINDOW_SIZE, AnchorMap, Placer, Classifier, DepthTracker, FilterProcessor, Index, IndexBuilder, IndexSet, Locator, PendingBatch, PinnedBuffer,
                      concat_reads, get_minimizer_hashes_and_positions, pack_ascii, paired_should_keep,
-                     get_minimizer_variant, set_minimizer_variant, stats_allreduce, unpaired_should_keep, VERIFY_OVER, VERIFY_UNPLACED)
+                     get_minimizer_variant, set_minimizer_variant, stats_allreduce, unpaired_should_keep, VERIFY_OVER, VERIFY_UNPLACED, cigar_string)
 
 __all__ = ["DeaconHipError", "build", "declared_symbols", "Index", "IndexBuilder", "IndexSet", "Classifier", "Locator", "DepthTracker", "AnchorMap", "Placer", "FilterProcessor", "PinnedBuffer", "PendingBatch", "concat_reads",
            "pack_ascii", "stats_allreduce", "set_minimizer_variant", "get_minimizer_variant",
            "get_minimizer_hashes_and_positions", "unpaired_should_keep", "paired_should_keep",
-           "DEFAULT_KMER_LENGTH", "DEFAULT_WINDOW_SIZE", "VERIFY_OVER", "VERIFY_UNPLACED"]
+           "DEFAULT_KMER_LENGTH", "DEFAULT_WINDOW_SIZE", "VERIFY_OVER", "VERIFY_UNPLACED", "cigar_string"]

@@ -153,6 +153,7 @@ class VerifyParams(C.Structure):
 VERIFY_MAX_EDITS = 1023  # DCN_VERIFY_MAX_EDITS
 VERIFY_OVER = 0xFFFFFFFE  # DCN_VERIFY_OVER
 VERIFY_UNPLACED = 0xFFFFFFFF  # DCN_VERIFY_UNPLACED
+CIGAR_INS, CIGAR_DEL, CIGAR_EQUAL, CIGAR_DIFF = 1, 2, 7, 8  # DCN_CIGAR_*: BAM's codes of the ops of dcn_align_batch
 
 
 def build(force=False, jobs=6):
@@ -265,10 +266,11 @@ _SIGNATURES = {
     "dcn_anchor_map_keep_bases": (C.c_int, [_vp]),
     "dcn_anchor_map_fetch": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
     "dcn_verify_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "dcn_align_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64]),
 }
 
 _lib = None
-ABI = (1, 13)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 14)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

@@ -3805,36 +3805,58 @@ struct MapArgs {
     // `verify`: map's placements, each compared base by base with the reference (dcn_verify_batch)
     bool verify = false, verified_only = false;
     unsigned max_edits = DCN_VERIFY_MAX_EDITS, max_div = 200;
+    // `align`: verify, and the alignment of every verified placement as cg:Z: (dcn_align_batch); verify is set as well
+    bool align = false;
 };
 
 // one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
 // hits of the read), ns (positions of the read)
 // (`verify`: edits = what dcn_verify_batch said of the row, and the line gains ve and, for a verified row, NM, with column
 // 10 = column 11 - NM; map passes DCN_VERIFY_UNPLACED, which no placed row has, and prints what it always did)
+// (`align`: cigar = the n_ops runs of a verified row, as dcn_align_batch gives them: column 10 = its '=' bases, column 11 =
+// all its bases, and cg:Z: follows NM)
 void append_paf(std::string &rows, const std::string &read_name, uint32_t read_len, const dcn_split_placement &p,
-                const std::string &record_name, uint32_t record_len, uint32_t k, uint32_t edits = DCN_VERIFY_UNPLACED) {
+                const std::string &record_name, uint32_t record_len, uint32_t k, uint32_t edits = DCN_VERIFY_UNPLACED,
+                const uint32_t *cigar = nullptr, uint64_t n_ops = 0) {
     const uint64_t on_read = p.read_end - p.read_start, on_ref = p.ref_end - p.ref_start;
     const bool verified = edits != DCN_VERIFY_UNPLACED && edits != DCN_VERIFY_OVER;
-    const uint64_t matches = verified ? std::max(on_read, on_ref) - edits : std::min<uint64_t>((uint64_t)p.votes * k, on_read);
+    uint64_t matches = verified ? std::max(on_read, on_ref) - edits : std::min<uint64_t>((uint64_t)p.votes * k, on_read);
+    uint64_t block = std::max(on_read, on_ref);
+    if (verified && cigar) {
+        matches = block = 0;
+        for (uint64_t q = 0; q < n_ops; ++q) {
+            block += cigar[q] >> 4;
+            if ((cigar[q] & 15u) == DCN_CIGAR_EQUAL) matches += cigar[q] >> 4;
+        }
+    }
     rows.append(read_name);
     rows += '\t' + std::to_string(read_len) + '\t' + std::to_string(p.read_start) + '\t' + std::to_string(p.read_end) + '\t';
     rows += p.reverse ? '-' : '+';
     rows += '\t' + record_name + '\t' + std::to_string(record_len) + '\t' + std::to_string(p.ref_start) + '\t' +
-            std::to_string(p.ref_end) + '\t' + std::to_string(matches) + '\t' + std::to_string(std::max(on_read, on_ref)) + '\t' +
+            std::to_string(p.ref_end) + '\t' + std::to_string(matches) + '\t' + std::to_string(block) + '\t' +
             std::to_string(p.mapq);
     rows += "\tcm:i:" + std::to_string(p.votes) + "\trk:i:" + std::to_string(p.rank) + "\tnp:i:" + std::to_string(p.n_placed) +
             "\trv:i:" + std::to_string(p.rival_votes) + "\tna:i:" + std::to_string(p.n_anchors) + "\tns:i:" +
             std::to_string(p.n_positions);
     if (verified) rows += "\tve:i:1\tNM:i:" + std::to_string(edits);
     else if (edits == DCN_VERIFY_OVER) rows += "\tve:i:0";
+    if (verified && cigar) {
+        rows += "\tcg:Z:";
+        for (uint64_t q = 0; q < n_ops; ++q) {
+            const uint32_t op = cigar[q] & 15u;
+            rows += std::to_string(cigar[q] >> 4);
+            rows += op == DCN_CIGAR_EQUAL ? '=' : op == DCN_CIGAR_DIFF ? 'X' : op == DCN_CIGAR_INS ? 'I' : 'D';
+        }
+        if (n_ops == 0) rows += '*'; // (two empty extents: no placement call reports one)
+    }
     rows += '\n';
 }
 
 int run_map(const MapArgs &a) {
     const Stopwatch watch;
     AnchorRef R;
-    load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, a.verify ? "DCN_CLI_VERIFY_BATCH_BASES" : "DCN_CLI_MAP_BATCH_BASES", a.quiet,
-                    a.verify);
+    load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, 
+                    a.align ? "DCN_CLI_ALIGN_BATCH_BASES" : a.verify ? "DCN_CLI_VERIFY_BATCH_BASES" : "DCN_CLI_MAP_BATCH_BASES", a.quiet, a.verify);
     Context &ctx = *R.ctx;
     dcn_place_split_params prm = {};
     prm.band_bases = a.band;
@@ -3845,6 +3867,7 @@ int run_map(const MapArgs &a) {
     FastxReader rd(a.input);
     uint64_t reads_in = 0, placed = 0, split_reads = 0, placements = 0, mapq60 = 0, mapq0 = 0;
     uint64_t verified = 0, unverified = 0, edits_sum = 0, verified_bases = 0;
+    uint64_t op_bases[16] = {}, cigar_ops = 0; // (align: bases per op code, and runs)
     dcn_verify_params vprm = {};
     vprm.max_edits = a.max_edits;
     vprm.max_permille = a.max_div;
@@ -3853,7 +3876,8 @@ int run_map(const MapArgs &a) {
     Batch b;
     std::vector<uint64_t> place_off;
     std::vector<dcn_split_placement> pl;
-    std::vector<uint32_t> edits;
+    std::vector<uint32_t> edits, cigar;
+    std::vector<uint64_t> cigar_off;
     std::string rows;
     for_each_batch(rd, b, R.batch_bases, R.batch_reads, [&] {
         const uint32_t n_reads = (uint32_t)b.recs.size();
@@ -3862,7 +3886,19 @@ int run_map(const MapArgs &a) {
         pl.resize((size_t)n_reads * a.max_placements);  // (never more than max_placements per read)
         deacon::check(dcn_place_split_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &prm, place_off.data(),
                                             pl.data(), pl.size(), nullptr));
-        if (a.verify) { // the same reads, the rows just placed
+        if (a.align) { // the same reads, the rows just placed: their distances and the runs of the verified ones
+            edits.resize(place_off[n_reads]);
+            cigar_off.assign(place_off[n_reads] + 1, 0);
+            for (int attempt = 0;; ++attempt) {
+                const int rc = dcn_align_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), pl.data(),
+                                               place_off[n_reads], edits.data(), cigar_off.data(), cigar.data(), cigar.size());
+                if (rc != DCN_ERR_CAPACITY || attempt) {
+                    deacon::check(rc);
+                    break;
+                }
+                cigar.resize(cigar_off[place_off[n_reads]]); // (the size the first call reported)
+            }
+        } else if (a.verify) {
             edits.resize(place_off[n_reads]);
             deacon::check(dcn_verify_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), pl.data(),
                                            place_off[n_reads], edits.data()));
@@ -3889,6 +3925,14 @@ int run_map(const MapArgs &a) {
                         verified_bases += std::max<uint64_t>(p.read_end - p.read_start, p.ref_end - p.ref_start);
                     }
                 }
+                if (a.align) {
+                    const uint32_t *const runs = cigar.data() + cigar_off[q];
+                    const uint64_t n_ops = cigar_off[q + 1] - cigar_off[q];
+                    cigar_ops += n_ops;
+                    for (uint64_t o = 0; o < n_ops; ++o) op_bases[runs[o] & 15u] += runs[o] >> 4;
+                    append_paf(rows, name, rec.seq_len, p, R.names[p.record], R.lens[p.record], R.k, edits[q], runs, n_ops);
+                    continue;
+                }
                 append_paf(rows, name, rec.seq_len, p, R.names[p.record], R.lens[p.record], R.k, a.verify ? edits[q] : DCN_VERIFY_UNPLACED);
             }
         }
@@ -3900,6 +3944,10 @@ int run_map(const MapArgs &a) {
         if (a.verify)
             std::fprintf(stderr, "Verified %llu of %llu placements (%llu edits over %llu bases)\n", (unsigned long long)verified,
                          (unsigned long long)placements, (unsigned long long)edits_sum, (unsigned long long)verified_bases);
+        if (a.align)
+            std::fprintf(stderr, "Aligned %llu placements in %llu runs (%llu =, %llu X, %llu I, %llu D)\n", (unsigned long long)verified,
+                         (unsigned long long)cigar_ops, (unsigned long long)op_bases[DCN_CIGAR_EQUAL], (unsigned long long)op_bases[DCN_CIGAR_DIFF],
+                         (unsigned long long)op_bases[DCN_CIGAR_INS], (unsigned long long)op_bases[DCN_CIGAR_DEL]);
         std::fprintf(stderr, "Mapped %llu of %llu reads in %llu placements (%llu reads with two or more) in %s\n",
                      (unsigned long long)placed, (unsigned long long)reads_in, (unsigned long long)placements,
                      (unsigned long long)split_reads, fmt_duration(secs).c_str());
@@ -3919,6 +3967,11 @@ int run_map(const MapArgs &a) {
                         "  \"edits\": %llu,\n  \"verified_bases\": %llu,\n",
                     a.max_edits, a.max_div, (unsigned long long)verified, (unsigned long long)unverified, (unsigned long long)edits_sum,
                     (unsigned long long)verified_bases);
+        if (a.align)
+            appendf(js, "  \"matches\": %llu,\n  \"mismatches\": %llu,\n  \"insertions\": %llu,\n  \"deletions\": %llu,\n"
+                        "  \"cigar_ops\": %llu,\n",
+                    (unsigned long long)op_bases[DCN_CIGAR_EQUAL], (unsigned long long)op_bases[DCN_CIGAR_DIFF],
+                    (unsigned long long)op_bases[DCN_CIGAR_INS], (unsigned long long)op_bases[DCN_CIGAR_DEL], (unsigned long long)cigar_ops);
         appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
         for (uint32_t r = 0; r < R.n_records; ++r) {
             js += (r ? ",\n    {" : "\n    {");
@@ -4065,6 +4118,7 @@ void usage() {
                  "  map     Report up to N placements per read on a reference, each with a mapping quality, as PAF\n"
                  "  map-pairs  Place the two mates of each pair jointly: proper pairs, rescued mates, insert sizes, as PAF\n"
                  "  verify  As map, with every placement compared base by base with the reference: edit distance, as PAF\n"
+                 "  align   As verify, with the alignment of every verified placement: cg:Z: with = X I D, as PAF\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -4261,6 +4315,43 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "complemented on the - strand, and the record's extent, global over both.  A base that is not ACGT (N) matches\n"
                "nothing.  The threshold is min(-e, longer extent * --max-div / 1000): both are conventions, not measured optima.\n"
                "Placements, qualities and every other column and tag are map's for the same arguments.\n"
+               "Mates are independent here: one input.\n";
+    else if (sub == "align")
+        text = "Report up to N placements of each read on a reference, verify each base by base and print its alignment, as PAF\n\n"
+               "Usage: deacon-hip align [OPTIONS] <REF> [READS]\n\n"
+               "Arguments:\n"
+               "  <REF>     Path to the reference fastx file: its records are numbered and named in file order\n"
+               "  [READS]   Optional path to fastx file (or - for stdin; gz, bgzf, zst, xz and bz2 found by content) [default: -]\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Keys that may anchor: a minimizer index file, whose k and w are used\n"
+               "                                 [default: the minimizers of <REF> at -k / -w]\n"
+               "  -k <K>                         K-mer length without -x [default: 31]\n"
+               "  -w <W>                         Minimizer window size without -x [default: 15]\n"
+               "  -o, --output <OUTPUT>          PAF, one line per placement, as verify prints it (- for stdout) [default: -].  For\n"
+               "                                 a verified placement (ve:i:1) cg:Z:<cigar> follows NM:i:<edits>, column 10 is\n"
+               "                                 the number of = bases of the alignment and column 11 the number of all its\n"
+               "                                 bases (= X I D).  A placement over the threshold (ve:i:0) is verify's line\n"
+               "  -e, --max-edits <N>            Verified means at most N edits (0..1023) [default: 1023, a convention]\n"
+               "      --max-div <N>              ... and at most N per 1000 bases of the longer extent (0..1000) [default: 200,\n"
+               "                                 a convention]\n"
+               "      --verified-only            No line for a placement over the threshold\n"
+               "  -N, --max-placements <N>       Placements per read, each from the anchor hits no earlier one explained (1..8)\n"
+               "                                 [default: 4]\n"
+               "      --band <N>                 Width of a diagonal band in bases [default: 256, a convention]\n"
+               "  -a, --min-votes <N>            Minimum number of anchor hits in a placement's cell [default: 2, as filter's -a,\n"
+               "                                 a convention]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per read (0 = entire read) [default: 0]\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file: verify's, and matches, mismatches, insertions,\n"
+               "                                 deletions (bases of = X I D) and cigar_ops (runs) over the verified placements\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
+               "  -h, --help                     Print help\n\n"
+               "Alignment: global over the read's extent (reverse-complemented on the - strand) and the record's extent, at the\n"
+               "Levenshtein distance that verify reports, written in the record's direction: = a base of both that is equal, X a\n"
+               "base of both that differs, I a base of the read alone, D a base of the record alone.  Among the alignments of that\n"
+               "distance the one printed is fixed by a rule (from the end of both extents: X before I before D before =), so the\n"
+               "output does not depend on how the work is cut.  No soft clips, no extension over the read's flanks, no SAM.\n"
+               "Placements, qualities, thresholds and every other column and tag are verify's for the same arguments.\n"
                "Mates are independent here: one input.\n";
     else if (sub == "map-pairs")
         text = "Place the two mates of each pair jointly on a reference: proper pairs, rescued mates and insert sizes, as PAF\n\n"
@@ -4552,9 +4643,10 @@ int main(int argc, char **argv) {
             if (pos.size() > 2) die("place takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[2] + "')");
             return run_place(a);
         }
-        if (args[0] == "map" || args[0] == "verify") {
+        if (args[0] == "map" || args[0] == "verify" || args[0] == "align") {
             MapArgs a;
-            a.verify = args[0] == "verify";
+            a.align = args[0] == "align";
+            a.verify = a.align || args[0] == "verify";
             std::vector<std::string> pos;
             auto number = [&](const std::string &v, const char *flag, long long lo, long long hi) {
                 char *end = nullptr;

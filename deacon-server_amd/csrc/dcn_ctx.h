@@ -16,6 +16,7 @@
 
 struct dcn_split_round; // (dcn_place.h)
 struct dcn_verify_item; // (dcn_verify.h)
+struct dcn_align_work;  // (dcn_verify.h)
 
 // One pipeline step of a host batch: reads [r0, r1) = units [u0, u1) = bases [b0, b1) of the batch stream.
 // groups [g0, g1) of the invalid-base mask that crossed the link as their non-zero words only: n (group, word) pairs at
@@ -182,6 +183,14 @@ struct dcn_ctx {
     dcn_verify_item *d_vfy_items = nullptr;
     uint32_t *d_vfy_out = nullptr;
     uint64_t vfy_cap = 0;
+    // align buffers (lazy, first dcn_align_batch; each grows to the largest call's need): the aligned rows, per row the
+    // number of runs and their CSR offsets with the scan's scratch, the trace of one group of rows (words; at most the
+    // budget of DCN_ALIGN_TRACE_BYTES, or one row's trace when that is larger), the run slots and the compact runs
+    dcn_align_work *d_aln_work = nullptr;
+    uint32_t *d_aln_n_ops = nullptr, *d_aln_trace = nullptr, *d_aln_slots = nullptr, *d_aln_cigar = nullptr;
+    uint64_t *d_aln_offsets = nullptr;
+    unsigned long long *d_aln_block_sums = nullptr;
+    uint64_t aln_work_cap = 0, aln_rows_cap = 0, aln_offsets_cap = 0, aln_trace_cap = 0, aln_slots_cap = 0, aln_cigar_cap = 0;
     // deferred state of the last enqueued device-API batch
     bool batch_pending = false;
     bool lean = false; // a small host batch is being submitted: copies and result copies go on `stream` itself (submit_impl)

@@ -1,5 +1,6 @@
-// dcn_verify.h -- kept reference bases of an anchor map and the verify kernel's arguments (internal; verify.hip,
-// verify_api.hip, and place_api.hip for the append of dcn_anchor_map_add).
+// dcn_verify.h -- kept reference bases of an anchor map, the verify kernel's arguments, the host side that verify and
+// align share, and the align kernels' arguments (internal; verify.hip, verify_api.hip, align.hip, align_api.hip, and
+// place_api.hip for the append of dcn_anchor_map_add).
 #pragma once
 
 #include "dcn_internal.h"
@@ -47,3 +48,52 @@ struct dcn_verify_args {
     uint32_t *out;
 };
 int dcn_launch_verify(const dcn_verify_args &args, hipStream_t stream);
+
+// ---- the host side that dcn_verify_batch and dcn_align_batch share (verify_api.hip) ---------------------------------
+// What the walk over a call's rows leaves: one checked item per row, the largest threshold of a row that needs a
+// wavefront, and the bases of the batch.
+struct dcn_verify_plan {
+    std::vector<dcn_verify_item> items;
+    uint32_t e_max = 0;
+    uint64_t n_bases = 0;
+};
+// every check of dcn_verify_batch, in its order and with its messages; items stays empty when there is nothing to run
+int dcn_verify_walk(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                    const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, const uint32_t *edits,
+                    dcn_verify_plan *plan);
+// stage, pack, the verify kernel: the run stays open behind the DISTINCT mark (the caller marks FINISH and calls
+// finish_run), the edits are in ctx->d_vfy_out and the items in ctx->d_vfy_items
+int dcn_verify_enqueue(dcn_ctx *c, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                       const dcn_verify_plan &plan, int *prof_slot_out);
+
+// ---- aligned placements (align.hip, align_api.hip; the trace and the walk back are in dcn_align.h) ------------------
+// One aligned row (edits = d <= E) of a call, in row order.  The host has summed the trace sizes (d + 1)^2 and the op
+// bounds 2 d + 1 of the rows in front of it.
+struct dcn_align_work {
+    uint64_t trace_base; // words of trace in front of this row, over the whole call (a group subtracts its first row's)
+    uint64_t slot_end;   // the end of this row's slot of 2 d + 1 runs: the runs are written downwards from here
+    uint32_t row, d;
+};
+static_assert(sizeof(dcn_align_work) == 24, "align work item");
+
+struct dcn_align_args {
+    const dcn_verify_item *items; // the call's rows, as the verify kernel took them
+    const dcn_align_work *work;
+    uint64_t w0, w1;              // the group: work items [w0, w1)
+    const uint32_t *s_packed, *s_invmask, *t_packed, *t_invmask;
+    uint32_t lds_stride;          // words of one wavefront array: >= 2 * (the largest d of the call) + 1
+    uint32_t *trace;              // the group's trace: item w's begins at work[w].trace_base - trace_origin
+    uint64_t trace_origin;        // work[w0].trace_base
+    uint32_t *slots;              // the call's run slots
+    uint32_t *n_ops;              // per row of the call (zero before: a row that is not aligned has no runs)
+};
+int dcn_launch_align(const dcn_align_args &args, hipStream_t stream);
+
+struct dcn_align_gather_args {
+    const dcn_align_work *work;
+    uint64_t n_work;
+    const uint32_t *slots, *n_ops;
+    const uint64_t *cigar_offsets; // n_rows + 1: the scan of n_ops
+    uint32_t *cigar;
+};
+int dcn_launch_align_gather(const dcn_align_gather_args &args, hipStream_t stream);

@@ -1,5 +1,7 @@
 // verify_api.hip -- the C ABI of kept reference bases (dcn_anchor_map_keep_bases, dcn_anchor_map_fetch), the store behind
-// them (dcn_verify.h; dcn_anchor_map_add of place_api.hip appends to it) and dcn_verify_batch (kernel in verify.hip).
+// them (dcn_verify.h; dcn_anchor_map_add of place_api.hip appends to it) and dcn_verify_batch (kernel in verify.hip).  Its
+// checks with the walk over the rows (dcn_verify_walk) and its staging, packing and launch (dcn_verify_enqueue) are
+// functions of their own: dcn_align_batch (align_api.hip) begins with the same two.
 #include "dcn_ctx.h"
 #include "dcn_verify.h"
 
@@ -119,8 +121,14 @@ extern "C" int dcn_anchor_map_fetch(const dcn_index *map, uint32_t record, uint6
     return DCN_OK;
 }
 
-extern "C" int dcn_verify_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
-                                const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits) {
+// The checks of dcn_verify_batch and dcn_align_batch, in the order their messages promise, and the walk over the rows.
+// plan->items stays empty when the call has nothing to run (no reads or no rows).
+int dcn_verify_walk(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                    const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, const uint32_t *edits,
+                    dcn_verify_plan *plan) {
+    plan->items.clear();
+    plan->e_max = 0;
+    plan->n_bases = 0;
     const dcn_verify_params *prm = static_cast<const dcn_verify_params *>(params);
     // (the parameters first: what is wrong with them does not depend on the context or the map)
     if (!prm) return dcn_fail(DCN_ERR_ARG, "params is NULL");
@@ -141,7 +149,7 @@ extern "C" int dcn_verify_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_
     }
     if (!offsets) return dcn_fail(DCN_ERR_ARG, "offsets is NULL");
     DCN_TRY(validate_host_batch(ctx, offsets, n_reads));
-    const uint64_t n_bases = offsets[n_reads];
+    const uint64_t n_bases = plan->n_bases = offsets[n_reads];
     if (n_bases > 0 && !bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
     if (row_offsets) {
         if (row_offsets[0] != 0) return dcn_fail(DCN_ERR_ARG, "row_offsets[0] must be 0");
@@ -155,7 +163,8 @@ extern "C" int dcn_verify_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_
 
     // every row against its read and its record; what the kernel gets is resolved to stream positions here
     const dcn_base_store *store = map->store;
-    std::vector<dcn_verify_item> items(n_rows);
+    std::vector<dcn_verify_item> &items = plan->items;
+    items.resize(n_rows);
     uint32_t e_max = 0;
     uint64_t row = 0;
     for (uint32_t r = 0; r < n_reads; ++r) {
@@ -192,8 +201,19 @@ extern "C" int dcn_verify_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_
             if (gap <= it.E) e_max = std::max(e_max, it.E); // (a row whose lengths differ by more is OVER without a wavefront)
         }
     }
+    plan->e_max = e_max;
+    return DCN_OK;
+}
 
-    dcn_ctx *c = ctx;
+// Stages the batch and the items, packs, and launches the verify kernel: the run is left open behind the DISTINCT mark,
+// its results in c->d_vfy_out.  The caller marks FINISH and ends the run (finish_run).
+int dcn_verify_enqueue(dcn_ctx *c, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                       const dcn_verify_plan &plan, int *prof_slot_out) {
+    const dcn_base_store *store = map->store;
+    const std::vector<dcn_verify_item> &items = plan.items;
+    const uint64_t n_rows = items.size(), n_bases = plan.n_bases;
+    const uint32_t e_max = plan.e_max;
+    *prof_slot_out = -1;
     DCN_HIP(hipSetDevice(c->device));
     if (n_rows > c->vfy_cap) {
         if (c->d_vfy_items) hipFree(c->d_vfy_items);
@@ -211,6 +231,7 @@ extern "C" int dcn_verify_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_
     DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st)); // (short_batch = 0: the pack kernel packs)
     int prof_slot = -1;
     DCN_TRY(prof_begin(c, &prof_slot));
+    *prof_slot_out = prof_slot;
     // the front end up to the packed stream and the invalid mask: no plan, no scan (their slots stay empty)
     DCN_TRY(dcn_launch_pack(c->d_ascii, 0, n_bases, c->d_packed + DCN_FRONT_PAD, c->d_invmask + DCN_FRONT_PAD, c->d_status, st));
     DCN_PROF_MARK(DCN_STAGE_PACK);
@@ -228,6 +249,18 @@ extern "C" int dcn_verify_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_
     va.lds_stride = (2 * e_max + 1 + 3) / 4 * 4;
     va.out = c->d_vfy_out;
     DCN_TRY(dcn_launch_verify(va, st));
+    return DCN_OK;
+}
+
+extern "C" int dcn_verify_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                                const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits) {
+    dcn_verify_plan plan;
+    DCN_TRY(dcn_verify_walk(ctx, map, bases, offsets, n_reads, params, row_offsets, rows, n_rows, edits, &plan));
+    if (plan.items.empty()) return DCN_OK;
+    dcn_ctx *c = ctx;
+    hipStream_t st = c->stream;
+    int prof_slot = -1;
+    DCN_TRY(dcn_verify_enqueue(c, map, bases, offsets, n_reads, plan, &prof_slot));
     DCN_PROF_MARK(DCN_STAGE_FINISH);
     DCN_TRY(finish_run(c, prof_slot));
     DCN_HIP(hipMemcpy(edits, c->d_vfy_out, n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost));

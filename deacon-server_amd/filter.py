@@ -671,6 +671,12 @@ PAIR_PLACEMENT_DTYPE = np.dtype(SPLIT_PLACEMENT_DTYPE.descr + [("flags", np.uint
                                                                ("tlen", np.int64)])
 PAIR_PROPER, PAIR_RESCUED, PAIR_MATE_PLACED = 1, 2, 4  # DCN_PAIR_*: bits of `flags`
 VERIFY_OVER, VERIFY_UNPLACED = N.VERIFY_OVER, N.VERIFY_UNPLACED  # DCN_VERIFY_*: what `edits` holds instead of a distance
+_CIGAR_LETTERS = {N.CIGAR_INS: "I", N.CIGAR_DEL: "D", N.CIGAR_EQUAL: "=", N.CIGAR_DIFF: "X"}
+
+
+def cigar_string(ops):
+    """the runs of one row of Placer.align_batch (len << 4 | op, BAM's codes) -> "12=1X3I..." ("" for no runs)"""
+    return "".join("%d%s" % (int(x) >> 4, _CIGAR_LETTERS[int(x) & 15]) for x in ops)
 
 
 class AnchorMap(Index):
@@ -845,6 +851,36 @@ class Placer(_Context):
         N.check(N.lib().dcn_verify_batch(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None, _ptr(offsets), n_reads,
                                          C.byref(p), _ptr(row_offsets), _ptr(rows) if n_rows else None, n_rows, _ptr(edits)))
         return edits[:n_rows]
+
+    def align_batch(self, bases, offsets, rows, row_offsets=None, max_edits=1023, max_permille=200, capacity=None):
+        """verify_batch, and the alignment of every row with edits = d <= E (dcn_align_batch; the definition of an aligned
+        placement is in include/deacon_hip.h): -> (edits, cigar_offsets, cigar).  edits is verify_batch's; row r's runs
+        are cigar[cigar_offsets[r]:cigar_offsets[r + 1]], each len << 4 | op with BAM's codes (I = 1, D = 2, '=' = 7,
+        X = 8; cigar_string() prints them), in the record's direction; an OVER or UNPLACED row has none.  capacity=None:
+        one call with an estimate and, on DCN_ERR_CAPACITY, a second with the size the first reported; a number: one call
+        with that capacity, and the error is raised.  profile(): pack in its slot, both kernels, the scan and the
+        gather in 'finish'."""
+        bases, offsets, n_reads = _batch(bases, offsets)
+        rows = np.ascontiguousarray(rows)
+        n_rows = len(rows)
+        if row_offsets is not None:
+            row_offsets = np.ascontiguousarray(row_offsets, dtype=np.uint64)
+        edits = np.zeros(max(n_rows, 1), np.uint32)
+        cigar_offsets = np.zeros(n_rows + 1, np.uint64)
+        p = N.VerifyParams(int(max_edits), int(max_permille), rows.dtype.itemsize, 0)
+
+        def call(cap):
+            cigar = np.zeros(max(cap, 1), np.uint32)
+            rc = N.lib().dcn_align_batch(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None, _ptr(offsets), n_reads,
+                                         C.byref(p), _ptr(row_offsets), _ptr(rows) if n_rows else None, n_rows, _ptr(edits),
+                                         _ptr(cigar_offsets), _ptr(cigar) if cap else None, cap)
+            return rc, cigar
+
+        rc, cigar = call(4 * n_rows + 64 if capacity is None else int(capacity))
+        if rc == N.DCN_ERR_CAPACITY and capacity is None:
+            rc, cigar = call(int(cigar_offsets[n_rows]))
+        N.check(rc)
+        return edits[:n_rows], cigar_offsets, cigar[:int(cigar_offsets[n_rows])]
 
     def place_pairs(self, reads1, reads2, **kw):
         """the mates of two lists, interleaved -> place_pair_batch's result"""

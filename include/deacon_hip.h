@@ -76,9 +76,10 @@ enum {
  * 1.10 = dcn_place_split_batch.
  * 1.11 = dcn_place_pair_batch.
  * 1.12 = dcn_ctx_last_batch_short.
- * 1.13 = dcn_anchor_map_keep_bases / _fetch, dcn_verify_batch. */
+ * 1.13 = dcn_anchor_map_keep_bases / _fetch, dcn_verify_batch.
+ * 1.14 = dcn_align_batch. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 13
+#define DCN_ABI_MINOR 14
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -866,6 +867,59 @@ typedef struct dcn_verify_params {
  * call.  dcn_ctx_set_profiling covers it: pack in its slot, the verify kernel in FINISH; plan, scan and DISTINCT are empty. */
 int dcn_verify_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
                      const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits);
+
+/* ---- aligned placements: the CIGAR of each verified placement (ABI 1.14) ---------------------------------------------
+ * (no reference counterpart.)  dcn_verify_batch ends at a number; dcn_align_batch also says where the edits are.
+ *
+ * THE DEFINITION OF AN ALIGNED PLACEMENT.  Rules 1-6 of a verified placement stand: S, T, m, n, EQUAL, d, E, OVER,
+ * UNPLACED.  Added:
+ *   A1. A row with edits = d <= E has an alignment.  A row that is OVER or UNPLACED has zero ops.
+ *   A2. D[i][j] is the Levenshtein distance of S[0, i) and T[0, j) under rule 2's equality.
+ *   A3. Walk from (m, n) to (0, 0).  At (i, j) != (0, 0) with s = D[i][j], take the first that applies:
+ *         X  if i > 0, j > 0 and D[i-1][j-1] = s - 1.  Go to (i-1, j-1).
+ *         I  (a base of S alone) if i > 0 and D[i-1][j] = s - 1.  Go to (i-1, j).
+ *         D  (a base of T alone) if j > 0 and D[i][j-1] = s - 1.  Go to (i, j-1).
+ *         =  otherwise.  Go to (i-1, j-1).  Then S[i-1] EQUAL T[j-1] and D[i-1][j-1] = s, a property of unit costs.
+ *   A4. The steps reversed are the alignment from the start of both intervals.  Equal neighbours merge into runs.  A run
+ *       is one uint32_t, len << 4 | op, with BAM's codes: I = 1, D = 2, '=' = 7, X = 8.  #X + #I + #D = d; '=' + X + I
+ *       covers m; '=' + X + D covers n; n_ops <= 2 d + 1.  A row with max(m, n) >= 2^28 is DCN_ERR_ARG, naming the row.
+ *   A5. S is the reverse complement when the row says so, and T is always forward.  So the ops are in the record's
+ *       direction, as PAF's cg wants them.
+ *   A6. Integers only.  The result is unique.  Nothing depends on lanes, LDS sizes, the scratch budget or how a batch is
+ *       cut.
+ * A3 is stated in D alone: a model needs no wavefront.  The kernel reads no base for it, because D[i][j] <= s - 1 exactly
+ * when F_{s-1}[j - i] >= i, where F_s[k] is the furthest base of S that a path of cost <= s reaches on diagonal k = j - i:
+ * what the wavefront of the verify kernel computes.  The align kernel runs that wavefront once more with E = d and keeps
+ * every F_s (4 (d + 1)^2 bytes per row, 4 MiB at d = 1023), then walks back in d steps. */
+#define DCN_CIGAR_INS 1u
+#define DCN_CIGAR_DEL 2u
+#define DCN_CIGAR_EQUAL 7u
+#define DCN_CIGAR_DIFF 8u
+
+/*   ctx .. n_rows   as for dcn_verify_batch: the same checks in the same order with the same messages and row numbers
+ *   edits           n_rows entries: exactly what dcn_verify_batch returns
+ *   cigar_offsets   n_rows + 1 entries: row r's runs are cigar[cigar_offsets[r] .. cigar_offsets[r + 1])
+ *   cigar           `capacity` entries, or NULL with capacity 0
+ * DCN_ERR_ARG beyond dcn_verify_batch's: cigar_offsets is NULL; a placed row with max(m, n) >= 2^28 (the message names
+ * the first such row); more than 2^32 - 1 rows (the runs are counted per row in 32 bits and scanned to 64-bit offsets);
+ * cigar is NULL although the runs fit `capacity` and there are some.  DCN_ERR_CAPACITY when the rows have more than
+ * `capacity` runs: edits and cigar_offsets are complete, cigar_offsets[n_rows] is the size needed, and cigar is not
+ * written (dcn_locate_batch's convention: call again with that capacity).  Host pointers, blocking, refused while batches
+ * are in flight; the six counters of the context are left unchanged.
+ * The traces of the aligned rows go through one device buffer, in groups of consecutive rows: a group closes when the
+ * next row's trace would pass the budget, and always holds at least one row.  The budget is 1 GiB, or the bytes that the
+ * environment variable DCN_ALIGN_TRACE_BYTES names, read at call time (tests set a few hundred bytes).  The default is a
+ * convention, not a measured optimum: nobody has tuned it, and in the one run recorded in DESIGN.md section 17 a budget of
+ * 8 GiB was more than twice as fast on 10 kbp reads, because 1 GiB of their traces is fewer rows than the device holds waves.
+ * The results do not depend on it.  Device memory, freed with the context, each sized by
+ * the largest call: the trace buffer, max(min(budget, the call's traces), the largest row's trace); 36 bytes per row as
+ * for dcn_verify_batch and 12 more; 24 bytes per aligned row; 4 (2 d + 1) bytes of run slots per aligned row; the runs.
+ * The wavefront runs twice per aligned row, once to find d and once to keep its wavefronts.
+ * dcn_ctx_set_profiling covers it: pack in its slot; the verify kernel, the align kernel of every group, the scan of the
+ * run counts and the gather in FINISH (with the two read-backs between them); plan, scan and DISTINCT are empty. */
+int dcn_align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                    const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits,
+                    uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity);
 
 /* ---- counters: ProcessingStats (src/local_filter.rs:179-187, merged at :388-396) -------------------------- */
 
