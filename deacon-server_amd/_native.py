@@ -156,6 +156,21 @@ VERIFY_UNPLACED = 0xFFFFFFFF  # DCN_VERIFY_UNPLACED
 CIGAR_INS, CIGAR_DEL, CIGAR_EQUAL, CIGAR_DIFF = 1, 2, 7, 8  # DCN_CIGAR_*: BAM's codes of the ops of dcn_align_batch
 
 
+class PileupCallParams(C.Structure):
+    _fields_ = [
+        ("min_depth", C.c_uint32),
+        ("min_permille", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+# DCN_PILEUP_*: the columns of a pileup, the flags of a site and the code of no call
+PILEUP_A, PILEUP_C, PILEUP_G, PILEUP_T, PILEUP_N, PILEUP_DEL, PILEUP_INS, PILEUP_REV = range(8)
+PILEUP_COLUMNS = 8
+PILEUP_SITE_SUB, PILEUP_SITE_DEL, PILEUP_SITE_INS = 1, 2, 4
+PILEUP_NO_CODE = 7
+
+
 def build(force=False, jobs=6):
     """Compile every HIP source for gfx950 into lib/libdeacon_hip.so (hipcc cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -267,10 +282,15 @@ _SIGNATURES = {
     "dcn_anchor_map_fetch": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
     "dcn_verify_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp]),
     "dcn_align_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64]),
+    "dcn_anchor_map_pileup_enable": (C.c_int, [_vp, C.c_int]),
+    "dcn_anchor_map_pileup_reset": (C.c_int, [_vp]),
+    "dcn_pileup_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp, _u64p]),
+    "dcn_anchor_map_pileup_fetch": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
+    "dcn_anchor_map_pileup_call": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _u64p]),
 }
 
 _lib = None
-ABI = (1, 14)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 15)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

@@ -3807,6 +3807,10 @@ struct MapArgs {
     unsigned max_edits = DCN_VERIFY_MAX_EDITS, max_div = 200;
     // `align`: verify, and the alignment of every verified placement as cg:Z: (dcn_align_batch); verify is set as well
     bool align = false;
+    // `pileup`: the aligned placements summed per reference position (dcn_pileup_batch); verify is set as well, -o is the TSV
+    bool pileup = false, all_ranks = false, all_positions = false, has_sites = false;
+    unsigned min_mapq = 1, min_depth = 3, min_frac = 500;
+    std::string sites;
 };
 
 // one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
@@ -3856,8 +3860,9 @@ int run_map(const MapArgs &a) {
     const Stopwatch watch;
     AnchorRef R;
     load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, 
-                    a.align ? "DCN_CLI_ALIGN_BATCH_BASES" : a.verify ? "DCN_CLI_VERIFY_BATCH_BASES" : "DCN_CLI_MAP_BATCH_BASES", a.quiet, a.verify);
+                    a.align || a.pileup ? "DCN_CLI_ALIGN_BATCH_BASES" : a.verify ? "DCN_CLI_VERIFY_BATCH_BASES" : "DCN_CLI_MAP_BATCH_BASES", a.quiet, a.verify);
     Context &ctx = *R.ctx;
+    if (a.pileup) deacon::check(dcn_anchor_map_pileup_enable(R.map.p, 1)); // (after the records: a pileup does not grow)
     dcn_place_split_params prm = {};
     prm.band_bases = a.band;
     prm.min_votes = a.min_votes;
@@ -3868,6 +3873,8 @@ int run_map(const MapArgs &a) {
     uint64_t reads_in = 0, placed = 0, split_reads = 0, placements = 0, mapq60 = 0, mapq0 = 0;
     uint64_t verified = 0, unverified = 0, edits_sum = 0, verified_bases = 0;
     uint64_t op_bases[16] = {}, cigar_ops = 0; // (align: bases per op code, and runs)
+    uint64_t rows_selected = 0, rows_added = 0; // (pileup)
+    std::vector<dcn_split_placement> chosen;
     dcn_verify_params vprm = {};
     vprm.max_edits = a.max_edits;
     vprm.max_permille = a.max_div;
@@ -3898,6 +3905,17 @@ int run_map(const MapArgs &a) {
                 }
                 cigar.resize(cigar_off[place_off[n_reads]]); // (the size the first call reported)
             }
+        } else if (a.pileup) { // the rows just placed, those that --min-mapq and the rank leave: unplaced in a copy
+            edits.resize(place_off[n_reads]);
+            chosen.assign(pl.begin(), pl.begin() + (ptrdiff_t)place_off[n_reads]);
+            for (dcn_split_placement &p : chosen) {
+                if (p.mapq >= a.min_mapq && (a.all_ranks || p.rank == 0)) ++rows_selected;
+                else p.record = UINT32_MAX;
+            }
+            uint64_t added = 0;
+            deacon::check(dcn_pileup_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), chosen.data(),
+                                           place_off[n_reads], edits.data(), &added));
+            rows_added += added;
         } else if (a.verify) {
             edits.resize(place_off[n_reads]);
             deacon::check(dcn_verify_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), pl.data(),
@@ -3916,6 +3934,11 @@ int run_map(const MapArgs &a) {
                 const dcn_split_placement &p = pl[q];
                 ++per_record[p.record];
                 mapq60 += p.mapq == 60, mapq0 += p.mapq == 0;
+                if (a.pileup) { // (no PAF here: a row that was left out is neither verified nor unverified)
+                    if (edits[q] == DCN_VERIFY_OVER) ++unverified;
+                    else if (edits[q] != DCN_VERIFY_UNPLACED) ++verified, edits_sum += edits[q];
+                    continue;
+                }
                 if (a.verify) {
                     if (edits[q] == DCN_VERIFY_OVER) {
                         ++unverified;
@@ -3938,10 +3961,75 @@ int run_map(const MapArgs &a) {
         }
         out.write(rows);
     });
+    // pileup: the counters of every record, a stretch at a time, as TSV; the sites of the same stretches
+    uint64_t covered = 0, n_sites = 0, column_sum[DCN_PILEUP_COLUMNS] = {};
+    if (a.pileup) {
+        TextOut sites_out;
+        if (a.has_sites) sites_out.open(a.sites, false);
+        out.write("record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\n");
+        if (a.has_sites) sites_out.write("record\tpos\tref\tcall\tdepth\tflags\n");
+        dcn_pileup_call_params cprm = {};
+        cprm.min_depth = a.min_depth;
+        cprm.min_permille = a.min_frac;
+        const uint64_t stretch = 1u << 20;
+        std::vector<uint32_t> counts, site_info;
+        std::vector<uint64_t> site_pos;
+        std::vector<uint8_t> ref_text;
+        std::string site_rows;
+        for (uint32_t r = 0; r < R.n_records; ++r) {
+            for (uint64_t start = 0; start < R.lens[r]; start += stretch) {
+                const uint64_t n = std::min<uint64_t>(stretch, R.lens[r] - start);
+                counts.resize(n * DCN_PILEUP_COLUMNS);
+                ref_text.resize(n);
+                deacon::check(dcn_anchor_map_pileup_fetch(R.map.p, r, start, n, counts.data()));
+                deacon::check(dcn_anchor_map_fetch(R.map.p, r, start, n, ref_text.data()));
+                rows.clear();
+                for (uint64_t q = 0; q < n; ++q) {
+                    const uint32_t *const c = counts.data() + q * DCN_PILEUP_COLUMNS;
+                    uint64_t depth = 0;
+                    for (int col = 0; col <= DCN_PILEUP_DEL; ++col) depth += c[col];
+                    for (int col = 0; col < DCN_PILEUP_COLUMNS; ++col) column_sum[col] += c[col];
+                    covered += depth > 0;
+                    if (!a.all_positions && depth == 0 && c[DCN_PILEUP_INS] == 0) continue;
+                    rows += R.names[r] + '\t' + std::to_string(start + q) + '\t' + (char)ref_text[q];
+                    for (int col = 0; col < DCN_PILEUP_COLUMNS; ++col) rows += '\t' + std::to_string(c[col]);
+                    rows += '\n';
+                }
+                out.write(rows);
+                uint64_t found = 0;
+                for (int attempt = 0;; ++attempt) { // (dcn_locate_batch's convention: the first call reports the size)
+                    const int rc = dcn_anchor_map_pileup_call(R.map.p, &cprm, r, start, n, nullptr, site_pos.data(), site_info.data(),
+                                                              site_pos.size(), &found);
+                    if (rc != DCN_ERR_CAPACITY || attempt) {
+                        deacon::check(rc);
+                        break;
+                    }
+                    site_pos.resize(found);
+                    site_info.resize(found);
+                }
+                n_sites += found;
+                if (!a.has_sites) continue;
+                site_rows.clear();
+                for (uint64_t i = 0; i < found; ++i) {
+                    const uint32_t *const c = counts.data() + (site_pos[i] - start) * DCN_PILEUP_COLUMNS;
+                    uint64_t depth = 0;
+                    for (int col = 0; col <= DCN_PILEUP_DEL; ++col) depth += c[col];
+                    const uint32_t code = (site_info[i] >> 8) & 0xFFu;
+                    site_rows += R.names[r] + '\t' + std::to_string(site_pos[i]) + '\t' + (char)ref_text[site_pos[i] - start] + '\t' +
+                                 (code <= 4 ? "ACGT-"[code] : 'N') + '\t' + std::to_string(depth) + '\t' + std::to_string(site_info[i] & 0xFFu) + '\n';
+                }
+                sites_out.write(site_rows);
+            }
+        }
+        if (a.has_sites) sites_out.finish();
+    }
     out.finish();
     const double secs = watch.seconds();
     if (!a.quiet) {
-        if (a.verify)
+        if (a.pileup)
+            std::fprintf(stderr, "Piled up %llu of %llu placements on %llu positions (%llu sites)\n", (unsigned long long)rows_added,
+                         (unsigned long long)placements, (unsigned long long)covered, (unsigned long long)n_sites);
+        if (a.verify && !a.pileup)
             std::fprintf(stderr, "Verified %llu of %llu placements (%llu edits over %llu bases)\n", (unsigned long long)verified,
                          (unsigned long long)placements, (unsigned long long)edits_sum, (unsigned long long)verified_bases);
         if (a.align)
@@ -3972,6 +4060,17 @@ int run_map(const MapArgs &a) {
                         "  \"cigar_ops\": %llu,\n",
                     (unsigned long long)op_bases[DCN_CIGAR_EQUAL], (unsigned long long)op_bases[DCN_CIGAR_DIFF],
                     (unsigned long long)op_bases[DCN_CIGAR_INS], (unsigned long long)op_bases[DCN_CIGAR_DEL], (unsigned long long)cigar_ops);
+        if (a.pileup) {
+            appendf(js, "  \"min_mapq\": %u,\n  \"all_ranks\": %s,\n  \"min_depth\": %u,\n  \"min_permille\": %u,\n"
+                        "  \"rows_selected\": %llu,\n  \"rows_added\": %llu,\n  \"positions_covered\": %llu,\n  \"sites\": %llu,\n",
+                    a.min_mapq, a.all_ranks ? "true" : "false", a.min_depth, a.min_frac, (unsigned long long)rows_selected,
+                    (unsigned long long)rows_added, (unsigned long long)covered, (unsigned long long)n_sites);
+            const char *const column_names[DCN_PILEUP_COLUMNS] = {"A", "C", "G", "T", "N", "del", "ins", "rev"};
+            js += "  \"columns\": {";
+            for (int col = 0; col < DCN_PILEUP_COLUMNS; ++col)
+                appendf(js, "%s\"%s\": %llu", col ? ", " : "", column_names[col], (unsigned long long)column_sum[col]);
+            js += "},\n";
+        }
         appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
         for (uint32_t r = 0; r < R.n_records; ++r) {
             js += (r ? ",\n    {" : "\n    {");
@@ -4119,6 +4218,7 @@ void usage() {
                  "  map-pairs  Place the two mates of each pair jointly: proper pairs, rescued mates, insert sizes, as PAF\n"
                  "  verify  As map, with every placement compared base by base with the reference: edit distance, as PAF\n"
                  "  align   As verify, with the alignment of every verified placement: cg:Z: with = X I D, as PAF\n"
+                 "  pileup  As align, summed per reference position: counts of A C G T N, gaps and strand, and site calls, as TSV\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -4353,6 +4453,51 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "output does not depend on how the work is cut.  No soft clips, no extension over the read's flanks, no SAM.\n"
                "Placements, qualities, thresholds and every other column and tag are verify's for the same arguments.\n"
                "Mates are independent here: one input.\n";
+    else if (sub == "pileup")
+        text = "Align each read's placements on a reference and count, per reference position, what the reads show there, as TSV\n\n"
+               "Usage: deacon-hip pileup [OPTIONS] <REF> [READS]\n\n"
+               "Arguments:\n"
+               "  <REF>     Path to the reference fastx file: its records are numbered and named in file order\n"
+               "  [READS]   Optional path to fastx file (or - for stdin; gz, bgzf, zst, xz and bz2 found by content) [default: -]\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Keys that may anchor: a minimizer index file, whose k and w are used\n"
+               "                                 [default: the minimizers of <REF> at -k / -w]\n"
+               "  -k <K>                         K-mer length without -x [default: 31]\n"
+               "  -w <W>                         Minimizer window size without -x [default: 15]\n"
+               "  -o, --output <OUTPUT>          TSV with the columns record pos ref A C G T N del ins rev, written after the last\n"
+               "                                 read (- for stdout) [default: -].  pos is 0-based, as in PAF.  One line per\n"
+               "                                 position with depth > 0 or ins > 0, records in file order\n"
+               "      --all-positions            One line for every position of every record\n"
+               "      --sites <FILE>             TSV with the columns record pos ref call depth flags: the positions whose call\n"
+               "                                 differs from the reference (flags 1), is a gap (2), or that carry an inserted\n"
+               "                                 run behind them (4), under --min-depth and --min-frac\n"
+               "      --min-depth <N>            A call needs a depth of at least N [default: 3, a convention]\n"
+               "      --min-frac <N>             ... and N per 1000 of the depth for the most frequent of A C G T and gap\n"
+               "                                 (0..1000) [default: 500, a convention]\n"
+               "      --min-mapq <N>             Only placements of mapping quality N or more add (0..60) [default: 1, a convention]\n"
+               "      --all-ranks                Every placement of a read adds, not only its first (rank 0)\n"
+               "  -e, --max-edits <N>            Only a placement of at most N edits adds (0..1023) [default: 1023, a convention]\n"
+               "      --max-div <N>              ... and at most N per 1000 bases of the longer extent (0..1000) [default: 200,\n"
+               "                                 a convention]\n"
+               "  -N, --max-placements <N>       Placements per read, each from the anchor hits no earlier one explained (1..8)\n"
+               "                                 [default: 4]\n"
+               "      --band <N>                 Width of a diagonal band in bases [default: 256, a convention]\n"
+               "  -a, --min-votes <N>            Minimum number of anchor hits in a placement's cell [default: 2, as filter's -a,\n"
+               "                                 a convention]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per read (0 = entire read) [default: 0]\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file: map's, and rows_selected, rows_added,\n"
+               "                                 positions_covered, sites and the totals of the eight columns\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
+               "  -h, --help                     Print help\n\n"
+               "Counts: every selected placement within the thresholds is aligned as align aligns it.  Each base of the record's\n"
+               "extent gets one count: in the column of the read's base there (N for a base that is not ACGT), or in del when\n"
+               "the read has none.  An inserted run, of whatever length, is one count in ins at the base in front of it; the\n"
+               "inserted bases are not recorded.  rev counts the same bases once more for reads on the - strand.  depth is\n"
+               "A + C + G + T + N + del.  The counts are integers and do not depend on how the input is cut into batches.\n"
+               "Calls: the most frequent of A C G T and gap (the first of them on a tie; N never wins) when it reaches\n"
+               "--min-frac of a depth of at least --min-depth.  The defaults are conventions, not measured optima.\n"
+               "No inserted bases, no consensus sequence, no VCF, no base qualities.  Mates are independent here: one input.\n";
     else if (sub == "map-pairs")
         text = "Place the two mates of each pair jointly on a reference: proper pairs, rescued mates and insert sizes, as PAF\n\n"
                "Usage: deacon-hip map-pairs [OPTIONS] <REF> <READS1> [READS2]\n\n"
@@ -4643,10 +4788,11 @@ int main(int argc, char **argv) {
             if (pos.size() > 2) die("place takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[2] + "')");
             return run_place(a);
         }
-        if (args[0] == "map" || args[0] == "verify" || args[0] == "align") {
+        if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup") {
             MapArgs a;
             a.align = args[0] == "align";
-            a.verify = a.align || args[0] == "verify";
+            a.pileup = args[0] == "pileup";
+            a.verify = a.align || a.pileup || args[0] == "verify";
             std::vector<std::string> pos;
             auto number = [&](const std::string &v, const char *flag, long long lo, long long hi) {
                 char *end = nullptr;
@@ -4664,7 +4810,13 @@ int main(int argc, char **argv) {
                 else if (s == "-N" || s == "--max-placements") a.max_placements = (unsigned)number(need(++i), "-N", 1, DCN_PLACE_SPLIT_MAX);
                 else if (a.verify && (s == "-e" || s == "--max-edits")) a.max_edits = (unsigned)number(need(++i), "--max-edits", 0, DCN_VERIFY_MAX_EDITS);
                 else if (a.verify && s == "--max-div") a.max_div = (unsigned)number(need(++i), "--max-div", 0, 1000);
-                else if (a.verify && s == "--verified-only") a.verified_only = true;
+                else if (a.verify && !a.pileup && s == "--verified-only") a.verified_only = true;
+                else if (a.pileup && s == "--min-mapq") a.min_mapq = (unsigned)number(need(++i), "--min-mapq", 0, 60);
+                else if (a.pileup && s == "--min-depth") a.min_depth = (unsigned)number(need(++i), "--min-depth", 0, 0xFFFFFFFFll);
+                else if (a.pileup && s == "--min-frac") a.min_frac = (unsigned)number(need(++i), "--min-frac", 0, 1000);
+                else if (a.pileup && s == "--sites") a.sites = need(++i), a.has_sites = true;
+                else if (a.pileup && s == "--all-ranks") a.all_ranks = true;
+                else if (a.pileup && s == "--all-positions") a.all_positions = true;
                 else if (s == "--band") a.band = (unsigned)number(need(++i), "--band", 1, 0xFFFFFFFFll);
                 else if (s == "-a" || s == "--min-votes") a.min_votes = (unsigned)number(need(++i), "--min-votes", 1, 0xFFFFFFFFll);
                 else if (s == "-p" || s == "--prefix-length") a.prefix_length = (size_t)number(need(++i), "--prefix-length", 0, 0x7FFFFFFFFFFFFFFFll);

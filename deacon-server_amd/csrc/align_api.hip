@@ -1,5 +1,7 @@
 // align_api.hip -- dcn_align_batch: the rows of dcn_verify_batch, each verified one with its alignment (kernels in
-// align.hip, the trace and the walk back in dcn_align.h, the checks and the first pass in verify_api.hip).
+// align.hip, the trace and the walk back in dcn_align.h, the checks and the first pass in verify_api.hip).  Its rules
+// over the rows (dcn_align_check_rows), its passes up to the scan of the run counts (dcn_align_runs) and its gather
+// (dcn_align_gather_runs) are functions of their own: dcn_pileup_batch (pileup_api.hip) runs the same sequence.
 #include "dcn_align.h"
 #include "dcn_ctx.h"
 #include "dcn_dump_sweep.h"
@@ -33,28 +35,26 @@ int grow(T **p, uint64_t *cap, uint64_t need, const char *what) {
 }
 } // namespace
 
-extern "C" int dcn_align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
-                               const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits,
-                               uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity) {
-    dcn_verify_plan plan;
-    DCN_TRY(dcn_verify_walk(ctx, map, bases, offsets, n_reads, params, row_offsets, rows, n_rows, edits, &plan));
-    if (!cigar_offsets) return dcn_fail(DCN_ERR_ARG, "cigar_offsets is NULL");
-    if (plan.items.empty()) {
-        cigar_offsets[0] = 0;
-        return DCN_OK;
-    }
+int dcn_align_check_rows(const dcn_verify_plan &plan) {
+    const uint64_t n_rows = plan.items.size();
     if (n_rows > UINT32_MAX) return dcn_fail(DCN_ERR_ARG, "n_rows must be below 2^32 (the runs of a call are counted per row in 32 bits)");
     for (uint64_t row = 0; row < n_rows; ++row) {
         const dcn_verify_item &it = plan.items[row];
         if (!(it.flags & 2u) && std::max(it.m, it.n) >= (1u << 28))
             return dcn_fail(DCN_ERR_ARG, "row " + std::to_string(row) + ": an interval of 2^28 bases or more has no run length (len << 4 | op)");
     }
+    return DCN_OK;
+}
 
-    dcn_ctx *c = ctx;
+int dcn_align_runs(dcn_ctx *c, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                   const dcn_verify_plan &plan, uint32_t *edits, int *prof_slot_out, uint64_t *n_work_out) {
+    const uint64_t n_rows = plan.items.size();
     hipStream_t st = c->stream;
     int prof_slot = -1;
+    *prof_slot_out = -1;
     // pass 1: every row's d (verify_kernel, as dcn_verify_batch runs it)
     DCN_TRY(dcn_verify_enqueue(c, map, bases, offsets, n_reads, plan, &prof_slot));
+    *prof_slot_out = prof_slot;
     DCN_HIP(hipStreamSynchronize(st));
     DCN_HIP(hipMemcpy(edits, c->d_vfy_out, n_rows * sizeof(uint32_t), hipMemcpyDeviceToHost));
 
@@ -119,6 +119,39 @@ extern "C" int dcn_align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t
     }
     DCN_TRY(dcn_launch_offsets_scan(c->d_aln_n_ops, (uint32_t)n_rows, c->d_aln_block_sums, c->d_aln_offsets, st));
     DCN_HIP(hipStreamSynchronize(st));
+    *n_work_out = n_work;
+    return DCN_OK;
+}
+
+int dcn_align_gather_runs(dcn_ctx *c, uint64_t n_work, uint64_t total) {
+    DCN_TRY(grow(&c->d_aln_cigar, &c->aln_cigar_cap, total, "align runs"));
+    dcn_align_gather_args ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.work = c->d_aln_work;
+    ga.n_work = n_work;
+    ga.slots = c->d_aln_slots;
+    ga.n_ops = c->d_aln_n_ops;
+    ga.cigar_offsets = c->d_aln_offsets;
+    ga.cigar = c->d_aln_cigar;
+    return dcn_launch_align_gather(ga, c->stream);
+}
+
+extern "C" int dcn_align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                               const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits,
+                               uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity) {
+    dcn_verify_plan plan;
+    DCN_TRY(dcn_verify_walk(ctx, map, bases, offsets, n_reads, params, row_offsets, rows, n_rows, edits, &plan));
+    if (!cigar_offsets) return dcn_fail(DCN_ERR_ARG, "cigar_offsets is NULL");
+    if (plan.items.empty()) {
+        cigar_offsets[0] = 0;
+        return DCN_OK;
+    }
+    DCN_TRY(dcn_align_check_rows(plan));
+    dcn_ctx *c = ctx;
+    hipStream_t st = c->stream;
+    int prof_slot = -1;
+    uint64_t n_work = 0;
+    DCN_TRY(dcn_align_runs(c, map, bases, offsets, n_reads, plan, edits, &prof_slot, &n_work));
     DCN_HIP(hipMemcpy(cigar_offsets, c->d_aln_offsets, (n_rows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
     const uint64_t total = cigar_offsets[n_rows];
     const bool fits = total <= capacity;
@@ -127,18 +160,7 @@ extern "C" int dcn_align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t
         DCN_TRY(finish_run(c, prof_slot));
         return dcn_fail(DCN_ERR_ARG, "cigar is NULL");
     }
-    if (fits && total > 0) {
-        DCN_TRY(grow(&c->d_aln_cigar, &c->aln_cigar_cap, total, "align runs"));
-        dcn_align_gather_args ga;
-        memset(&ga, 0, sizeof(ga));
-        ga.work = c->d_aln_work;
-        ga.n_work = n_work;
-        ga.slots = c->d_aln_slots;
-        ga.n_ops = c->d_aln_n_ops;
-        ga.cigar_offsets = c->d_aln_offsets;
-        ga.cigar = c->d_aln_cigar;
-        DCN_TRY(dcn_launch_align_gather(ga, st));
-    }
+    if (fits && total > 0) DCN_TRY(dcn_align_gather_runs(c, n_work, total));
     DCN_PROF_MARK(DCN_STAGE_FINISH);
     DCN_TRY(finish_run(c, prof_slot));
     if (!fits)

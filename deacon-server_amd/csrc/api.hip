@@ -441,6 +441,8 @@ extern "C" int dcn_index_clone(const dcn_index *index, int device, dcn_index **o
     idx->d_anchor = nullptr; // ... and a replica of an anchor map has no words
     idx->anchor_records = 0;
     idx->store = nullptr; // ... and keeps no bases
+    idx->d_pileup = nullptr; // ... and has no pileup
+    idx->pileup_bases = 0;
     const uint64_t bytes = idx->n_groups * DCN_GROUP_SLOTS * sizeof(uint64_t);
     // Another GPU: the keys cross the link, not the table (a tenth of the bytes at the default 8 slots per key; dcn_table_clone_by_keys).
     // The same GPU: a device-to-device copy of the table at HBM's pace.  DCN_CLONE_BY_KEYS=1 / DCN_CLONE_BY_COPY=1 force one form
@@ -494,6 +496,7 @@ extern "C" void dcn_index_destroy(dcn_index *index) {
     if (index->d_depth) hipFree(index->d_depth);
     if (index->d_anchor) hipFree(index->d_anchor);
     dcn_base_store_free(index->store);
+    if (index->d_pileup) hipFree(index->d_pileup);
     delete index;
 }
 

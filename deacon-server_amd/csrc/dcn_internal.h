@@ -114,6 +114,10 @@ struct dcn_index {
     uint32_t anchor_records = 0;
     // ... and the bases of its records (dcn_anchor_map_keep_bases, verify_api.hip).  Null: none are kept.
     dcn_base_store *store = nullptr;
+    // ... and the pileup over them (dcn_anchor_map_pileup_enable, pileup_api.hip): 8 counters per base of the store as it
+    // was when enabled, pileup_bases of them, laid out by dcn_pile_index (dcn_pileup.h).  Null: none.
+    uint32_t *d_pileup = nullptr;
+    uint64_t pileup_bases = 0;
     dcn_table_view view() const {
         dcn_table_view v;
         v.slots = d_slots;

@@ -1,6 +1,7 @@
 // dcn_verify.h -- kept reference bases of an anchor map, the verify kernel's arguments, the host side that verify and
-// align share, and the align kernels' arguments (internal; verify.hip, verify_api.hip, align.hip, align_api.hip, and
-// place_api.hip for the append of dcn_anchor_map_add).
+// align share, the align kernels' arguments, the host side that align and pileup share, and the pileup kernels' arguments
+// (internal; verify.hip, verify_api.hip, align.hip, align_api.hip, pileup.hip, pileup_api.hip, and place_api.hip for the
+// append of dcn_anchor_map_add).
 #pragma once
 
 #include "dcn_internal.h"
@@ -97,3 +98,44 @@ struct dcn_align_gather_args {
     uint32_t *cigar;
 };
 int dcn_launch_align_gather(const dcn_align_gather_args &args, hipStream_t stream);
+
+// ---- the host side that dcn_align_batch and dcn_pileup_batch share (align_api.hip) -----------------------------------
+// align's own rules over a walked call: fewer than 2^32 rows, and no placed row with an interval of 2^28 bases or more
+int dcn_align_check_rows(const dcn_verify_plan &plan);
+// verify, the read-back of the edits, the work list, the align kernel of every trace group and the scan of the run
+// counts, then a wait: the edits are in `edits`, the run counts in c->d_aln_n_ops, their offsets in c->d_aln_offsets, the
+// runs in the slots.  The run stays open behind the DISTINCT mark, as dcn_verify_enqueue leaves it.
+int dcn_align_runs(dcn_ctx *c, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                   const dcn_verify_plan &plan, uint32_t *edits, int *prof_slot_out, uint64_t *n_work_out);
+// the gather of `total` > 0 runs from the slots into c->d_aln_cigar, which grows to hold them
+int dcn_align_gather_runs(dcn_ctx *c, uint64_t n_work, uint64_t total);
+
+// ---- pileup (pileup.hip, pileup_api.hip; the shared arithmetic is in dcn_pileup.h) ----------------------------------
+struct dcn_pileup_args {
+    const dcn_verify_item *items; // the call's rows, as the verify kernel took them
+    const dcn_align_work *work;   // the aligned ones
+    uint64_t n_work;
+    const uint32_t *s_packed, *s_invmask; // the batch: views behind DCN_FRONT_PAD
+    const uint32_t *n_ops;                // per row of the call
+    const uint64_t *cigar_offsets;        // ... and where its runs begin
+    const uint32_t *cigar;
+    uint32_t *counters; // the map's pileup: dcn_pile_index(column, store base, bases)
+    uint64_t bases;
+};
+int dcn_launch_pileup(const dcn_pileup_args &args, hipStream_t stream);
+
+struct dcn_pileup_call_args {
+    const uint32_t *counters;
+    uint64_t bases;
+    const uint32_t *t_packed, *t_invmask; // the store
+    uint64_t base0, n;                    // the range: store bases [base0, base0 + n)
+    uint64_t pos0;                        // ... and the record position of its first base
+    uint32_t min_depth, min_permille;
+    uint8_t *calls;                // n characters (the counting pass)
+    uint32_t *block_counts;        // sites per workgroup (the counting pass)
+    const uint64_t *block_offsets; // their scan (the writing pass)
+    uint64_t *site_pos;
+    uint32_t *site_info;
+};
+uint32_t dcn_pileup_call_blocks(uint64_t n); // workgroups of a range of n positions
+int dcn_launch_pileup_call(const dcn_pileup_call_args &args, bool write, hipStream_t stream);

@@ -1,0 +1,208 @@
+// pileup_api.hip -- the C ABI of pileups (dcn_anchor_map_pileup_enable / _reset / _fetch / _call, dcn_pileup_batch;
+// kernels in pileup.hip, the shared arithmetic in dcn_pileup.h).  dcn_pileup_batch is dcn_align_batch's sequence
+// (verify_api.hip's walk, align_api.hip's passes and gather) with the runs left on the device and the pileup kernel behind.
+#include "dcn_ctx.h"
+#include "dcn_dump_sweep.h"
+#include "dcn_pileup.h"
+#include "dcn_verify.h"
+
+#include <cstring>
+
+using namespace dcn_impl;
+
+static_assert(sizeof(dcn_pileup_call_params) == 16, "pileup call params are ABI");
+static_assert(DCN_PILEUP_A == DCN_PILE_A && DCN_PILEUP_C == DCN_PILE_C && DCN_PILEUP_G == DCN_PILE_G && DCN_PILEUP_T == DCN_PILE_T &&
+                  DCN_PILEUP_N == DCN_PILE_N && DCN_PILEUP_DEL == DCN_PILE_DEL && DCN_PILEUP_INS == DCN_PILE_INS &&
+                  DCN_PILEUP_REV == DCN_PILE_REV && DCN_PILEUP_COLUMNS == DCN_PILE_COLUMNS,
+              "the columns of the header and of dcn_pileup.h");
+static_assert(DCN_PILEUP_SITE_SUB == DCN_PILE_SITE_SUB && DCN_PILEUP_SITE_DEL == DCN_PILE_SITE_DEL &&
+                  DCN_PILEUP_SITE_INS == DCN_PILE_SITE_INS && DCN_PILEUP_NO_CODE == DCN_PILE_NO_CODE,
+              "the site flags of the header and of dcn_pileup.h");
+
+namespace {
+int check_store(const dcn_index *map) {
+    if (!map) return dcn_fail(DCN_ERR_ARG, "map is NULL");
+    if (!map->d_anchor) return dcn_fail(DCN_ERR_ARG, "the index is not an anchor map (dcn_anchor_map_create)");
+    if (!map->store) return dcn_fail(DCN_ERR_ARG, "the map keeps no bases (dcn_anchor_map_keep_bases before the first add)");
+    return DCN_OK;
+}
+
+int check_pileup(const dcn_index *map) {
+    DCN_TRY(check_store(map));
+    if (!map->d_pileup) return dcn_fail(DCN_ERR_ARG, "the map has no pileup (dcn_anchor_map_pileup_enable)");
+    return DCN_OK;
+}
+
+// the range [start, start + n_bases) of a record, as dcn_anchor_map_fetch checks it -> its first base in the store
+int check_range(const dcn_index *map, const char *who, uint32_t record, uint64_t start, uint64_t n_bases, uint64_t *base0) {
+    const dcn_base_store *s = map->store;
+    if (record >= s->rec_len.size())
+        return dcn_fail(DCN_ERR_ARG, std::string(who) + ": record " + std::to_string(record) + " of " + std::to_string(s->rec_len.size()) + " added");
+    const uint64_t len = s->rec_len[record];
+    if (start > len || n_bases > len - start)
+        return dcn_fail(DCN_ERR_ARG, std::string(who) + ": bases [" + std::to_string(start) + ", " + std::to_string(start) + " + " +
+                                         std::to_string(n_bases) + ") are past the record's " + std::to_string(len) + " bases");
+    *base0 = s->rec_start[record] + start;
+    return DCN_OK;
+}
+
+// device memory of one call, freed when it ends
+struct scratch {
+    void *p[6] = {};
+    int n = 0;
+    template <typename T>
+    int get(T **out, uint64_t count, const char *what) {
+        DCN_TRY(dev_alloc(out, count, what));
+        p[n++] = *out;
+        return DCN_OK;
+    }
+    ~scratch() {
+        for (int i = 0; i < n; ++i) hipFree(p[i]);
+    }
+};
+} // namespace
+
+extern "C" int dcn_anchor_map_pileup_enable(dcn_index *map, int enable) {
+    DCN_TRY(check_store(map));
+    if (!enable) {
+        if (map->d_pileup) {
+            DCN_HIP(hipSetDevice(map->device));
+            hipFree(map->d_pileup);
+        }
+        map->d_pileup = nullptr;
+        map->pileup_bases = 0;
+        return DCN_OK;
+    }
+    if (map->d_pileup) return DCN_OK;
+    DCN_HIP(hipSetDevice(map->device));
+    const uint64_t bases = std::max<uint64_t>(map->store->used, 32); // (whole 32-base groups, as the store counts them)
+    DCN_TRY(dev_alloc_zeroed(&map->d_pileup, bases * DCN_PILE_COLUMNS, "pileup counters"));
+    map->pileup_bases = bases;
+    return DCN_OK;
+}
+
+extern "C" int dcn_anchor_map_pileup_reset(dcn_index *map) {
+    DCN_TRY(check_pileup(map));
+    DCN_HIP(hipSetDevice(map->device));
+    DCN_HIP(hipMemset(map->d_pileup, 0, map->pileup_bases * DCN_PILE_COLUMNS * sizeof(uint32_t)));
+    DCN_HIP(hipDeviceSynchronize()); // (null-stream work must not be overtaken by a context's stream)
+    return DCN_OK;
+}
+
+extern "C" int dcn_pileup_batch(dcn_ctx *ctx, dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                                const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits,
+                                uint64_t *n_added) {
+    dcn_verify_plan plan;
+    DCN_TRY(dcn_verify_walk(ctx, map, bases, offsets, n_reads, params, row_offsets, rows, n_rows, edits, &plan));
+    if (!map->d_pileup) return dcn_fail(DCN_ERR_ARG, "the map has no pileup (dcn_anchor_map_pileup_enable)");
+    if (n_added) *n_added = 0;
+    if (plan.items.empty()) return DCN_OK;
+    DCN_TRY(dcn_align_check_rows(plan));
+
+    dcn_ctx *c = ctx;
+    hipStream_t st = c->stream;
+    int prof_slot = -1;
+    uint64_t n_work = 0, total = 0;
+    DCN_TRY(dcn_align_runs(c, map, bases, offsets, n_reads, plan, edits, &prof_slot, &n_work));
+    DCN_HIP(hipMemcpy(&total, c->d_aln_offsets + n_rows, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (total > 0) { // the runs stay on the device: the buffer grows to what the scan reports
+        DCN_TRY(dcn_align_gather_runs(c, n_work, total));
+        dcn_pileup_args pa;
+        memset(&pa, 0, sizeof(pa));
+        pa.items = c->d_vfy_items;
+        pa.work = c->d_aln_work;
+        pa.n_work = n_work;
+        pa.s_packed = c->d_packed + DCN_FRONT_PAD;
+        pa.s_invmask = c->d_invmask + DCN_FRONT_PAD;
+        pa.n_ops = c->d_aln_n_ops;
+        pa.cigar_offsets = c->d_aln_offsets;
+        pa.cigar = c->d_aln_cigar;
+        pa.counters = map->d_pileup;
+        pa.bases = map->pileup_bases;
+        DCN_TRY(dcn_launch_pileup(pa, st));
+    }
+    DCN_PROF_MARK(DCN_STAGE_FINISH);
+    DCN_TRY(finish_run(c, prof_slot));
+    if (n_added) { // rule P2: the rows with an alignment and n > 0
+        uint64_t added = 0;
+        for (uint64_t row = 0; row < n_rows; ++row) added += edits[row] < DCN_VERIFY_OVER && plan.items[row].n > 0;
+        *n_added = added;
+    }
+    return DCN_OK;
+}
+
+extern "C" int dcn_anchor_map_pileup_fetch(const dcn_index *map, uint32_t record, uint64_t start, uint64_t n_bases, uint32_t *counts) {
+    DCN_TRY(check_pileup(map));
+    uint64_t b0 = 0;
+    DCN_TRY(check_range(map, "pileup fetch", record, start, n_bases, &b0));
+    if (n_bases == 0) return DCN_OK;
+    if (!counts) return dcn_fail(DCN_ERR_ARG, "counts is NULL");
+    DCN_HIP(hipSetDevice(map->device));
+#if defined(DCN_PILEUP_POSITION_MAJOR)
+    DCN_HIP(hipMemcpy(counts, map->d_pileup + b0 * DCN_PILE_COLUMNS, n_bases * DCN_PILE_COLUMNS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+#else
+    std::vector<uint32_t> plane(n_bases); // column-major on the device: a plane at a time, transposed here
+    for (uint32_t col = 0; col < DCN_PILE_COLUMNS; ++col) {
+        DCN_HIP(hipMemcpy(plane.data(), map->d_pileup + dcn_pile_index(col, b0, map->pileup_bases), n_bases * sizeof(uint32_t),
+                          hipMemcpyDeviceToHost));
+        for (uint64_t q = 0; q < n_bases; ++q) counts[q * DCN_PILE_COLUMNS + col] = plane[q];
+    }
+#endif
+    return DCN_OK;
+}
+
+extern "C" int dcn_anchor_map_pileup_call(const dcn_index *map, const void *params, uint32_t record, uint64_t start, uint64_t n_bases,
+                                          uint8_t *calls, uint64_t *site_pos, uint32_t *site_info, uint64_t capacity, uint64_t *n_sites) {
+    const dcn_pileup_call_params *prm = static_cast<const dcn_pileup_call_params *>(params);
+    if (!prm) return dcn_fail(DCN_ERR_ARG, "params is NULL");
+    if (prm->reserved[0] != 0 || prm->reserved[1] != 0) return dcn_fail(DCN_ERR_ARG, "params.reserved must be 0");
+    if (prm->min_permille > 1000) return dcn_fail(DCN_ERR_ARG, "params.min_permille must be 0..1000");
+    DCN_TRY(check_pileup(map));
+    uint64_t b0 = 0;
+    DCN_TRY(check_range(map, "pileup call", record, start, n_bases, &b0));
+    if (!n_sites) return dcn_fail(DCN_ERR_ARG, "n_sites is NULL");
+    *n_sites = 0;
+    if (n_bases == 0) return DCN_OK;
+    DCN_HIP(hipSetDevice(map->device));
+
+    const uint32_t blocks = dcn_pileup_call_blocks(n_bases);
+    scratch mem;
+    dcn_pileup_call_args ca;
+    memset(&ca, 0, sizeof(ca));
+    uint32_t *d_counts = nullptr;
+    uint64_t *d_offsets = nullptr;
+    unsigned long long *d_sums = nullptr;
+    DCN_TRY(mem.get(&ca.calls, n_bases, "pileup calls"));
+    DCN_TRY(mem.get(&d_counts, blocks, "pileup site counts"));
+    DCN_TRY(mem.get(&d_offsets, (uint64_t)blocks + 1, "pileup site offsets"));
+    DCN_TRY(mem.get(&d_sums, blocks / DCN_SCAN_BLOCK + 2, "pileup scan sums"));
+    ca.counters = map->d_pileup;
+    ca.bases = map->pileup_bases;
+    ca.t_packed = map->store->d_packed;
+    ca.t_invmask = map->store->d_invmask;
+    ca.base0 = b0;
+    ca.n = n_bases;
+    ca.pos0 = start;
+    ca.min_depth = prm->min_depth;
+    ca.min_permille = prm->min_permille;
+    ca.block_counts = d_counts;
+    ca.block_offsets = d_offsets;
+    // count, scan, gather: the shape of dcn_locate_batch and dcn_align_batch (the null stream: a map has none of its own)
+    DCN_TRY(dcn_launch_pileup_call(ca, false, nullptr));
+    DCN_TRY(dcn_launch_offsets_scan(d_counts, blocks, d_sums, d_offsets, nullptr));
+    uint64_t total = 0;
+    DCN_HIP(hipMemcpy(&total, d_offsets + blocks, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    *n_sites = total;
+    if (calls) DCN_HIP(hipMemcpy(calls, ca.calls, n_bases, hipMemcpyDeviceToHost));
+    if (total > capacity)
+        return dcn_fail(DCN_ERR_CAPACITY, "the sites hold " + std::to_string(capacity) + " entries, the range has " + std::to_string(total) +
+                                              " (n_sites and calls are complete: call again with that capacity)");
+    if (total == 0) return DCN_OK;
+    if (!site_pos || !site_info) return dcn_fail(DCN_ERR_ARG, "site_pos/site_info is NULL");
+    DCN_TRY(mem.get(&ca.site_pos, total, "pileup site positions"));
+    DCN_TRY(mem.get(&ca.site_info, total, "pileup site info"));
+    DCN_TRY(dcn_launch_pileup_call(ca, true, nullptr));
+    DCN_HIP(hipMemcpy(site_pos, ca.site_pos, total * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    DCN_HIP(hipMemcpy(site_info, ca.site_info, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return DCN_OK;
+}

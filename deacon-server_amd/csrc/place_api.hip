@@ -193,6 +193,9 @@ extern "C" int dcn_anchor_map_create(const dcn_index *index, dcn_index **out) {
 extern "C" int dcn_anchor_map_add(dcn_index *map, dcn_ctx *ctx, const uint8_t *bases, const uint64_t *offsets,
                                   uint32_t n_records, uint32_t *first_record) {
     DCN_TRY(check_map(map));
+    if (map->d_pileup)
+        return dcn_fail(DCN_ERR_ARG, "the map has a pileup, which covers the records added before it was enabled and does not grow: "
+                                     "dcn_anchor_map_pileup_enable(map, 0) first");
     if (!ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
     DCN_TRY(check_ctx_matches(ctx, map, "the map"));
     if (first_record) *first_record = map->anchor_records;

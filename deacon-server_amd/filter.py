@@ -671,6 +671,11 @@ PAIR_PLACEMENT_DTYPE = np.dtype(SPLIT_PLACEMENT_DTYPE.descr + [("flags", np.uint
                                                                ("tlen", np.int64)])
 PAIR_PROPER, PAIR_RESCUED, PAIR_MATE_PLACED = 1, 2, 4  # DCN_PAIR_*: bits of `flags`
 VERIFY_OVER, VERIFY_UNPLACED = N.VERIFY_OVER, N.VERIFY_UNPLACED  # DCN_VERIFY_*: what `edits` holds instead of a distance
+# DCN_PILEUP_*: the columns of AnchorMap.pileup_fetch, the flags of a site's info and the code of no call
+PILEUP_A, PILEUP_C, PILEUP_G, PILEUP_T, PILEUP_N, PILEUP_DEL, PILEUP_INS, PILEUP_REV = (
+    N.PILEUP_A, N.PILEUP_C, N.PILEUP_G, N.PILEUP_T, N.PILEUP_N, N.PILEUP_DEL, N.PILEUP_INS, N.PILEUP_REV)
+PILEUP_COLUMNS = N.PILEUP_COLUMNS
+PILEUP_SITE_SUB, PILEUP_SITE_DEL, PILEUP_SITE_INS, PILEUP_NO_CODE = N.PILEUP_SITE_SUB, N.PILEUP_SITE_DEL, N.PILEUP_SITE_INS, N.PILEUP_NO_CODE
 _CIGAR_LETTERS = {N.CIGAR_INS: "I", N.CIGAR_DEL: "D", N.CIGAR_EQUAL: "=", N.CIGAR_DIFF: "X"}
 
 
@@ -693,6 +698,7 @@ class AnchorMap(Index):
         super().__init__(h, index.device)
         self._ctx = None
         self.keeps_bases = bool(keep_bases)
+        self._record_lengths = []
         if keep_bases:
             N.check(N.lib().dcn_anchor_map_keep_bases(self._h))
 
@@ -701,6 +707,53 @@ class AnchorMap(Index):
         out = np.zeros(max(int(n), 1), np.uint8)
         N.check(N.lib().dcn_anchor_map_fetch(self._h, int(record), int(start), int(n), _ptr(out)))
         return out[:int(n)].tobytes()
+
+    def pileup_enable(self):
+        """Eight uint32 counters per base of the records added so far, all zero (dcn_anchor_map_pileup_enable; the
+        definition of a pileup is in include/deacon_hip.h): 32 B of device memory per kept base.  The map must keep
+        bases; while the pileup is enabled add() is refused.  Placer.pileup_batch adds rows to it."""
+        N.check(N.lib().dcn_anchor_map_pileup_enable(self._h, 1))
+
+    def pileup_disable(self):
+        N.check(N.lib().dcn_anchor_map_pileup_enable(self._h, 0))
+
+    def pileup_reset(self):
+        """every counter back to zero"""
+        N.check(N.lib().dcn_anchor_map_pileup_reset(self._h))
+
+    def pileup_fetch(self, record, start=0, n=None):
+        """the counters of positions [start, start + n) of a record (n=None: to its end) -> np.uint32[n, 8], the columns
+        PILEUP_A, C, G, T, N, DEL, INS, REV"""
+        start, n = int(start), self._to_end(record, start) if n is None else int(n)
+        out = np.zeros((max(n, 1), N.PILEUP_COLUMNS), np.uint32)
+        N.check(N.lib().dcn_anchor_map_pileup_fetch(self._h, int(record), start, n, _ptr(out)))
+        return out[:n]
+
+    def pileup_call(self, record, start=0, n=None, min_depth=3, min_permille=500):
+        """Rule P6 over positions [start, start + n) of a record (n=None: to its end) -> (calls bytes of ACGT-N, site_pos
+        np.uint64[], site_info np.uint32[]): the sites in ascending record position, info = flags (PILEUP_SITE_SUB / _DEL /
+        _INS) | call_code << 8 | ref_code << 16.  min_depth = 3 and min_permille = 500 are conventions, not measured
+        optima.  One call with an estimate and, on DCN_ERR_CAPACITY, a second with the size the first reported."""
+        start, n = int(start), self._to_end(record, start) if n is None else int(n)
+        p = N.PileupCallParams(int(min_depth), int(min_permille), (C.c_uint32 * 2)(0, 0))
+        calls = np.zeros(max(n, 1), np.uint8)
+        n_sites = C.c_uint64()
+
+        def call(cap):
+            pos, info = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint32)
+            rc = N.lib().dcn_anchor_map_pileup_call(self._h, C.byref(p), int(record), start, n, _ptr(calls), _ptr(pos) if cap else None,
+                                                    _ptr(info) if cap else None, cap, C.byref(n_sites))
+            return rc, pos, info
+
+        rc, pos, info = call(n // 64 + 64)
+        if rc == N.DCN_ERR_CAPACITY:
+            rc, pos, info = call(int(n_sites.value))
+        N.check(rc)
+        return calls[:n].tobytes(), pos[:int(n_sites.value)], info[:int(n_sites.value)]
+
+    def _to_end(self, record, start):
+        """bases from `start` to the end of a record (the lengths of the records add() has taken are kept here)"""
+        return self._record_lengths[int(record)] - int(start)
 
     def clone(self, device):
         h = C.c_void_p()
@@ -723,6 +776,7 @@ class AnchorMap(Index):
         first = C.c_uint32()
         ctx = self._context(int(offsets[-1]) if n > 0 else 0, n)
         N.check(N.lib().dcn_anchor_map_add(self._h, ctx._h, _ptr(bases) if len(bases) else None, _ptr(offsets), n, C.byref(first)))
+        self._record_lengths += np.diff(offsets.astype(np.int64)).tolist() if n else []
         return first.value
 
     def add_records(self, records):
@@ -881,6 +935,33 @@ class Placer(_Context):
             rc, cigar = call(int(cigar_offsets[n_rows]))
         N.check(rc)
         return edits[:n_rows], cigar_offsets, cigar[:int(cigar_offsets[n_rows])]
+
+    def pileup_batch(self, bases, offsets, rows, row_offsets=None, max_edits=1023, max_permille=200, select=None):
+        """align_batch's rows added to the anchor map's pileup (dcn_pileup_batch; the definition of a pileup is in
+        include/deacon_hip.h): every row with an alignment adds one count per base of its record interval, in the column
+        of the read's base there or in DEL, one in INS per inserted run, and REV beside each on the reverse strand.  The
+        runs never leave the device.  select: an optional boolean mask over the rows; a row it leaves out is given as
+        unplaced, in a copy (the caller's rows are not written).  -> (edits np.uint32[n_rows] as verify_batch returns
+        them for the rows given, n_added).  The map needs AnchorMap.pileup_enable() first.  profile(): pack in its slot,
+        everything else in 'finish'."""
+        bases, offsets, n_reads = _batch(bases, offsets)
+        rows = np.ascontiguousarray(rows)
+        n_rows = len(rows)
+        if select is not None:
+            select = np.asarray(select, bool)
+            if select.shape != (n_rows,):
+                raise ValueError("pileup_batch: select must hold one boolean per row")
+            rows = rows.copy()
+            rows["record"][~select] = UNPLACED
+        if row_offsets is not None:
+            row_offsets = np.ascontiguousarray(row_offsets, dtype=np.uint64)
+        edits = np.zeros(max(n_rows, 1), np.uint32)
+        n_added = C.c_uint64()
+        p = N.VerifyParams(int(max_edits), int(max_permille), rows.dtype.itemsize, 0)
+        N.check(N.lib().dcn_pileup_batch(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None, _ptr(offsets), n_reads,
+                                         C.byref(p), _ptr(row_offsets), _ptr(rows) if n_rows else None, n_rows, _ptr(edits),
+                                         C.byref(n_added)))
+        return edits[:n_rows], int(n_added.value)
 
     def place_pairs(self, reads1, reads2, **kw):
         """the mates of two lists, interleaved -> place_pair_batch's result"""

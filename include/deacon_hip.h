@@ -77,9 +77,10 @@ enum {
  * 1.11 = dcn_place_pair_batch.
  * 1.12 = dcn_ctx_last_batch_short.
  * 1.13 = dcn_anchor_map_keep_bases / _fetch, dcn_verify_batch.
- * 1.14 = dcn_align_batch. */
+ * 1.14 = dcn_align_batch.
+ * 1.15 = dcn_anchor_map_pileup_* / dcn_pileup_batch. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 14
+#define DCN_ABI_MINOR 15
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -920,6 +921,100 @@ int dcn_verify_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, c
 int dcn_align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
                     const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits,
                     uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity);
+
+/* ---- pileup: per-base counts of the aligned rows on the reference, and site calls (ABI 1.15) --------------------------
+ * (no reference counterpart.)  dcn_align_batch's results are per read; a pileup sums them per reference position.
+ *
+ * THE DEFINITION OF A PILEUP.  Rules 1-6 of a verified placement and A1-A6 of an aligned placement stand.  Added:
+ *   P1. A map that keeps bases may hold a pileup: for every base of every record added so far, eight uint32_t counters,
+ *       all zero when enabled: the columns DCN_PILEUP_A .. DCN_PILEUP_REV below.
+ *   P2. Only a row with an alignment (A1: edits = d <= E) adds.  An OVER row, an UNPLACED row and a row with n = 0 add
+ *       nothing.  The library has no policy on which rows count: a caller leaves a row out by setting its record to
+ *       UINT32_MAX.
+ *   P3. Walk the row's runs from the start of both intervals; i counts bases of S (already reverse-complemented when the
+ *       row says so), j bases of T.
+ *         An '=' or X step at (i, j) adds 1 at record position ref_start + j, in the column of S[i]: A, C, G, T by rule
+ *           2's alphabet regardless of case, or N when S[i] is invalid.
+ *         A D step adds 1 to DEL at ref_start + j.
+ *         Every '=', X and D step of a row with reverse = 1 also adds 1 to REV at its position.
+ *         An I RUN, of whatever length, adds 1 to INS: at ref_start + j - 1, the base of T in front of it, if j > 0, else
+ *           at ref_start.  This is always inside T, since n > 0.  Inserted bases are not recorded.
+ *   P4. depth(p) is the sum of columns 0-5.  Over one row, each position of T receives exactly one add among columns 0-5.
+ *   P5. Integers only.  Adds commute: the counters after any sequence of calls depend only on the multiset of rows added,
+ *       not on how batches are cut, on align's trace groups, on lanes or on order.  A counter wraps above 2^32 - 1;
+ *       nothing saturates.
+ *   P6. Calls, with the parameters min_depth and min_permille (0 .. 1000).  At a position:
+ *         best is the first of A, C, G, T, DEL with the largest count; N never wins.
+ *         The position is CALLED when depth > 0, depth >= min_depth and best_count * 1000 >= depth * min_permille
+ *           (64-bit products).  The call character is then one of ACGT-; otherwise it is N.
+ *         ref is the record's base, where an invalid base differs from everything.
+ *         Flags: DCN_PILEUP_SITE_SUB when the position is called, the call is a base and it differs from ref;
+ *           DCN_PILEUP_SITE_DEL when it is called and the call is '-'; DCN_PILEUP_SITE_INS when depth > 0,
+ *           depth >= min_depth and INS * 1000 >= depth * min_permille, whether or not the position is called.
+ *         A SITE is a position with flags != 0; site_info = flags | call_code << 8 | ref_code << 16, with the codes
+ *           0-3 = A, C, G, T, 4 = DEL and DCN_PILEUP_NO_CODE = no call, or an invalid reference base.
+ *       min_depth = 3 and min_permille = 500 are conventions of the layers above, not measured optima. */
+#define DCN_PILEUP_A 0
+#define DCN_PILEUP_C 1
+#define DCN_PILEUP_G 2
+#define DCN_PILEUP_T 3
+#define DCN_PILEUP_N 4
+#define DCN_PILEUP_DEL 5
+#define DCN_PILEUP_INS 6
+#define DCN_PILEUP_REV 7
+#define DCN_PILEUP_COLUMNS 8
+#define DCN_PILEUP_SITE_SUB 1u
+#define DCN_PILEUP_SITE_DEL 2u
+#define DCN_PILEUP_SITE_INS 4u
+#define DCN_PILEUP_NO_CODE 7u
+typedef struct dcn_pileup_call_params {
+    uint32_t min_depth;
+    uint32_t min_permille; /* 0 .. 1000 */
+    uint32_t reserved[2];  /* must be 0 */
+} dcn_pileup_call_params;  /* 16 bytes */
+
+/* dcn_anchor_map_pileup_enable comes after the records: it allocates 32 bytes of device memory per kept base (whole
+ * 32-base groups, as the store counts them) and zeroes them; dcn_index_memory does not count this memory, as it does not
+ * count the base store.  DCN_ERR_ARG for an index that is not a map and for a map that keeps no bases.  Enabling again
+ * changes nothing; enable = 0 frees.  While a pileup is enabled dcn_anchor_map_add on that map is DCN_ERR_ARG (a pileup
+ * does not grow); a map without one behaves exactly as before in every call.  dcn_index_clone gives an index without the
+ * pileup, dcn_index_destroy frees it.  dcn_anchor_map_pileup_reset zeroes every counter. */
+int dcn_anchor_map_pileup_enable(dcn_index *map, int enable);
+int dcn_anchor_map_pileup_reset(dcn_index *map);
+
+/*   ctx .. n_rows   as for dcn_verify_batch: the same checks in the same order with the same messages and row numbers
+ *   edits           n_rows entries: exactly what dcn_verify_batch returns
+ *   n_added         may be NULL: the number of rows that added, by P2
+ * DCN_ERR_ARG beyond dcn_verify_batch's: a map with no pileup enabled; dcn_align_batch's rules on a row with
+ * max(m, n) >= 2^28 and on more than 2^32 - 1 rows.  Any DCN_ERR_ARG leaves the counters untouched.  Host pointers,
+ * blocking, refused while batches are in flight; the six counters of the context are left unchanged.  One call at a time
+ * per map: overlapping calls on one map (from two contexts) are not supported.
+ * The call runs dcn_align_batch's passes: verify, the align kernel of every trace group (DCN_ALIGN_TRACE_BYTES applies as
+ * it does there), the scan of the run counts and the gather.  The runs stay on the device, in a buffer of the context
+ * that grows to the size the scan reports (no capacity protocol); then the pileup kernel walks them, one wave per aligned
+ * row, and adds with atomic adds on the map's counters.  Device memory: dcn_align_batch's.
+ * dcn_ctx_set_profiling covers it: pack in its slot, everything else in FINISH; plan, scan and DISTINCT are empty. */
+int dcn_pileup_batch(dcn_ctx *ctx, dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                     const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits,
+                     uint64_t *n_added);
+
+/* The counters of positions [start, start + n_bases) of a record, position-major: counts[8 q + column] belongs to
+ * position start + q (on the device they lie column by column; the call transposes).  Blocking.  Errors as for
+ * dcn_anchor_map_fetch, and DCN_ERR_ARG for a map with no pileup enabled.  n_bases = 0 succeeds. */
+int dcn_anchor_map_pileup_fetch(const dcn_index *map, uint32_t record, uint64_t start, uint64_t n_bases, uint32_t *counts);
+
+/* Rule P6 over positions [start, start + n_bases) of a record.
+ *   params      a dcn_pileup_call_params (declared void * for the reason given at dcn_locate_batch); reserved != 0 or
+ *               min_permille > 1000 is DCN_ERR_ARG
+ *   calls       NULL, or n_bases characters of ACGT-N
+ *   site_pos    the sites in ascending position, record-relative and 0-based; site_info as P6 packs it
+ *   capacity    entries of site_pos and of site_info
+ *   n_sites     always receives the number of sites there is
+ * DCN_ERR_CAPACITY when capacity is smaller: calls is complete and no site is written; NULLs with capacity 0 ask for the
+ * count (dcn_locate_batch's convention: call again with that capacity).  Range errors as for dcn_anchor_map_fetch.
+ * Blocking; one thread per position, a scan of the per-workgroup site counts, and a second pass that writes the sites. */
+int dcn_anchor_map_pileup_call(const dcn_index *map, const void *params, uint32_t record, uint64_t start, uint64_t n_bases,
+                               uint8_t *calls, uint64_t *site_pos, uint32_t *site_info, uint64_t capacity, uint64_t *n_sites);
 
 /* ---- counters: ProcessingStats (src/local_filter.rs:179-187, merged at :388-396) -------------------------- */
 
