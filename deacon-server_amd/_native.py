@@ -171,6 +171,27 @@ PILEUP_SITE_SUB, PILEUP_SITE_DEL, PILEUP_SITE_INS = 1, 2, 4
 PILEUP_NO_CODE = 7
 
 
+class ExtendParams(C.Structure):
+    _fields_ = [
+        ("penalty", C.c_uint32),
+        ("end_bonus", C.c_uint32),
+        ("max_edits", C.c_uint32),
+        ("row_stride", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class Extension(C.Structure):
+    _fields_ = [
+        ("read_start", C.c_uint32),
+        ("read_end", C.c_uint32),
+        ("ref_start", C.c_uint64),
+        ("ref_end", C.c_uint64),
+        ("left_edits", C.c_uint32),
+        ("right_edits", C.c_uint32),
+    ]
+
+
 def build(force=False, jobs=6):
     """Compile every HIP source for gfx950 into lib/libdeacon_hip.so (hipcc cross-compiles without a GPU)."""
     csrc = os.path.join(_PKG, "csrc")
@@ -287,10 +308,11 @@ _SIGNATURES = {
     "dcn_pileup_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp, _u64p]),
     "dcn_anchor_map_pileup_fetch": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
     "dcn_anchor_map_pileup_call": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _u64p]),
+    "dcn_extend_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp]),
 }
 
 _lib = None
-ABI = (1, 15)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 16)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

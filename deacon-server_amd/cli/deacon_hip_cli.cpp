@@ -3811,6 +3811,11 @@ struct MapArgs {
     bool pileup = false, all_ranks = false, all_positions = false, has_sites = false;
     unsigned min_mapq = 1, min_depth = 3, min_frac = 500;
     std::string sites;
+    // `extend`: map's placements carried over the read's flanks (dcn_extend_batch), then align's PAF with -o and / or
+    // pileup's counts with --pileup / --sites, both over the extended rows; verify is set as well
+    bool extend = false, has_output = false, has_pileup_out = false;
+    unsigned penalty = 6, end_bonus = 4, ext_max_edits = DCN_VERIFY_MAX_EDITS;
+    std::string pileup_out;
 };
 
 // one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
@@ -3821,7 +3826,7 @@ struct MapArgs {
 // all its bases, and cg:Z: follows NM)
 void append_paf(std::string &rows, const std::string &read_name, uint32_t read_len, const dcn_split_placement &p,
                 const std::string &record_name, uint32_t record_len, uint32_t k, uint32_t edits = DCN_VERIFY_UNPLACED,
-                const uint32_t *cigar = nullptr, uint64_t n_ops = 0) {
+                const uint32_t *cigar = nullptr, uint64_t n_ops = 0, const std::string &more_tags = std::string()) {
     const uint64_t on_read = p.read_end - p.read_start, on_ref = p.ref_end - p.ref_start;
     const bool verified = edits != DCN_VERIFY_UNPLACED && edits != DCN_VERIFY_OVER;
     uint64_t matches = verified ? std::max(on_read, on_ref) - edits : std::min<uint64_t>((uint64_t)p.votes * k, on_read);
@@ -3853,6 +3858,7 @@ void append_paf(std::string &rows, const std::string &read_name, uint32_t read_l
         }
         if (n_ops == 0) rows += '*'; // (two empty extents: no placement call reports one)
     }
+    rows += more_tags; // (`extend`: xl, xr, cl, cr)
     rows += '\n';
 }
 
@@ -3860,17 +3866,30 @@ int run_map(const MapArgs &a) {
     const Stopwatch watch;
     AnchorRef R;
     load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, 
-                    a.align || a.pileup ? "DCN_CLI_ALIGN_BATCH_BASES" : a.verify ? "DCN_CLI_VERIFY_BATCH_BASES" : "DCN_CLI_MAP_BATCH_BASES", a.quiet, a.verify);
+                    a.align || a.pileup || a.extend ? "DCN_CLI_ALIGN_BATCH_BASES" : a.verify ? "DCN_CLI_VERIFY_BATCH_BASES" : "DCN_CLI_MAP_BATCH_BASES", a.quiet, a.verify);
     Context &ctx = *R.ctx;
-    if (a.pileup) deacon::check(dcn_anchor_map_pileup_enable(R.map.p, 1)); // (after the records: a pileup does not grow)
+    const bool piles = a.pileup || (a.extend && (a.has_pileup_out || a.has_sites)); // (the map's counters are used)
+    if (piles) deacon::check(dcn_anchor_map_pileup_enable(R.map.p, 1)); // (after the records: a pileup does not grow)
     dcn_place_split_params prm = {};
     prm.band_bases = a.band;
     prm.min_votes = a.min_votes;
     prm.prefix_length = a.prefix_length;
     prm.max_placements = a.max_placements;
-    TextOut out(a.output, true);
+    TextOut out;
+    const bool prints = !a.extend || a.has_output; // (`extend` prints PAF only when asked to)
+    if (prints) out.open(a.output, true);
     FastxReader rd(a.input);
     uint64_t reads_in = 0, placed = 0, split_reads = 0, placements = 0, mapq60 = 0, mapq0 = 0;
+    uint64_t rows_extended = 0, bases_gained = 0, bases_clipped = 0, full_length_rows = 0; // (extend)
+    dcn_extend_params xprm = {};
+    xprm.penalty = a.penalty;
+    xprm.end_bonus = a.end_bonus;
+    xprm.max_edits = a.ext_max_edits;
+    xprm.row_stride = sizeof(dcn_split_placement);
+    std::vector<dcn_extension> ext;
+    std::vector<dcn_split_placement> xpl; // the rows just placed with the four coordinates of their extension
+    std::vector<uint32_t> pile_edits;     // (`extend` with -o keeps align's edits of every row for the PAF)
+    std::string tags;
     uint64_t verified = 0, unverified = 0, edits_sum = 0, verified_bases = 0;
     uint64_t op_bases[16] = {}, cigar_ops = 0; // (align: bases per op code, and runs)
     uint64_t rows_selected = 0, rows_added = 0; // (pileup)
@@ -3893,11 +3912,23 @@ int run_map(const MapArgs &a) {
         pl.resize((size_t)n_reads * a.max_placements);  // (never more than max_placements per read)
         deacon::check(dcn_place_split_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &prm, place_off.data(),
                                             pl.data(), pl.size(), nullptr));
-        if (a.align) { // the same reads, the rows just placed: their distances and the runs of the verified ones
+        if (a.extend) { // the rows just placed, grown over the flanks of their reads: what every call below takes
+            ext.resize(place_off[n_reads]);
+            deacon::check(dcn_extend_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &xprm, place_off.data(), pl.data(),
+                                           place_off[n_reads], ext.data()));
+            xpl.assign(pl.begin(), pl.begin() + (ptrdiff_t)place_off[n_reads]);
+            for (size_t q = 0; q < xpl.size(); ++q) {
+                xpl[q].read_start = ext[q].read_start, xpl[q].read_end = ext[q].read_end;
+                xpl[q].ref_start = ext[q].ref_start, xpl[q].ref_end = ext[q].ref_end;
+            }
+        }
+        const dcn_split_placement *const use = a.extend ? xpl.data() : pl.data(); // the rows of verify, align and pileup
+        const bool aligns = a.align || (a.extend && a.has_output);
+        if (aligns) { // the same reads, the rows just placed: their distances and the runs of the verified ones
             edits.resize(place_off[n_reads]);
             cigar_off.assign(place_off[n_reads] + 1, 0);
             for (int attempt = 0;; ++attempt) {
-                const int rc = dcn_align_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), pl.data(),
+                const int rc = dcn_align_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), use,
                                                place_off[n_reads], edits.data(), cigar_off.data(), cigar.data(), cigar.size());
                 if (rc != DCN_ERR_CAPACITY || attempt) {
                     deacon::check(rc);
@@ -3905,18 +3936,24 @@ int run_map(const MapArgs &a) {
                 }
                 cigar.resize(cigar_off[place_off[n_reads]]); // (the size the first call reported)
             }
-        } else if (a.pileup) { // the rows just placed, those that --min-mapq and the rank leave: unplaced in a copy
+        } else if (a.extend && !piles) { // (neither output: the distances of the extended rows, for the summary)
             edits.resize(place_off[n_reads]);
-            chosen.assign(pl.begin(), pl.begin() + (ptrdiff_t)place_off[n_reads]);
+            deacon::check(dcn_verify_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), use,
+                                           place_off[n_reads], edits.data()));
+        }
+        if (piles) { // the rows just placed, those that --min-mapq and the rank leave: unplaced in a copy
+            std::vector<uint32_t> &into = aligns ? pile_edits : edits;
+            into.resize(place_off[n_reads]);
+            chosen.assign(use, use + (ptrdiff_t)place_off[n_reads]);
             for (dcn_split_placement &p : chosen) {
                 if (p.mapq >= a.min_mapq && (a.all_ranks || p.rank == 0)) ++rows_selected;
                 else p.record = UINT32_MAX;
             }
             uint64_t added = 0;
             deacon::check(dcn_pileup_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), chosen.data(),
-                                           place_off[n_reads], edits.data(), &added));
+                                           place_off[n_reads], into.data(), &added));
             rows_added += added;
-        } else if (a.verify) {
+        } else if (a.verify && !a.align && !a.extend) {
             edits.resize(place_off[n_reads]);
             deacon::check(dcn_verify_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), pl.data(),
                                            place_off[n_reads], edits.data()));
@@ -3931,9 +3968,22 @@ int run_map(const MapArgs &a) {
             placements += p1 - p0;
             const std::string name(p1 > p0 ? id_token(b, rec) : std::string_view());
             for (uint64_t q = p0; q < p1; ++q) {
-                const dcn_split_placement &p = pl[q];
+                const dcn_split_placement &p = use[q];
                 ++per_record[p.record];
                 mapq60 += p.mapq == 60, mapq0 += p.mapq == 0;
+                if (a.extend) { // what the flanks gave, and what is left of the read: in the record's direction
+                    const uint64_t lo = pl[q].read_start - p.read_start, hi = p.read_end - pl[q].read_end;
+                    const uint64_t clip_lo = p.read_start, clip_hi = rec.seq_len - p.read_end;
+                    rows_extended += lo + hi > 0, bases_gained += lo + hi, bases_clipped += clip_lo + clip_hi;
+                    full_length_rows += clip_lo + clip_hi == 0;
+                    tags = "\txl:i:" + std::to_string(p.reverse ? hi : lo) + "\txr:i:" + std::to_string(p.reverse ? lo : hi) +
+                           "\tcl:i:" + std::to_string(p.reverse ? clip_hi : clip_lo) + "\tcr:i:" + std::to_string(p.reverse ? clip_lo : clip_hi);
+                    if (!a.has_output) { // (no PAF: the distances count, as in pileup)
+                        if (edits[q] == DCN_VERIFY_OVER) ++unverified;
+                        else if (edits[q] != DCN_VERIFY_UNPLACED) ++verified, edits_sum += edits[q];
+                        continue;
+                    }
+                }
                 if (a.pileup) { // (no PAF here: a row that was left out is neither verified nor unverified)
                     if (edits[q] == DCN_VERIFY_OVER) ++unverified;
                     else if (edits[q] != DCN_VERIFY_UNPLACED) ++verified, edits_sum += edits[q];
@@ -3948,25 +3998,27 @@ int run_map(const MapArgs &a) {
                         verified_bases += std::max<uint64_t>(p.read_end - p.read_start, p.ref_end - p.ref_start);
                     }
                 }
-                if (a.align) {
+                if (aligns) {
                     const uint32_t *const runs = cigar.data() + cigar_off[q];
                     const uint64_t n_ops = cigar_off[q + 1] - cigar_off[q];
                     cigar_ops += n_ops;
                     for (uint64_t o = 0; o < n_ops; ++o) op_bases[runs[o] & 15u] += runs[o] >> 4;
-                    append_paf(rows, name, rec.seq_len, p, R.names[p.record], R.lens[p.record], R.k, edits[q], runs, n_ops);
+                    append_paf(rows, name, rec.seq_len, p, R.names[p.record], R.lens[p.record], R.k, edits[q], runs, n_ops, a.extend ? tags : std::string());
                     continue;
                 }
                 append_paf(rows, name, rec.seq_len, p, R.names[p.record], R.lens[p.record], R.k, a.verify ? edits[q] : DCN_VERIFY_UNPLACED);
             }
         }
-        out.write(rows);
+        if (prints) out.write(rows);
     });
     // pileup: the counters of every record, a stretch at a time, as TSV; the sites of the same stretches
     uint64_t covered = 0, n_sites = 0, column_sum[DCN_PILEUP_COLUMNS] = {};
-    if (a.pileup) {
-        TextOut sites_out;
+    if (piles) {
+        TextOut sites_out, pile_file;
         if (a.has_sites) sites_out.open(a.sites, false);
-        out.write("record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\n");
+        if (a.extend && a.has_pileup_out) pile_file.open(a.pileup_out, false);
+        TextOut *const tsv = a.pileup ? &out : a.has_pileup_out ? &pile_file : nullptr; // (`extend --sites` alone: no table)
+        if (tsv) tsv->write("record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\n");
         if (a.has_sites) sites_out.write("record\tpos\tref\tcall\tdepth\tflags\n");
         dcn_pileup_call_params cprm = {};
         cprm.min_depth = a.min_depth;
@@ -3995,7 +4047,7 @@ int run_map(const MapArgs &a) {
                     for (int col = 0; col < DCN_PILEUP_COLUMNS; ++col) rows += '\t' + std::to_string(c[col]);
                     rows += '\n';
                 }
-                out.write(rows);
+                if (tsv) tsv->write(rows);
                 uint64_t found = 0;
                 for (int attempt = 0;; ++attempt) { // (dcn_locate_batch's convention: the first call reports the size)
                     const int rc = dcn_anchor_map_pileup_call(R.map.p, &cprm, r, start, n, nullptr, site_pos.data(), site_info.data(),
@@ -4022,17 +4074,22 @@ int run_map(const MapArgs &a) {
             }
         }
         if (a.has_sites) sites_out.finish();
+        if (a.extend && a.has_pileup_out) pile_file.finish();
     }
-    out.finish();
+    if (prints) out.finish();
     const double secs = watch.seconds();
     if (!a.quiet) {
-        if (a.pileup)
+        if (a.extend)
+            std::fprintf(stderr, "Extended %llu of %llu placements by %llu bases (%llu bases clipped, %llu placements full length)\n",
+                         (unsigned long long)rows_extended, (unsigned long long)placements, (unsigned long long)bases_gained,
+                         (unsigned long long)bases_clipped, (unsigned long long)full_length_rows);
+        if (piles)
             std::fprintf(stderr, "Piled up %llu of %llu placements on %llu positions (%llu sites)\n", (unsigned long long)rows_added,
                          (unsigned long long)placements, (unsigned long long)covered, (unsigned long long)n_sites);
         if (a.verify && !a.pileup)
             std::fprintf(stderr, "Verified %llu of %llu placements (%llu edits over %llu bases)\n", (unsigned long long)verified,
                          (unsigned long long)placements, (unsigned long long)edits_sum, (unsigned long long)verified_bases);
-        if (a.align)
+        if (a.align || (a.extend && a.has_output))
             std::fprintf(stderr, "Aligned %llu placements in %llu runs (%llu =, %llu X, %llu I, %llu D)\n", (unsigned long long)verified,
                          (unsigned long long)cigar_ops, (unsigned long long)op_bases[DCN_CIGAR_EQUAL], (unsigned long long)op_bases[DCN_CIGAR_DIFF],
                          (unsigned long long)op_bases[DCN_CIGAR_INS], (unsigned long long)op_bases[DCN_CIGAR_DEL]);
@@ -4055,12 +4112,17 @@ int run_map(const MapArgs &a) {
                         "  \"edits\": %llu,\n  \"verified_bases\": %llu,\n",
                     a.max_edits, a.max_div, (unsigned long long)verified, (unsigned long long)unverified, (unsigned long long)edits_sum,
                     (unsigned long long)verified_bases);
-        if (a.align)
+        if (a.extend)
+            appendf(js, "  \"penalty\": %u,\n  \"end_bonus\": %u,\n  \"ext_max_edits\": %u,\n  \"rows_extended\": %llu,\n"
+                        "  \"bases_gained\": %llu,\n  \"bases_clipped\": %llu,\n  \"full_length_rows\": %llu,\n",
+                    a.penalty, a.end_bonus, a.ext_max_edits, (unsigned long long)rows_extended, (unsigned long long)bases_gained,
+                    (unsigned long long)bases_clipped, (unsigned long long)full_length_rows);
+        if (a.align || (a.extend && a.has_output))
             appendf(js, "  \"matches\": %llu,\n  \"mismatches\": %llu,\n  \"insertions\": %llu,\n  \"deletions\": %llu,\n"
                         "  \"cigar_ops\": %llu,\n",
                     (unsigned long long)op_bases[DCN_CIGAR_EQUAL], (unsigned long long)op_bases[DCN_CIGAR_DIFF],
                     (unsigned long long)op_bases[DCN_CIGAR_INS], (unsigned long long)op_bases[DCN_CIGAR_DEL], (unsigned long long)cigar_ops);
-        if (a.pileup) {
+        if (piles) {
             appendf(js, "  \"min_mapq\": %u,\n  \"all_ranks\": %s,\n  \"min_depth\": %u,\n  \"min_permille\": %u,\n"
                         "  \"rows_selected\": %llu,\n  \"rows_added\": %llu,\n  \"positions_covered\": %llu,\n  \"sites\": %llu,\n",
                     a.min_mapq, a.all_ranks ? "true" : "false", a.min_depth, a.min_frac, (unsigned long long)rows_selected,
@@ -4219,6 +4281,7 @@ void usage() {
                  "  verify  As map, with every placement compared base by base with the reference: edit distance, as PAF\n"
                  "  align   As verify, with the alignment of every verified placement: cg:Z: with = X I D, as PAF\n"
                  "  pileup  As align, summed per reference position: counts of A C G T N, gaps and strand, and site calls, as TSV\n"
+                 "  extend  As map, each placement carried over the flanks of its read, the rest soft-clipped; then align, pileup\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -4498,6 +4561,55 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "Calls: the most frequent of A C G T and gap (the first of them on a tie; N never wins) when it reaches\n"
                "--min-frac of a depth of at least --min-depth.  The defaults are conventions, not measured optima.\n"
                "No inserted bases, no consensus sequence, no VCF, no base qualities.  Mates are independent here: one input.\n";
+    else if (sub == "extend")
+        text = "Carry each read's placements over the flanks of the read, clip the rest, then align them and / or pile them up\n\n"
+               "Usage: deacon-hip extend [OPTIONS] <REF> [READS]\n\n"
+               "Arguments:\n"
+               "  <REF>     Path to the reference fastx file: its records are numbered and named in file order\n"
+               "  [READS]   Optional path to fastx file (or - for stdin; gz, bgzf, zst, xz and bz2 found by content) [default: -]\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Keys that may anchor: a minimizer index file, whose k and w are used\n"
+               "                                 [default: the minimizers of <REF> at -k / -w]\n"
+               "  -k <K>                         K-mer length without -x [default: 31]\n"
+               "  -w <W>                         Minimizer window size without -x [default: 15]\n"
+               "      --penalty <N>              An edit in a flank costs N matched bases of read plus record (2..255)\n"
+               "                                 [default: 6, a convention]\n"
+               "      --end-bonus <N>            Reaching the read's end is worth N (0..65535) [default: 4, a convention]\n"
+               "      --ext-max-edits <N>        At most N edits per flank (0..1023) [default: 1023, a convention]\n"
+               "  -o, --output <OUTPUT>          PAF, one line per placement, as align prints it for the extended extents (- for\n"
+               "                                 stdout), then xl:i: and xr:i:, the read bases gained on the record's left and\n"
+               "                                 right, and cl:i: and cr:i:, the soft clips there [default: no PAF]\n"
+               "      --pileup <FILE>            pileup's TSV over the extended placements: record pos ref A C G T N del ins rev\n"
+               "      --sites <FILE>             pileup's site TSV over them: record pos ref call depth flags\n"
+               "      --all-positions            One line of --pileup for every position of every record\n"
+               "      --min-depth <N>            A call needs a depth of at least N [default: 3, a convention]\n"
+               "      --min-frac <N>             ... and N per 1000 of the depth for the most frequent of A C G T and gap\n"
+               "                                 (0..1000) [default: 500, a convention]\n"
+               "      --min-mapq <N>             Only placements of mapping quality N or more add (0..60) [default: 1, a convention]\n"
+               "      --all-ranks                Every placement of a read adds, not only its first (rank 0)\n"
+               "  -e, --max-edits <N>            Verified means at most N edits over the extended extents (0..1023) [default: 1023,\n"
+               "                                 a convention]\n"
+               "      --max-div <N>              ... and at most N per 1000 bases of the longer extended extent (0..1000)\n"
+               "                                 [default: 200, a convention]\n"
+               "  -N, --max-placements <N>       Placements per read, each from the anchor hits no earlier one explained (1..8)\n"
+               "                                 [default: 4]\n"
+               "      --band <N>                 Width of a diagonal band in bases [default: 256, a convention]\n"
+               "  -a, --min-votes <N>            Minimum number of anchor hits in a placement's cell [default: 2, as filter's -a,\n"
+               "                                 a convention]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per read (0 = entire read) [default: 0]\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file: verify's for the extended extents, and penalty,\n"
+               "                                 end_bonus, ext_max_edits, rows_extended, bases_gained, bases_clipped and\n"
+               "                                 full_length_rows; align's keys with -o, pileup's with --pileup or --sites\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
+               "  -h, --help                     Print help\n\n"
+               "Extension: a placement's extents begin and end on the k-mer of an anchor hit.  On either side, the read's bases\n"
+               "outside them are compared with the record's bases outside them, from the placement outwards: the extension ends\n"
+               "where read bases + record bases - penalty * edits is largest (plus --end-bonus at the read's end; among equals the\n"
+               "fewer edits, then the more read bases), and never leaves the read or the record.  What is left of the read is\n"
+               "the soft clip.  The defaults are conventions, not measured optima.  Integers only: the output does not depend\n"
+               "on how the input is cut into batches.  Unit costs, no affine gaps, no SAM.\n"
+               "Placements and qualities are map's for the same arguments.  Mates are independent here: one input.\n";
     else if (sub == "map-pairs")
         text = "Place the two mates of each pair jointly on a reference: proper pairs, rescued mates and insert sizes, as PAF\n\n"
                "Usage: deacon-hip map-pairs [OPTIONS] <REF> <READS1> [READS2]\n\n"
@@ -4788,11 +4900,12 @@ int main(int argc, char **argv) {
             if (pos.size() > 2) die("place takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[2] + "')");
             return run_place(a);
         }
-        if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup") {
+        if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup" || args[0] == "extend") {
             MapArgs a;
             a.align = args[0] == "align";
             a.pileup = args[0] == "pileup";
-            a.verify = a.align || a.pileup || args[0] == "verify";
+            a.extend = args[0] == "extend";
+            a.verify = a.align || a.pileup || a.extend || args[0] == "verify";
             std::vector<std::string> pos;
             auto number = [&](const std::string &v, const char *flag, long long lo, long long hi) {
                 char *end = nullptr;
@@ -4806,17 +4919,21 @@ int main(int argc, char **argv) {
                 if (s == "-x" || s == "--index") a.index = need(++i), a.has_index = true;
                 else if (s == "-k") a.k = (unsigned)number(need(++i), "-k", 1, 56);
                 else if (s == "-w") a.w = (unsigned)number(need(++i), "-w", 1, 255);
-                else if (s == "-o" || s == "--output") a.output = need(++i);
+                else if (s == "-o" || s == "--output") a.output = need(++i), a.has_output = true;
+                else if (a.extend && s == "--penalty") a.penalty = (unsigned)number(need(++i), "--penalty", 2, 255);
+                else if (a.extend && s == "--end-bonus") a.end_bonus = (unsigned)number(need(++i), "--end-bonus", 0, 65535);
+                else if (a.extend && s == "--ext-max-edits") a.ext_max_edits = (unsigned)number(need(++i), "--ext-max-edits", 0, DCN_VERIFY_MAX_EDITS);
+                else if (a.extend && s == "--pileup") a.pileup_out = need(++i), a.has_pileup_out = true;
                 else if (s == "-N" || s == "--max-placements") a.max_placements = (unsigned)number(need(++i), "-N", 1, DCN_PLACE_SPLIT_MAX);
                 else if (a.verify && (s == "-e" || s == "--max-edits")) a.max_edits = (unsigned)number(need(++i), "--max-edits", 0, DCN_VERIFY_MAX_EDITS);
                 else if (a.verify && s == "--max-div") a.max_div = (unsigned)number(need(++i), "--max-div", 0, 1000);
-                else if (a.verify && !a.pileup && s == "--verified-only") a.verified_only = true;
-                else if (a.pileup && s == "--min-mapq") a.min_mapq = (unsigned)number(need(++i), "--min-mapq", 0, 60);
-                else if (a.pileup && s == "--min-depth") a.min_depth = (unsigned)number(need(++i), "--min-depth", 0, 0xFFFFFFFFll);
-                else if (a.pileup && s == "--min-frac") a.min_frac = (unsigned)number(need(++i), "--min-frac", 0, 1000);
-                else if (a.pileup && s == "--sites") a.sites = need(++i), a.has_sites = true;
-                else if (a.pileup && s == "--all-ranks") a.all_ranks = true;
-                else if (a.pileup && s == "--all-positions") a.all_positions = true;
+                else if (a.verify && !a.pileup && !a.extend && s == "--verified-only") a.verified_only = true;
+                else if ((a.pileup || a.extend) && s == "--min-mapq") a.min_mapq = (unsigned)number(need(++i), "--min-mapq", 0, 60);
+                else if ((a.pileup || a.extend) && s == "--min-depth") a.min_depth = (unsigned)number(need(++i), "--min-depth", 0, 0xFFFFFFFFll);
+                else if ((a.pileup || a.extend) && s == "--min-frac") a.min_frac = (unsigned)number(need(++i), "--min-frac", 0, 1000);
+                else if ((a.pileup || a.extend) && s == "--sites") a.sites = need(++i), a.has_sites = true;
+                else if ((a.pileup || a.extend) && s == "--all-ranks") a.all_ranks = true;
+                else if ((a.pileup || a.extend) && s == "--all-positions") a.all_positions = true;
                 else if (s == "--band") a.band = (unsigned)number(need(++i), "--band", 1, 0xFFFFFFFFll);
                 else if (s == "-a" || s == "--min-votes") a.min_votes = (unsigned)number(need(++i), "--min-votes", 1, 0xFFFFFFFFll);
                 else if (s == "-p" || s == "--prefix-length") a.prefix_length = (size_t)number(need(++i), "--prefix-length", 0, 0x7FFFFFFFFFFFFFFFll);

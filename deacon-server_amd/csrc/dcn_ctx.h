@@ -17,6 +17,8 @@
 struct dcn_split_round; // (dcn_place.h)
 struct dcn_verify_item; // (dcn_verify.h)
 struct dcn_align_work;  // (dcn_verify.h)
+struct dcn_extend_item;   // (dcn_verify.h)
+struct dcn_extend_result; // (dcn_verify.h)
 
 // One pipeline step of a host batch: reads [r0, r1) = units [u0, u1) = bases [b0, b1) of the batch stream.
 // groups [g0, g1) of the invalid-base mask that crossed the link as their non-zero words only: n (group, word) pairs at
@@ -191,6 +193,10 @@ struct dcn_ctx {
     uint64_t *d_aln_offsets = nullptr;
     unsigned long long *d_aln_block_sums = nullptr;
     uint64_t aln_work_cap = 0, aln_rows_cap = 0, aln_offsets_cap = 0, aln_trace_cap = 0, aln_slots_cap = 0, aln_cigar_cap = 0;
+    // extend buffers (lazy, first dcn_extend_batch; dcn_verify.h): two items and two results per row, grown to the largest n_rows
+    dcn_extend_item *d_ext_items = nullptr;
+    dcn_extend_result *d_ext_out = nullptr;
+    uint64_t ext_cap = 0;
     // deferred state of the last enqueued device-API batch
     bool batch_pending = false;
     bool lean = false; // a small host batch is being submitted: copies and result copies go on `stream` itself (submit_impl)

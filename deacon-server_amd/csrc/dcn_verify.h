@@ -1,7 +1,7 @@
 // dcn_verify.h -- kept reference bases of an anchor map, the verify kernel's arguments, the host side that verify and
-// align share, the align kernels' arguments, the host side that align and pileup share, and the pileup kernels' arguments
-// (internal; verify.hip, verify_api.hip, align.hip, align_api.hip, pileup.hip, pileup_api.hip, and place_api.hip for the
-// append of dcn_anchor_map_add).
+// align share, the align kernels' arguments, the host side that align and pileup share, the pileup kernels' arguments and
+// the extend kernel's (internal; verify.hip, verify_api.hip, align.hip, align_api.hip, pileup.hip, pileup_api.hip,
+// extend.hip, extend_api.hip, and place_api.hip for the append of dcn_anchor_map_add).
 #pragma once
 
 #include "dcn_internal.h"
@@ -139,3 +139,32 @@ struct dcn_pileup_call_args {
 };
 uint32_t dcn_pileup_call_blocks(uint64_t n); // workgroups of a range of n positions
 int dcn_launch_pileup_call(const dcn_pileup_call_args &args, bool write, hipStream_t stream);
+
+// ---- extended placements (extend.hip, extend_api.hip; the shared arithmetic is in dcn_extend.h) ----------------------
+// One flank of one row as the kernel takes it: item 2 r is the left flank of row r, item 2 r + 1 its right flank.  The
+// host has checked the row and resolved both sequences of the flank to stream positions, as dcn_verify_item has them.
+struct dcn_extend_item {
+    int64_t u_origin; // U in the batch stream: its first base, or the end of its bases when it is read backwards
+    int64_t v_origin; // V in the store, likewise
+    uint32_t f, g;    // |U|, |V|
+    uint32_t cap;     // dcn_ext_cap: the last score of the wavefront
+    uint32_t flags;   // bit 0: U is read backwards; bit 1: V is; bit 2: the row is unplaced (nothing else is read)
+};
+static_assert(sizeof(dcn_extend_item) == 32, "extend item");
+
+// what the kernel leaves per flank: rule X5's (i*, j*, D*)
+struct dcn_extend_result {
+    uint32_t i, j, d, reserved;
+};
+static_assert(sizeof(dcn_extend_result) == 16, "extend result");
+
+struct dcn_extend_args {
+    const dcn_extend_item *items;
+    uint64_t n_items;
+    const uint32_t *s_packed, *s_invmask; // the batch: views behind DCN_FRONT_PAD
+    const uint32_t *t_packed, *t_invmask; // the store
+    uint32_t lds_stride;                  // words of one wavefront array: >= 2 * (the largest cap of the call) + 1
+    uint32_t penalty, end_bonus;
+    dcn_extend_result *out;
+};
+int dcn_launch_extend(const dcn_extend_args &args, hipStream_t stream);

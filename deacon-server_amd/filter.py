@@ -670,6 +670,9 @@ SPLIT_PLACEMENT_DTYPE = np.dtype(PLACEMENT_DTYPE.descr + [("rank", np.uint32), (
 PAIR_PLACEMENT_DTYPE = np.dtype(SPLIT_PLACEMENT_DTYPE.descr + [("flags", np.uint32), ("pair_votes", np.uint32),
                                                                ("tlen", np.int64)])
 PAIR_PROPER, PAIR_RESCUED, PAIR_MATE_PLACED = 1, 2, 4  # DCN_PAIR_*: bits of `flags`
+# numpy view of dcn_extension (32 bytes): the four coordinates of an extended row and the edits of its two flanks
+EXTENSION_DTYPE = np.dtype([("read_start", np.uint32), ("read_end", np.uint32), ("ref_start", np.uint64), ("ref_end", np.uint64),
+                            ("left_edits", np.uint32), ("right_edits", np.uint32)])
 VERIFY_OVER, VERIFY_UNPLACED = N.VERIFY_OVER, N.VERIFY_UNPLACED  # DCN_VERIFY_*: what `edits` holds instead of a distance
 # DCN_PILEUP_*: the columns of AnchorMap.pileup_fetch, the flags of a site's info and the code of no call
 PILEUP_A, PILEUP_C, PILEUP_G, PILEUP_T, PILEUP_N, PILEUP_DEL, PILEUP_INS, PILEUP_REV = (
@@ -962,6 +965,31 @@ class Placer(_Context):
                                          C.byref(p), _ptr(row_offsets), _ptr(rows) if n_rows else None, n_rows, _ptr(edits),
                                          C.byref(n_added)))
         return edits[:n_rows], int(n_added.value)
+
+    def extend_batch(self, bases, offsets, rows, row_offsets=None, penalty=6, end_bonus=4, max_edits=1023):
+        """Each placement carried over the two flanks of its read, the bases outside its outermost anchor hits
+        (dcn_extend_batch; the definition of an extended placement is in include/deacon_hip.h): on either side the end
+        that maximises read bases + record bases - penalty * edits, with end_bonus added for reaching the read's end and
+        at most max_edits edits; what is left of the read is the soft clip.  rows, row_offsets: as for verify_batch.
+        penalty = 6, end_bonus = 4 and max_edits = 1023 are conventions, not measured optima.
+        -> (rows_extended, extension): a copy of `rows`, of the same dtype, with read_start, read_end, ref_start and
+        ref_end replaced -- what verify_batch, align_batch and pileup_batch take next -- and EXTENSION_DTYPE[n_rows] with
+        the same four and the edits of the left and the right flank, in the record's direction.  An unplaced row comes
+        back as it was.  profile(): pack in its slot, the extend kernel in 'finish'."""
+        bases, offsets, n_reads = _batch(bases, offsets)
+        rows = np.ascontiguousarray(rows)
+        n_rows = len(rows)
+        if row_offsets is not None:
+            row_offsets = np.ascontiguousarray(row_offsets, dtype=np.uint64)
+        ext = np.zeros(max(n_rows, 1), EXTENSION_DTYPE)
+        p = N.ExtendParams(int(penalty), int(end_bonus), int(max_edits), rows.dtype.itemsize, (C.c_uint32 * 2)(0, 0))
+        N.check(N.lib().dcn_extend_batch(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None, _ptr(offsets), n_reads,
+                                         C.byref(p), _ptr(row_offsets), _ptr(rows) if n_rows else None, n_rows, _ptr(ext)))
+        ext = ext[:n_rows]
+        rows_extended = rows.copy()
+        for name in ("read_start", "read_end", "ref_start", "ref_end"):
+            rows_extended[name] = ext[name]
+        return rows_extended, ext
 
     def place_pairs(self, reads1, reads2, **kw):
         """the mates of two lists, interleaved -> place_pair_batch's result"""

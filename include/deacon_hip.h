@@ -78,9 +78,10 @@ enum {
  * 1.12 = dcn_ctx_last_batch_short.
  * 1.13 = dcn_anchor_map_keep_bases / _fetch, dcn_verify_batch.
  * 1.14 = dcn_align_batch.
- * 1.15 = dcn_anchor_map_pileup_* / dcn_pileup_batch. */
+ * 1.15 = dcn_anchor_map_pileup_* / dcn_pileup_batch.
+ * 1.16 = dcn_extend_batch. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 15
+#define DCN_ABI_MINOR 16
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -1015,6 +1016,70 @@ int dcn_anchor_map_pileup_fetch(const dcn_index *map, uint32_t record, uint64_t 
  * Blocking; one thread per position, a scan of the per-workgroup site counts, and a second pass that writes the sites. */
 int dcn_anchor_map_pileup_call(const dcn_index *map, const void *params, uint32_t record, uint64_t start, uint64_t n_bases,
                                uint8_t *calls, uint64_t *site_pos, uint32_t *site_info, uint64_t capacity, uint64_t *n_sites);
+
+/* ---- extended placements: each placement carried over the read's flanks, with soft clips (ABI 1.16) -------------------
+ * (no reference counterpart.)  A placement's two intervals begin and end on the k-mer of an anchor hit: the read's bases
+ * outside the outermost hits are never compared with the reference by the calls above.  dcn_extend_batch grows the
+ * interval pair of each row over both flanks as far as the bases support it; what is left of the read is the soft clip.
+ * The result is again a row that dcn_verify_batch, dcn_align_batch and dcn_pileup_batch accept as they are.
+ *
+ * THE DEFINITION OF AN EXTENDED PLACEMENT.  Rules 1-2 of a verified placement stand: S, T, EQUAL, and an invalid base
+ * equals nothing.  For a row with record != UINT32_MAX:
+ *   X1. Orientation.  L is the read's length.  R' is the read as given, or its reverse complement when the row says
+ *       reverse.  S = R'[a, b): forward (a, b) = (read_start, read_end); reverse (a, b) = (L - read_end, L - read_start).
+ *       T = record[ref_start, ref_end).  Lr is the record's length.
+ *   X2. The two flanks are treated separately and identically.  Right: U = R'[b, L), V = record[ref_end, Lr).  Left: U is
+ *       R'[0, a) read backwards, V is record[0, ref_start) read backwards.  f = |U|, g = |V|; either may be 0.  A flank
+ *       never reaches into another read of the batch or into another record of the map.
+ *   X3. D[i][j] is the Levenshtein distance of U[0, i) and V[0, j) at unit costs, under rule 2's equality.
+ *   X4. A cell (i, j) with 0 <= i <= f, 0 <= j <= g and D[i][j] <= max_edits is a candidate.  Its value is
+ *       i + j - penalty * D[i][j], plus end_bonus when i = f.  Arithmetic is 64-bit and signed.  (0, 0) is always a
+ *       candidate.
+ *   X5. The flank's extension is the candidate of largest value; among equals the one with the smaller D, then the one
+ *       with the larger i.  This is unique.  Call it (i*, j*, D*).
+ *   X6. The extended row: S' = R'[a - i_left, b + i_right), T' = record[ref_start - j_left, ref_end + j_right).  Mapped
+ *       back to the read as given: forward read_start' = read_start - i_left, read_end' = read_end + i_right; reverse
+ *       read_start' = read_start - i_right, read_end' = read_end + i_left.  left and right are in the record's
+ *       direction, as rule A5 has the ops.  The soft clips are what remains: a - i_left bases of R' in front and
+ *       L - b - i_right behind.
+ *   X7. A row with record == UINT32_MAX comes back with its four coordinates as given and both edit counts 0.
+ *   X8. Integers only.  Nothing depends on lanes, LDS sizes, a band, an early stop or how a batch is cut.
+ * Consequences, which a kernel may use (they are not rules).  With penalty >= 2 a winning cell has j - i <= D and
+ * D <= (2 f + end_bonus) / (penalty - 1).  For a fixed cost s and diagonal k = j - i the best cell is the furthest-reaching
+ * one, F_s[k], of the verify kernel's wavefront: so the answer is the maximum of 2 F_s[k] + k - penalty * s over the
+ * wavefronts, plus the bonus where F_s[k] = f, ties going first to the smaller s, then to the larger F.  The loop may stop
+ * at score s once 2 f + end_bonus - (penalty - 1) (s + 1) <= the best value so far.  A flank that matches to its end is
+ * finished at s = 0.
+ * penalty = 6, end_bonus = 4 and max_edits = 1023 are the conventions of the layers above, not measured optima. */
+typedef struct dcn_extend_params {
+    uint32_t penalty;     /* 2 .. 255 */
+    uint32_t end_bonus;   /* 0 .. 65535 */
+    uint32_t max_edits;   /* 0 .. DCN_VERIFY_MAX_EDITS */
+    uint32_t row_stride;  /* as in dcn_verify_params */
+    uint32_t reserved[2]; /* must be 0 */
+} dcn_extend_params;      /* 24 bytes */
+
+typedef struct dcn_extension {
+    uint32_t read_start, read_end;    /* of the read as given */
+    uint64_t ref_start, ref_end;
+    uint32_t left_edits, right_edits; /* D* of each flank */
+} dcn_extension;                      /* 32 bytes */
+
+/*   ctx .. n_rows   as for dcn_verify_batch, with a dcn_extend_params: the same checks of row_offsets and of every placed
+ *                   row, in the same order, with the same messages and row numbers
+ *   out             n_rows dcn_extension (declared void * for the reason given at dcn_locate_batch)
+ * DCN_ERR_ARG, before any device work: what dcn_verify_batch lists, with penalty outside 2 .. 255 and end_bonus above
+ * 65535 in place of max_permille, and out is NULL -- which, unlike dcn_verify_batch's edits, is looked at after the rows, so a
+ * bad row is named first.  Host pointers, blocking, batch limits as for dcn_place_batch; refused
+ * while batches are in flight; the six counters of the context are left unchanged.  The rows are not written: a caller
+ * copies the four coordinates of `out` into its rows and hands those to dcn_verify_batch, dcn_align_batch or
+ * dcn_pileup_batch.  The batch is staged and packed again (no plan, no scan), so the call may follow any call on the same
+ * context.  The host resolves each placed row to two flanks; the kernel runs the wavefront of the verify kernel on each,
+ * 16 lanes per flank, and tracks the best candidate.  Device memory, freed with the context: 96 bytes per row of the
+ * largest call.  dcn_ctx_set_profiling covers it: pack in its slot, the extend kernel in FINISH; plan, scan and DISTINCT
+ * are empty. */
+int dcn_extend_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                     const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, void *out);
 
 /* ---- counters: ProcessingStats (src/local_filter.rs:179-187, merged at :388-396) -------------------------- */
 
