@@ -3,10 +3,12 @@ kernel's verdict (plan.hip), against the CPU oracle: keep, hits, total and the s
 expects that path asserts through FilterProcessor.last_batch_short() that the batch took it, every test that expects the
 classic path that it did not.  The batches and what they contain: tests/_short_fused_cases.py.
 
-Every batch here has a few thousand reads, below the 2^19 at which the plan kernel switches from planning blocks of 256
-reads to blocks of 2,048: the tile layout of the large blocks (ranges of 2,048 tiles, whole waves) is covered on this path
-only by bench.py's oracle checks of the 10 M-read headline batch.  last_batch_short() reports batches of the
-device-pointer API, which is what every test here uses."""
+The short path has no planning blocks: the plan kernel returns at once for a batch the shape kernel declared short, and read
+r is lane r % 64 of workgroup r // 64 of the scan kernel, whatever the batch's size.  The batches here have a few thousand
+reads.  The cases module still speaks of planning blocks of 256 reads: that is how the classic path lays out the same
+batches when test 6 switches the short path off (blocks of 2,048 reads from 2^19 reads on, which only bench.py's oracle
+checks of the 10 M-read headline batch reach).  last_batch_short() reports batches of the device-pointer API, which is what
+every test here uses."""
 import numpy as np
 import pytest
 
@@ -40,14 +42,21 @@ def make_proc(dcn, gidx, **kw):
 
 
 class DeviceBatch:
-    """a batch in device memory, its bases `shift` bytes into their allocation"""
+    """a batch in device memory, its bases `shift` bytes into their allocation.  outside = (front, back): what the `shift`
+    bytes in front of the stream and the 64 bytes behind it hold instead of zeros"""
 
-    def __init__(self, oracle, reads, unit_id=None, shift=0, counts=True):
+    def __init__(self, oracle, reads, unit_id=None, shift=0, counts=True, outside=None):
         self.reads, self.unit_id = reads, unit_id
         self.b, self.o = oracle.concat_reads(reads)
         dev = torch.device("cuda:0")
         self.buf = torch.zeros(len(self.b) + shift + 64, dtype=torch.uint8, device=dev)
         self.buf[shift:shift + len(self.b)] = torch.from_numpy(self.b).to(dev)
+        if outside is not None:
+            front, back = outside
+            assert len(front) == shift and len(back) == 64
+            around = np.frombuffer(bytes(front) + bytes(back), dtype=np.uint8).copy()
+            self.buf[:shift] = torch.from_numpy(around[:shift]).to(dev)
+            self.buf[shift + len(self.b):] = torch.from_numpy(around[shift:]).to(dev)
         self.d_b = self.buf[shift:]
         assert self.d_b.data_ptr() % 16 == shift % 16
         self.d_o = torch.from_numpy(self.o.view(np.int64)).to(dev)
@@ -81,10 +90,10 @@ class DeviceBatch:
         return want
 
 
-def run_one(oracle, dcn, oidx, gidx, reads, short, unit_id=None, shift=0, **kw):
+def run_one(oracle, dcn, oidx, gidx, reads, short, unit_id=None, shift=0, outside=None, **kw):
     """one batch on a fresh processor: results and counters against the oracle, and the path it took"""
     proc = make_proc(dcn, gidx, **kw)
-    batch = DeviceBatch(oracle, reads, unit_id, shift)
+    batch = DeviceBatch(oracle, reads, unit_id, shift, outside=outside)
     batch.enqueue(proc)
     proc.synchronize()
     assert proc.last_batch_short() is short
