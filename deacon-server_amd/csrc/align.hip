@@ -1,6 +1,6 @@
 // align.hip -- the alignment of a verified placement (THE DEFINITION OF AN ALIGNED PLACEMENT, include/deacon_hip.h).
-//   align_kernel         one wave per aligned row.  The wavefront of verify.hip once more, with E = the row's distance d
-//                        (known from verify_kernel), prev / cur in LDS as there; every wavefront is also stored to the
+//   align_kernel         one wave per aligned row.  The wavefront of dcn_wavefront.h (dcn_wf_diagonal, the plain load) with
+//                        E = the row's distance d (known from verify_kernel), prev / cur in LDS; every wavefront is also stored to the
 //                        row's trace in global memory (dcn_align.h: F_s[k] at s * s + k + s, (d + 1)^2 words).  Behind a
 //                        fence lane 0 walks back over the trace (dcn_aln_traceback, d dependent steps, no base read) and
 //                        writes the runs from the end of the row's slot downwards, then the row's n_ops.
@@ -9,14 +9,11 @@
 // trace by E instead of d.  Integers only; nothing depends on lanes, the LDS size or the groups the host cuts.
 #include "dcn_align.h"
 #include "dcn_verify.h"
-#include "dcn_verify_words.h"
+#include "dcn_wavefront.h"
 
 #include <algorithm>
 
 namespace {
-
-__device__ inline int64_t imin(int64_t a, int64_t b) { return a < b ? a : b; }
-__device__ inline int64_t imax(int64_t a, int64_t b) { return a > b ? a : b; }
 
 __global__ __launch_bounds__(64) void align_kernel(dcn_align_args a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -29,34 +26,20 @@ __global__ __launch_bounds__(64) void align_kernel(dcn_align_args a) {
         // (every condition down to the lanes' own diagonals is the same for the whole wave: the barriers are met by all)
         bool reached = E == 0; // (d = 0: the alignment is m '=', no wavefront is read)
         if (E > 0 && 2 * E + 1 <= (int64_t)a.lds_stride) {
-            const dcn_vfy_side S = {a.s_packed, a.s_invmask, it.s_origin, it.flags & 1u};
-            const dcn_vfy_side T = {a.t_packed, a.t_invmask, it.t_origin, 0u};
+            const dcn_wf_side S = {a.s_packed, a.s_invmask, it.s_origin, it.flags & 1u};
+            const dcn_wf_side T = {a.t_packed, a.t_invmask, it.t_origin, 0u};
             uint32_t *prev = lds, *cur = lds + a.lds_stride;
             __syncthreads(); // the row before this one has been read to its end
             for (int64_t s = 0; s <= E; ++s) {
-                const int64_t lo = imax(-s, -m), hi = imin(s, n);
-                const int64_t plo = imax(1 - s, -m), phi = imin(s - 1, n); // the diagonals of score s - 1
+                const int64_t lo = dcn_wf_max(-s, -m), hi = dcn_wf_min(s, n);
                 bool found = false;
                 for (int64_t k0 = lo; k0 <= hi; k0 += 64) {
                     const int64_t k = k0 + lane;
                     if (k > hi) continue;
-                    int64_t i = 0;
-                    if (s > 0) {
-                        i = -1;
-                        if (k >= plo && k <= phi) i = (int64_t)prev[k + E] + 1;
-                        if (k - 1 >= plo && k - 1 <= phi) i = imax(i, (int64_t)prev[k - 1 + E]);
-                        if (k + 1 >= plo && k + 1 <= phi) i = imax(i, (int64_t)prev[k + 1 + E] + 1);
-                        i = imin(i, imin(m, n - k));
-                    }
-                    const int64_t j = i + k;
-                    if (i >= 0 && j >= 0) { // (always: verify.hip says why)
-                        const int64_t room = imin(m - i, n - j);
-                        if (room > 0) i += (int64_t)dcn_vfy_match_run(S, i, T, j, (uint64_t)room);
-                    }
-                    const uint32_t f = (uint32_t)imax(i, (int64_t)0);
+                    const uint32_t f = (uint32_t)dcn_wf_diagonal<dcn_wf_plain>(prev, E, s, k, m, n, S, T);
                     cur[k + E] = f;
                     trace[dcn_aln_trace_at(s, k)] = f; // (-s <= k <= s: within the (d + 1)^2 words)
-                    if (k == k_end && i >= m) found = true;
+                    if (k == k_end && f >= it.m) found = true;
                 }
                 if (__any(found)) {
                     reached = s == E; // (the distance is d: verify_kernel found it by the same wavefront)
@@ -92,10 +75,8 @@ __global__ __launch_bounds__(GATHER_THREADS) void align_gather_kernel(dcn_align_
 
 int dcn_launch_align(const dcn_align_args &args, hipStream_t stream) {
     if (args.w1 <= args.w0) return DCN_OK;
-    const size_t lds_bytes = ((size_t)args.lds_stride * 2 * sizeof(uint32_t) + 15) / 16 * 16;
-    const uint64_t resident = (uint64_t)dcn_cu_count() * 32; // one-wave workgroups: at most 32 per CU
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(args.w1 - args.w0, resident * 4);
-    hipLaunchKernelGGL(align_kernel, dim3(blocks), dim3(64), lds_bytes, stream, args);
+    const dcn_wave_grid g = dcn_wave_grid_for(args.w1 - args.w0, 2, args.lds_stride);
+    hipLaunchKernelGGL(align_kernel, dim3(g.blocks), dim3(64), g.lds_bytes, stream, args);
     DCN_HIP(hipGetLastError());
     return DCN_OK;
 }

@@ -21,18 +21,6 @@ uint64_t trace_budget_words() {
     const uint64_t bytes = s && *s ? std::strtoull(s, nullptr, 10) : DCN_ALIGN_TRACE_DEFAULT;
     return bytes / sizeof(uint32_t);
 }
-
-// a device buffer of the context that only grows
-template <typename T>
-int grow(T **p, uint64_t *cap, uint64_t need, const char *what) {
-    if (need <= *cap && *p) return DCN_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    DCN_TRY(dev_alloc(p, need, what));
-    *cap = need;
-    return DCN_OK;
-}
 } // namespace
 
 int dcn_align_check_rows(const dcn_verify_plan &plan) {

@@ -1,6 +1,6 @@
 // dcn_align.h -- the trace of the align kernel (align.hip) and the walk back over it (THE DEFINITION OF AN ALIGNED
 // PLACEMENT, include/deacon_hip.h).  Plain integer arithmetic over a trace pointer: compiles for the host as well
-// (tests/cpp/align_trace_test.cpp), as dcn_verify_words.h does.
+// (tests/cpp/align_trace_test.cpp), as dcn_wavefront.h does.
 //   The trace of one row holds every wavefront of its edit distance d, triangular, without padding: F_s[k], the furthest
 // base of S that a path of cost <= s reaches on diagonal k = j - i, is trace[s * s + (k + s)], s = 0 .. d, k = -s .. +s:
 // (d + 1)^2 words.  A diagonal outside [max(-s, -m), min(s, n)] is neither written nor read.
@@ -12,28 +12,21 @@
 
 #include <stdint.h>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define DCN_ALN_FN __host__ __device__ inline
-#else
-#define DCN_ALN_FN inline
-#endif
+#include "dcn_wavefront.h"
 
 // BAM's codes of the four ops; a run is len << 4 | op
 constexpr uint32_t DCN_ALN_I = 1, DCN_ALN_D = 2, DCN_ALN_EQ = 7, DCN_ALN_X = 8;
 
 // words of a row's trace, and the most runs its alignment can have (between two edits at most one run of '=')
-DCN_ALN_FN uint64_t dcn_aln_trace_words(uint64_t d) { return (d + 1) * (d + 1); }
-DCN_ALN_FN uint64_t dcn_aln_ops_bound(uint64_t d) { return 2 * d + 1; }
-
-DCN_ALN_FN int64_t dcn_aln_min(int64_t a, int64_t b) { return a < b ? a : b; }
-DCN_ALN_FN int64_t dcn_aln_max(int64_t a, int64_t b) { return a > b ? a : b; }
+DCN_WF_FN uint64_t dcn_aln_trace_words(uint64_t d) { return (d + 1) * (d + 1); }
+DCN_WF_FN uint64_t dcn_aln_ops_bound(uint64_t d) { return 2 * d + 1; }
 
 // where F_s[k] lies in a row's trace
-DCN_ALN_FN uint64_t dcn_aln_trace_at(int64_t s, int64_t k) { return (uint64_t)(s * s + k + s); }
+DCN_WF_FN uint64_t dcn_aln_trace_at(int64_t s, int64_t k) { return (uint64_t)(s * s + k + s); }
 
 // One word of a trace.  On the device the wave that walks has written the trace itself, through the cache of its compute
 // unit's neighbours as well: the load is an agent-scope one, which no stale line can answer.
-DCN_ALN_FN int64_t dcn_aln_trace_load(const uint32_t *p) {
+DCN_WF_FN int64_t dcn_aln_trace_load(const uint32_t *p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return (int64_t)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #else
@@ -42,8 +35,8 @@ DCN_ALN_FN int64_t dcn_aln_trace_load(const uint32_t *p) {
 }
 
 // F_s[k], or -1 for a diagonal that score s does not have
-DCN_ALN_FN int64_t dcn_aln_trace_get(const uint32_t *trace, int64_t s, int64_t k, int64_t m, int64_t n) {
-    if (k < dcn_aln_max(-s, -m) || k > dcn_aln_min(s, n)) return -1;
+DCN_WF_FN int64_t dcn_aln_trace_get(const uint32_t *trace, int64_t s, int64_t k, int64_t m, int64_t n) {
+    if (k < dcn_wf_max(-s, -m) || k > dcn_wf_min(s, n)) return -1;
     return dcn_aln_trace_load(trace + dcn_aln_trace_at(s, k));
 }
 
@@ -53,11 +46,11 @@ struct dcn_aln_writer {
     uint32_t *at; // the next run goes to at[-1]
     uint32_t op, len;
 };
-DCN_ALN_FN void dcn_aln_flush(dcn_aln_writer &w) {
+DCN_WF_FN void dcn_aln_flush(dcn_aln_writer &w) {
     if (w.len) *--w.at = (w.len << 4) | w.op;
     w.len = 0;
 }
-DCN_ALN_FN void dcn_aln_emit(dcn_aln_writer &w, uint32_t op, uint32_t len) {
+DCN_WF_FN void dcn_aln_emit(dcn_aln_writer &w, uint32_t op, uint32_t len) {
     if (len == 0) return;
     if (op != w.op) dcn_aln_flush(w), w.op = op;
     w.len += len;
@@ -65,14 +58,14 @@ DCN_ALN_FN void dcn_aln_emit(dcn_aln_writer &w, uint32_t op, uint32_t len) {
 
 // The walk of rule A3 from (m, n) at cost d back to (0, 0): d steps.  The runs end at slot_end[-1]; -> their number,
 // at most 2 d + 1 (the caller's slot holds that many).  m, n < 2^28.
-DCN_ALN_FN uint32_t dcn_aln_traceback(const uint32_t *trace, int64_t m, int64_t n, int64_t d, uint32_t *slot_end) {
+DCN_WF_FN uint32_t dcn_aln_traceback(const uint32_t *trace, int64_t m, int64_t n, int64_t d, uint32_t *slot_end) {
     dcn_aln_writer w = {slot_end, DCN_ALN_EQ, 0};
     int64_t k = n - m, i = m;
     for (int64_t s = d; s > 0; --s) {
         // the furthest cell of this diagonal that each edit reaches from cost s - 1 (-1: from a diagonal that is not there)
         const int64_t fX = dcn_aln_trace_get(trace, s - 1, k, m, n), fI = dcn_aln_trace_get(trace, s - 1, k + 1, m, n);
         const int64_t vX = fX < 0 ? -1 : fX + 1, vI = fI < 0 ? -1 : fI + 1, vD = dcn_aln_trace_get(trace, s - 1, k - 1, m, n);
-        const int64_t e = dcn_aln_max(vX, dcn_aln_max(vI, vD));
+        const int64_t e = dcn_wf_max(vX, dcn_wf_max(vI, vD));
         if (i > e) { // EQUAL pairs down to the first cell an edit reaches: no cell between has an edit predecessor
             dcn_aln_emit(w, DCN_ALN_EQ, (uint32_t)(i - e));
             i = e;

@@ -184,7 +184,7 @@ struct dcn_ctx {
     // verify buffers (lazy, first dcn_verify_batch; dcn_verify.h): one item and one result per row, grown to the largest n_rows
     dcn_verify_item *d_vfy_items = nullptr;
     uint32_t *d_vfy_out = nullptr;
-    uint64_t vfy_cap = 0;
+    uint64_t vfy_items_cap = 0, vfy_out_cap = 0;
     // align buffers (lazy, first dcn_align_batch; each grows to the largest call's need): the aligned rows, per row the
     // number of runs and their CSR offsets with the scan's scratch, the trace of one group of rows (words; at most the
     // budget of DCN_ALIGN_TRACE_BYTES, or one row's trace when that is larger), the run slots and the compact runs
@@ -196,7 +196,7 @@ struct dcn_ctx {
     // extend buffers (lazy, first dcn_extend_batch; dcn_verify.h): two items and two results per row, grown to the largest n_rows
     dcn_extend_item *d_ext_items = nullptr;
     dcn_extend_result *d_ext_out = nullptr;
-    uint64_t ext_cap = 0;
+    uint64_t ext_items_cap = 0, ext_out_cap = 0;
     // deferred state of the last enqueued device-API batch
     bool batch_pending = false;
     bool lean = false; // a small host batch is being submitted: copies and result copies go on `stream` itself (submit_impl)
@@ -240,6 +240,18 @@ int dev_alloc(T **p, uint64_t count, const char *what) {
         *p = nullptr;
         return dcn_fail(DCN_ERR_NOMEM, std::string("hipMalloc ") + what + ": " + hipGetErrorString(e));
     }
+    return DCN_OK;
+}
+
+// a device buffer of a context that only grows: at least `need` T behind *p, *cap of them
+template <typename T>
+int grow(T **p, uint64_t *cap, uint64_t need, const char *what) {
+    if (need <= *cap && *p) return DCN_OK;
+    if (*p) hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    DCN_TRY(dev_alloc(p, need, what));
+    *cap = need;
     return DCN_OK;
 }
 

@@ -1,18 +1,19 @@
-// dcn_verify.h -- kept reference bases of an anchor map, the verify kernel's arguments, the host side that verify and
-// align share, the align kernels' arguments, the host side that align and pileup share, the pileup kernels' arguments and
+// dcn_verify.h -- kept reference bases of an anchor map, the launch shape of the wavefront kernels, the verify kernel's
+// arguments, the host side that every row call shares (checks, walk, front end), the align kernels' arguments, the host side that align and pileup share, the pileup kernels' arguments and
 // the extend kernel's (internal; verify.hip, verify_api.hip, align.hip, align_api.hip, pileup.hip, pileup_api.hip,
 // extend.hip, extend_api.hip, and place_api.hip for the append of dcn_anchor_map_add).
 #pragma once
 
 #include "dcn_internal.h"
 
+#include <cstring>
 #include <vector>
 
 // The bases of every record added to a map after dcn_anchor_map_keep_bases, as the pack kernel leaves them: one 2-bit
 // stream and one invalid-base bit per base (0.375 B per base).  Every add call starts at a 32-base-aligned offset of the
 // store, so its append is two device-to-device copies of whole words; record R starts at rec_start[R] = that offset +
 // offsets[r] of its call, anywhere within a word.  cap and used are bases, multiples of 32; both arrays end in
-// DCN_STORE_PAD_WORDS readable words (dcn_verify_words.h reads one word past a base).
+// DCN_STORE_PAD_WORDS readable words (dcn_wavefront.h reads one word past a base).
 constexpr uint64_t DCN_STORE_PAD_WORDS = 8;
 constexpr uint64_t DCN_STORE_INITIAL_BASES = 1ull << 24;
 struct dcn_base_store {
@@ -28,6 +29,20 @@ void dcn_base_store_free(dcn_base_store *s);
 int dcn_base_store_append(dcn_base_store *s, const uint32_t *packed, const uint32_t *invmask, uint64_t n_bases, hipStream_t stream,
                           uint64_t *batch_start);
 void dcn_base_store_commit(dcn_base_store *s, uint64_t batch_start, const uint64_t *offsets, uint32_t n_records);
+
+// The launch of a wavefront kernel (verify.hip, align.hip, extend.hip): one-wave workgroups that stride over n work items
+// (at most 32 are resident per CU; four times that many), each with `arrays` wavefront arrays of lds_stride words of
+// dynamic LDS.
+struct dcn_wave_grid {
+    uint32_t blocks;
+    size_t lds_bytes;
+};
+#pragma GCC visibility push(hidden)
+inline dcn_wave_grid dcn_wave_grid_for(uint64_t n, uint32_t arrays, uint32_t lds_stride) {
+    const uint64_t resident = (uint64_t)dcn_cu_count() * 32;
+    return {(uint32_t)(n < resident * 4 ? n : resident * 4), ((size_t)lds_stride * arrays * sizeof(uint32_t) + 15) / 16 * 16};
+}
+#pragma GCC visibility pop
 
 // One row as the kernel takes it: the host has checked the row against the read and the record and resolved both
 // intervals to stream positions (the kernel trusts nothing the host has not checked).
@@ -50,8 +65,76 @@ struct dcn_verify_args {
 };
 int dcn_launch_verify(const dcn_verify_args &args, hipStream_t stream);
 
-// ---- the host side that dcn_verify_batch and dcn_align_batch share (verify_api.hip) ---------------------------------
-// What the walk over a call's rows leaves: one checked item per row, the largest threshold of a row that needs a
+// ---- the host side of a row call: dcn_verify_batch, dcn_align_batch, dcn_pileup_batch, dcn_extend_batch (verify_api.hip) ----
+// What every row call is given.  max_permille is rule 4's and has no say in dcn_extend_batch, which leaves it 0.
+struct dcn_row_call {
+    dcn_ctx *ctx;
+    const dcn_index *map;
+    const uint8_t *bases;
+    const uint64_t *offsets;
+    uint32_t n_reads;
+    uint32_t max_edits, max_permille, row_stride;
+    const uint64_t *row_offsets;
+    const void *rows;
+    uint64_t n_rows;
+};
+
+#pragma GCC visibility push(hidden)
+namespace dcn_impl {
+// the map is an anchor map that keeps bases
+int check_store(const dcn_index *map);
+// the range [start, start + n_bases) of a record of such a map -> its first base in the store; `who` begins the messages
+int check_range(const dcn_index *map, const char *who, uint32_t record, uint64_t start, uint64_t n_bases, uint64_t *base0);
+
+// The checks that a row call makes once, behind those of its own parameters' other fields, in the order their messages
+// promise: max_edits, max_permille, row_stride, the context, the map, the batch and row_offsets.  *run is whether there is
+// anything to walk (reads and rows; `rows` is not NULL then); *n_bases the bases of the batch.
+int rows_check(const dcn_row_call &call, bool *run, uint64_t *n_bases);
+
+// The walk over the rows of a checked call: every placed row against its read and its record, then
+// row_fn(row, placement, read_offset, read_length, record_start, record_length), which makes of the row what its kernel
+// takes.  An unplaced row (record == UINT32_MAX) is handed over unchecked, with a record of 0 bases at 0.
+template <typename RowFn>
+int rows_walk(const dcn_row_call &call, RowFn &&row_fn) {
+    const dcn_base_store *store = call.map->store;
+    uint64_t row = 0;
+    for (uint32_t r = 0; r < call.n_reads; ++r) {
+        const uint64_t row_end = call.row_offsets ? call.row_offsets[r + 1] : (uint64_t)r + 1;
+        const uint64_t read_len = call.offsets[r + 1] - call.offsets[r];
+        for (; row < row_end; ++row) {
+            dcn_placement p;
+            memcpy(&p, static_cast<const uint8_t *>(call.rows) + row * call.row_stride, sizeof(p));
+            if (p.record == UINT32_MAX) {
+                row_fn(row, p, call.offsets[r], read_len, (uint64_t)0, (uint64_t)0);
+                continue;
+            }
+            // (the message is put together only when a row is wrong: ten million rows are walked here per call)
+            const auto bad = [row](const std::string &what) { return dcn_fail(DCN_ERR_ARG, "row " + std::to_string(row) + ": " + what); };
+            if (p.record >= store->rec_len.size())
+                return bad("record " + std::to_string(p.record) + " of " + std::to_string(store->rec_len.size()) + " added");
+            if (p.reverse > 1) return bad("reverse must be 0 or 1");
+            if (p.read_start > p.read_end) return bad("read_start is behind read_end");
+            if (p.read_end > read_len)
+                return bad("read_end " + std::to_string(p.read_end) + " is past the read's " + std::to_string(read_len) + " bases");
+            if (p.ref_start > p.ref_end) return bad("ref_start is behind ref_end");
+            const uint64_t rec_len = store->rec_len[p.record];
+            if (p.ref_end > rec_len)
+                return bad("ref_end " + std::to_string(p.ref_end) + " is past the record's " + std::to_string(rec_len) + " bases");
+            row_fn(row, p, call.offsets[r], read_len, store->rec_start[p.record], rec_len);
+        }
+    }
+    return DCN_OK;
+}
+
+// The front end of a row call on the context's device: the items go to d_items, the batch is staged, the status cleared,
+// the run begun (*prof_slot_out) and the batch packed, with the marks of the four stages up to DISTINCT (no plan, no
+// scan: their slots stay empty).  The run stays open: the caller launches its kernels, marks FINISH and calls finish_run.
+int rows_front(dcn_ctx *c, void *d_items, const void *items, uint64_t item_bytes, const uint8_t *bases, uint64_t n_bases,
+               const uint64_t *offsets, uint32_t n_reads, int *prof_slot_out);
+} // namespace dcn_impl
+#pragma GCC visibility pop
+
+// What verify's walk over a call's rows leaves: one checked item per row, the largest threshold of a row that needs a
 // wavefront, and the bases of the batch.
 struct dcn_verify_plan {
     std::vector<dcn_verify_item> items;
@@ -62,7 +145,7 @@ struct dcn_verify_plan {
 int dcn_verify_walk(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
                     const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, const uint32_t *edits,
                     dcn_verify_plan *plan);
-// stage, pack, the verify kernel: the run stays open behind the DISTINCT mark (the caller marks FINISH and calls
+// rows_front and the verify kernel: the run stays open behind the DISTINCT mark (the caller marks FINISH and calls
 // finish_run), the edits are in ctx->d_vfy_out and the items in ctx->d_vfy_items
 int dcn_verify_enqueue(dcn_ctx *c, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
                        const dcn_verify_plan &plan, int *prof_slot_out);

@@ -1,7 +1,7 @@
 // extend.hip -- the extension of a placement over one flank of its read (THE DEFINITION OF AN EXTENDED PLACEMENT,
-// include/deacon_hip.h): the wavefront of verify.hip over the flank's two sequences U and V, which both begin at the
-// placement's edge, with the best candidate of rule X5 tracked over the scores.  F_s[k], the diagonals of a score, the
-// cut to the rectangle and the match runs are dcn_extend.h's, shared with the host.
+// include/deacon_hip.h): the wavefront of dcn_wavefront.h (dcn_wf_diagonal, the guarded load: the store has no word in front
+// of base 0) over the flank's two sequences U and V, which both begin at the placement's edge, with the best candidate of
+// rule X5 tracked over the scores.  Value, order, stop and cap are dcn_extend.h's, shared with the host.
 //   Shape: 16 lanes per flank, four flanks per wave, one wave per workgroup; items 4 q .. 4 q + 3 are both flanks of two
 //   consecutive rows.  Most flanks are 10-20 bases and end at score 0 or 1 with one to three diagonals, so a wave per
 //   flank would leave 61 lanes idle; 16 lanes cover every score up to 7 in one pass, and at the default penalty a flank
@@ -13,8 +13,6 @@
 //   the same best, so the stop of dcn_ext_done is uniform over the flank and the barriers are met by the whole wave.
 #include "dcn_verify.h"
 #include "dcn_extend.h"
-
-#include <algorithm>
 
 namespace {
 
@@ -36,21 +34,21 @@ __global__ __launch_bounds__(64) void extend_kernel(dcn_extend_args a) {
             if (!active && lane == 0) a.out[t] = dcn_extend_result{0u, 0u, 0u, 0u};
         }
         const int64_t f = it.f, g = it.g, cap = it.cap;
-        const dcn_vfy_side U = {a.s_packed, a.s_invmask, it.u_origin, it.flags & 1u};
-        const dcn_vfy_side V = {a.t_packed, a.t_invmask, it.v_origin, (it.flags >> 1) & 1u};
+        const dcn_wf_side U = {a.s_packed, a.s_invmask, it.u_origin, it.flags & 1u};
+        const dcn_wf_side V = {a.t_packed, a.t_invmask, it.v_origin, (it.flags >> 1) & 1u};
         uint32_t *prev = mine, *cur = mine + a.lds_stride;
         dcn_ext_best best = {INT64_MIN, 0, 0, 0};
         __syncthreads(); // the flanks before these have been read to their end
         for (int64_t s = 0;; ++s) {
             if (active) {
-                const int64_t lo = dcn_ext_max(-s, -f), hi = dcn_ext_min(s, g);
+                const int64_t lo = dcn_wf_max(-s, -f), hi = dcn_wf_min(s, g);
                 long long v_s = INT64_MIN;
                 unsigned i_s = 0;
                 int k_s = 0;
                 for (int64_t k0 = lo; k0 <= hi; k0 += FLANK_LANES) {
                     const int64_t k = k0 + lane;
                     if (k > hi) continue;
-                    const int64_t i = dcn_ext_diagonal(prev, cap, s, k, f, g, U, V);
+                    const int64_t i = dcn_wf_diagonal<dcn_wf_guarded>(prev, cap, s, k, f, g, U, V);
                     cur[k + cap] = (uint32_t)i;
                     const int64_t v = dcn_ext_value(i, k, s, f, penalty, end_bonus);
                     if (dcn_ext_better(v, i, v_s, i_s)) v_s = v, i_s = (unsigned)i, k_s = (int)k;
@@ -82,11 +80,8 @@ __global__ __launch_bounds__(64) void extend_kernel(dcn_extend_args a) {
 int dcn_launch_extend(const dcn_extend_args &args, hipStream_t stream) {
     if (args.n_items == 0) return DCN_OK;
     // two wavefront arrays per flank of the wave; 64 KB at DCN_VERIFY_MAX_EDITS, a few hundred bytes for short reads
-    const size_t lds_bytes = ((size_t)args.lds_stride * 2 * WAVE_FLANKS * sizeof(uint32_t) + 15) / 16 * 16;
-    const uint64_t waves = (args.n_items + WAVE_FLANKS - 1) / WAVE_FLANKS;
-    const uint64_t resident = (uint64_t)dcn_cu_count() * 32; // one-wave workgroups: at most 32 per CU
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(waves, resident * 4);
-    hipLaunchKernelGGL(extend_kernel, dim3(blocks), dim3(64), lds_bytes, stream, args);
+    const dcn_wave_grid g = dcn_wave_grid_for((args.n_items + WAVE_FLANKS - 1) / WAVE_FLANKS, 2 * WAVE_FLANKS, args.lds_stride);
+    hipLaunchKernelGGL(extend_kernel, dim3(g.blocks), dim3(64), g.lds_bytes, stream, args);
     DCN_HIP(hipGetLastError());
     return DCN_OK;
 }

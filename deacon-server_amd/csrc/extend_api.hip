@@ -1,6 +1,7 @@
 // extend_api.hip -- the C ABI of extended placements (dcn_extend_batch; kernel in extend.hip, the shared arithmetic in
-// dcn_extend.h).  The checks and the walk over the rows are dcn_verify_batch's own (dcn_verify_walk, verify_api.hip); a
-// second walk resolves every placed row to its two flanks, and the answers of the flanks are put together here by rule X6.
+// dcn_extend.h).  The once-only checks, the walk over the rows and the front end are every row call's (rows_check,
+// rows_walk, rows_front; dcn_verify.h): the walk resolves every placed row to its two flanks, and the answers of the
+// flanks are put together here by rule X6.
 #include "dcn_ctx.h"
 #include "dcn_extend.h"
 #include "dcn_verify.h"
@@ -39,68 +40,39 @@ extern "C" int dcn_extend_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_
     if (prm->reserved[0] != 0 || prm->reserved[1] != 0) return dcn_fail(DCN_ERR_ARG, "params.reserved must be 0");
     if (prm->penalty < 2 || prm->penalty > 255) return dcn_fail(DCN_ERR_ARG, "params.penalty must be 2..255");
     if (prm->end_bonus > 65535) return dcn_fail(DCN_ERR_ARG, "params.end_bonus must be 0..65535");
-    dcn_verify_params vprm; // (max_edits and row_stride are checked by the walk, with its messages)
-    vprm.max_edits = prm->max_edits;
-    vprm.max_permille = 0;
-    vprm.row_stride = prm->row_stride;
-    vprm.reserved = 0;
-    dcn_verify_plan plan;
-    uint32_t not_null = 0; // (the walk asks for verify's `edits`; `out` is looked at below)
-    DCN_TRY(dcn_verify_walk(ctx, map, bases, offsets, n_reads, &vprm, row_offsets, rows, n_rows, &not_null, &plan));
-    if (plan.items.empty()) return DCN_OK;
-    if (!out) return dcn_fail(DCN_ERR_ARG, "out is NULL");
+    const dcn_row_call call = {ctx, map, bases, offsets, n_reads, prm->max_edits, 0u, prm->row_stride, row_offsets, rows, n_rows};
+    bool run = false;
+    uint64_t n_bases = 0;
+    DCN_TRY(rows_check(call, &run, &n_bases));
+    if (!run) return DCN_OK;
 
     // every row is checked: two flanks of each
-    const dcn_base_store *store = map->store;
     std::vector<dcn_extend_item> items(2 * n_rows);
     uint32_t cap_max = 0;
-    {
-        uint64_t row = 0;
-        for (uint32_t r = 0; r < n_reads; ++r) {
-            const uint64_t row_end = row_offsets ? row_offsets[r + 1] : (uint64_t)r + 1;
-            const uint64_t read_len = offsets[r + 1] - offsets[r];
-            for (; row < row_end; ++row) {
-                dcn_placement p;
-                memcpy(&p, static_cast<const uint8_t *>(rows) + row * prm->row_stride, sizeof(p));
-                if (p.record == UINT32_MAX) {
-                    memset(&items[2 * row], 0, 2 * sizeof(dcn_extend_item));
-                    items[2 * row].flags = items[2 * row + 1].flags = 4u;
-                    continue;
-                }
-                for (int side = 0; side < 2; ++side) {
-                    dcn_extend_item &it = items[2 * row + side];
-                    it = flank_item(p, side == 0, offsets[r], read_len, store->rec_start[p.record], store->rec_len[p.record], *prm);
-                    cap_max = std::max(cap_max, it.cap);
-                }
-            }
+    const int rc = rows_walk(call, [&](uint64_t row, const dcn_placement &p, uint64_t read_off, uint64_t read_len, uint64_t rec_start, uint64_t rec_len) {
+        if (p.record == UINT32_MAX) {
+            memset(&items[2 * row], 0, 2 * sizeof(dcn_extend_item));
+            items[2 * row].flags = items[2 * row + 1].flags = 4u;
+            return;
         }
-    }
+        for (int side = 0; side < 2; ++side) {
+            dcn_extend_item &it = items[2 * row + side];
+            it = flank_item(p, side == 0, read_off, read_len, rec_start, rec_len, *prm);
+            cap_max = std::max(cap_max, it.cap);
+        }
+    });
+    DCN_TRY(rc);
+    if (!out) return dcn_fail(DCN_ERR_ARG, "out is NULL");
 
     dcn_ctx *c = ctx;
-    const uint64_t n_items = items.size(), n_bases = plan.n_bases;
-    DCN_HIP(hipSetDevice(c->device));
-    if (n_rows > c->ext_cap) {
-        if (c->d_ext_items) hipFree(c->d_ext_items);
-        if (c->d_ext_out) hipFree(c->d_ext_out);
-        c->d_ext_items = nullptr;
-        c->d_ext_out = nullptr;
-        c->ext_cap = 0;
-        DCN_TRY(dev_alloc(&c->d_ext_items, n_items, "extend flanks"));
-        DCN_TRY(dev_alloc(&c->d_ext_out, n_items, "extend results"));
-        c->ext_cap = n_rows;
-    }
-    DCN_TRY(staged_h2d(c, c->d_ext_items, items.data(), n_items * sizeof(dcn_extend_item)));
-    DCN_TRY(stage_batch(c, bases, n_bases, offsets, n_reads, nullptr));
+    const uint64_t n_items = items.size();
     hipStream_t st = c->stream;
-    DCN_HIP(hipMemsetAsync(c->d_status, 0, sizeof(dcn_status), st)); // (short_batch = 0: the pack kernel packs)
     int prof_slot = -1;
-    DCN_TRY(prof_begin(c, &prof_slot));
-    // the front end up to the packed stream and the invalid mask, as dcn_verify_batch runs it
-    DCN_TRY(dcn_launch_pack(c->d_ascii, 0, n_bases, c->d_packed + DCN_FRONT_PAD, c->d_invmask + DCN_FRONT_PAD, c->d_status, st));
-    DCN_PROF_MARK(DCN_STAGE_PACK);
-    DCN_PROF_MARK(DCN_STAGE_PLAN);
-    DCN_PROF_MARK(DCN_STAGE_SCAN);
-    DCN_PROF_MARK(DCN_STAGE_DISTINCT);
+    DCN_HIP(hipSetDevice(c->device));
+    DCN_TRY(grow(&c->d_ext_items, &c->ext_items_cap, n_items, "extend flanks"));
+    DCN_TRY(grow(&c->d_ext_out, &c->ext_out_cap, n_items, "extend results"));
+    DCN_TRY(rows_front(c, c->d_ext_items, items.data(), n_items * sizeof(dcn_extend_item), bases, n_bases, offsets, n_reads, &prof_slot));
+    const dcn_base_store *store = map->store;
     dcn_extend_args xa;
     memset(&xa, 0, sizeof(xa));
     xa.items = c->d_ext_items;

@@ -2,7 +2,7 @@
 // include/deacon_hip.h; what the host shares is in dcn_pileup.h).
 //   pileup_kernel        one wave per aligned row, over align's work list.  The row's runs in chunks of 64: lane r loads
 //                        run r and its steps on S and T, a wave prefix sum gives each run its (i, j); then, run by run,
-//                        the lanes stride over the run's bases, read S[i] (dcn_verify_words.h, with the strand flag) and
+//                        the lanes stride over the run's bases, read S[i] (dcn_wavefront.h, with the strand flag) and
 //                        add 1 with atomicAdd on uint32_t.  A row with n = 0 adds nothing.
 //   pileup_call_kernel   one thread per position of a range: rule P6.  <false> writes the call characters and the
 //                        workgroup's number of sites; <true>, behind the scan of those numbers, writes the sites compactly
@@ -11,7 +11,7 @@
 #include "dcn_dump_sweep.h"
 #include "dcn_pileup.h"
 #include "dcn_verify.h"
-#include "dcn_verify_words.h"
+#include "dcn_wavefront.h"
 
 #include <algorithm>
 
@@ -28,7 +28,7 @@ __global__ __launch_bounds__(PILE_THREADS) void pileup_kernel(dcn_pileup_args a)
         const uint32_t count = a.n_ops[wk.row];
         if (it.n == 0 || count == 0) continue; // (the same for the whole wave)
         const uint32_t *const runs = a.cigar + a.cigar_offsets[wk.row];
-        const dcn_vfy_side S = {a.s_packed, a.s_invmask, it.s_origin, it.flags & 1u};
+        const dcn_wf_side S = {a.s_packed, a.s_invmask, it.s_origin, it.flags & 1u};
         const uint32_t reverse = it.flags & 1u, m = it.m, n = it.n;
         const uint64_t t0 = (uint64_t)it.t_origin;
         uint32_t *const counters = a.counters;
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(PILE_THREADS) void pileup_kernel(dcn_pileup_args a)
         const auto column_of = [&](uint32_t i) {
             if (i >= m) return DCN_PILE_N; // (never: the runs cover exactly m bases of S)
             uint32_t x, inv;
-            dcn_vfy_side16(S, (int64_t)i, &x, &inv);
+            dcn_wf_side16<dcn_wf_plain>(S, (int64_t)i, &x, &inv);
             return dcn_pile_column(x & 3u, inv & 1u);
         };
         const auto add = [&](uint32_t column, uint32_t j) {

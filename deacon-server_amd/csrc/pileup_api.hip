@@ -20,29 +20,9 @@ static_assert(DCN_PILEUP_SITE_SUB == DCN_PILE_SITE_SUB && DCN_PILEUP_SITE_DEL ==
               "the site flags of the header and of dcn_pileup.h");
 
 namespace {
-int check_store(const dcn_index *map) {
-    if (!map) return dcn_fail(DCN_ERR_ARG, "map is NULL");
-    if (!map->d_anchor) return dcn_fail(DCN_ERR_ARG, "the index is not an anchor map (dcn_anchor_map_create)");
-    if (!map->store) return dcn_fail(DCN_ERR_ARG, "the map keeps no bases (dcn_anchor_map_keep_bases before the first add)");
-    return DCN_OK;
-}
-
 int check_pileup(const dcn_index *map) {
     DCN_TRY(check_store(map));
     if (!map->d_pileup) return dcn_fail(DCN_ERR_ARG, "the map has no pileup (dcn_anchor_map_pileup_enable)");
-    return DCN_OK;
-}
-
-// the range [start, start + n_bases) of a record, as dcn_anchor_map_fetch checks it -> its first base in the store
-int check_range(const dcn_index *map, const char *who, uint32_t record, uint64_t start, uint64_t n_bases, uint64_t *base0) {
-    const dcn_base_store *s = map->store;
-    if (record >= s->rec_len.size())
-        return dcn_fail(DCN_ERR_ARG, std::string(who) + ": record " + std::to_string(record) + " of " + std::to_string(s->rec_len.size()) + " added");
-    const uint64_t len = s->rec_len[record];
-    if (start > len || n_bases > len - start)
-        return dcn_fail(DCN_ERR_ARG, std::string(who) + ": bases [" + std::to_string(start) + ", " + std::to_string(start) + " + " +
-                                         std::to_string(n_bases) + ") are past the record's " + std::to_string(len) + " bases");
-    *base0 = s->rec_start[record] + start;
     return DCN_OK;
 }
 

@@ -1,9 +1,10 @@
 // align_trace_test.cpp -- the walk back of the align kernel (dcn_align.h) on the host, under the address and
-// undefined-behaviour sanitizers (tests/test_align_abi.py builds and runs it).  A host wavefront fills the triangular
-// trace exactly as align.hip lays it out -- F_s[k] at s * s + k + s, (d + 1)^2 words, diagonals outside
+// undefined-behaviour sanitizers (tests/test_align_abi.py builds and runs it).  The kernels' own wavefront step
+// (dcn_wavefront.h, the plain load) fills the triangular trace exactly as align.hip lays it out -- F_s[k] at s * s + k + s, (d + 1)^2 words, diagonals outside
 // [max(-s, -m), min(s, n)] never touched (they hold a poison value) -- dcn_aln_traceback walks it into a slot of exactly
 // 2 d + 1 runs, and every run is compared with a walk over the full table by rule A3 cell by cell.
 #include "dcn_align.h"
+#include "packed_stream.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -54,28 +55,24 @@ std::vector<uint32_t> table_walk(const std::string &S, const std::string &T, int
 
 constexpr uint32_t POISON = 0xDEADBEEFu;
 
-// the wavefront of verify.hip / align.hip, one base at a time -> the trace of exactly (d + 1)^2 words
+// the wavefront of verify.hip / align.hip (dcn_wf_diagonal of dcn_wavefront.h with the plain load, as the kernels call
+// it, over both texts packed) -> the trace of exactly (d + 1)^2 words.  The wavefront of score s - 1 is read where the
+// trace holds it: F_{s-1}[k] at trace[(s - 1)^2 + k + (s - 1)].
 std::vector<uint32_t> wavefront_trace(const std::string &S, const std::string &T, int64_t d) {
     const int64_t m = (int64_t)S.size(), n = (int64_t)T.size();
+    const PackedStream ps(S, 0, 1), pt(T, 0, 1); // (both read forwards: one word behind the last base)
+    const dcn_wf_side side_s = {ps.p(), ps.m(), 0, 0u}, side_t = {pt.p(), pt.m(), 0, 0u};
     std::vector<uint32_t> trace((size_t)dcn_aln_trace_words((uint64_t)d), POISON);
     for (int64_t s = 0; s <= d; ++s) {
-        const int64_t lo = std::max(-s, -m), hi = std::min(s, n), plo = std::max(1 - s, -m), phi = std::min(s - 1, n);
+        const int64_t lo = std::max(-s, -m), hi = std::min(s, n);
+        const uint32_t *const prev = s > 0 ? trace.data() + dcn_aln_trace_at(s - 1, 1 - s) : nullptr;
         bool found = false;
         for (int64_t k = lo; k <= hi; ++k) {
-            int64_t i = 0;
-            if (s > 0) {
-                i = -1;
-                auto prev = [&](int64_t kk) { return (int64_t)trace[(size_t)dcn_aln_trace_at(s - 1, kk)]; };
-                if (k >= plo && k <= phi) i = prev(k) + 1;
-                if (k - 1 >= plo && k - 1 <= phi) i = std::max(i, prev(k - 1));
-                if (k + 1 >= plo && k + 1 <= phi) i = std::max(i, prev(k + 1) + 1);
-                i = std::min(i, std::min(m, n - k));
-            }
-            if (i < 0 || i + k < 0) {
-                std::fprintf(stderr, "a negative position at s=%lld k=%lld\n", (long long)s, (long long)k);
+            const int64_t i = dcn_wf_diagonal<dcn_wf_plain>(prev, s - 1, s, k, m, n, side_s, side_t);
+            if (i > m || i + k > n || i + k < 0) {
+                std::fprintf(stderr, "a position outside the rectangle at s=%lld k=%lld\n", (long long)s, (long long)k);
                 std::exit(1);
             }
-            while (i < m && i + k < n && equal_bases(S[(size_t)i], T[(size_t)(i + k)])) ++i;
             trace[(size_t)dcn_aln_trace_at(s, k)] = (uint32_t)i;
             if (k == n - m && i >= m) found = true;
         }

@@ -1,12 +1,12 @@
-// The flank routine of the extend kernel (csrc/dcn_extend.h: dcn_ext_flank over dcn_ext_diagonal, dcn_ext_match_run and the
-// fetch that never reads in front of a stream) compiled for the host, against rules X3-X5 of THE DEFINITION OF AN EXTENDED
+// The flank routine of the extend kernel (csrc/dcn_extend.h: dcn_ext_flank over dcn_wavefront.h's dcn_wf_diagonal with the
+// guarded load, the fetch that never reads in front of a stream) compiled for the host, against rules X3-X5 of THE DEFINITION OF AN EXTENDED
 // PLACEMENT from a full table.  The streams are heap arrays of exactly the words the real ones have: the batch stream with
 // its pad in front and behind, the store with no word in front of base 0 and its pad words behind -- under the address
 // sanitizer a read of word -1 of the store, or past either pad, ends the program.  All four combinations of strand and
 // side; left flanks that start at store bases 0 .. 33; right flanks that end at the last base of the last record; reads
 // and records that lie side by side and continue each other's bases.  Packing is dcn_pack.h's, as on the device.
-#include "dcn_pack.h"
 #include "dcn_extend.h"
+#include "packed_stream.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -49,30 +49,6 @@ static std::string revcomp(const std::string &s) {
     return r;
 }
 static std::string reversed(const std::string &s) { return std::string(s.rbegin(), s.rend()); }
-
-// a stream as the pack kernel leaves it: `front` words in front of base 0 and `back` words behind the last 32-base group
-struct Stream {
-    std::vector<uint32_t> packed, mask;
-    size_t front;
-    Stream(const std::string &s, size_t front_words, size_t back_words) : front(front_words) {
-        const size_t groups = (s.size() + 31) / 32;
-        packed.assign(front + 2 * groups + back_words, 0);
-        mask.assign(front + groups + back_words, 0);
-        for (size_t g = 0; g < groups; ++g) {
-            for (int q = 0; q < 8; ++q) {
-                uint32_t w = 0;
-                for (int j = 0; j < 4; ++j) {
-                    const size_t i = g * 32 + 4 * q + j;
-                    w |= (uint32_t)(uint8_t)(i < s.size() ? s[i] : 'A') << (8 * j);
-                }
-                packed[front + 2 * g + q / 4] |= dcn_pack4(w) << (8 * (q % 4));
-                mask[front + g] |= dcn_invalid4(w) << (4 * q);
-            }
-        }
-    }
-    const uint32_t *p() const { return packed.data() + front; }
-    const uint32_t *m() const { return mask.data() + front; }
-};
 
 static std::string random_text(size_t n, int p_invalid) {
     std::string s(n, 'A');
@@ -156,7 +132,7 @@ int main() {
         const bool first = trial % 4 == 0, last = trial % 4 == 1;
         const std::string batch_text = (first ? std::string() : before) + read + (last ? std::string() : after);
         const uint64_t read_off = first ? 0 : before.size();
-        const Stream batch(batch_text, FRONT_PAD, TAIL_PAD), store(rec0 + rec1, 0, STORE_PAD);
+        const PackedStream batch(batch_text, FRONT_PAD, TAIL_PAD), store(rec0 + rec1, 0, STORE_PAD);
 
         const uint32_t penalty = 2 + rnd() % 8, end_bonus = rnd() % 12, max_edits = rnd() % 4 == 0 ? rnd() % 4 : 1023;
         for (int side = 0; side < 2; ++side) {
@@ -169,8 +145,8 @@ int main() {
             const bool u_back = is_left != (reverse != 0);
             const uint32_t f = (uint32_t)(u_back ? rs : L - re), g = (uint32_t)(is_left ? fs : Lr - fe);
             CHECK(f == U.size() && g == V.size(), "trial %d side %d: f %u g %u", trial, side, f, g);
-            const dcn_vfy_side Us = {batch.p(), batch.m(), (int64_t)(read_off + (u_back ? rs : re)), u_back ? 1u : 0u};
-            const dcn_vfy_side Vs = {store.p(), store.m(), (int64_t)(rec_start + (is_left ? fs : fe)), is_left ? 1u : 0u};
+            const dcn_wf_side Us = {batch.p(), batch.m(), (int64_t)(read_off + (u_back ? rs : re)), u_back ? 1u : 0u};
+            const dcn_wf_side Vs = {store.p(), store.m(), (int64_t)(rec_start + (is_left ? fs : fe)), is_left ? 1u : 0u};
             const uint32_t cap = dcn_ext_cap(f, g, penalty, end_bonus, max_edits);
             std::vector<uint32_t> wave(2 * (2 * (size_t)cap + 1)); // exactly the two arrays
             uint32_t gi = 0, gj = 0, gd = 0;

@@ -1,8 +1,8 @@
-// The word helpers of the verify kernel (csrc/dcn_verify_words.h) compiled for the host, against naive loops over ASCII:
+// The word helpers of the verify kernel (csrc/dcn_wavefront.h) compiled for the host, against naive loops over ASCII:
 // fetches at every bit offset, the reverse complement of a word, and the run of EQUAL bases from every offset 0..31 of both
 // streams, forward and reverse, with and without invalid bases.  Packing is dcn_pack.h's, as on the device.
 #include "dcn_pack.h"
-#include "dcn_verify_words.h"
+#include "dcn_wavefront.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -80,9 +80,9 @@ int main() {
         uint32_t br = 0, rc = 0;
         for (int b = 0; b < 32; ++b) br |= ((x >> b) & 1u) << (31 - b);
         for (int u = 0; u < 16; ++u) rc |= ((((x >> (2 * (15 - u))) & 3u) ^ 2u)) << (2 * u);
-        CHECK(dcn_vfy_brev32(x) == br, "%08x", x);
-        CHECK(dcn_vfy_revcomp16(x) == rc, "%08x", x);
-        CHECK(dcn_vfy_rev16(x & 0xFFFFu) == (br >> 16), "%08x", x);
+        CHECK(dcn_wf_brev32(x) == br, "%08x", x);
+        CHECK(dcn_wf_revcomp16(x) == rc, "%08x", x);
+        CHECK(dcn_wf_rev16(x & 0xFFFFu) == (br >> 16), "%08x", x);
     }
     // run16: first difference or invalid bit, whichever comes first
     for (int u = 0; u <= 16; ++u)
@@ -92,7 +92,7 @@ int main() {
             if (u < 16) xt ^= 1u << (2 * u + (rnd() & 1)); // group u differs
             if (u < 15 && (rnd() & 1)) xt ^= rnd() << (2 * u + 2); // ... and anything behind it may
             const uint32_t inv = v < 16 ? (1u << v) | ((rnd() & 0xFFFFu) << v) : 0u;
-            CHECK(dcn_vfy_run16(xs, xt, inv & 0xFFFFu) == (uint32_t)(u < v ? u : v), "u=%d v=%d", u, v);
+            CHECK(dcn_wf_run16(xs, xt, inv & 0xFFFFu) == (uint32_t)(u < v ? u : v), "u=%d v=%d", u, v);
         }
     // fetches and runs over text, at every offset 0..31 of both streams
     const int PAD = 2;
@@ -106,7 +106,7 @@ int main() {
             for (auto &c : b) c ^= (rnd() & 1) ? 0x20 : 0; // case differs at random: equal all the same
         const Stream A(a, PAD), B(b, PAD);
         for (size_t i = 0; i + 16 <= a.size(); i += 7) {
-            const uint32_t x = dcn_vfy_fetch16(A.p(), (int64_t)i), m = dcn_vfy_mask16(A.m(), (int64_t)i);
+            const uint32_t x = dcn_wf_fetch16<dcn_wf_plain>(A.p(), (int64_t)i), m = dcn_wf_mask16<dcn_wf_plain>(A.m(), (int64_t)i);
             for (int u = 0; u < 16; ++u) {
                 CHECK(((x >> (2 * u)) & 3u) == (((uint32_t)a[i + u] >> 1) & 3u), "fetch16 at %zu + %d", i, u);
                 CHECK(((m >> u) & 1u) == (valid(a[i + u]) ? 0u : 1u), "mask16 at %zu + %d", i, u);
@@ -122,8 +122,8 @@ int main() {
                     const uint64_t limit = rep == 5 ? rnd() % 40 : std::min(a.size() - i, b.size() - j);
                     uint64_t want = 0;
                     while (want < limit && equal(a[i + want], b[j + want])) ++want;
-                    const dcn_vfy_side S = {A.p(), A.m(), 0, 0u}, T = {B.p(), B.m(), 0, 0u};
-                    const uint64_t got = dcn_vfy_match_run(S, i, T, j, limit);
+                    const dcn_wf_side S = {A.p(), A.m(), 0, 0u}, T = {B.p(), B.m(), 0, 0u};
+                    const uint64_t got = dcn_wf_match_run<dcn_wf_plain>(S, i, T, j, limit);
                     CHECK(got == want, "forward variant %d i=%lld j=%lld limit=%llu: %llu, want %llu", variant, (long long)i,
                           (long long)j, (unsigned long long)limit, (unsigned long long)got, (unsigned long long)want);
                 }
@@ -139,24 +139,24 @@ int main() {
                 std::string f = std::string(to, 'G') + a.substr(so, 400);
                 for (size_t q = to + rnd() % 40; q < f.size(); q += 30 + rnd() % 50) f[q] = f[q] == 'A' ? 'C' : 'A';
                 const Stream Fs(f, PAD);
-                const dcn_vfy_side SF = {A.p(), A.m(), (int64_t)so, 0u}, TF = {Fs.p(), Fs.m(), (int64_t)to, 0u};
+                const dcn_wf_side SF = {A.p(), A.m(), (int64_t)so, 0u}, TF = {Fs.p(), Fs.m(), (int64_t)to, 0u};
                 for (int rep = 0; rep < 4; ++rep) {
                     const int64_t i = rep == 0 ? 0 : (int64_t)(rnd() % 400);
                     const uint64_t limit = 400 - i;
                     uint64_t want = 0;
                     while (want < limit && equal(a[so + i + want], f[to + i + want])) ++want;
-                    const uint64_t got = dcn_vfy_match_run(SF, i, TF, i, limit);
+                    const uint64_t got = dcn_wf_match_run<dcn_wf_plain>(SF, i, TF, i, limit);
                     CHECK(got == want, "shifted variant %d so=%d to=%d i=%lld: %llu, want %llu", variant, so, to, (long long)i,
                           (unsigned long long)got, (unsigned long long)want);
                 }
                 const Stream Cs(c, PAD);
-                const dcn_vfy_side S = {A.p(), A.m(), (int64_t)hi, 1u}, T = {Cs.p(), Cs.m(), (int64_t)to, 0u};
+                const dcn_wf_side S = {A.p(), A.m(), (int64_t)hi, 1u}, T = {Cs.p(), Cs.m(), (int64_t)to, 0u};
                 for (int rep = 0; rep < 4; ++rep) {
                     const int64_t i = rep == 0 ? 0 : (int64_t)(rnd() % (hi - lo));
                     const uint64_t limit = (hi - lo) - i;
                     uint64_t want = 0;
                     while (want < limit && equal(comp(a[hi - 1 - (i + want)]), c[to + i + want])) ++want;
-                    const uint64_t got = dcn_vfy_match_run(S, i, T, i, limit);
+                    const uint64_t got = dcn_wf_match_run<dcn_wf_plain>(S, i, T, i, limit);
                     CHECK(got == want, "reverse variant %d lo=%zu to=%d i=%lld: %llu, want %llu", variant, lo, to, (long long)i,
                           (unsigned long long)got, (unsigned long long)want);
                 }
@@ -166,16 +166,16 @@ int main() {
     {
         const std::string a = random_text(200, 0, 0);
         const Stream A(a, PAD);
-        const dcn_vfy_side S = {A.p(), A.m(), 0, 0u};
+        const dcn_wf_side S = {A.p(), A.m(), 0, 0u};
         for (uint64_t limit = 0; limit <= 40; ++limit)
-            for (int64_t i = 0; i < 33; ++i) CHECK(dcn_vfy_match_run(S, i, S, i, limit) == limit, "limit %llu", (unsigned long long)limit);
+            for (int64_t i = 0; i < 33; ++i) CHECK(dcn_wf_match_run<dcn_wf_plain>(S, i, S, i, limit) == limit, "limit %llu", (unsigned long long)limit);
         std::string n = a;
         n[37] = 'N';
         const Stream Ns(n, PAD);
-        const dcn_vfy_side SN = {Ns.p(), Ns.m(), 0, 0u};
-        CHECK(dcn_vfy_match_run(SN, 0, SN, 0, 200) == 37, "N against N");
-        CHECK(dcn_vfy_match_run(SN, 37, SN, 37, 5) == 0, "N against N at the start");
-        CHECK(dcn_vfy_match_run(SN, 38, SN, 38, 100) == 100, "behind the N");
+        const dcn_wf_side SN = {Ns.p(), Ns.m(), 0, 0u};
+        CHECK(dcn_wf_match_run<dcn_wf_plain>(SN, 0, SN, 0, 200) == 37, "N against N");
+        CHECK(dcn_wf_match_run<dcn_wf_plain>(SN, 37, SN, 37, 5) == 0, "N against N at the start");
+        CHECK(dcn_wf_match_run<dcn_wf_plain>(SN, 38, SN, 38, 100) == 100, "behind the N");
     }
     if (failures) {
         std::printf("%d failures\n", failures);

@@ -113,7 +113,7 @@ def test_align_help_text():
 
 
 def test_walk_back_on_the_host(tmp_path):
-    """tests/cpp/align_trace_test.cpp: a host wavefront that fills the triangular trace, dcn_align.h's walk back over it into
+    """tests/cpp/align_trace_test.cpp: the kernels' wavefront step (dcn_wavefront.h) fills the triangular trace, dcn_align.h's walk back over it into
     a slot of exactly 2 d + 1 runs, and a walk over the full table by rule A3, under the address and undefined-behaviour
     sanitizers: a few thousand random pairs (three alphabets, empty sides, unrelated pairs) and d = 0, 1, 31, 32, 33, 63, 64, 65"""
     exe = tmp_path / "align_trace_test"

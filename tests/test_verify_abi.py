@@ -119,12 +119,23 @@ def test_verify_help_text():
 
 
 def test_word_helpers_on_the_host(tmp_path):
-    """tests/cpp/verify_helpers_test.cpp: dcn_verify_words.h compiled for the host under the address and undefined-behaviour
+    """tests/cpp/verify_helpers_test.cpp: dcn_wavefront.h compiled for the host under the address and undefined-behaviour
     sanitizers, against naive loops: fetches, the reverse complement of a word, runs from every offset 0..31 of both streams"""
     exe = tmp_path / "verify_helpers_test"
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-fsanitize=address,undefined",
                            "-I", os.path.join(ROOT, "deacon-server_amd", "csrc"),
                            os.path.join(ROOT, "tests", "cpp", "verify_helpers_test.cpp"), "-o", str(exe)])
+    subprocess.check_call([str(exe)])
+
+
+def test_wavefront_step_on_the_host(tmp_path):
+    """tests/cpp/wavefront_test.cpp: the wavefront step that the verify, align and extend kernels share (dcn_wavefront.h)
+    compiled for the host under the address and undefined-behaviour sanitizers, driven over all scores as verify_kernel
+    drives it, every F_s[k] and the thresholded distance against a full Levenshtein table, under both word loads"""
+    exe = tmp_path / "wavefront_test"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-fsanitize=address,undefined",
+                           "-I", os.path.join(ROOT, "deacon-server_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "wavefront_test.cpp"), "-o", str(exe)])
     subprocess.check_call([str(exe)])
 
 
