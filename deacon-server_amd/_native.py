@@ -171,6 +171,29 @@ PILEUP_SITE_SUB, PILEUP_SITE_DEL, PILEUP_SITE_INS = 1, 2, 4
 PILEUP_NO_CODE = 7
 
 
+class Insertion(C.Structure):
+    _fields_ = [
+        ("pos", C.c_uint64),
+        ("bases_offset", C.c_uint64),
+        ("len", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+class InsertionAllele(C.Structure):
+    _fields_ = [
+        ("pos", C.c_uint64),
+        ("bases_offset", C.c_uint64),
+        ("len", C.c_uint32),
+        ("count", C.c_uint32),
+        ("events", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+INSERTION_FRONT, INSERTION_REVERSE = 1, 2  # DCN_INSERTION_*: the flags of an event; an allele has FRONT only
+
+
 class ExtendParams(C.Structure):
     _fields_ = [
         ("penalty", C.c_uint32),
@@ -309,10 +332,14 @@ _SIGNATURES = {
     "dcn_anchor_map_pileup_fetch": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
     "dcn_anchor_map_pileup_call": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _u64p]),
     "dcn_extend_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "dcn_anchor_map_pileup_keep_insertions": (C.c_int, [_vp, C.c_int]),
+    "dcn_anchor_map_insertions_info": (C.c_int, [_vp, _u64p, _u64p]),
+    "dcn_anchor_map_insertions_fetch": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _u64p, _u64p]),
+    "dcn_anchor_map_insertions_call": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _u64p, _u64p]),
 }
 
 _lib = None
-ABI = (1, 16)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 17)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

@@ -3816,6 +3816,11 @@ struct MapArgs {
     bool extend = false, has_output = false, has_pileup_out = false;
     unsigned penalty = 6, end_bonus = 4, ext_max_edits = DCN_VERIFY_MAX_EDITS;
     std::string pileup_out;
+    // `consensus`: extend's placements piled up under pileup's selection on a map that keeps an insertion ledger; then the
+    // consensus of every record as FASTA with -o and / or its differences from the reference with --variants.  extend and
+    // verify are set as well; -o is the FASTA, so there is no PAF
+    bool consensus = false, fill_ref = false, has_fasta = false, has_variants = false;
+    std::string fasta, variants;
 };
 
 // one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
@@ -3868,8 +3873,9 @@ int run_map(const MapArgs &a) {
     load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, 
                     a.align || a.pileup || a.extend ? "DCN_CLI_ALIGN_BATCH_BASES" : a.verify ? "DCN_CLI_VERIFY_BATCH_BASES" : "DCN_CLI_MAP_BATCH_BASES", a.quiet, a.verify);
     Context &ctx = *R.ctx;
-    const bool piles = a.pileup || (a.extend && (a.has_pileup_out || a.has_sites)); // (the map's counters are used)
+    const bool piles = a.pileup || a.consensus || (a.extend && (a.has_pileup_out || a.has_sites)); // (the map's counters are used)
     if (piles) deacon::check(dcn_anchor_map_pileup_enable(R.map.p, 1)); // (after the records: a pileup does not grow)
+    if (a.consensus) deacon::check(dcn_anchor_map_pileup_keep_insertions(R.map.p, 1)); // (before the first row adds)
     dcn_place_split_params prm = {};
     prm.band_bases = a.band;
     prm.min_votes = a.min_votes;
@@ -4013,9 +4019,18 @@ int run_map(const MapArgs &a) {
     });
     // pileup: the counters of every record, a stretch at a time, as TSV; the sites of the same stretches
     uint64_t covered = 0, n_sites = 0, column_sum[DCN_PILEUP_COLUMNS] = {};
+    uint64_t insertion_events = 0, inserted_bases = 0, insertion_alleles = 0, substitutions = 0, deleted_positions = 0, consensus_bases = 0,
+             uncalled_positions = 0; // (consensus)
     if (piles) {
-        TextOut sites_out, pile_file;
+        TextOut sites_out, pile_file, fasta_out, variants_out;
         if (a.has_sites) sites_out.open(a.sites, false);
+        if (a.has_fasta) fasta_out.open(a.fasta, true);
+        if (a.has_variants) variants_out.open(a.variants, false);
+        if (a.has_variants) variants_out.write("record\tpos\ttype\tref\talt\tdepth\tcount\tevents\n");
+        if (a.consensus) deacon::check(dcn_anchor_map_insertions_info(R.map.p, &insertion_events, &inserted_bases));
+        std::vector<uint8_t> calls, allele_bases;
+        std::vector<dcn_insertion_allele> alleles;
+        std::string seq, variant_rows;
         if (a.extend && a.has_pileup_out) pile_file.open(a.pileup_out, false);
         TextOut *const tsv = a.pileup ? &out : a.has_pileup_out ? &pile_file : nullptr; // (`extend --sites` alone: no table)
         if (tsv) tsv->write("record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\n");
@@ -4029,9 +4044,11 @@ int run_map(const MapArgs &a) {
         std::vector<uint8_t> ref_text;
         std::string site_rows;
         for (uint32_t r = 0; r < R.n_records; ++r) {
+            if (a.has_fasta) fasta_out.write(">" + R.names[r] + "\n");
             for (uint64_t start = 0; start < R.lens[r]; start += stretch) {
                 const uint64_t n = std::min<uint64_t>(stretch, R.lens[r] - start);
                 counts.resize(n * DCN_PILEUP_COLUMNS);
+                if (a.consensus) calls.resize(n);
                 ref_text.resize(n);
                 deacon::check(dcn_anchor_map_pileup_fetch(R.map.p, r, start, n, counts.data()));
                 deacon::check(dcn_anchor_map_fetch(R.map.p, r, start, n, ref_text.data()));
@@ -4050,7 +4067,7 @@ int run_map(const MapArgs &a) {
                 if (tsv) tsv->write(rows);
                 uint64_t found = 0;
                 for (int attempt = 0;; ++attempt) { // (dcn_locate_batch's convention: the first call reports the size)
-                    const int rc = dcn_anchor_map_pileup_call(R.map.p, &cprm, r, start, n, nullptr, site_pos.data(), site_info.data(),
+                    const int rc = dcn_anchor_map_pileup_call(R.map.p, &cprm, r, start, n, a.consensus ? calls.data() : nullptr, site_pos.data(), site_info.data(),
                                                               site_pos.size(), &found);
                     if (rc != DCN_ERR_CAPACITY || attempt) {
                         deacon::check(rc);
@@ -4060,6 +4077,55 @@ int run_map(const MapArgs &a) {
                     site_info.resize(found);
                 }
                 n_sites += found;
+                if (a.consensus) { // rule L7 over the stretch: the called insertions, then position by position
+                    uint64_t n_alleles = 0, n_inserted = 0;
+                    for (int attempt = 0;; ++attempt) {
+                        const int rc = dcn_anchor_map_insertions_call(R.map.p, &cprm, r, start, n, alleles.data(), alleles.size(), allele_bases.data(),
+                                                                      allele_bases.size(), &n_alleles, &n_inserted);
+                        if (rc != DCN_ERR_CAPACITY || attempt) {
+                            deacon::check(rc);
+                            break;
+                        }
+                        alleles.resize(n_alleles);
+                        allele_bases.resize(n_inserted);
+                    }
+                    insertion_alleles += n_alleles;
+                    seq.clear();
+                    variant_rows.clear();
+                    uint64_t next = 0; // the next allele: they are in ascending position
+                    for (uint64_t q = 0; q < n; ++q) {
+                        const uint32_t *const c = counts.data() + q * DCN_PILEUP_COLUMNS;
+                        uint64_t depth = 0;
+                        for (int col = 0; col <= DCN_PILEUP_DEL; ++col) depth += c[col];
+                        const dcn_insertion_allele *const al = next < n_alleles && alleles[next].pos == start + q ? &alleles[next++] : nullptr;
+                        const auto insertion = [&] {
+                            const std::string alt((const char *)allele_bases.data() + al->bases_offset, al->len);
+                            seq += alt;
+                            if (a.has_variants)
+                                variant_rows += R.names[r] + '\t' + std::to_string(start + q) + '\t' + (al->flags & DCN_INSERTION_FRONT ? "INS_FRONT" : "INS") +
+                                                "\t.\t" + alt + '\t' + std::to_string(depth) + '\t' + std::to_string(al->count) + '\t' +
+                                                std::to_string(al->events) + '\n';
+                        };
+                        if (al && (al->flags & DCN_INSERTION_FRONT)) insertion();
+                        const char call = (char)calls[q], ref = (char)ref_text[q];
+                        if (call == 'N') { // (not called: P6 writes N there and nowhere else)
+                            ++uncalled_positions;
+                            seq += a.fill_ref ? ref : 'N';
+                        } else {
+                            const uint32_t best = call == '-' ? c[DCN_PILEUP_DEL] : c[call == 'A' ? DCN_PILEUP_A : call == 'C' ? DCN_PILEUP_C : call == 'G' ? DCN_PILEUP_G : DCN_PILEUP_T];
+                            if (call != '-') seq += call;
+                            if (call == '-') ++deleted_positions;
+                            else if (call != ref) ++substitutions;
+                            if (a.has_variants && call != ref)
+                                variant_rows += R.names[r] + '\t' + std::to_string(start + q) + '\t' + (call == '-' ? "DEL" : "SUB") + '\t' + ref + '\t' + call +
+                                                '\t' + std::to_string(depth) + '\t' + std::to_string(best) + "\t0\n";
+                        }
+                        if (al && !(al->flags & DCN_INSERTION_FRONT)) insertion();
+                    }
+                    consensus_bases += seq.size();
+                    if (a.has_fasta) fasta_out.write(seq);
+                    if (a.has_variants) variants_out.write(variant_rows);
+                }
                 if (!a.has_sites) continue;
                 site_rows.clear();
                 for (uint64_t i = 0; i < found; ++i) {
@@ -4072,8 +4138,11 @@ int run_map(const MapArgs &a) {
                 }
                 sites_out.write(site_rows);
             }
+            if (a.has_fasta) fasta_out.write("\n");
         }
         if (a.has_sites) sites_out.finish();
+        if (a.has_fasta) fasta_out.finish();
+        if (a.has_variants) variants_out.finish();
         if (a.extend && a.has_pileup_out) pile_file.finish();
     }
     if (prints) out.finish();
@@ -4086,6 +4155,10 @@ int run_map(const MapArgs &a) {
         if (piles)
             std::fprintf(stderr, "Piled up %llu of %llu placements on %llu positions (%llu sites)\n", (unsigned long long)rows_added,
                          (unsigned long long)placements, (unsigned long long)covered, (unsigned long long)n_sites);
+        if (a.consensus)
+            std::fprintf(stderr, "Consensus of %llu bases: %llu substitutions, %llu deleted positions, %llu insertions of %llu events, %llu positions without a call\n",
+                         (unsigned long long)consensus_bases, (unsigned long long)substitutions, (unsigned long long)deleted_positions,
+                         (unsigned long long)insertion_alleles, (unsigned long long)insertion_events, (unsigned long long)uncalled_positions);
         if (a.verify && !a.pileup)
             std::fprintf(stderr, "Verified %llu of %llu placements (%llu edits over %llu bases)\n", (unsigned long long)verified,
                          (unsigned long long)placements, (unsigned long long)edits_sum, (unsigned long long)verified_bases);
@@ -4133,6 +4206,12 @@ int run_map(const MapArgs &a) {
                 appendf(js, "%s\"%s\": %llu", col ? ", " : "", column_names[col], (unsigned long long)column_sum[col]);
             js += "},\n";
         }
+        if (a.consensus)
+            appendf(js, "  \"fill_ref\": %s,\n  \"insertion_events\": %llu,\n  \"inserted_bases\": %llu,\n  \"insertion_alleles\": %llu,\n"
+                        "  \"substitutions\": %llu,\n  \"deleted_positions\": %llu,\n  \"consensus_bases\": %llu,\n  \"uncalled_positions\": %llu,\n",
+                    a.fill_ref ? "true" : "false", (unsigned long long)insertion_events, (unsigned long long)inserted_bases,
+                    (unsigned long long)insertion_alleles, (unsigned long long)substitutions, (unsigned long long)deleted_positions,
+                    (unsigned long long)consensus_bases, (unsigned long long)uncalled_positions);
         appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
         for (uint32_t r = 0; r < R.n_records; ++r) {
             js += (r ? ",\n    {" : "\n    {");
@@ -4282,6 +4361,7 @@ void usage() {
                  "  align   As verify, with the alignment of every verified placement: cg:Z: with = X I D, as PAF\n"
                  "  pileup  As align, summed per reference position: counts of A C G T N, gaps and strand, and site calls, as TSV\n"
                  "  extend  As map, each placement carried over the flanks of its read, the rest soft-clipped; then align, pileup\n"
+                 "  consensus  As extend and pileup, keeping inserted bases: the sequence the reads support as FASTA, and its variants\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -4610,6 +4690,61 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "the soft clip.  The defaults are conventions, not measured optima.  Integers only: the output does not depend\n"
                "on how the input is cut into batches.  Unit costs, no affine gaps, no SAM.\n"
                "Placements and qualities are map's for the same arguments.  Mates are independent here: one input.\n";
+    else if (sub == "consensus")
+        text = "Pile the extended placements of the reads up on a reference, keep the inserted bases, and write the sequence\n"
+               "the reads support\n\n"
+               "Usage: deacon-hip consensus [OPTIONS] <REF> [READS]\n\n"
+               "Arguments:\n"
+               "  <REF>     Path to the reference fastx file: its records are numbered and named in file order\n"
+               "  [READS]   Optional path to fastx file (or - for stdin; gz, bgzf, zst, xz and bz2 found by content) [default: -]\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Keys that may anchor: a minimizer index file, whose k and w are used\n"
+               "                                 [default: the minimizers of <REF> at -k / -w]\n"
+               "  -k <K>                         K-mer length without -x [default: 31]\n"
+               "  -w <W>                         Minimizer window size without -x [default: 15]\n"
+               "  -o, --output <OUTPUT>          FASTA: per record of <REF> a line >name and its consensus on one line (- for\n"
+               "                                 stdout) [default: no FASTA]\n"
+               "      --variants <FILE>          TSV: record pos type ref alt depth count events, pos 0-based as in PAF; one SUB line\n"
+               "                                 per substituted position, one DEL line per deleted position (alt -), one INS or\n"
+               "                                 INS_FRONT line per called insertion behind or in front of pos (ref ., count = the\n"
+               "                                 reads with exactly these bases, events = all insertions there; 0 on other lines)\n"
+               "      --fill-ref                 A position without a call takes the reference's base, not N\n"
+               "      --pileup <FILE>            pileup's TSV over the extended placements: record pos ref A C G T N del ins rev\n"
+               "      --sites <FILE>             pileup's site TSV over them: record pos ref call depth flags\n"
+               "      --all-positions            One line of --pileup for every position of every record\n"
+               "      --min-depth <N>            A call needs a depth of at least N [default: 3, a convention]\n"
+               "      --min-frac <N>             ... and N per 1000 of the depth for the most frequent of A C G T and gap, and\n"
+               "                                 for the insertions at a position (0..1000) [default: 500, a convention]\n"
+               "      --min-mapq <N>             Only placements of mapping quality N or more add (0..60) [default: 1, a convention]\n"
+               "      --all-ranks                Every placement of a read adds, not only its first (rank 0)\n"
+               "      --penalty <N>              An edit in a flank costs N matched bases of read plus record (2..255)\n"
+               "                                 [default: 6, a convention]\n"
+               "      --end-bonus <N>            Reaching the read's end is worth N (0..65535) [default: 4, a convention]\n"
+               "      --ext-max-edits <N>        At most N edits per flank (0..1023) [default: 1023, a convention]\n"
+               "  -e, --max-edits <N>            Only placements of at most N edits over the extended extents add (0..1023)\n"
+               "                                 [default: 1023, a convention]\n"
+               "      --max-div <N>              ... and of at most N per 1000 bases of the longer extended extent (0..1000)\n"
+               "                                 [default: 200, a convention]\n"
+               "  -N, --max-placements <N>       Placements per read, each from the anchor hits no earlier one explained (1..8)\n"
+               "                                 [default: 4]\n"
+               "      --band <N>                 Width of a diagonal band in bases [default: 256, a convention]\n"
+               "  -a, --min-votes <N>            Minimum number of anchor hits in a placement's cell [default: 2, as filter's -a,\n"
+               "                                 a convention]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per read (0 = entire read) [default: 0]\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file: extend's and pileup's keys, and fill_ref,\n"
+               "                                 insertion_events, inserted_bases, insertion_alleles, substitutions,\n"
+               "                                 deleted_positions, consensus_bases and uncalled_positions\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
+               "  -h, --help                     Print help\n\n"
+               "Consensus, position by position of a record: the bases of an insertion called in front of the position; the\n"
+               "called base, nothing where a gap is called, N (or the reference's base with --fill-ref) where nothing is; the\n"
+               "bases of an insertion called behind it.  An insertion is called where the reads with an insertion there reach\n"
+               "--min-frac of a depth of at least --min-depth; its bases are those most of them agree on (on a tie one behind\n"
+               "the position before one in front, then the shorter, then the first by letter), whatever their own share: count\n"
+               "and events say what it is.  The thresholds are conventions, not measured optima.  Integers and bytes only: the\n"
+               "output does not depend on how the input is cut into batches.  Deleted positions are not merged, indels are not\n"
+               "left-normalised.  VCF, base qualities and affine gaps are not built.  Mates are independent here: one input.\n";
     else if (sub == "map-pairs")
         text = "Place the two mates of each pair jointly on a reference: proper pairs, rescued mates and insert sizes, as PAF\n\n"
                "Usage: deacon-hip map-pairs [OPTIONS] <REF> <READS1> [READS2]\n\n"
@@ -4900,11 +5035,12 @@ int main(int argc, char **argv) {
             if (pos.size() > 2) die("place takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[2] + "')");
             return run_place(a);
         }
-        if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup" || args[0] == "extend") {
+        if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup" || args[0] == "extend" || args[0] == "consensus") {
             MapArgs a;
             a.align = args[0] == "align";
             a.pileup = args[0] == "pileup";
-            a.extend = args[0] == "extend";
+            a.consensus = args[0] == "consensus";
+            a.extend = args[0] == "extend" || a.consensus;
             a.verify = a.align || a.pileup || a.extend || args[0] == "verify";
             std::vector<std::string> pos;
             auto number = [&](const std::string &v, const char *flag, long long lo, long long hi) {
@@ -4919,6 +5055,9 @@ int main(int argc, char **argv) {
                 if (s == "-x" || s == "--index") a.index = need(++i), a.has_index = true;
                 else if (s == "-k") a.k = (unsigned)number(need(++i), "-k", 1, 56);
                 else if (s == "-w") a.w = (unsigned)number(need(++i), "-w", 1, 255);
+                else if (a.consensus && (s == "-o" || s == "--output")) a.fasta = need(++i), a.has_fasta = true; // (the FASTA: there is no PAF)
+                else if (a.consensus && s == "--variants") a.variants = need(++i), a.has_variants = true;
+                else if (a.consensus && s == "--fill-ref") a.fill_ref = true;
                 else if (s == "-o" || s == "--output") a.output = need(++i), a.has_output = true;
                 else if (a.extend && s == "--penalty") a.penalty = (unsigned)number(need(++i), "--penalty", 2, 255);
                 else if (a.extend && s == "--end-bonus") a.end_bonus = (unsigned)number(need(++i), "--end-bonus", 0, 65535);

@@ -82,6 +82,8 @@ uint32_t dcn_current_variant();
 
 struct dcn_base_store; // (dcn_verify.h)
 void dcn_base_store_free(dcn_base_store *s);
+struct dcn_ins_ledger; // (dcn_verify.h)
+void dcn_ins_ledger_free(dcn_ins_ledger *l);
 
 struct dcn_index {
     // captured when the index is created (built, loaded, merged, cloned): the rule its keys were selected by travels
@@ -118,6 +120,10 @@ struct dcn_index {
     // was when enabled, pileup_bases of them, laid out by dcn_pile_index (dcn_pileup.h).  Null: none.
     uint32_t *d_pileup = nullptr;
     uint64_t pileup_bases = 0;
+    // ... the rows that have added to it since it was enabled or reset, and the insertion ledger beside it
+    // (dcn_anchor_map_pileup_keep_insertions, insertions_api.hip).  Null: none is kept.
+    uint64_t pileup_rows = 0;
+    dcn_ins_ledger *ledger = nullptr;
     dcn_table_view view() const {
         dcn_table_view v;
         v.slots = d_slots;

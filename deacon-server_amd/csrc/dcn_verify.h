@@ -251,3 +251,73 @@ struct dcn_extend_args {
     dcn_extend_result *out;
 };
 int dcn_launch_extend(const dcn_extend_args &args, hipStream_t stream);
+
+// ---- insertion ledger (insertions.hip, insertions_api.hip; the shared arithmetic is in dcn_insertions.h) --------------
+struct dcn_ins_event; // (dcn_insertions.h)
+// The ledger of a map (dcn_anchor_map_pileup_keep_insertions): the events and their bases on the device, both arrays
+// growing geometrically from DCN_INSERTION_LEDGER_EVENTS (read when the ledger first grows), and the scratch of the append
+// inside dcn_pileup_batch, which lives with the ledger: per aligned row of a call its events and bases, their offsets and
+// the scan's sums, and the two totals, which are zero between calls.
+struct dcn_ins_ledger {
+    dcn_ins_event *d_events = nullptr;
+    uint8_t *d_bases = nullptr;
+    uint64_t event_cap = 0, base_cap = 0, n_events = 0, n_bases = 0;
+    uint32_t *d_row_events = nullptr, *d_row_bases = nullptr;
+    uint64_t rows_cap = 0;
+    uint64_t *d_event_offsets = nullptr, *d_base_offsets = nullptr;
+    unsigned long long *d_event_sums = nullptr, *d_base_sums = nullptr;
+    uint64_t offsets_cap = 0;
+    unsigned long long *d_totals = nullptr; // events, bases
+};
+void dcn_ins_ledger_free(dcn_ins_ledger *l);
+
+// the walk of pileup_kernel over the same work list (args.counters is not looked at)
+struct dcn_ins_append_args {
+    dcn_pileup_args rows;
+    uint32_t *row_events, *row_bases; // per work item (the counting pass)
+    unsigned long long *totals;       // ... and their sums over the call, added to
+    const uint64_t *event_offsets, *base_offsets; // their scans (the writing pass)
+    dcn_ins_event *events;                        // the ledger's arrays, from where this call appends
+    uint8_t *bases;
+    uint64_t event0, base0;
+};
+int dcn_launch_ins_count(const dcn_ins_append_args &args, hipStream_t stream);
+int dcn_launch_ins_write(const dcn_ins_append_args &args, hipStream_t stream);
+// the append of dcn_pileup_batch on a map that keeps a ledger, behind the pileup kernel on the context's stream
+int dcn_insertions_append(dcn_ctx *c, dcn_index *map, const dcn_pileup_args &rows);
+
+// fetch and call over the range [base0, base0 + n) of the store
+struct dcn_ins_range_args {
+    const uint32_t *counters; // the map's pileup
+    uint64_t bases;
+    const uint32_t *t_packed, *t_invmask;
+    uint64_t base0, n, pos0;
+    uint32_t min_depth, min_permille;
+    uint32_t *counts, *flags;       // per position: the events that count (L2, L6), and whether it has a called insertion
+    const uint64_t *bucket_offsets; // the scan of counts
+    uint32_t *cursor;               // per position, zero before the scatter
+    uint64_t *slots;                // per bucket entry: the event of the ledger
+    const dcn_ins_event *events;
+    const uint8_t *ledger_bases;
+    uint64_t n_events;
+    // fetch
+    uint64_t n_slots;
+    uint32_t *slot_lens;
+    const uint64_t *slot_offsets; // their scan
+    void *out_events;             // dcn_insertion per slot
+    uint8_t *out_bases;
+    // call
+    const uint64_t *allele_offsets; // the scan of flags
+    uint64_t n_alleles;
+    uint64_t *win_event;
+    uint32_t *win_count, *win_events, *win_len;
+    uint64_t *win_pos;
+    const uint64_t *win_offsets; // the scan of win_len
+    void *out_alleles;           // dcn_insertion_allele per allele
+};
+int dcn_launch_ins_plane(const dcn_ins_range_args &args, bool call, hipStream_t stream);
+int dcn_launch_ins_scatter(const dcn_ins_range_args &args, hipStream_t stream);
+int dcn_launch_ins_slot_lens(const dcn_ins_range_args &args, hipStream_t stream);
+int dcn_launch_ins_gather(const dcn_ins_range_args &args, hipStream_t stream);
+int dcn_launch_ins_winner(const dcn_ins_range_args &args, hipStream_t stream);
+int dcn_launch_ins_alleles(const dcn_ins_range_args &args, hipStream_t stream);

@@ -1,5 +1,6 @@
 // pileup_api.hip -- the C ABI of pileups (dcn_anchor_map_pileup_enable / _reset / _fetch / _call, dcn_pileup_batch;
-// kernels in pileup.hip, the shared arithmetic in dcn_pileup.h).  dcn_pileup_batch is dcn_align_batch's sequence
+// kernels in pileup.hip, the shared arithmetic in dcn_pileup.h; a kept insertion ledger, insertions_api.hip, is appended
+// to, emptied and freed here).  dcn_pileup_batch is dcn_align_batch's sequence
 // (verify_api.hip's walk, align_api.hip's passes and gather) with the runs left on the device and the pileup kernel behind.
 #include "dcn_ctx.h"
 #include "dcn_dump_sweep.h"
@@ -48,9 +49,12 @@ extern "C" int dcn_anchor_map_pileup_enable(dcn_index *map, int enable) {
         if (map->d_pileup) {
             DCN_HIP(hipSetDevice(map->device));
             hipFree(map->d_pileup);
+            dcn_ins_ledger_free(map->ledger);
         }
         map->d_pileup = nullptr;
         map->pileup_bases = 0;
+        map->pileup_rows = 0;
+        map->ledger = nullptr;
         return DCN_OK;
     }
     if (map->d_pileup) return DCN_OK;
@@ -58,6 +62,7 @@ extern "C" int dcn_anchor_map_pileup_enable(dcn_index *map, int enable) {
     const uint64_t bases = std::max<uint64_t>(map->store->used, 32); // (whole 32-base groups, as the store counts them)
     DCN_TRY(dev_alloc_zeroed(&map->d_pileup, bases * DCN_PILE_COLUMNS, "pileup counters"));
     map->pileup_bases = bases;
+    map->pileup_rows = 0;
     return DCN_OK;
 }
 
@@ -66,6 +71,8 @@ extern "C" int dcn_anchor_map_pileup_reset(dcn_index *map) {
     DCN_HIP(hipSetDevice(map->device));
     DCN_HIP(hipMemset(map->d_pileup, 0, map->pileup_bases * DCN_PILE_COLUMNS * sizeof(uint32_t)));
     DCN_HIP(hipDeviceSynchronize()); // (null-stream work must not be overtaken by a context's stream)
+    map->pileup_rows = 0;
+    if (map->ledger) map->ledger->n_events = map->ledger->n_bases = 0; // (the arrays stay: the next append begins at their start)
     return DCN_OK;
 }
 
@@ -100,14 +107,14 @@ extern "C" int dcn_pileup_batch(dcn_ctx *ctx, dcn_index *map, const uint8_t *bas
         pa.counters = map->d_pileup;
         pa.bases = map->pileup_bases;
         DCN_TRY(dcn_launch_pileup(pa, st));
+        if (map->ledger) DCN_TRY(dcn_insertions_append(c, map, pa)); // rule L2, behind the same checks
     }
     DCN_PROF_MARK(DCN_STAGE_FINISH);
     DCN_TRY(finish_run(c, prof_slot));
-    if (n_added) { // rule P2: the rows with an alignment and n > 0
-        uint64_t added = 0;
-        for (uint64_t row = 0; row < n_rows; ++row) added += edits[row] < DCN_VERIFY_OVER && plan.items[row].n > 0;
-        *n_added = added;
-    }
+    uint64_t added = 0; // rule P2: the rows with an alignment and n > 0
+    for (uint64_t row = 0; row < n_rows; ++row) added += edits[row] < DCN_VERIFY_OVER && plan.items[row].n > 0;
+    map->pileup_rows += added; // (rule L1 asks)
+    if (n_added) *n_added = added;
     return DCN_OK;
 }
 

@@ -679,6 +679,12 @@ PILEUP_A, PILEUP_C, PILEUP_G, PILEUP_T, PILEUP_N, PILEUP_DEL, PILEUP_INS, PILEUP
     N.PILEUP_A, N.PILEUP_C, N.PILEUP_G, N.PILEUP_T, N.PILEUP_N, N.PILEUP_DEL, N.PILEUP_INS, N.PILEUP_REV)
 PILEUP_COLUMNS = N.PILEUP_COLUMNS
 PILEUP_SITE_SUB, PILEUP_SITE_DEL, PILEUP_SITE_INS, PILEUP_NO_CODE = N.PILEUP_SITE_SUB, N.PILEUP_SITE_DEL, N.PILEUP_SITE_INS, N.PILEUP_NO_CODE
+# numpy views of dcn_insertion (24 bytes) and dcn_insertion_allele (32 bytes): an event of an insertion ledger and the
+# called insertion of a position; bases_offset points into the bases returned beside them
+INSERTION_DTYPE = np.dtype([("pos", np.uint64), ("bases_offset", np.uint64), ("len", np.uint32), ("flags", np.uint32)])
+INSERTION_ALLELE_DTYPE = np.dtype([("pos", np.uint64), ("bases_offset", np.uint64), ("len", np.uint32), ("count", np.uint32),
+                                   ("events", np.uint32), ("flags", np.uint32)])
+INSERTION_FRONT, INSERTION_REVERSE = N.INSERTION_FRONT, N.INSERTION_REVERSE  # DCN_INSERTION_*: bits of `flags`
 _CIGAR_LETTERS = {N.CIGAR_INS: "I", N.CIGAR_DEL: "D", N.CIGAR_EQUAL: "=", N.CIGAR_DIFF: "X"}
 
 
@@ -753,6 +759,77 @@ class AnchorMap(Index):
             rc, pos, info = call(int(n_sites.value))
         N.check(rc)
         return calls[:n].tobytes(), pos[:int(n_sites.value)], info[:int(n_sites.value)]
+
+    def pileup_keep_insertions(self, keep=True):
+        """An insertion ledger beside the pileup (dcn_anchor_map_pileup_keep_insertions; the definition of an insertion
+        ledger is in include/deacon_hip.h): every I run that Placer.pileup_batch counts in INS also leaves its bases.
+        Refused once a row has added since pileup_enable() or pileup_reset(); keep=False drops it and leaves the counters."""
+        N.check(N.lib().dcn_anchor_map_pileup_keep_insertions(self._h, 1 if keep else 0))
+
+    def insertions_info(self):
+        """-> (events of the ledger, the sum of their lengths)"""
+        n_events, n_bases = C.c_uint64(), C.c_uint64()
+        N.check(N.lib().dcn_anchor_map_insertions_info(self._h, C.byref(n_events), C.byref(n_bases)))
+        return int(n_events.value), int(n_bases.value)
+
+    def _insertions(self, fn, head, dtype, n, estimate):
+        """one call with an estimate and, on DCN_ERR_CAPACITY, a second with the sizes the first reported"""
+        n_items, n_ins = C.c_uint64(), C.c_uint64()
+
+        def call(cap, base_cap):
+            items, bases = np.zeros(max(cap, 1), dtype), np.zeros(max(base_cap, 1), np.uint8)
+            rc = fn(*head, _ptr(items) if cap else None, cap, _ptr(bases) if base_cap else None, base_cap, C.byref(n_items), C.byref(n_ins))
+            return rc, items, bases
+
+        rc, items, bases = call(estimate, 4 * estimate)
+        if rc == N.DCN_ERR_CAPACITY:
+            rc, items, bases = call(int(n_items.value), int(n_ins.value))
+        N.check(rc)
+        return items[:int(n_items.value)], bases[:int(n_ins.value)].tobytes()
+
+    def insertions_fetch(self, record, start=0, n=None):
+        """The events of the ledger anchored in [start, start + n) of a record (n=None: to its end), in the canonical order
+        of rule L4 -> (INSERTION_DTYPE[], bases bytes): event e's bases are bases[e.bases_offset : e.bases_offset + e.len]."""
+        start, n = int(start), self._to_end(record, start) if n is None else int(n)
+        return self._insertions(N.lib().dcn_anchor_map_insertions_fetch, (self._h, int(record), start, n), INSERTION_DTYPE, n, n // 16 + 64)
+
+    def insertions_call(self, record, start=0, n=None, min_depth=3, min_permille=500):
+        """Rule L6 over [start, start + n) of a record -> (INSERTION_ALLELE_DTYPE[], bases bytes): per position with a called
+        insertion its winning allele, its count and the events there, in ascending position.  The thresholds are
+        pileup_call's, conventions and not measured optima."""
+        start, n = int(start), self._to_end(record, start) if n is None else int(n)
+        p = N.PileupCallParams(int(min_depth), int(min_permille), (C.c_uint32 * 2)(0, 0))
+        return self._insertions(N.lib().dcn_anchor_map_insertions_call, (self._h, C.byref(p), int(record), start, n), INSERTION_ALLELE_DTYPE,
+                                n, n // 64 + 64)
+
+    def consensus(self, record, start=0, n=None, min_depth=3, min_permille=500, fill_ref=False):
+        """Rule L7 over [start, start + n) of a record -> bytes: per position the bases of a called front insertion, the
+        called base (nothing for '-'; N, or with fill_ref the record's own base, where there is no call), the bases of a
+        called insertion behind it.  Assembled here from pileup_call's characters and insertions_call's alleles: a linear
+        copy, with numpy and no loop over bases."""
+        start, n = int(start), self._to_end(record, start) if n is None else int(n)
+        calls = np.frombuffer(self.pileup_call(record, start, n, min_depth, min_permille)[0], np.uint8)
+        alleles, ins = self.insertions_call(record, start, n, min_depth, min_permille)
+        ins = np.frombuffer(ins, np.uint8)
+        own = calls
+        if fill_ref:  # a position without a call: pileup_call writes N there, as it does nowhere else (N never wins)
+            own = np.where(calls == ord("N"), np.frombuffer(self.fetch(record, start, n), np.uint8), calls)
+        own_len = (own != ord("-")).astype(np.int64)
+        q = (alleles["pos"].astype(np.int64) - start)
+        front = (alleles["flags"] & N.INSERTION_FRONT) != 0
+        before, behind = np.zeros(n, np.int64), np.zeros(n, np.int64)
+        before[q[front]] = alleles["len"][front]
+        behind[q[~front]] = alleles["len"][~front]
+        begin = np.concatenate(([0], np.cumsum(before + own_len + behind)))  # where each position's output begins
+        out = np.zeros(int(begin[-1]), np.uint8)
+        keep = own_len.astype(bool)
+        out[(begin[:-1] + before)[keep]] = own[keep]
+        if len(alleles):
+            dst0 = np.where(front, begin[:-1][q], (begin[:-1] + before + own_len)[q])  # where each allele's bases begin
+            lens = alleles["len"].astype(np.int64)
+            within = np.arange(int(lens.sum()), dtype=np.int64) - np.repeat(np.cumsum(lens) - lens, lens)
+            out[np.repeat(dst0, lens) + within] = ins[np.repeat(alleles["bases_offset"].astype(np.int64), lens) + within]
+        return out.tobytes()
 
     def _to_end(self, record, start):
         """bases from `start` to the end of a record (the lengths of the records add() has taken are kept here)"""

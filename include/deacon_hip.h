@@ -79,9 +79,10 @@ enum {
  * 1.13 = dcn_anchor_map_keep_bases / _fetch, dcn_verify_batch.
  * 1.14 = dcn_align_batch.
  * 1.15 = dcn_anchor_map_pileup_* / dcn_pileup_batch.
- * 1.16 = dcn_extend_batch. */
+ * 1.16 = dcn_extend_batch.
+ * 1.17 = dcn_anchor_map_pileup_keep_insertions, dcn_anchor_map_insertions_info / _fetch / _call. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 16
+#define DCN_ABI_MINOR 17
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -939,7 +940,8 @@ int dcn_align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, co
  *         A D step adds 1 to DEL at ref_start + j.
  *         Every '=', X and D step of a row with reverse = 1 also adds 1 to REV at its position.
  *         An I RUN, of whatever length, adds 1 to INS: at ref_start + j - 1, the base of T in front of it, if j > 0, else
- *           at ref_start.  This is always inside T, since n > 0.  Inserted bases are not recorded.
+ *           at ref_start.  This is always inside T, since n > 0.  The inserted bases are recorded only by an insertion
+ *           ledger (below).
  *   P4. depth(p) is the sum of columns 0-5.  Over one row, each position of T receives exactly one add among columns 0-5.
  *   P5. Integers only.  Adds commute: the counters after any sequence of calls depend only on the multiset of rows added,
  *       not on how batches are cut, on align's trace groups, on lanes or on order.  A counter wraps above 2^32 - 1;
@@ -1016,6 +1018,83 @@ int dcn_anchor_map_pileup_fetch(const dcn_index *map, uint32_t record, uint64_t 
  * Blocking; one thread per position, a scan of the per-workgroup site counts, and a second pass that writes the sites. */
 int dcn_anchor_map_pileup_call(const dcn_index *map, const void *params, uint32_t record, uint64_t start, uint64_t n_bases,
                                uint8_t *calls, uint64_t *site_pos, uint32_t *site_info, uint64_t capacity, uint64_t *n_sites);
+
+/* ---- insertion ledger: the inserted bases beside a pileup, insertion alleles (ABI 1.17) --------------------------------
+ * (no reference counterpart.)  The INS column of a pileup says that an insertion sits at a base, not what it is.  A ledger
+ * keeps every insertion's bases, so that the sequence the reads support can be written out.
+ *
+ * THE DEFINITION OF AN INSERTION LEDGER.  Rules 1-6 of a verified placement, A1-A6 and P1-P6 stand.  Added:
+ *   L1. A map with a pileup enabled may keep an insertion ledger: a multiset of events, empty when switched on.  Switching
+ *       it on is DCN_ERR_ARG once any row has added to the pileup (P2) since the pileup was enabled or last reset, so the
+ *       ledger and the INS column always describe the same rows.
+ *   L2. While the ledger is kept, every I run that P3 counts in INS also appends one event (p, front, len, bases, reverse):
+ *         p is the position P3 adds to: ref_start + j - 1, or ref_start when j = 0;
+ *         front is 1 exactly in the j = 0 case: the run then lies in front of p, not behind it;
+ *         len is the run's length;
+ *         bases are S[i .. i + len) as upper-case ASCII A C G T, with N for an invalid base (S is already
+ *           reverse-complemented on a reverse row: the bases are in the record's direction);
+ *         reverse is the row's strand.
+ *       Hence at every position the number of events equals INS, while no counter has wrapped.
+ *   L3. Events commute: the ledger depends on the multiset of rows added, not on how batches are cut, on align's trace
+ *       groups, on lanes or on order.
+ *   L4. The canonical order, used wherever events are returned: ascending p; then front 0 before 1; then the shorter len;
+ *       then bases as bytes (so A < C < G < N < T); then reverse 0 before 1.  Equal events are indistinguishable, so the
+ *       output is fully determined.
+ *   L5. An ALLELE at p is a class of events equal in (front, len, bases); its count is the size of the class.  The WINNER
+ *       is the allele with the largest count; ties go to the allele that comes first in L4's order.
+ *   L6. With P6's parameters, position p HAS A CALLED INSERTION when P6 sets DCN_PILEUP_SITE_INS there and INS > 0 (which
+ *       matters at min_permille = 0, where P6 flags every deep position).  The call is the winner, reported with its count
+ *       and with events = INS(p).  The winner's own count is not thresholded: the caller has both numbers.
+ *   L7. The consensus of a range, position by position: the bases of a called insertion with front = 1 there; then the
+ *       base P6 calls, nothing when P6 calls '-', and fill(p) when the position is not called (N, or with "fill from the
+ *       reference" the record's own base in upper case, N for an invalid one); then the bases of a called insertion with
+ *       front = 0.  An insertion applies whether or not the position itself is called or deleted.
+ *   L8. Integers and bytes only.  The result is unique.
+ * The winner of a position is found by counting every event of the position against every other: quadratic in the events
+ * of ONE position, which is fine at the depths the pileup is measured at and unmeasured beyond. */
+#define DCN_INSERTION_FRONT 1u
+#define DCN_INSERTION_REVERSE 2u
+typedef struct dcn_insertion {
+    uint64_t pos;          /* record-relative, 0-based */
+    uint64_t bases_offset; /* into the bases array of the same call */
+    uint32_t len;
+    uint32_t flags;        /* DCN_INSERTION_FRONT, DCN_INSERTION_REVERSE */
+} dcn_insertion;           /* 24 bytes */
+typedef struct dcn_insertion_allele {
+    uint64_t pos, bases_offset;
+    uint32_t len, count, events, flags; /* flags: DCN_INSERTION_FRONT only */
+} dcn_insertion_allele;                 /* 32 bytes */
+
+/* keep != 0 switches the ledger on (L1; keeping again changes nothing), keep = 0 drops it and leaves the counters.
+ * DCN_ERR_ARG for a map without a pileup, and by rule L1; dcn_anchor_map_pileup_reset also empties a kept ledger,
+ * dcn_anchor_map_pileup_enable(map, 0) also frees it, dcn_index_clone gives an index without it, dcn_index_memory does not
+ * count it.  On a map that keeps a ledger dcn_pileup_batch also appends, in the same call and behind the same checks (any
+ * DCN_ERR_ARG leaves the counters and the ledger untouched): a counting pass over the aligned rows, one read-back of the
+ * two totals, and only when there is an I run the two scans, the growth of the ledger (geometric, from
+ * DCN_INSERTION_LEDGER_EVENTS events, read when the ledger first grows) and the writing pass.  A map on which no ledger is
+ * kept behaves byte for byte as before; with one, the eight counters are exactly what they were.  Blocking. */
+int dcn_anchor_map_pileup_keep_insertions(dcn_index *map, int keep);
+/* the events of the ledger and the sum of their lengths (either pointer may be NULL).  Blocking. */
+int dcn_anchor_map_insertions_info(const dcn_index *map, uint64_t *n_events, uint64_t *n_bases);
+
+/* The events anchored in [start, start + n_bases) of a record, in L4's order, with bases_offset ascending and dense.
+ *   events      dcn_insertion entries (declared void * for the reason given at dcn_locate_batch), event_capacity of them
+ *   bases       base_capacity bytes
+ *   n_events, n_inserted   always receive the number of events and the sum of their lengths
+ * DCN_ERR_CAPACITY when either capacity is too small: nothing else is written then; NULLs with capacity 0 ask for the
+ * sizes.  Range errors as for dcn_anchor_map_fetch; DCN_ERR_ARG for a map that keeps no ledger and for a range with 2^32
+ * events or more.  Blocking: the INS plane of the range, its scan, a pass over the whole ledger that scatters the events
+ * of the range into their positions' buckets, a gather, and a sort of each bucket on the host. */
+int dcn_anchor_map_insertions_fetch(const dcn_index *map, uint32_t record, uint64_t start, uint64_t n_bases, void *events,
+                                    uint64_t event_capacity, uint8_t *bases, uint64_t base_capacity, uint64_t *n_events,
+                                    uint64_t *n_inserted);
+
+/* Rule L6 over [start, start + n_bases) of a record: one dcn_insertion_allele per position with a called insertion, in
+ * ascending pos, under the same capacity protocol.  params is a dcn_pileup_call_params, with the checks, the order and the
+ * messages of dcn_anchor_map_pileup_call.  Blocking. */
+int dcn_anchor_map_insertions_call(const dcn_index *map, const void *params, uint32_t record, uint64_t start, uint64_t n_bases,
+                                   void *alleles, uint64_t allele_capacity, uint8_t *bases, uint64_t base_capacity,
+                                   uint64_t *n_alleles, uint64_t *n_inserted);
 
 /* ---- extended placements: each placement carried over the read's flanks, with soft clips (ABI 1.16) -------------------
  * (no reference counterpart.)  A placement's two intervals begin and end on the k-mer of an anchor hit: the read's bases
