@@ -23,6 +23,13 @@ using dcn_host::HostPool;
 uint32_t dcn_cu_count() {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    // DCN_GRID_CUS, read at call time: a test hook that lowers the count (never raises it), so that a few hundred items
+    // already make every capped grid loop.  Unset, empty, 0 or not a number: the device's count.
+    const char *s = std::getenv("DCN_GRID_CUS");
+    char *end = nullptr;
+    unsigned long long cap = s && *s ? std::strtoull(s, &end, 10) : 0;
+    if (end && *end) cap = 0; // (something behind the digits: not a number)
+    if (cap >= 1) cus = (int)std::min<unsigned long long>(cap, (unsigned long long)std::max(cus, 1));
     return (uint32_t)std::max(cus, 1);
 }
 
