@@ -194,6 +194,14 @@ class InsertionAllele(C.Structure):
 INSERTION_FRONT, INSERTION_REVERSE = 1, 2  # DCN_INSERTION_*: the flags of an event; an allele has FRONT only
 
 
+class PileupQualParams(C.Structure):
+    _fields_ = [
+        ("qual_offset", C.c_uint32),
+        ("min_base_qual", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 class ExtendParams(C.Structure):
     _fields_ = [
         ("penalty", C.c_uint32),
@@ -336,10 +344,13 @@ _SIGNATURES = {
     "dcn_anchor_map_insertions_info": (C.c_int, [_vp, _u64p, _u64p]),
     "dcn_anchor_map_insertions_fetch": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _u64p, _u64p]),
     "dcn_anchor_map_insertions_call": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _u64p, _u64p]),
+    "dcn_anchor_map_pileup_keep_qualities": (C.c_int, [_vp, C.c_int]),
+    "dcn_pileup_batch_qual": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _u64p]),
+    "dcn_anchor_map_pileup_fetch_qualities": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
 }
 
 _lib = None
-ABI = (1, 17)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 18)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

@@ -929,6 +929,16 @@ class FastxReader {
         return true;
     }
 
+    // whether the input begins with a FASTA record, and then the first word of its header; nothing is consumed
+    bool begins_with_fasta(std::string *name) {
+        if (peek() != '>') return false;
+        const char *line = buf_.data() + pos_ + 1, *end = buf_.data() + end_;
+        size_t n = 0;
+        while (line + n < end && line[n] != '\n' && line[n] != '\r' && line[n] != ' ' && line[n] != '\t') ++n;
+        name->assign(line, n);
+        return true;
+    }
+
   private:
     void refill() {
         if (eof_) return;
@@ -3821,6 +3831,10 @@ struct MapArgs {
     // verify are set as well; -o is the FASTA, so there is no PAF
     bool consensus = false, fill_ref = false, has_fasta = false, has_variants = false;
     std::string fasta, variants;
+    // `call`: consensus with the reads' base qualities (dcn_pileup_batch_qual on a map that also keeps quality sums): a base
+    // below --min-baseq counts as N, --variants and --pileup gain the quality columns; consensus, extend and verify are set
+    bool call = false;
+    unsigned min_baseq = 20, qual_offset = 33;
 };
 
 // one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
@@ -3869,6 +3883,16 @@ void append_paf(std::string &rows, const std::string &read_name, uint32_t read_l
 
 int run_map(const MapArgs &a) {
     const Stopwatch watch;
+    const auto no_qualities = [](const std::string &name) {
+        die("call needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
+    };
+    std::unique_ptr<FastxReader> reads; // (`call` looks at the first record before the reference is loaded)
+    if (a.call) {
+        if (a.ref.empty()) die("the following required arguments were not provided: <REF>");
+        reads.reset(new FastxReader(a.input));
+        std::string name;
+        if (reads->begins_with_fasta(&name)) no_qualities(name);
+    }
     AnchorRef R;
     load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, 
                     a.align || a.pileup || a.extend ? "DCN_CLI_ALIGN_BATCH_BASES" : a.verify ? "DCN_CLI_VERIFY_BATCH_BASES" : "DCN_CLI_MAP_BATCH_BASES", a.quiet, a.verify);
@@ -3876,6 +3900,11 @@ int run_map(const MapArgs &a) {
     const bool piles = a.pileup || a.consensus || (a.extend && (a.has_pileup_out || a.has_sites)); // (the map's counters are used)
     if (piles) deacon::check(dcn_anchor_map_pileup_enable(R.map.p, 1)); // (after the records: a pileup does not grow)
     if (a.consensus) deacon::check(dcn_anchor_map_pileup_keep_insertions(R.map.p, 1)); // (before the first row adds)
+    if (a.call) deacon::check(dcn_anchor_map_pileup_keep_qualities(R.map.p, 1));
+    dcn_pileup_qual_params qprm = {};
+    qprm.qual_offset = a.qual_offset;
+    qprm.min_base_qual = a.min_baseq;
+    std::vector<uint8_t> quals; // (`call`: the quality lines of the batch, parallel to its bases)
     dcn_place_split_params prm = {};
     prm.band_bases = a.band;
     prm.min_votes = a.min_votes;
@@ -3884,7 +3913,8 @@ int run_map(const MapArgs &a) {
     TextOut out;
     const bool prints = !a.extend || a.has_output; // (`extend` prints PAF only when asked to)
     if (prints) out.open(a.output, true);
-    FastxReader rd(a.input);
+    if (!reads) reads.reset(new FastxReader(a.input));
+    FastxReader &rd = *reads;
     uint64_t reads_in = 0, placed = 0, split_reads = 0, placements = 0, mapq60 = 0, mapq0 = 0;
     uint64_t rows_extended = 0, bases_gained = 0, bases_clipped = 0, full_length_rows = 0; // (extend)
     dcn_extend_params xprm = {};
@@ -3956,8 +3986,18 @@ int run_map(const MapArgs &a) {
                 else p.record = UINT32_MAX;
             }
             uint64_t added = 0;
-            deacon::check(dcn_pileup_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), chosen.data(),
-                                           place_off[n_reads], into.data(), &added));
+            if (a.call) {
+                quals.resize(b.offsets.back());
+                for (uint32_t r = 0; r < n_reads; ++r) {
+                    const Rec &rec = b.recs[r];
+                    if (rec.qual_off == NO_QUAL) no_qualities(std::string(id_token(b, rec)));
+                    std::memcpy(quals.data() + b.offsets[r], b.chars() + rec.qual_off, rec.seq_len);
+                }
+                deacon::check(dcn_pileup_batch_qual(ctx.p, R.map.p, b.bases.data(), quals.data(), b.offsets.data(), n_reads, &vprm, &qprm,
+                                                    place_off.data(), chosen.data(), place_off[n_reads], into.data(), &added));
+            } else
+                deacon::check(dcn_pileup_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), chosen.data(),
+                                               place_off[n_reads], into.data(), &added));
             rows_added += added;
         } else if (a.verify && !a.align && !a.extend) {
             edits.resize(place_off[n_reads]);
@@ -4021,25 +4061,32 @@ int run_map(const MapArgs &a) {
     uint64_t covered = 0, n_sites = 0, column_sum[DCN_PILEUP_COLUMNS] = {};
     uint64_t insertion_events = 0, inserted_bases = 0, insertion_alleles = 0, substitutions = 0, deleted_positions = 0, consensus_bases = 0,
              uncalled_positions = 0; // (consensus)
+    uint64_t qual_sum[4] = {};       // (call)
     if (piles) {
         TextOut sites_out, pile_file, fasta_out, variants_out;
         if (a.has_sites) sites_out.open(a.sites, false);
         if (a.has_fasta) fasta_out.open(a.fasta, true);
         if (a.has_variants) variants_out.open(a.variants, false);
-        if (a.has_variants) variants_out.write("record\tpos\ttype\tref\talt\tdepth\tcount\tevents\n");
+        if (a.has_variants) variants_out.write(a.call ? "record\tpos\ttype\tref\talt\tdepth\tcount\tevents\tref_qual\talt_qual\n"
+                                                      : "record\tpos\ttype\tref\talt\tdepth\tcount\tevents\n");
         if (a.consensus) deacon::check(dcn_anchor_map_insertions_info(R.map.p, &insertion_events, &inserted_bases));
         std::vector<uint8_t> calls, allele_bases;
         std::vector<dcn_insertion_allele> alleles;
         std::string seq, variant_rows;
         if (a.extend && a.has_pileup_out) pile_file.open(a.pileup_out, false);
         TextOut *const tsv = a.pileup ? &out : a.has_pileup_out ? &pile_file : nullptr; // (`extend --sites` alone: no table)
-        if (tsv) tsv->write("record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\n");
+        if (tsv) tsv->write(a.call ? "record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\tqA\tqC\tqG\tqT\n" : "record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\n");
         if (a.has_sites) sites_out.write("record\tpos\tref\tcall\tdepth\tflags\n");
         dcn_pileup_call_params cprm = {};
         cprm.min_depth = a.min_depth;
         cprm.min_permille = a.min_frac;
         const uint64_t stretch = 1u << 20;
-        std::vector<uint32_t> counts, site_info;
+        std::vector<uint32_t> counts, site_info, qsums;
+        // (`call`) the mean quality of a column's bases at a position, rounded down; "." when it has none
+        const auto mean_qual = [](const uint32_t *c, const uint32_t *qs, int col) {
+            return col < 0 || c[col] == 0 ? std::string(".") : std::to_string(qs[col] / c[col]);
+        };
+        const auto base_column = [](char ch) { return ch == 'A' ? DCN_PILEUP_A : ch == 'C' ? DCN_PILEUP_C : ch == 'G' ? DCN_PILEUP_G : ch == 'T' ? DCN_PILEUP_T : -1; };
         std::vector<uint64_t> site_pos;
         std::vector<uint8_t> ref_text;
         std::string site_rows;
@@ -4051,6 +4098,11 @@ int run_map(const MapArgs &a) {
                 if (a.consensus) calls.resize(n);
                 ref_text.resize(n);
                 deacon::check(dcn_anchor_map_pileup_fetch(R.map.p, r, start, n, counts.data()));
+                if (a.call) {
+                    qsums.resize(n * 4);
+                    deacon::check(dcn_anchor_map_pileup_fetch_qualities(R.map.p, r, start, n, qsums.data()));
+                    for (uint64_t q = 0; q < n * 4; ++q) qual_sum[q & 3] += qsums[q];
+                }
                 deacon::check(dcn_anchor_map_fetch(R.map.p, r, start, n, ref_text.data()));
                 rows.clear();
                 for (uint64_t q = 0; q < n; ++q) {
@@ -4062,6 +4114,8 @@ int run_map(const MapArgs &a) {
                     if (!a.all_positions && depth == 0 && c[DCN_PILEUP_INS] == 0) continue;
                     rows += R.names[r] + '\t' + std::to_string(start + q) + '\t' + (char)ref_text[q];
                     for (int col = 0; col < DCN_PILEUP_COLUMNS; ++col) rows += '\t' + std::to_string(c[col]);
+                    if (a.call)
+                        for (int col = 0; col < 4; ++col) rows += '\t' + std::to_string(qsums[q * 4 + col]);
                     rows += '\n';
                 }
                 if (tsv) tsv->write(rows);
@@ -4104,7 +4158,7 @@ int run_map(const MapArgs &a) {
                             if (a.has_variants)
                                 variant_rows += R.names[r] + '\t' + std::to_string(start + q) + '\t' + (al->flags & DCN_INSERTION_FRONT ? "INS_FRONT" : "INS") +
                                                 "\t.\t" + alt + '\t' + std::to_string(depth) + '\t' + std::to_string(al->count) + '\t' +
-                                                std::to_string(al->events) + '\n';
+                                                std::to_string(al->events) + (a.call ? "\t.\t.\n" : "\n");
                         };
                         if (al && (al->flags & DCN_INSERTION_FRONT)) insertion();
                         const char call = (char)calls[q], ref = (char)ref_text[q];
@@ -4116,9 +4170,14 @@ int run_map(const MapArgs &a) {
                             if (call != '-') seq += call;
                             if (call == '-') ++deleted_positions;
                             else if (call != ref) ++substitutions;
-                            if (a.has_variants && call != ref)
+                            if (a.has_variants && call != ref) {
                                 variant_rows += R.names[r] + '\t' + std::to_string(start + q) + '\t' + (call == '-' ? "DEL" : "SUB") + '\t' + ref + '\t' + call +
-                                                '\t' + std::to_string(depth) + '\t' + std::to_string(best) + "\t0\n";
+                                                '\t' + std::to_string(depth) + '\t' + std::to_string(best) + "\t0";
+                                if (a.call && call == '-') variant_rows += "\t.\t.";
+                                else if (a.call)
+                                    variant_rows += '\t' + mean_qual(c, qsums.data() + q * 4, base_column(ref)) + '\t' + mean_qual(c, qsums.data() + q * 4, base_column(call));
+                                variant_rows += '\n';
+                            }
                         }
                         if (al && !(al->flags & DCN_INSERTION_FRONT)) insertion();
                     }
@@ -4212,6 +4271,10 @@ int run_map(const MapArgs &a) {
                     a.fill_ref ? "true" : "false", (unsigned long long)insertion_events, (unsigned long long)inserted_bases,
                     (unsigned long long)insertion_alleles, (unsigned long long)substitutions, (unsigned long long)deleted_positions,
                     (unsigned long long)consensus_bases, (unsigned long long)uncalled_positions);
+        if (a.call)
+            appendf(js, "  \"min_base_qual\": %u,\n  \"qual_offset\": %u,\n  \"quality_sums\": {\"A\": %llu, \"C\": %llu, \"G\": %llu, \"T\": %llu},\n",
+                    a.min_baseq, a.qual_offset, (unsigned long long)qual_sum[0], (unsigned long long)qual_sum[1], (unsigned long long)qual_sum[2],
+                    (unsigned long long)qual_sum[3]);
         appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
         for (uint32_t r = 0; r < R.n_records; ++r) {
             js += (r ? ",\n    {" : "\n    {");
@@ -4362,6 +4425,7 @@ void usage() {
                  "  pileup  As align, summed per reference position: counts of A C G T N, gaps and strand, and site calls, as TSV\n"
                  "  extend  As map, each placement carried over the flanks of its read, the rest soft-clipped; then align, pileup\n"
                  "  consensus  As extend and pileup, keeping inserted bases: the sequence the reads support as FASTA, and its variants\n"
+                 "  call    As consensus, with the reads' base qualities: low-quality bases do not vote, variants carry mean qualities\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -4745,6 +4809,74 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "and events say what it is.  The thresholds are conventions, not measured optima.  Integers and bytes only: the\n"
                "output does not depend on how the input is cut into batches.  Deleted positions are not merged, indels are not\n"
                "left-normalised.  VCF, base qualities and affine gaps are not built.  Mates are independent here: one input.\n";
+    else if (sub == "call")
+        text = "Pile the extended placements of FASTQ reads up on a reference with their base qualities: bases below a quality\n"
+               "threshold do not vote, and every variant says how good the bases for and against it were\n\n"
+               "Usage: deacon-hip call [OPTIONS] <REF> [READS]\n\n"
+               "Arguments:\n"
+               "  <REF>     Path to the reference fastx file: its records are numbered and named in file order\n"
+               "  [READS]   Optional path to FASTQ file (or - for stdin; gz, bgzf, zst, xz and bz2 found by content) [default: -]\n"
+               "            A record without a quality line (FASTA) is an error: consensus takes such reads\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Keys that may anchor: a minimizer index file, whose k and w are used\n"
+               "                                 [default: the minimizers of <REF> at -k / -w]\n"
+               "  -k <K>                         K-mer length without -x [default: 31]\n"
+               "  -w <W>                         Minimizer window size without -x [default: 15]\n"
+               "  -o, --output <OUTPUT>          FASTA: per record of <REF> a line >name and its consensus on one line (- for\n"
+               "                                 stdout) [default: no FASTA]\n"
+               "      --variants <FILE>          TSV: record pos type ref alt depth count events, pos 0-based as in PAF; one SUB line\n"
+               "                                 per substituted position, one DEL line per deleted position (alt -), one INS or\n"
+               "                                 INS_FRONT line per called insertion behind or in front of pos (ref ., count = the\n"
+               "                                 reads with exactly these bases, events = all insertions there; 0 on other lines)\n"
+               "                                 With two more columns, ref_qual alt_qual: on a SUB line the mean quality, rounded\n"
+               "                                 down, of the counted bases that show the reference's base and of those that show\n"
+               "                                 alt (. for none, or for a reference base that is not ACGT); . on every other line\n"
+               "      --fill-ref                 A position without a call takes the reference's base, not N\n"
+               "      --min-baseq <Q>            A base of quality below Q counts as N: it adds to the depth and never wins\n"
+               "                                 (0..255) [default: 20, a convention]\n"
+               "      --qual-offset <N>          The quality of a base is its quality character minus N, 0 when that is negative\n"
+               "                                 (0..255) [default: 33]\n"
+               "      --pileup <FILE>            pileup's TSV over the extended placements: record pos ref A C G T N del ins rev, then\n"
+               "                                 qA qC qG qT: the sums of the qualities of the bases counted in A C G T\n"
+               "      --sites <FILE>             pileup's site TSV over them: record pos ref call depth flags\n"
+               "      --all-positions            One line of --pileup for every position of every record\n"
+               "      --min-depth <N>            A call needs a depth of at least N [default: 3, a convention]\n"
+               "      --min-frac <N>             ... and N per 1000 of the depth for the most frequent of A C G T and gap, and\n"
+               "                                 for the insertions at a position (0..1000) [default: 500, a convention]\n"
+               "      --min-mapq <N>             Only placements of mapping quality N or more add (0..60) [default: 1, a convention]\n"
+               "      --all-ranks                Every placement of a read adds, not only its first (rank 0)\n"
+               "      --penalty <N>              An edit in a flank costs N matched bases of read plus record (2..255)\n"
+               "                                 [default: 6, a convention]\n"
+               "      --end-bonus <N>            Reaching the read's end is worth N (0..65535) [default: 4, a convention]\n"
+               "      --ext-max-edits <N>        At most N edits per flank (0..1023) [default: 1023, a convention]\n"
+               "  -e, --max-edits <N>            Only placements of at most N edits over the extended extents add (0..1023)\n"
+               "                                 [default: 1023, a convention]\n"
+               "      --max-div <N>              ... and of at most N per 1000 bases of the longer extended extent (0..1000)\n"
+               "                                 [default: 200, a convention]\n"
+               "  -N, --max-placements <N>       Placements per read, each from the anchor hits no earlier one explained (1..8)\n"
+               "                                 [default: 4]\n"
+               "      --band <N>                 Width of a diagonal band in bases [default: 256, a convention]\n"
+               "  -a, --min-votes <N>            Minimum number of anchor hits in a placement's cell [default: 2, as filter's -a,\n"
+               "                                 a convention]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per read (0 = entire read) [default: 0]\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file: extend's and pileup's keys, and fill_ref,\n"
+               "                                 insertion_events, inserted_bases, insertion_alleles, substitutions,\n"
+               "                                 deleted_positions, consensus_bases and uncalled_positions; min_base_qual,\n"
+               "                                 qual_offset and quality_sums, the totals of qA qC qG qT\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
+               "  -h, --help                     Print help\n\n"
+               "Consensus, position by position of a record: the bases of an insertion called in front of the position; the\n"
+               "called base, nothing where a gap is called, N (or the reference's base with --fill-ref) where nothing is; the\n"
+               "bases of an insertion called behind it.  An insertion is called where the reads with an insertion there reach\n"
+               "--min-frac of a depth of at least --min-depth; its bases are those most of them agree on (on a tie one behind\n"
+               "the position before one in front, then the shorter, then the first by letter), whatever their own share: count\n"
+               "and events say what it is.  The thresholds are conventions, not measured optima.  Integers and bytes only: the\n"
+               "output does not depend on how the input is cut into batches.  Deleted positions are not merged, indels are not\n"
+               "left-normalised.  Qualities: alignment does not look at them, so the placements and their edits are consensus's;\n"
+               "only what a base counts as changes.  With --min-baseq 0 the FASTA is consensus's.  The qualities of inserted bases\n"
+               "are not looked at.  No quality-weighted calls or likelihoods, no VCF, no affine gaps.  Mates are independent\n"
+               "here: one input.\n";
     else if (sub == "map-pairs")
         text = "Place the two mates of each pair jointly on a reference: proper pairs, rescued mates and insert sizes, as PAF\n\n"
                "Usage: deacon-hip map-pairs [OPTIONS] <REF> <READS1> [READS2]\n\n"
@@ -5035,11 +5167,13 @@ int main(int argc, char **argv) {
             if (pos.size() > 2) die("place takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[2] + "')");
             return run_place(a);
         }
-        if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup" || args[0] == "extend" || args[0] == "consensus") {
+        if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup" || args[0] == "extend" || args[0] == "consensus" ||
+            args[0] == "call") {
             MapArgs a;
             a.align = args[0] == "align";
             a.pileup = args[0] == "pileup";
-            a.consensus = args[0] == "consensus";
+            a.call = args[0] == "call";
+            a.consensus = args[0] == "consensus" || a.call;
             a.extend = args[0] == "extend" || a.consensus;
             a.verify = a.align || a.pileup || a.extend || args[0] == "verify";
             std::vector<std::string> pos;
@@ -5058,6 +5192,8 @@ int main(int argc, char **argv) {
                 else if (a.consensus && (s == "-o" || s == "--output")) a.fasta = need(++i), a.has_fasta = true; // (the FASTA: there is no PAF)
                 else if (a.consensus && s == "--variants") a.variants = need(++i), a.has_variants = true;
                 else if (a.consensus && s == "--fill-ref") a.fill_ref = true;
+                else if (a.call && s == "--min-baseq") a.min_baseq = (unsigned)number(need(++i), "--min-baseq", 0, 255);
+                else if (a.call && s == "--qual-offset") a.qual_offset = (unsigned)number(need(++i), "--qual-offset", 0, 255);
                 else if (s == "-o" || s == "--output") a.output = need(++i), a.has_output = true;
                 else if (a.extend && s == "--penalty") a.penalty = (unsigned)number(need(++i), "--penalty", 2, 255);
                 else if (a.extend && s == "--end-bonus") a.end_bonus = (unsigned)number(need(++i), "--end-bonus", 0, 65535);

@@ -197,6 +197,9 @@ struct dcn_ctx {
     dcn_extend_item *d_ext_items = nullptr;
     dcn_extend_result *d_ext_out = nullptr;
     uint64_t ext_items_cap = 0, ext_out_cap = 0;
+    // quality buffer (lazy, first dcn_pileup_batch_qual): one byte per base, grown to the largest such batch
+    uint8_t *d_pile_quals = nullptr;
+    uint64_t pile_quals_cap = 0;
     // deferred state of the last enqueued device-API batch
     bool batch_pending = false;
     bool lean = false; // a small host batch is being submitted: copies and result copies go on `stream` itself (submit_impl)

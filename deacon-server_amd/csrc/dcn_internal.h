@@ -124,6 +124,9 @@ struct dcn_index {
     // (dcn_anchor_map_pileup_keep_insertions, insertions_api.hip).  Null: none is kept.
     uint64_t pileup_rows = 0;
     dcn_ins_ledger *ledger = nullptr;
+    // ... and the quality sums beside the counters (dcn_anchor_map_pileup_keep_qualities, pileup_api.hip): 4 words per base
+    // of the pileup, laid out by dcn_pile_sum_index (dcn_pileup.h).  Null: none are kept.
+    uint32_t *d_pileup_qsums = nullptr;
     dcn_table_view view() const {
         dcn_table_view v;
         v.slots = d_slots;

@@ -1,7 +1,7 @@
 // dcn_pileup.h -- what the host and the device share of a pileup (THE DEFINITION OF A PILEUP, include/deacon_hip.h): where a
-// counter lies, how far a run moves on S and on T, the adds of one run, and the call of one position (kernels in
-// pileup.hip, the C ABI in pileup_api.hip).  Plain integer arithmetic: compiles for the host as well
-// (tests/cpp/pileup_walk_test.cpp), as dcn_align.h does.
+// counter lies, how far a run moves on S and on T, the adds of one run, the same with base qualities (THE DEFINITION OF A
+// QUALITY-AWARE PILEUP), and the call of one position (kernels in pileup.hip, the C ABI in pileup_api.hip).  Plain integer
+// arithmetic: compiles for the host as well (tests/cpp/pileup_walk_test.cpp, pileup_qual_walk_test.cpp), as dcn_align.h does.
 #pragma once
 
 #include <stdint.h>
@@ -51,6 +51,57 @@ DCN_PILE_FN void dcn_pile_run(uint32_t run, uint32_t i, uint32_t j, uint32_t rev
     }
     for (uint32_t q = lane; q < len; q += lanes) {
         add(op == DCN_ALN_D ? DCN_PILE_DEL : column_of(i + q), j + q);
+        if (reverse) add(DCN_PILE_REV, j + q);
+    }
+}
+
+// ---- rules Q2 - Q4: base qualities (THE DEFINITION OF A QUALITY-AWARE PILEUP) -------------------------------------------
+constexpr uint32_t DCN_PILE_SUM_COLUMNS = 4; // QA QC QG QT
+
+// rule Q2: the quality of a byte of the quality array; a byte below the offset is quality 0
+DCN_PILE_FN uint32_t dcn_pile_quality(uint32_t byte, uint32_t qual_offset) { return byte >= qual_offset ? byte - qual_offset : 0u; }
+
+// rule Q2: where in the batch the quality of S[i] lies.  s_origin is the row's (dcn_verify_item): the first base of the read
+// interval, or its end on a reverse row, where S[i] is the complement of the base at s_origin - 1 - i.
+DCN_PILE_FN int64_t dcn_pile_qual_pos(int64_t s_origin, uint32_t reverse, uint32_t i) {
+    return reverse ? s_origin - 1 - (int64_t)i : s_origin + (int64_t)i;
+}
+
+// rule Q3: a base column under the threshold counts as N; N stays N
+DCN_PILE_FN uint32_t dcn_pile_qual_column(uint32_t column, uint32_t q, uint32_t min_base_qual) {
+    return column <= DCN_PILE_T && q < min_base_qual ? DCN_PILE_N : column;
+}
+
+// Where sum (column, base) lies among the 4 * bases words of a map's quality sums: four planes, as the counters'; four
+// words per position under -DDCN_PILEUP_POSITION_MAJOR.
+DCN_PILE_FN uint64_t dcn_pile_sum_index(uint32_t column, uint64_t base, uint64_t bases) {
+#if defined(DCN_PILEUP_POSITION_MAJOR)
+    (void)bases;
+    return base * DCN_PILE_SUM_COLUMNS + column;
+#else
+    return (uint64_t)column * bases + base;
+#endif
+}
+
+// Rules Q3 and Q4 for one run: dcn_pile_run with the quality of every '=' / X base looked at.  quality_of(i) is q(S[i]);
+// add_sum(column, j, q) adds q to the sum of a base column at base j of T.  I and D runs are dcn_pile_run's.
+template <typename ColumnOf, typename QualityOf, typename Add, typename AddSum>
+DCN_PILE_FN void dcn_pile_run_qual(uint32_t run, uint32_t i, uint32_t j, uint32_t reverse, uint32_t min_base_qual, uint32_t lane, uint32_t lanes,
+                                   ColumnOf column_of, QualityOf quality_of, Add add, AddSum add_sum) {
+    const uint32_t op = run & 15u, len = run >> 4;
+    if (op == DCN_ALN_I) {
+        if (lane == 0) add(DCN_PILE_INS, j > 0 ? j - 1 : 0u);
+        return;
+    }
+    for (uint32_t q = lane; q < len; q += lanes) {
+        if (op == DCN_ALN_D) {
+            add(DCN_PILE_DEL, j + q);
+        } else {
+            const uint32_t quality = quality_of(i + q);
+            const uint32_t column = dcn_pile_qual_column(column_of(i + q), quality, min_base_qual);
+            add(column, j + q);
+            if (column <= DCN_PILE_T) add_sum(column, j + q, quality);
+        }
         if (reverse) add(DCN_PILE_REV, j + q);
     }
 }

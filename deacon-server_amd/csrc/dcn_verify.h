@@ -207,6 +207,15 @@ struct dcn_pileup_args {
 };
 int dcn_launch_pileup(const dcn_pileup_args &args, hipStream_t stream);
 
+// the same walk with base qualities (dcn_pileup_batch_qual): rules Q2 - Q4
+struct dcn_pileup_qual_args {
+    dcn_pileup_args rows;
+    const uint8_t *quals; // one byte per base of the batch, parallel to the stream behind s_packed
+    uint32_t *sums;       // the map's quality sums: dcn_pile_sum_index(column, store base, rows.bases); null: none are kept
+    uint32_t qual_offset, min_base_qual;
+};
+int dcn_launch_pileup_qual(const dcn_pileup_qual_args &args, hipStream_t stream);
+
 struct dcn_pileup_call_args {
     const uint32_t *counters;
     uint64_t bases;

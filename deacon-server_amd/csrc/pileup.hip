@@ -1,9 +1,13 @@
-// pileup.hip -- the per-base counts of aligned rows and the calls over them (THE DEFINITION OF A PILEUP,
-// include/deacon_hip.h; what the host shares is in dcn_pileup.h).
+// pileup.hip -- the per-base counts of aligned rows and the calls over them (THE DEFINITION OF A PILEUP and THE DEFINITION
+// OF A QUALITY-AWARE PILEUP, include/deacon_hip.h; what the host shares is in dcn_pileup.h).
 //   pileup_kernel        one wave per aligned row, over align's work list.  The row's runs in chunks of 64: lane r loads
 //                        run r and its steps on S and T, a wave prefix sum gives each run its (i, j); then, run by run,
 //                        the lanes stride over the run's bases, read S[i] (dcn_wavefront.h, with the strand flag) and
 //                        add 1 with atomicAdd on uint32_t.  A row with n = 0 adds nothing.
+//                        <true> (dcn_pileup_batch_qual) also loads the byte of S[i]'s quality from the staged qualities:
+//                        the lanes of a run read consecutive bytes, ascending on a forward row and descending on a reverse
+//                        one.  A base column under the threshold becomes N (rule Q3), and on a map that keeps sums a second
+//                        atomicAdd adds the quality to the column's sum (rule Q4).  <false> is the kernel it was.
 //   pileup_call_kernel   one thread per position of a range: rule P6.  <false> writes the call characters and the
 //                        workgroup's number of sites; <true>, behind the scan of those numbers, writes the sites compactly
 //                        in ascending position.  Both passes decide in the same code.
@@ -14,12 +18,18 @@
 #include "dcn_wavefront.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
 constexpr uint32_t PILE_THREADS = 256; // four waves, a row each
 
-__global__ __launch_bounds__(PILE_THREADS) void pileup_kernel(dcn_pileup_args a) {
+__device__ inline const dcn_pileup_args &rows_of(const dcn_pileup_args &a) { return a; }
+__device__ inline const dcn_pileup_args &rows_of(const dcn_pileup_qual_args &a) { return a.rows; }
+
+template <bool QUAL>
+__global__ __launch_bounds__(PILE_THREADS) void pileup_kernel(std::conditional_t<QUAL, dcn_pileup_qual_args, dcn_pileup_args> args) {
+    const dcn_pileup_args &a = rows_of(args);
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t waves = (uint64_t)gridDim.x * (PILE_THREADS / 64);
     for (uint64_t w = (uint64_t)blockIdx.x * (PILE_THREADS / 64) + threadIdx.x / 64; w < a.n_work; w += waves) {
@@ -42,6 +52,19 @@ __global__ __launch_bounds__(PILE_THREADS) void pileup_kernel(dcn_pileup_args a)
         const auto add = [&](uint32_t column, uint32_t j) {
             if (j < n) atomicAdd(counters + dcn_pile_index(column, t0 + j, bases), 1u); // (always: '=', X and D cover exactly n)
         };
+        const auto quality_of = [&](uint32_t i) -> uint32_t { // rule Q2: the byte at the base's batch position
+            if constexpr (QUAL) {
+                if (i >= m) return 0u; // (never, as above: nothing outside the read interval is loaded)
+                return dcn_pile_quality(args.quals[dcn_pile_qual_pos(it.s_origin, reverse, i)], args.qual_offset);
+            } else {
+                return 0u;
+            }
+        };
+        const auto add_sum = [&](uint32_t column, uint32_t j, uint32_t q) { // rule Q4
+            if constexpr (QUAL) {
+                if (args.sums && j < n) atomicAdd(args.sums + dcn_pile_sum_index(column, t0 + j, bases), q);
+            }
+        };
         uint32_t i0 = 0, j0 = 0; // where the chunk begins
         for (uint32_t c0 = 0; c0 < count; c0 += 64) {
             const uint32_t here = min(64u, count - c0);
@@ -52,8 +75,13 @@ __global__ __launch_bounds__(PILE_THREADS) void pileup_kernel(dcn_pileup_args a)
                 if (lane >= d) si += oi, sj += oj;
             }
             const uint32_t my_i = i0 + si - dcn_pile_step_s(run), my_j = j0 + sj - dcn_pile_step_t(run);
-            for (uint32_t r = 0; r < here; ++r)
-                dcn_pile_run(__shfl(run, r), __shfl(my_i, r), __shfl(my_j, r), reverse, lane, 64u, column_of, add);
+            for (uint32_t r = 0; r < here; ++r) {
+                if constexpr (QUAL)
+                    dcn_pile_run_qual(__shfl(run, r), __shfl(my_i, r), __shfl(my_j, r), reverse, args.min_base_qual, lane, 64u, column_of,
+                                      quality_of, add, add_sum);
+                else
+                    dcn_pile_run(__shfl(run, r), __shfl(my_i, r), __shfl(my_j, r), reverse, lane, 64u, column_of, add);
+            }
             i0 += __shfl(si, 63);
             j0 += __shfl(sj, 63);
         }
@@ -91,13 +119,23 @@ __global__ __launch_bounds__(CALL_THREADS) void pileup_call_kernel(dcn_pileup_ca
     }
 }
 
+// the grid of both forms of pileup_kernel
+uint32_t pileup_blocks(uint64_t n_work) {
+    const uint64_t per_block = PILE_THREADS / 64;
+    return (uint32_t)std::min<uint64_t>((n_work + per_block - 1) / per_block, (uint64_t)dcn_cu_count() * 32);
+}
 } // namespace
 
 int dcn_launch_pileup(const dcn_pileup_args &args, hipStream_t stream) {
     if (args.n_work == 0) return DCN_OK;
-    const uint64_t per_block = PILE_THREADS / 64;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((args.n_work + per_block - 1) / per_block, (uint64_t)dcn_cu_count() * 32);
-    hipLaunchKernelGGL(pileup_kernel, dim3(blocks), dim3(PILE_THREADS), 0, stream, args);
+    hipLaunchKernelGGL(pileup_kernel<false>, dim3(pileup_blocks(args.n_work)), dim3(PILE_THREADS), 0, stream, args);
+    DCN_HIP(hipGetLastError());
+    return DCN_OK;
+}
+
+int dcn_launch_pileup_qual(const dcn_pileup_qual_args &args, hipStream_t stream) {
+    if (args.rows.n_work == 0) return DCN_OK;
+    hipLaunchKernelGGL(pileup_kernel<true>, dim3(pileup_blocks(args.rows.n_work)), dim3(PILE_THREADS), 0, stream, args);
     DCN_HIP(hipGetLastError());
     return DCN_OK;
 }

@@ -1,7 +1,9 @@
-// pileup_api.hip -- the C ABI of pileups (dcn_anchor_map_pileup_enable / _reset / _fetch / _call, dcn_pileup_batch;
+// pileup_api.hip -- the C ABI of pileups (dcn_anchor_map_pileup_enable / _reset / _fetch / _call, dcn_pileup_batch, and with
+// base qualities dcn_anchor_map_pileup_keep_qualities / _fetch_qualities, dcn_pileup_batch_qual;
 // kernels in pileup.hip, the shared arithmetic in dcn_pileup.h; a kept insertion ledger, insertions_api.hip, is appended
 // to, emptied and freed here).  dcn_pileup_batch is dcn_align_batch's sequence
-// (verify_api.hip's walk, align_api.hip's passes and gather) with the runs left on the device and the pileup kernel behind.
+// (verify_api.hip's walk, align_api.hip's passes and gather) with the runs left on the device and the pileup kernel behind;
+// dcn_pileup_batch_qual is the same sequence with the qualities staged in front of the kernel's quality form.
 #include "dcn_ctx.h"
 #include "dcn_dump_sweep.h"
 #include "dcn_pileup.h"
@@ -12,6 +14,7 @@
 using namespace dcn_impl;
 
 static_assert(sizeof(dcn_pileup_call_params) == 16, "pileup call params are ABI");
+static_assert(sizeof(dcn_pileup_qual_params) == 16, "pileup quality params are ABI");
 static_assert(DCN_PILEUP_A == DCN_PILE_A && DCN_PILEUP_C == DCN_PILE_C && DCN_PILEUP_G == DCN_PILE_G && DCN_PILEUP_T == DCN_PILE_T &&
                   DCN_PILEUP_N == DCN_PILE_N && DCN_PILEUP_DEL == DCN_PILE_DEL && DCN_PILEUP_INS == DCN_PILE_INS &&
                   DCN_PILEUP_REV == DCN_PILE_REV && DCN_PILEUP_COLUMNS == DCN_PILE_COLUMNS,
@@ -24,6 +27,12 @@ namespace {
 int check_pileup(const dcn_index *map) {
     DCN_TRY(check_store(map));
     if (!map->d_pileup) return dcn_fail(DCN_ERR_ARG, "the map has no pileup (dcn_anchor_map_pileup_enable)");
+    return DCN_OK;
+}
+
+int check_qsums(const dcn_index *map) {
+    DCN_TRY(check_pileup(map));
+    if (!map->d_pileup_qsums) return dcn_fail(DCN_ERR_ARG, "the map keeps no quality sums (dcn_anchor_map_pileup_keep_qualities)");
     return DCN_OK;
 }
 
@@ -50,8 +59,10 @@ extern "C" int dcn_anchor_map_pileup_enable(dcn_index *map, int enable) {
             DCN_HIP(hipSetDevice(map->device));
             hipFree(map->d_pileup);
             dcn_ins_ledger_free(map->ledger);
+            if (map->d_pileup_qsums) hipFree(map->d_pileup_qsums);
         }
         map->d_pileup = nullptr;
+        map->d_pileup_qsums = nullptr;
         map->pileup_bases = 0;
         map->pileup_rows = 0;
         map->ledger = nullptr;
@@ -70,23 +81,36 @@ extern "C" int dcn_anchor_map_pileup_reset(dcn_index *map) {
     DCN_TRY(check_pileup(map));
     DCN_HIP(hipSetDevice(map->device));
     DCN_HIP(hipMemset(map->d_pileup, 0, map->pileup_bases * DCN_PILE_COLUMNS * sizeof(uint32_t)));
+    if (map->d_pileup_qsums) DCN_HIP(hipMemset(map->d_pileup_qsums, 0, map->pileup_bases * DCN_PILE_SUM_COLUMNS * sizeof(uint32_t)));
     DCN_HIP(hipDeviceSynchronize()); // (null-stream work must not be overtaken by a context's stream)
     map->pileup_rows = 0;
     if (map->ledger) map->ledger->n_events = map->ledger->n_bases = 0; // (the arrays stay: the next append begins at their start)
     return DCN_OK;
 }
 
-extern "C" int dcn_pileup_batch(dcn_ctx *ctx, dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
-                                const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits,
-                                uint64_t *n_added) {
-    dcn_verify_plan plan;
-    DCN_TRY(dcn_verify_walk(ctx, map, bases, offsets, n_reads, params, row_offsets, rows, n_rows, edits, &plan));
-    if (!map->d_pileup) return dcn_fail(DCN_ERR_ARG, "the map has no pileup (dcn_anchor_map_pileup_enable)");
-    if (n_added) *n_added = 0;
-    if (plan.items.empty()) return DCN_OK;
-    DCN_TRY(dcn_align_check_rows(plan));
+extern "C" int dcn_anchor_map_pileup_keep_qualities(dcn_index *map, int keep) {
+    DCN_TRY(check_pileup(map));
+    if (!keep) {
+        if (map->d_pileup_qsums) {
+            DCN_HIP(hipSetDevice(map->device));
+            hipFree(map->d_pileup_qsums);
+        }
+        map->d_pileup_qsums = nullptr;
+        return DCN_OK;
+    }
+    if (map->d_pileup_qsums) return DCN_OK;
+    if (map->pileup_rows != 0) // rule Q1
+        return dcn_fail(DCN_ERR_ARG, std::to_string(map->pileup_rows) + " rows have added to the pileup since it was enabled or reset: the sums "
+                                                                         "begin with the counters (dcn_anchor_map_pileup_reset first)");
+    DCN_HIP(hipSetDevice(map->device));
+    return dev_alloc_zeroed(&map->d_pileup_qsums, map->pileup_bases * DCN_PILE_SUM_COLUMNS, "pileup quality sums");
+}
 
-    dcn_ctx *c = ctx;
+namespace {
+// What dcn_pileup_batch and dcn_pileup_batch_qual run behind their checks.  qprm = null: the plain call.
+int pileup_run(dcn_ctx *c, dcn_index *map, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint32_t n_reads,
+               const dcn_verify_plan &plan, const dcn_pileup_qual_params *qprm, uint32_t *edits, uint64_t *n_added) {
+    const uint64_t n_rows = plan.items.size();
     hipStream_t st = c->stream;
     int prof_slot = -1;
     uint64_t n_work = 0, total = 0;
@@ -106,16 +130,65 @@ extern "C" int dcn_pileup_batch(dcn_ctx *ctx, dcn_index *map, const uint8_t *bas
         pa.cigar = c->d_aln_cigar;
         pa.counters = map->d_pileup;
         pa.bases = map->pileup_bases;
-        DCN_TRY(dcn_launch_pileup(pa, st));
+        if (qprm) { // the qualities, a byte per base, in front of the kernel on the context's stream
+            DCN_TRY(grow(&c->d_pile_quals, &c->pile_quals_cap, plan.n_bases, "pileup qualities"));
+            DCN_TRY(staged_h2d(c, c->d_pile_quals, quals, plan.n_bases));
+            DCN_TRY(stage_done(c));
+            dcn_pileup_qual_args qa;
+            memset(&qa, 0, sizeof(qa));
+            qa.rows = pa;
+            qa.quals = c->d_pile_quals;
+            qa.sums = map->d_pileup_qsums;
+            qa.qual_offset = qprm->qual_offset;
+            qa.min_base_qual = qprm->min_base_qual;
+            DCN_TRY(dcn_launch_pileup_qual(qa, st));
+        } else {
+            DCN_TRY(dcn_launch_pileup(pa, st));
+        }
         if (map->ledger) DCN_TRY(dcn_insertions_append(c, map, pa)); // rule L2, behind the same checks
     }
     DCN_PROF_MARK(DCN_STAGE_FINISH);
     DCN_TRY(finish_run(c, prof_slot));
     uint64_t added = 0; // rule P2: the rows with an alignment and n > 0
     for (uint64_t row = 0; row < n_rows; ++row) added += edits[row] < DCN_VERIFY_OVER && plan.items[row].n > 0;
-    map->pileup_rows += added; // (rule L1 asks)
+    map->pileup_rows += added; // (rules L1 and Q1 ask)
     if (n_added) *n_added = added;
     return DCN_OK;
+}
+} // namespace
+
+extern "C" int dcn_pileup_batch(dcn_ctx *ctx, dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                                const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits,
+                                uint64_t *n_added) {
+    dcn_verify_plan plan;
+    DCN_TRY(dcn_verify_walk(ctx, map, bases, offsets, n_reads, params, row_offsets, rows, n_rows, edits, &plan));
+    if (!map->d_pileup) return dcn_fail(DCN_ERR_ARG, "the map has no pileup (dcn_anchor_map_pileup_enable)");
+    if (map->d_pileup_qsums) // rule Q1: sums and counters describe the same rows
+        return dcn_fail(DCN_ERR_ARG, "the map keeps quality sums, and these rows have no qualities: dcn_pileup_batch_qual adds to it "
+                                     "(or dcn_anchor_map_pileup_keep_qualities(map, 0) first)");
+    if (n_added) *n_added = 0;
+    if (plan.items.empty()) return DCN_OK;
+    DCN_TRY(dcn_align_check_rows(plan));
+    return pileup_run(ctx, map, bases, nullptr, offsets, n_reads, plan, nullptr, edits, n_added);
+}
+
+extern "C" int dcn_pileup_batch_qual(dcn_ctx *ctx, dcn_index *map, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets,
+                                     uint32_t n_reads, const void *params, const void *qual_params, const uint64_t *row_offsets,
+                                     const void *rows, uint64_t n_rows, uint32_t *edits, uint64_t *n_added) {
+    dcn_verify_plan plan;
+    DCN_TRY(dcn_verify_walk(ctx, map, bases, offsets, n_reads, params, row_offsets, rows, n_rows, edits, &plan));
+    if (!map->d_pileup) return dcn_fail(DCN_ERR_ARG, "the map has no pileup (dcn_anchor_map_pileup_enable)");
+    if (!plan.items.empty()) DCN_TRY(dcn_align_check_rows(plan));
+    // (dcn_pileup_batch's checks end here)
+    const dcn_pileup_qual_params *qprm = static_cast<const dcn_pileup_qual_params *>(qual_params);
+    if (!qprm) return dcn_fail(DCN_ERR_ARG, "qual_params is NULL");
+    if (qprm->reserved[0] != 0 || qprm->reserved[1] != 0) return dcn_fail(DCN_ERR_ARG, "qual_params.reserved must be 0");
+    if (qprm->qual_offset > 255) return dcn_fail(DCN_ERR_ARG, "qual_params.qual_offset must be 0..255");
+    if (qprm->min_base_qual > 255) return dcn_fail(DCN_ERR_ARG, "qual_params.min_base_qual must be 0..255");
+    if (!plan.items.empty() && plan.n_bases > 0 && !quals) return dcn_fail(DCN_ERR_ARG, "quals is NULL");
+    if (n_added) *n_added = 0;
+    if (plan.items.empty()) return DCN_OK;
+    return pileup_run(ctx, map, bases, quals, offsets, n_reads, plan, qprm, edits, n_added);
 }
 
 extern "C" int dcn_anchor_map_pileup_fetch(const dcn_index *map, uint32_t record, uint64_t start, uint64_t n_bases, uint32_t *counts) {
@@ -133,6 +206,26 @@ extern "C" int dcn_anchor_map_pileup_fetch(const dcn_index *map, uint32_t record
         DCN_HIP(hipMemcpy(plane.data(), map->d_pileup + dcn_pile_index(col, b0, map->pileup_bases), n_bases * sizeof(uint32_t),
                           hipMemcpyDeviceToHost));
         for (uint64_t q = 0; q < n_bases; ++q) counts[q * DCN_PILE_COLUMNS + col] = plane[q];
+    }
+#endif
+    return DCN_OK;
+}
+
+extern "C" int dcn_anchor_map_pileup_fetch_qualities(const dcn_index *map, uint32_t record, uint64_t start, uint64_t n_bases, uint32_t *sums) {
+    DCN_TRY(check_qsums(map));
+    uint64_t b0 = 0;
+    DCN_TRY(check_range(map, "pileup fetch", record, start, n_bases, &b0));
+    if (n_bases == 0) return DCN_OK;
+    if (!sums) return dcn_fail(DCN_ERR_ARG, "sums is NULL");
+    DCN_HIP(hipSetDevice(map->device));
+#if defined(DCN_PILEUP_POSITION_MAJOR)
+    DCN_HIP(hipMemcpy(sums, map->d_pileup_qsums + b0 * DCN_PILE_SUM_COLUMNS, n_bases * DCN_PILE_SUM_COLUMNS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+#else
+    std::vector<uint32_t> plane(n_bases); // (as dcn_anchor_map_pileup_fetch: a plane at a time, transposed here)
+    for (uint32_t col = 0; col < DCN_PILE_SUM_COLUMNS; ++col) {
+        DCN_HIP(hipMemcpy(plane.data(), map->d_pileup_qsums + dcn_pile_sum_index(col, b0, map->pileup_bases), n_bases * sizeof(uint32_t),
+                          hipMemcpyDeviceToHost));
+        for (uint64_t q = 0; q < n_bases; ++q) sums[q * DCN_PILE_SUM_COLUMNS + col] = plane[q];
     }
 #endif
     return DCN_OK;

@@ -766,6 +766,22 @@ class AnchorMap(Index):
         Refused once a row has added since pileup_enable() or pileup_reset(); keep=False drops it and leaves the counters."""
         N.check(N.lib().dcn_anchor_map_pileup_keep_insertions(self._h, 1 if keep else 0))
 
+    def pileup_keep_qualities(self, keep=True):
+        """Quality sums beside the pileup (dcn_anchor_map_pileup_keep_qualities; the definition of a quality-aware pileup is
+        in include/deacon_hip.h): four uint32 per base, to which Placer.pileup_batch(..., quals=) adds the quality of every
+        base it counts in A, C, G or T.  16 B of device memory per kept base.  Refused once a row has added since
+        pileup_enable() or pileup_reset(); while they are kept pileup_batch needs quals.  keep=False frees them and leaves the
+        counters."""
+        N.check(N.lib().dcn_anchor_map_pileup_keep_qualities(self._h, 1 if keep else 0))
+
+    def pileup_fetch_qualities(self, record, start=0, n=None):
+        """the quality sums of positions [start, start + n) of a record (n=None: to its end) -> np.uint32[n, 4], the columns
+        PILEUP_A, C, G, T"""
+        start, n = int(start), self._to_end(record, start) if n is None else int(n)
+        out = np.zeros((max(n, 1), 4), np.uint32)
+        N.check(N.lib().dcn_anchor_map_pileup_fetch_qualities(self._h, int(record), start, n, _ptr(out)))
+        return out[:n]
+
     def insertions_info(self):
         """-> (events of the ledger, the sum of their lengths)"""
         n_events, n_bases = C.c_uint64(), C.c_uint64()
@@ -1016,17 +1032,29 @@ class Placer(_Context):
         N.check(rc)
         return edits[:n_rows], cigar_offsets, cigar[:int(cigar_offsets[n_rows])]
 
-    def pileup_batch(self, bases, offsets, rows, row_offsets=None, max_edits=1023, max_permille=200, select=None):
+    def pileup_batch(self, bases, offsets, rows, row_offsets=None, max_edits=1023, max_permille=200, select=None, quals=None,
+                     min_base_qual=0, qual_offset=33):
         """align_batch's rows added to the anchor map's pileup (dcn_pileup_batch; the definition of a pileup is in
         include/deacon_hip.h): every row with an alignment adds one count per base of its record interval, in the column
         of the read's base there or in DEL, one in INS per inserted run, and REV beside each on the reverse strand.  The
         runs never leave the device.  select: an optional boolean mask over the rows; a row it leaves out is given as
         unplaced, in a copy (the caller's rows are not written).  -> (edits np.uint32[n_rows] as verify_batch returns
         them for the rows given, n_added).  The map needs AnchorMap.pileup_enable() first.  profile(): pack in its slot,
-        everything else in 'finish'."""
+        everything else in 'finish'.
+        quals: the base qualities, a uint8 array or bytes with one byte per base of the batch (dcn_pileup_batch_qual; the
+        definition of a quality-aware pileup is in include/deacon_hip.h).  A base of quality byte - qual_offset below
+        min_base_qual counts in N instead of its column, and a map with AnchorMap.pileup_keep_qualities() also sums the
+        qualities of the counted bases.  What aligns does not change.  quals=None: the call without qualities, whatever
+        min_base_qual and qual_offset say."""
         bases, offsets, n_reads = _batch(bases, offsets)
         rows = np.ascontiguousarray(rows)
         n_rows = len(rows)
+        if quals is not None:
+            if isinstance(quals, (bytes, bytearray, memoryview)):
+                quals = np.frombuffer(quals, np.uint8)
+            if not isinstance(quals, np.ndarray) or quals.dtype != np.uint8 or quals.shape != (len(bases),):
+                raise ValueError("pileup_batch: quals must be uint8 or bytes with one byte per base of the batch")
+            quals = np.ascontiguousarray(quals)
         if select is not None:
             select = np.asarray(select, bool)
             if select.shape != (n_rows,):
@@ -1038,6 +1066,12 @@ class Placer(_Context):
         edits = np.zeros(max(n_rows, 1), np.uint32)
         n_added = C.c_uint64()
         p = N.VerifyParams(int(max_edits), int(max_permille), rows.dtype.itemsize, 0)
+        if quals is not None:
+            qp = N.PileupQualParams(int(qual_offset), int(min_base_qual), (C.c_uint32 * 2)(0, 0))
+            N.check(N.lib().dcn_pileup_batch_qual(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None,
+                                                  _ptr(quals) if len(quals) else None, _ptr(offsets), n_reads, C.byref(p), C.byref(qp),
+                                                  _ptr(row_offsets), _ptr(rows) if n_rows else None, n_rows, _ptr(edits), C.byref(n_added)))
+            return edits[:n_rows], int(n_added.value)
         N.check(N.lib().dcn_pileup_batch(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None, _ptr(offsets), n_reads,
                                          C.byref(p), _ptr(row_offsets), _ptr(rows) if n_rows else None, n_rows, _ptr(edits),
                                          C.byref(n_added)))

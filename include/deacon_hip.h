@@ -80,9 +80,10 @@ enum {
  * 1.14 = dcn_align_batch.
  * 1.15 = dcn_anchor_map_pileup_* / dcn_pileup_batch.
  * 1.16 = dcn_extend_batch.
- * 1.17 = dcn_anchor_map_pileup_keep_insertions, dcn_anchor_map_insertions_info / _fetch / _call. */
+ * 1.17 = dcn_anchor_map_pileup_keep_insertions, dcn_anchor_map_insertions_info / _fetch / _call.
+ * 1.18 = dcn_anchor_map_pileup_keep_qualities / _fetch_qualities, dcn_pileup_batch_qual. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 17
+#define DCN_ABI_MINOR 18
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -1095,6 +1096,59 @@ int dcn_anchor_map_insertions_fetch(const dcn_index *map, uint32_t record, uint6
 int dcn_anchor_map_insertions_call(const dcn_index *map, const void *params, uint32_t record, uint64_t start, uint64_t n_bases,
                                    void *alleles, uint64_t allele_capacity, uint8_t *bases, uint64_t base_capacity,
                                    uint64_t *n_alleles, uint64_t *n_inserted);
+
+/* ---- quality-aware pileup: base qualities, low-quality bases as N, quality sums (ABI 1.18) -----------------------------
+ * (no reference counterpart.)  dcn_pileup_batch counts every base of a read alike.  With the quality line of a FASTQ record
+ * a base the sequencer doubted can be kept out of the base columns, and the sums say how good the bases of a column were.
+ *
+ * THE DEFINITION OF A QUALITY-AWARE PILEUP.  Rules 1-6 of a verified placement, A1-A6, P1-P6 and L1-L8 stand.  Added:
+ *   Q1. A map with a pileup enabled may keep quality sums: four more uint32_t per kept base, the columns QA QC QG QT, all
+ *       zero when switched on.  Switching them on is DCN_ERR_ARG once a row has added since the pileup was enabled or last
+ *       reset (L1's rule), so the sums and the counters always describe the same rows; for the same reason
+ *       dcn_pileup_batch, whose rows have no qualities, is DCN_ERR_ARG on a map that keeps sums.
+ *   Q2. dcn_pileup_batch_qual takes quals: one byte per base of the batch, parallel to bases; quals[offsets[r] + x]
+ *       belongs to bases[offsets[r] + x].  The quality of a base is q = byte >= qual_offset ? byte - qual_offset : 0, so
+ *       0 .. 255; a byte below the offset is no error, and the host does not look at the bytes.  On a forward row S[i] is
+ *       the batch base at s_origin + i; on a reverse row it is the complement of the batch base at s_origin - 1 - i (s_origin
+ *       being the first base of the read interval, or its end when reverse).  q(S[i]) is the quality at that same batch
+ *       position: qualities are not complemented.
+ *   Q3. An '=' or X step at (i, j) whose column by P3 is A, C, G or T adds to N instead when q(S[i]) < min_base_qual.  A
+ *       base that is N by P3 stays N.  REV, D steps and I runs are exactly P3's, so P4 holds unchanged.  With
+ *       min_base_qual = 0 the eight counters equal dcn_pileup_batch's for the same rows.
+ *   Q4. On a map that keeps sums, every step that adds to column c of A, C, G, T also adds q(S[i]) to Qc at that position.
+ *       A sum wraps above 2^32 - 1.
+ *   Q5. An insertion ledger receives the same events as from dcn_pileup_batch: qualities do not touch inserted bases.
+ *   Q6. Integers only.  Adds commute: counters and sums depend only on the multiset of (row, its qualities).  edits are
+ *       dcn_verify_batch's: the call never changes what aligns.  P6, L6 and L7 are unchanged: they read the counters and do
+ *       not care how those were made. */
+typedef struct dcn_pileup_qual_params {
+    uint32_t qual_offset;   /* 0 .. 255; 33 for FASTQ */
+    uint32_t min_base_qual; /* 0 .. 255 */
+    uint32_t reserved[2];   /* must be 0 */
+} dcn_pileup_qual_params;   /* 16 bytes */
+
+/* keep != 0 switches the sums on (Q1; keeping again changes nothing): 16 bytes of device memory per base of the pileup,
+ * allocated and zeroed here; keep = 0 frees them and leaves the counters.  DCN_ERR_ARG for a map without a pileup, and by
+ * rule Q1; dcn_anchor_map_pileup_reset zeroes the sums too, dcn_anchor_map_pileup_enable(map, 0) also frees them,
+ * dcn_index_clone gives an index without them, dcn_index_memory does not count them. */
+int dcn_anchor_map_pileup_keep_qualities(dcn_index *map, int keep);
+
+/* dcn_pileup_batch under rules Q2 to Q6: its checks come first, in their order and with their messages; then
+ *   qual_params   a dcn_pileup_qual_params (declared void * for the reason given at dcn_locate_batch): NULL, reserved != 0,
+ *                 qual_offset > 255 and min_base_qual > 255 are DCN_ERR_ARG
+ *   quals         NULL is DCN_ERR_ARG when there is anything to run
+ * Any DCN_ERR_ARG leaves the counters, the sums and a kept ledger untouched.  A map that keeps no sums takes the call as
+ * well: rule Q3 alone then.  The call runs dcn_pileup_batch's passes; the qualities go to a buffer of the context of one
+ * byte per base of the largest such batch, copied in front of the pileup kernel, whose lanes load one byte per '=' / X base
+ * and add a second time where sums are kept.  dcn_ctx_set_profiling: as dcn_pileup_batch, the copy with FINISH. */
+int dcn_pileup_batch_qual(dcn_ctx *ctx, dcn_index *map, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets,
+                          uint32_t n_reads, const void *params, const void *qual_params, const uint64_t *row_offsets,
+                          const void *rows, uint64_t n_rows, uint32_t *edits, uint64_t *n_added);
+
+/* The sums of positions [start, start + n_bases) of a record, position-major: sums[4 q + column] belongs to position
+ * start + q, the columns being DCN_PILEUP_A .. DCN_PILEUP_T.  Blocking.  Errors as for dcn_anchor_map_pileup_fetch, and
+ * DCN_ERR_ARG for a map that keeps no sums. */
+int dcn_anchor_map_pileup_fetch_qualities(const dcn_index *map, uint32_t record, uint64_t start, uint64_t n_bases, uint32_t *sums);
 
 /* ---- extended placements: each placement carried over the read's flanks, with soft clips (ABI 1.16) -------------------
  * (no reference counterpart.)  A placement's two intervals begin and end on the k-mer of an anchor hit: the read's bases
