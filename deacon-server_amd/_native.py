@@ -202,6 +202,37 @@ class PileupQualParams(C.Structure):
     ]
 
 
+class GenotypeParams(C.Structure):
+    _fields_ = [
+        ("ploidy", C.c_uint32),
+        ("min_depth", C.c_uint32),
+        ("min_gq", C.c_uint32),
+        ("min_qual", C.c_uint32),
+        ("err_centi", C.c_uint32),
+        ("het_centi", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class GenotypeSite(C.Structure):
+    _fields_ = [
+        ("pos", C.c_uint64),
+        ("qual", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("ad", C.c_uint32 * 4),
+        ("gt", C.c_uint8),
+        ("gq", C.c_uint8),
+        ("ref_code", C.c_uint8),
+        ("reserved0", C.c_uint8),
+        ("pl", C.c_uint8 * 10),
+        ("reserved1", C.c_uint8 * 2),
+    ]
+
+
+GENOTYPE_NONE = 255  # DCN_GENOTYPE_NONE: the gt byte of a position that is not called
+GENOTYPES = ("AA", "AC", "CC", "AG", "CG", "GG", "AT", "CT", "GT", "TT")  # rule G3's order at ploidy 2; ploidy 1: A C G T
+
+
 class ExtendParams(C.Structure):
     _fields_ = [
         ("penalty", C.c_uint32),
@@ -347,10 +378,11 @@ _SIGNATURES = {
     "dcn_anchor_map_pileup_keep_qualities": (C.c_int, [_vp, C.c_int]),
     "dcn_pileup_batch_qual": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _u64p]),
     "dcn_anchor_map_pileup_fetch_qualities": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
+    "dcn_anchor_map_genotype": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _u64p]),
 }
 
 _lib = None
-ABI = (1, 18)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 19)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

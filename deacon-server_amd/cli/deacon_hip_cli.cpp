@@ -3835,6 +3835,11 @@ struct MapArgs {
     // below --min-baseq counts as N, --variants and --pileup gain the quality columns; consensus, extend and verify are set
     bool call = false;
     unsigned min_baseq = 20, qual_offset = 33;
+    // `genotype`: call, and the genotype of every position from the counters and the quality sums (dcn_anchor_map_genotype):
+    // its SNV sites as VCF with --vcf; call, consensus, extend and verify are set as well
+    bool genotype = false, has_vcf = false;
+    unsigned ploidy = 2, min_gq = 20, min_qual = 20;
+    std::string vcf, sample = "sample";
 };
 
 // one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
@@ -3883,12 +3888,14 @@ void append_paf(std::string &rows, const std::string &read_name, uint32_t read_l
 
 int run_map(const MapArgs &a) {
     const Stopwatch watch;
-    const auto no_qualities = [](const std::string &name) {
-        die("call needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
+    const auto no_qualities = [&a](const std::string &name) {
+        die(std::string(a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
     };
     std::unique_ptr<FastxReader> reads; // (`call` looks at the first record before the reference is loaded)
     if (a.call) {
         if (a.ref.empty()) die("the following required arguments were not provided: <REF>");
+        if (a.genotype && !a.has_fasta && !a.has_variants && !a.has_pileup_out && !a.has_sites && !a.has_vcf && !a.has_summary)
+            die("nothing to write: give at least one of -o <OUTPUT>, --variants <FILE>, --pileup <FILE>, --sites <FILE>, --vcf <FILE>, -s <SUMMARY>");
         reads.reset(new FastxReader(a.input));
         std::string name;
         if (reads->begins_with_fasta(&name)) no_qualities(name);
@@ -4062,8 +4069,34 @@ int run_map(const MapArgs &a) {
     uint64_t insertion_events = 0, inserted_bases = 0, insertion_alleles = 0, substitutions = 0, deleted_positions = 0, consensus_bases = 0,
              uncalled_positions = 0; // (consensus)
     uint64_t qual_sum[4] = {};       // (call)
+    uint64_t genotyped_positions = 0, vcf_sites = 0, het_sites = 0, hom_alt_sites = 0; // (genotype)
     if (piles) {
         TextOut sites_out, pile_file, fasta_out, variants_out;
+        std::unique_ptr<Output> vcf_out; // (.gz as BGZF, .zst and .xz by extension, as filter's outputs)
+        const auto vcf_write = [&vcf_out](const std::string &text) { vcf_out->write(std::vector<char>(text.begin(), text.end())); };
+        if (a.has_vcf) { // VCF 4.2, SNVs only: indels stay in --variants
+            vcf_out.reset(new Output(a.vcf, 2));
+            std::string head = std::string("##fileformat=VCFv4.2\n##source=deacon-hip ") + VERSION + "\n";
+            for (uint32_t r = 0; r < R.n_records; ++r) head += "##contig=<ID=" + R.names[r] + ",length=" + std::to_string(R.lens[r]) + ">\n";
+            head += "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Depth: reads with a base, an N or a deletion at the position\">\n"
+                    "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
+                    "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: phred gap to the second best genotype, at most 99\">\n"
+                    "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Bases A, C, G, T of at least the minimum base quality\">\n"
+                    "##FORMAT=<ID=AD,Number=R,Type=Integer,Description=\"Such bases per allele\">\n"
+                    "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods, at most 255\">\n"
+                    "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + a.sample + "\n";
+            vcf_write(head);
+        }
+        dcn_genotype_params gprm = {};
+        gprm.ploidy = a.ploidy;
+        gprm.min_depth = a.min_depth;
+        gprm.min_gq = a.min_gq;
+        gprm.min_qual = a.min_qual;
+        gprm.err_centi = 477; // 1000 log10 3 and 1000 log10 2, rounded: rule G2's and G3's conventions
+        gprm.het_centi = 301;
+        std::vector<uint8_t> geno_gt;
+        std::vector<dcn_genotype_site> geno_sites;
+        std::string vcf_rows;
         if (a.has_sites) sites_out.open(a.sites, false);
         if (a.has_fasta) fasta_out.open(a.fasta, true);
         if (a.has_variants) variants_out.open(a.variants, false);
@@ -4185,6 +4218,52 @@ int run_map(const MapArgs &a) {
                     if (a.has_fasta) fasta_out.write(seq);
                     if (a.has_variants) variants_out.write(variant_rows);
                 }
+                if (a.genotype) { // rules G1-G8 over the stretch; a site's line is written from the site alone
+                    geno_gt.resize(n);
+                    uint64_t n_geno = 0;
+                    for (int attempt = 0;; ++attempt) {
+                        const int rc = dcn_anchor_map_genotype(R.map.p, &gprm, r, start, n, geno_gt.data(), nullptr, geno_sites.data(), geno_sites.size(), &n_geno);
+                        if (rc != DCN_ERR_CAPACITY || attempt) {
+                            deacon::check(rc);
+                            break;
+                        }
+                        geno_sites.resize(n_geno);
+                    }
+                    for (uint64_t q = 0; q < n; ++q) genotyped_positions += geno_gt[q] != DCN_GENOTYPE_NONE;
+                    vcf_sites += n_geno;
+                    vcf_rows.clear();
+                    for (uint64_t i = 0; i < n_geno; ++i) {
+                        const dcn_genotype_site &g = geno_sites[i];
+                        // the genotype's alleles x <= y (G3's order: index y (y + 1) / 2 + x), then (REF, ALTs in A C G T order)
+                        unsigned x = g.gt, y = g.gt;
+                        if (a.ploidy == 2)
+                            for (y = 0; (y + 1) * (y + 2) / 2 <= g.gt; ++y) {}
+                        if (a.ploidy == 2) x = g.gt - y * (y + 1) / 2;
+                        (x != y ? het_sites : hom_alt_sites) += 1;
+                        unsigned alleles[3] = {g.ref_code, 0, 0}, n_alleles = 1;
+                        if (x != g.ref_code) alleles[n_alleles++] = x;
+                        if (y != g.ref_code && y != x) alleles[n_alleles++] = y;
+                        const auto index_of = [&](unsigned c) { return c == alleles[0] ? 0u : c == alleles[1] ? 1u : 2u; };
+                        const auto pair_index = [](unsigned p, unsigned q2) { return p <= q2 ? q2 * (q2 + 1) / 2 + p : p * (p + 1) / 2 + q2; };
+                        vcf_rows += R.names[r] + '\t' + std::to_string(g.pos + 1) + "\t.\t" + "ACGT"[g.ref_code] + '\t';
+                        for (unsigned k = 1; k < n_alleles; ++k) vcf_rows += std::string(k > 1 ? "," : "") + "ACGT"[alleles[k]];
+                        vcf_rows += '\t' + std::to_string(g.qual) + "\tPASS\tDP=" + std::to_string(g.depth) + "\tGT:GQ:DP:AD:PL\t";
+                        if (a.ploidy == 2) vcf_rows += std::to_string(std::min(index_of(x), index_of(y))) + '/' + std::to_string(std::max(index_of(x), index_of(y)));
+                        else vcf_rows += std::to_string(index_of(x));
+                        vcf_rows += ':' + std::to_string(g.gq) + ':' + std::to_string((uint64_t)g.ad[0] + g.ad[1] + g.ad[2] + g.ad[3]) + ':';
+                        for (unsigned k = 0; k < n_alleles; ++k) vcf_rows += (k ? "," : "") + std::to_string(g.ad[alleles[k]]);
+                        vcf_rows += ':';
+                        bool first = true;
+                        for (unsigned j = 0; j < n_alleles; ++j)
+                            for (unsigned i2 = 0; i2 <= (a.ploidy == 2 ? j : 0u); ++i2) {
+                                const unsigned at = a.ploidy == 2 ? pair_index(alleles[i2], alleles[j]) : alleles[j];
+                                vcf_rows += (first ? "" : ",") + std::to_string(g.pl[at]);
+                                first = false;
+                            }
+                        vcf_rows += '\n';
+                    }
+                    if (a.has_vcf) vcf_write(vcf_rows);
+                }
                 if (!a.has_sites) continue;
                 site_rows.clear();
                 for (uint64_t i = 0; i < found; ++i) {
@@ -4202,6 +4281,7 @@ int run_map(const MapArgs &a) {
         if (a.has_sites) sites_out.finish();
         if (a.has_fasta) fasta_out.finish();
         if (a.has_variants) variants_out.finish();
+        if (a.has_vcf) vcf_out->close();
         if (a.extend && a.has_pileup_out) pile_file.finish();
     }
     if (prints) out.finish();
@@ -4275,6 +4355,11 @@ int run_map(const MapArgs &a) {
             appendf(js, "  \"min_base_qual\": %u,\n  \"qual_offset\": %u,\n  \"quality_sums\": {\"A\": %llu, \"C\": %llu, \"G\": %llu, \"T\": %llu},\n",
                     a.min_baseq, a.qual_offset, (unsigned long long)qual_sum[0], (unsigned long long)qual_sum[1], (unsigned long long)qual_sum[2],
                     (unsigned long long)qual_sum[3]);
+        if (a.genotype)
+            appendf(js, "  \"ploidy\": %u,\n  \"min_gq\": %u,\n  \"min_qual\": %u,\n  \"genotyped_positions\": %llu,\n  \"vcf_sites\": %llu,\n"
+                        "  \"het_sites\": %llu,\n  \"hom_alt_sites\": %llu,\n",
+                    a.ploidy, a.min_gq, a.min_qual, (unsigned long long)genotyped_positions, (unsigned long long)vcf_sites,
+                    (unsigned long long)het_sites, (unsigned long long)hom_alt_sites);
         appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
         for (uint32_t r = 0; r < R.n_records; ++r) {
             js += (r ? ",\n    {" : "\n    {");
@@ -4426,6 +4511,7 @@ void usage() {
                  "  extend  As map, each placement carried over the flanks of its read, the rest soft-clipped; then align, pileup\n"
                  "  consensus  As extend and pileup, keeping inserted bases: the sequence the reads support as FASTA, and its variants\n"
                  "  call    As consensus, with the reads' base qualities: low-quality bases do not vote, variants carry mean qualities\n"
+                 "  genotype  As call, with a genotype per position from counts and quality sums: GQ, PL, QUAL, SNV sites as VCF\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -4877,6 +4963,90 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "only what a base counts as changes.  With --min-baseq 0 the FASTA is consensus's.  The qualities of inserted bases\n"
                "are not looked at.  No quality-weighted calls or likelihoods, no VCF, no affine gaps.  Mates are independent\n"
                "here: one input.\n";
+    else if (sub == "genotype")
+        text = "Pile the extended placements of FASTQ reads up on a reference with their base qualities, as call does, and give\n"
+               "every position a genotype with a quality from the counts and the quality sums: the SNV sites as VCF\n\n"
+               "Usage: deacon-hip genotype [OPTIONS] <REF> [READS]\n\n"
+               "Arguments:\n"
+               "  <REF>     Path to the reference fastx file: its records are numbered and named in file order\n"
+               "  [READS]   Optional path to FASTQ file (or - for stdin; gz, bgzf, zst, xz and bz2 found by content) [default: -]\n"
+               "            A record without a quality line (FASTA) is an error: consensus takes such reads\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Keys that may anchor: a minimizer index file, whose k and w are used\n"
+               "                                 [default: the minimizers of <REF> at -k / -w]\n"
+               "  -k <K>                         K-mer length without -x [default: 31]\n"
+               "  -w <W>                         Minimizer window size without -x [default: 15]\n"
+               "  -o, --output <OUTPUT>          FASTA: per record of <REF> a line >name and its consensus on one line (- for\n"
+               "                                 stdout) [default: no FASTA]\n"
+               "      --variants <FILE>          TSV: record pos type ref alt depth count events, pos 0-based as in PAF; one SUB line\n"
+               "                                 per substituted position, one DEL line per deleted position (alt -), one INS or\n"
+               "                                 INS_FRONT line per called insertion behind or in front of pos (ref ., count = the\n"
+               "                                 reads with exactly these bases, events = all insertions there; 0 on other lines)\n"
+               "                                 With two more columns, ref_qual alt_qual: on a SUB line the mean quality, rounded\n"
+               "                                 down, of the counted bases that show the reference's base and of those that show\n"
+               "                                 alt (. for none, or for a reference base that is not ACGT); . on every other line\n"
+               "      --vcf <FILE>               VCF 4.2, SNVs only (- for stdout; .gz as BGZF, .zst and .xz by extension): one line per\n"
+               "                                 position whose genotype is called and is\n"
+               "                                 not the reference's, with QUAL, INFO DP (all reads there) and GT:GQ:DP:AD:PL over\n"
+               "                                 the reference's base and the genotype's other bases; insertions and deletions stay\n"
+               "                                 in --variants [default: no VCF]\n"
+               "      --ploidy <1|2>             Genotypes of one base (A C G T) or of two (AA AC CC AG CG GG AT CT GT TT) [default: 2]\n"
+               "      --min-gq <N>               A genotype is called at a genotype quality of at least N: the phred gap between the\n"
+               "                                 best and the second best genotype (0..99) [default: 20, a convention]\n"
+               "      --min-qual <N>             A site needs QUAL of at least N: the phred gap between the reference's homozygote and\n"
+               "                                 the best genotype [default: 20, a convention]\n"
+               "      --sample <NAME>            The sample column's name [default: sample]\n"
+               "      --fill-ref                 A position without a call takes the reference's base, not N\n"
+               "      --min-baseq <Q>            A base of quality below Q counts as N: it adds to the depth and never wins\n"
+               "                                 (0..255) [default: 20, a convention]\n"
+               "      --qual-offset <N>          The quality of a base is its quality character minus N, 0 when that is negative\n"
+               "                                 (0..255) [default: 33]\n"
+               "      --pileup <FILE>            pileup's TSV over the extended placements: record pos ref A C G T N del ins rev, then\n"
+               "                                 qA qC qG qT: the sums of the qualities of the bases counted in A C G T\n"
+               "      --sites <FILE>             pileup's site TSV over them: record pos ref call depth flags\n"
+               "      --all-positions            One line of --pileup for every position of every record\n"
+               "      --min-depth <N>            A call needs a depth of at least N, a genotype as many bases A C G T\n"
+               "                                 [default: 3, a convention]\n"
+               "      --min-frac <N>             ... and N per 1000 of the depth for the most frequent of A C G T and gap, and\n"
+               "                                 for the insertions at a position (0..1000) [default: 500, a convention]\n"
+               "      --min-mapq <N>             Only placements of mapping quality N or more add (0..60) [default: 1, a convention]\n"
+               "      --all-ranks                Every placement of a read adds, not only its first (rank 0)\n"
+               "      --penalty <N>              An edit in a flank costs N matched bases of read plus record (2..255)\n"
+               "                                 [default: 6, a convention]\n"
+               "      --end-bonus <N>            Reaching the read's end is worth N (0..65535) [default: 4, a convention]\n"
+               "      --ext-max-edits <N>        At most N edits per flank (0..1023) [default: 1023, a convention]\n"
+               "  -e, --max-edits <N>            Only placements of at most N edits over the extended extents add (0..1023)\n"
+               "                                 [default: 1023, a convention]\n"
+               "      --max-div <N>              ... and of at most N per 1000 bases of the longer extended extent (0..1000)\n"
+               "                                 [default: 200, a convention]\n"
+               "  -N, --max-placements <N>       Placements per read, each from the anchor hits no earlier one explained (1..8)\n"
+               "                                 [default: 4]\n"
+               "      --band <N>                 Width of a diagonal band in bases [default: 256, a convention]\n"
+               "  -a, --min-votes <N>            Minimum number of anchor hits in a placement's cell [default: 2, as filter's -a,\n"
+               "                                 a convention]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per read (0 = entire read) [default: 0]\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file: extend's and pileup's keys, and fill_ref,\n"
+               "                                 insertion_events, inserted_bases, insertion_alleles, substitutions,\n"
+               "                                 deleted_positions, consensus_bases and uncalled_positions; min_base_qual,\n"
+               "                                 qual_offset and quality_sums, the totals of qA qC qG qT; ploidy, min_gq, min_qual,\n"
+               "                                 genotyped_positions, vcf_sites, het_sites and hom_alt_sites\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
+               "  -h, --help                     Print help\n\n"
+               "Consensus, position by position of a record: the bases of an insertion called in front of the position; the\n"
+               "called base, nothing where a gap is called, N (or the reference's base with --fill-ref) where nothing is; the\n"
+               "bases of an insertion called behind it.  An insertion is called where the reads with an insertion there reach\n"
+               "--min-frac of a depth of at least --min-depth; its bases are those most of them agree on (on a tie one behind\n"
+               "the position before one in front, then the shorter, then the first by letter), whatever their own share: count\n"
+               "and events say what it is.  The thresholds are conventions, not measured optima.  Integers and bytes only: the\n"
+               "output does not depend on how the input is cut into batches.  Deleted positions are not merged, indels are not\n"
+               "left-normalised.  Qualities: alignment does not look at them, so the placements and their edits are consensus's;\n"
+               "only what a base counts as changes.  With --min-baseq 0 the FASTA is consensus's.  The qualities of inserted bases\n"
+               "are not looked at.  -o, --variants, --pileup and --sites are call's, byte for byte.  Genotypes: a base of quality q\n"
+               "that a genotype does not explain costs q + 4.77 phred, a base of a heterozygote 3.01; the costs are sums over the\n"
+               "counted bases A C G T, in integers (hundredths of a phred), and a matching base costs nothing.  The constants and\n"
+               "thresholds are conventions, not measured optima.  SNVs only: no indels in the VCF, no priors, no strand or mapping\n"
+               "quality terms, no phasing, no affine gaps.  Mates are independent here: one input.\n";
     else if (sub == "map-pairs")
         text = "Place the two mates of each pair jointly on a reference: proper pairs, rescued mates and insert sizes, as PAF\n\n"
                "Usage: deacon-hip map-pairs [OPTIONS] <REF> <READS1> [READS2]\n\n"
@@ -5168,11 +5338,12 @@ int main(int argc, char **argv) {
             return run_place(a);
         }
         if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup" || args[0] == "extend" || args[0] == "consensus" ||
-            args[0] == "call") {
+            args[0] == "call" || args[0] == "genotype") {
             MapArgs a;
             a.align = args[0] == "align";
             a.pileup = args[0] == "pileup";
-            a.call = args[0] == "call";
+            a.genotype = args[0] == "genotype";
+            a.call = args[0] == "call" || a.genotype;
             a.consensus = args[0] == "consensus" || a.call;
             a.extend = args[0] == "extend" || a.consensus;
             a.verify = a.align || a.pileup || a.extend || args[0] == "verify";
@@ -5194,6 +5365,11 @@ int main(int argc, char **argv) {
                 else if (a.consensus && s == "--fill-ref") a.fill_ref = true;
                 else if (a.call && s == "--min-baseq") a.min_baseq = (unsigned)number(need(++i), "--min-baseq", 0, 255);
                 else if (a.call && s == "--qual-offset") a.qual_offset = (unsigned)number(need(++i), "--qual-offset", 0, 255);
+                else if (a.genotype && s == "--vcf") a.vcf = need(++i), a.has_vcf = true;
+                else if (a.genotype && s == "--ploidy") a.ploidy = (unsigned)number(need(++i), "--ploidy", 1, 2);
+                else if (a.genotype && s == "--min-gq") a.min_gq = (unsigned)number(need(++i), "--min-gq", 0, 99);
+                else if (a.genotype && s == "--min-qual") a.min_qual = (unsigned)number(need(++i), "--min-qual", 0, 0xFFFFFFFFll);
+                else if (a.genotype && s == "--sample") a.sample = need(++i);
                 else if (s == "-o" || s == "--output") a.output = need(++i), a.has_output = true;
                 else if (a.extend && s == "--penalty") a.penalty = (unsigned)number(need(++i), "--penalty", 2, 255);
                 else if (a.extend && s == "--end-bonus") a.end_bonus = (unsigned)number(need(++i), "--end-bonus", 0, 65535);

@@ -274,7 +274,26 @@ int dev_alloc_zeroed(T **p, uint64_t count, const char *what) {
     *p = d;
     return DCN_OK;
 }
+} // namespace dcn_impl
 
+// device memory of one range call over a pileup (pileup_api.hip, genotype_api.hip), freed when the call ends
+namespace dcn_pile_api {
+struct scratch {
+    void *p[6] = {};
+    int n = 0;
+    template <typename T>
+    int get(T **out, uint64_t count, const char *what) {
+        DCN_TRY(dcn_impl::dev_alloc(out, count, what));
+        p[n++] = *out;
+        return DCN_OK;
+    }
+    ~scratch() {
+        for (int i = 0; i < n; ++i) hipFree(p[i]);
+    }
+};
+} // namespace dcn_pile_api
+
+namespace dcn_impl {
 // device scratch that goes back on every way out
 struct DevMem {
     void *p = nullptr;

@@ -232,6 +232,36 @@ struct dcn_pileup_call_args {
 uint32_t dcn_pileup_call_blocks(uint64_t n); // workgroups of a range of n positions
 int dcn_launch_pileup_call(const dcn_pileup_call_args &args, bool write, hipStream_t stream);
 
+// what the range calls over a pileup share on the host (pileup_api.hip defines the checks; genotype_api.hip uses them too)
+#pragma GCC visibility push(hidden)
+namespace dcn_pile_api {
+// the map is an anchor map that keeps bases and has a pileup
+int check_pileup(const dcn_index *map);
+// ... and keeps quality sums
+int check_qsums(const dcn_index *map);
+// (their scratch holder, dcn_pile_api::scratch, is in dcn_ctx.h, where dev_alloc is)
+} // namespace dcn_pile_api
+#pragma GCC visibility pop
+
+// ---- genotypes (genotype.hip, genotype_api.hip; the shared arithmetic is in dcn_genotype.h) ---------------------------
+struct dcn_genotype_args {
+    const uint32_t *counters, *sums; // the map's pileup and its quality sums
+    uint64_t bases;
+    const uint32_t *t_packed, *t_invmask; // the store
+    uint64_t base0, n;                    // the range: store bases [base0, base0 + n)
+    uint64_t pos0;                        // ... and the record position of its first base
+    uint32_t ploidy, min_depth, min_gq, min_qual, err_centi, het_centi;
+    // per position of the range, each behind a pad of base0 & 3 bytes: byte (base0 & 3) + q belongs to position q, so that
+    // the byte of a store base divisible by 4 lies on a word of the buffer (the counting pass; dcn_genotype_out_bytes each)
+    uint8_t *gt, *gq;
+    uint32_t *block_counts;        // sites per workgroup (the counting pass)
+    const uint64_t *block_offsets; // their scan (the writing pass)
+    void *sites;                   // dcn_genotype_site per site
+};
+uint32_t dcn_genotype_blocks(uint64_t base0, uint64_t n);    // workgroups of a range
+uint64_t dcn_genotype_out_bytes(uint64_t base0, uint64_t n); // bytes of args.gt and of args.gq
+int dcn_launch_genotype(const dcn_genotype_args &args, bool write, hipStream_t stream);
+
 // ---- extended placements (extend.hip, extend_api.hip; the shared arithmetic is in dcn_extend.h) ----------------------
 // One flank of one row as the kernel takes it: item 2 r is the left flank of row r, item 2 r + 1 its right flank.  The
 // host has checked the row and resolved both sequences of the flank to stream positions, as dcn_verify_item has them.

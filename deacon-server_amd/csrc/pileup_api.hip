@@ -23,34 +23,20 @@ static_assert(DCN_PILEUP_SITE_SUB == DCN_PILE_SITE_SUB && DCN_PILEUP_SITE_DEL ==
                   DCN_PILEUP_SITE_INS == DCN_PILE_SITE_INS && DCN_PILEUP_NO_CODE == DCN_PILE_NO_CODE,
               "the site flags of the header and of dcn_pileup.h");
 
-namespace {
-int check_pileup(const dcn_index *map) {
+// (declared in dcn_verify.h, the scratch holder in dcn_ctx.h: genotype_api.hip makes the same checks)
+int dcn_pile_api::check_pileup(const dcn_index *map) {
     DCN_TRY(check_store(map));
     if (!map->d_pileup) return dcn_fail(DCN_ERR_ARG, "the map has no pileup (dcn_anchor_map_pileup_enable)");
     return DCN_OK;
 }
 
-int check_qsums(const dcn_index *map) {
+int dcn_pile_api::check_qsums(const dcn_index *map) {
     DCN_TRY(check_pileup(map));
     if (!map->d_pileup_qsums) return dcn_fail(DCN_ERR_ARG, "the map keeps no quality sums (dcn_anchor_map_pileup_keep_qualities)");
     return DCN_OK;
 }
 
-// device memory of one call, freed when it ends
-struct scratch {
-    void *p[6] = {};
-    int n = 0;
-    template <typename T>
-    int get(T **out, uint64_t count, const char *what) {
-        DCN_TRY(dev_alloc(out, count, what));
-        p[n++] = *out;
-        return DCN_OK;
-    }
-    ~scratch() {
-        for (int i = 0; i < n; ++i) hipFree(p[i]);
-    }
-};
-} // namespace
+using namespace dcn_pile_api;
 
 extern "C" int dcn_anchor_map_pileup_enable(dcn_index *map, int enable) {
     DCN_TRY(check_store(map));

@@ -685,6 +685,11 @@ INSERTION_DTYPE = np.dtype([("pos", np.uint64), ("bases_offset", np.uint64), ("l
 INSERTION_ALLELE_DTYPE = np.dtype([("pos", np.uint64), ("bases_offset", np.uint64), ("len", np.uint32), ("count", np.uint32),
                                    ("events", np.uint32), ("flags", np.uint32)])
 INSERTION_FRONT, INSERTION_REVERSE = N.INSERTION_FRONT, N.INSERTION_REVERSE  # DCN_INSERTION_*: bits of `flags`
+# dcn_genotype_site, 48 bytes: what AnchorMap.genotype returns per site
+GENOTYPE_SITE_DTYPE = np.dtype([("pos", np.uint64), ("qual", np.uint32), ("depth", np.uint32), ("ad", np.uint32, (4,)), ("gt", np.uint8),
+                                ("gq", np.uint8), ("ref_code", np.uint8), ("reserved0", np.uint8), ("pl", np.uint8, (10,)),
+                                ("reserved1", np.uint8, (2,))])
+GENOTYPE_NONE, GENOTYPES = N.GENOTYPE_NONE, N.GENOTYPES
 _CIGAR_LETTERS = {N.CIGAR_INS: "I", N.CIGAR_DEL: "D", N.CIGAR_EQUAL: "=", N.CIGAR_DIFF: "X"}
 
 
@@ -781,6 +786,30 @@ class AnchorMap(Index):
         out = np.zeros((max(n, 1), 4), np.uint32)
         N.check(N.lib().dcn_anchor_map_pileup_fetch_qualities(self._h, int(record), start, n, _ptr(out)))
         return out[:n]
+
+    def genotype(self, record, start=0, n=None, ploidy=2, min_depth=3, min_gq=20, min_qual=20, err_centi=477, het_centi=301):
+        """Rules G1-G8 (the definition of a genotype is in include/deacon_hip.h) over positions [start, start + n) of a record
+        (n=None: to its end) of a map that keeps quality sums -> (gt np.uint8[n], gq np.uint8[n], sites GENOTYPE_SITE_DTYPE[]).
+        gt is the index of the best genotype in GENOTYPES' order (ploidy 1: A C G T), or GENOTYPE_NONE where the position is
+        not called; gq its quality, 0 .. 99, either way; the sites are the called positions whose genotype is not the
+        reference's, in ascending position.  The defaults are conventions, not measured optima.  One call with an estimate
+        and, on DCN_ERR_CAPACITY, a second with the size the first reported."""
+        start, n = int(start), self._to_end(record, start) if n is None else int(n)
+        p = N.GenotypeParams(int(ploidy), int(min_depth), int(min_gq), int(min_qual), int(err_centi), int(het_centi), (C.c_uint32 * 2)(0, 0))
+        gt, gq = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+        n_sites = C.c_uint64()
+
+        def call(cap):
+            sites = np.zeros(max(cap, 1), GENOTYPE_SITE_DTYPE)
+            rc = N.lib().dcn_anchor_map_genotype(self._h, C.byref(p), int(record), start, n, _ptr(gt), _ptr(gq), _ptr(sites) if cap else None,
+                                                 cap, C.byref(n_sites))
+            return rc, sites
+
+        rc, sites = call(n // 64 + 64)
+        if rc == N.DCN_ERR_CAPACITY:
+            rc, sites = call(int(n_sites.value))
+        N.check(rc)
+        return gt[:n], gq[:n], sites[:int(n_sites.value)]
 
     def insertions_info(self):
         """-> (events of the ledger, the sum of their lengths)"""

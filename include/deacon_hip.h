@@ -81,9 +81,10 @@ enum {
  * 1.15 = dcn_anchor_map_pileup_* / dcn_pileup_batch.
  * 1.16 = dcn_extend_batch.
  * 1.17 = dcn_anchor_map_pileup_keep_insertions, dcn_anchor_map_insertions_info / _fetch / _call.
- * 1.18 = dcn_anchor_map_pileup_keep_qualities / _fetch_qualities, dcn_pileup_batch_qual. */
+ * 1.18 = dcn_anchor_map_pileup_keep_qualities / _fetch_qualities, dcn_pileup_batch_qual.
+ * 1.19 = dcn_anchor_map_genotype. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 18
+#define DCN_ABI_MINOR 19
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -1149,6 +1150,75 @@ int dcn_pileup_batch_qual(dcn_ctx *ctx, dcn_index *map, const uint8_t *bases, co
  * start + q, the columns being DCN_PILEUP_A .. DCN_PILEUP_T.  Blocking.  Errors as for dcn_anchor_map_pileup_fetch, and
  * DCN_ERR_ARG for a map that keeps no sums. */
 int dcn_anchor_map_pileup_fetch_qualities(const dcn_index *map, uint32_t record, uint64_t start, uint64_t n_bases, uint32_t *sums);
+
+/* ---- genotypes: likelihoods from the counters and the quality sums, per position (ABI 1.19) ---------------------------
+ * (no reference counterpart.)  Rule P6 calls the single most frequent column: a haploid majority vote that does not say
+ * how sure it is.  In phred units a mismatching base of quality q costs q + 10 log10 3, so the sums of rule Q4 together
+ * with the counters are the sufficient statistic of the textbook genotype likelihood: no pass over the reads is needed.
+ *
+ * THE DEFINITION OF A GENOTYPE.  Rules P1-P6, L1-L8 and Q1-Q6 stand.  Added:
+ *   G1. Inputs.  A genotype is computed at one position of a map that keeps quality sums (Q1), from two sets of numbers
+ *       only: the four base counters n[A..T] and the four sums Q[A..T].  N, DEL, INS and REV do not vote.
+ *       D = n[A] + n[C] + n[G] + n[T].
+ *   G2. Column cost.  All costs are unsigned 64-bit integers in hundredths of a phred.  M[c] = 100 Q[c] + err_centi n[c]:
+ *       the cost of explaining every base of column c as an error.  The default err_centi is 477: 1000 log10 3, rounded.
+ *   G3. Genotype costs and order.  Ploidy 2 has ten genotypes x/y, x <= y, in VCF order (index y (y + 1) / 2 + x over
+ *       A, C, G, T): AA, AC, CC, AG, CG, GG, AT, CT, GT, TT.
+ *         cost(x/x) = the sum of M[c] over c != x.
+ *         cost(x/y) = the sum of M[c] over c not in {x, y}, plus het_centi (n[x] + n[y]).  The default het_centi is 301:
+ *           1000 log10 2, rounded.
+ *       Ploidy 1 has four genotypes A, C, G, T, with cost(x) = the sum of M[c] over c != x.
+ *       The cost of a matching base, -10 log10(1 - e), is taken as 0: the stated approximation that makes counts and sums
+ *       sufficient.
+ *   G4. Best genotype, GQ, PL.  best is the first genotype in G3's order with the smallest cost.  second is the smallest
+ *       cost among the others; it may equal the best cost.  GQ = min(99, (second - cost[best]) / 100),
+ *       PL[g] = min(255, (cost[g] - cost[best]) / 100): integer quotients both.
+ *   G5. QUAL = (cost(ref/ref) - cost[best]) / 100, saturated at 2^32 - 1, where ref/ref is the homozygous genotype of the
+ *       record's base (just ref at ploidy 1).  QUAL is 0 where the reference base is invalid.
+ *   G6. Called.  A position is CALLED when D >= max(1, min_depth) and GQ >= min_gq.  Its gt byte is the genotype's index
+ *       when called and DCN_GENOTYPE_NONE otherwise; its gq byte is GQ either way.
+ *   G7. Site.  A position is a SITE when it is called, the reference base is valid, best is not ref/ref and
+ *       QUAL >= min_qual.
+ *   G8. Integers only.  The result is a function of the twelve numbers (the counters, the sums, the reference base and
+ *       P4's depth, which a site only reports) and the parameters, unique while no counter or sum has wrapped.
+ *       min_depth = 3, min_gq = 20, min_qual = 20, err_centi = 477 and het_centi = 301 are conventions of the layers
+ *       above, not measured optima. */
+#define DCN_GENOTYPE_NONE 255u
+typedef struct dcn_genotype_params {
+    uint32_t ploidy;      /* 1 or 2 */
+    uint32_t min_depth;
+    uint32_t min_gq;      /* 0 .. 99 */
+    uint32_t min_qual;
+    uint32_t err_centi;   /* 0 .. 100000, so that every cost fits 64 bits */
+    uint32_t het_centi;   /* 0 .. 100000 */
+    uint32_t reserved[2]; /* must be 0 */
+} dcn_genotype_params;    /* 32 bytes */
+typedef struct dcn_genotype_site {
+    uint64_t pos;         /* record-relative, 0-based */
+    uint32_t qual;        /* G5 */
+    uint32_t depth;       /* P4's depth: all six columns */
+    uint32_t ad[4];       /* n[A..T] */
+    uint8_t gt, gq;
+    uint8_t ref_code;     /* 0 .. 3 */
+    uint8_t reserved0;
+    uint8_t pl[10];       /* G3's order; the entries past the ploidy's genotypes are 0 */
+    uint8_t reserved1[2];
+} dcn_genotype_site;      /* 48 bytes */
+
+/* Rules G1-G8 over positions [start, start + n_bases) of a record.
+ *   params      a dcn_genotype_params (declared void * for the reason given at dcn_locate_batch): NULL, reserved != 0,
+ *               a ploidy other than 1 or 2, min_gq > 99, err_centi or het_centi above 100000 are DCN_ERR_ARG, in this order
+ *   gt, gq      each NULL, or n_bases bytes (G6)
+ *   sites       dcn_genotype_site entries in ascending position (declared void * likewise), capacity of them
+ *   n_sites     always receives the number of sites there is
+ * DCN_ERR_ARG then for a map without a pileup and for one that keeps no quality sums; range errors as for
+ * dcn_anchor_map_fetch.  n_bases = 0 succeeds.  DCN_ERR_CAPACITY when capacity is smaller: gt and gq are complete and no
+ * site is written; NULL with capacity 0 asks for the count (dcn_anchor_map_pileup_call's protocol).
+ * Blocking, on the null stream with scratch of the call: a pass that writes gt and gq and counts the sites per workgroup,
+ * a scan of those counts, and a second pass that recomputes the costs and writes the sites.  The grid is sized by the
+ * range (DCN_GRID_CUS does not apply).  No new memory on the map and no pass over reads. */
+int dcn_anchor_map_genotype(const dcn_index *map, const void *params, uint32_t record, uint64_t start, uint64_t n_bases,
+                            uint8_t *gt, uint8_t *gq, void *sites, uint64_t capacity, uint64_t *n_sites);
 
 /* ---- extended placements: each placement carried over the read's flanks, with soft clips (ABI 1.16) -------------------
  * (no reference counterpart.)  A placement's two intervals begin and end on the k-mer of an anchor hit: the read's bases
