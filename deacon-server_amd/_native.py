@@ -233,6 +233,15 @@ GENOTYPE_NONE = 255  # DCN_GENOTYPE_NONE: the gt byte of a position that is not 
 GENOTYPES = ("AA", "AC", "CC", "AG", "CG", "GG", "AT", "CT", "GT", "TT")  # rule G3's order at ploidy 2; ploidy 1: A C G T
 
 
+class DuplicateParams(C.Structure):
+    _fields_ = [
+        ("row_stride", C.c_uint32),
+        ("paired", C.c_uint32),
+        ("both_ends", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class ExtendParams(C.Structure):
     _fields_ = [
         ("penalty", C.c_uint32),
@@ -379,10 +388,14 @@ _SIGNATURES = {
     "dcn_pileup_batch_qual": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _u64p]),
     "dcn_anchor_map_pileup_fetch_qualities": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
     "dcn_anchor_map_genotype": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _u64p]),
+    "dcn_anchor_map_duplicates_enable": (C.c_int, [_vp, C.c_int]),
+    "dcn_anchor_map_duplicates_reset": (C.c_int, [_vp]),
+    "dcn_anchor_map_duplicates_info": (C.c_int, [_vp, _u64p, _u64p, _u64p]),
+    "dcn_mark_duplicates_batch": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _u64p]),
 }
 
 _lib = None
-ABI = (1, 19)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 20)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

@@ -3840,6 +3840,10 @@ struct MapArgs {
     bool genotype = false, has_vcf = false;
     unsigned ploidy = 2, min_gq = 20, min_qual = 20;
     std::string vcf, sample = "sample";
+    // `markdup`: genotype, with the reads whose end an earlier read had (dcn_mark_duplicates_batch on the selected extended
+    // rows) left out of the pile-up, or with --keep-duplicates only marked and reported; genotype and all it sets are set
+    bool markdup = false, keep_duplicates = false, both_ends = false, has_duplicates = false;
+    std::string duplicates;
 };
 
 // one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
@@ -3889,13 +3893,14 @@ void append_paf(std::string &rows, const std::string &read_name, uint32_t read_l
 int run_map(const MapArgs &a) {
     const Stopwatch watch;
     const auto no_qualities = [&a](const std::string &name) {
-        die(std::string(a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
+        die(std::string(a.markdup ? "markdup" : a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
     };
     std::unique_ptr<FastxReader> reads; // (`call` looks at the first record before the reference is loaded)
     if (a.call) {
         if (a.ref.empty()) die("the following required arguments were not provided: <REF>");
-        if (a.genotype && !a.has_fasta && !a.has_variants && !a.has_pileup_out && !a.has_sites && !a.has_vcf && !a.has_summary)
-            die("nothing to write: give at least one of -o <OUTPUT>, --variants <FILE>, --pileup <FILE>, --sites <FILE>, --vcf <FILE>, -s <SUMMARY>");
+        if (a.genotype && !a.has_fasta && !a.has_variants && !a.has_pileup_out && !a.has_sites && !a.has_vcf && !a.has_summary && !a.has_duplicates)
+            die(std::string("nothing to write: give at least one of -o <OUTPUT>, --variants <FILE>, --pileup <FILE>, --sites <FILE>, --vcf <FILE>, ") +
+                (a.markdup ? "--duplicates <FILE>, " : "") + "-s <SUMMARY>");
         reads.reset(new FastxReader(a.input));
         std::string name;
         if (reads->begins_with_fasta(&name)) no_qualities(name);
@@ -3908,6 +3913,19 @@ int run_map(const MapArgs &a) {
     if (piles) deacon::check(dcn_anchor_map_pileup_enable(R.map.p, 1)); // (after the records: a pileup does not grow)
     if (a.consensus) deacon::check(dcn_anchor_map_pileup_keep_insertions(R.map.p, 1)); // (before the first row adds)
     if (a.call) deacon::check(dcn_anchor_map_pileup_keep_qualities(R.map.p, 1));
+    if (a.markdup) deacon::check(dcn_anchor_map_duplicates_enable(R.map.p, 1));
+    dcn_duplicate_params dprm = {};
+    dprm.row_stride = sizeof(dcn_split_placement);
+    dprm.paired = 0; // (mates are placed independently here: a read is a unit)
+    dprm.both_ends = a.both_ends ? 1 : 0;
+    std::vector<uint8_t> dup_flags;
+    std::vector<uint64_t> dup_first;
+    std::string dup_rows;
+    TextOut dup_out;
+    if (a.has_duplicates) {
+        dup_out.open(a.duplicates, false);
+        dup_out.write("read\tordinal\tfirst\trecord\tstrand\tpos5\n");
+    }
     dcn_pileup_qual_params qprm = {};
     qprm.qual_offset = a.qual_offset;
     qprm.min_base_qual = a.min_baseq;
@@ -3991,6 +4009,28 @@ int run_map(const MapArgs &a) {
             for (dcn_split_placement &p : chosen) {
                 if (p.mapq >= a.min_mapq && (a.all_ranks || p.rank == 0)) ++rows_selected;
                 else p.record = UINT32_MAX;
+            }
+            if (a.markdup) { // the selected rows' ends against every read so far: one call per batch, so an ordinal is a read's number
+                dup_flags.assign(n_reads, 0);
+                dup_first.assign(n_reads, 0);
+                deacon::check(dcn_mark_duplicates_batch(R.map.p, b.offsets.data(), n_reads, &dprm, place_off.data(), chosen.data(),
+                                                        place_off[n_reads], dup_flags.data(), dup_first.data(), nullptr));
+                dup_rows.clear();
+                for (uint32_t r = 0; r < n_reads; ++r) {
+                    if (!dup_flags[r]) continue;
+                    if (a.has_duplicates) { // rule D3's end, from the read's first selected row
+                        uint64_t q = place_off[r];
+                        while (chosen[q].record == UINT32_MAX) ++q;
+                        const dcn_split_placement &p = chosen[q];
+                        const long long pos5 = p.reverse ? (long long)(p.ref_end + p.read_start) : (long long)p.ref_start - (long long)p.read_start;
+                        dup_rows.append(id_token(b, b.recs[r]));
+                        dup_rows += '\t' + std::to_string(reads_in + r) + '\t' + std::to_string(dup_first[r]) + '\t' + R.names[p.record] + '\t' +
+                                    (p.reverse ? '-' : '+') + '\t' + std::to_string(pos5) + '\n';
+                    }
+                    if (!a.keep_duplicates)
+                        for (uint64_t q = place_off[r]; q < place_off[r + 1]; ++q) chosen[q].record = UINT32_MAX;
+                }
+                if (a.has_duplicates) dup_out.write(dup_rows);
             }
             uint64_t added = 0;
             if (a.call) {
@@ -4285,12 +4325,18 @@ int run_map(const MapArgs &a) {
         if (a.extend && a.has_pileup_out) pile_file.finish();
     }
     if (prints) out.finish();
+    uint64_t reads_keyed = 0, distinct_fragments = 0; // (markdup)
+    if (a.markdup) deacon::check(dcn_anchor_map_duplicates_info(R.map.p, nullptr, &reads_keyed, &distinct_fragments));
+    if (a.has_duplicates) dup_out.finish();
     const double secs = watch.seconds();
     if (!a.quiet) {
         if (a.extend)
             std::fprintf(stderr, "Extended %llu of %llu placements by %llu bases (%llu bases clipped, %llu placements full length)\n",
                          (unsigned long long)rows_extended, (unsigned long long)placements, (unsigned long long)bases_gained,
                          (unsigned long long)bases_clipped, (unsigned long long)full_length_rows);
+        if (a.markdup)
+            std::fprintf(stderr, "Marked %llu of %llu reads with an end as duplicates%s\n", (unsigned long long)(reads_keyed - distinct_fragments),
+                         (unsigned long long)reads_keyed, a.keep_duplicates ? " (kept)" : "");
         if (piles)
             std::fprintf(stderr, "Piled up %llu of %llu placements on %llu positions (%llu sites)\n", (unsigned long long)rows_added,
                          (unsigned long long)placements, (unsigned long long)covered, (unsigned long long)n_sites);
@@ -4360,6 +4406,11 @@ int run_map(const MapArgs &a) {
                         "  \"het_sites\": %llu,\n  \"hom_alt_sites\": %llu,\n",
                     a.ploidy, a.min_gq, a.min_qual, (unsigned long long)genotyped_positions, (unsigned long long)vcf_sites,
                     (unsigned long long)het_sites, (unsigned long long)hom_alt_sites);
+        if (a.markdup)
+            appendf(js, "  \"duplicates_both_ends\": %s,\n  \"keep_duplicates\": %s,\n  \"reads_keyed\": %llu,\n  \"duplicate_reads\": %llu,\n"
+                        "  \"distinct_fragments\": %llu,\n",
+                    a.both_ends ? "true" : "false", a.keep_duplicates ? "true" : "false", (unsigned long long)reads_keyed,
+                    (unsigned long long)(reads_keyed - distinct_fragments), (unsigned long long)distinct_fragments);
         appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
         for (uint32_t r = 0; r < R.n_records; ++r) {
             js += (r ? ",\n    {" : "\n    {");
@@ -4512,6 +4563,7 @@ void usage() {
                  "  consensus  As extend and pileup, keeping inserted bases: the sequence the reads support as FASTA, and its variants\n"
                  "  call    As consensus, with the reads' base qualities: low-quality bases do not vote, variants carry mean qualities\n"
                  "  genotype  As call, with a genotype per position from counts and quality sums: GQ, PL, QUAL, SNV sites as VCF\n"
+                 "  markdup  As genotype, with reads that repeat the unclipped end of an earlier read marked and left out first\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -5047,6 +5099,106 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "counted bases A C G T, in integers (hundredths of a phred), and a matching base costs nothing.  The constants and\n"
                "thresholds are conventions, not measured optima.  SNVs only: no indels in the VCF, no priors, no strand or mapping\n"
                "quality terms, no phasing, no affine gaps.  Mates are independent here: one input.\n";
+    else if (sub == "markdup")
+        text = "Mark the reads whose placement repeats the unclipped 5' end of an earlier read's (PCR and optical duplicates),\n"
+               "leave them out, and pile the rest up and genotype it as genotype does\n\n"
+               "Usage: deacon-hip markdup [OPTIONS] <REF> [READS]\n\n"
+               "Arguments:\n"
+               "  <REF>     Path to the reference fastx file: its records are numbered and named in file order\n"
+               "  [READS]   Optional path to FASTQ file (or - for stdin; gz, bgzf, zst, xz and bz2 found by content) [default: -]\n"
+               "            A record without a quality line (FASTA) is an error: consensus takes such reads\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Keys that may anchor: a minimizer index file, whose k and w are used\n"
+               "                                 [default: the minimizers of <REF> at -k / -w]\n"
+               "  -k <K>                         K-mer length without -x [default: 31]\n"
+               "  -w <W>                         Minimizer window size without -x [default: 15]\n"
+               "  -o, --output <OUTPUT>          FASTA: per record of <REF> a line >name and its consensus on one line (- for\n"
+               "                                 stdout) [default: no FASTA]\n"
+               "      --variants <FILE>          TSV: record pos type ref alt depth count events, pos 0-based as in PAF; one SUB line\n"
+               "                                 per substituted position, one DEL line per deleted position (alt -), one INS or\n"
+               "                                 INS_FRONT line per called insertion behind or in front of pos (ref ., count = the\n"
+               "                                 reads with exactly these bases, events = all insertions there; 0 on other lines)\n"
+               "                                 With two more columns, ref_qual alt_qual: on a SUB line the mean quality, rounded\n"
+               "                                 down, of the counted bases that show the reference's base and of those that show\n"
+               "                                 alt (. for none, or for a reference base that is not ACGT); . on every other line\n"
+               "      --vcf <FILE>               VCF 4.2, SNVs only (- for stdout; .gz as BGZF, .zst and .xz by extension): one line per\n"
+               "                                 position whose genotype is called and is\n"
+               "                                 not the reference's, with QUAL, INFO DP (all reads there) and GT:GQ:DP:AD:PL over\n"
+               "                                 the reference's base and the genotype's other bases; insertions and deletions stay\n"
+               "                                 in --variants [default: no VCF]\n"
+               "      --ploidy <1|2>             Genotypes of one base (A C G T) or of two (AA AC CC AG CG GG AT CT GT TT) [default: 2]\n"
+               "      --min-gq <N>               A genotype is called at a genotype quality of at least N: the phred gap between the\n"
+               "                                 best and the second best genotype (0..99) [default: 20, a convention]\n"
+               "      --min-qual <N>             A site needs QUAL of at least N: the phred gap between the reference's homozygote and\n"
+               "                                 the best genotype [default: 20, a convention]\n"
+               "      --sample <NAME>            The sample column's name [default: sample]\n"
+               "      --keep-duplicates          Mark and report the duplicates, but pile every read up: the other outputs are\n"
+               "                                 genotype's\n"
+               "      --both-ends                A duplicate repeats the unclipped 3' end of the earlier read as well\n"
+               "      --duplicates <FILE>        TSV: read ordinal first record strand pos5, one line per duplicate read in input\n"
+               "                                 order: its name, its number in the input from 0, the number of the first read\n"
+               "                                 with the same end, and the end: pos5 is 0-based and may be negative or past the\n"
+               "                                 record's end [default: no TSV]\n"
+               "      --fill-ref                 A position without a call takes the reference's base, not N\n"
+               "      --min-baseq <Q>            A base of quality below Q counts as N: it adds to the depth and never wins\n"
+               "                                 (0..255) [default: 20, a convention]\n"
+               "      --qual-offset <N>          The quality of a base is its quality character minus N, 0 when that is negative\n"
+               "                                 (0..255) [default: 33]\n"
+               "      --pileup <FILE>            pileup's TSV over the extended placements: record pos ref A C G T N del ins rev, then\n"
+               "                                 qA qC qG qT: the sums of the qualities of the bases counted in A C G T\n"
+               "      --sites <FILE>             pileup's site TSV over them: record pos ref call depth flags\n"
+               "      --all-positions            One line of --pileup for every position of every record\n"
+               "      --min-depth <N>            A call needs a depth of at least N, a genotype as many bases A C G T\n"
+               "                                 [default: 3, a convention]\n"
+               "      --min-frac <N>             ... and N per 1000 of the depth for the most frequent of A C G T and gap, and\n"
+               "                                 for the insertions at a position (0..1000) [default: 500, a convention]\n"
+               "      --min-mapq <N>             Only placements of mapping quality N or more add (0..60) [default: 1, a convention]\n"
+               "      --all-ranks                Every placement of a read adds, not only its first (rank 0)\n"
+               "      --penalty <N>              An edit in a flank costs N matched bases of read plus record (2..255)\n"
+               "                                 [default: 6, a convention]\n"
+               "      --end-bonus <N>            Reaching the read's end is worth N (0..65535) [default: 4, a convention]\n"
+               "      --ext-max-edits <N>        At most N edits per flank (0..1023) [default: 1023, a convention]\n"
+               "  -e, --max-edits <N>            Only placements of at most N edits over the extended extents add (0..1023)\n"
+               "                                 [default: 1023, a convention]\n"
+               "      --max-div <N>              ... and of at most N per 1000 bases of the longer extended extent (0..1000)\n"
+               "                                 [default: 200, a convention]\n"
+               "  -N, --max-placements <N>       Placements per read, each from the anchor hits no earlier one explained (1..8)\n"
+               "                                 [default: 4]\n"
+               "      --band <N>                 Width of a diagonal band in bases [default: 256, a convention]\n"
+               "  -a, --min-votes <N>            Minimum number of anchor hits in a placement's cell [default: 2, as filter's -a,\n"
+               "                                 a convention]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per read (0 = entire read) [default: 0]\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file: extend's and pileup's keys, and fill_ref,\n"
+               "                                 insertion_events, inserted_bases, insertion_alleles, substitutions,\n"
+               "                                 deleted_positions, consensus_bases and uncalled_positions; min_base_qual,\n"
+               "                                 qual_offset and quality_sums, the totals of qA qC qG qT; ploidy, min_gq, min_qual,\n"
+               "                                 genotyped_positions, vcf_sites, het_sites and hom_alt_sites; duplicates_both_ends,\n"
+               "                                 keep_duplicates, reads_keyed (reads with an end), duplicate_reads and\n"
+               "                                 distinct_fragments\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
+               "  -h, --help                     Print help\n\n"
+               "Consensus, position by position of a record: the bases of an insertion called in front of the position; the\n"
+               "called base, nothing where a gap is called, N (or the reference's base with --fill-ref) where nothing is; the\n"
+               "bases of an insertion called behind it.  An insertion is called where the reads with an insertion there reach\n"
+               "--min-frac of a depth of at least --min-depth; its bases are those most of them agree on (on a tie one behind\n"
+               "the position before one in front, then the shorter, then the first by letter), whatever their own share: count\n"
+               "and events say what it is.  The thresholds are conventions, not measured optima.  Integers and bytes only: the\n"
+               "output does not depend on how the input is cut into batches.  Deleted positions are not merged, indels are not\n"
+               "left-normalised.  Qualities: alignment does not look at them, so the placements and their edits are consensus's;\n"
+               "only what a base counts as changes.  With --min-baseq 0 the FASTA is consensus's.  The qualities of inserted bases\n"
+               "are not looked at.  -o, --variants, --pileup and --sites are call's, byte for byte.  Genotypes: a base of quality q\n"
+               "that a genotype does not explain costs q + 4.77 phred, a base of a heterozygote 3.01; the costs are sums over the\n"
+               "counted bases A C G T, in integers (hundredths of a phred), and a matching base costs nothing.  The constants and\n"
+               "thresholds are conventions, not measured optima.  SNVs only: no indels in the VCF, no priors, no strand or mapping\n"
+               "quality terms, no phasing, no affine gaps.\n"
+               "Duplicates: the end of a read is the record, the strand and the unclipped 5' coordinate of its first placement\n"
+               "that --min-mapq and the rank leave, so soft clips do not matter; a read whose end an earlier read of the input had\n"
+               "is a duplicate, and none of its placements adds.  First seen wins: a streaming rule, not a best-quality rule, so\n"
+               "the order of the input matters and how it is cut into batches does not.  The comparison is exact.  No\n"
+               "optical-distance rule; nothing is read from the bases or the qualities.  Mates are independent here: one input,\n"
+               "and a read is a unit.  Pairs as units (one key from both mates' ends) are a feature of the library\n"
+               "(dcn_mark_duplicates_batch) and of the Python layer (AnchorMap.mark_duplicates), not of this mode.\n";
     else if (sub == "map-pairs")
         text = "Place the two mates of each pair jointly on a reference: proper pairs, rescued mates and insert sizes, as PAF\n\n"
                "Usage: deacon-hip map-pairs [OPTIONS] <REF> <READS1> [READS2]\n\n"
@@ -5338,11 +5490,12 @@ int main(int argc, char **argv) {
             return run_place(a);
         }
         if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup" || args[0] == "extend" || args[0] == "consensus" ||
-            args[0] == "call" || args[0] == "genotype") {
+            args[0] == "call" || args[0] == "genotype" || args[0] == "markdup") {
             MapArgs a;
             a.align = args[0] == "align";
             a.pileup = args[0] == "pileup";
-            a.genotype = args[0] == "genotype";
+            a.markdup = args[0] == "markdup";
+            a.genotype = args[0] == "genotype" || a.markdup;
             a.call = args[0] == "call" || a.genotype;
             a.consensus = args[0] == "consensus" || a.call;
             a.extend = args[0] == "extend" || a.consensus;
@@ -5370,6 +5523,9 @@ int main(int argc, char **argv) {
                 else if (a.genotype && s == "--min-gq") a.min_gq = (unsigned)number(need(++i), "--min-gq", 0, 99);
                 else if (a.genotype && s == "--min-qual") a.min_qual = (unsigned)number(need(++i), "--min-qual", 0, 0xFFFFFFFFll);
                 else if (a.genotype && s == "--sample") a.sample = need(++i);
+                else if (a.markdup && s == "--keep-duplicates") a.keep_duplicates = true;
+                else if (a.markdup && s == "--both-ends") a.both_ends = true;
+                else if (a.markdup && s == "--duplicates") a.duplicates = need(++i), a.has_duplicates = true;
                 else if (s == "-o" || s == "--output") a.output = need(++i), a.has_output = true;
                 else if (a.extend && s == "--penalty") a.penalty = (unsigned)number(need(++i), "--penalty", 2, 255);
                 else if (a.extend && s == "--end-bonus") a.end_bonus = (unsigned)number(need(++i), "--end-bonus", 0, 65535);

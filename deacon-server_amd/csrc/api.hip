@@ -446,6 +446,7 @@ extern "C" int dcn_index_clone(const dcn_index *index, int device, dcn_index **o
     idx->pileup_rows = 0;
     idx->ledger = nullptr; // ... nor an insertion ledger
     idx->d_pileup_qsums = nullptr; // ... nor quality sums
+    idx->dups = nullptr; // ... nor a duplicate set
     const uint64_t bytes = idx->n_groups * DCN_GROUP_SLOTS * sizeof(uint64_t);
     // Another GPU: the keys cross the link, not the table (a tenth of the bytes at the default 8 slots per key; dcn_table_clone_by_keys).
     // The same GPU: a device-to-device copy of the table at HBM's pace.  DCN_CLONE_BY_KEYS=1 / DCN_CLONE_BY_COPY=1 force one form
@@ -502,6 +503,7 @@ extern "C" void dcn_index_destroy(dcn_index *index) {
     if (index->d_pileup) hipFree(index->d_pileup);
     dcn_ins_ledger_free(index->ledger);
     if (index->d_pileup_qsums) hipFree(index->d_pileup_qsums);
+    dcn_dup_set_free(index->dups);
     delete index;
 }
 

@@ -84,6 +84,8 @@ struct dcn_base_store; // (dcn_verify.h)
 void dcn_base_store_free(dcn_base_store *s);
 struct dcn_ins_ledger; // (dcn_verify.h)
 void dcn_ins_ledger_free(dcn_ins_ledger *l);
+struct dcn_dup_set; // (dcn_verify.h)
+void dcn_dup_set_free(dcn_dup_set *d);
 
 struct dcn_index {
     // captured when the index is created (built, loaded, merged, cloned): the rule its keys were selected by travels
@@ -127,6 +129,9 @@ struct dcn_index {
     // ... and the quality sums beside the counters (dcn_anchor_map_pileup_keep_qualities, pileup_api.hip): 4 words per base
     // of the pileup, laid out by dcn_pile_sum_index (dcn_pileup.h).  Null: none are kept.
     uint32_t *d_pileup_qsums = nullptr;
+    // ... and the duplicate set (dcn_anchor_map_duplicates_enable, duplicates_api.hip), which needs neither the bases nor
+    // the pileup.  Null: none is kept.
+    dcn_dup_set *dups = nullptr;
     dcn_table_view view() const {
         dcn_table_view v;
         v.slots = d_slots;

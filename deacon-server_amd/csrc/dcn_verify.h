@@ -90,13 +90,21 @@ int check_range(const dcn_index *map, const char *who, uint32_t record, uint64_t
 // promise: max_edits, max_permille, row_stride, the context, the map, the batch and row_offsets.  *run is whether there is
 // anything to walk (reads and rows; `rows` is not NULL then); *n_bases the bases of the batch.
 int rows_check(const dcn_row_call &call, bool *run, uint64_t *n_bases);
+// Two parts of rows_check for a call that has no context and no bases (dcn_mark_duplicates_batch): the row_stride, and
+// everything behind the context and the map -- n_rows against n_reads, offsets, row_offsets, rows.  With call.ctx NULL
+// the offsets are walked without a context's limits and call.bases is not looked at.
+int rows_stride_check(uint32_t row_stride);
+int rows_shape_check(const dcn_row_call &call, bool *run, uint64_t *n_bases);
 
 // The walk over the rows of a checked call: every placed row against its read and its record, then
 // row_fn(row, placement, read_offset, read_length, record_start, record_length), which makes of the row what its kernel
 // takes.  An unplaced row (record == UINT32_MAX) is handed over unchecked, with a record of 0 bases at 0.
+// A map that keeps no bases (dcn_mark_duplicates_batch alone walks one) has no record lengths on the host: its rows are
+// checked against the number of records added, ref_end against nothing, and row_fn gets a record of 0 bases at 0.
 template <typename RowFn>
 int rows_walk(const dcn_row_call &call, RowFn &&row_fn) {
     const dcn_base_store *store = call.map->store;
+    const uint64_t n_records = store ? store->rec_len.size() : call.map->anchor_records;
     uint64_t row = 0;
     for (uint32_t r = 0; r < call.n_reads; ++r) {
         const uint64_t row_end = call.row_offsets ? call.row_offsets[r + 1] : (uint64_t)r + 1;
@@ -110,13 +118,17 @@ int rows_walk(const dcn_row_call &call, RowFn &&row_fn) {
             }
             // (the message is put together only when a row is wrong: ten million rows are walked here per call)
             const auto bad = [row](const std::string &what) { return dcn_fail(DCN_ERR_ARG, "row " + std::to_string(row) + ": " + what); };
-            if (p.record >= store->rec_len.size())
-                return bad("record " + std::to_string(p.record) + " of " + std::to_string(store->rec_len.size()) + " added");
+            if (p.record >= n_records)
+                return bad("record " + std::to_string(p.record) + " of " + std::to_string(n_records) + " added");
             if (p.reverse > 1) return bad("reverse must be 0 or 1");
             if (p.read_start > p.read_end) return bad("read_start is behind read_end");
             if (p.read_end > read_len)
                 return bad("read_end " + std::to_string(p.read_end) + " is past the read's " + std::to_string(read_len) + " bases");
             if (p.ref_start > p.ref_end) return bad("ref_start is behind ref_end");
+            if (!store) {
+                row_fn(row, p, call.offsets[r], read_len, (uint64_t)0, (uint64_t)0);
+                continue;
+            }
             const uint64_t rec_len = store->rec_len[p.record];
             if (p.ref_end > rec_len)
                 return bad("ref_end " + std::to_string(p.ref_end) + " is past the record's " + std::to_string(rec_len) + " bases");
@@ -261,6 +273,46 @@ struct dcn_genotype_args {
 uint32_t dcn_genotype_blocks(uint64_t base0, uint64_t n);    // workgroups of a range
 uint64_t dcn_genotype_out_bytes(uint64_t base0, uint64_t n); // bytes of args.gt and of args.gq
 int dcn_launch_genotype(const dcn_genotype_args &args, bool write, hipStream_t stream);
+
+// ---- duplicate marking (duplicates.hip, duplicates_api.hip; the shared arithmetic is in dcn_duplicates.h) ---------------
+struct dcn_dup_item; // (dcn_duplicates.h)
+struct dcn_dup_key;
+// The duplicate set of a map (dcn_anchor_map_duplicates_enable): the key log, one 48-byte key per unit handed in since the
+// last reset, indexed by ordinal and growing geometrically; the table of 8-byte slots, each an ordinal or DCN_DUP_EMPTY, a
+// power of two of them that starts at DCN_DUPLICATE_TABLE_SLOTS (read when the set first grows) and doubles; rule D1's
+// three counters, which live on the host; and the buffers of a call, which live with the set and only grow.
+struct dcn_dup_set {
+    dcn_dup_key *d_log = nullptr;
+    uint64_t log_cap = 0;
+    unsigned long long *d_slots = nullptr;
+    uint64_t n_slots = 0;
+    uint64_t seen = 0, keyed = 0, keys = 0;
+    dcn_dup_item *d_items = nullptr;
+    uint64_t items_cap = 0;
+    uint8_t *d_dup = nullptr;
+    uint64_t dup_cap = 0;
+    uint64_t *d_first = nullptr;
+    uint64_t first_cap = 0;
+    unsigned long long *d_n_dup = nullptr;
+};
+void dcn_dup_set_free(dcn_dup_set *d);
+
+struct dcn_dup_args {
+    const dcn_dup_item *items; // one per read of the call
+    uint64_t n_units, ord0;    // unit u has ordinal ord0 + u
+    uint32_t paired, both_ends;
+    dcn_dup_key *log;          // by ordinal
+    unsigned long long *slots;
+    uint64_t mask;             // slots - 1
+    uint8_t *dup;              // per unit
+    uint64_t *first;
+    unsigned long long *n_dup; // added to
+};
+int dcn_launch_dup_keys(const dcn_dup_args &args, hipStream_t stream);
+int dcn_launch_dup_insert(const dcn_dup_args &args, hipStream_t stream);
+int dcn_launch_dup_lookup(const dcn_dup_args &args, hipStream_t stream);
+// every occupied slot of old_slots[0, n_old) into args.slots, which is empty or holds other keys
+int dcn_launch_dup_rehash(const dcn_dup_args &args, const unsigned long long *old_slots, uint64_t n_old, hipStream_t stream);
 
 // ---- extended placements (extend.hip, extend_api.hip; the shared arithmetic is in dcn_extend.h) ----------------------
 // One flank of one row as the kernel takes it: item 2 r is the left flank of row r, item 2 r + 1 its right flank.  The

@@ -136,11 +136,22 @@ int dcn_impl::rows_check(const dcn_row_call &call, bool *run, uint64_t *n_bases)
     if (call.max_edits > DCN_VERIFY_MAX_EDITS)
         return dcn_fail(DCN_ERR_ARG, "params.max_edits must be 0.." + std::to_string(DCN_VERIFY_MAX_EDITS));
     if (call.max_permille > 1000) return dcn_fail(DCN_ERR_ARG, "params.max_permille must be 0..1000");
-    if (call.row_stride < sizeof(dcn_placement) || call.row_stride % 8 != 0)
-        return dcn_fail(DCN_ERR_ARG, "params.row_stride must be at least 48 and a multiple of 8");
+    DCN_TRY(rows_stride_check(call.row_stride));
     if (!call.ctx) return dcn_fail(DCN_ERR_ARG, "ctx is NULL");
     DCN_TRY(check_store(call.map));
     DCN_TRY(check_ctx_matches(call.ctx, call.map, "the map"));
+    return rows_shape_check(call, run, n_bases);
+}
+
+int dcn_impl::rows_stride_check(uint32_t row_stride) {
+    if (row_stride < sizeof(dcn_placement) || row_stride % 8 != 0)
+        return dcn_fail(DCN_ERR_ARG, "params.row_stride must be at least 48 and a multiple of 8");
+    return DCN_OK;
+}
+
+int dcn_impl::rows_shape_check(const dcn_row_call &call, bool *run, uint64_t *n_bases) {
+    *run = false;
+    *n_bases = 0;
     const uint32_t n_reads = call.n_reads;
     const uint64_t *const offsets = call.offsets, *const row_offsets = call.row_offsets;
     if (!row_offsets && call.n_rows != n_reads)
@@ -150,9 +161,10 @@ int dcn_impl::rows_check(const dcn_row_call &call, bool *run, uint64_t *n_bases)
         return DCN_OK;
     }
     if (!offsets) return dcn_fail(DCN_ERR_ARG, "offsets is NULL");
-    DCN_TRY(validate_host_batch(call.ctx, offsets, n_reads));
+    if (call.ctx) DCN_TRY(validate_host_batch(call.ctx, offsets, n_reads));
+    else DCN_TRY(check_offsets_walk(offsets, n_reads, "offsets", "read longer than 2^32 bases"));
     *n_bases = offsets[n_reads];
-    if (*n_bases > 0 && !call.bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
+    if (call.ctx && *n_bases > 0 && !call.bases) return dcn_fail(DCN_ERR_ARG, "bases is NULL");
     if (row_offsets) {
         if (row_offsets[0] != 0) return dcn_fail(DCN_ERR_ARG, "row_offsets[0] must be 0");
         for (uint32_t r = 0; r < n_reads; ++r)

@@ -811,6 +811,45 @@ class AnchorMap(Index):
         N.check(rc)
         return gt[:n], gq[:n], sites[:int(n_sites.value)]
 
+    def duplicates_enable(self):
+        """An empty duplicate set on the map (dcn_anchor_map_duplicates_enable; the definition of a duplicate is in
+        include/deacon_hip.h); again changes nothing.  The map need not keep bases."""
+        N.check(N.lib().dcn_anchor_map_duplicates_enable(self._h, 1))
+
+    def duplicates_disable(self):
+        N.check(N.lib().dcn_anchor_map_duplicates_enable(self._h, 0))
+
+    def duplicates_reset(self):
+        """the set empty and the ordinals back at 0"""
+        N.check(N.lib().dcn_anchor_map_duplicates_reset(self._h))
+
+    def duplicates_info(self):
+        """-> (seen, keyed, keys): units handed in since the last reset, those with a key, the distinct keys; the number of
+        duplicates so far is keyed - keys"""
+        seen, keyed, keys = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        N.check(N.lib().dcn_anchor_map_duplicates_info(self._h, C.byref(seen), C.byref(keyed), C.byref(keys)))
+        return int(seen.value), int(keyed.value), int(keys.value)
+
+    def mark_duplicates(self, offsets, rows, row_offsets=None, paired=False, both_ends=False):
+        """Rules D1-D7 over the rows of a batch (dcn_mark_duplicates_batch): offsets are the batch's (only the reads' lengths
+        are taken from them), rows and row_offsets as Placer.verify_batch takes them.  A unit is a read, or with paired=True
+        reads 2u and 2u + 1; its key is the unclipped 5' end (with both_ends also the 3' end) of the first placed row of each
+        of its reads, and it is a duplicate when a unit handed in earlier since the last reset, in this call or a call before
+        it, had the same key.  -> (dup np.uint8[units], first np.uint64[units]: the ordinal of the first unit with the key,
+        2^64 - 1 for a unit without one)."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n_reads = len(offsets) - 1
+        rows = np.ascontiguousarray(rows)
+        n_rows = len(rows)
+        if row_offsets is not None:
+            row_offsets = np.ascontiguousarray(row_offsets, dtype=np.uint64)
+        n_units = n_reads // 2 if paired else n_reads
+        dup, first = np.zeros(max(n_units, 1), np.uint8), np.zeros(max(n_units, 1), np.uint64)
+        p = N.DuplicateParams(rows.dtype.itemsize, int(bool(paired)), int(bool(both_ends)), 0)
+        N.check(N.lib().dcn_mark_duplicates_batch(self._h, _ptr(offsets), n_reads, C.byref(p), _ptr(row_offsets), _ptr(rows) if n_rows else None,
+                                                  n_rows, _ptr(dup), _ptr(first), None))
+        return dup[:n_units], first[:n_units]
+
     def insertions_info(self):
         """-> (events of the ledger, the sum of their lengths)"""
         n_events, n_bases = C.c_uint64(), C.c_uint64()

@@ -82,9 +82,10 @@ enum {
  * 1.16 = dcn_extend_batch.
  * 1.17 = dcn_anchor_map_pileup_keep_insertions, dcn_anchor_map_insertions_info / _fetch / _call.
  * 1.18 = dcn_anchor_map_pileup_keep_qualities / _fetch_qualities, dcn_pileup_batch_qual.
- * 1.19 = dcn_anchor_map_genotype. */
+ * 1.19 = dcn_anchor_map_genotype.
+ * 1.20 = dcn_anchor_map_duplicates_enable / _reset / _info, dcn_mark_duplicates_batch. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 19
+#define DCN_ABI_MINOR 20
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -1219,6 +1220,79 @@ typedef struct dcn_genotype_site {
  * range (DCN_GRID_CUS does not apply).  No new memory on the map and no pass over reads. */
 int dcn_anchor_map_genotype(const dcn_index *map, const void *params, uint32_t record, uint64_t start, uint64_t n_bases,
                             uint8_t *gt, uint8_t *gq, void *sites, uint64_t capacity, uint64_t *n_sites);
+
+/* ---- duplicates: a first-seen key set on the map, kept across batches (ABI 1.20) --------------------------------------
+ * (no reference counterpart.)  Rule G2 charges every counted base as an independent observation, and rule P2 leaves to the
+ * caller which rows count: "a caller leaves a row out by setting its record to UINT32_MAX".  Copies of one fragment (PCR,
+ * optical) are not independent, and what tells them apart from two fragments is where their ends lie.  This is the
+ * device-side answer to "has a fragment with these ends been seen before?".
+ *
+ * THE DEFINITION OF A DUPLICATE.  Rules 1-2 of a verified placement stand for what a row is.  Added:
+ *   D1. The set.  An anchor map may keep a DUPLICATE SET: keys, for each key the smallest ordinal of a unit that carried
+ *       it, and a counter `seen` of the units handed in.  It is empty with seen = 0 when switched on and after a reset.  It
+ *       needs neither kept bases nor a pileup.
+ *   D2. Units.  A call hands in the rows of n_reads reads, with row_offsets as in dcn_verify_batch (NULL: row r belongs to
+ *       read r).  In single mode unit u is read u.  In paired mode n_reads is even and unit u is reads 2u and 2u + 1.  Unit
+ *       u of a call has ordinal seen + u, and after the call seen has grown by the number of units, keyed or not: with one
+ *       call per input batch an ordinal is the read's (the pair's) number in the input.
+ *   D3. Ends.  The END of a read is taken from its first row with record != UINT32_MAX; a read with no such row has no
+ *       end.  With L the read's length from `offsets`:
+ *         pos5 = ref_start - read_start on a forward row, ref_end + read_start on a reverse row:
+ *       the unclipped 5' coordinate, a signed 64-bit number that may be negative or lie past the record's end.  The end is
+ *       (record, reverse, pos5).  With both_ends it also has
+ *         pos3 = ref_end + (L - read_end) on a forward row, ref_start - (L - read_end) on a reverse row.
+ *       Clips therefore do not matter: (ref_start 100, read_start 0) and (ref_start 105, read_start 5) on one strand are
+ *       the same end.
+ *   D4. Key.  The key has three parts: the mode bits (paired, both_ends), the number of ends, and the ends.  A single unit
+ *       with an end has one end.  A paired unit has the ends of whichever mates have one, two of them sorted ascending as
+ *       tuples (record, pos5, reverse[, pos3]): a pair and the same pair with its mates swapped have one key.  A unit with
+ *       no end has no key.  Two keys are equal only when every component is equal; keys of different modes or with
+ *       different numbers of ends never match.  Comparison is exact: no decision rests on a hash alone.
+ *   D5. Duplicate.  After the call's units are in the set, first(u) is the smallest ordinal that carries u's key, over
+ *       everything since the last reset, this call included.  Unit u is a DUPLICATE when first(u) is smaller than its own
+ *       ordinal.  A unit without a key is never a duplicate, and its first is UINT64_MAX.
+ *   D6. Determinism.  First seen wins: a streaming rule, not a best-quality rule.  The flags depend on the order of the
+ *       units in the input.  They do not depend on how the input is cut into calls (as long as no pair is cut), on lanes,
+ *       on the table's size or on the hash.  Integers only.
+ *   D7. Stated limits.  A lone mate is not matched against the ends of pairs.  The orientation is whatever the rows say.
+ *       There is no optical-distance rule.  Nothing is read from the bases or the qualities. */
+typedef struct dcn_duplicate_params {
+    uint32_t row_stride; /* as in dcn_verify_params */
+    uint32_t paired;     /* 0 | 1 */
+    uint32_t both_ends;  /* 0 | 1 */
+    uint32_t reserved;   /* must be 0 */
+} dcn_duplicate_params;  /* 16 bytes */
+
+/* Switches the duplicate set of an anchor map on (enable != 0: again changes nothing) or off (0: frees it).  DCN_ERR_ARG
+ * for an index that is not a map.  Device memory, which dcn_index_memory does not count, from the first call that hands
+ * units in: 48 bytes per unit handed in since the last reset (the key log, growing geometrically) and 8 bytes per slot of
+ * a table that keeps at least two slots per key and doubles (a power of two; the test hook DCN_DUPLICATE_TABLE_SLOTS, read
+ * when the set first grows, sets the capacity it starts with, 2^20 otherwise), and 40 bytes per read plus 9 per unit of the
+ * largest call.  dcn_index_clone gives an index without the set, dcn_index_destroy frees it; dcn_anchor_map_add stays
+ * allowed while a set is kept. */
+int dcn_anchor_map_duplicates_enable(dcn_index *map, int enable);
+/* Empties the set and puts seen back to 0; the memory stays.  DCN_ERR_ARG for a map without a set. */
+int dcn_anchor_map_duplicates_reset(dcn_index *map);
+/* seen: units handed in since the last reset; keyed: those with a key; keys: the distinct keys.  The number of duplicates
+ * so far is keyed - keys.  Any pointer may be NULL.  DCN_ERR_ARG for a map without a set.  No device work. */
+int dcn_anchor_map_duplicates_info(const dcn_index *map, uint64_t *seen, uint64_t *keyed, uint64_t *keys);
+/* Rules D1-D7 over the rows of n_reads reads.
+ *   offsets       n_reads + 1 entries, as in dcn_verify_batch: only the reads' lengths are taken from them (no bases)
+ *   params        a dcn_duplicate_params (declared void * for the reason given at dcn_locate_batch)
+ *   row_offsets, rows, n_rows   as in dcn_verify_batch; only the 48 bytes at the head of a row are read
+ *   dup, first    each NULL, or one entry per unit (n_reads units, n_reads / 2 in paired mode): D5's flag (0 | 1) and first
+ *   n_duplicates  NULL, or receives the number of duplicates among the call's units
+ * DCN_ERR_ARG, before any device work and with the set and seen untouched: params NULL, reserved != 0, paired > 1,
+ * both_ends > 1, then dcn_verify_batch's checks in its order and with its messages (row_stride; the map, which here must be
+ * an anchor map with a duplicate set and need not keep bases; n_rows against n_reads -- and here an odd n_reads in paired
+ * mode; offsets; row_offsets; rows; then every placed row, the message naming the first wrong one).  A map that keeps no
+ * bases knows no record lengths: ref_end is then checked against nothing.  Host pointers, blocking, on the null stream;
+ * one call at a time per map.  Three kernels, one thread per unit, grids sized by the batch (DCN_GRID_CUS does not apply):
+ * the keys into the log, the insert, the lookup; in front of them the table grows, by a rehash kernel, so that it has at
+ * least 2 * (keys + units of the call) slots. */
+int dcn_mark_duplicates_batch(dcn_index *map, const uint64_t *offsets, uint32_t n_reads, const void *params,
+                              const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint8_t *dup, uint64_t *first,
+                              uint64_t *n_duplicates);
 
 /* ---- extended placements: each placement carried over the read's flanks, with soft clips (ABI 1.16) -------------------
  * (no reference counterpart.)  A placement's two intervals begin and end on the k-mer of an anchor hit: the read's bases
