@@ -242,6 +242,48 @@ class DuplicateParams(C.Structure):
     ]
 
 
+class Deletion(C.Structure):
+    _fields_ = [
+        ("pos", C.c_uint64),
+        ("len", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+DELETION_REVERSE = 1  # DCN_DELETION_REVERSE: the flag of an event of a deletion ledger
+INDEL_DELETION, INDEL_FRONT = 1, 2  # DCN_INDEL_*: the flags of an indel site
+
+
+class IndelParams(C.Structure):
+    _fields_ = [
+        ("ploidy", C.c_uint32),
+        ("min_depth", C.c_uint32),
+        ("min_gq", C.c_uint32),
+        ("min_qual", C.c_uint32),
+        ("min_count", C.c_uint32),
+        ("indel_centi", C.c_uint32),
+        ("het_centi", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class IndelSite(C.Structure):
+    _fields_ = [
+        ("pos", C.c_uint64),
+        ("bases_offset", C.c_uint64),
+        ("len", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("qual", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("count", C.c_uint32),
+        ("events", C.c_uint32),
+        ("gt", C.c_uint8),
+        ("gq", C.c_uint8),
+        ("pl", C.c_uint8 * 3),
+        ("reserved", C.c_uint8 * 3),
+    ]
+
+
 class ExtendParams(C.Structure):
     _fields_ = [
         ("penalty", C.c_uint32),
@@ -392,10 +434,14 @@ _SIGNATURES = {
     "dcn_anchor_map_duplicates_reset": (C.c_int, [_vp]),
     "dcn_anchor_map_duplicates_info": (C.c_int, [_vp, _u64p, _u64p, _u64p]),
     "dcn_mark_duplicates_batch": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _u64p]),
+    "dcn_anchor_map_pileup_keep_deletions": (C.c_int, [_vp, C.c_int]),
+    "dcn_anchor_map_deletions_info": (C.c_int, [_vp, _u64p, _u64p]),
+    "dcn_anchor_map_deletions_fetch": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _u64p]),
+    "dcn_anchor_map_indels_genotype": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _u64p, _u64p]),
 }
 
 _lib = None
-ABI = (1, 20)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 21)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

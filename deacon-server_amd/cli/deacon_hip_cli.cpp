@@ -3844,6 +3844,10 @@ struct MapArgs {
     // rows) left out of the pile-up, or with --keep-duplicates only marked and reported; genotype and all it sets are set
     bool markdup = false, keep_duplicates = false, both_ends = false, has_duplicates = false;
     std::string duplicates;
+    // `indels`: markdup on a map that also keeps a deletion ledger, with the genotype of the winning insertion and the winning
+    // deletion of every position (dcn_anchor_map_indels_genotype) as INDEL lines of the VCF; markdup and all it sets are set
+    bool indels = false;
+    unsigned indel_qual = 20, min_indel_count = 2;
 };
 
 // one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
@@ -3893,7 +3897,7 @@ void append_paf(std::string &rows, const std::string &read_name, uint32_t read_l
 int run_map(const MapArgs &a) {
     const Stopwatch watch;
     const auto no_qualities = [&a](const std::string &name) {
-        die(std::string(a.markdup ? "markdup" : a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
+        die(std::string(a.indels ? "indels" : a.markdup ? "markdup" : a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
     };
     std::unique_ptr<FastxReader> reads; // (`call` looks at the first record before the reference is loaded)
     if (a.call) {
@@ -3913,6 +3917,7 @@ int run_map(const MapArgs &a) {
     if (piles) deacon::check(dcn_anchor_map_pileup_enable(R.map.p, 1)); // (after the records: a pileup does not grow)
     if (a.consensus) deacon::check(dcn_anchor_map_pileup_keep_insertions(R.map.p, 1)); // (before the first row adds)
     if (a.call) deacon::check(dcn_anchor_map_pileup_keep_qualities(R.map.p, 1));
+    if (a.indels) deacon::check(dcn_anchor_map_pileup_keep_deletions(R.map.p, 1));
     if (a.markdup) deacon::check(dcn_anchor_map_duplicates_enable(R.map.p, 1));
     dcn_duplicate_params dprm = {};
     dprm.row_stride = sizeof(dcn_split_placement);
@@ -4110,16 +4115,22 @@ int run_map(const MapArgs &a) {
              uncalled_positions = 0; // (consensus)
     uint64_t qual_sum[4] = {};       // (call)
     uint64_t genotyped_positions = 0, vcf_sites = 0, het_sites = 0, hom_alt_sites = 0; // (genotype)
+    uint64_t deletion_events = 0, deleted_bases = 0, indel_sites = 0, insertion_sites = 0, deletion_sites = 0, het_indel_sites = 0,
+             hom_indel_sites = 0; // (indels)
     if (piles) {
         TextOut sites_out, pile_file, fasta_out, variants_out;
         std::unique_ptr<Output> vcf_out; // (.gz as BGZF, .zst and .xz by extension, as filter's outputs)
         const auto vcf_write = [&vcf_out](const std::string &text) { vcf_out->write(std::vector<char>(text.begin(), text.end())); };
-        if (a.has_vcf) { // VCF 4.2, SNVs only: indels stay in --variants
+        if (a.has_vcf) { // VCF 4.2, SNVs only: indels stay in --variants (`indels`: and as INDEL lines here)
             vcf_out.reset(new Output(a.vcf, 2));
             std::string head = std::string("##fileformat=VCFv4.2\n##source=deacon-hip ") + VERSION + "\n";
             for (uint32_t r = 0; r < R.n_records; ++r) head += "##contig=<ID=" + R.names[r] + ",length=" + std::to_string(R.lens[r]) + ">\n";
-            head += "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Depth: reads with a base, an N or a deletion at the position\">\n"
-                    "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
+            head += "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Depth: reads with a base, an N or a deletion at the position\">\n";
+            if (a.indels)
+                head += "##INFO=<ID=INDEL,Number=0,Type=Flag,Description=\"An insertion or a deletion\">\n"
+                        "##INFO=<ID=IDV,Number=1,Type=Integer,Description=\"Reads that carry the allele\">\n"
+                        "##INFO=<ID=IEV,Number=1,Type=Integer,Description=\"Insertions behind, or deletions that begin at, the position, of any allele\">\n";
+            head += "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
                     "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: phred gap to the second best genotype, at most 99\">\n"
                     "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Bases A, C, G, T of at least the minimum base quality\">\n"
                     "##FORMAT=<ID=AD,Number=R,Type=Integer,Description=\"Such bases per allele\">\n"
@@ -4137,6 +4148,19 @@ int run_map(const MapArgs &a) {
         std::vector<uint8_t> geno_gt;
         std::vector<dcn_genotype_site> geno_sites;
         std::string vcf_rows;
+        dcn_indel_params iprm = {}; // (`indels`)
+        iprm.ploidy = a.ploidy;
+        iprm.min_depth = a.min_depth;
+        iprm.min_gq = a.min_gq;
+        iprm.min_qual = a.min_qual;
+        iprm.min_count = a.min_indel_count;
+        iprm.indel_centi = 100 * a.indel_qual;
+        iprm.het_centi = 301;
+        std::vector<dcn_indel_site> ind_sites;
+        std::vector<uint8_t> ind_bases, ref_more;
+        std::vector<std::pair<uint64_t, size_t>> snv_at; // per SNV line of the stretch: its POS and where it begins in vcf_rows
+        std::string merged_rows;
+        if (a.indels) deacon::check(dcn_anchor_map_deletions_info(R.map.p, &deletion_events, &deleted_bases));
         if (a.has_sites) sites_out.open(a.sites, false);
         if (a.has_fasta) fasta_out.open(a.fasta, true);
         if (a.has_variants) variants_out.open(a.variants, false);
@@ -4153,7 +4177,9 @@ int run_map(const MapArgs &a) {
         dcn_pileup_call_params cprm = {};
         cprm.min_depth = a.min_depth;
         cprm.min_permille = a.min_frac;
-        const uint64_t stretch = 1u << 20;
+        // (DCN_CLI_STRETCH_BASES: a test hook, so that a short record has the seams between two stretches)
+        const char *const stretch_env = std::getenv("DCN_CLI_STRETCH_BASES");
+        const uint64_t stretch = stretch_env && *stretch_env ? std::max<uint64_t>(std::strtoull(stretch_env, nullptr, 10), 1) : 1u << 20;
         std::vector<uint32_t> counts, site_info, qsums;
         // (`call`) the mean quality of a column's bases at a position, rounded down; "." when it has none
         const auto mean_qual = [](const uint32_t *c, const uint32_t *qs, int col) {
@@ -4272,8 +4298,10 @@ int run_map(const MapArgs &a) {
                     for (uint64_t q = 0; q < n; ++q) genotyped_positions += geno_gt[q] != DCN_GENOTYPE_NONE;
                     vcf_sites += n_geno;
                     vcf_rows.clear();
+                    snv_at.clear();
                     for (uint64_t i = 0; i < n_geno; ++i) {
                         const dcn_genotype_site &g = geno_sites[i];
+                        if (a.indels) snv_at.emplace_back(g.pos + 1, vcf_rows.size());
                         // the genotype's alleles x <= y (G3's order: index y (y + 1) / 2 + x), then (REF, ALTs in A C G T order)
                         unsigned x = g.gt, y = g.gt;
                         if (a.ploidy == 2)
@@ -4301,6 +4329,69 @@ int run_map(const MapArgs &a) {
                                 first = false;
                             }
                         vcf_rows += '\n';
+                    }
+                    if (a.indels) { // rules I1-I8 over the stretch: the INDEL lines, merged into the SNV lines by POS, the SNV line of a POS first
+                        uint64_t n_ind = 0, n_ind_bases = 0;
+                        for (int attempt = 0;; ++attempt) {
+                            const int rc = dcn_anchor_map_indels_genotype(R.map.p, &iprm, r, start, n, ind_sites.data(), ind_sites.size(), ind_bases.data(),
+                                                                          ind_bases.size(), &n_ind, &n_ind_bases);
+                            if (rc != DCN_ERR_CAPACITY || attempt) {
+                                deacon::check(rc);
+                                break;
+                            }
+                            ind_sites.resize(n_ind);
+                            ind_bases.resize(n_ind_bases);
+                        }
+                        indel_sites += n_ind;
+                        // bases [from, from + count) of the record: the stretch's own, or fetched where a line reaches beyond it
+                        const auto ref_bases = [&](uint64_t from, uint64_t count) {
+                            if (from >= start && from + count <= start + n) return std::string((const char *)ref_text.data() + (from - start), count);
+                            ref_more.resize(count);
+                            deacon::check(dcn_anchor_map_fetch(R.map.p, r, from, count, ref_more.data()));
+                            return std::string(ref_more.begin(), ref_more.end());
+                        };
+                        merged_rows.clear();
+                        size_t next_snv = 0;
+                        const auto snvs_up_to = [&](uint64_t pos) {
+                            while (next_snv < snv_at.size() && snv_at[next_snv].first <= pos) {
+                                const size_t from = snv_at[next_snv].second, to = next_snv + 1 < snv_at.size() ? snv_at[next_snv + 1].second : vcf_rows.size();
+                                merged_rows.append(vcf_rows, from, to - from);
+                                ++next_snv;
+                            }
+                        };
+                        for (uint64_t i = 0; i < n_ind; ++i) {
+                            const dcn_indel_site &s = ind_sites[i];
+                            uint64_t pos1 = 0;
+                            std::string ref_allele, alt;
+                            if (s.flags & DCN_INDEL_DELETION) {
+                                ++deletion_sites;
+                                if (s.len >= R.lens[r]) // (every placement of the tool holds a k-mer of '=' bases)
+                                    die("internal error: a deletion of the whole record '" + R.names[r] + "'");
+                                ref_allele = ref_bases(s.pos > 0 ? s.pos - 1 : 0, (uint64_t)s.len + 1);
+                                pos1 = s.pos > 0 ? s.pos : 1;
+                                alt = s.pos > 0 ? ref_allele.substr(0, 1) : ref_allele.substr(s.len, 1);
+                            } else {
+                                ++insertion_sites;
+                                const std::string ins((const char *)ind_bases.data() + s.bases_offset, s.len);
+                                const bool front = (s.flags & DCN_INDEL_FRONT) != 0;
+                                ref_allele = ref_bases(front && s.pos > 0 ? s.pos - 1 : s.pos, 1);
+                                pos1 = front ? (s.pos > 0 ? s.pos : 1) : s.pos + 1;
+                                alt = front && s.pos == 0 ? ins + ref_allele : ref_allele + ins;
+                            }
+                            const bool hom = s.gt == a.ploidy; // V/V, or V at ploidy 1
+                            (hom ? hom_indel_sites : het_indel_sites) += 1;
+                            const uint32_t others = s.depth >= s.count ? s.depth - s.count : 0;
+                            snvs_up_to(pos1);
+                            merged_rows += R.names[r] + '\t' + std::to_string(pos1) + "\t.\t" + ref_allele + '\t' + alt + '\t' + std::to_string(s.qual) +
+                                           "\tPASS\tINDEL;DP=" + std::to_string(s.depth) + ";IDV=" + std::to_string(s.count) + ";IEV=" + std::to_string(s.events) +
+                                           "\tGT:GQ:DP:AD:PL\t" + (a.ploidy == 1 ? "1" : hom ? "1/1" : "0/1") + ':' + std::to_string(s.gq) + ':' +
+                                           std::to_string((uint64_t)others + s.count) + ':' + std::to_string(others) + ',' + std::to_string(s.count) + ':' +
+                                           std::to_string(s.pl[0]) + ',' + std::to_string(s.pl[1]);
+                            if (a.ploidy == 2) merged_rows += ',' + std::to_string(s.pl[2]);
+                            merged_rows += '\n';
+                        }
+                        snvs_up_to(UINT64_MAX);
+                        vcf_rows.swap(merged_rows);
                     }
                     if (a.has_vcf) vcf_write(vcf_rows);
                 }
@@ -4344,6 +4435,10 @@ int run_map(const MapArgs &a) {
             std::fprintf(stderr, "Consensus of %llu bases: %llu substitutions, %llu deleted positions, %llu insertions of %llu events, %llu positions without a call\n",
                          (unsigned long long)consensus_bases, (unsigned long long)substitutions, (unsigned long long)deleted_positions,
                          (unsigned long long)insertion_alleles, (unsigned long long)insertion_events, (unsigned long long)uncalled_positions);
+        if (a.indels)
+            std::fprintf(stderr, "Genotyped %llu indel sites (%llu insertions, %llu deletions) over %llu deletion events of %llu bases\n",
+                         (unsigned long long)indel_sites, (unsigned long long)insertion_sites, (unsigned long long)deletion_sites,
+                         (unsigned long long)deletion_events, (unsigned long long)deleted_bases);
         if (a.verify && !a.pileup)
             std::fprintf(stderr, "Verified %llu of %llu placements (%llu edits over %llu bases)\n", (unsigned long long)verified,
                          (unsigned long long)placements, (unsigned long long)edits_sum, (unsigned long long)verified_bases);
@@ -4411,6 +4506,13 @@ int run_map(const MapArgs &a) {
                         "  \"distinct_fragments\": %llu,\n",
                     a.both_ends ? "true" : "false", a.keep_duplicates ? "true" : "false", (unsigned long long)reads_keyed,
                     (unsigned long long)(reads_keyed - distinct_fragments), (unsigned long long)distinct_fragments);
+        if (a.indels)
+            appendf(js, "  \"indel_qual\": %u,\n  \"min_indel_count\": %u,\n  \"deletion_events\": %llu,\n  \"deleted_bases\": %llu,\n"
+                        "  \"indel_sites\": %llu,\n  \"insertion_sites\": %llu,\n  \"deletion_sites\": %llu,\n  \"het_indel_sites\": %llu,\n"
+                        "  \"hom_indel_sites\": %llu,\n",
+                    a.indel_qual, a.min_indel_count, (unsigned long long)deletion_events, (unsigned long long)deleted_bases,
+                    (unsigned long long)indel_sites, (unsigned long long)insertion_sites, (unsigned long long)deletion_sites,
+                    (unsigned long long)het_indel_sites, (unsigned long long)hom_indel_sites);
         appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
         for (uint32_t r = 0; r < R.n_records; ++r) {
             js += (r ? ",\n    {" : "\n    {");
@@ -4564,6 +4666,7 @@ void usage() {
                  "  call    As consensus, with the reads' base qualities: low-quality bases do not vote, variants carry mean qualities\n"
                  "  genotype  As call, with a genotype per position from counts and quality sums: GQ, PL, QUAL, SNV sites as VCF\n"
                  "  markdup  As genotype, with reads that repeat the unclipped end of an earlier read marked and left out first\n"
+                 "  indels  As markdup, with a genotype per insertion and deletion from the two ledgers: INDEL lines in the VCF\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -5199,6 +5302,125 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "optical-distance rule; nothing is read from the bases or the qualities.  Mates are independent here: one input,\n"
                "and a read is a unit.  Pairs as units (one key from both mates' ends) are a feature of the library\n"
                "(dcn_mark_duplicates_batch) and of the Python layer (AnchorMap.mark_duplicates), not of this mode.\n";
+    else if (sub == "indels")
+        text = "Mark duplicates, pile up and genotype as markdup does, keep the deleted runs beside the inserted bases, and give the\n"
+               "insertion and the deletion most reads carry at a position a genotype of their own: INDEL lines in the VCF\n\n"
+               "Usage: deacon-hip indels [OPTIONS] <REF> [READS]\n\n"
+               "Arguments:\n"
+               "  <REF>     Path to the reference fastx file: its records are numbered and named in file order\n"
+               "  [READS]   Optional path to FASTQ file (or - for stdin; gz, bgzf, zst, xz and bz2 found by content) [default: -]\n"
+               "            A record without a quality line (FASTA) is an error: consensus takes such reads\n\n"
+               "Options:\n"
+               "  -x, --index <INDEX>            Keys that may anchor: a minimizer index file, whose k and w are used\n"
+               "                                 [default: the minimizers of <REF> at -k / -w]\n"
+               "  -k <K>                         K-mer length without -x [default: 31]\n"
+               "  -w <W>                         Minimizer window size without -x [default: 15]\n"
+               "  -o, --output <OUTPUT>          FASTA: per record of <REF> a line >name and its consensus on one line (- for\n"
+               "                                 stdout) [default: no FASTA]\n"
+               "      --variants <FILE>          TSV: record pos type ref alt depth count events, pos 0-based as in PAF; one SUB line\n"
+               "                                 per substituted position, one DEL line per deleted position (alt -), one INS or\n"
+               "                                 INS_FRONT line per called insertion behind or in front of pos (ref ., count = the\n"
+               "                                 reads with exactly these bases, events = all insertions there; 0 on other lines)\n"
+               "                                 With two more columns, ref_qual alt_qual: on a SUB line the mean quality, rounded\n"
+               "                                 down, of the counted bases that show the reference's base and of those that show\n"
+               "                                 alt (. for none, or for a reference base that is not ACGT); . on every other line\n"
+               "      --vcf <FILE>               VCF 4.2, SNVs only (- for stdout; .gz as BGZF, .zst and .xz by extension): one line per\n"
+               "                                 position whose genotype is called and is\n"
+               "                                 not the reference's, with QUAL, INFO DP (all reads there) and GT:GQ:DP:AD:PL over\n"
+               "                                 the reference's base and the genotype's other bases; insertions and deletions stay\n"
+               "                                 in --variants [default: no VCF]\n"
+               "      --ploidy <1|2>             Genotypes of one base (A C G T) or of two (AA AC CC AG CG GG AT CT GT TT) [default: 2]\n"
+               "      --min-gq <N>               A genotype is called at a genotype quality of at least N: the phred gap between the\n"
+               "                                 best and the second best genotype (0..99) [default: 20, a convention]\n"
+               "      --min-qual <N>             A site needs QUAL of at least N: the phred gap between the reference's homozygote and\n"
+               "                                 the best genotype [default: 20, a convention]\n"
+               "      --sample <NAME>            The sample column's name [default: sample]\n"
+               "      --keep-duplicates          Mark and report the duplicates, but pile every read up: the other outputs are\n"
+               "                                 genotype's\n"
+               "      --both-ends                A duplicate repeats the unclipped 3' end of the earlier read as well\n"
+               "      --duplicates <FILE>        TSV: read ordinal first record strand pos5, one line per duplicate read in input\n"
+               "                                 order: its name, its number in the input from 0, the number of the first read\n"
+               "                                 with the same end, and the end: pos5 is 0-based and may be negative or past the\n"
+               "                                 record's end [default: no TSV]\n"
+               "      --indel-qual <Q>           What one read that contradicts an indel genotype costs, in phred: a gap has no base\n"
+               "                                 quality (0..1000) [default: 20, a convention]\n"
+               "      --min-indel-count <N>      An insertion or a deletion needs N reads that carry exactly it [default: 2, a convention]\n"
+               "      --fill-ref                 A position without a call takes the reference's base, not N\n"
+               "      --min-baseq <Q>            A base of quality below Q counts as N: it adds to the depth and never wins\n"
+               "                                 (0..255) [default: 20, a convention]\n"
+               "      --qual-offset <N>          The quality of a base is its quality character minus N, 0 when that is negative\n"
+               "                                 (0..255) [default: 33]\n"
+               "      --pileup <FILE>            pileup's TSV over the extended placements: record pos ref A C G T N del ins rev, then\n"
+               "                                 qA qC qG qT: the sums of the qualities of the bases counted in A C G T\n"
+               "      --sites <FILE>             pileup's site TSV over them: record pos ref call depth flags\n"
+               "      --all-positions            One line of --pileup for every position of every record\n"
+               "      --min-depth <N>            A call needs a depth of at least N, a genotype as many bases A C G T\n"
+               "                                 [default: 3, a convention]\n"
+               "      --min-frac <N>             ... and N per 1000 of the depth for the most frequent of A C G T and gap, and\n"
+               "                                 for the insertions at a position (0..1000) [default: 500, a convention]\n"
+               "      --min-mapq <N>             Only placements of mapping quality N or more add (0..60) [default: 1, a convention]\n"
+               "      --all-ranks                Every placement of a read adds, not only its first (rank 0)\n"
+               "      --penalty <N>              An edit in a flank costs N matched bases of read plus record (2..255)\n"
+               "                                 [default: 6, a convention]\n"
+               "      --end-bonus <N>            Reaching the read's end is worth N (0..65535) [default: 4, a convention]\n"
+               "      --ext-max-edits <N>        At most N edits per flank (0..1023) [default: 1023, a convention]\n"
+               "  -e, --max-edits <N>            Only placements of at most N edits over the extended extents add (0..1023)\n"
+               "                                 [default: 1023, a convention]\n"
+               "      --max-div <N>              ... and of at most N per 1000 bases of the longer extended extent (0..1000)\n"
+               "                                 [default: 200, a convention]\n"
+               "  -N, --max-placements <N>       Placements per read, each from the anchor hits no earlier one explained (1..8)\n"
+               "                                 [default: 4]\n"
+               "      --band <N>                 Width of a diagonal band in bases [default: 256, a convention]\n"
+               "  -a, --min-votes <N>            Minimum number of anchor hits in a placement's cell [default: 2, as filter's -a,\n"
+               "                                 a convention]\n"
+               "  -p, --prefix-length <N>        Search only the first N nucleotides per read (0 = entire read) [default: 0]\n"
+               "  -s, --summary <SUMMARY>        Path to JSON summary output file: extend's and pileup's keys, and fill_ref,\n"
+               "                                 insertion_events, inserted_bases, insertion_alleles, substitutions,\n"
+               "                                 deleted_positions, consensus_bases and uncalled_positions; min_base_qual,\n"
+               "                                 qual_offset and quality_sums, the totals of qA qC qG qT; ploidy, min_gq, min_qual,\n"
+               "                                 genotyped_positions, vcf_sites, het_sites and hom_alt_sites; duplicates_both_ends,\n"
+               "                                 keep_duplicates, reads_keyed (reads with an end), duplicate_reads and\n"
+               "                                 distinct_fragments; indel_qual, min_indel_count, deletion_events, deleted_bases,\n"
+               "                                 indel_sites, insertion_sites, deletion_sites, het_indel_sites and hom_indel_sites\n"
+               "  -t, --threads <THREADS>        Accepted for compatibility (one reader thread feeds the GPU)\n"
+               "  -q, --quiet                    Suppress progress reporting\n"
+               "  -h, --help                     Print help\n\n"
+               "Consensus, position by position of a record: the bases of an insertion called in front of the position; the\n"
+               "called base, nothing where a gap is called, N (or the reference's base with --fill-ref) where nothing is; the\n"
+               "bases of an insertion called behind it.  An insertion is called where the reads with an insertion there reach\n"
+               "--min-frac of a depth of at least --min-depth; its bases are those most of them agree on (on a tie one behind\n"
+               "the position before one in front, then the shorter, then the first by letter), whatever their own share: count\n"
+               "and events say what it is.  The thresholds are conventions, not measured optima.  Integers and bytes only: the\n"
+               "output does not depend on how the input is cut into batches.  Deleted positions are not merged, indels are not\n"
+               "left-normalised.  Qualities: alignment does not look at them, so the placements and their edits are consensus's;\n"
+               "only what a base counts as changes.  With --min-baseq 0 the FASTA is consensus's.  The qualities of inserted bases\n"
+               "are not looked at.  -o, --variants, --pileup and --sites are call's, byte for byte.  Genotypes: a base of quality q\n"
+               "that a genotype does not explain costs q + 4.77 phred, a base of a heterozygote 3.01; the costs are sums over the\n"
+               "counted bases A C G T, in integers (hundredths of a phred), and a matching base costs nothing.  The constants and\n"
+               "thresholds are conventions, not measured optima.  SNVs only: no indels in the VCF, no priors, no strand or mapping\n"
+               "quality terms, no phasing, no affine gaps.\n"
+               "Duplicates: the end of a read is the record, the strand and the unclipped 5' coordinate of its first placement\n"
+               "that --min-mapq and the rank leave, so soft clips do not matter; a read whose end an earlier read of the input had\n"
+               "is a duplicate, and none of its placements adds.  First seen wins: a streaming rule, not a best-quality rule, so\n"
+               "the order of the input matters and how it is cut into batches does not.  The comparison is exact.  No\n"
+               "optical-distance rule; nothing is read from the bases or the qualities.  Mates are independent here: one input,\n"
+               "and a read is a unit.  Pairs as units (one key from both mates' ends) are a feature of the library\n"
+               "(dcn_mark_duplicates_batch) and of the Python layer (AnchorMap.mark_duplicates), not of this mode.\n"
+               "Indels: whatever --vcf says above, the VCF of this mode also has a line for the insertion most reads with an\n"
+               "insertion at a position agree on and for the deletion most reads with a deletion that begins there agree on (of\n"
+               "at least --min-indel-count reads each), when its genotype against everything else is called and is not the\n"
+               "reference's: a reads carry it, o = depth - a do not, and R/R costs --indel-qual a, R/V 3.01 (a + o), V/V\n"
+               "--indel-qual o (at --ploidy 1: R and V).  GQ, PL, QUAL, --min-depth (of all reads there), --min-gq and --min-qual\n"
+               "work as for a base.  The line is\n"
+               "  name POS . REF ALT QUAL PASS INDEL;DP=depth;IDV=a;IEV=e GT:GQ:DP:AD:PL gt:gq:dp:o,a:pl\n"
+               "with e the insertions behind, or the deletions that begin at, the position, of any allele, FORMAT DP = o + a, GT\n"
+               "0/1 or 1/1 (1 at --ploidy 1) and three PL (two).  REF and ALT begin with the base in front, POS is that base's; at\n"
+               "the first base of a record they end with the base behind.  The header gains INFO INDEL, IDV and IEV.  Lines of a\n"
+               "record are in non-descending POS, the SNV line of a POS first.  With the INDEL lines and those three header lines\n"
+               "removed the VCF is markdup's, and -o, --variants, --pileup, --sites and --duplicates are markdup's, byte for byte.\n"
+               "One allele per kind and position: no multi-allelic indel lines; overlapping deletions with different starts are\n"
+               "lines of their own.  In a repeat the gap lies where the alignment puts it, at the repeat's far end: not\n"
+               "left-normalised.  20 and 2 are conventions, not measured optima.\n";
     else if (sub == "map-pairs")
         text = "Place the two mates of each pair jointly on a reference: proper pairs, rescued mates and insert sizes, as PAF\n\n"
                "Usage: deacon-hip map-pairs [OPTIONS] <REF> <READS1> [READS2]\n\n"
@@ -5490,11 +5712,12 @@ int main(int argc, char **argv) {
             return run_place(a);
         }
         if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup" || args[0] == "extend" || args[0] == "consensus" ||
-            args[0] == "call" || args[0] == "genotype" || args[0] == "markdup") {
+            args[0] == "call" || args[0] == "genotype" || args[0] == "markdup" || args[0] == "indels") {
             MapArgs a;
             a.align = args[0] == "align";
             a.pileup = args[0] == "pileup";
-            a.markdup = args[0] == "markdup";
+            a.indels = args[0] == "indels";
+            a.markdup = args[0] == "markdup" || a.indels;
             a.genotype = args[0] == "genotype" || a.markdup;
             a.call = args[0] == "call" || a.genotype;
             a.consensus = args[0] == "consensus" || a.call;
@@ -5526,6 +5749,8 @@ int main(int argc, char **argv) {
                 else if (a.markdup && s == "--keep-duplicates") a.keep_duplicates = true;
                 else if (a.markdup && s == "--both-ends") a.both_ends = true;
                 else if (a.markdup && s == "--duplicates") a.duplicates = need(++i), a.has_duplicates = true;
+                else if (a.indels && s == "--indel-qual") a.indel_qual = (unsigned)number(need(++i), "--indel-qual", 0, 1000);
+                else if (a.indels && s == "--min-indel-count") a.min_indel_count = (unsigned)number(need(++i), "--min-indel-count", 0, 0xFFFFFFFFll);
                 else if (s == "-o" || s == "--output") a.output = need(++i), a.has_output = true;
                 else if (a.extend && s == "--penalty") a.penalty = (unsigned)number(need(++i), "--penalty", 2, 255);
                 else if (a.extend && s == "--end-bonus") a.end_bonus = (unsigned)number(need(++i), "--end-bonus", 0, 65535);

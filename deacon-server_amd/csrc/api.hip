@@ -445,6 +445,7 @@ extern "C" int dcn_index_clone(const dcn_index *index, int device, dcn_index **o
     idx->pileup_bases = 0;
     idx->pileup_rows = 0;
     idx->ledger = nullptr; // ... nor an insertion ledger
+    idx->del_ledger = nullptr; // ... nor a deletion ledger
     idx->d_pileup_qsums = nullptr; // ... nor quality sums
     idx->dups = nullptr; // ... nor a duplicate set
     const uint64_t bytes = idx->n_groups * DCN_GROUP_SLOTS * sizeof(uint64_t);
@@ -502,6 +503,7 @@ extern "C" void dcn_index_destroy(dcn_index *index) {
     dcn_base_store_free(index->store);
     if (index->d_pileup) hipFree(index->d_pileup);
     dcn_ins_ledger_free(index->ledger);
+    dcn_del_ledger_free(index->del_ledger);
     if (index->d_pileup_qsums) hipFree(index->d_pileup_qsums);
     dcn_dup_set_free(index->dups);
     delete index;

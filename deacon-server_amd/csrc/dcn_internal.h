@@ -84,6 +84,8 @@ struct dcn_base_store; // (dcn_verify.h)
 void dcn_base_store_free(dcn_base_store *s);
 struct dcn_ins_ledger; // (dcn_verify.h)
 void dcn_ins_ledger_free(dcn_ins_ledger *l);
+struct dcn_del_ledger; // (dcn_verify.h)
+void dcn_del_ledger_free(dcn_del_ledger *l);
 struct dcn_dup_set; // (dcn_verify.h)
 void dcn_dup_set_free(dcn_dup_set *d);
 
@@ -126,6 +128,8 @@ struct dcn_index {
     // (dcn_anchor_map_pileup_keep_insertions, insertions_api.hip).  Null: none is kept.
     uint64_t pileup_rows = 0;
     dcn_ins_ledger *ledger = nullptr;
+    // ... and the deletion ledger (dcn_anchor_map_pileup_keep_deletions, indels_api.hip).  Null: none is kept.
+    dcn_del_ledger *del_ledger = nullptr;
     // ... and the quality sums beside the counters (dcn_anchor_map_pileup_keep_qualities, pileup_api.hip): 4 words per base
     // of the pileup, laid out by dcn_pile_sum_index (dcn_pileup.h).  Null: none are kept.
     uint32_t *d_pileup_qsums = nullptr;

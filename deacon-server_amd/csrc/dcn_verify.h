@@ -412,3 +412,83 @@ int dcn_launch_ins_slot_lens(const dcn_ins_range_args &args, hipStream_t stream)
 int dcn_launch_ins_gather(const dcn_ins_range_args &args, hipStream_t stream);
 int dcn_launch_ins_winner(const dcn_ins_range_args &args, hipStream_t stream);
 int dcn_launch_ins_alleles(const dcn_ins_range_args &args, hipStream_t stream);
+
+// ---- deletion ledger and indel genotypes (indels.hip, indels_api.hip; the shared arithmetic is in dcn_indels.h) ----------
+struct dcn_del_event; // (dcn_indels.h)
+// The deletion ledger of a map (dcn_anchor_map_pileup_keep_deletions): the events on the device, growing geometrically from
+// DCN_DELETION_LEDGER_EVENTS (read when the ledger first grows), and the scratch of the append, which lives with the ledger:
+// per aligned row of a call its events, their offsets and the scan's sums, and the total, which is zero between calls.
+struct dcn_del_ledger {
+    dcn_del_event *d_events = nullptr;
+    uint64_t event_cap = 0, n_events = 0, n_deleted = 0;
+    uint32_t *d_row_events = nullptr;
+    uint64_t rows_cap = 0;
+    uint64_t *d_event_offsets = nullptr;
+    unsigned long long *d_event_sums = nullptr;
+    uint64_t offsets_cap = 0;
+    unsigned long long *d_totals = nullptr; // events, their lengths
+};
+void dcn_del_ledger_free(dcn_del_ledger *l);
+
+// the walk of pileup_kernel over the same work list (args.counters is not looked at)
+struct dcn_del_append_args {
+    dcn_pileup_args rows;
+    uint32_t *row_events;          // per work item (the counting pass)
+    unsigned long long *totals;    // the events of the call and the sum of their lengths, added to
+    const uint64_t *event_offsets; // the scan of row_events (the writing pass)
+    dcn_del_event *events;         // the ledger's array, from where this call appends
+    uint64_t event0;
+};
+int dcn_launch_del_count(const dcn_del_append_args &args, hipStream_t stream);
+int dcn_launch_del_write(const dcn_del_append_args &args, hipStream_t stream);
+// the append of dcn_pileup_batch on a map that keeps a deletion ledger, behind the pileup kernel on the context's stream
+int dcn_deletions_append(dcn_ctx *c, dcn_index *map, const dcn_pileup_args &rows);
+
+// fetch and the deletion side of a genotype call over the range [base0, base0 + n) of the store
+struct dcn_del_range_args {
+    uint64_t base0, n, pos0;
+    const dcn_del_event *events;
+    uint64_t n_events;
+    uint32_t *counts;               // per position: STARTS (rule R5), zero before the plane kernel
+    const uint64_t *bucket_offsets; // the scan of counts
+    uint32_t *cursor;               // per position, zero before the scatter
+    uint64_t *slots;                // per bucket entry: the event of the ledger
+    uint64_t n_slots;
+    void *out_events;               // fetch: dcn_deletion per slot
+    uint32_t *win_count, *win_len;  // genotype: per position the winner's count and length (0 where STARTS is 0)
+};
+int dcn_launch_del_plane(const dcn_del_range_args &args, hipStream_t stream);
+int dcn_launch_del_scatter(const dcn_del_range_args &args, hipStream_t stream);
+int dcn_launch_del_gather(const dcn_del_range_args &args, hipStream_t stream);
+int dcn_launch_del_winner(const dcn_del_range_args &args, hipStream_t stream);
+
+// rules I1 - I6 over the range: count, scan, write (genotype.hip's shape), then the inserted bases of the insertion sites
+struct dcn_indel_site_args {
+    const uint32_t *counters; // the map's pileup
+    uint64_t bases;
+    uint64_t base0, n, pos0;
+    uint32_t ploidy, min_depth, min_gq, min_qual, min_count, indel_centi, het_centi;
+    // the insertion candidates (null: the map keeps no insertion ledger, or the range has no event): per position whether
+    // INS > 0, its scan, and per flagged position ins_winner_kernel's arrays
+    const uint32_t *ins_flags;
+    const uint64_t *ins_offsets;
+    const uint64_t *ins_event;
+    const uint32_t *ins_count, *ins_events, *ins_len;
+    const dcn_ins_event *ins_ledger;
+    const uint8_t *ins_ledger_bases;
+    // the deletion candidates (null likewise): per position STARTS, the winner's count and its length
+    const uint32_t *del_starts, *del_count, *del_len;
+    uint32_t *block_counts;         // sites per workgroup (the counting pass)
+    unsigned long long *n_inserted; // the inserted bases of all sites, added to (the counting pass)
+    const uint64_t *block_offsets;  // the scan of block_counts (the writing pass)
+    void *sites;                    // dcn_indel_site per site; bases_offset is written by the bases pass
+    uint32_t *site_lens;            // per site: the inserted bases (0 for a deletion)
+    uint64_t *site_event;           // per site: the winning event of an insertion
+    uint64_t n_sites;
+    const uint64_t *site_offsets;   // the scan of site_lens
+    uint8_t *out_bases;
+};
+uint32_t dcn_indel_site_blocks(uint64_t n); // workgroups of a range of n positions
+int dcn_launch_indel_flags(const uint32_t *counts, uint32_t *flags, uint64_t n, hipStream_t stream);
+int dcn_launch_indel_sites(const dcn_indel_site_args &args, bool write, hipStream_t stream);
+int dcn_launch_indel_bases(const dcn_indel_site_args &args, hipStream_t stream);

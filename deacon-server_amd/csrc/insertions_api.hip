@@ -5,6 +5,7 @@
 #include "dcn_ctx.h"
 #include "dcn_dump_sweep.h"
 #include "dcn_insertions.h"
+#include "dcn_ledger_range.h"
 #include "dcn_verify.h"
 
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include <vector>
 
 using namespace dcn_impl;
+using namespace dcn_ledger_api;
 
 static_assert(sizeof(dcn_insertion) == 24 && sizeof(dcn_insertion_allele) == 32, "ledger events and alleles are ABI");
 static_assert(DCN_INSERTION_FRONT == DCN_INS_FRONT && DCN_INSERTION_REVERSE == DCN_INS_REVERSE, "the flags of the header and of dcn_insertions.h");
@@ -60,34 +62,31 @@ int check_ledger(const dcn_index *map) {
     return DCN_OK;
 }
 
-// device memory of one call, freed when it ends
-struct scratch {
-    std::vector<void *> p;
-    template <typename T>
-    int get(T **out, uint64_t count, const char *what) {
-        DCN_TRY(dev_alloc(out, count, what));
-        p.push_back(*out);
-        return DCN_OK;
-    }
-    ~scratch() {
-        for (void *q : p) hipFree(q);
-    }
-};
+int capacity_error(const char *what, uint64_t events, uint64_t event_capacity, uint64_t bases, uint64_t base_capacity) {
+    return dcn_fail(DCN_ERR_CAPACITY, std::string("the arrays hold ") + std::to_string(event_capacity) + " " + what + " and " +
+                                          std::to_string(base_capacity) + " bases, the range has " + std::to_string(events) + " and " +
+                                          std::to_string(bases) + " (both counts are complete: call again with those capacities)");
+}
+} // namespace
 
-// the scan of n counts into n + 1 offsets of the call's scratch, and its total
-int scan_counts(scratch &mem, const uint32_t *d_counts, uint64_t n, uint64_t **d_offsets, uint64_t *total, const char *what) {
+// ---- dcn_ledger_range.h: shared with indels_api.hip ------------------------------------------------------------------
+int dcn_ledger_api::scan_counts(scratch &mem, const uint32_t *d_counts, uint64_t n, uint64_t **d_offsets, uint64_t *total, const char *what) {
     unsigned long long *d_sums = nullptr;
     DCN_TRY(mem.get(d_offsets, n + 1, what));
-    DCN_TRY(mem.get(&d_sums, n / DCN_SCAN_BLOCK + 2, "insertion scan sums"));
+    DCN_TRY(mem.get(&d_sums, n / DCN_SCAN_BLOCK + 2, "ledger scan sums"));
     DCN_TRY(dcn_launch_offsets_scan(d_counts, (uint32_t)n, d_sums, *d_offsets, nullptr));
     DCN_HIP(hipMemcpy(total, *d_offsets + n, sizeof(uint64_t), hipMemcpyDeviceToHost));
     return DCN_OK;
 }
 
+int dcn_ledger_api::too_many(const char *who, uint64_t total) {
+    return dcn_fail(DCN_ERR_ARG, std::string(who) + ": the range has " + std::to_string(total) + " events, 2^32 or more: ask for a part of it");
+}
+
 // What fetch and call share: the checks behind those of the parameters, the counts of the range (the INS plane, under rule
 // L6 for a call), their scan and the scatter of the ledger's events into the buckets.  *n_slots = 0: nothing in the range.
-int range_buckets(const dcn_index *map, const char *who, bool call, uint32_t record, uint64_t start, uint64_t n_bases, uint32_t min_depth,
-                  uint32_t min_permille, scratch &mem, dcn_ins_range_args *ra, uint64_t *n_slots) {
+int dcn_ledger_api::range_buckets(const dcn_index *map, const char *who, bool call, uint32_t record, uint64_t start, uint64_t n_bases, uint32_t min_depth,
+                                  uint32_t min_permille, scratch &mem, dcn_ins_range_args *ra, uint64_t *n_slots) {
     *n_slots = 0;
     uint64_t b0 = 0;
     DCN_TRY(check_range(map, who, record, start, n_bases, &b0));
@@ -114,8 +113,7 @@ int range_buckets(const dcn_index *map, const char *who, bool call, uint32_t rec
     DCN_TRY(scan_counts(mem, ra->counts, n_bases, &d_offsets, &total, "insertion bucket offsets"));
     ra->bucket_offsets = d_offsets;
     if (total == 0) return DCN_OK;
-    if (total > UINT32_MAX)
-        return dcn_fail(DCN_ERR_ARG, std::string(who) + ": the range has " + std::to_string(total) + " events, 2^32 or more: ask for a part of it");
+    if (total > UINT32_MAX) return too_many(who, total);
     DCN_TRY(mem.get(&ra->cursor, n_bases, "insertion cursors"));
     DCN_TRY(mem.get(&ra->slots, total, "insertion buckets"));
     DCN_HIP(hipMemset(ra->cursor, 0, n_bases * sizeof(uint32_t)));
@@ -125,13 +123,6 @@ int range_buckets(const dcn_index *map, const char *who, bool call, uint32_t rec
     *n_slots = total;
     return DCN_OK;
 }
-
-int capacity_error(const char *what, uint64_t events, uint64_t event_capacity, uint64_t bases, uint64_t base_capacity) {
-    return dcn_fail(DCN_ERR_CAPACITY, std::string("the arrays hold ") + std::to_string(event_capacity) + " " + what + " and " +
-                                          std::to_string(base_capacity) + " bases, the range has " + std::to_string(events) + " and " +
-                                          std::to_string(bases) + " (both counts are complete: call again with those capacities)");
-}
-} // namespace
 
 void dcn_ins_ledger_free(dcn_ins_ledger *l) {
     if (!l) return;

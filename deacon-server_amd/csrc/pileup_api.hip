@@ -1,7 +1,7 @@
 // pileup_api.hip -- the C ABI of pileups (dcn_anchor_map_pileup_enable / _reset / _fetch / _call, dcn_pileup_batch, and with
 // base qualities dcn_anchor_map_pileup_keep_qualities / _fetch_qualities, dcn_pileup_batch_qual;
-// kernels in pileup.hip, the shared arithmetic in dcn_pileup.h; a kept insertion ledger, insertions_api.hip, is appended
-// to, emptied and freed here).  dcn_pileup_batch is dcn_align_batch's sequence
+// kernels in pileup.hip, the shared arithmetic in dcn_pileup.h; a kept insertion ledger, insertions_api.hip, and a kept
+// deletion ledger, indels_api.hip, are appended to, emptied and freed here).  dcn_pileup_batch is dcn_align_batch's sequence
 // (verify_api.hip's walk, align_api.hip's passes and gather) with the runs left on the device and the pileup kernel behind;
 // dcn_pileup_batch_qual is the same sequence with the qualities staged in front of the kernel's quality form.
 #include "dcn_ctx.h"
@@ -45,6 +45,7 @@ extern "C" int dcn_anchor_map_pileup_enable(dcn_index *map, int enable) {
             DCN_HIP(hipSetDevice(map->device));
             hipFree(map->d_pileup);
             dcn_ins_ledger_free(map->ledger);
+            dcn_del_ledger_free(map->del_ledger);
             if (map->d_pileup_qsums) hipFree(map->d_pileup_qsums);
         }
         map->d_pileup = nullptr;
@@ -52,6 +53,7 @@ extern "C" int dcn_anchor_map_pileup_enable(dcn_index *map, int enable) {
         map->pileup_bases = 0;
         map->pileup_rows = 0;
         map->ledger = nullptr;
+        map->del_ledger = nullptr;
         return DCN_OK;
     }
     if (map->d_pileup) return DCN_OK;
@@ -71,6 +73,7 @@ extern "C" int dcn_anchor_map_pileup_reset(dcn_index *map) {
     DCN_HIP(hipDeviceSynchronize()); // (null-stream work must not be overtaken by a context's stream)
     map->pileup_rows = 0;
     if (map->ledger) map->ledger->n_events = map->ledger->n_bases = 0; // (the arrays stay: the next append begins at their start)
+    if (map->del_ledger) map->del_ledger->n_events = map->del_ledger->n_deleted = 0;
     return DCN_OK;
 }
 
@@ -132,6 +135,7 @@ int pileup_run(dcn_ctx *c, dcn_index *map, const uint8_t *bases, const uint8_t *
             DCN_TRY(dcn_launch_pileup(pa, st));
         }
         if (map->ledger) DCN_TRY(dcn_insertions_append(c, map, pa)); // rule L2, behind the same checks
+        if (map->del_ledger) DCN_TRY(dcn_deletions_append(c, map, pa)); // rule R2, likewise
     }
     DCN_PROF_MARK(DCN_STAGE_FINISH);
     DCN_TRY(finish_run(c, prof_slot));

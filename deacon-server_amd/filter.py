@@ -690,6 +690,13 @@ GENOTYPE_SITE_DTYPE = np.dtype([("pos", np.uint64), ("qual", np.uint32), ("depth
                                 ("gq", np.uint8), ("ref_code", np.uint8), ("reserved0", np.uint8), ("pl", np.uint8, (10,)),
                                 ("reserved1", np.uint8, (2,))])
 GENOTYPE_NONE, GENOTYPES = N.GENOTYPE_NONE, N.GENOTYPES
+# numpy views of dcn_deletion (16 bytes) and dcn_indel_site (48 bytes): an event of a deletion ledger, and what
+# AnchorMap.indels_genotype returns per site; bases_offset points into the bases returned beside the sites
+DELETION_DTYPE = np.dtype([("pos", np.uint64), ("len", np.uint32), ("flags", np.uint32)])
+INDEL_SITE_DTYPE = np.dtype([("pos", np.uint64), ("bases_offset", np.uint64), ("len", np.uint32), ("flags", np.uint32), ("qual", np.uint32),
+                             ("depth", np.uint32), ("count", np.uint32), ("events", np.uint32), ("gt", np.uint8), ("gq", np.uint8),
+                             ("pl", np.uint8, (3,)), ("reserved", np.uint8, (3,))])
+DELETION_REVERSE, INDEL_DELETION, INDEL_FRONT = N.DELETION_REVERSE, N.INDEL_DELETION, N.INDEL_FRONT  # DCN_DELETION_*, DCN_INDEL_*
 _CIGAR_LETTERS = {N.CIGAR_INS: "I", N.CIGAR_DEL: "D", N.CIGAR_EQUAL: "=", N.CIGAR_DIFF: "X"}
 
 
@@ -885,6 +892,48 @@ class AnchorMap(Index):
         p = N.PileupCallParams(int(min_depth), int(min_permille), (C.c_uint32 * 2)(0, 0))
         return self._insertions(N.lib().dcn_anchor_map_insertions_call, (self._h, C.byref(p), int(record), start, n), INSERTION_ALLELE_DTYPE,
                                 n, n // 64 + 64)
+
+    def pileup_keep_deletions(self, keep=True):
+        """A deletion ledger beside the pileup (dcn_anchor_map_pileup_keep_deletions; the definition of a deletion ledger is
+        in include/deacon_hip.h): every D run of a row that Placer.pileup_batch adds also leaves (position, length, strand).
+        Refused once a row has added since pileup_enable() or pileup_reset(); keep=False drops it and leaves the counters."""
+        N.check(N.lib().dcn_anchor_map_pileup_keep_deletions(self._h, 1 if keep else 0))
+
+    def deletions_info(self):
+        """-> (events of the deletion ledger, the sum of their lengths)"""
+        n_events, n_deleted = C.c_uint64(), C.c_uint64()
+        N.check(N.lib().dcn_anchor_map_deletions_info(self._h, C.byref(n_events), C.byref(n_deleted)))
+        return int(n_events.value), int(n_deleted.value)
+
+    def deletions_fetch(self, record, start=0, n=None):
+        """The events of the deletion ledger that begin in [start, start + n) of a record (n=None: to its end), in the
+        canonical order of rule R4 -> DELETION_DTYPE[].  One call with an estimate and, on DCN_ERR_CAPACITY, a second with
+        the size the first reported."""
+        start, n = int(start), self._to_end(record, start) if n is None else int(n)
+        n_events = C.c_uint64()
+
+        def call(cap):
+            events = np.zeros(max(cap, 1), DELETION_DTYPE)
+            rc = N.lib().dcn_anchor_map_deletions_fetch(self._h, int(record), start, n, _ptr(events) if cap else None, cap, C.byref(n_events))
+            return rc, events
+
+        rc, events = call(n // 16 + 64)
+        if rc == N.DCN_ERR_CAPACITY:
+            rc, events = call(int(n_events.value))
+        N.check(rc)
+        return events[:int(n_events.value)]
+
+    def indels_genotype(self, record, start=0, n=None, ploidy=2, min_depth=3, min_gq=20, min_qual=20, min_count=2, indel_centi=2000,
+                        het_centi=301):
+        """Rules I1-I8 (the definition of an indel genotype is in include/deacon_hip.h) over [start, start + n) of a record
+        (n=None: to its end) of a map that keeps an insertion ledger, a deletion ledger or both -> (INDEL_SITE_DTYPE[], bases
+        bytes): per position the winning insertion and the winning deletion that begin there, each genotyped against
+        everything else, where the genotype is not the reference's; an insertion site's bases are
+        bases[bases_offset : bases_offset + len].  The defaults are conventions, not measured optima."""
+        start, n = int(start), self._to_end(record, start) if n is None else int(n)
+        p = N.IndelParams(int(ploidy), int(min_depth), int(min_gq), int(min_qual), int(min_count), int(indel_centi), int(het_centi), 0)
+        return self._insertions(N.lib().dcn_anchor_map_indels_genotype, (self._h, C.byref(p), int(record), start, n), INDEL_SITE_DTYPE, n,
+                                n // 64 + 64)
 
     def consensus(self, record, start=0, n=None, min_depth=3, min_permille=500, fill_ref=False):
         """Rule L7 over [start, start + n) of a record -> bytes: per position the bases of a called front insertion, the

@@ -83,9 +83,10 @@ enum {
  * 1.17 = dcn_anchor_map_pileup_keep_insertions, dcn_anchor_map_insertions_info / _fetch / _call.
  * 1.18 = dcn_anchor_map_pileup_keep_qualities / _fetch_qualities, dcn_pileup_batch_qual.
  * 1.19 = dcn_anchor_map_genotype.
- * 1.20 = dcn_anchor_map_duplicates_enable / _reset / _info, dcn_mark_duplicates_batch. */
+ * 1.20 = dcn_anchor_map_duplicates_enable / _reset / _info, dcn_mark_duplicates_batch.
+ * 1.21 = dcn_anchor_map_pileup_keep_deletions, dcn_anchor_map_deletions_info / _fetch, dcn_anchor_map_indels_genotype. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 20
+#define DCN_ABI_MINOR 21
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -1293,6 +1294,134 @@ int dcn_anchor_map_duplicates_info(const dcn_index *map, uint64_t *seen, uint64_
 int dcn_mark_duplicates_batch(dcn_index *map, const uint64_t *offsets, uint32_t n_reads, const void *params,
                               const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint8_t *dup, uint64_t *first,
                               uint64_t *n_duplicates);
+
+/* ---- indels: a deletion ledger beside the pileup, genotypes of insertions and deletions (ABI 1.21) --------------------
+ * (no reference counterpart.)  The DEL column of a pileup says that a position is deleted in some reads, not which runs the
+ * reads carry: three reads with a 2-base deletion at 100 look like one read with a 3-base deletion at 100 under two reads
+ * with a 1-base deletion at 101.  A deletion ledger keeps every run, and with it and the insertion ledger an indel allele
+ * can be given a genotype against everything else, as rule G4 gives one to a base.
+ *
+ * THE DEFINITION OF A DELETION LEDGER.  Rules 1-6 of a verified placement, A1-A6, P1-P6 and L1-L8 stand.  Added:
+ *   R1. A map with a pileup enabled may keep a deletion ledger: a multiset of events, empty when switched on.  Switching it
+ *       on is DCN_ERR_ARG once a row has added since the pileup was enabled or last reset (L1's rule), so the ledger and the
+ *       DEL column always describe the same rows.  It is independent of the insertion ledger and of the quality sums.
+ *   R2. While the ledger is kept, every D run of a row that adds (P2) appends one event (p, len, reverse):
+ *         p = ref_start + j is the position of the run's first D step;
+ *         len is the run's length (runs are maximal, by A4);
+ *         reverse is the row's strand.
+ *       Hence, while no counter has wrapped, DEL(q) equals the number of events with p <= q < p + len at every position q,
+ *       and the sum of all len is the DEL column's total.  A D run may be the first or the last run of a row.
+ *   R3. Events commute, as in L3: the ledger depends on the multiset of rows added, not on how batches are cut, on align's
+ *       trace groups, on lanes or on order.
+ *   R4. The canonical order, used wherever events are returned: ascending p; then the shorter len; then reverse 0 before 1.
+ *   R5. STARTS(p) is the number of events with that p.  An ALLELE at p is the class of its events with one len; its count
+ *       is the size of the class.  The WINNER is the allele with the largest count; ties go to the shorter.
+ *   R6. Integers only.  The result is unique.
+ *
+ * THE DEFINITION OF AN INDEL GENOTYPE.  Rules P1-P6, L1-L8, R1-R6 and G4 stand.  Added:
+ *   I1. Candidates.  At position p the insertion candidate is L5's winner, with a = its count and e = INS(p); it exists when
+ *       the map keeps an insertion ledger and INS(p) > 0 (L6's thresholds do not apply here).  The deletion candidate is
+ *       R5's winner, with a = its count and e = STARTS(p); it exists when the map keeps a deletion ledger and STARTS(p) > 0.
+ *       A candidate with a < max(1, min_count) is dropped.  A position has at most two candidates.
+ *   I2. Depth.  depth is P4's depth(p), and o = depth >= a ? depth - a : 0.  A row carries one allele at most once at one p,
+ *       and it adds exactly one of columns 0-5 at p, so a <= depth while nothing has wrapped.  Reads that carry another
+ *       allele count in o; so do reads with a D at p that began earlier.
+ *   I3. Costs, in unsigned 64-bit hundredths of a phred.  Ploidy 2, in VCF order R/R, R/V, V/V:
+ *         indel_centi a,  het_centi (a + o),  indel_centi o.
+ *       Ploidy 1, R then V: indel_centi a, indel_centi o.  indel_centi is what one read that contradicts the genotype
+ *       costs: a gap has no base quality, so it is a constant.
+ *   I4. The best genotype, GQ and PL[0 .. 3) follow G4: the first genotype in I3's order with the smallest cost is best, GQ
+ *       is capped at 99 and PL at 255, both by integer quotients.  QUAL = (cost(R/R) - cost[best]) / 100, saturated at
+ *       2^32 - 1 (cost(R) at ploidy 1).
+ *   I5. A candidate is CALLED when depth >= max(1, min_depth) and GQ >= min_gq.  It is a SITE when it is called, best is
+ *       not R/R (R at ploidy 1) and QUAL >= min_qual.
+ *   I6. Sites come in ascending pos.  At one pos the order is a front insertion (L2), then the deletion, then an insertion
+ *       behind.
+ *   I7. Stated limits.  One candidate per kind and position: there are no multi-allelic indel records.  Overlapping
+ *       deletions with different starts are independent sites.  The position is where A3 puts the gap: A3 takes an edit as
+ *       soon as one is available when it walks back from the end, so in a repeat the gap lies at the repeat's far end in
+ *       the record's direction.  Both strands agree on that, since T is always forward.  VCF's convention is the near end;
+ *       this is not normalised here.
+ *   I8. Integers only; a function of the counters, the two ledgers and the parameters.  indel_centi = 2000, min_count = 2
+ *       and the defaults shared with G8 are conventions, not measured optima. */
+#define DCN_DELETION_REVERSE 1u
+typedef struct dcn_deletion {
+    uint64_t pos;   /* record-relative, 0-based: R2's p */
+    uint32_t len;
+    uint32_t flags; /* DCN_DELETION_REVERSE */
+} dcn_deletion;     /* 16 bytes */
+#define DCN_INDEL_DELETION 1u
+#define DCN_INDEL_FRONT 2u /* an insertion in front of pos (L2) */
+typedef struct dcn_indel_params {
+    uint32_t ploidy;      /* 1 or 2 */
+    uint32_t min_depth;
+    uint32_t min_gq;      /* 0 .. 99 */
+    uint32_t min_qual;
+    uint32_t min_count;
+    uint32_t indel_centi; /* 0 .. 100000 */
+    uint32_t het_centi;   /* 0 .. 100000 */
+    uint32_t reserved;    /* must be 0 */
+} dcn_indel_params;       /* 32 bytes */
+typedef struct dcn_indel_site {
+    uint64_t pos;          /* record-relative, 0-based */
+    uint64_t bases_offset; /* into the bases array of the same call */
+    uint32_t len;          /* inserted or deleted bases */
+    uint32_t flags;        /* DCN_INDEL_DELETION, DCN_INDEL_FRONT */
+    uint32_t qual;         /* I4 */
+    uint32_t depth;        /* P4's depth */
+    uint32_t count;        /* a */
+    uint32_t events;       /* e */
+    uint8_t gt;            /* the best genotype's index in I3's order */
+    uint8_t gq;
+    uint8_t pl[3];         /* I3's order; pl[2] is 0 at ploidy 1 */
+    uint8_t reserved[3];
+} dcn_indel_site;          /* 48 bytes */
+
+/* The twin of dcn_anchor_map_pileup_keep_insertions.  keep != 0 switches the deletion ledger on (R1; keeping again changes
+ * nothing), keep = 0 drops it and leaves the counters.  DCN_ERR_ARG for a map without a pileup, and by rule R1;
+ * dcn_anchor_map_pileup_reset also empties a kept ledger, dcn_anchor_map_pileup_enable(map, 0) and dcn_index_destroy free it,
+ * dcn_index_clone gives an index without it, dcn_index_memory does not count it.  On a map that keeps one, dcn_pileup_batch
+ * and dcn_pileup_batch_qual also append, in the same call and behind the same checks (any DCN_ERR_ARG leaves counters and
+ * ledgers untouched), on the context's stream and accounted in FINISH: a counting pass over the aligned rows, one read-back
+ * of the totals, and only when there is a D run the scan, the growth of the ledger (16 bytes per event, geometric from
+ * DCN_DELETION_LEDGER_EVENTS events, 2^20 by default, read when the ledger first grows) and the writing pass.  A map on
+ * which no deletion ledger is kept behaves byte for byte as before; with one, the eight counters, the quality sums and the
+ * insertion ledger are exactly what they were.  Blocking. */
+int dcn_anchor_map_pileup_keep_deletions(dcn_index *map, int keep);
+/* the events of the ledger and the sum of their lengths (either pointer may be NULL).  No device work.  DCN_ERR_ARG for a
+ * map that keeps no deletion ledger. */
+int dcn_anchor_map_deletions_info(const dcn_index *map, uint64_t *n_events, uint64_t *n_deleted);
+
+/* The events with p in [start, start + n_bases) of a record, in R4's order.  An event belongs to the range by its p alone,
+ * even when its run leaves the range.
+ *   events      dcn_deletion entries (declared void * for the reason given at dcn_locate_batch), capacity of them
+ *   n_events    always receives the number of events there is
+ * DCN_ERR_CAPACITY when capacity is smaller: nothing else is written then; NULL with capacity 0 asks for the size.  Range
+ * errors as for dcn_anchor_map_fetch; DCN_ERR_ARG for a map that keeps no deletion ledger and for a range with 2^32 events
+ * or more.  Blocking: a pass over the whole ledger that counts the events of the range per position (no pileup column holds
+ * STARTS), the scan, a second pass that scatters them into their positions' buckets, a gather, and a sort of each bucket
+ * on the host. */
+int dcn_anchor_map_deletions_fetch(const dcn_index *map, uint32_t record, uint64_t start, uint64_t n_bases, void *events,
+                                   uint64_t capacity, uint64_t *n_events);
+
+/* Rules I1-I8 over positions [start, start + n_bases) of a record.
+ *   params      a dcn_indel_params (declared void * likewise): NULL, reserved != 0, a ploidy other than 1 or 2, min_gq > 99,
+ *               indel_centi or het_centi above 100000 are DCN_ERR_ARG, in this order
+ *   sites       dcn_indel_site entries in I6's order (declared void * likewise), site_capacity of them
+ *   bases       base_capacity bytes: the inserted bases of the insertion sites.  bases_offset is ascending and dense; a
+ *               deletion site has len = the deleted length and bases_offset = the offset reached so far
+ *   n_sites, n_inserted   always receive the number of sites and the sum of the insertion sites' lengths
+ * DCN_ERR_ARG then for n_sites / n_inserted NULL, for a map without a pileup and for one that keeps neither ledger (one is
+ * enough: the other kind then has no candidates); then the range errors of dcn_anchor_map_fetch.  Quality sums are not
+ * needed.  DCN_ERR_CAPACITY when either capacity is too small: nothing else is written then; NULLs with capacity 0 ask for
+ * the sizes (dcn_anchor_map_insertions_call's protocol).  Blocking, on the null stream with scratch of the call, no memory
+ * on the map: the insertion side is dcn_anchor_map_insertions_call's buckets and winner kernel with "INS > 0" as the flag,
+ * the deletion side dcn_anchor_map_deletions_fetch's buckets and a winner by len; then one thread per position counts its
+ * sites, a scan of the per-workgroup counts, a second pass that decides again and writes the sites, the scan of the
+ * insertion sites' lengths and the copy of their bases. */
+int dcn_anchor_map_indels_genotype(const dcn_index *map, const void *params, uint32_t record, uint64_t start, uint64_t n_bases,
+                                   void *sites, uint64_t site_capacity, uint8_t *bases, uint64_t base_capacity, uint64_t *n_sites,
+                                   uint64_t *n_inserted);
 
 /* ---- extended placements: each placement carried over the read's flanks, with soft clips (ABI 1.16) -------------------
  * (no reference counterpart.)  A placement's two intervals begin and end on the k-mer of an anchor hit: the read's bases
