@@ -284,6 +284,16 @@ class IndelSite(C.Structure):
     ]
 
 
+class LeftAlignInfo(C.Structure):
+    _fields_ = [
+        ("rows_aligned", C.c_uint64),
+        ("rows_changed", C.c_uint64),
+        ("gaps_shifted", C.c_uint64),
+        ("columns_passed", C.c_uint64),
+        ("gaps_merged", C.c_uint64),
+    ]
+
+
 class ExtendParams(C.Structure):
     _fields_ = [
         ("penalty", C.c_uint32),
@@ -438,10 +448,13 @@ _SIGNATURES = {
     "dcn_anchor_map_deletions_info": (C.c_int, [_vp, _u64p, _u64p]),
     "dcn_anchor_map_deletions_fetch": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _u64p]),
     "dcn_anchor_map_indels_genotype": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _u64p, _u64p]),
+    "dcn_left_align_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "dcn_anchor_map_pileup_left_align": (C.c_int, [_vp, C.c_int]),
+    "dcn_anchor_map_pileup_left_align_info": (C.c_int, [_vp, _vp]),
 }
 
 _lib = None
-ABI = (1, 21)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 22)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

@@ -3847,6 +3847,9 @@ struct MapArgs {
     // `indels`: markdup on a map that also keeps a deletion ledger, with the genotype of the winning insertion and the winning
     // deletion of every position (dcn_anchor_map_indels_genotype) as INDEL lines of the VCF; markdup and all it sets are set
     bool indels = false;
+    // `normalize`: indels on a map whose pileup left-aligns every row first (dcn_anchor_map_pileup_left_align): an indel in a
+    // repeat stands at the repeat's near end, where VCF wants it; indels and all it sets are set
+    bool normalize = false;
     unsigned indel_qual = 20, min_indel_count = 2;
 };
 
@@ -3897,7 +3900,7 @@ void append_paf(std::string &rows, const std::string &read_name, uint32_t read_l
 int run_map(const MapArgs &a) {
     const Stopwatch watch;
     const auto no_qualities = [&a](const std::string &name) {
-        die(std::string(a.indels ? "indels" : a.markdup ? "markdup" : a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
+        die(std::string(a.normalize ? "normalize" : a.indels ? "indels" : a.markdup ? "markdup" : a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
     };
     std::unique_ptr<FastxReader> reads; // (`call` looks at the first record before the reference is loaded)
     if (a.call) {
@@ -3918,6 +3921,7 @@ int run_map(const MapArgs &a) {
     if (a.consensus) deacon::check(dcn_anchor_map_pileup_keep_insertions(R.map.p, 1)); // (before the first row adds)
     if (a.call) deacon::check(dcn_anchor_map_pileup_keep_qualities(R.map.p, 1));
     if (a.indels) deacon::check(dcn_anchor_map_pileup_keep_deletions(R.map.p, 1));
+    if (a.normalize) deacon::check(dcn_anchor_map_pileup_left_align(R.map.p, 1)); // (rule N8: before the first row adds)
     if (a.markdup) deacon::check(dcn_anchor_map_duplicates_enable(R.map.p, 1));
     dcn_duplicate_params dprm = {};
     dprm.row_stride = sizeof(dcn_split_placement);
@@ -4130,6 +4134,7 @@ int run_map(const MapArgs &a) {
                 head += "##INFO=<ID=INDEL,Number=0,Type=Flag,Description=\"An insertion or a deletion\">\n"
                         "##INFO=<ID=IDV,Number=1,Type=Integer,Description=\"Reads that carry the allele\">\n"
                         "##INFO=<ID=IEV,Number=1,Type=Integer,Description=\"Insertions behind, or deletions that begin at, the position, of any allele\">\n";
+            if (a.normalize) head += "##left_aligned=The positions of insertions and deletions are left-aligned per read\n";
             head += "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
                     "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: phred gap to the second best genotype, at most 99\">\n"
                     "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Bases A, C, G, T of at least the minimum base quality\">\n"
@@ -4419,6 +4424,8 @@ int run_map(const MapArgs &a) {
     uint64_t reads_keyed = 0, distinct_fragments = 0; // (markdup)
     if (a.markdup) deacon::check(dcn_anchor_map_duplicates_info(R.map.p, nullptr, &reads_keyed, &distinct_fragments));
     if (a.has_duplicates) dup_out.finish();
+    dcn_left_align_info left = {}; // (normalize)
+    if (a.normalize) deacon::check(dcn_anchor_map_pileup_left_align_info(R.map.p, &left));
     const double secs = watch.seconds();
     if (!a.quiet) {
         if (a.extend)
@@ -4439,6 +4446,10 @@ int run_map(const MapArgs &a) {
             std::fprintf(stderr, "Genotyped %llu indel sites (%llu insertions, %llu deletions) over %llu deletion events of %llu bases\n",
                          (unsigned long long)indel_sites, (unsigned long long)insertion_sites, (unsigned long long)deletion_sites,
                          (unsigned long long)deletion_events, (unsigned long long)deleted_bases);
+        if (a.normalize)
+            std::fprintf(stderr, "Left-aligned %llu gaps over %llu columns in %llu of %llu placements (%llu gaps merged)\n",
+                         (unsigned long long)left.gaps_shifted, (unsigned long long)left.columns_passed, (unsigned long long)left.rows_changed,
+                         (unsigned long long)left.rows_aligned, (unsigned long long)left.gaps_merged);
         if (a.verify && !a.pileup)
             std::fprintf(stderr, "Verified %llu of %llu placements (%llu edits over %llu bases)\n", (unsigned long long)verified,
                          (unsigned long long)placements, (unsigned long long)edits_sum, (unsigned long long)verified_bases);
@@ -4513,6 +4524,11 @@ int run_map(const MapArgs &a) {
                     a.indel_qual, a.min_indel_count, (unsigned long long)deletion_events, (unsigned long long)deleted_bases,
                     (unsigned long long)indel_sites, (unsigned long long)insertion_sites, (unsigned long long)deletion_sites,
                     (unsigned long long)het_indel_sites, (unsigned long long)hom_indel_sites);
+        if (a.normalize)
+            appendf(js, "  \"left_aligned_rows\": %llu,\n  \"left_aligned_gaps\": %llu,\n  \"left_align_columns\": %llu,\n"
+                        "  \"left_align_merged_gaps\": %llu,\n",
+                    (unsigned long long)left.rows_changed, (unsigned long long)left.gaps_shifted, (unsigned long long)left.columns_passed,
+                    (unsigned long long)left.gaps_merged);
         appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
         for (uint32_t r = 0; r < R.n_records; ++r) {
             js += (r ? ",\n    {" : "\n    {");
@@ -4667,6 +4683,7 @@ void usage() {
                  "  genotype  As call, with a genotype per position from counts and quality sums: GQ, PL, QUAL, SNV sites as VCF\n"
                  "  markdup  As genotype, with reads that repeat the unclipped end of an earlier read marked and left out first\n"
                  "  indels  As markdup, with a genotype per insertion and deletion from the two ledgers: INDEL lines in the VCF\n"
+                 "  normalize  As indels, with every read's gaps left-aligned first: an indel in a repeat stands at its near end\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -5302,7 +5319,7 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "optical-distance rule; nothing is read from the bases or the qualities.  Mates are independent here: one input,\n"
                "and a read is a unit.  Pairs as units (one key from both mates' ends) are a feature of the library\n"
                "(dcn_mark_duplicates_batch) and of the Python layer (AnchorMap.mark_duplicates), not of this mode.\n";
-    else if (sub == "indels")
+    else if (sub == "indels" || sub == "normalize") // (normalize: indels' text with another head and a paragraph more, below)
         text = "Mark duplicates, pile up and genotype as markdup does, keep the deleted runs beside the inserted bases, and give the\n"
                "insertion and the deletion most reads carry at a position a genotype of their own: INDEL lines in the VCF\n\n"
                "Usage: deacon-hip indels [OPTIONS] <REF> [READS]\n\n"
@@ -5542,6 +5559,29 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "  compare    Report how many minimizers 2 to 32 indexes share, pair by pair\n"
                "  select     Keep the minimizers of several indexes chosen by which of the indexes hold them\n";
     if (!text) return false;
+    if (sub == "normalize") { // every option of indels keeps its text
+        std::string t = text;
+        t.erase(0, t.find("Usage: deacon-hip indels"));
+        t.replace(0, std::strlen("Usage: deacon-hip indels"), "Usage: deacon-hip normalize");
+        t = "Mark duplicates, pile up and genotype as indels does, with the gaps of every read's alignment moved to the near end\n"
+            "of their repeat first: the INDEL lines of the VCF stand where other callers and truth sets put them\n\n" + t +
+            "Left alignment: whatever the last sentences above say, in this mode a gap that lies in a homopolymer or a tandem\n"
+            "repeat is moved, read by read and before anything is counted, as far towards the start of the record as it can go\n"
+            "without changing the read's edit distance: a deleted stretch moves one base while the base in front of it equals\n"
+            "its last base, an inserted stretch while the read's base in front of it equals its last base; gaps of one kind\n"
+            "that meet become one and move on.  Substitutions keep their columns.  So the pileup, both ledgers, the quality\n"
+            "sums, -o, --variants and the VCF all see the moved gaps, and REF and ALT of an INDEL line do not end in the same\n"
+            "base.  The text of a line is indels'; the header gains one line, ##left_aligned.  -s gains left_aligned_rows (the\n"
+            "placements in which a gap moved), left_aligned_gaps, left_align_columns (the bases they moved over) and\n"
+            "left_align_merged_gaps.  Two limits: a read that begins inside a repeat cannot carry its gap in front of its own\n"
+            "first base, so such reads report the gap further right than reads that cover the repeat; and an insertion behind\n"
+            "a mismatch of the read is stopped by the read's base there, not by the reference's, so its line can still end in\n"
+            "the base in front.  Not normalised against the reference beyond a read's own extent; no multi-allelic lines.  On\n"
+            "input without a gap in a repeat the outputs are indels', byte for byte, apart from that header line and the\n"
+            "four fields.\n";
+        std::fputs(t.c_str(), stdout);
+        return true;
+    }
     std::fputs(text, stdout);
     return true;
 }
@@ -5712,11 +5752,12 @@ int main(int argc, char **argv) {
             return run_place(a);
         }
         if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup" || args[0] == "extend" || args[0] == "consensus" ||
-            args[0] == "call" || args[0] == "genotype" || args[0] == "markdup" || args[0] == "indels") {
+            args[0] == "call" || args[0] == "genotype" || args[0] == "markdup" || args[0] == "indels" || args[0] == "normalize") {
             MapArgs a;
             a.align = args[0] == "align";
             a.pileup = args[0] == "pileup";
-            a.indels = args[0] == "indels";
+            a.normalize = args[0] == "normalize";
+            a.indels = args[0] == "indels" || a.normalize;
             a.markdup = args[0] == "markdup" || a.indels;
             a.genotype = args[0] == "genotype" || a.markdup;
             a.call = args[0] == "call" || a.genotype;

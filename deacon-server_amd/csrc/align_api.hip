@@ -1,10 +1,12 @@
 // align_api.hip -- dcn_align_batch: the rows of dcn_verify_batch, each verified one with its alignment (kernels in
-// align.hip, the trace and the walk back in dcn_align.h, the checks and the first pass in verify_api.hip).  Its rules
+// align.hip, the trace and the walk back in dcn_align.h, the checks and the first pass in verify_api.hip), and
+// dcn_left_align_batch: the same call with the left-align kernel (left_align.hip, dcn_left_align.h) in front of the scan.  Its rules
 // over the rows (dcn_align_check_rows), its passes up to the scan of the run counts (dcn_align_runs) and its gather
 // (dcn_align_gather_runs) are functions of their own: dcn_pileup_batch (pileup_api.hip) runs the same sequence.
 #include "dcn_align.h"
 #include "dcn_ctx.h"
 #include "dcn_dump_sweep.h"
+#include "dcn_left_align.h"
 #include "dcn_verify.h"
 
 #include <cstdlib>
@@ -35,7 +37,7 @@ int dcn_align_check_rows(const dcn_verify_plan &plan) {
 }
 
 int dcn_align_runs(dcn_ctx *c, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
-                   const dcn_verify_plan &plan, uint32_t *edits, int *prof_slot_out, uint64_t *n_work_out) {
+                   const dcn_verify_plan &plan, uint32_t *edits, int *prof_slot_out, uint64_t *n_work_out, dcn_la_totals *left) {
     const uint64_t n_rows = plan.items.size();
     hipStream_t st = c->stream;
     int prof_slot = -1;
@@ -105,8 +107,28 @@ int dcn_align_runs(dcn_ctx *c, const dcn_index *map, const uint8_t *bases, const
         DCN_TRY(dcn_launch_align(aa, st)); // (one stream: a group's kernel has read its trace before the next one writes)
         w0 = w1;
     }
+    if (left) { // rules N1 - N5 on the runs in their slots: the scan and everything behind it see the result
+        DCN_TRY(grow(&c->d_aln_scratch, &c->aln_scratch_cap, slot_words, "left-align scratch"));
+        if (!c->d_aln_la_totals) DCN_TRY(dev_alloc(&c->d_aln_la_totals, 4, "left-align totals"));
+        DCN_HIP(hipMemsetAsync(c->d_aln_la_totals, 0, 4 * sizeof(unsigned long long), st));
+        dcn_left_align_args la;
+        memset(&la, 0, sizeof(la));
+        la.items = aa.items;
+        la.work = aa.work;
+        la.n_work = n_work;
+        la.s_packed = aa.s_packed;
+        la.s_invmask = aa.s_invmask;
+        la.t_packed = aa.t_packed;
+        la.t_invmask = aa.t_invmask;
+        la.slots = c->d_aln_slots;
+        la.scratch = c->d_aln_scratch;
+        la.n_ops = c->d_aln_n_ops;
+        la.totals = c->d_aln_la_totals;
+        DCN_TRY(dcn_launch_left_align(la, st));
+    }
     DCN_TRY(dcn_launch_offsets_scan(c->d_aln_n_ops, (uint32_t)n_rows, c->d_aln_block_sums, c->d_aln_offsets, st));
     DCN_HIP(hipStreamSynchronize(st));
+    if (left) DCN_HIP(hipMemcpy(left, c->d_aln_la_totals, sizeof(*left), hipMemcpyDeviceToHost));
     *n_work_out = n_work;
     return DCN_OK;
 }
@@ -124,9 +146,11 @@ int dcn_align_gather_runs(dcn_ctx *c, uint64_t n_work, uint64_t total) {
     return dcn_launch_align_gather(ga, c->stream);
 }
 
-extern "C" int dcn_align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
-                               const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits,
-                               uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity) {
+namespace {
+// dcn_align_batch, and with `left` dcn_left_align_batch: the same checks, order and messages
+int align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads, const void *params,
+                const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits, uint64_t *cigar_offsets, uint32_t *cigar,
+                uint64_t capacity, dcn_la_totals *left, uint64_t *n_aligned) {
     dcn_verify_plan plan;
     DCN_TRY(dcn_verify_walk(ctx, map, bases, offsets, n_reads, params, row_offsets, rows, n_rows, edits, &plan));
     if (!cigar_offsets) return dcn_fail(DCN_ERR_ARG, "cigar_offsets is NULL");
@@ -139,7 +163,8 @@ extern "C" int dcn_align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t
     hipStream_t st = c->stream;
     int prof_slot = -1;
     uint64_t n_work = 0;
-    DCN_TRY(dcn_align_runs(c, map, bases, offsets, n_reads, plan, edits, &prof_slot, &n_work));
+    DCN_TRY(dcn_align_runs(c, map, bases, offsets, n_reads, plan, edits, &prof_slot, &n_work, left));
+    *n_aligned = n_work;
     DCN_HIP(hipMemcpy(cigar_offsets, c->d_aln_offsets, (n_rows + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
     const uint64_t total = cigar_offsets[n_rows];
     const bool fits = total <= capacity;
@@ -156,4 +181,29 @@ extern "C" int dcn_align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t
                                               " (cigar_offsets is complete: call again with that capacity)");
     if (total > 0) DCN_HIP(hipMemcpy(cigar, c->d_aln_cigar, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return DCN_OK;
+}
+} // namespace
+
+extern "C" int dcn_align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                               const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits,
+                               uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity) {
+    uint64_t n_aligned = 0;
+    return align_batch(ctx, map, bases, offsets, n_reads, params, row_offsets, rows, n_rows, edits, cigar_offsets, cigar, capacity, nullptr,
+                       &n_aligned);
+}
+
+static_assert(sizeof(dcn_left_align_info) == 40 && sizeof(dcn_la_totals) == 32, "left-align info is ABI");
+
+extern "C" int dcn_left_align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                                    const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits,
+                                    uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity, void *info_out) {
+    dcn_left_align_info *const info = static_cast<dcn_left_align_info *>(info_out);
+    dcn_la_totals t = {0, 0, 0, 0};
+    uint64_t n_aligned = 0;
+    if (info) memset(info, 0, sizeof(*info));
+    const int rc = align_batch(ctx, map, bases, offsets, n_reads, params, row_offsets, rows, n_rows, edits, cigar_offsets, cigar, capacity, &t,
+                               &n_aligned);
+    // (complete whenever cigar_offsets is: DCN_ERR_CAPACITY included)
+    if (info) *info = {n_aligned, t.rows_changed, t.gaps_shifted, t.columns_passed, t.gaps_merged};
+    return rc;
 }

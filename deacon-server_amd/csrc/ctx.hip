@@ -95,7 +95,7 @@ static void free_ctx(dcn_ctx *c) {
                    c->d_pls_rbits, c->d_pls_n_rounds, c->d_pls_read_counts, c->d_pls_counts, c->d_pls_block_sums,
                    c->d_pls_offsets, c->d_pls_rounds, c->d_pls_out, c->d_ppr_out, c->d_ppr_hist, c->d_vfy_items, c->d_vfy_out,
                    c->d_aln_work, c->d_aln_n_ops, c->d_aln_trace, c->d_aln_slots, c->d_aln_cigar, c->d_aln_offsets, c->d_aln_block_sums,
-                   c->d_ext_items, c->d_ext_out, c->d_pile_quals};
+                   c->d_ext_items, c->d_ext_out, c->d_pile_quals, c->d_aln_scratch, c->d_aln_la_totals};
     for (void *p : dev)
         if (p && !((char *)p >= c->d_slab && (char *)p < c->d_slab + c->slab_bytes)) hipFree(p);
     if (c->d_slab) hipFree(c->d_slab);

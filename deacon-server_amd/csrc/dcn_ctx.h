@@ -193,6 +193,10 @@ struct dcn_ctx {
     uint64_t *d_aln_offsets = nullptr;
     unsigned long long *d_aln_block_sums = nullptr;
     uint64_t aln_work_cap = 0, aln_rows_cap = 0, aln_offsets_cap = 0, aln_trace_cap = 0, aln_slots_cap = 0, aln_cigar_cap = 0;
+    // left-align buffers (lazy, first call that left-aligns): a second slot array and the four totals of a call
+    uint32_t *d_aln_scratch = nullptr;
+    uint64_t aln_scratch_cap = 0;
+    unsigned long long *d_aln_la_totals = nullptr;
     // extend buffers (lazy, first dcn_extend_batch; dcn_verify.h): two items and two results per row, grown to the largest n_rows
     dcn_extend_item *d_ext_items = nullptr;
     dcn_extend_result *d_ext_out = nullptr;

@@ -130,6 +130,10 @@ struct dcn_index {
     dcn_ins_ledger *ledger = nullptr;
     // ... and the deletion ledger (dcn_anchor_map_pileup_keep_deletions, indels_api.hip).  Null: none is kept.
     dcn_del_ledger *del_ledger = nullptr;
+    // ... and whether its rows are left-aligned before they are piled up (dcn_anchor_map_pileup_left_align, rule N8), with
+    // dcn_left_align_info's five numbers summed over the calls since the pileup was enabled or reset
+    bool pileup_left_align = false;
+    uint64_t left_align_info[5] = {0, 0, 0, 0, 0};
     // ... and the quality sums beside the counters (dcn_anchor_map_pileup_keep_qualities, pileup_api.hip): 4 words per base
     // of the pileup, laid out by dcn_pile_sum_index (dcn_pileup.h).  Null: none are kept.
     uint32_t *d_pileup_qsums = nullptr;

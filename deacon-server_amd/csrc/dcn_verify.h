@@ -194,14 +194,30 @@ struct dcn_align_gather_args {
 };
 int dcn_launch_align_gather(const dcn_align_gather_args &args, hipStream_t stream);
 
+// the left alignment of the rows' runs in their slots, behind the last align kernel (left_align.hip, dcn_left_align.h)
+struct dcn_left_align_args {
+    const dcn_verify_item *items;
+    const dcn_align_work *work;
+    uint64_t n_work;
+    const uint32_t *s_packed, *s_invmask, *t_packed, *t_invmask;
+    uint32_t *slots;            // the call's run slots: a changed row's runs end at its slot_end again
+    uint32_t *scratch;          // as many words as the slots: a row builds its new runs in the words of its own slot
+    uint32_t *n_ops;            // per row of the call: a changed row's is written again
+    unsigned long long *totals; // rows changed, gaps shifted, columns passed, gaps merged: added to
+};
+int dcn_launch_left_align(const dcn_left_align_args &args, hipStream_t stream);
+
 // ---- the host side that dcn_align_batch and dcn_pileup_batch share (align_api.hip) -----------------------------------
 // align's own rules over a walked call: fewer than 2^32 rows, and no placed row with an interval of 2^28 bases or more
 int dcn_align_check_rows(const dcn_verify_plan &plan);
 // verify, the read-back of the edits, the work list, the align kernel of every trace group and the scan of the run
 // counts, then a wait: the edits are in `edits`, the run counts in c->d_aln_n_ops, their offsets in c->d_aln_offsets, the
 // runs in the slots.  The run stays open behind the DISTINCT mark, as dcn_verify_enqueue leaves it.
+// `left` not null: the left-align kernel runs behind the last align kernel and in front of the scan, and its four totals
+// are read back into *left.  Null: not one launch, copy or allocation more than before.
+struct dcn_la_totals; // (dcn_left_align.h)
 int dcn_align_runs(dcn_ctx *c, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
-                   const dcn_verify_plan &plan, uint32_t *edits, int *prof_slot_out, uint64_t *n_work_out);
+                   const dcn_verify_plan &plan, uint32_t *edits, int *prof_slot_out, uint64_t *n_work_out, dcn_la_totals *left);
 // the gather of `total` > 0 runs from the slots into c->d_aln_cigar, which grows to hold them
 int dcn_align_gather_runs(dcn_ctx *c, uint64_t n_work, uint64_t total);
 

@@ -125,6 +125,23 @@ DCN_WF_FN uint64_t dcn_wf_match_run(const dcn_wf_side &S, int64_t i, const dcn_w
     return t < limit ? t : limit;
 }
 
+// A side read backwards from its sequence base a: base k of the result is the complement of the side's base a - k, and
+// its invalid bit.  Both sides of a comparison turned this way compare as they did (the complement of a code is the
+// code ^ 2 on both).  A forward side becomes a reverse one and the other way round: no new fetch is needed.
+DCN_WF_FN dcn_wf_side dcn_wf_side_back(const dcn_wf_side &s, int64_t a) {
+    dcn_wf_side b = s;
+    b.reverse = s.reverse ? 0u : 1u;
+    b.origin = s.reverse ? s.origin - 1 - a : s.origin + a + 1;
+    return b;
+}
+
+// the backward form of dcn_wf_match_run: the length of the run S[i - t] == T[j - t], t = 0, 1, ..., at most `limit`.  The
+// 16 bases of the last group may begin up to 15 bases in front of base i - limit + 1: Load says what is readable there.
+template <typename Load>
+DCN_WF_FN uint64_t dcn_wf_match_run_back(const dcn_wf_side &S, int64_t i, const dcn_wf_side &T, int64_t j, uint64_t limit) {
+    return dcn_wf_match_run<Load>(dcn_wf_side_back(S, i), 0, dcn_wf_side_back(T, j), 0, limit);
+}
+
 // One diagonal of one score.  F_s[k] is the furthest base i of S (m bases) that a path of cost <= s reaches on diagonal
 // k = j - i (j: the base of T, n bases), for max(-s, -m) <= k <= min(s, n).  It comes from F_{s-1}[k] + 1 (substitution),
 // F_{s-1}[k - 1] (a base of T alone) and F_{s-1}[k + 1] + 1 (a base of S alone), cut to the rectangle, then runs on while

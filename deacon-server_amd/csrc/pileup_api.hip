@@ -6,6 +6,7 @@
 // dcn_pileup_batch_qual is the same sequence with the qualities staged in front of the kernel's quality form.
 #include "dcn_ctx.h"
 #include "dcn_dump_sweep.h"
+#include "dcn_left_align.h"
 #include "dcn_pileup.h"
 #include "dcn_verify.h"
 
@@ -54,6 +55,8 @@ extern "C" int dcn_anchor_map_pileup_enable(dcn_index *map, int enable) {
         map->pileup_rows = 0;
         map->ledger = nullptr;
         map->del_ledger = nullptr;
+        map->pileup_left_align = false;
+        memset(map->left_align_info, 0, sizeof(map->left_align_info));
         return DCN_OK;
     }
     if (map->d_pileup) return DCN_OK;
@@ -74,6 +77,24 @@ extern "C" int dcn_anchor_map_pileup_reset(dcn_index *map) {
     map->pileup_rows = 0;
     if (map->ledger) map->ledger->n_events = map->ledger->n_bases = 0; // (the arrays stay: the next append begins at their start)
     if (map->del_ledger) map->del_ledger->n_events = map->del_ledger->n_deleted = 0;
+    memset(map->left_align_info, 0, sizeof(map->left_align_info));
+    return DCN_OK;
+}
+
+extern "C" int dcn_anchor_map_pileup_left_align(dcn_index *map, int on) {
+    DCN_TRY(check_pileup(map));
+    if ((on != 0) == map->pileup_left_align) return DCN_OK;
+    if (map->pileup_rows != 0) // rule N8
+        return dcn_fail(DCN_ERR_ARG, std::to_string(map->pileup_rows) + " rows have added to the pileup since it was enabled or reset: every row of "
+                                                                         "a pileup is piled up the same way (dcn_anchor_map_pileup_reset first)");
+    map->pileup_left_align = on != 0;
+    return DCN_OK;
+}
+
+extern "C" int dcn_anchor_map_pileup_left_align_info(const dcn_index *map, void *info) {
+    DCN_TRY(check_pileup(map));
+    if (!info) return dcn_fail(DCN_ERR_ARG, "info is NULL");
+    memcpy(info, map->left_align_info, sizeof(dcn_left_align_info));
     return DCN_OK;
 }
 
@@ -103,7 +124,8 @@ int pileup_run(dcn_ctx *c, dcn_index *map, const uint8_t *bases, const uint8_t *
     hipStream_t st = c->stream;
     int prof_slot = -1;
     uint64_t n_work = 0, total = 0;
-    DCN_TRY(dcn_align_runs(c, map, bases, offsets, n_reads, plan, edits, &prof_slot, &n_work));
+    dcn_la_totals left = {0, 0, 0, 0}; // rule N8: the runs that are piled up are N5's while the map's switch is on
+    DCN_TRY(dcn_align_runs(c, map, bases, offsets, n_reads, plan, edits, &prof_slot, &n_work, map->pileup_left_align ? &left : nullptr));
     DCN_HIP(hipMemcpy(&total, c->d_aln_offsets + n_rows, sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (total > 0) { // the runs stay on the device: the buffer grows to what the scan reports
         DCN_TRY(dcn_align_gather_runs(c, n_work, total));
@@ -141,7 +163,14 @@ int pileup_run(dcn_ctx *c, dcn_index *map, const uint8_t *bases, const uint8_t *
     DCN_TRY(finish_run(c, prof_slot));
     uint64_t added = 0; // rule P2: the rows with an alignment and n > 0
     for (uint64_t row = 0; row < n_rows; ++row) added += edits[row] < DCN_VERIFY_OVER && plan.items[row].n > 0;
-    map->pileup_rows += added; // (rules L1 and Q1 ask)
+    map->pileup_rows += added; // (rules L1, Q1 and N8 ask)
+    if (map->pileup_left_align) {
+        map->left_align_info[0] += n_work;
+        map->left_align_info[1] += left.rows_changed;
+        map->left_align_info[2] += left.gaps_shifted;
+        map->left_align_info[3] += left.columns_passed;
+        map->left_align_info[4] += left.gaps_merged;
+    }
     if (n_added) *n_added = added;
     return DCN_OK;
 }

@@ -693,6 +693,10 @@ GENOTYPE_NONE, GENOTYPES = N.GENOTYPE_NONE, N.GENOTYPES
 # numpy views of dcn_deletion (16 bytes) and dcn_indel_site (48 bytes): an event of a deletion ledger, and what
 # AnchorMap.indels_genotype returns per site; bases_offset points into the bases returned beside the sites
 DELETION_DTYPE = np.dtype([("pos", np.uint64), ("len", np.uint32), ("flags", np.uint32)])
+# dcn_left_align_info: the rows with an alignment, and of those the rows in which a gap took a step, the gaps that took one, their steps
+# and the times two gaps became one
+LEFT_ALIGN_INFO_DTYPE = np.dtype([("rows_aligned", np.uint64), ("rows_changed", np.uint64), ("gaps_shifted", np.uint64),
+                                  ("columns_passed", np.uint64), ("gaps_merged", np.uint64)])
 INDEL_SITE_DTYPE = np.dtype([("pos", np.uint64), ("bases_offset", np.uint64), ("len", np.uint32), ("flags", np.uint32), ("qual", np.uint32),
                              ("depth", np.uint32), ("count", np.uint32), ("events", np.uint32), ("gt", np.uint8), ("gq", np.uint8),
                              ("pl", np.uint8, (3,)), ("reserved", np.uint8, (3,))])
@@ -898,6 +902,20 @@ class AnchorMap(Index):
         in include/deacon_hip.h): every D run of a row that Placer.pileup_batch adds also leaves (position, length, strand).
         Refused once a row has added since pileup_enable() or pileup_reset(); keep=False drops it and leaves the counters."""
         N.check(N.lib().dcn_anchor_map_pileup_keep_deletions(self._h, 1 if keep else 0))
+
+    def pileup_left_align(self, on=True):
+        """Left-align every row before it is piled up (dcn_anchor_map_pileup_left_align; the definition of a left-aligned
+        placement is in include/deacon_hip.h): while on, Placer.pileup_batch adds the runs of rule N5 to the counters, the
+        quality sums and both ledgers, so that a gap in a repeat lies at the repeat's near end.  Refused once a row has
+        added since pileup_enable() or pileup_reset() (rule N8); pileup_disable() clears it."""
+        N.check(N.lib().dcn_anchor_map_pileup_left_align(self._h, 1 if on else 0))
+
+    def pileup_left_align_info(self):
+        """-> dict of LEFT_ALIGN_INFO_DTYPE's five numbers, summed over the pileup_batch calls that ran with
+        pileup_left_align() on since pileup_enable() or pileup_reset()"""
+        info = np.zeros(1, LEFT_ALIGN_INFO_DTYPE)
+        N.check(N.lib().dcn_anchor_map_pileup_left_align_info(self._h, _ptr(info)))
+        return {name: int(info[name][0]) for name in LEFT_ALIGN_INFO_DTYPE.names}
 
     def deletions_info(self):
         """-> (events of the deletion ledger, the sum of their lengths)"""
@@ -1127,6 +1145,20 @@ class Placer(_Context):
         one call with an estimate and, on DCN_ERR_CAPACITY, a second with the size the first reported; a number: one call
         with that capacity, and the error is raised.  profile(): pack in its slot, both kernels, the scan and the
         gather in 'finish'."""
+        return self._align_batch(None, bases, offsets, rows, row_offsets, max_edits, max_permille, capacity)
+
+    def left_align_batch(self, bases, offsets, rows, row_offsets=None, max_edits=1023, max_permille=200, capacity=None):
+        """align_batch with every aligned row left-aligned (dcn_left_align_batch; the definition of a left-aligned placement
+        is in include/deacon_hip.h): a gap in a homopolymer or a tandem repeat lies at the repeat's near end in the record's
+        direction, as VCF wants it, not at the far end where the walk back leaves it.  -> (edits, cigar_offsets, cigar,
+        info): the first three as align_batch returns them, edits identical; info a dict of LEFT_ALIGN_INFO_DTYPE's five
+        numbers for this call."""
+        info = np.zeros(1, LEFT_ALIGN_INFO_DTYPE)
+        out = self._align_batch(info, bases, offsets, rows, row_offsets, max_edits, max_permille, capacity)
+        return out + ({name: int(info[name][0]) for name in LEFT_ALIGN_INFO_DTYPE.names},)
+
+    def _align_batch(self, info, bases, offsets, rows, row_offsets, max_edits, max_permille, capacity):
+        """align_batch (info None) and left_align_batch (a LEFT_ALIGN_INFO_DTYPE[1] that receives the totals)"""
         bases, offsets, n_reads = _batch(bases, offsets)
         rows = np.ascontiguousarray(rows)
         n_rows = len(rows)
@@ -1138,9 +1170,10 @@ class Placer(_Context):
 
         def call(cap):
             cigar = np.zeros(max(cap, 1), np.uint32)
-            rc = N.lib().dcn_align_batch(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None, _ptr(offsets), n_reads,
-                                         C.byref(p), _ptr(row_offsets), _ptr(rows) if n_rows else None, n_rows, _ptr(edits),
-                                         _ptr(cigar_offsets), _ptr(cigar) if cap else None, cap)
+            args = (self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None, _ptr(offsets), n_reads,
+                    C.byref(p), _ptr(row_offsets), _ptr(rows) if n_rows else None, n_rows, _ptr(edits),
+                    _ptr(cigar_offsets), _ptr(cigar) if cap else None, cap)
+            rc = N.lib().dcn_align_batch(*args) if info is None else N.lib().dcn_left_align_batch(*args, _ptr(info))
             return rc, cigar
 
         rc, cigar = call(4 * n_rows + 64 if capacity is None else int(capacity))

@@ -84,9 +84,10 @@ enum {
  * 1.18 = dcn_anchor_map_pileup_keep_qualities / _fetch_qualities, dcn_pileup_batch_qual.
  * 1.19 = dcn_anchor_map_genotype.
  * 1.20 = dcn_anchor_map_duplicates_enable / _reset / _info, dcn_mark_duplicates_batch.
- * 1.21 = dcn_anchor_map_pileup_keep_deletions, dcn_anchor_map_deletions_info / _fetch, dcn_anchor_map_indels_genotype. */
+ * 1.21 = dcn_anchor_map_pileup_keep_deletions, dcn_anchor_map_deletions_info / _fetch, dcn_anchor_map_indels_genotype.
+ * 1.22 = dcn_left_align_batch, dcn_anchor_map_pileup_left_align / _left_align_info. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 21
+#define DCN_ABI_MINOR 22
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -1422,6 +1423,73 @@ int dcn_anchor_map_deletions_fetch(const dcn_index *map, uint32_t record, uint64
 int dcn_anchor_map_indels_genotype(const dcn_index *map, const void *params, uint32_t record, uint64_t start, uint64_t n_bases,
                                    void *sites, uint64_t site_capacity, uint8_t *bases, uint64_t base_capacity, uint64_t *n_sites,
                                    uint64_t *n_inserted);
+
+/* ---- left-aligned placements: the gaps of an alignment at a repeat's near end (ABI 1.22) -------------------------------
+ * (no reference counterpart.)  A3 leaves a gap at the far end of a repeat (I7); VCF's convention is the near end.
+ *
+ * THE DEFINITION OF A LEFT-ALIGNED PLACEMENT.  Rules 1-6 of a verified placement and A1-A6 of an aligned placement stand.
+ * Read the alignment column by column: an '=' or X column pairs S[i] with T[j], an I column is S[i] alone, a D column is
+ * T[j] alone.  Added:
+ *   N1. A GAP is a maximal run of I or of D.  The gaps are taken in order from the start of both intervals.  A gap is final
+ *       before the next one is looked at.
+ *   N2. One STEP for a D gap over T[j, j+len), where the column in front pairs S[x] with T[j-1] and is an '=' or X column:
+ *       the step is allowed if T[j-1] EQUAL T[j+len-1] by rule 2 (an invalid base equals nothing, so such a column is never
+ *       passed), and not if that column is the row's first column.  After the step the gap covers T[j-1, j+len-1); the
+ *       column follows the gap, pairs S[x] with T[j+len-1] and keeps its op.
+ *   N3. One step for an I gap over S[i, i+len), where the column in front pairs S[i-1] with T[y]: allowed if S[i-1] EQUAL
+ *       S[i+len-1] and the column is not the row's first.  After the step the gap covers S[i-1, i+len-1); the column
+ *       follows the gap, pairs S[i+len-1] with T[y] and keeps its op.  S is the reverse complement when the row says so
+ *       (A5): the comparison is on S as aligned.
+ *   N4. A gap takes steps until none is allowed.  If it comes to lie directly behind an earlier gap of the same kind, the
+ *       two become one gap, which goes on taking steps with its new length.  A gap directly behind a gap of the other kind
+ *       stops (this cannot arise from an A3 alignment, where an I next to a D costs more than an X, and N2 / N3 preserve
+ *       the cost: the rule is stated so that the definition is total).  A gap that A3 put first in the row stays first, and
+ *       no step makes a gap first.
+ *   N5. Afterwards equal neighbouring ops merge into runs, as in A4.  The result has the same multiset of column ops and
+ *       the same d, so it is still an optimal alignment; '=' + X + I covers m, '=' + X + D covers n, and n_ops <= 2 d + 1
+ *       still holds.  n_ops may be larger or smaller than before.  A row without a gap is unchanged.
+ *   N6. The procedure is idempotent and its result unique.  It depends only on S, T and A3's ops: not on lanes, chunking,
+ *       trace groups or how a batch is cut.  Integers only.
+ *   N7. Stated limits.  A row that begins inside a repeat cannot carry its gap past its own first column: such rows report
+ *       the gap further right than rows that cover the repeat (the mirror of I7's limit at the far end).  An insertion in
+ *       front of which the read has an X column is stopped by the read's base, not by the record's: its VCF line can
+ *       therefore still end in the anchor's base.
+ *   N8. A map's pileup either left-aligns every row that adds to it or none: dcn_anchor_map_pileup_left_align changes the
+ *       switch only while no row has added since the pileup was enabled or reset (Q1's spirit).
+ * The totals count, over the rows of a call: ROWS CHANGED, the rows in which a gap took a step; GAPS SHIFTED, the gaps of
+ * A3's alignment that took at least one step, a gap that merged into an earlier one counting for itself; COLUMNS PASSED, the
+ * steps of all gaps; GAPS MERGED, the times two gaps became one. */
+typedef struct dcn_left_align_info {
+    uint64_t rows_aligned;   /* the rows with an alignment (A1) */
+    uint64_t rows_changed;
+    uint64_t gaps_shifted;
+    uint64_t columns_passed;
+    uint64_t gaps_merged;
+} dcn_left_align_info;       /* 40 bytes */
+
+/* dcn_align_batch with rules N1-N7 applied to every aligned row: the arguments, the checks, their order, their messages
+ * and row numbers, and the capacity protocol are dcn_align_batch's.  edits is identical; cigar_offsets and cigar are those
+ * of N5 (cigar_offsets[n_rows] is the size needed, counted behind the left alignment).
+ *   info   a dcn_left_align_info (declared void * for the reason given at dcn_locate_batch), or NULL; it is zeroed first
+ *          and complete whenever cigar_offsets is (DCN_ERR_CAPACITY included)
+ * One kernel more than dcn_align_batch, behind the align kernel of the last trace group and in front of the scan of the run
+ * counts, accounted in FINISH: a wave per aligned row, which reads the row's runs once and does nothing more when none is
+ * a gap.  Device memory beyond dcn_align_batch's, freed with the context: a second array of run slots (4 (2 d + 1) bytes
+ * per aligned row of the largest call) and 32 bytes. */
+int dcn_left_align_batch(dcn_ctx *ctx, const dcn_index *map, const uint8_t *bases, const uint64_t *offsets, uint32_t n_reads,
+                         const void *params, const uint64_t *row_offsets, const void *rows, uint64_t n_rows, uint32_t *edits,
+                         uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity, void *info);
+
+/* Rule N8's switch.  While it is on, dcn_pileup_batch and dcn_pileup_batch_qual pile up the runs of N5 and append N5's
+ * events to both ledgers: counters, quality sums and ledgers are those of a caller who had handed in left-aligned
+ * alignments.  on != 0 sets it, on = 0 clears it; setting it to what it is changes nothing and always succeeds.
+ * DCN_ERR_ARG for a map without a pileup, and when rows have added since the pileup was enabled or reset (the message names
+ * dcn_anchor_map_pileup_reset).  dcn_anchor_map_pileup_enable(map, 0) clears it; dcn_anchor_map_pileup_reset keeps it and
+ * zeroes the totals.  A map that never sets it behaves exactly as before in every call: not one launch or copy more. */
+int dcn_anchor_map_pileup_left_align(dcn_index *map, int on);
+/* A dcn_left_align_info (declared void * likewise) summed over the map's pileup calls that ran with the switch on, since
+ * the pileup was enabled or reset.  No device work.  DCN_ERR_ARG for a map without a pileup, then for info NULL. */
+int dcn_anchor_map_pileup_left_align_info(const dcn_index *map, void *info);
 
 /* ---- extended placements: each placement carried over the read's flanks, with soft clips (ABI 1.16) -------------------
  * (no reference counterpart.)  A placement's two intervals begin and end on the k-mer of an anchor hit: the read's bases
