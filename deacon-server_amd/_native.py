@@ -294,6 +294,41 @@ class LeftAlignInfo(C.Structure):
     ]
 
 
+class StrandParams(C.Structure):
+    _fields_ = [
+        ("max_sb_centi", C.c_uint32),
+        ("min_alt_strand", C.c_uint32),
+        ("min_strand_depth", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class StrandQuery(C.Structure):
+    _fields_ = [
+        ("pos", C.c_uint64),
+        ("kind", C.c_uint32),
+        ("ref_code", C.c_uint32),
+        ("alt_mask", C.c_uint32),
+        ("count", C.c_uint32),
+        ("count_reverse", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class StrandSite(C.Structure):
+    _fields_ = [
+        ("fwd", C.c_uint32 * 4),
+        ("rev", C.c_uint32 * 4),
+        ("table", C.c_uint32 * 4),
+        ("sb_centi", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+STRAND_BIAS, STRAND_ONE_SIDED = 1, 2  # DCN_STRAND_*: the flags of rule S6
+
+
 class ExtendParams(C.Structure):
     _fields_ = [
         ("penalty", C.c_uint32),
@@ -451,10 +486,14 @@ _SIGNATURES = {
     "dcn_left_align_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp]),
     "dcn_anchor_map_pileup_left_align": (C.c_int, [_vp, C.c_int]),
     "dcn_anchor_map_pileup_left_align_info": (C.c_int, [_vp, _vp]),
+    "dcn_anchor_map_pileup_keep_strands": (C.c_int, [_vp, C.c_int]),
+    "dcn_anchor_map_pileup_fetch_strands": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
+    "dcn_anchor_map_strand_evidence": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp]),
+    "dcn_anchor_map_indels_strand": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp]),
 }
 
 _lib = None
-ABI = (1, 22)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 23)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():

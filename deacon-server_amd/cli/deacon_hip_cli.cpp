@@ -3851,6 +3851,11 @@ struct MapArgs {
     // repeat stands at the repeat's near end, where VCF wants it; indels and all it sets are set
     bool normalize = false;
     unsigned indel_qual = 20, min_indel_count = 2;
+    // `strand`: normalize on a map whose pileup also keeps strand planes (dcn_anchor_map_pileup_keep_strands): every VCF line
+    // carries its strand evidence (dcn_anchor_map_strand_evidence, dcn_anchor_map_indels_strand) as FILTER, SB, ADF and ADR;
+    // normalize and all it sets are set
+    bool strand = false;
+    unsigned max_sb = 1083, min_alt_strand = 1, min_strand_depth = 3;
 };
 
 // one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
@@ -3900,7 +3905,7 @@ void append_paf(std::string &rows, const std::string &read_name, uint32_t read_l
 int run_map(const MapArgs &a) {
     const Stopwatch watch;
     const auto no_qualities = [&a](const std::string &name) {
-        die(std::string(a.normalize ? "normalize" : a.indels ? "indels" : a.markdup ? "markdup" : a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
+        die(std::string(a.strand ? "strand" : a.normalize ? "normalize" : a.indels ? "indels" : a.markdup ? "markdup" : a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
     };
     std::unique_ptr<FastxReader> reads; // (`call` looks at the first record before the reference is loaded)
     if (a.call) {
@@ -3922,6 +3927,7 @@ int run_map(const MapArgs &a) {
     if (a.call) deacon::check(dcn_anchor_map_pileup_keep_qualities(R.map.p, 1));
     if (a.indels) deacon::check(dcn_anchor_map_pileup_keep_deletions(R.map.p, 1));
     if (a.normalize) deacon::check(dcn_anchor_map_pileup_left_align(R.map.p, 1)); // (rule N8: before the first row adds)
+    if (a.strand) deacon::check(dcn_anchor_map_pileup_keep_strands(R.map.p, 1));     // (rule S1: likewise)
     if (a.markdup) deacon::check(dcn_anchor_map_duplicates_enable(R.map.p, 1));
     dcn_duplicate_params dprm = {};
     dprm.row_stride = sizeof(dcn_split_placement);
@@ -4121,6 +4127,7 @@ int run_map(const MapArgs &a) {
     uint64_t genotyped_positions = 0, vcf_sites = 0, het_sites = 0, hom_alt_sites = 0; // (genotype)
     uint64_t deletion_events = 0, deleted_bases = 0, indel_sites = 0, insertion_sites = 0, deletion_sites = 0, het_indel_sites = 0,
              hom_indel_sites = 0; // (indels)
+    uint64_t strand_bias_sites = 0, one_strand_sites = 0, filtered_sites = 0; // (strand)
     if (piles) {
         TextOut sites_out, pile_file, fasta_out, variants_out;
         std::unique_ptr<Output> vcf_out; // (.gz as BGZF, .zst and .xz by extension, as filter's outputs)
@@ -4129,7 +4136,12 @@ int run_map(const MapArgs &a) {
             vcf_out.reset(new Output(a.vcf, 2));
             std::string head = std::string("##fileformat=VCFv4.2\n##source=deacon-hip ") + VERSION + "\n";
             for (uint32_t r = 0; r < R.n_records; ++r) head += "##contig=<ID=" + R.names[r] + ",length=" + std::to_string(R.lens[r]) + ">\n";
+            if (a.strand)
+                head += "##FILTER=<ID=strand_bias,Description=\"SB at or above --max-sb: the allele and the strand are not independent\">\n"
+                        "##FILTER=<ID=one_strand,Description=\"Both strands cover the site, the allele is on fewer than --min-alt-strand reads of one\">\n";
             head += "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Depth: reads with a base, an N or a deletion at the position\">\n";
+            if (a.strand)
+                head += "##INFO=<ID=SB,Number=1,Type=Float,Description=\"Strand bias: chi-square of the 2 x 2 table of allele by strand, one degree of freedom\">\n";
             if (a.indels)
                 head += "##INFO=<ID=INDEL,Number=0,Type=Flag,Description=\"An insertion or a deletion\">\n"
                         "##INFO=<ID=IDV,Number=1,Type=Integer,Description=\"Reads that carry the allele\">\n"
@@ -4138,8 +4150,11 @@ int run_map(const MapArgs &a) {
             head += "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
                     "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: phred gap to the second best genotype, at most 99\">\n"
                     "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Bases A, C, G, T of at least the minimum base quality\">\n"
-                    "##FORMAT=<ID=AD,Number=R,Type=Integer,Description=\"Such bases per allele\">\n"
-                    "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods, at most 255\">\n"
+                    "##FORMAT=<ID=AD,Number=R,Type=Integer,Description=\"Such bases per allele\">\n";
+            if (a.strand)
+                head += "##FORMAT=<ID=ADF,Number=R,Type=Integer,Description=\"AD on the forward strand\">\n"
+                        "##FORMAT=<ID=ADR,Number=R,Type=Integer,Description=\"AD on the reverse strand\">\n";
+            head += "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods, at most 255\">\n"
                     "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + a.sample + "\n";
             vcf_write(head);
         }
@@ -4163,6 +4178,23 @@ int run_map(const MapArgs &a) {
         iprm.het_centi = 301;
         std::vector<dcn_indel_site> ind_sites;
         std::vector<uint8_t> ind_bases, ref_more;
+        dcn_strand_params sprm = {}; // (`strand`)
+        sprm.max_sb_centi = a.max_sb;
+        sprm.min_alt_strand = a.min_alt_strand;
+        sprm.min_strand_depth = a.min_strand_depth;
+        std::vector<dcn_strand_query> strand_queries;
+        std::vector<dcn_strand_site> snv_strand, ind_strand;
+        std::vector<uint32_t> ind_reverse, planes;
+        // the FILTER column and SB of a site, and its place in the summary
+        const auto strand_filter = [&](const dcn_strand_site &e) {
+            strand_bias_sites += (e.flags & DCN_STRAND_BIAS) != 0, one_strand_sites += (e.flags & DCN_STRAND_ONE_SIDED) != 0, filtered_sites += e.flags != 0;
+            return std::string(e.flags == 0 ? "PASS" : e.flags == DCN_STRAND_BIAS ? "strand_bias" : e.flags == DCN_STRAND_ONE_SIDED ? "one_strand" : "strand_bias;one_strand");
+        };
+        const auto strand_sb = [](const dcn_strand_site &e) {
+            char text[32];
+            std::snprintf(text, sizeof text, "%u.%02u", e.sb_centi / 100u, e.sb_centi % 100u);
+            return std::string(text);
+        };
         std::vector<std::pair<uint64_t, size_t>> snv_at; // per SNV line of the stretch: its POS and where it begins in vcf_rows
         std::string merged_rows;
         if (a.indels) deacon::check(dcn_anchor_map_deletions_info(R.map.p, &deletion_events, &deleted_bases));
@@ -4177,7 +4209,10 @@ int run_map(const MapArgs &a) {
         std::string seq, variant_rows;
         if (a.extend && a.has_pileup_out) pile_file.open(a.pileup_out, false);
         TextOut *const tsv = a.pileup ? &out : a.has_pileup_out ? &pile_file : nullptr; // (`extend --sites` alone: no table)
-        if (tsv) tsv->write(a.call ? "record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\tqA\tqC\tqG\tqT\n" : "record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\n");
+        if (tsv)
+            tsv->write(a.strand ? "record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\tqA\tqC\tqG\tqT\trA\trC\trG\trT\n"
+                       : a.call ? "record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\tqA\tqC\tqG\tqT\n"
+                                : "record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\n");
         if (a.has_sites) sites_out.write("record\tpos\tref\tcall\tdepth\tflags\n");
         dcn_pileup_call_params cprm = {};
         cprm.min_depth = a.min_depth;
@@ -4207,6 +4242,10 @@ int run_map(const MapArgs &a) {
                     deacon::check(dcn_anchor_map_pileup_fetch_qualities(R.map.p, r, start, n, qsums.data()));
                     for (uint64_t q = 0; q < n * 4; ++q) qual_sum[q & 3] += qsums[q];
                 }
+                if (a.strand && tsv) {
+                    planes.resize(n * 4);
+                    deacon::check(dcn_anchor_map_pileup_fetch_strands(R.map.p, r, start, n, planes.data()));
+                }
                 deacon::check(dcn_anchor_map_fetch(R.map.p, r, start, n, ref_text.data()));
                 rows.clear();
                 for (uint64_t q = 0; q < n; ++q) {
@@ -4220,6 +4259,8 @@ int run_map(const MapArgs &a) {
                     for (int col = 0; col < DCN_PILEUP_COLUMNS; ++col) rows += '\t' + std::to_string(c[col]);
                     if (a.call)
                         for (int col = 0; col < 4; ++col) rows += '\t' + std::to_string(qsums[q * 4 + col]);
+                    if (a.strand && tsv)
+                        for (int col = 0; col < 4; ++col) rows += '\t' + std::to_string(planes[q * 4 + col]);
                     rows += '\n';
                 }
                 if (tsv) tsv->write(rows);
@@ -4304,6 +4345,21 @@ int run_map(const MapArgs &a) {
                     vcf_sites += n_geno;
                     vcf_rows.clear();
                     snv_at.clear();
+                    if (a.strand) { // rules S3, S5 and S6 at the stretch's sites: ALT = the genotype's alleles other than the record's base
+                        strand_queries.assign(n_geno, dcn_strand_query{});
+                        snv_strand.resize(n_geno);
+                        for (uint64_t i = 0; i < n_geno; ++i) {
+                            const dcn_genotype_site &g = geno_sites[i];
+                            unsigned x = g.gt, y = g.gt;
+                            if (a.ploidy == 2)
+                                for (y = 0; (y + 1) * (y + 2) / 2 <= g.gt; ++y) {}
+                            if (a.ploidy == 2) x = g.gt - y * (y + 1) / 2;
+                            strand_queries[i].pos = g.pos;
+                            strand_queries[i].ref_code = g.ref_code;
+                            strand_queries[i].alt_mask = ((1u << x) | (1u << y)) & ~(1u << g.ref_code);
+                        }
+                        deacon::check(dcn_anchor_map_strand_evidence(R.map.p, &sprm, r, strand_queries.data(), n_geno, snv_strand.data()));
+                    }
                     for (uint64_t i = 0; i < n_geno; ++i) {
                         const dcn_genotype_site &g = geno_sites[i];
                         if (a.indels) snv_at.emplace_back(g.pos + 1, vcf_rows.size());
@@ -4320,12 +4376,22 @@ int run_map(const MapArgs &a) {
                         const auto pair_index = [](unsigned p, unsigned q2) { return p <= q2 ? q2 * (q2 + 1) / 2 + p : p * (p + 1) / 2 + q2; };
                         vcf_rows += R.names[r] + '\t' + std::to_string(g.pos + 1) + "\t.\t" + "ACGT"[g.ref_code] + '\t';
                         for (unsigned k = 1; k < n_alleles; ++k) vcf_rows += std::string(k > 1 ? "," : "") + "ACGT"[alleles[k]];
-                        vcf_rows += '\t' + std::to_string(g.qual) + "\tPASS\tDP=" + std::to_string(g.depth) + "\tGT:GQ:DP:AD:PL\t";
+                        if (a.strand)
+                            vcf_rows += '\t' + std::to_string(g.qual) + '\t' + strand_filter(snv_strand[i]) + "\tDP=" + std::to_string(g.depth) +
+                                        ";SB=" + strand_sb(snv_strand[i]) + "\tGT:GQ:DP:AD:ADF:ADR:PL\t";
+                        else
+                            vcf_rows += '\t' + std::to_string(g.qual) + "\tPASS\tDP=" + std::to_string(g.depth) + "\tGT:GQ:DP:AD:PL\t";
                         if (a.ploidy == 2) vcf_rows += std::to_string(std::min(index_of(x), index_of(y))) + '/' + std::to_string(std::max(index_of(x), index_of(y)));
                         else vcf_rows += std::to_string(index_of(x));
                         vcf_rows += ':' + std::to_string(g.gq) + ':' + std::to_string((uint64_t)g.ad[0] + g.ad[1] + g.ad[2] + g.ad[3]) + ':';
                         for (unsigned k = 0; k < n_alleles; ++k) vcf_rows += (k ? "," : "") + std::to_string(g.ad[alleles[k]]);
                         vcf_rows += ':';
+                        if (a.strand) { // over the same alleles as AD
+                            for (unsigned k = 0; k < n_alleles; ++k) vcf_rows += (k ? "," : "") + std::to_string(snv_strand[i].fwd[alleles[k]]);
+                            vcf_rows += ':';
+                            for (unsigned k = 0; k < n_alleles; ++k) vcf_rows += (k ? "," : "") + std::to_string(snv_strand[i].rev[alleles[k]]);
+                            vcf_rows += ':';
+                        }
                         bool first = true;
                         for (unsigned j = 0; j < n_alleles; ++j)
                             for (unsigned i2 = 0; i2 <= (a.ploidy == 2 ? j : 0u); ++i2) {
@@ -4348,6 +4414,19 @@ int run_map(const MapArgs &a) {
                             ind_bases.resize(n_ind_bases);
                         }
                         indel_sites += n_ind;
+                        if (a.strand) { // rule S4: the winners' reverse events from the ledgers, then the table, the score and the flags
+                            ind_reverse.resize(n_ind);
+                            ind_strand.resize(n_ind);
+                            strand_queries.assign(n_ind, dcn_strand_query{});
+                            deacon::check(dcn_anchor_map_indels_strand(R.map.p, r, ind_sites.data(), n_ind, ind_bases.data(), ind_reverse.data()));
+                            for (uint64_t i = 0; i < n_ind; ++i) {
+                                strand_queries[i].pos = ind_sites[i].pos;
+                                strand_queries[i].kind = 1;
+                                strand_queries[i].count = ind_sites[i].count;
+                                strand_queries[i].count_reverse = ind_reverse[i];
+                            }
+                            deacon::check(dcn_anchor_map_strand_evidence(R.map.p, &sprm, r, strand_queries.data(), n_ind, ind_strand.data()));
+                        }
                         // bases [from, from + count) of the record: the stretch's own, or fetched where a line reaches beyond it
                         const auto ref_bases = [&](uint64_t from, uint64_t count) {
                             if (from >= start && from + count <= start + n) return std::string((const char *)ref_text.data() + (from - start), count);
@@ -4387,11 +4466,17 @@ int run_map(const MapArgs &a) {
                             (hom ? hom_indel_sites : het_indel_sites) += 1;
                             const uint32_t others = s.depth >= s.count ? s.depth - s.count : 0;
                             snvs_up_to(pos1);
-                            merged_rows += R.names[r] + '\t' + std::to_string(pos1) + "\t.\t" + ref_allele + '\t' + alt + '\t' + std::to_string(s.qual) +
-                                           "\tPASS\tINDEL;DP=" + std::to_string(s.depth) + ";IDV=" + std::to_string(s.count) + ";IEV=" + std::to_string(s.events) +
-                                           "\tGT:GQ:DP:AD:PL\t" + (a.ploidy == 1 ? "1" : hom ? "1/1" : "0/1") + ':' + std::to_string(s.gq) + ':' +
-                                           std::to_string((uint64_t)others + s.count) + ':' + std::to_string(others) + ',' + std::to_string(s.count) + ':' +
-                                           std::to_string(s.pl[0]) + ',' + std::to_string(s.pl[1]);
+                            merged_rows += R.names[r] + '\t' + std::to_string(pos1) + "\t.\t" + ref_allele + '\t' + alt + '\t' + std::to_string(s.qual) + '\t' +
+                                           (a.strand ? strand_filter(ind_strand[i]) : std::string("PASS")) + "\tINDEL;DP=" + std::to_string(s.depth) +
+                                           ";IDV=" + std::to_string(s.count) + ";IEV=" + std::to_string(s.events) +
+                                           (a.strand ? ";SB=" + strand_sb(ind_strand[i]) + "\tGT:GQ:DP:AD:ADF:ADR:PL\t" : std::string("\tGT:GQ:DP:AD:PL\t")) +
+                                           (a.ploidy == 1 ? "1" : hom ? "1/1" : "0/1") + ':' + std::to_string(s.gq) + ':' +
+                                           std::to_string((uint64_t)others + s.count) + ':' + std::to_string(others) + ',' + std::to_string(s.count) + ':';
+                            if (a.strand) { // o,a split by strand: rule S4's table, a,c forward and b,d reverse
+                                const uint32_t *const t = ind_strand[i].table;
+                                merged_rows += std::to_string(t[0]) + ',' + std::to_string(t[2]) + ':' + std::to_string(t[1]) + ',' + std::to_string(t[3]) + ':';
+                            }
+                            merged_rows += std::to_string(s.pl[0]) + ',' + std::to_string(s.pl[1]);
                             if (a.ploidy == 2) merged_rows += ',' + std::to_string(s.pl[2]);
                             merged_rows += '\n';
                         }
@@ -4450,6 +4535,9 @@ int run_map(const MapArgs &a) {
             std::fprintf(stderr, "Left-aligned %llu gaps over %llu columns in %llu of %llu placements (%llu gaps merged)\n",
                          (unsigned long long)left.gaps_shifted, (unsigned long long)left.columns_passed, (unsigned long long)left.rows_changed,
                          (unsigned long long)left.rows_aligned, (unsigned long long)left.gaps_merged);
+        if (a.strand)
+            std::fprintf(stderr, "Filtered %llu VCF lines by strand (%llu strand_bias, %llu one_strand)\n", (unsigned long long)filtered_sites,
+                         (unsigned long long)strand_bias_sites, (unsigned long long)one_strand_sites);
         if (a.verify && !a.pileup)
             std::fprintf(stderr, "Verified %llu of %llu placements (%llu edits over %llu bases)\n", (unsigned long long)verified,
                          (unsigned long long)placements, (unsigned long long)edits_sum, (unsigned long long)verified_bases);
@@ -4529,6 +4617,11 @@ int run_map(const MapArgs &a) {
                         "  \"left_align_merged_gaps\": %llu,\n",
                     (unsigned long long)left.rows_changed, (unsigned long long)left.gaps_shifted, (unsigned long long)left.columns_passed,
                     (unsigned long long)left.gaps_merged);
+        if (a.strand)
+            appendf(js, "  \"max_sb\": %u,\n  \"min_alt_strand\": %u,\n  \"min_strand_depth\": %u,\n  \"strand_bias_sites\": %llu,\n"
+                        "  \"one_strand_sites\": %llu,\n  \"filtered_sites\": %llu,\n",
+                    a.max_sb, a.min_alt_strand, a.min_strand_depth, (unsigned long long)strand_bias_sites, (unsigned long long)one_strand_sites,
+                    (unsigned long long)filtered_sites);
         appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
         for (uint32_t r = 0; r < R.n_records; ++r) {
             js += (r ? ",\n    {" : "\n    {");
@@ -4684,6 +4777,7 @@ void usage() {
                  "  markdup  As genotype, with reads that repeat the unclipped end of an earlier read marked and left out first\n"
                  "  indels  As markdup, with a genotype per insertion and deletion from the two ledgers: INDEL lines in the VCF\n"
                  "  normalize  As indels, with every read's gaps left-aligned first: an indel in a repeat stands at its near end\n"
+                 "  strand  As normalize, with per-allele strand counts: FILTER strand_bias / one_strand, SB, ADF and ADR in the VCF\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -5319,7 +5413,7 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "optical-distance rule; nothing is read from the bases or the qualities.  Mates are independent here: one input,\n"
                "and a read is a unit.  Pairs as units (one key from both mates' ends) are a feature of the library\n"
                "(dcn_mark_duplicates_batch) and of the Python layer (AnchorMap.mark_duplicates), not of this mode.\n";
-    else if (sub == "indels" || sub == "normalize") // (normalize: indels' text with another head and a paragraph more, below)
+    else if (sub == "indels" || sub == "normalize" || sub == "strand") // (normalize: indels' text with another head and a paragraph more, below; strand: normalize's likewise)
         text = "Mark duplicates, pile up and genotype as markdup does, keep the deleted runs beside the inserted bases, and give the\n"
                "insertion and the deletion most reads carry at a position a genotype of their own: INDEL lines in the VCF\n\n"
                "Usage: deacon-hip indels [OPTIONS] <REF> [READS]\n\n"
@@ -5559,12 +5653,26 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "  compare    Report how many minimizers 2 to 32 indexes share, pair by pair\n"
                "  select     Keep the minimizers of several indexes chosen by which of the indexes hold them\n";
     if (!text) return false;
-    if (sub == "normalize") { // every option of indels keeps its text
+    if (sub == "normalize" || sub == "strand") { // every option of indels keeps its text
+        const bool strand = sub == "strand";
         std::string t = text;
         t.erase(0, t.find("Usage: deacon-hip indels"));
-        t.replace(0, std::strlen("Usage: deacon-hip indels"), "Usage: deacon-hip normalize");
-        t = "Mark duplicates, pile up and genotype as indels does, with the gaps of every read's alignment moved to the near end\n"
-            "of their repeat first: the INDEL lines of the VCF stand where other callers and truth sets put them\n\n" + t +
+        t.replace(0, std::strlen("Usage: deacon-hip indels"), strand ? "Usage: deacon-hip strand" : "Usage: deacon-hip normalize");
+        if (strand) { // the three options of the mode, behind indels' own two
+            const std::string at = "      --min-indel-count <N>";
+            const size_t line_end = t.find('\n', t.find(at));
+            t.insert(line_end + 1,
+                     "      --max-sb <N>               A VCF line whose SB, in hundredths, is at least N gets FILTER strand_bias; 0 switches\n"
+                     "                                 the flag off (0..65535) [default: 1083, a convention: chi-square 10.83, p = 0.001]\n"
+                     "      --min-alt-strand <N>       A line whose allele is on fewer than N reads of one strand, while both strands cover\n"
+                     "                                 the site, gets FILTER one_strand [default: 1, a convention]\n"
+                     "      --min-strand-depth <N>     Reads a strand needs at the site to count as covering it [default: 3, a convention]\n");
+        }
+        t = std::string(strand ? "Mark duplicates, left-align, pile up and genotype as normalize does, with the reverse reads counted per allele as\n"
+                                 "well: every VCF line says on which strands its alleles were seen, and whether that looks like an artefact\n\n"
+                               : "Mark duplicates, pile up and genotype as indels does, with the gaps of every read's alignment moved to the near end\n"
+                                 "of their repeat first: the INDEL lines of the VCF stand where other callers and truth sets put them\n\n") +
+            t +
             "Left alignment: whatever the last sentences above say, in this mode a gap that lies in a homopolymer or a tandem\n"
             "repeat is moved, read by read and before anything is counted, as far towards the start of the record as it can go\n"
             "without changing the read's edit distance: a deleted stretch moves one base while the base in front of it equals\n"
@@ -5579,6 +5687,21 @@ bool subcommand_help(const std::vector<std::string> &args) {
             "the base in front.  Not normalised against the reference beyond a read's own extent; no multi-allelic lines.  On\n"
             "input without a gap in a repeat the outputs are indels', byte for byte, apart from that header line and the\n"
             "four fields.\n";
+        if (strand)
+            t += "\nStrand evidence: the pileup keeps four more counters per position, the bases A C G T seen on reverse reads (a base\n"
+                 "that counts as N adds to none of them); --pileup gains the columns rA rC rG rT, and the forward count of a base is\n"
+                 "its column less these.  For every VCF line a 2 x 2 table is made: the reference allele forward and reverse, the\n"
+                 "line's ALT alleles forward and reverse; on an INDEL line the second row is the winning allele's events of each\n"
+                 "strand, from the two ledgers, and the first every other read at the position.  SB is 100 N (ad - bc)^2 /\n"
+                 "(r1 r2 c1 c2) in integers, printed as d.dd and capped at 655.35; tables with a cell of 1024 or more are halved until\n"
+                 "none has.  FILTER is PASS, strand_bias (SB at least --max-sb), one_strand (the allele on fewer than\n"
+                 "--min-alt-strand reads of a strand that, like the other, has --min-strand-depth reads at the site) or\n"
+                 "strand_bias;one_strand.  Filtered lines are written, not dropped.  INFO gains SB=; FORMAT gains ADF:ADR behind AD,\n"
+                 "over AD's alleles, so that ADF + ADR = AD field by field (on INDEL lines o,a by strand).  The header gains two\n"
+                 "##FILTER lines, ##INFO SB and ##FORMAT ADF and ADR.  -s gains max_sb, min_alt_strand, min_strand_depth,\n"
+                 "strand_bias_sites, one_strand_sites and filtered_sites.  A homozygous ALT line has no reference reads and scores 0.\n"
+                 "No Yates correction, no exact test, no mapping quality terms, no priors, no phasing.  With FILTER put back to PASS\n"
+                 "and SB, ADF, ADR, the five header lines and the four columns removed, the outputs are normalize's, byte for byte.\n";
         std::fputs(t.c_str(), stdout);
         return true;
     }
@@ -5752,11 +5875,12 @@ int main(int argc, char **argv) {
             return run_place(a);
         }
         if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup" || args[0] == "extend" || args[0] == "consensus" ||
-            args[0] == "call" || args[0] == "genotype" || args[0] == "markdup" || args[0] == "indels" || args[0] == "normalize") {
+            args[0] == "call" || args[0] == "genotype" || args[0] == "markdup" || args[0] == "indels" || args[0] == "normalize" || args[0] == "strand") {
             MapArgs a;
             a.align = args[0] == "align";
             a.pileup = args[0] == "pileup";
-            a.normalize = args[0] == "normalize";
+            a.strand = args[0] == "strand";
+            a.normalize = args[0] == "normalize" || a.strand;
             a.indels = args[0] == "indels" || a.normalize;
             a.markdup = args[0] == "markdup" || a.indels;
             a.genotype = args[0] == "genotype" || a.markdup;
@@ -5792,6 +5916,9 @@ int main(int argc, char **argv) {
                 else if (a.markdup && s == "--duplicates") a.duplicates = need(++i), a.has_duplicates = true;
                 else if (a.indels && s == "--indel-qual") a.indel_qual = (unsigned)number(need(++i), "--indel-qual", 0, 1000);
                 else if (a.indels && s == "--min-indel-count") a.min_indel_count = (unsigned)number(need(++i), "--min-indel-count", 0, 0xFFFFFFFFll);
+                else if (a.strand && s == "--max-sb") a.max_sb = (unsigned)number(need(++i), "--max-sb", 0, 65535);
+                else if (a.strand && s == "--min-alt-strand") a.min_alt_strand = (unsigned)number(need(++i), "--min-alt-strand", 0, 0xFFFFFFFFll);
+                else if (a.strand && s == "--min-strand-depth") a.min_strand_depth = (unsigned)number(need(++i), "--min-strand-depth", 0, 0xFFFFFFFFll);
                 else if (s == "-o" || s == "--output") a.output = need(++i), a.has_output = true;
                 else if (a.extend && s == "--penalty") a.penalty = (unsigned)number(need(++i), "--penalty", 2, 255);
                 else if (a.extend && s == "--end-bonus") a.end_bonus = (unsigned)number(need(++i), "--end-bonus", 0, 65535);

@@ -447,6 +447,7 @@ extern "C" int dcn_index_clone(const dcn_index *index, int device, dcn_index **o
     idx->ledger = nullptr; // ... nor an insertion ledger
     idx->del_ledger = nullptr; // ... nor a deletion ledger
     idx->d_pileup_qsums = nullptr; // ... nor quality sums
+    idx->d_pileup_strands = nullptr; // ... nor strand planes
     idx->dups = nullptr; // ... nor a duplicate set
     const uint64_t bytes = idx->n_groups * DCN_GROUP_SLOTS * sizeof(uint64_t);
     // Another GPU: the keys cross the link, not the table (a tenth of the bytes at the default 8 slots per key; dcn_table_clone_by_keys).
@@ -505,6 +506,7 @@ extern "C" void dcn_index_destroy(dcn_index *index) {
     dcn_ins_ledger_free(index->ledger);
     dcn_del_ledger_free(index->del_ledger);
     if (index->d_pileup_qsums) hipFree(index->d_pileup_qsums);
+    if (index->d_pileup_strands) hipFree(index->d_pileup_strands);
     dcn_dup_set_free(index->dups);
     delete index;
 }

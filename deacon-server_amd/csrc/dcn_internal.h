@@ -137,6 +137,9 @@ struct dcn_index {
     // ... and the quality sums beside the counters (dcn_anchor_map_pileup_keep_qualities, pileup_api.hip): 4 words per base
     // of the pileup, laid out by dcn_pile_sum_index (dcn_pileup.h).  Null: none are kept.
     uint32_t *d_pileup_qsums = nullptr;
+    // ... and the strand planes (dcn_anchor_map_pileup_keep_strands, pileup_api.hip): 4 words per base of the pileup, laid
+    // out by dcn_pile_strand_index (dcn_pileup.h).  Null: none are kept.
+    uint32_t *d_pileup_strands = nullptr;
     // ... and the duplicate set (dcn_anchor_map_duplicates_enable, duplicates_api.hip), which needs neither the bases nor
     // the pileup.  Null: none is kept.
     dcn_dup_set *dups = nullptr;

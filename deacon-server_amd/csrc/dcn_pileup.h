@@ -38,20 +38,42 @@ DCN_PILE_FN uint32_t dcn_pile_step_t(uint32_t run) { return (run & 15u) == DCN_A
 // the column of a base of S: the pack kernel's codes are A C T G, the columns A C G T; an invalid base counts as N
 DCN_PILE_FN uint32_t dcn_pile_column(uint32_t code, uint32_t invalid) { return invalid ? DCN_PILE_N : (code ^ (code >> 1)) & 3u; }
 
+// rule S2 (THE DEFINITION OF STRAND EVIDENCE): a map that keeps no strand planes adds nothing
+struct dcn_pile_no_strand {
+    DCN_PILE_FN void operator()(uint32_t, uint32_t) const {}
+};
+
+// Where reverse counter (column, base) lies among the 4 * bases words of a map's strand planes RA RC RG RT: four planes, as
+// the counters'; four words per position under -DDCN_PILEUP_POSITION_MAJOR.
+constexpr uint32_t DCN_PILE_STRAND_COLUMNS = 4;
+DCN_PILE_FN uint64_t dcn_pile_strand_index(uint32_t column, uint64_t base, uint64_t bases) {
+#if defined(DCN_PILEUP_POSITION_MAJOR)
+    (void)bases;
+    return base * DCN_PILE_STRAND_COLUMNS + column;
+#else
+    return (uint64_t)column * bases + base;
+#endif
+}
+
 // Rule P3 for one run that starts at (i, j), as lane `lane` of `lanes` sees it: the lanes stride over the run's bases.
 // column_of(i) is the column of S[i]; add(column, j) adds 1 at base j of T.  An I run is one add, by lane 0, at the base of
-// T in front of it (at base 0 when there is none: the caller has n > 0).
-template <typename ColumnOf, typename Add>
+// T in front of it (at base 0 when there is none: the caller has n > 0).  add_strand(column, j) is rule S2's add: called on
+// a reverse row alone, for an '=' or X step counted in A, C, G or T.
+template <typename ColumnOf, typename Add, typename AddStrand = dcn_pile_no_strand>
 DCN_PILE_FN void dcn_pile_run(uint32_t run, uint32_t i, uint32_t j, uint32_t reverse, uint32_t lane, uint32_t lanes, ColumnOf column_of,
-                              Add add) {
+                              Add add, AddStrand add_strand = AddStrand()) {
     const uint32_t op = run & 15u, len = run >> 4;
     if (op == DCN_ALN_I) {
         if (lane == 0) add(DCN_PILE_INS, j > 0 ? j - 1 : 0u);
         return;
     }
     for (uint32_t q = lane; q < len; q += lanes) {
-        add(op == DCN_ALN_D ? DCN_PILE_DEL : column_of(i + q), j + q);
-        if (reverse) add(DCN_PILE_REV, j + q);
+        const uint32_t column = op == DCN_ALN_D ? DCN_PILE_DEL : column_of(i + q);
+        add(column, j + q);
+        if (reverse) {
+            add(DCN_PILE_REV, j + q);
+            if (column <= DCN_PILE_T) add_strand(column, j + q);
+        }
     }
 }
 
@@ -85,24 +107,29 @@ DCN_PILE_FN uint64_t dcn_pile_sum_index(uint32_t column, uint64_t base, uint64_t
 
 // Rules Q3 and Q4 for one run: dcn_pile_run with the quality of every '=' / X base looked at.  quality_of(i) is q(S[i]);
 // add_sum(column, j, q) adds q to the sum of a base column at base j of T.  I and D runs are dcn_pile_run's.
-template <typename ColumnOf, typename QualityOf, typename Add, typename AddSum>
+// add_strand is dcn_pile_run's, with the column of rule Q3.
+template <typename ColumnOf, typename QualityOf, typename Add, typename AddSum, typename AddStrand = dcn_pile_no_strand>
 DCN_PILE_FN void dcn_pile_run_qual(uint32_t run, uint32_t i, uint32_t j, uint32_t reverse, uint32_t min_base_qual, uint32_t lane, uint32_t lanes,
-                                   ColumnOf column_of, QualityOf quality_of, Add add, AddSum add_sum) {
+                                   ColumnOf column_of, QualityOf quality_of, Add add, AddSum add_sum, AddStrand add_strand = AddStrand()) {
     const uint32_t op = run & 15u, len = run >> 4;
     if (op == DCN_ALN_I) {
         if (lane == 0) add(DCN_PILE_INS, j > 0 ? j - 1 : 0u);
         return;
     }
     for (uint32_t q = lane; q < len; q += lanes) {
+        uint32_t column = DCN_PILE_DEL;
         if (op == DCN_ALN_D) {
             add(DCN_PILE_DEL, j + q);
         } else {
             const uint32_t quality = quality_of(i + q);
-            const uint32_t column = dcn_pile_qual_column(column_of(i + q), quality, min_base_qual);
+            column = dcn_pile_qual_column(column_of(i + q), quality, min_base_qual);
             add(column, j + q);
             if (column <= DCN_PILE_T) add_sum(column, j + q, quality);
         }
-        if (reverse) add(DCN_PILE_REV, j + q);
+        if (reverse) {
+            add(DCN_PILE_REV, j + q);
+            if (column <= DCN_PILE_T) add_strand(column, j + q);
+        }
     }
 }
 

@@ -244,6 +244,16 @@ struct dcn_pileup_qual_args {
 };
 int dcn_launch_pileup_qual(const dcn_pileup_qual_args &args, hipStream_t stream);
 
+// either walk on a map that keeps strand planes (rule S2): the planes ride behind the arguments of the kernel it was, so
+// that the kernels of a map without planes take the arguments they took
+template <typename Rows>
+struct dcn_pileup_strand_args {
+    Rows rows;
+    uint32_t *strands; // the map's strand planes: dcn_pile_strand_index(column, store base, bases)
+};
+int dcn_launch_pileup_strand(const dcn_pileup_args &args, uint32_t *strands, hipStream_t stream);
+int dcn_launch_pileup_qual_strand(const dcn_pileup_qual_args &args, uint32_t *strands, hipStream_t stream);
+
 struct dcn_pileup_call_args {
     const uint32_t *counters;
     uint64_t bases;
@@ -267,6 +277,8 @@ namespace dcn_pile_api {
 int check_pileup(const dcn_index *map);
 // ... and keeps quality sums
 int check_qsums(const dcn_index *map);
+// ... or keeps strand planes
+int check_strands(const dcn_index *map);
 // (their scratch holder, dcn_pile_api::scratch, is in dcn_ctx.h, where dev_alloc is)
 } // namespace dcn_pile_api
 #pragma GCC visibility pop
@@ -508,3 +520,42 @@ uint32_t dcn_indel_site_blocks(uint64_t n); // workgroups of a range of n positi
 int dcn_launch_indel_flags(const uint32_t *counts, uint32_t *flags, uint64_t n, hipStream_t stream);
 int dcn_launch_indel_sites(const dcn_indel_site_args &args, bool write, hipStream_t stream);
 int dcn_launch_indel_bases(const dcn_indel_site_args &args, hipStream_t stream);
+
+// ---- strand evidence (strand.hip, strand_api.hip; the shared arithmetic is in dcn_strand.h) ---------------------------
+// one checked query as the kernel takes it: the store base of its position behind the fields of a dcn_strand_query
+struct dcn_strand_query_item {
+    uint64_t base;
+    uint32_t kind, ref_code, alt_mask, count, count_reverse, reserved;
+};
+static_assert(sizeof(dcn_strand_query_item) == 32, "strand query item");
+struct dcn_strand_site_item { // a dcn_strand_site
+    uint32_t fwd[4], rev[4], table[4], sb_centi, flags, reserved[2];
+};
+static_assert(sizeof(dcn_strand_site_item) == 64, "strand site item");
+struct dcn_strand_evidence_args {
+    const uint32_t *counters, *strands; // the map's pileup and its strand planes
+    uint64_t bases;
+    const dcn_strand_query_item *queries;
+    uint64_t n;
+    uint32_t max_sb_centi, min_alt_strand, min_strand_depth;
+    dcn_strand_site_item *out;
+};
+int dcn_launch_strand_evidence(const dcn_strand_evidence_args &args, hipStream_t stream);
+
+// The key of an indel site and of a ledger event: the store base of its position, then I6's order at one position (0 a
+// front insertion, 1 the deletion, 2 an insertion behind).  Ascending keys are I6's order.
+__host__ __device__ inline uint64_t dcn_indel_strand_key(uint64_t base, uint32_t order) { return base * 4u + order; }
+struct dcn_indel_strand_args {
+    const uint64_t *site_keys;         // ascending, n_sites of them
+    const uint32_t *site_len;          // the allele's length
+    const uint64_t *site_bases_offset; // an insertion site's bases in site_bases
+    const uint8_t *site_bases;
+    uint64_t n_sites;
+    const dcn_ins_event *ins_events;   // the ledgers; n_*_events = 0: no site of that kind
+    const uint8_t *ins_ledger_bases;
+    uint64_t n_ins_events;
+    const dcn_del_event *del_events;
+    uint64_t n_del_events;
+    uint32_t *count_reverse;           // per site, zero before
+};
+int dcn_launch_indel_strand(const dcn_indel_strand_args &args, hipStream_t stream);

@@ -8,6 +8,10 @@
 //                        the lanes of a run read consecutive bytes, ascending on a forward row and descending on a reverse
 //                        one.  A base column under the threshold becomes N (rule Q3), and on a map that keeps sums a second
 //                        atomicAdd adds the quality to the column's sum (rule Q4).  <false> is the kernel it was.
+//                        <., true> (a map that keeps strand planes, rule S2) takes the planes behind the other arguments:
+//                        on a reverse row a base counted in A, C, G or T adds 1 to the plane of its column as well, the
+//                        lanes again to consecutive words.  `reverse` is the wave's, so a forward row branches round the
+//                        add as it does round REV's: no memory operation more.  <., false> are the kernels they were.
 //   pileup_call_kernel   one thread per position of a range: rule P6.  <false> writes the call characters and the
 //                        workgroup's number of sites; <true>, behind the scan of those numbers, writes the sites compactly
 //                        in ascending position.  Both passes decide in the same code.
@@ -28,7 +32,18 @@ __device__ inline const dcn_pileup_args &rows_of(const dcn_pileup_args &a) { ret
 __device__ inline const dcn_pileup_args &rows_of(const dcn_pileup_qual_args &a) { return a.rows; }
 
 template <bool QUAL>
-__global__ __launch_bounds__(PILE_THREADS) void pileup_kernel(std::conditional_t<QUAL, dcn_pileup_qual_args, dcn_pileup_args> args) {
+using pile_rows_t = std::conditional_t<QUAL, dcn_pileup_qual_args, dcn_pileup_args>;
+template <bool QUAL, bool STRAND>
+using pile_args_t = std::conditional_t<STRAND, dcn_pileup_strand_args<pile_rows_t<QUAL>>, pile_rows_t<QUAL>>;
+
+template <bool QUAL>
+__device__ inline const pile_rows_t<QUAL> &call_of(const pile_rows_t<QUAL> &a) { return a; }
+template <bool QUAL>
+__device__ inline const pile_rows_t<QUAL> &call_of(const dcn_pileup_strand_args<pile_rows_t<QUAL>> &a) { return a.rows; }
+
+template <bool QUAL, bool STRAND>
+__global__ __launch_bounds__(PILE_THREADS) void pileup_kernel(pile_args_t<QUAL, STRAND> all) {
+    const pile_rows_t<QUAL> &args = call_of<QUAL>(all);
     const dcn_pileup_args &a = rows_of(args);
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t waves = (uint64_t)gridDim.x * (PILE_THREADS / 64);
@@ -65,6 +80,11 @@ __global__ __launch_bounds__(PILE_THREADS) void pileup_kernel(std::conditional_t
                 if (args.sums && j < n) atomicAdd(args.sums + dcn_pile_sum_index(column, t0 + j, bases), q);
             }
         };
+        const auto add_strand = [&](uint32_t column, uint32_t j) { // rule S2 (the runs call it on a reverse row alone)
+            if constexpr (STRAND) {
+                if (j < n) atomicAdd(all.strands + dcn_pile_strand_index(column, t0 + j, bases), 1u);
+            }
+        };
         uint32_t i0 = 0, j0 = 0; // where the chunk begins
         for (uint32_t c0 = 0; c0 < count; c0 += 64) {
             const uint32_t here = min(64u, count - c0);
@@ -76,9 +96,14 @@ __global__ __launch_bounds__(PILE_THREADS) void pileup_kernel(std::conditional_t
             }
             const uint32_t my_i = i0 + si - dcn_pile_step_s(run), my_j = j0 + sj - dcn_pile_step_t(run);
             for (uint32_t r = 0; r < here; ++r) {
-                if constexpr (QUAL)
+                if constexpr (QUAL && STRAND)
+                    dcn_pile_run_qual(__shfl(run, r), __shfl(my_i, r), __shfl(my_j, r), reverse, args.min_base_qual, lane, 64u, column_of,
+                                      quality_of, add, add_sum, add_strand);
+                else if constexpr (QUAL)
                     dcn_pile_run_qual(__shfl(run, r), __shfl(my_i, r), __shfl(my_j, r), reverse, args.min_base_qual, lane, 64u, column_of,
                                       quality_of, add, add_sum);
+                else if constexpr (STRAND)
+                    dcn_pile_run(__shfl(run, r), __shfl(my_i, r), __shfl(my_j, r), reverse, lane, 64u, column_of, add, add_strand);
                 else
                     dcn_pile_run(__shfl(run, r), __shfl(my_i, r), __shfl(my_j, r), reverse, lane, 64u, column_of, add);
             }
@@ -119,7 +144,7 @@ __global__ __launch_bounds__(CALL_THREADS) void pileup_call_kernel(dcn_pileup_ca
     }
 }
 
-// the grid of both forms of pileup_kernel
+// the grid of every form of pileup_kernel
 uint32_t pileup_blocks(uint64_t n_work) {
     const uint64_t per_block = PILE_THREADS / 64;
     return (uint32_t)std::min<uint64_t>((n_work + per_block - 1) / per_block, (uint64_t)dcn_cu_count() * 32);
@@ -128,14 +153,30 @@ uint32_t pileup_blocks(uint64_t n_work) {
 
 int dcn_launch_pileup(const dcn_pileup_args &args, hipStream_t stream) {
     if (args.n_work == 0) return DCN_OK;
-    hipLaunchKernelGGL(pileup_kernel<false>, dim3(pileup_blocks(args.n_work)), dim3(PILE_THREADS), 0, stream, args);
+    hipLaunchKernelGGL((pileup_kernel<false, false>), dim3(pileup_blocks(args.n_work)), dim3(PILE_THREADS), 0, stream, args);
     DCN_HIP(hipGetLastError());
     return DCN_OK;
 }
 
 int dcn_launch_pileup_qual(const dcn_pileup_qual_args &args, hipStream_t stream) {
     if (args.rows.n_work == 0) return DCN_OK;
-    hipLaunchKernelGGL(pileup_kernel<true>, dim3(pileup_blocks(args.rows.n_work)), dim3(PILE_THREADS), 0, stream, args);
+    hipLaunchKernelGGL((pileup_kernel<true, false>), dim3(pileup_blocks(args.rows.n_work)), dim3(PILE_THREADS), 0, stream, args);
+    DCN_HIP(hipGetLastError());
+    return DCN_OK;
+}
+
+int dcn_launch_pileup_strand(const dcn_pileup_args &args, uint32_t *strands, hipStream_t stream) {
+    if (args.n_work == 0) return DCN_OK;
+    const dcn_pileup_strand_args<dcn_pileup_args> all = {args, strands};
+    hipLaunchKernelGGL((pileup_kernel<false, true>), dim3(pileup_blocks(args.n_work)), dim3(PILE_THREADS), 0, stream, all);
+    DCN_HIP(hipGetLastError());
+    return DCN_OK;
+}
+
+int dcn_launch_pileup_qual_strand(const dcn_pileup_qual_args &args, uint32_t *strands, hipStream_t stream) {
+    if (args.rows.n_work == 0) return DCN_OK;
+    const dcn_pileup_strand_args<dcn_pileup_qual_args> all = {args, strands};
+    hipLaunchKernelGGL((pileup_kernel<true, true>), dim3(pileup_blocks(args.rows.n_work)), dim3(PILE_THREADS), 0, stream, all);
     DCN_HIP(hipGetLastError());
     return DCN_OK;
 }

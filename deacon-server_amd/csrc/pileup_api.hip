@@ -1,5 +1,6 @@
 // pileup_api.hip -- the C ABI of pileups (dcn_anchor_map_pileup_enable / _reset / _fetch / _call, dcn_pileup_batch, and with
-// base qualities dcn_anchor_map_pileup_keep_qualities / _fetch_qualities, dcn_pileup_batch_qual;
+// base qualities dcn_anchor_map_pileup_keep_qualities / _fetch_qualities, dcn_pileup_batch_qual; the strand planes of rule S1,
+// dcn_anchor_map_pileup_keep_strands / _fetch_strands;
 // kernels in pileup.hip, the shared arithmetic in dcn_pileup.h; a kept insertion ledger, insertions_api.hip, and a kept
 // deletion ledger, indels_api.hip, are appended to, emptied and freed here).  dcn_pileup_batch is dcn_align_batch's sequence
 // (verify_api.hip's walk, align_api.hip's passes and gather) with the runs left on the device and the pileup kernel behind;
@@ -37,6 +38,12 @@ int dcn_pile_api::check_qsums(const dcn_index *map) {
     return DCN_OK;
 }
 
+int dcn_pile_api::check_strands(const dcn_index *map) {
+    DCN_TRY(check_pileup(map));
+    if (!map->d_pileup_strands) return dcn_fail(DCN_ERR_ARG, "the map keeps no strand planes (dcn_anchor_map_pileup_keep_strands)");
+    return DCN_OK;
+}
+
 using namespace dcn_pile_api;
 
 extern "C" int dcn_anchor_map_pileup_enable(dcn_index *map, int enable) {
@@ -48,9 +55,11 @@ extern "C" int dcn_anchor_map_pileup_enable(dcn_index *map, int enable) {
             dcn_ins_ledger_free(map->ledger);
             dcn_del_ledger_free(map->del_ledger);
             if (map->d_pileup_qsums) hipFree(map->d_pileup_qsums);
+            if (map->d_pileup_strands) hipFree(map->d_pileup_strands);
         }
         map->d_pileup = nullptr;
         map->d_pileup_qsums = nullptr;
+        map->d_pileup_strands = nullptr;
         map->pileup_bases = 0;
         map->pileup_rows = 0;
         map->ledger = nullptr;
@@ -73,6 +82,8 @@ extern "C" int dcn_anchor_map_pileup_reset(dcn_index *map) {
     DCN_HIP(hipSetDevice(map->device));
     DCN_HIP(hipMemset(map->d_pileup, 0, map->pileup_bases * DCN_PILE_COLUMNS * sizeof(uint32_t)));
     if (map->d_pileup_qsums) DCN_HIP(hipMemset(map->d_pileup_qsums, 0, map->pileup_bases * DCN_PILE_SUM_COLUMNS * sizeof(uint32_t)));
+    if (map->d_pileup_strands)
+        DCN_HIP(hipMemset(map->d_pileup_strands, 0, map->pileup_bases * DCN_PILE_STRAND_COLUMNS * sizeof(uint32_t)));
     DCN_HIP(hipDeviceSynchronize()); // (null-stream work must not be overtaken by a context's stream)
     map->pileup_rows = 0;
     if (map->ledger) map->ledger->n_events = map->ledger->n_bases = 0; // (the arrays stay: the next append begins at their start)
@@ -116,6 +127,24 @@ extern "C" int dcn_anchor_map_pileup_keep_qualities(dcn_index *map, int keep) {
     return dev_alloc_zeroed(&map->d_pileup_qsums, map->pileup_bases * DCN_PILE_SUM_COLUMNS, "pileup quality sums");
 }
 
+extern "C" int dcn_anchor_map_pileup_keep_strands(dcn_index *map, int keep) {
+    DCN_TRY(check_pileup(map));
+    if (!keep) {
+        if (map->d_pileup_strands) {
+            DCN_HIP(hipSetDevice(map->device));
+            hipFree(map->d_pileup_strands);
+        }
+        map->d_pileup_strands = nullptr;
+        return DCN_OK;
+    }
+    if (map->d_pileup_strands) return DCN_OK;
+    if (map->pileup_rows != 0) // rule S1
+        return dcn_fail(DCN_ERR_ARG, std::to_string(map->pileup_rows) + " rows have added to the pileup since it was enabled or reset: the strand "
+                                                                         "planes begin with the counters (dcn_anchor_map_pileup_reset first)");
+    DCN_HIP(hipSetDevice(map->device));
+    return dev_alloc_zeroed(&map->d_pileup_strands, map->pileup_bases * DCN_PILE_STRAND_COLUMNS, "pileup strand planes");
+}
+
 namespace {
 // What dcn_pileup_batch and dcn_pileup_batch_qual run behind their checks.  qprm = null: the plain call.
 int pileup_run(dcn_ctx *c, dcn_index *map, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint32_t n_reads,
@@ -152,7 +181,10 @@ int pileup_run(dcn_ctx *c, dcn_index *map, const uint8_t *bases, const uint8_t *
             qa.sums = map->d_pileup_qsums;
             qa.qual_offset = qprm->qual_offset;
             qa.min_base_qual = qprm->min_base_qual;
-            DCN_TRY(dcn_launch_pileup_qual(qa, st));
+            if (map->d_pileup_strands) DCN_TRY(dcn_launch_pileup_qual_strand(qa, map->d_pileup_strands, st)); // rule S2
+            else DCN_TRY(dcn_launch_pileup_qual(qa, st));
+        } else if (map->d_pileup_strands) {
+            DCN_TRY(dcn_launch_pileup_strand(pa, map->d_pileup_strands, st));
         } else {
             DCN_TRY(dcn_launch_pileup(pa, st));
         }
@@ -245,6 +277,27 @@ extern "C" int dcn_anchor_map_pileup_fetch_qualities(const dcn_index *map, uint3
         DCN_HIP(hipMemcpy(plane.data(), map->d_pileup_qsums + dcn_pile_sum_index(col, b0, map->pileup_bases), n_bases * sizeof(uint32_t),
                           hipMemcpyDeviceToHost));
         for (uint64_t q = 0; q < n_bases; ++q) sums[q * DCN_PILE_SUM_COLUMNS + col] = plane[q];
+    }
+#endif
+    return DCN_OK;
+}
+
+extern "C" int dcn_anchor_map_pileup_fetch_strands(const dcn_index *map, uint32_t record, uint64_t start, uint64_t n_bases, uint32_t *rev) {
+    DCN_TRY(check_strands(map));
+    uint64_t b0 = 0;
+    DCN_TRY(check_range(map, "pileup fetch", record, start, n_bases, &b0));
+    if (n_bases == 0) return DCN_OK;
+    if (!rev) return dcn_fail(DCN_ERR_ARG, "rev is NULL");
+    DCN_HIP(hipSetDevice(map->device));
+#if defined(DCN_PILEUP_POSITION_MAJOR)
+    DCN_HIP(hipMemcpy(rev, map->d_pileup_strands + b0 * DCN_PILE_STRAND_COLUMNS, n_bases * DCN_PILE_STRAND_COLUMNS * sizeof(uint32_t),
+                      hipMemcpyDeviceToHost));
+#else
+    std::vector<uint32_t> plane(n_bases); // (as dcn_anchor_map_pileup_fetch: a plane at a time, transposed here)
+    for (uint32_t col = 0; col < DCN_PILE_STRAND_COLUMNS; ++col) {
+        DCN_HIP(hipMemcpy(plane.data(), map->d_pileup_strands + dcn_pile_strand_index(col, b0, map->pileup_bases), n_bases * sizeof(uint32_t),
+                          hipMemcpyDeviceToHost));
+        for (uint64_t q = 0; q < n_bases; ++q) rev[q * DCN_PILE_STRAND_COLUMNS + col] = plane[q];
     }
 #endif
     return DCN_OK;

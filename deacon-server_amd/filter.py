@@ -701,6 +701,12 @@ INDEL_SITE_DTYPE = np.dtype([("pos", np.uint64), ("bases_offset", np.uint64), ("
                              ("depth", np.uint32), ("count", np.uint32), ("events", np.uint32), ("gt", np.uint8), ("gq", np.uint8),
                              ("pl", np.uint8, (3,)), ("reserved", np.uint8, (3,))])
 DELETION_REVERSE, INDEL_DELETION, INDEL_FRONT = N.DELETION_REVERSE, N.INDEL_DELETION, N.INDEL_FRONT  # DCN_DELETION_*, DCN_INDEL_*
+# numpy views of dcn_strand_query (32 bytes) and dcn_strand_site (64 bytes): what AnchorMap.strand_evidence takes and returns
+STRAND_QUERY_DTYPE = np.dtype([("pos", np.uint64), ("kind", np.uint32), ("ref_code", np.uint32), ("alt_mask", np.uint32), ("count", np.uint32),
+                               ("count_reverse", np.uint32), ("reserved", np.uint32)])
+STRAND_SITE_DTYPE = np.dtype([("fwd", np.uint32, (4,)), ("rev", np.uint32, (4,)), ("table", np.uint32, (4,)), ("sb_centi", np.uint32),
+                              ("flags", np.uint32), ("reserved", np.uint32, (2,))])
+STRAND_BIAS, STRAND_ONE_SIDED = N.STRAND_BIAS, N.STRAND_ONE_SIDED  # DCN_STRAND_*
 _CIGAR_LETTERS = {N.CIGAR_INS: "I", N.CIGAR_DEL: "D", N.CIGAR_EQUAL: "=", N.CIGAR_DIFF: "X"}
 
 
@@ -952,6 +958,81 @@ class AnchorMap(Index):
         p = N.IndelParams(int(ploidy), int(min_depth), int(min_gq), int(min_qual), int(min_count), int(indel_centi), int(het_centi), 0)
         return self._insertions(N.lib().dcn_anchor_map_indels_genotype, (self._h, C.byref(p), int(record), start, n), INDEL_SITE_DTYPE, n,
                                 n // 64 + 64)
+
+    def pileup_keep_strands(self, keep=True):
+        """Strand planes beside the pileup (dcn_anchor_map_pileup_keep_strands; the definition of strand evidence is in
+        include/deacon_hip.h): four uint32 per base, RA RC RG RT, to which Placer.pileup_batch adds 1 for every base of a
+        reverse row that it counts in A, C, G or T.  16 B of device memory per kept base.  Refused once a row has added since
+        pileup_enable() or pileup_reset(); keep=False frees them and leaves the counters."""
+        N.check(N.lib().dcn_anchor_map_pileup_keep_strands(self._h, 1 if keep else 0))
+
+    def pileup_fetch_strands(self, record, start=0, n=None):
+        """the reverse counters of positions [start, start + n) of a record (n=None: to its end) -> np.uint32[n, 4], the
+        columns PILEUP_A, C, G, T; the forward count of a column is pileup_fetch's counter less this one"""
+        start, n = int(start), self._to_end(record, start) if n is None else int(n)
+        out = np.zeros((max(n, 1), 4), np.uint32)
+        N.check(N.lib().dcn_anchor_map_pileup_fetch_strands(self._h, int(record), start, n, _ptr(out)))
+        return out[:n]
+
+    def strand_evidence(self, record, queries, max_sb_centi=1083, min_alt_strand=1, min_strand_depth=3):
+        """Rules S3-S6 (the definition of strand evidence is in include/deacon_hip.h) at the sites of `queries`, a
+        STRAND_QUERY_DTYPE[] in any order, of a map that keeps strand planes -> STRAND_SITE_DTYPE[len(queries)]: the forward
+        and reverse counts of the four columns (base queries), the 2 x 2 table, the score in hundredths of a chi-square and
+        the flags STRAND_BIAS / STRAND_ONE_SIDED.  The defaults are conventions, not measured optima."""
+        queries = np.ascontiguousarray(queries, dtype=STRAND_QUERY_DTYPE)
+        p = N.StrandParams(int(max_sb_centi), int(min_alt_strand), int(min_strand_depth), 0)
+        out = np.zeros(max(len(queries), 1), STRAND_SITE_DTYPE)
+        N.check(N.lib().dcn_anchor_map_strand_evidence(self._h, C.byref(p), int(record), _ptr(queries) if len(queries) else None, len(queries),
+                                                       _ptr(out)))
+        return out[:len(queries)]
+
+    def indels_strand(self, record, sites, bases=b""):
+        """a_rev of rule S4 for the sites and bases that indels_genotype returned (dcn_anchor_map_indels_strand) ->
+        np.uint32[len(sites)]: how many events of each site's winning allele came from reverse rows.  Needs the ledgers, not
+        the strand planes."""
+        sites = np.ascontiguousarray(sites, dtype=INDEL_SITE_DTYPE)
+        bases = np.frombuffer(bytes(bases), np.uint8)
+        out = np.zeros(max(len(sites), 1), np.uint32)
+        N.check(N.lib().dcn_anchor_map_indels_strand(self._h, int(record), _ptr(sites) if len(sites) else None, len(sites),
+                                                     _ptr(bases) if len(bases) else None, _ptr(out)))
+        return out[:len(sites)]
+
+    @staticmethod
+    def strand_queries_of_genotypes(sites, ploidy=2):
+        """the base queries of genotype()'s sites: ALT = the alleles of the site's genotype other than the record's base"""
+        q = np.zeros(len(sites), STRAND_QUERY_DTYPE)
+        gt = sites["gt"].astype(np.int64)
+        if int(ploidy) == 2:  # rule G3's order: index y (y + 1) / 2 + x, x <= y
+            y = ((np.sqrt(8 * gt + 1) - 1) // 2).astype(np.int64)
+            x = gt - y * (y + 1) // 2
+        else:
+            x = y = gt
+        ref = sites["ref_code"].astype(np.int64)
+        q["pos"], q["ref_code"] = sites["pos"], ref
+        q["alt_mask"] = ((1 << x) | (1 << y)) & ~(1 << ref) & 15
+        return q
+
+    @staticmethod
+    def strand_queries_of_indels(sites, count_reverse):
+        """the indel queries of indels_genotype()'s sites, with indels_strand()'s numbers"""
+        q = np.zeros(len(sites), STRAND_QUERY_DTYPE)
+        q["pos"], q["kind"], q["count"], q["count_reverse"] = sites["pos"], 1, sites["count"], count_reverse
+        return q
+
+    def genotype_strand(self, record, start=0, n=None, ploidy=2, min_depth=3, min_gq=20, min_qual=20, err_centi=477, het_centi=301,
+                        max_sb_centi=1083, min_alt_strand=1, min_strand_depth=3):
+        """genotype() and, for its sites, strand_evidence() -> (gt, gq, sites GENOTYPE_SITE_DTYPE[], STRAND_SITE_DTYPE[])"""
+        gt, gq, sites = self.genotype(record, start, n, ploidy, min_depth, min_gq, min_qual, err_centi, het_centi)
+        return gt, gq, sites, self.strand_evidence(record, self.strand_queries_of_genotypes(sites, ploidy), max_sb_centi, min_alt_strand,
+                                                   min_strand_depth)
+
+    def indels_genotype_strand(self, record, start=0, n=None, ploidy=2, min_depth=3, min_gq=20, min_qual=20, min_count=2, indel_centi=2000,
+                               het_centi=301, max_sb_centi=1083, min_alt_strand=1, min_strand_depth=3):
+        """indels_genotype() and, for its sites, indels_strand() and strand_evidence() -> (sites INDEL_SITE_DTYPE[], bases
+        bytes, STRAND_SITE_DTYPE[])"""
+        sites, bases = self.indels_genotype(record, start, n, ploidy, min_depth, min_gq, min_qual, min_count, indel_centi, het_centi)
+        queries = self.strand_queries_of_indels(sites, self.indels_strand(record, sites, bases))
+        return sites, bases, self.strand_evidence(record, queries, max_sb_centi, min_alt_strand, min_strand_depth)
 
     def consensus(self, record, start=0, n=None, min_depth=3, min_permille=500, fill_ref=False):
         """Rule L7 over [start, start + n) of a record -> bytes: per position the bases of a called front insertion, the

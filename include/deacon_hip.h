@@ -85,9 +85,10 @@ enum {
  * 1.19 = dcn_anchor_map_genotype.
  * 1.20 = dcn_anchor_map_duplicates_enable / _reset / _info, dcn_mark_duplicates_batch.
  * 1.21 = dcn_anchor_map_pileup_keep_deletions, dcn_anchor_map_deletions_info / _fetch, dcn_anchor_map_indels_genotype.
- * 1.22 = dcn_left_align_batch, dcn_anchor_map_pileup_left_align / _left_align_info. */
+ * 1.22 = dcn_left_align_batch, dcn_anchor_map_pileup_left_align / _left_align_info.
+ * 1.23 = dcn_anchor_map_pileup_keep_strands / _fetch_strands, dcn_anchor_map_strand_evidence, dcn_anchor_map_indels_strand. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 22
+#define DCN_ABI_MINOR 23
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
@@ -1490,6 +1491,112 @@ int dcn_anchor_map_pileup_left_align(dcn_index *map, int on);
 /* A dcn_left_align_info (declared void * likewise) summed over the map's pileup calls that ran with the switch on, since
  * the pileup was enabled or reset.  No device work.  DCN_ERR_ARG for a map without a pileup, then for info NULL. */
 int dcn_anchor_map_pileup_left_align_info(const dcn_index *map, void *info);
+
+/* ---- strand evidence: per-allele reverse counts, a bias score and two flags (ABI 1.23) ---------------------------------
+ * (no reference counterpart.)  The REV column says how many reverse rows covered a base, not which allele they showed, and
+ * rule G1 keeps it out of the vote.  A heterozygote seen on both strands and an artefact carried by reads of one
+ * orientation look alike in the counters.  Four more planes tell them apart; the two ledgers already carry each event's
+ * strand.
+ *
+ * THE DEFINITION OF STRAND EVIDENCE.  Rules P1-P6, Q1-Q6, L1-L8, R1-R6, G1-G8 and I1-I8 stand.  Added:
+ *   S1. A map with a pileup may keep STRAND PLANES: four more uint32_t counters per kept base, RA RC RG RT, all zero when
+ *       switched on.  They cost 16 bytes per base and are laid out as the counters are, planes of one column each (four
+ *       words per position under -DDCN_PILEUP_POSITION_MAJOR).  Switching them on is DCN_ERR_ARG once a row has added
+ *       since the pileup was enabled or last reset (L1's rule).  dcn_anchor_map_pileup_reset zeroes them,
+ *       dcn_anchor_map_pileup_enable(map, 0) and dcn_index_destroy free them, dcn_index_clone gives an index without them,
+ *       dcn_index_memory does not count them.
+ *   S2. While the planes are kept, every '=' or X step of a row with reverse = 1 also adds 1 to R[c] at that position,
+ *       where c is the column the step is counted in: P3's, or with qualities Q3's.  This applies only when c is one of A,
+ *       C, G, T: a base that counts as N (an invalid base, a base under min_base_qual) adds to no plane, and neither do D
+ *       and I runs.  Hence R[c] <= n[c] everywhere, F[c] = n[c] - R[c] is the forward count, and
+ *       RA + RC + RG + RT <= REV.  The adds commute (P5).  Left alignment (N8) applies first, as to everything counted.
+ *   S3. The TABLE of a base site.  Given a position, the record's base ref (valid) and a non-empty set ALT of columns
+ *       other than ref:  a = F[ref], b = R[ref], c = the sum of F[x] over x in ALT, d = the same sum of R[x].
+ *   S4. The TABLE of an indel site of rule I5, with a_all = its count and a_rev = the number of the winner's events with
+ *       reverse = 1:  d = a_rev;  c = a_all - a_rev;  b = REV(p) >= d ? REV(p) - d : 0;
+ *       a = (depth - REV(p)) >= c ? depth - REV(p) - c : 0, with depth - REV(p) taken as 0 when depth < REV(p).  So the
+ *       first row is "every read there that does not carry the allele", which is what rule I2 calls o.
+ *   S5. The SCORE, in integers only, in hundredths of a chi-square with one degree of freedom.  Let m = max(a, b, c, d),
+ *       s = 0 when m < 1024 and (the bit length of m) - 10 otherwise.  All four are shifted right by s, so that each is
+ *       below 1024 (GATK shrinks large tables the same way before its Fisher test).  N = a + b + c + d, r1 = a + b,
+ *       r2 = c + d, c1 = a + c, c2 = b + d.  If r1 r2 c1 c2 = 0 the score is 0.  Otherwise
+ *         sb_centi = min(65535, 100 N (ad - bc)^2 / (r1 r2 c1 c2)),
+ *       an integer quotient of unsigned 64-bit numbers: N < 2^12 and |ad - bc| < 2^20, so the numerator stays below
+ *       2^7 * 2^12 * 2^40 = 2^59, and the denominator below 2^44.
+ *   S6. FLAGS.  DCN_STRAND_BIAS when max_sb_centi > 0 and sb_centi >= max_sb_centi.  DCN_STRAND_ONE_SIDED when
+ *       min(c, d) < min_alt_strand and both a + c and b + d are at least min_strand_depth: both strands cover the site,
+ *       yet the allele is on one.  This flag uses the unshifted table.  A site with no flag passes.
+ *   S7. Stated limits.  A hom-alt site has an empty reference row and scores 0.  There is no Yates correction and no exact
+ *       test.  Only the winner of each indel kind is counted.  max_sb_centi = 1083 is a convention, not a measured optimum:
+ *       chi-square 10.83, p = 0.001 at one degree of freedom.  min_alt_strand = 1 and min_strand_depth = 3 are conventions
+ *       too.
+ *   S8. The result is unique while no counter has wrapped: a function of the counters, the planes, the ledgers and the
+ *       parameters. */
+#define DCN_STRAND_BIAS 1u
+#define DCN_STRAND_ONE_SIDED 2u
+typedef struct dcn_strand_params {
+    uint32_t max_sb_centi;     /* 0: the bias flag is off */
+    uint32_t min_alt_strand;
+    uint32_t min_strand_depth;
+    uint32_t reserved;         /* must be 0 */
+} dcn_strand_params;           /* 16 bytes */
+typedef struct dcn_strand_query {
+    uint64_t pos;           /* record-relative, 0-based */
+    uint32_t kind;          /* 0 a base site (S3), 1 an indel site (S4) */
+    uint32_t ref_code;      /* base: the record's base, 0 .. 3 */
+    uint32_t alt_mask;      /* base: ALT, bits 0 .. 3 */
+    uint32_t count;         /* indel: a_all */
+    uint32_t count_reverse; /* indel: a_rev */
+    uint32_t reserved;      /* must be 0 */
+} dcn_strand_query;         /* 32 bytes */
+typedef struct dcn_strand_site {
+    uint32_t fwd[4];      /* base: F[A..T]; indel: 0 */
+    uint32_t rev[4];      /* base: R[A..T]; indel: 0 */
+    uint32_t table[4];    /* a, b, c, d, unshifted */
+    uint32_t sb_centi;    /* S5 */
+    uint32_t flags;       /* S6: DCN_STRAND_BIAS, DCN_STRAND_ONE_SIDED */
+    uint32_t reserved[2]; /* 0 */
+} dcn_strand_site;        /* 64 bytes */
+
+/* The twin of dcn_anchor_map_pileup_keep_deletions for rule S1's planes.  keep != 0 switches them on (keeping again changes
+ * nothing): 16 bytes of device memory per base of the pileup, allocated and zeroed here; keep = 0 frees them and leaves the
+ * counters.  DCN_ERR_ARG for a map without a pileup, and by rule S1; on a map that keeps planes dcn_pileup_batch and
+ * dcn_pileup_batch_qual launch the strand form of the pileup kernel instead of the plain one: the same walk, with one
+ * more add per counted base of a reverse row, and not one memory operation more on a forward row.  A map on which the
+ * switch is off issues exactly the launches and copies it issued before.  Blocking. */
+int dcn_anchor_map_pileup_keep_strands(dcn_index *map, int keep);
+
+/* The planes of positions [start, start + n_bases) of a record, position-major: rev[4 q + column] belongs to position
+ * start + q, the columns being DCN_PILEUP_A .. DCN_PILEUP_T.  Blocking.  Errors as for dcn_anchor_map_pileup_fetch, and
+ * DCN_ERR_ARG for a map that keeps no planes. */
+int dcn_anchor_map_pileup_fetch_strands(const dcn_index *map, uint32_t record, uint64_t start, uint64_t n_bases, uint32_t *rev);
+
+/* Rules S3-S6 at n_queries sites of a record.
+ *   params    a dcn_strand_params (declared void * for the reason given at dcn_locate_batch)
+ *   queries   dcn_strand_query entries (declared void * likewise), in any order
+ *   out       dcn_strand_site entries (declared void * likewise), one per query
+ * DCN_ERR_ARG, in this order: params NULL or reserved != 0; a map without a pileup or without planes; a record out of
+ * range; then, when n_queries > 0, queries or out NULL; then the first wrong query, with its index in the message: a pos
+ * past the record, a kind above 1 (or reserved != 0), a base query with ref_code > 3, an empty alt_mask, bits above 3 in it
+ * or ref's bit in it, an indel query with count_reverse > count.  n_queries = 0 succeeds with no device work.  Blocking, on
+ * the null stream with scratch of the call: the queries go up, one thread per query gathers the position's counters (and on
+ * a base query its four reverse counters) and applies dcn_strand.h's rule, and the sites come back. */
+int dcn_anchor_map_strand_evidence(const dcn_index *map, const void *params, uint32_t record, const void *queries, uint64_t n_queries,
+                                   void *out);
+
+/* a_rev of rule S4 for the sites that dcn_anchor_map_indels_genotype returned: count_reverse[s] receives the number of
+ * events with reverse = 1 among the winning allele of sites[s].
+ *   sites, bases   dcn_indel_site entries and the inserted bases, as that call wrote them (sites declared void *)
+ * DCN_ERR_ARG for a map without a pileup, a record out of range, sites or count_reverse NULL when n_sites > 0, then for the
+ * first wrong site with its index in the message: a pos past the record, sites not in I6's order, an insertion site whose
+ * bases_offset is not the sum of the insertion sites' lengths in front of it (and bases NULL then), a site whose kind has no
+ * ledger on the map.  It needs no strand planes: the ledgers carry the strand.  n_sites = 0 succeeds with no device work.
+ * Blocking, on the null stream with scratch of the call: the sites' keys, lengths and bases go up, then one thread per event
+ * of each ledger that has a site finds the site of its (pos, kind, front) by binary search, compares len, and on an
+ * insertion the bases, and when it is a reverse event adds 1 atomically.  The winner and site kernels of
+ * dcn_anchor_map_indels_genotype are not involved. */
+int dcn_anchor_map_indels_strand(const dcn_index *map, uint32_t record, const void *sites, uint64_t n_sites, const uint8_t *bases,
+                                 uint32_t *count_reverse);
 
 /* ---- extended placements: each placement carried over the read's flanks, with soft clips (ABI 1.16) -------------------
  * (no reference counterpart.)  A placement's two intervals begin and end on the k-mer of an anchor hit: the read's bases
