@@ -329,6 +329,36 @@ class StrandSite(C.Structure):
 STRAND_BIAS, STRAND_ONE_SIDED = 1, 2  # DCN_STRAND_*: the flags of rule S6
 
 
+class BlockParams(C.Structure):  # dcn_block_params of include/deacon_hip_blocks.h, 48 bytes
+    _fields_ = [
+        ("ploidy", C.c_uint32),
+        ("min_depth", C.c_uint32),
+        ("min_gq", C.c_uint32),
+        ("min_qual", C.c_uint32),
+        ("err_centi", C.c_uint32),
+        ("het_centi", C.c_uint32),
+        ("n_edges", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("edges", C.c_uint8 * 16),
+    ]
+
+
+class ReferenceBlock(C.Structure):  # dcn_reference_block, 40 bytes
+    _fields_ = [
+        ("pos", C.c_uint64),
+        ("sum_depth", C.c_uint64),
+        ("len", C.c_uint32),
+        ("min_depth", C.c_uint32),
+        ("max_depth", C.c_uint32),
+        ("min_gq", C.c_uint32),
+        ("cls", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+BLOCK_NO_COVERAGE, BLOCK_UNCALLED, BLOCK_REF, BLOCK_VARIANT = 0, 1, 2, 255  # DCN_BLOCK_*: the classes of rule B2
+
+
 class ExtendParams(C.Structure):
     _fields_ = [
         ("penalty", C.c_uint32),
@@ -492,8 +522,16 @@ _SIGNATURES = {
     "dcn_anchor_map_indels_strand": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64, _vp, _vp]),
 }
 
+# the functions that include/deacon_hip_blocks.h declares (ABI 1.24): a table of their own, so that _SIGNATURES stays the set
+# of include/deacon_hip.h
+BLOCKS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "deacon_hip_blocks.h")
+_BLOCK_SIGNATURES = {
+    "dcn_anchor_map_reference_blocks": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _u64p]),
+    "dcn_reference_blocks_merge": (C.c_int, [_vp, C.c_uint64, _u64p]),
+}
+
 _lib = None
-ABI = (1, 23)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 24)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():
@@ -506,7 +544,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with __graft_entry__.build() "
             "(make -C deacon-server_amd/csrc). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()):
         f = getattr(L, name)  # AttributeError if the library does not export a declared symbol
         f.restype = res
         f.argtypes = args

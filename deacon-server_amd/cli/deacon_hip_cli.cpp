@@ -43,6 +43,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <cerrno>
 #include <chrono>
 #include <condition_variable>
@@ -65,6 +66,7 @@
 #include "fast_inflate.hpp"
 #include "parallel_gzip.hpp"
 #include "deacon_hip.hpp"
+#include "deacon_hip_blocks.h"
 
 namespace {
 
@@ -3856,6 +3858,12 @@ struct MapArgs {
     // normalize and all it sets are set
     bool strand = false;
     unsigned max_sb = 1083, min_alt_strand = 1, min_strand_depth = 3;
+    // `gvcf`: strand, with the reference blocks of every record (dcn_anchor_map_reference_blocks, asked stretch by stretch and
+    // merged over the seams by dcn_reference_blocks_merge) as block lines between the VCF's lines (--gvcf) and as a BED of
+    // callable regions (--callable); strand and all it sets are set
+    bool gvcf = false, has_gvcf = false, has_callable = false;
+    std::string gvcf_out, callable;
+    std::vector<unsigned> gq_bands = {20, 40, 60, 80, 99}; // (checked by the library, whose errors the tool passes on)
 };
 
 // one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
@@ -3905,14 +3913,14 @@ void append_paf(std::string &rows, const std::string &read_name, uint32_t read_l
 int run_map(const MapArgs &a) {
     const Stopwatch watch;
     const auto no_qualities = [&a](const std::string &name) {
-        die(std::string(a.strand ? "strand" : a.normalize ? "normalize" : a.indels ? "indels" : a.markdup ? "markdup" : a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
+        die(std::string(a.gvcf ? "gvcf" : a.strand ? "strand" : a.normalize ? "normalize" : a.indels ? "indels" : a.markdup ? "markdup" : a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
     };
     std::unique_ptr<FastxReader> reads; // (`call` looks at the first record before the reference is loaded)
     if (a.call) {
         if (a.ref.empty()) die("the following required arguments were not provided: <REF>");
-        if (a.genotype && !a.has_fasta && !a.has_variants && !a.has_pileup_out && !a.has_sites && !a.has_vcf && !a.has_summary && !a.has_duplicates)
+        if (a.genotype && !a.has_fasta && !a.has_variants && !a.has_pileup_out && !a.has_sites && !a.has_vcf && !a.has_summary && !a.has_duplicates && !a.has_gvcf && !a.has_callable)
             die(std::string("nothing to write: give at least one of -o <OUTPUT>, --variants <FILE>, --pileup <FILE>, --sites <FILE>, --vcf <FILE>, ") +
-                (a.markdup ? "--duplicates <FILE>, " : "") + "-s <SUMMARY>");
+                (a.gvcf ? "--gvcf <FILE>, --callable <FILE>, " : "") + (a.markdup ? "--duplicates <FILE>, " : "") + "-s <SUMMARY>");
         reads.reset(new FastxReader(a.input));
         std::string name;
         if (reads->begins_with_fasta(&name)) no_qualities(name);
@@ -4128,12 +4136,18 @@ int run_map(const MapArgs &a) {
     uint64_t deletion_events = 0, deleted_bases = 0, indel_sites = 0, insertion_sites = 0, deletion_sites = 0, het_indel_sites = 0,
              hom_indel_sites = 0; // (indels)
     uint64_t strand_bias_sites = 0, one_strand_sites = 0, filtered_sites = 0; // (strand)
+    uint64_t n_blocks = 0, block_bases = 0, no_coverage_bases = 0, uncalled_bases = 0, ref_bases = 0, record_bases = 0; // (gvcf)
+    std::vector<uint64_t> ref_bases_by_band(a.gq_bands.size() + 1, 0);
     if (piles) {
         TextOut sites_out, pile_file, fasta_out, variants_out;
         std::unique_ptr<Output> vcf_out; // (.gz as BGZF, .zst and .xz by extension, as filter's outputs)
         const auto vcf_write = [&vcf_out](const std::string &text) { vcf_out->write(std::vector<char>(text.begin(), text.end())); };
-        if (a.has_vcf) { // VCF 4.2, SNVs only: indels stay in --variants (`indels`: and as INDEL lines here)
-            vcf_out.reset(new Output(a.vcf, 2));
+        std::unique_ptr<Output> gvcf_out; // (`gvcf`)
+        const auto gvcf_write = [&gvcf_out](const std::string &text) { gvcf_out->write(std::vector<char>(text.begin(), text.end())); };
+        TextOut callable_out;
+        std::string vcf_head; // the header without its #CHROM line
+        if (a.has_vcf || a.has_gvcf) { // VCF 4.2, SNVs only: indels stay in --variants (`indels`: and as INDEL lines here)
+            if (a.has_vcf) vcf_out.reset(new Output(a.vcf, 2));
             std::string head = std::string("##fileformat=VCFv4.2\n##source=deacon-hip ") + VERSION + "\n";
             for (uint32_t r = 0; r < R.n_records; ++r) head += "##contig=<ID=" + R.names[r] + ",length=" + std::to_string(R.lens[r]) + ">\n";
             if (a.strand)
@@ -4154,10 +4168,25 @@ int run_map(const MapArgs &a) {
             if (a.strand)
                 head += "##FORMAT=<ID=ADF,Number=R,Type=Integer,Description=\"AD on the forward strand\">\n"
                         "##FORMAT=<ID=ADR,Number=R,Type=Integer,Description=\"AD on the reverse strand\">\n";
-            head += "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods, at most 255\">\n"
-                    "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + a.sample + "\n";
-            vcf_write(head);
+            head += "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods, at most 255\">\n";
+            vcf_head = head;
+            head += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + a.sample + "\n";
+            if (a.has_vcf) vcf_write(head);
         }
+        if (a.has_gvcf) { // the --vcf header and, in front of #CHROM, what the block lines use
+            gvcf_out.reset(new Output(a.gvcf_out, 2));
+            std::string head = vcf_head +
+                               "##ALT=<ID=NON_REF,Description=\"Any allele other than the reference's: the line is a reference block\">\n"
+                               "##INFO=<ID=END,Number=1,Type=Integer,Description=\"Last position of the block\">\n"
+                               "##FORMAT=<ID=MIN_DP,Number=1,Type=Integer,Description=\"Smallest DP of the block's positions\">\n";
+            for (size_t b = 0; b <= a.gq_bands.size(); ++b) {
+                const unsigned lo = b ? a.gq_bands[b - 1] : 0u, hi = b < a.gq_bands.size() ? a.gq_bands[b] : 100u;
+                head += "##GVCFBlock" + std::to_string(lo) + "-" + std::to_string(hi) + "=minGQ=" + std::to_string(lo) + "(inclusive),maxGQ=" +
+                        std::to_string(hi) + "(exclusive)\n";
+            }
+            gvcf_write(head + "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + a.sample + "\n");
+        }
+        if (a.has_callable) callable_out.open(a.callable, false);
         dcn_genotype_params gprm = {};
         gprm.ploidy = a.ploidy;
         gprm.min_depth = a.min_depth;
@@ -4229,8 +4258,35 @@ int run_map(const MapArgs &a) {
         std::vector<uint64_t> site_pos;
         std::vector<uint8_t> ref_text;
         std::string site_rows;
+        // (`gvcf`) rules B1-B9 a stretch at a time: the stretch's blocks behind the one block that the stretch before left open at
+        // the seam, merged (rule B7); every block but an open last one is final and goes out, with the stretch's VCF lines, in
+        // POS order, a block's line in front of a VCF line of its POS.  No per-position bytes are fetched.
+        dcn_block_params bprm = {};
+        bprm.ploidy = a.ploidy, bprm.min_depth = a.min_depth, bprm.min_gq = a.min_gq, bprm.min_qual = a.min_qual, bprm.err_centi = 477, bprm.het_centi = 301;
+        bprm.n_edges = (uint32_t)std::min<size_t>(a.gq_bands.size(), 16);
+        for (size_t b = 0; b < a.gq_bands.size() && b < 16; ++b) bprm.edges[b] = (uint8_t)std::min(a.gq_bands[b], 255u);
+        std::vector<dcn_reference_block> blocks, fresh;
+        std::vector<uint64_t> breaks;
+        std::string gvcf_rows;
+        uint64_t bed_from = 0, bed_to = 0; // the callable interval that is open, [bed_from, bed_to) with label bed_label
+        const char *bed_label = nullptr;
+        std::string bed_rows;
+        const auto bed_add = [&](uint32_t r, uint64_t from, uint64_t to, const char *label) { // label = nullptr: the record ends
+            if (label && bed_label == label && bed_to == from) {
+                bed_to = to;
+                return;
+            }
+            if (bed_label && bed_to > bed_from)
+                bed_rows += R.names[r] + '\t' + std::to_string(bed_from) + '\t' + std::to_string(bed_to) + '\t' + bed_label + '\n';
+            bed_from = from, bed_to = to, bed_label = label;
+        };
+        static const char *const LABEL_NO_COVERAGE = "NO_COVERAGE", *const LABEL_LOW = "LOW_CONFIDENCE", *const LABEL_CALLABLE = "CALLABLE";
+        uint64_t bed_cursor = 0; // the first position of the record that no final block and no gap in front of one has covered
         for (uint32_t r = 0; r < R.n_records; ++r) {
             if (a.has_fasta) fasta_out.write(">" + R.names[r] + "\n");
+            record_bases += R.lens[r];
+            blocks.clear();
+            bed_cursor = 0, bed_label = nullptr;
             for (uint64_t start = 0; start < R.lens[r]; start += stretch) {
                 const uint64_t n = std::min<uint64_t>(stretch, R.lens[r] - start);
                 counts.resize(n * DCN_PILEUP_COLUMNS);
@@ -4345,6 +4401,7 @@ int run_map(const MapArgs &a) {
                     vcf_sites += n_geno;
                     vcf_rows.clear();
                     snv_at.clear();
+                    uint64_t gvcf_indels = 0; // (`gvcf`) the INDEL lines of the stretch: their positions are the breaks
                     if (a.strand) { // rules S3, S5 and S6 at the stretch's sites: ALT = the genotype's alleles other than the record's base
                         strand_queries.assign(n_geno, dcn_strand_query{});
                         snv_strand.resize(n_geno);
@@ -4414,6 +4471,7 @@ int run_map(const MapArgs &a) {
                             ind_bases.resize(n_ind_bases);
                         }
                         indel_sites += n_ind;
+                        gvcf_indels = n_ind;
                         if (a.strand) { // rule S4: the winners' reverse events from the ledgers, then the table, the score and the flags
                             ind_reverse.resize(n_ind);
                             ind_strand.resize(n_ind);
@@ -4484,6 +4542,71 @@ int run_map(const MapArgs &a) {
                         vcf_rows.swap(merged_rows);
                     }
                     if (a.has_vcf) vcf_write(vcf_rows);
+                    if (a.gvcf) {
+                        breaks.clear();
+                        for (uint64_t i = 0; i < ind_sites.size() && i < gvcf_indels; ++i) breaks.push_back(ind_sites[i].pos);
+                        uint64_t n_fresh = 0;
+                        for (int attempt = 0;; ++attempt) {
+                            const int rc = dcn_anchor_map_reference_blocks(R.map.p, &bprm, r, start, n, breaks.data(), breaks.size(), nullptr, fresh.data(),
+                                                                           fresh.size(), &n_fresh);
+                            if (rc != DCN_ERR_CAPACITY || attempt) {
+                                deacon::check(rc);
+                                break;
+                            }
+                            fresh.resize(n_fresh);
+                        }
+                        blocks.insert(blocks.end(), fresh.begin(), fresh.begin() + n_fresh);
+                        uint64_t kept = 0;
+                        deacon::check(dcn_reference_blocks_merge(blocks.data(), blocks.size(), &kept));
+                        blocks.resize(kept);
+                        const bool last_stretch = start + n == R.lens[r];
+                        // the last block stays open while the record goes on behind it
+                        const bool open = !last_stretch && kept > 0 && blocks[kept - 1].pos + blocks[kept - 1].len == start + n;
+                        const uint64_t n_final = open ? kept - 1 : kept;
+                        gvcf_rows.clear();
+                        size_t line = 0; // where the next VCF line of the stretch begins in vcf_rows
+                        const auto vcf_lines_before = [&](uint64_t pos1) { // the VCF lines whose POS is under pos1
+                            while (line < vcf_rows.size()) {
+                                const size_t tab = vcf_rows.find('\t', line), end = vcf_rows.find('\n', line) + 1;
+                                if (std::strtoull(vcf_rows.c_str() + tab + 1, nullptr, 10) >= pos1) break;
+                                gvcf_rows.append(vcf_rows, line, end - line);
+                                line = end;
+                            }
+                        };
+                        for (uint64_t i = 0; i < n_final; ++i) {
+                            const dcn_reference_block &b = blocks[i];
+                            ++n_blocks, block_bases += b.len;
+                            const bool is_ref = b.cls >= DCN_BLOCK_REF;
+                            if (b.cls == DCN_BLOCK_NO_COVERAGE) no_coverage_bases += b.len;
+                            else if (!is_ref) uncalled_bases += b.len;
+                            else ref_bases += b.len, ref_bases_by_band[std::min<size_t>(b.cls - DCN_BLOCK_REF, ref_bases_by_band.size() - 1)] += b.len;
+                            if (a.has_callable) {
+                                if (b.pos > bed_cursor) bed_add(r, bed_cursor, b.pos, LABEL_CALLABLE); // VARIANT positions
+                                bed_add(r, b.pos, b.pos + b.len, b.cls == DCN_BLOCK_NO_COVERAGE ? LABEL_NO_COVERAGE : is_ref ? LABEL_CALLABLE : LABEL_LOW);
+                                bed_cursor = b.pos + b.len;
+                            }
+                            if (!a.has_gvcf) continue;
+                            vcf_lines_before(b.pos + 1);
+                            uint8_t base = 'N';
+                            if (b.pos >= start) base = ref_text[b.pos - start];
+                            else deacon::check(dcn_anchor_map_fetch(R.map.p, r, b.pos, 1, &base));
+                            gvcf_rows += R.names[r] + '\t' + std::to_string(b.pos + 1) + "\t.\t" + (char)std::toupper(base) + "\t<NON_REF>\t.\t.\tEND=" +
+                                         std::to_string(b.pos + b.len) + "\tGT:GQ:DP:MIN_DP\t" +
+                                         (is_ref ? (a.ploidy == 2 ? "0/0" : "0") : (a.ploidy == 2 ? "./." : ".")) + ':' + std::to_string(b.min_gq) + ':' +
+                                         std::to_string(b.sum_depth / b.len) + ':' + std::to_string(b.min_depth) + '\n';
+                        }
+                        if (a.has_gvcf) {
+                            vcf_lines_before(UINT64_MAX);
+                            gvcf_write(gvcf_rows);
+                        }
+                        blocks.erase(blocks.begin(), blocks.begin() + n_final);
+                        if (last_stretch && a.has_callable) {
+                            if (R.lens[r] > bed_cursor) bed_add(r, bed_cursor, R.lens[r], LABEL_CALLABLE);
+                            bed_add(r, 0, 0, nullptr);
+                            callable_out.write(bed_rows);
+                            bed_rows.clear();
+                        }
+                    }
                 }
                 if (!a.has_sites) continue;
                 site_rows.clear();
@@ -4503,6 +4626,8 @@ int run_map(const MapArgs &a) {
         if (a.has_fasta) fasta_out.finish();
         if (a.has_variants) variants_out.finish();
         if (a.has_vcf) vcf_out->close();
+        if (a.has_gvcf) gvcf_out->close();
+        if (a.has_callable) callable_out.finish();
         if (a.extend && a.has_pileup_out) pile_file.finish();
     }
     if (prints) out.finish();
@@ -4538,6 +4663,10 @@ int run_map(const MapArgs &a) {
         if (a.strand)
             std::fprintf(stderr, "Filtered %llu VCF lines by strand (%llu strand_bias, %llu one_strand)\n", (unsigned long long)filtered_sites,
                          (unsigned long long)strand_bias_sites, (unsigned long long)one_strand_sites);
+        if (a.gvcf)
+            std::fprintf(stderr, "Cut %llu bases into %llu reference blocks (%llu bases reference, %llu not called, %llu without coverage)\n",
+                         (unsigned long long)record_bases, (unsigned long long)n_blocks, (unsigned long long)ref_bases, (unsigned long long)uncalled_bases,
+                         (unsigned long long)no_coverage_bases);
         if (a.verify && !a.pileup)
             std::fprintf(stderr, "Verified %llu of %llu placements (%llu edits over %llu bases)\n", (unsigned long long)verified,
                          (unsigned long long)placements, (unsigned long long)edits_sum, (unsigned long long)verified_bases);
@@ -4622,6 +4751,16 @@ int run_map(const MapArgs &a) {
                         "  \"one_strand_sites\": %llu,\n  \"filtered_sites\": %llu,\n",
                     a.max_sb, a.min_alt_strand, a.min_strand_depth, (unsigned long long)strand_bias_sites, (unsigned long long)one_strand_sites,
                     (unsigned long long)filtered_sites);
+        if (a.gvcf) {
+            appendf(js, "  \"blocks\": %llu,\n  \"block_bases\": %llu,\n  \"variant_positions\": %llu,\n  \"no_coverage_bases\": %llu,\n"
+                        "  \"uncalled_bases\": %llu,\n  \"ref_bases\": %llu,\n  \"ref_bases_by_band\": [",
+                    (unsigned long long)n_blocks, (unsigned long long)block_bases, (unsigned long long)(record_bases - block_bases),
+                    (unsigned long long)no_coverage_bases, (unsigned long long)uncalled_bases, (unsigned long long)ref_bases);
+            for (size_t b = 0; b < ref_bases_by_band.size(); ++b) appendf(js, "%s%llu", b ? ", " : "", (unsigned long long)ref_bases_by_band[b]);
+            js += "],\n  \"gq_bands\": [";
+            for (size_t b = 0; b < a.gq_bands.size(); ++b) appendf(js, "%s%u", b ? ", " : "", a.gq_bands[b]);
+            js += "],\n";
+        }
         appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
         for (uint32_t r = 0; r < R.n_records; ++r) {
             js += (r ? ",\n    {" : "\n    {");
@@ -4778,6 +4917,7 @@ void usage() {
                  "  indels  As markdup, with a genotype per insertion and deletion from the two ledgers: INDEL lines in the VCF\n"
                  "  normalize  As indels, with every read's gaps left-aligned first: an indel in a repeat stands at its near end\n"
                  "  strand  As normalize, with per-allele strand counts: FILTER strand_bias / one_strand, SB, ADF and ADR in the VCF\n"
+                 "  gvcf    As strand, with reference blocks between the VCF's lines (a gVCF) and a BED of callable regions\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -5413,7 +5553,8 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "optical-distance rule; nothing is read from the bases or the qualities.  Mates are independent here: one input,\n"
                "and a read is a unit.  Pairs as units (one key from both mates' ends) are a feature of the library\n"
                "(dcn_mark_duplicates_batch) and of the Python layer (AnchorMap.mark_duplicates), not of this mode.\n";
-    else if (sub == "indels" || sub == "normalize" || sub == "strand") // (normalize: indels' text with another head and a paragraph more, below; strand: normalize's likewise)
+    else if (sub == "indels" || sub == "normalize" || sub == "strand" || sub == "gvcf") // (gvcf: strand's, likewise)
+        // (normalize: indels' text with another head and a paragraph more, below; strand: normalize's likewise)
         text = "Mark duplicates, pile up and genotype as markdup does, keep the deleted runs beside the inserted bases, and give the\n"
                "insertion and the deletion most reads carry at a position a genotype of their own: INDEL lines in the VCF\n\n"
                "Usage: deacon-hip indels [OPTIONS] <REF> [READS]\n\n"
@@ -5653,11 +5794,11 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "  compare    Report how many minimizers 2 to 32 indexes share, pair by pair\n"
                "  select     Keep the minimizers of several indexes chosen by which of the indexes hold them\n";
     if (!text) return false;
-    if (sub == "normalize" || sub == "strand") { // every option of indels keeps its text
-        const bool strand = sub == "strand";
+    if (sub == "normalize" || sub == "strand" || sub == "gvcf") { // every option of indels keeps its text
+        const bool gvcf = sub == "gvcf", strand = sub == "strand" || gvcf;
         std::string t = text;
         t.erase(0, t.find("Usage: deacon-hip indels"));
-        t.replace(0, std::strlen("Usage: deacon-hip indels"), strand ? "Usage: deacon-hip strand" : "Usage: deacon-hip normalize");
+        t.replace(0, std::strlen("Usage: deacon-hip indels"), gvcf ? "Usage: deacon-hip gvcf" : strand ? "Usage: deacon-hip strand" : "Usage: deacon-hip normalize");
         if (strand) { // the three options of the mode, behind indels' own two
             const std::string at = "      --min-indel-count <N>";
             const size_t line_end = t.find('\n', t.find(at));
@@ -5667,8 +5808,19 @@ bool subcommand_help(const std::vector<std::string> &args) {
                      "      --min-alt-strand <N>       A line whose allele is on fewer than N reads of one strand, while both strands cover\n"
                      "                                 the site, gets FILTER one_strand [default: 1, a convention]\n"
                      "      --min-strand-depth <N>     Reads a strand needs at the site to count as covering it [default: 3, a convention]\n");
+            if (gvcf) // ... and the three of this mode behind them
+                t.insert(t.find('\n', t.find("      --min-strand-depth <N>")) + 1,
+                         "      --gvcf <FILE>              The VCF with one <NON_REF> line per reference block between its lines: a run of\n"
+                         "                                 positions of one class, with END, the smallest GQ, the mean and the smallest DP\n"
+                         "                                 (.gz as BGZF, .zst and .xz by extension, as --vcf)\n"
+                         "      --gq-bands <LIST>          GQ values, ascending, at which a reference block ends and another begins (at most\n"
+                         "                                 15, each 1..99) [default: 20,40,60,80,99, a convention]\n"
+                         "      --callable <FILE>          BED: record start end label, the label NO_COVERAGE, LOW_CONFIDENCE or CALLABLE;\n"
+                         "                                 the intervals tile every record\n");
         }
-        t = std::string(strand ? "Mark duplicates, left-align, pile up and genotype as normalize does, with the reverse reads counted per allele as\n"
+        t = std::string(gvcf ? "Mark duplicates, left-align, pile up and genotype as strand does, and say of every other position what the reads\n"
+                               "say there: reference blocks between the VCF's lines (a gVCF) and a BED of callable regions\n\n"
+                        : strand ? "Mark duplicates, left-align, pile up and genotype as normalize does, with the reverse reads counted per allele as\n"
                                  "well: every VCF line says on which strands its alleles were seen, and whether that looks like an artefact\n\n"
                                : "Mark duplicates, pile up and genotype as indels does, with the gaps of every read's alignment moved to the near end\n"
                                  "of their repeat first: the INDEL lines of the VCF stand where other callers and truth sets put them\n\n") +
@@ -5702,6 +5854,23 @@ bool subcommand_help(const std::vector<std::string> &args) {
                  "strand_bias_sites, one_strand_sites and filtered_sites.  A homozygous ALT line has no reference reads and scores 0.\n"
                  "No Yates correction, no exact test, no mapping quality terms, no priors, no phasing.  With FILTER put back to PASS\n"
                  "and SB, ADF, ADR, the five header lines and the four columns removed, the outputs are normalize's, byte for byte.\n";
+        if (gvcf)
+            t += "\nReference blocks: every position gets a class.  VARIANT: a position with a line in the VCF (an SNV line's, and the\n"
+                 "position an INDEL line's event is counted at).  NO_COVERAGE: no read has a base, an N or a deletion there.\n"
+                 "REF: called (--min-depth, --min-gq), the record's base valid, and the best genotype the reference's; REF positions\n"
+                 "are banded by GQ at --gq-bands.  Everything else is not called: too few bases, GQ under --min-gq, a non-reference\n"
+                 "genotype under --min-qual, a record base that is not ACGT, only N or deleted bases -- so the positions under a\n"
+                 "deletion that most reads carry are not called; they are not excluded.  A block is a maximal run of one class other\n"
+                 "than VARIANT; it is computed on the device from the counters, a stretch of the record at a time, and joined across\n"
+                 "the stretches.  --gvcf writes every line of --vcf unchanged and, between them in POS order, one line per block:\n"
+                 "REF the record's base at the block's first position, ALT <NON_REF>, QUAL and FILTER '.', INFO END=, and\n"
+                 "GT:GQ:DP:MIN_DP with GT 0/0 for a REF block and ./. otherwise (0 and . with --ploidy 1), GQ the block's smallest,\n"
+                 "DP the mean of its positions' DP rounded down, MIN_DP their smallest.  The header gains ##ALT NON_REF, ##INFO END,\n"
+                 "##FORMAT MIN_DP and one ##GVCFBlock line per band.  Variant lines do not gain <NON_REF>: a limit.  --callable labels\n"
+                 "NO_COVERAGE as it is, not-called blocks LOW_CONFIDENCE, every REF band and every VARIANT position CALLABLE, and\n"
+                 "joins neighbours of one label.  -s gains blocks, block_bases, variant_positions, no_coverage_bases, uncalled_bases,\n"
+                 "ref_bases, ref_bases_by_band and gq_bands.  One sample; no joint calling.  Without the three options every output\n"
+                 "is strand's, byte for byte.\n";
         std::fputs(t.c_str(), stdout);
         return true;
     }
@@ -5875,11 +6044,12 @@ int main(int argc, char **argv) {
             return run_place(a);
         }
         if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup" || args[0] == "extend" || args[0] == "consensus" ||
-            args[0] == "call" || args[0] == "genotype" || args[0] == "markdup" || args[0] == "indels" || args[0] == "normalize" || args[0] == "strand") {
+            args[0] == "call" || args[0] == "genotype" || args[0] == "markdup" || args[0] == "indels" || args[0] == "normalize" || args[0] == "strand" || args[0] == "gvcf") {
             MapArgs a;
             a.align = args[0] == "align";
             a.pileup = args[0] == "pileup";
-            a.strand = args[0] == "strand";
+            a.gvcf = args[0] == "gvcf";
+            a.strand = args[0] == "strand" || a.gvcf;
             a.normalize = args[0] == "normalize" || a.strand;
             a.indels = args[0] == "indels" || a.normalize;
             a.markdup = args[0] == "markdup" || a.indels;
@@ -5919,6 +6089,17 @@ int main(int argc, char **argv) {
                 else if (a.strand && s == "--max-sb") a.max_sb = (unsigned)number(need(++i), "--max-sb", 0, 65535);
                 else if (a.strand && s == "--min-alt-strand") a.min_alt_strand = (unsigned)number(need(++i), "--min-alt-strand", 0, 0xFFFFFFFFll);
                 else if (a.strand && s == "--min-strand-depth") a.min_strand_depth = (unsigned)number(need(++i), "--min-strand-depth", 0, 0xFFFFFFFFll);
+                else if (a.gvcf && s == "--gvcf") a.gvcf_out = need(++i), a.has_gvcf = true;
+                else if (a.gvcf && s == "--callable") a.callable = need(++i), a.has_callable = true;
+                else if (a.gvcf && s == "--gq-bands") { // comma-separated numbers; which lists are allowed is the library's to say
+                    a.gq_bands.clear();
+                    const std::string list = need(++i);
+                    for (size_t from = 0; from <= list.size();) {
+                        const size_t comma = std::min(list.find(',', from), list.size());
+                        if (comma > from || !list.empty()) a.gq_bands.push_back((unsigned)number(list.substr(from, comma - from), "--gq-bands", 0, 255));
+                        from = comma + 1;
+                    }
+                }
                 else if (s == "-o" || s == "--output") a.output = need(++i), a.has_output = true;
                 else if (a.extend && s == "--penalty") a.penalty = (unsigned)number(need(++i), "--penalty", 2, 255);
                 else if (a.extend && s == "--end-bonus") a.end_bonus = (unsigned)number(need(++i), "--end-bonus", 0, 65535);

@@ -283,10 +283,12 @@ int dev_alloc_zeroed(T **p, uint64_t count, const char *what) {
 // device memory of one range call over a pileup (pileup_api.hip, genotype_api.hip), freed when the call ends
 namespace dcn_pile_api {
 struct scratch {
-    void *p[6] = {};
+    static constexpr int SLOTS = 6; // dcn_anchor_map_genotype and dcn_anchor_map_reference_blocks fill all of them
+    void *p[SLOTS] = {};
     int n = 0;
     template <typename T>
     int get(T **out, uint64_t count, const char *what) {
+        if (n == SLOTS) return dcn_fail(DCN_ERR_INTERNAL, std::string("no scratch slot left for ") + what);
         DCN_TRY(dcn_impl::dev_alloc(out, count, what));
         p[n++] = *out;
         return DCN_OK;

@@ -559,3 +559,30 @@ struct dcn_indel_strand_args {
     uint32_t *count_reverse;           // per site, zero before
 };
 int dcn_launch_indel_strand(const dcn_indel_strand_args &args, hipStream_t stream);
+
+// ---- reference blocks (blocks.hip, blocks_api.hip; the shared rule is in dcn_blocks.h) --------------------------------
+struct dcn_blocks_args {
+    const uint32_t *counters, *sums; // the map's pileup and its quality sums
+    uint64_t bases;
+    const uint32_t *t_packed, *t_invmask; // the store
+    uint64_t base0, n;                    // the range: store bases [base0, base0 + n)
+    uint64_t pos0;                        // ... and the record position of its first base
+    uint32_t ploidy, min_depth, min_gq, min_qual, err_centi, het_centi;
+    uint64_t edges_lo, edges_hi; // dcn_blk_edges
+    // per position of the range, each behind a pad of dcn_blocks_pad(base0) bytes, dcn_blocks_out_bytes each; the bytes of
+    // the pad and behind the range are DCN_BLK_VARIANT in cls
+    uint8_t *cls, *gq;
+    const uint64_t *breaks; // positions of the range, relative to its first
+    uint64_t n_breaks;
+    uint32_t *block_counts;        // heads per workgroup (the counting pass)
+    const uint64_t *block_offsets; // their scan (the reducing pass)
+    void *blocks;                  // dcn_reference_block per head, filled by dcn_launch_blocks_fill before the reducing pass
+    uint64_t n_blocks;
+};
+uint32_t dcn_blocks_groups(uint64_t base0, uint64_t n);    // workgroups of a range
+uint64_t dcn_blocks_pad(uint64_t base0);                   // bytes in front of the range's first in args.cls and args.gq
+uint64_t dcn_blocks_out_bytes(uint64_t base0, uint64_t n); // bytes of args.cls and of args.gq
+int dcn_launch_blocks_classify(const dcn_blocks_args &args, hipStream_t stream);
+int dcn_launch_blocks_breaks(const dcn_blocks_args &args, hipStream_t stream);
+int dcn_launch_blocks_heads(const dcn_blocks_args &args, bool reduce, hipStream_t stream);
+int dcn_launch_blocks_fill(const dcn_blocks_args &args, hipStream_t stream);

@@ -707,6 +707,10 @@ STRAND_QUERY_DTYPE = np.dtype([("pos", np.uint64), ("kind", np.uint32), ("ref_co
 STRAND_SITE_DTYPE = np.dtype([("fwd", np.uint32, (4,)), ("rev", np.uint32, (4,)), ("table", np.uint32, (4,)), ("sb_centi", np.uint32),
                               ("flags", np.uint32), ("reserved", np.uint32, (2,))])
 STRAND_BIAS, STRAND_ONE_SIDED = N.STRAND_BIAS, N.STRAND_ONE_SIDED  # DCN_STRAND_*
+# dcn_reference_block (include/deacon_hip_blocks.h), 40 bytes: what AnchorMap.reference_blocks returns per block
+REFERENCE_BLOCK_DTYPE = np.dtype([("pos", np.uint64), ("sum_depth", np.uint64), ("len", np.uint32), ("min_depth", np.uint32),
+                                  ("max_depth", np.uint32), ("min_gq", np.uint32), ("cls", np.uint32), ("reserved", np.uint32)])
+BLOCK_NO_COVERAGE, BLOCK_UNCALLED, BLOCK_REF, BLOCK_VARIANT = N.BLOCK_NO_COVERAGE, N.BLOCK_UNCALLED, N.BLOCK_REF, N.BLOCK_VARIANT  # DCN_BLOCK_*
 _CIGAR_LETTERS = {N.CIGAR_INS: "I", N.CIGAR_DEL: "D", N.CIGAR_EQUAL: "=", N.CIGAR_DIFF: "X"}
 
 
@@ -827,6 +831,37 @@ class AnchorMap(Index):
             rc, sites = call(int(n_sites.value))
         N.check(rc)
         return gt[:n], gq[:n], sites[:int(n_sites.value)]
+
+    def reference_blocks(self, record, start=0, n=None, breaks=None, gq_edges=(20, 40, 60, 80, 99), ploidy=2, min_depth=3, min_gq=20,
+                         min_qual=20, err_centi=477, het_centi=301):
+        """Rules B1-B9 (the definition of a reference block is in include/deacon_hip_blocks.h) over positions [start, start + n)
+        of a record (n=None: to its end) of a map that keeps quality sums -> (cls np.uint8[n], blocks REFERENCE_BLOCK_DTYPE[]).
+        cls is BLOCK_VARIANT at a genotype site and at every position of `breaks` (record positions inside the range, any
+        order), BLOCK_NO_COVERAGE, BLOCK_UNCALLED, or BLOCK_REF + the number of gq_edges at or under the position's GQ; the
+        blocks are the maximal runs of one class other than BLOCK_VARIANT, in ascending position.  The default edges are a
+        convention, not a measured optimum.  One call with an estimate and, on DCN_ERR_CAPACITY, a second with the size the
+        first reported."""
+        start, n = int(start), self._to_end(record, start) if n is None else int(n)
+        edges = [int(e) for e in gq_edges]
+        if len(edges) > 16 or any(not 0 <= e <= 255 for e in edges):  # (what the struct can carry; which lists are allowed is the library's to say)
+            raise ValueError("gq_edges does not fit dcn_block_params: at most 16 entries of 0..255 (the library allows 15 of 1..99)")
+        p = N.BlockParams(int(ploidy), int(min_depth), int(min_gq), int(min_qual), int(err_centi), int(het_centi), len(edges), 0,
+                          (C.c_uint8 * 16)(*edges))
+        brk = np.ascontiguousarray(np.asarray([] if breaks is None else breaks, dtype=np.uint64).reshape(-1))
+        cls = np.zeros(max(n, 1), np.uint8)
+        n_blocks = C.c_uint64()
+
+        def call(cap):
+            blocks = np.zeros(max(cap, 1), REFERENCE_BLOCK_DTYPE)
+            rc = N.lib().dcn_anchor_map_reference_blocks(self._h, C.byref(p), int(record), start, n, _ptr(brk) if len(brk) else None, len(brk),
+                                                         _ptr(cls), _ptr(blocks) if cap else None, cap, C.byref(n_blocks))
+            return rc, blocks
+
+        rc, blocks = call(n // 64 + 64)
+        if rc == N.DCN_ERR_CAPACITY:
+            rc, blocks = call(int(n_blocks.value))
+        N.check(rc)
+        return cls[:n], blocks[:int(n_blocks.value)]
 
     def duplicates_enable(self):
         """An empty duplicate set on the map (dcn_anchor_map_duplicates_enable; the definition of a duplicate is in
@@ -1519,6 +1554,15 @@ class FilterProcessor(_Context):
         N.check(N.lib().dcn_should_keep_hashes(self._h, _ptr(hashes) if len(hashes) else None, _ptr(hash_offsets),
                                                n_units, C.byref(p), _ptr(keep), _ptr(hits), _ptr(total)))
         return keep[:n_units].astype(bool), hits[:n_units], total[:n_units]
+
+
+def merge_blocks(blocks):
+    """Rule B6 (dcn_reference_blocks_merge; host only): REFERENCE_BLOCK_DTYPE[] in ascending position -> a new array in which
+    touching blocks of one class are one.  Blocks that overlap or are out of order are an error."""
+    out = np.array(blocks, dtype=REFERENCE_BLOCK_DTYPE, copy=True).reshape(-1)
+    kept = C.c_uint64()
+    N.check(N.lib().dcn_reference_blocks_merge(_ptr(out) if len(out) else None, len(out), C.byref(kept)))
+    return out[:int(kept.value)]
 
 
 def stats_allreduce(processors):
