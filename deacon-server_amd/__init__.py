@@ -10,7 +10,8 @@ from .filter import (DEFAULT_KMER_LENGTH, DEFAULT_WINDOW_SIZE, AnchorMap, Placer
                      EXTENSION_DTYPE, INSERTION_DTYPE, INSERTION_ALLELE_DTYPE, INSERTION_FRONT, INSERTION_REVERSE,
                      GENOTYPE_SITE_DTYPE, GENOTYPE_NONE, GENOTYPES, DELETION_DTYPE, INDEL_SITE_DTYPE, LEFT_ALIGN_INFO_DTYPE, DELETION_REVERSE,
                      INDEL_DELETION, INDEL_FRONT, STRAND_QUERY_DTYPE, STRAND_SITE_DTYPE, STRAND_BIAS, STRAND_ONE_SIDED,
-                     REFERENCE_BLOCK_DTYPE, BLOCK_NO_COVERAGE, BLOCK_UNCALLED, BLOCK_REF, BLOCK_VARIANT, merge_blocks)
+                     REFERENCE_BLOCK_DTYPE, BLOCK_NO_COVERAGE, BLOCK_UNCALLED, BLOCK_REF, BLOCK_VARIANT, merge_blocks,
+                     PHASE_SITE_DTYPE, PHASE_RESULT_DTYPE, PHASE_HEAD, PHASE_JOINED)
 
 __all__ = ["DeaconHipError", "build", "declared_symbols", "Index", "IndexBuilder", "IndexSet", "Classifier", "Locator", "DepthTracker", "AnchorMap", "Placer", "FilterProcessor", "PinnedBuffer", "PendingBatch", "concat_reads",
            "pack_ascii", "stats_allreduce", "set_minimizer_variant", "get_minimizer_variant",
@@ -20,4 +21,5 @@ __all__ = ["DeaconHipError", "build", "declared_symbols", "Index", "IndexBuilder
            "EXTENSION_DTYPE", "INSERTION_DTYPE", "INSERTION_ALLELE_DTYPE", "INSERTION_FRONT", "INSERTION_REVERSE",
            "GENOTYPE_SITE_DTYPE", "GENOTYPE_NONE", "GENOTYPES", "DELETION_DTYPE", "INDEL_SITE_DTYPE", "LEFT_ALIGN_INFO_DTYPE", "DELETION_REVERSE",
            "INDEL_DELETION", "INDEL_FRONT", "STRAND_QUERY_DTYPE", "STRAND_SITE_DTYPE", "STRAND_BIAS", "STRAND_ONE_SIDED",
-           "REFERENCE_BLOCK_DTYPE", "BLOCK_NO_COVERAGE", "BLOCK_UNCALLED", "BLOCK_REF", "BLOCK_VARIANT", "merge_blocks"]
+           "REFERENCE_BLOCK_DTYPE", "BLOCK_NO_COVERAGE", "BLOCK_UNCALLED", "BLOCK_REF", "BLOCK_VARIANT", "merge_blocks",
+           "PHASE_SITE_DTYPE", "PHASE_RESULT_DTYPE", "PHASE_HEAD", "PHASE_JOINED"]

@@ -530,8 +530,25 @@ _BLOCK_SIGNATURES = {
     "dcn_reference_blocks_merge": (C.c_int, [_vp, C.c_uint64, _u64p]),
 }
 
+# ... and those of include/deacon_hip_phase.h (ABI 1.25), likewise
+PHASE_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "deacon_hip_phase.h")
+_PHASE_SIGNATURES = {
+    "dcn_anchor_map_phase_sites": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "dcn_anchor_map_phase_info": (C.c_int, [_vp, _vp]),
+    "dcn_phase_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _u64p]),
+    "dcn_anchor_map_phase_links": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
+    "dcn_anchor_map_phase_solve": (C.c_int, [_vp, _vp, _vp]),
+}
+
+
+class PhaseParams(C.Structure):  # dcn_phase_params of include/deacon_hip_phase.h, 16 bytes
+    _fields_ = [("min_reads", C.c_uint32), ("max_minor_permille", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+PHASE_HEAD, PHASE_JOINED = 1, 2  # DCN_PHASE_*: the flags of a dcn_phase_result
+
 _lib = None
-ABI = (1, 24)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
+ABI = (1, 25)  # DCN_ABI_MAJOR, the DCN_ABI_MINOR these signatures need
 
 
 def lib():
@@ -544,7 +561,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with __graft_entry__.build() "
             "(make -C deacon-server_amd/csrc). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + list(_PHASE_SIGNATURES.items()):
         f = getattr(L, name)  # AttributeError if the library does not export a declared symbol
         f.restype = res
         f.argtypes = args

@@ -67,6 +67,7 @@
 #include "parallel_gzip.hpp"
 #include "deacon_hip.hpp"
 #include "deacon_hip_blocks.h"
+#include "deacon_hip_phase.h"
 
 namespace {
 
@@ -3864,6 +3865,12 @@ struct MapArgs {
     bool gvcf = false, has_gvcf = false, has_callable = false;
     std::string gvcf_out, callable;
     std::vector<unsigned> gq_bands = {20, 40, 60, 80, 99}; // (checked by the library, whose errors the tool passes on)
+    // `phase`: gvcf, with a second pass over the reads once the heterozygous SNV sites are known (dcn_anchor_map_phase_sites,
+    // dcn_phase_batch, dcn_anchor_map_phase_solve): a heterozygous SNV line in a set of two or more sites gets g1|g2 and PS;
+    // gvcf and all it sets are set
+    bool phase = false, has_phase_sets = false, has_links = false;
+    unsigned min_link_reads = 2, max_link_minor = 200;
+    std::string phase_sets, links;
 };
 
 // one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
@@ -3913,14 +3920,14 @@ void append_paf(std::string &rows, const std::string &read_name, uint32_t read_l
 int run_map(const MapArgs &a) {
     const Stopwatch watch;
     const auto no_qualities = [&a](const std::string &name) {
-        die(std::string(a.gvcf ? "gvcf" : a.strand ? "strand" : a.normalize ? "normalize" : a.indels ? "indels" : a.markdup ? "markdup" : a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
+        die(std::string(a.phase ? "phase" : a.gvcf ? "gvcf" : a.strand ? "strand" : a.normalize ? "normalize" : a.indels ? "indels" : a.markdup ? "markdup" : a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
     };
     std::unique_ptr<FastxReader> reads; // (`call` looks at the first record before the reference is loaded)
     if (a.call) {
         if (a.ref.empty()) die("the following required arguments were not provided: <REF>");
-        if (a.genotype && !a.has_fasta && !a.has_variants && !a.has_pileup_out && !a.has_sites && !a.has_vcf && !a.has_summary && !a.has_duplicates && !a.has_gvcf && !a.has_callable)
+        if (a.genotype && !a.has_fasta && !a.has_variants && !a.has_pileup_out && !a.has_sites && !a.has_vcf && !a.has_summary && !a.has_duplicates && !a.has_gvcf && !a.has_callable && !a.has_phase_sets && !a.has_links)
             die(std::string("nothing to write: give at least one of -o <OUTPUT>, --variants <FILE>, --pileup <FILE>, --sites <FILE>, --vcf <FILE>, ") +
-                (a.gvcf ? "--gvcf <FILE>, --callable <FILE>, " : "") + (a.markdup ? "--duplicates <FILE>, " : "") + "-s <SUMMARY>");
+                (a.gvcf ? "--gvcf <FILE>, --callable <FILE>, " : "") + (a.phase ? "--phase-sets <FILE>, --links <FILE>, " : "") + (a.markdup ? "--duplicates <FILE>, " : "") + "-s <SUMMARY>");
         reads.reset(new FastxReader(a.input));
         std::string name;
         if (reads->begins_with_fasta(&name)) no_qualities(name);
@@ -3989,7 +3996,11 @@ int run_map(const MapArgs &a) {
     std::vector<uint32_t> edits, cigar;
     std::vector<uint64_t> cigar_off;
     std::string rows;
-    for_each_batch(rd, b, R.batch_bases, R.batch_reads, [&] {
+    // (`phase`) the second pass: the same batches, the same rows, the same duplicate marking, and dcn_phase_batch in the pileup
+    // call's place; nothing is counted or written a second time
+    bool second_pass = false;
+    uint64_t rows_linking = 0;
+    const auto on_batch = [&] {
         const uint32_t n_reads = (uint32_t)b.recs.size();
         ctx.fit(b.offsets.back());
         place_off.assign((size_t)n_reads + 1, 0);
@@ -4008,7 +4019,7 @@ int run_map(const MapArgs &a) {
         }
         const dcn_split_placement *const use = a.extend ? xpl.data() : pl.data(); // the rows of verify, align and pileup
         const bool aligns = a.align || (a.extend && a.has_output);
-        if (aligns) { // the same reads, the rows just placed: their distances and the runs of the verified ones
+        if (aligns && !second_pass) { // the same reads, the rows just placed: their distances and the runs of the verified ones
             edits.resize(place_off[n_reads]);
             cigar_off.assign(place_off[n_reads] + 1, 0);
             for (int attempt = 0;; ++attempt) {
@@ -4020,7 +4031,7 @@ int run_map(const MapArgs &a) {
                 }
                 cigar.resize(cigar_off[place_off[n_reads]]); // (the size the first call reported)
             }
-        } else if (a.extend && !piles) { // (neither output: the distances of the extended rows, for the summary)
+        } else if (a.extend && !piles && !second_pass) { // (neither output: the distances of the extended rows, for the summary)
             edits.resize(place_off[n_reads]);
             deacon::check(dcn_verify_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), use,
                                            place_off[n_reads], edits.data()));
@@ -4030,7 +4041,7 @@ int run_map(const MapArgs &a) {
             into.resize(place_off[n_reads]);
             chosen.assign(use, use + (ptrdiff_t)place_off[n_reads]);
             for (dcn_split_placement &p : chosen) {
-                if (p.mapq >= a.min_mapq && (a.all_ranks || p.rank == 0)) ++rows_selected;
+                if (p.mapq >= a.min_mapq && (a.all_ranks || p.rank == 0)) rows_selected += !second_pass;
                 else p.record = UINT32_MAX;
             }
             if (a.markdup) { // the selected rows' ends against every read so far: one call per batch, so an ordinal is a read's number
@@ -4041,7 +4052,7 @@ int run_map(const MapArgs &a) {
                 dup_rows.clear();
                 for (uint32_t r = 0; r < n_reads; ++r) {
                     if (!dup_flags[r]) continue;
-                    if (a.has_duplicates) { // rule D3's end, from the read's first selected row
+                    if (a.has_duplicates && !second_pass) { // rule D3's end, from the read's first selected row
                         uint64_t q = place_off[r];
                         while (chosen[q].record == UINT32_MAX) ++q;
                         const dcn_split_placement &p = chosen[q];
@@ -4053,7 +4064,7 @@ int run_map(const MapArgs &a) {
                     if (!a.keep_duplicates)
                         for (uint64_t q = place_off[r]; q < place_off[r + 1]; ++q) chosen[q].record = UINT32_MAX;
                 }
-                if (a.has_duplicates) dup_out.write(dup_rows);
+                if (a.has_duplicates && !second_pass) dup_out.write(dup_rows);
             }
             uint64_t added = 0;
             if (a.call) {
@@ -4062,6 +4073,13 @@ int run_map(const MapArgs &a) {
                     const Rec &rec = b.recs[r];
                     if (rec.qual_off == NO_QUAL) no_qualities(std::string(id_token(b, rec)));
                     std::memcpy(quals.data() + b.offsets[r], b.chars() + rec.qual_off, rec.seq_len);
+                }
+                if (second_pass) {
+                    uint64_t linking = 0;
+                    deacon::check(dcn_phase_batch(ctx.p, R.map.p, b.bases.data(), quals.data(), b.offsets.data(), n_reads, &vprm, &qprm,
+                                                  place_off.data(), chosen.data(), place_off[n_reads], into.data(), &linking));
+                    rows_linking += linking;
+                    return;
                 }
                 deacon::check(dcn_pileup_batch_qual(ctx.p, R.map.p, b.bases.data(), quals.data(), b.offsets.data(), n_reads, &vprm, &qprm,
                                                     place_off.data(), chosen.data(), place_off[n_reads], into.data(), &added));
@@ -4126,7 +4144,95 @@ int run_map(const MapArgs &a) {
             }
         }
         if (prints) out.write(rows);
-    });
+    };
+    for_each_batch(rd, b, R.batch_bases, R.batch_reads, on_batch);
+    // (`phase`) between the pile-up and the output: the heterozygous SNV sites of every record from the genotype, a stretch at
+    // a time (a0 the record's base when the genotype holds it, else the lower column); the list set on the map; the duplicate
+    // set emptied and the input read again through the same batch loop, which hands the rows to dcn_phase_batch; the solve.
+    // The counters are still on the map for the output stage below.
+    std::vector<dcn_phase_site> ph_sites;
+    std::vector<dcn_phase_result> ph_res;
+    uint64_t phase_set_count = 0, phased_sites = 0, links_joined = 0, phase_n50 = 0;
+    if (a.phase) {
+        dcn_genotype_params gp = {};
+        gp.ploidy = a.ploidy, gp.min_depth = a.min_depth, gp.min_gq = a.min_gq, gp.min_qual = a.min_qual, gp.err_centi = 477, gp.het_centi = 301;
+        const char *const env = std::getenv("DCN_CLI_STRETCH_BASES");
+        const uint64_t step = env && *env ? std::max<uint64_t>(std::strtoull(env, nullptr, 10), 1) : 1u << 20;
+        std::vector<dcn_genotype_site> gs;
+        for (uint32_t r = 0; r < R.n_records; ++r)
+            for (uint64_t start = 0; start < R.lens[r]; start += step) {
+                const uint64_t n = std::min<uint64_t>(step, R.lens[r] - start);
+                uint64_t n_geno = 0;
+                for (int attempt = 0;; ++attempt) {
+                    const int rc = dcn_anchor_map_genotype(R.map.p, &gp, r, start, n, nullptr, nullptr, gs.data(), gs.size(), &n_geno);
+                    if (rc != DCN_ERR_CAPACITY || attempt) {
+                        deacon::check(rc);
+                        break;
+                    }
+                    gs.resize(n_geno);
+                }
+                for (uint64_t i = 0; i < n_geno; ++i) {
+                    const dcn_genotype_site &g = gs[i];
+                    unsigned x = g.gt, y = 0;
+                    for (y = 0; (y + 1) * (y + 2) / 2 <= g.gt; ++y) {}
+                    x = g.gt - y * (y + 1) / 2;
+                    if (x == y) continue;
+                    dcn_phase_site site = {};
+                    site.pos = g.pos, site.record = r;
+                    site.a0 = (uint8_t)(y == g.ref_code ? y : x); // (x < y: the record's base, else the lower column)
+                    site.a1 = (uint8_t)(y == g.ref_code ? x : y);
+                    ph_sites.push_back(site);
+                }
+            }
+        deacon::check(dcn_anchor_map_phase_sites(R.map.p, ph_sites.data(), ph_sites.size()));
+        if (!ph_sites.empty()) {
+            deacon::check(dcn_anchor_map_duplicates_reset(R.map.p));
+            FastxReader again(a.input);
+            second_pass = true;
+            for_each_batch(again, b, R.batch_bases, R.batch_reads, on_batch);
+            second_pass = false;
+            dcn_phase_params pp = {};
+            pp.min_reads = a.min_link_reads, pp.max_minor_permille = a.max_link_minor;
+            ph_res.resize(ph_sites.size());
+            deacon::check(dcn_anchor_map_phase_solve(R.map.p, &pp, ph_res.data()));
+        }
+        TextOut sets_out, links_out;
+        if (a.has_phase_sets) sets_out.open(a.phase_sets, false), sets_out.write("record\tfirst_pos\tlast_pos\tsites\n");
+        if (a.has_links) links_out.open(a.links, false), links_out.write("record\tpos\tnext_pos\tn00\tn01\tn10\tn11\tjoined\n");
+        std::string set_rows, link_rows;
+        std::vector<uint64_t> spans;
+        for (size_t s = 0; s < ph_sites.size();) {
+            size_t e = s + 1; // the set [s, e)
+            while (e < ph_sites.size() && !(ph_res[e].flags & DCN_PHASE_HEAD)) ++e;
+            if (e - s >= 2) {
+                ++phase_set_count, phased_sites += e - s;
+                spans.push_back(ph_sites[e - 1].pos - ph_sites[s].pos + 1);
+                set_rows += R.names[ph_sites[s].record] + '\t' + std::to_string(ph_sites[s].pos) + '\t' + std::to_string(ph_sites[e - 1].pos) + '\t' +
+                            std::to_string(e - s) + '\n';
+            }
+            s = e;
+        }
+        for (size_t s = 0; s + 1 < ph_sites.size(); ++s) {
+            links_joined += (ph_res[s].flags & DCN_PHASE_JOINED) != 0;
+            if (ph_sites[s + 1].record != ph_sites[s].record) continue;
+            link_rows += R.names[ph_sites[s].record] + '\t' + std::to_string(ph_sites[s].pos) + '\t' + std::to_string(ph_sites[s + 1].pos);
+            for (int c = 0; c < 4; ++c) link_rows += '\t' + std::to_string(ph_res[s].link[c]);
+            link_rows += (ph_res[s].flags & DCN_PHASE_JOINED) ? "\t1\n" : "\t0\n";
+        }
+        std::sort(spans.begin(), spans.end(), std::greater<uint64_t>());
+        uint64_t total = 0, sum = 0;
+        for (uint64_t v : spans) total += v;
+        for (uint64_t v : spans) {
+            sum += v;
+            if (2 * sum >= total) {
+                phase_n50 = v;
+                break;
+            }
+        }
+        if (a.has_phase_sets) sets_out.write(set_rows), sets_out.finish();
+        if (a.has_links) links_out.write(link_rows), links_out.finish();
+    }
+    size_t ph_cursor = 0; // the next site of the list: the output stage meets them in the list's order
     // pileup: the counters of every record, a stretch at a time, as TSV; the sites of the same stretches
     uint64_t covered = 0, n_sites = 0, column_sum[DCN_PILEUP_COLUMNS] = {};
     uint64_t insertion_events = 0, inserted_bases = 0, insertion_alleles = 0, substitutions = 0, deleted_positions = 0, consensus_bases = 0,
@@ -4169,6 +4275,7 @@ int run_map(const MapArgs &a) {
                 head += "##FORMAT=<ID=ADF,Number=R,Type=Integer,Description=\"AD on the forward strand\">\n"
                         "##FORMAT=<ID=ADR,Number=R,Type=Integer,Description=\"AD on the reverse strand\">\n";
             head += "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods, at most 255\">\n";
+            if (a.phase) head += "##FORMAT=<ID=PS,Number=1,Type=Integer,Description=\"Phase set: POS of the first site of the set the genotype is phased in\">\n";
             vcf_head = head;
             head += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + a.sample + "\n";
             if (a.has_vcf) vcf_write(head);
@@ -4431,14 +4538,28 @@ int run_map(const MapArgs &a) {
                         if (y != g.ref_code && y != x) alleles[n_alleles++] = y;
                         const auto index_of = [&](unsigned c) { return c == alleles[0] ? 0u : c == alleles[1] ? 1u : 2u; };
                         const auto pair_index = [](unsigned p, unsigned q2) { return p <= q2 ? q2 * (q2 + 1) / 2 + p : p * (p + 1) / 2 + q2; };
+                        // (`phase`) the site's entry of the list, when the line is heterozygous and its set has two sites or more
+                        const dcn_phase_result *ph = nullptr;
+                        size_t ph_at = 0;
+                        if (a.phase && x != y) {
+                            while (ph_cursor < ph_sites.size() &&
+                                   (ph_sites[ph_cursor].record < r || (ph_sites[ph_cursor].record == r && ph_sites[ph_cursor].pos < g.pos)))
+                                ++ph_cursor;
+                            if (ph_cursor < ph_res.size() && ph_sites[ph_cursor].record == r && ph_sites[ph_cursor].pos == g.pos &&
+                                ((ph_res[ph_cursor].flags & DCN_PHASE_JOINED) || !(ph_res[ph_cursor].flags & DCN_PHASE_HEAD)))
+                                ph = &ph_res[ph_cursor], ph_at = ph_cursor;
+                        }
                         vcf_rows += R.names[r] + '\t' + std::to_string(g.pos + 1) + "\t.\t" + "ACGT"[g.ref_code] + '\t';
                         for (unsigned k = 1; k < n_alleles; ++k) vcf_rows += std::string(k > 1 ? "," : "") + "ACGT"[alleles[k]];
                         if (a.strand)
                             vcf_rows += '\t' + std::to_string(g.qual) + '\t' + strand_filter(snv_strand[i]) + "\tDP=" + std::to_string(g.depth) +
-                                        ";SB=" + strand_sb(snv_strand[i]) + "\tGT:GQ:DP:AD:ADF:ADR:PL\t";
+                                        ";SB=" + strand_sb(snv_strand[i]) + (ph ? "\tGT:GQ:DP:AD:ADF:ADR:PL:PS\t" : "\tGT:GQ:DP:AD:ADF:ADR:PL\t");
                         else
                             vcf_rows += '\t' + std::to_string(g.qual) + "\tPASS\tDP=" + std::to_string(g.depth) + "\tGT:GQ:DP:AD:PL\t";
-                        if (a.ploidy == 2) vcf_rows += std::to_string(std::min(index_of(x), index_of(y))) + '/' + std::to_string(std::max(index_of(x), index_of(y)));
+                        if (ph) { // haplotype 1 carries a[hap], haplotype 2 a[1 - hap] (rule H6)
+                            const unsigned al[2] = {ph_sites[ph_at].a0, ph_sites[ph_at].a1};
+                            vcf_rows += std::to_string(index_of(al[ph->hap & 1u])) + '|' + std::to_string(index_of(al[1u - (ph->hap & 1u)]));
+                        } else if (a.ploidy == 2) vcf_rows += std::to_string(std::min(index_of(x), index_of(y))) + '/' + std::to_string(std::max(index_of(x), index_of(y)));
                         else vcf_rows += std::to_string(index_of(x));
                         vcf_rows += ':' + std::to_string(g.gq) + ':' + std::to_string((uint64_t)g.ad[0] + g.ad[1] + g.ad[2] + g.ad[3]) + ':';
                         for (unsigned k = 0; k < n_alleles; ++k) vcf_rows += (k ? "," : "") + std::to_string(g.ad[alleles[k]]);
@@ -4456,6 +4577,7 @@ int run_map(const MapArgs &a) {
                                 vcf_rows += (first ? "" : ",") + std::to_string(g.pl[at]);
                                 first = false;
                             }
+                        if (ph) vcf_rows += ':' + std::to_string(ph->set_pos + 1);
                         vcf_rows += '\n';
                     }
                     if (a.indels) { // rules I1-I8 over the stretch: the INDEL lines, merged into the SNV lines by POS, the SNV line of a POS first
@@ -4667,6 +4789,10 @@ int run_map(const MapArgs &a) {
             std::fprintf(stderr, "Cut %llu bases into %llu reference blocks (%llu bases reference, %llu not called, %llu without coverage)\n",
                          (unsigned long long)record_bases, (unsigned long long)n_blocks, (unsigned long long)ref_bases, (unsigned long long)uncalled_bases,
                          (unsigned long long)no_coverage_bases);
+        if (a.phase)
+            std::fprintf(stderr, "Phased %llu of %llu heterozygous SNV sites in %llu sets (%llu links joined, %llu placements linking)\n",
+                         (unsigned long long)phased_sites, (unsigned long long)ph_sites.size(), (unsigned long long)phase_set_count,
+                         (unsigned long long)links_joined, (unsigned long long)rows_linking);
         if (a.verify && !a.pileup)
             std::fprintf(stderr, "Verified %llu of %llu placements (%llu edits over %llu bases)\n", (unsigned long long)verified,
                          (unsigned long long)placements, (unsigned long long)edits_sum, (unsigned long long)verified_bases);
@@ -4761,6 +4887,11 @@ int run_map(const MapArgs &a) {
             for (size_t b = 0; b < a.gq_bands.size(); ++b) appendf(js, "%s%u", b ? ", " : "", a.gq_bands[b]);
             js += "],\n";
         }
+        if (a.phase)
+            appendf(js, "  \"min_link_reads\": %u,\n  \"max_link_minor\": %u,\n  \"phase_sites\": %llu,\n  \"phase_sets\": %llu,\n"
+                        "  \"phased_sites\": %llu,\n  \"links_joined\": %llu,\n  \"rows_linking\": %llu,\n  \"phase_set_n50\": %llu,\n",
+                    a.min_link_reads, a.max_link_minor, (unsigned long long)ph_sites.size(), (unsigned long long)phase_set_count,
+                    (unsigned long long)phased_sites, (unsigned long long)links_joined, (unsigned long long)rows_linking, (unsigned long long)phase_n50);
         appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
         for (uint32_t r = 0; r < R.n_records; ++r) {
             js += (r ? ",\n    {" : "\n    {");
@@ -4918,6 +5049,7 @@ void usage() {
                  "  normalize  As indels, with every read's gaps left-aligned first: an indel in a repeat stands at its near end\n"
                  "  strand  As normalize, with per-allele strand counts: FILTER strand_bias / one_strand, SB, ADF and ADR in the VCF\n"
                  "  gvcf    As strand, with reference blocks between the VCF's lines (a gVCF) and a BED of callable regions\n"
+                 "  phase   As gvcf, with a second pass over the reads: heterozygous SNV lines that reads link get 0|1 and PS\n"
                  "  server  Hold a pre-loaded minimizer index on the GPU for filtering with the client command\n"
                  "  client  Alternate version of filter: minimizers computed here, the index held by a server\n\n"
                  "Options:\n  -h, --help     Print help\n  -V, --version  Print version\n");
@@ -5553,7 +5685,7 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "optical-distance rule; nothing is read from the bases or the qualities.  Mates are independent here: one input,\n"
                "and a read is a unit.  Pairs as units (one key from both mates' ends) are a feature of the library\n"
                "(dcn_mark_duplicates_batch) and of the Python layer (AnchorMap.mark_duplicates), not of this mode.\n";
-    else if (sub == "indels" || sub == "normalize" || sub == "strand" || sub == "gvcf") // (gvcf: strand's, likewise)
+    else if (sub == "indels" || sub == "normalize" || sub == "strand" || sub == "gvcf" || sub == "phase") // (gvcf: strand's, likewise)
         // (normalize: indels' text with another head and a paragraph more, below; strand: normalize's likewise)
         text = "Mark duplicates, pile up and genotype as markdup does, keep the deleted runs beside the inserted bases, and give the\n"
                "insertion and the deletion most reads carry at a position a genotype of their own: INDEL lines in the VCF\n\n"
@@ -5794,11 +5926,11 @@ bool subcommand_help(const std::vector<std::string> &args) {
                "  compare    Report how many minimizers 2 to 32 indexes share, pair by pair\n"
                "  select     Keep the minimizers of several indexes chosen by which of the indexes hold them\n";
     if (!text) return false;
-    if (sub == "normalize" || sub == "strand" || sub == "gvcf") { // every option of indels keeps its text
-        const bool gvcf = sub == "gvcf", strand = sub == "strand" || gvcf;
+    if (sub == "normalize" || sub == "strand" || sub == "gvcf" || sub == "phase") { // every option of indels keeps its text
+        const bool phase = sub == "phase", gvcf = sub == "gvcf" || phase, strand = sub == "strand" || gvcf;
         std::string t = text;
         t.erase(0, t.find("Usage: deacon-hip indels"));
-        t.replace(0, std::strlen("Usage: deacon-hip indels"), gvcf ? "Usage: deacon-hip gvcf" : strand ? "Usage: deacon-hip strand" : "Usage: deacon-hip normalize");
+        t.replace(0, std::strlen("Usage: deacon-hip indels"), phase ? "Usage: deacon-hip phase" : gvcf ? "Usage: deacon-hip gvcf" : strand ? "Usage: deacon-hip strand" : "Usage: deacon-hip normalize");
         if (strand) { // the three options of the mode, behind indels' own two
             const std::string at = "      --min-indel-count <N>";
             const size_t line_end = t.find('\n', t.find(at));
@@ -5817,8 +5949,20 @@ bool subcommand_help(const std::vector<std::string> &args) {
                          "                                 15, each 1..99) [default: 20,40,60,80,99, a convention]\n"
                          "      --callable <FILE>          BED: record start end label, the label NO_COVERAGE, LOW_CONFIDENCE or CALLABLE;\n"
                          "                                 the intervals tile every record\n");
+            if (phase) // ... and the four of this mode behind those
+                t.insert(t.find('\n', t.find("                                 the intervals tile every record")) + 1,
+                         "      --min-link-reads <N>       Reads a link between two neighbouring heterozygous sites needs to join them\n"
+                         "                                 [default: 2, a convention]\n"
+                         "      --max-link-minor <N>       The most, in thousandths of a link's reads, that may show the rarer of the two\n"
+                         "                                 arrangements for the link to join (0..1000) [default: 200, a convention]\n"
+                         "      --phase-sets <FILE>        TSV: record first_pos last_pos sites, a line per phase set of two sites or more\n"
+                         "                                 (positions 0-based, as --sites)\n"
+                         "      --links <FILE>             TSV: record pos next_pos n00 n01 n10 n11 joined, a line per pair of neighbouring\n"
+                         "                                 heterozygous SNV sites of one record\n");
         }
-        t = std::string(gvcf ? "Mark duplicates, left-align, pile up and genotype as strand does, and say of every other position what the reads\n"
+        t = std::string(phase ? "Mark duplicates, left-align, pile up, genotype and cut into reference blocks as gvcf does, then read the input a\n"
+                                "second time to see which alleles of neighbouring heterozygous sites lie on the same reads: phased genotypes\n\n"
+                        : gvcf ? "Mark duplicates, left-align, pile up and genotype as strand does, and say of every other position what the reads\n"
                                "say there: reference blocks between the VCF's lines (a gVCF) and a BED of callable regions\n\n"
                         : strand ? "Mark duplicates, left-align, pile up and genotype as normalize does, with the reverse reads counted per allele as\n"
                                  "well: every VCF line says on which strands its alleles were seen, and whether that looks like an artefact\n\n"
@@ -5871,6 +6015,23 @@ bool subcommand_help(const std::vector<std::string> &args) {
                  "joins neighbours of one label.  -s gains blocks, block_bases, variant_positions, no_coverage_bases, uncalled_bases,\n"
                  "ref_bases, ref_bases_by_band and gq_bands.  One sample; no joint calling.  Without the three options every output\n"
                  "is strand's, byte for byte.\n";
+        if (phase)
+            t += "\nPhase: once the pile-up is complete the heterozygous SNV sites of the genotype are listed (allele 0 the record's\n"
+                 "base when the genotype holds it, else the lower of A C G T), the duplicate set is emptied and READS is read again:\n"
+                 "the same batches, the same duplicate marking, --min-baseq and left alignment, so every placement shows at each\n"
+                 "listed site the base the pile-up counted for it.  A placement that shows one of the two alleles at two\n"
+                 "neighbouring sites adds one to that pair's link: n00 n01 n10 n11 by the allele at the first and at the second\n"
+                 "site; a site where it shows another base, an N, a base under --min-baseq or a deletion links to neither side.\n"
+                 "A link joins its sites when it has --min-link-reads reads, cis (n00 + n11) and trans (n01 + n10) differ, and the\n"
+                 "rarer of the two is at most --max-link-minor thousandths of all; joined links chain sites into phase sets.  A\n"
+                 "heterozygous SNV line in a set of two sites or more gets GT g1|g2, the allele of haplotype 1 first, and PS, the\n"
+                 "POS of the set's first site, behind PL in FORMAT; every other line is gvcf's, byte for byte, and the header\n"
+                 "gains one line, ##FORMAT PS.  Which haplotype is called 1 is arbitrary per set.  -s gains min_link_reads,\n"
+                 "max_link_minor, phase_sites, phase_sets, phased_sites, links_joined, rows_linking and phase_set_n50 (of the\n"
+                 "sets' spans in bases).  READS is read twice, so it cannot be stdin; --ploidy 1 has nothing to phase.  Limits:\n"
+                 "links between neighbouring sites only, so a false heterozygous site between two true ones splits a set; none\n"
+                 "across the placements of one read or across mates; SNV sites only, INDEL lines stay unphased; no per-read\n"
+                 "haplotype tags.\n";
         std::fputs(t.c_str(), stdout);
         return true;
     }
@@ -6044,11 +6205,13 @@ int main(int argc, char **argv) {
             return run_place(a);
         }
         if (args[0] == "map" || args[0] == "verify" || args[0] == "align" || args[0] == "pileup" || args[0] == "extend" || args[0] == "consensus" ||
-            args[0] == "call" || args[0] == "genotype" || args[0] == "markdup" || args[0] == "indels" || args[0] == "normalize" || args[0] == "strand" || args[0] == "gvcf") {
+            args[0] == "call" || args[0] == "genotype" || args[0] == "markdup" || args[0] == "indels" || args[0] == "normalize" || args[0] == "strand" || args[0] == "gvcf" ||
+            args[0] == "phase") {
             MapArgs a;
             a.align = args[0] == "align";
             a.pileup = args[0] == "pileup";
-            a.gvcf = args[0] == "gvcf";
+            a.phase = args[0] == "phase";
+            a.gvcf = args[0] == "gvcf" || a.phase;
             a.strand = args[0] == "strand" || a.gvcf;
             a.normalize = args[0] == "normalize" || a.strand;
             a.indels = args[0] == "indels" || a.normalize;
@@ -6091,6 +6254,10 @@ int main(int argc, char **argv) {
                 else if (a.strand && s == "--min-strand-depth") a.min_strand_depth = (unsigned)number(need(++i), "--min-strand-depth", 0, 0xFFFFFFFFll);
                 else if (a.gvcf && s == "--gvcf") a.gvcf_out = need(++i), a.has_gvcf = true;
                 else if (a.gvcf && s == "--callable") a.callable = need(++i), a.has_callable = true;
+                else if (a.phase && s == "--min-link-reads") a.min_link_reads = (unsigned)number(need(++i), "--min-link-reads", 0, 0xFFFFFFFFll);
+                else if (a.phase && s == "--max-link-minor") a.max_link_minor = (unsigned)number(need(++i), "--max-link-minor", 0, 1000);
+                else if (a.phase && s == "--phase-sets") a.phase_sets = need(++i), a.has_phase_sets = true;
+                else if (a.phase && s == "--links") a.links = need(++i), a.has_links = true;
                 else if (a.gvcf && s == "--gq-bands") { // comma-separated numbers; which lists are allowed is the library's to say
                     a.gq_bands.clear();
                     const std::string list = need(++i);
@@ -6127,6 +6294,9 @@ int main(int argc, char **argv) {
             if (pos.size() > 0) a.ref = pos[0];
             if (pos.size() > 1) a.input = pos[1];
             if (pos.size() > 2) die(args[0] + " takes one input: mates are independent here, run it once per file (unexpected argument '" + pos[2] + "')");
+            if (a.phase && a.ploidy == 1) die("phase needs --ploidy 2: a haploid genotype has no heterozygous site to phase");
+            if (a.phase && !a.ref.empty() && a.input == "-")
+                die("phase reads its input twice (the pile-up, then the links between the sites that were found): give a file, not stdin");
             return run_map(a);
         }
         if (args[0] == "map-pairs") {

@@ -449,6 +449,7 @@ extern "C" int dcn_index_clone(const dcn_index *index, int device, dcn_index **o
     idx->d_pileup_qsums = nullptr; // ... nor quality sums
     idx->d_pileup_strands = nullptr; // ... nor strand planes
     idx->dups = nullptr; // ... nor a duplicate set
+    idx->phase = nullptr; // ... nor phase sites
     const uint64_t bytes = idx->n_groups * DCN_GROUP_SLOTS * sizeof(uint64_t);
     // Another GPU: the keys cross the link, not the table (a tenth of the bytes at the default 8 slots per key; dcn_table_clone_by_keys).
     // The same GPU: a device-to-device copy of the table at HBM's pace.  DCN_CLONE_BY_KEYS=1 / DCN_CLONE_BY_COPY=1 force one form
@@ -508,6 +509,7 @@ extern "C" void dcn_index_destroy(dcn_index *index) {
     if (index->d_pileup_qsums) hipFree(index->d_pileup_qsums);
     if (index->d_pileup_strands) hipFree(index->d_pileup_strands);
     dcn_dup_set_free(index->dups);
+    dcn_phase_list_free(index->phase);
     delete index;
 }
 

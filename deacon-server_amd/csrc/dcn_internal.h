@@ -88,6 +88,8 @@ struct dcn_del_ledger; // (dcn_verify.h)
 void dcn_del_ledger_free(dcn_del_ledger *l);
 struct dcn_dup_set; // (dcn_verify.h)
 void dcn_dup_set_free(dcn_dup_set *d);
+struct dcn_phase_list; // (dcn_verify.h)
+void dcn_phase_list_free(dcn_phase_list *l);
 
 struct dcn_index {
     // captured when the index is created (built, loaded, merged, cloned): the rule its keys were selected by travels
@@ -143,6 +145,9 @@ struct dcn_index {
     // ... and the duplicate set (dcn_anchor_map_duplicates_enable, duplicates_api.hip), which needs neither the bases nor
     // the pileup.  Null: none is kept.
     dcn_dup_set *dups = nullptr;
+    // ... and the phase site list with its links (dcn_anchor_map_phase_sites, phase_api.hip), which needs the bases and no
+    // pileup.  Null: none is set.
+    dcn_phase_list *phase = nullptr;
     dcn_table_view view() const {
         dcn_table_view v;
         v.slots = d_slots;

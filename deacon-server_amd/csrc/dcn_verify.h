@@ -283,6 +283,48 @@ int check_strands(const dcn_index *map);
 } // namespace dcn_pile_api
 #pragma GCC visibility pop
 
+// ---- phase (phase.hip, phase_api.hip; the shared arithmetic is in dcn_phase.h) -----------------------------------------
+// The site list of a map (dcn_anchor_map_phase_sites, rule H1) and the links over it, all on the device: per site its
+// base-store position (ascending: the store's records begin in the order they were added), its record position, a byte of
+// alleles (dcn_phase_pack_alleles, and DCN_PHASE_LINK_BIT when link s exists) and the four counters of link s; the two
+// counters of a call (rows that linked, link adds); and on the host rule H1's info, summed over the calls.
+constexpr uint32_t DCN_PHASE_LINK_BIT = 16;
+struct dcn_phase_list {
+    uint64_t n = 0;
+    uint64_t *d_base = nullptr, *d_pos = nullptr;
+    uint8_t *d_alleles = nullptr;
+    uint32_t *d_links = nullptr;
+    unsigned long long *d_call = nullptr;
+    uint64_t rows = 0, rows_linking = 0, link_adds = 0;
+};
+void dcn_phase_list_free(dcn_phase_list *l);
+
+struct dcn_phase_link_args {
+    dcn_pileup_args rows; // the pileup kernel's view of the call's rows; counters and bases are not looked at
+    const uint8_t *quals; // as dcn_pileup_qual_args (the <true> kernel alone reads the three)
+    uint32_t qual_offset, min_base_qual;
+    const uint64_t *site_base;
+    const uint8_t *site_alleles;
+    uint64_t n_sites;
+    uint32_t *links;
+    unsigned long long *call; // [0] += rows that added to a link, [1] += link adds
+};
+int dcn_launch_phase_link(const dcn_phase_link_args &args, bool qual, hipStream_t stream);
+
+struct dcn_phase_elem; // (dcn_phase.h)
+struct dcn_phase_solve_args {
+    const uint64_t *site_pos;
+    const uint8_t *site_alleles;
+    const uint32_t *links;
+    uint64_t n_sites;
+    uint32_t min_reads, max_minor_permille;
+    uint8_t *decisions;         // per site: dcn_phase_decide of link s, 0 where there is none
+    dcn_phase_elem *aggregates; // per workgroup of the scan: its sites' element, then the element of all sites in front
+    void *results;              // dcn_phase_result per site
+};
+uint64_t dcn_phase_solve_blocks(uint64_t n_sites); // workgroups of the scan: entries of `aggregates`
+int dcn_launch_phase_solve(const dcn_phase_solve_args &args, hipStream_t stream);
+
 // ---- genotypes (genotype.hip, genotype_api.hip; the shared arithmetic is in dcn_genotype.h) ---------------------------
 struct dcn_genotype_args {
     const uint32_t *counters, *sums; // the map's pileup and its quality sums

@@ -711,6 +711,12 @@ STRAND_BIAS, STRAND_ONE_SIDED = N.STRAND_BIAS, N.STRAND_ONE_SIDED  # DCN_STRAND_
 REFERENCE_BLOCK_DTYPE = np.dtype([("pos", np.uint64), ("sum_depth", np.uint64), ("len", np.uint32), ("min_depth", np.uint32),
                                   ("max_depth", np.uint32), ("min_gq", np.uint32), ("cls", np.uint32), ("reserved", np.uint32)])
 BLOCK_NO_COVERAGE, BLOCK_UNCALLED, BLOCK_REF, BLOCK_VARIANT = N.BLOCK_NO_COVERAGE, N.BLOCK_UNCALLED, N.BLOCK_REF, N.BLOCK_VARIANT  # DCN_BLOCK_*
+# dcn_phase_site (16 bytes) and dcn_phase_result (32 bytes) of include/deacon_hip_phase.h: what AnchorMap.phase_sites takes and
+# AnchorMap.phase_solve returns per site
+PHASE_SITE_DTYPE = np.dtype([("pos", np.uint64), ("record", np.uint32), ("a0", np.uint8), ("a1", np.uint8), ("reserved", np.uint8, (2,))])
+PHASE_RESULT_DTYPE = np.dtype([("set_pos", np.uint64), ("link", np.uint32, (4,)), ("set_index", np.uint32), ("hap", np.uint8),
+                               ("flags", np.uint8), ("reserved", np.uint8, (2,))])
+PHASE_HEAD, PHASE_JOINED = N.PHASE_HEAD, N.PHASE_JOINED  # DCN_PHASE_*
 _CIGAR_LETTERS = {N.CIGAR_INS: "I", N.CIGAR_DEL: "D", N.CIGAR_EQUAL: "=", N.CIGAR_DIFF: "X"}
 
 
@@ -862,6 +868,45 @@ class AnchorMap(Index):
             rc, blocks = call(int(n_blocks.value))
         N.check(rc)
         return cls[:n], blocks[:int(n_blocks.value)]
+
+    def phase_sites(self, sites):
+        """Rule H1 (dcn_anchor_map_phase_sites; the definition of a phase is in include/deacon_hip_phase.h): the map's list of
+        heterozygous sites, PHASE_SITE_DTYPE[] strictly ascending in (record, pos), a0 != a1 columns of A C G T.  Replaces the
+        list there was and zeroes every link; an empty list (or None) frees it.  The map must keep bases."""
+        sites = np.zeros(0, PHASE_SITE_DTYPE) if sites is None else np.ascontiguousarray(sites)
+        if sites.dtype != PHASE_SITE_DTYPE or sites.ndim != 1:
+            raise ValueError("phase_sites: sites must be a one-dimensional PHASE_SITE_DTYPE array")
+        N.check(N.lib().dcn_anchor_map_phase_sites(self._h, _ptr(sites) if len(sites) else None, len(sites)))
+
+    def phase_info(self):
+        """-> (sites, rows, rows_linking, link_adds): the sites of the list, the counted rows (rule P2) handed to
+        Placer.phase_batch since the list was set, those that added to at least one link, and the link adds"""
+        info = np.zeros(4, np.uint64)
+        N.check(N.lib().dcn_anchor_map_phase_info(self._h, _ptr(info)))
+        return tuple(int(v) for v in info)
+
+    def phase_links(self, first=0, n=None):
+        """the counters of sites [first, first + n) of the list (n=None: to its end) -> np.uint32[n, 4]: n00 n01 n10 n11 of
+        the link from site s to site s + 1 (rule H3), 0 where there is none"""
+        first = int(first)
+        sites = self.phase_info()[0]
+        if first < 0 or first > sites or (n is not None and int(n) < 0):
+            raise ValueError("phase_links: first must lie in 0 .. %d (the sites of the list) and n must not be negative" % sites)
+        n = sites - first if n is None else int(n)
+        out = np.zeros((max(n, 1), 4), np.uint32)
+        N.check(N.lib().dcn_anchor_map_phase_links(self._h, first, n, _ptr(out)))
+        return out[:n]
+
+    def phase_solve(self, min_reads=2, max_minor_permille=200):
+        """Rules H5-H7 over the whole list (dcn_anchor_map_phase_solve) -> PHASE_RESULT_DTYPE[sites]: per site the position
+        of its set's head, the four counters of its link to the next site, the index of its set, its haplotype bit and
+        PHASE_HEAD / PHASE_JOINED.  Haplotype 1 carries allele a[hap]; a set of one site is unphased.  min_reads = 2 and
+        max_minor_permille = 200 are conventions, not measured optima."""
+        p = N.PhaseParams(int(min_reads), int(max_minor_permille), (C.c_uint32 * 2)(0, 0))
+        n = self.phase_info()[0]
+        out = np.zeros(max(n, 1), PHASE_RESULT_DTYPE)
+        N.check(N.lib().dcn_anchor_map_phase_solve(self._h, C.byref(p), _ptr(out)))
+        return out[:n]
 
     def duplicates_enable(self):
         """An empty duplicate set on the map (dcn_anchor_map_duplicates_enable; the definition of a duplicate is in
@@ -1342,6 +1387,43 @@ class Placer(_Context):
                                          C.byref(p), _ptr(row_offsets), _ptr(rows) if n_rows else None, n_rows, _ptr(edits),
                                          C.byref(n_added)))
         return edits[:n_rows], int(n_added.value)
+
+    def phase_batch(self, bases, offsets, rows, row_offsets=None, max_edits=1023, max_permille=200, select=None, quals=None,
+                    min_base_qual=0, qual_offset=33):
+        """pileup_batch's rows looked at once more, at the sites of AnchorMap.phase_sites alone (dcn_phase_batch; the
+        definition of a phase is in include/deacon_hip_phase.h): every row with an alignment adds 1 to a counter of the
+        link between two neighbouring sites when it shows one of the two alleles at both.  Arguments as for pileup_batch,
+        and a row sees the column the pileup counted for it (quals, min_base_qual and the map's left-align switch
+        included).  The map needs no pileup, and none is written.  -> (edits np.uint32[n_rows], n_linking: the rows of this
+        call that added to at least one link)."""
+        bases, offsets, n_reads = _batch(bases, offsets)
+        rows = np.ascontiguousarray(rows)
+        n_rows = len(rows)
+        if quals is not None:
+            if isinstance(quals, (bytes, bytearray, memoryview)):
+                quals = np.frombuffer(quals, np.uint8)
+            if not isinstance(quals, np.ndarray) or quals.dtype != np.uint8 or quals.shape != (len(bases),):
+                raise ValueError("phase_batch: quals must be uint8 or bytes with one byte per base of the batch")
+            quals = np.ascontiguousarray(quals)
+            if len(quals) == 0:
+                quals = None  # (a batch without bases has no quality to look at: the call without Q3)
+        if select is not None:
+            select = np.asarray(select, bool)
+            if select.shape != (n_rows,):
+                raise ValueError("phase_batch: select must hold one boolean per row")
+            rows = rows.copy()
+            rows["record"][~select] = UNPLACED
+        if row_offsets is not None:
+            row_offsets = np.ascontiguousarray(row_offsets, dtype=np.uint64)
+        edits = np.zeros(max(n_rows, 1), np.uint32)
+        n_linking = C.c_uint64()
+        p = N.VerifyParams(int(max_edits), int(max_permille), rows.dtype.itemsize, 0)
+        qp = None if quals is None else N.PileupQualParams(int(qual_offset), int(min_base_qual), (C.c_uint32 * 2)(0, 0))
+        N.check(N.lib().dcn_phase_batch(self._h, self.anchor_map._h, _ptr(bases) if len(bases) else None,
+                                        None if quals is None else _ptr(quals), _ptr(offsets), n_reads, C.byref(p),
+                                        None if qp is None else C.byref(qp), _ptr(row_offsets), _ptr(rows) if n_rows else None, n_rows,
+                                        _ptr(edits), C.byref(n_linking)))
+        return edits[:n_rows], int(n_linking.value)
 
     def extend_batch(self, bases, offsets, rows, row_offsets=None, penalty=6, end_bonus=4, max_edits=1023):
         """Each placement carried over the two flanks of its read, the bases outside its outermost anchor hits

@@ -87,9 +87,10 @@ enum {
  * 1.21 = dcn_anchor_map_pileup_keep_deletions, dcn_anchor_map_deletions_info / _fetch, dcn_anchor_map_indels_genotype.
  * 1.22 = dcn_left_align_batch, dcn_anchor_map_pileup_left_align / _left_align_info.
  * 1.23 = dcn_anchor_map_pileup_keep_strands / _fetch_strands, dcn_anchor_map_strand_evidence, dcn_anchor_map_indels_strand.
- * 1.24 = dcn_anchor_map_reference_blocks, dcn_reference_blocks_merge: declared in deacon_hip_blocks.h, not here. */
+ * 1.24 = dcn_anchor_map_reference_blocks, dcn_reference_blocks_merge: declared in deacon_hip_blocks.h, not here.
+ * 1.25 = dcn_anchor_map_phase_sites / _info / _links / _solve, dcn_phase_batch: declared in deacon_hip_phase.h, not here. */
 #define DCN_ABI_MAJOR 1
-#define DCN_ABI_MINOR 24
+#define DCN_ABI_MINOR 25
 /* What the loaded library was built as: a binding asserts *major == DCN_ABI_MAJOR it was written against and
  * *minor >= the minor it needs, before its first other call (no reference counterpart: the reference is one crate). */
 int dcn_abi_version(uint32_t *major, uint32_t *minor);
