@@ -65,6 +65,7 @@
 #include "fast_deflate.hpp"
 #include "fast_inflate.hpp"
 #include "parallel_gzip.hpp"
+#include "map_text.hpp"
 #include "deacon_hip.hpp"
 #include "deacon_hip_blocks.h"
 #include "deacon_hip_phase.h"
@@ -2938,6 +2939,18 @@ void with_room(std::vector<T> &v, F call) {
     }
     deacon::check(rc);
 }
+// its sibling for a call that sizes two buffers: call(data1, capacity1, data2, capacity2, count1, count2) -> rc, which the
+// library answers with DCN_ERR_CAPACITY exactly when either count is above its capacity; both take the sizes reported
+template <typename T, typename U, typename F>
+void with_room(std::vector<T> &v, std::vector<U> &u, F call) {
+    uint64_t count_v = 0, count_u = 0;
+    int rc = call(v.data(), v.size(), u.data(), u.size(), count_v, count_u);
+    if (rc == DCN_ERR_CAPACITY && (count_v > v.size() || count_u > u.size())) {
+        v.resize(count_v), u.resize(count_u);
+        rc = call(v.data(), v.size(), u.data(), u.size(), count_v, count_u);
+    }
+    deacon::check(rc);
+}
 
 // bases that fill a batch and bases a context holds, or what the test hook `hook` says (many batches, records past the context)
 struct BatchSize {
@@ -3873,57 +3886,253 @@ struct MapArgs {
     std::string phase_sets, links;
 };
 
-// one PAF line: the 12 columns, then cm (votes), rk (rank), np (placements of the read), rv (rival votes), na (anchor
-// hits of the read), ns (positions of the read)
-// (`verify`: edits = what dcn_verify_batch said of the row, and the line gains ve and, for a verified row, NM, with column
-// 10 = column 11 - NM; map passes DCN_VERIFY_UNPLACED, which no placed row has, and prints what it always did)
-// (`align`: cigar = the n_ops runs of a verified row, as dcn_align_batch gives them: column 10 = its '=' bases, column 11 =
-// all its bases, and cg:Z: follows NM)
-void append_paf(std::string &rows, const std::string &read_name, uint32_t read_len, const dcn_split_placement &p,
-                const std::string &record_name, uint32_t record_len, uint32_t k, uint32_t edits = DCN_VERIFY_UNPLACED,
-                const uint32_t *cigar = nullptr, uint64_t n_ops = 0, const std::string &more_tags = std::string()) {
-    const uint64_t on_read = p.read_end - p.read_start, on_ref = p.ref_end - p.ref_start;
-    const bool verified = edits != DCN_VERIFY_UNPLACED && edits != DCN_VERIFY_OVER;
-    uint64_t matches = verified ? std::max(on_read, on_ref) - edits : std::min<uint64_t>((uint64_t)p.votes * k, on_read);
-    uint64_t block = std::max(on_read, on_ref);
-    if (verified && cigar) {
-        matches = block = 0;
-        for (uint64_t q = 0; q < n_ops; ++q) {
-            block += cigar[q] >> 4;
-            if ((cigar[q] & 15u) == DCN_CIGAR_EQUAL) matches += cigar[q] >> 4;
-        }
-    }
-    rows.append(read_name);
-    rows += '\t' + std::to_string(read_len) + '\t' + std::to_string(p.read_start) + '\t' + std::to_string(p.read_end) + '\t';
-    rows += p.reverse ? '-' : '+';
-    rows += '\t' + record_name + '\t' + std::to_string(record_len) + '\t' + std::to_string(p.ref_start) + '\t' +
-            std::to_string(p.ref_end) + '\t' + std::to_string(matches) + '\t' + std::to_string(block) + '\t' +
-            std::to_string(p.mapq);
-    rows += "\tcm:i:" + std::to_string(p.votes) + "\trk:i:" + std::to_string(p.rank) + "\tnp:i:" + std::to_string(p.n_placed) +
-            "\trv:i:" + std::to_string(p.rival_votes) + "\tna:i:" + std::to_string(p.n_anchors) + "\tns:i:" +
-            std::to_string(p.n_positions);
-    if (verified) rows += "\tve:i:1\tNM:i:" + std::to_string(edits);
-    else if (edits == DCN_VERIFY_OVER) rows += "\tve:i:0";
-    if (verified && cigar) {
-        rows += "\tcg:Z:";
-        for (uint64_t q = 0; q < n_ops; ++q) {
-            const uint32_t op = cigar[q] & 15u;
-            rows += std::to_string(cigar[q] >> 4);
-            rows += op == DCN_CIGAR_EQUAL ? '=' : op == DCN_CIGAR_DIFF ? 'X' : op == DCN_CIGAR_INS ? 'I' : 'D';
-        }
-        if (n_ops == 0) rows += '*'; // (two empty extents: no placement call reports one)
-    }
-    rows += more_tags; // (`extend`: xl, xr, cl, cr)
-    rows += '\n';
+// The map family.  The text of every line is cli/map_text.hpp's; here are the device calls, as stages over one state struct
+// (MapRun), and the counters (MapCounts) with the two functions that report them.
+using ull = unsigned long long;
+
+// (DCN_CLI_STRETCH_BASES: a test hook, so that a short record has the seams between two stretches)
+uint64_t stretch_bases() {
+    const char *const env = std::getenv("DCN_CLI_STRETCH_BASES");
+    return env && *env ? std::max<uint64_t>(std::strtoull(env, nullptr, 10), 1) : 1u << 20;
 }
 
-int run_map(const MapArgs &a) {
+struct MapCounts {
+    uint64_t reads_in = 0, placed = 0, split_reads = 0, placements = 0, mapq60 = 0, mapq0 = 0;
+    std::vector<uint64_t> per_record;
+    uint64_t rows_extended = 0, bases_gained = 0, bases_clipped = 0, full_length_rows = 0; // (extend)
+    uint64_t verified = 0, unverified = 0, edits_sum = 0, verified_bases = 0;
+    uint64_t op_bases[16] = {}, cigar_ops = 0;                                             // (align: bases per op code, and runs)
+    uint64_t rows_selected = 0, rows_added = 0, covered = 0, sites = 0, column_sum[DCN_PILEUP_COLUMNS] = {}; // (pileup)
+    uint64_t insertion_events = 0, inserted_bases = 0, insertion_alleles = 0, substitutions = 0, deleted_positions = 0, consensus_bases = 0,
+             uncalled_positions = 0; // (consensus)
+    uint64_t qual_sum[4] = {};       // (call)
+    uint64_t genotyped_positions = 0, vcf_sites = 0, het_sites = 0, hom_alt_sites = 0; // (genotype)
+    uint64_t reads_keyed = 0, distinct_fragments = 0;                                  // (markdup)
+    uint64_t deletion_events = 0, deleted_bases = 0, indel_sites = 0, insertion_sites = 0, deletion_sites = 0, het_indel_sites = 0,
+             hom_indel_sites = 0; // (indels)
+    dcn_left_align_info left = {}; // (normalize)
+    uint64_t strand_bias_sites = 0, one_strand_sites = 0, filtered_sites = 0; // (strand)
+    uint64_t blocks = 0, block_bases = 0, no_coverage_bases = 0, uncalled_bases = 0, ref_bases = 0, record_bases = 0; // (gvcf)
+    std::vector<uint64_t> ref_bases_by_band;
+    uint64_t phase_sites = 0, phase_sets = 0, phased_sites = 0, links_joined = 0, rows_linking = 0, phase_n50 = 0; // (phase)
+
+    // a row's distance where no PAF line is written: a row that was left out is neither verified nor unverified
+    void tally_distance(uint32_t edits) {
+        if (edits == DCN_VERIFY_OVER) ++unverified;
+        else if (edits != DCN_VERIFY_UNPLACED) ++verified, edits_sum += edits;
+    }
+    void tally_strand(const dcn_strand_site &e) { // a VCF line's place in the summary
+        strand_bias_sites += (e.flags & DCN_STRAND_BIAS) != 0, one_strand_sites += (e.flags & DCN_STRAND_ONE_SIDED) != 0, filtered_sites += e.flags != 0;
+    }
+};
+
+// the stderr lines of a run
+void map_report(const MapArgs &a, const MapCounts &n, bool piles, bool aligns, double secs) {
+    if (a.extend)
+        std::fprintf(stderr, "Extended %llu of %llu placements by %llu bases (%llu bases clipped, %llu placements full length)\n",
+                     (ull)n.rows_extended, (ull)n.placements, (ull)n.bases_gained, (ull)n.bases_clipped, (ull)n.full_length_rows);
+    if (a.markdup)
+        std::fprintf(stderr, "Marked %llu of %llu reads with an end as duplicates%s\n", (ull)(n.reads_keyed - n.distinct_fragments),
+                     (ull)n.reads_keyed, a.keep_duplicates ? " (kept)" : "");
+    if (piles)
+        std::fprintf(stderr, "Piled up %llu of %llu placements on %llu positions (%llu sites)\n", (ull)n.rows_added, (ull)n.placements,
+                     (ull)n.covered, (ull)n.sites);
+    if (a.consensus)
+        std::fprintf(stderr, "Consensus of %llu bases: %llu substitutions, %llu deleted positions, %llu insertions of %llu events, %llu positions without a call\n",
+                     (ull)n.consensus_bases, (ull)n.substitutions, (ull)n.deleted_positions, (ull)n.insertion_alleles, (ull)n.insertion_events,
+                     (ull)n.uncalled_positions);
+    if (a.indels)
+        std::fprintf(stderr, "Genotyped %llu indel sites (%llu insertions, %llu deletions) over %llu deletion events of %llu bases\n",
+                     (ull)n.indel_sites, (ull)n.insertion_sites, (ull)n.deletion_sites, (ull)n.deletion_events, (ull)n.deleted_bases);
+    if (a.normalize)
+        std::fprintf(stderr, "Left-aligned %llu gaps over %llu columns in %llu of %llu placements (%llu gaps merged)\n", (ull)n.left.gaps_shifted,
+                     (ull)n.left.columns_passed, (ull)n.left.rows_changed, (ull)n.left.rows_aligned, (ull)n.left.gaps_merged);
+    if (a.strand)
+        std::fprintf(stderr, "Filtered %llu VCF lines by strand (%llu strand_bias, %llu one_strand)\n", (ull)n.filtered_sites,
+                     (ull)n.strand_bias_sites, (ull)n.one_strand_sites);
+    if (a.gvcf)
+        std::fprintf(stderr, "Cut %llu bases into %llu reference blocks (%llu bases reference, %llu not called, %llu without coverage)\n",
+                     (ull)n.record_bases, (ull)n.blocks, (ull)n.ref_bases, (ull)n.uncalled_bases, (ull)n.no_coverage_bases);
+    if (a.phase)
+        std::fprintf(stderr, "Phased %llu of %llu heterozygous SNV sites in %llu sets (%llu links joined, %llu placements linking)\n",
+                     (ull)n.phased_sites, (ull)n.phase_sites, (ull)n.phase_sets, (ull)n.links_joined, (ull)n.rows_linking);
+    if (a.verify && !a.pileup)
+        std::fprintf(stderr, "Verified %llu of %llu placements (%llu edits over %llu bases)\n", (ull)n.verified, (ull)n.placements,
+                     (ull)n.edits_sum, (ull)n.verified_bases);
+    if (aligns)
+        std::fprintf(stderr, "Aligned %llu placements in %llu runs (%llu =, %llu X, %llu I, %llu D)\n", (ull)n.verified, (ull)n.cigar_ops,
+                     (ull)n.op_bases[DCN_CIGAR_EQUAL], (ull)n.op_bases[DCN_CIGAR_DIFF], (ull)n.op_bases[DCN_CIGAR_INS], (ull)n.op_bases[DCN_CIGAR_DEL]);
+    std::fprintf(stderr, "Mapped %llu of %llu reads in %llu placements (%llu reads with two or more) in %s\n", (ull)n.placed, (ull)n.reads_in,
+                 (ull)n.placements, (ull)n.split_reads, fmt_duration(secs).c_str());
+}
+
+// the -s summary of a run: every mode adds its keys behind those of the mode it is built on
+std::string map_summary(const MapArgs &a, const AnchorRef &R, const MapCounts &n, bool piles, bool aligns, double secs) {
+    const auto yes = [](bool v) { return v ? "true" : "false"; };
+    std::string js = summary_head() + ",\n  \"reference\": " + json_str(a.ref) + ",\n  \"input\": " + json_str(a.input);
+    appendf(js, ",\n  \"k\": %u,\n  \"w\": %u,\n  \"band_bases\": %u,\n  \"min_votes\": %u,\n  \"prefix_length\": %zu,\n"
+                "  \"records\": %u,\n  \"keys\": %llu,\n  \"anchors\": %llu,\n  \"repeats\": %llu,\n"
+                "  \"reads\": %llu,\n  \"placed\": %llu,\n  \"max_placements\": %u,\n  \"placements\": %llu,\n"
+                "  \"split_reads\": %llu,\n  \"mapq60\": %llu,\n  \"mapq0\": %llu,\n",
+            (unsigned)R.k, (unsigned)R.w, a.band, a.min_votes, a.prefix_length, R.m_records, (ull)R.m_keys, (ull)R.m_anchors, (ull)R.m_repeats,
+            (ull)n.reads_in, (ull)n.placed, a.max_placements, (ull)n.placements, (ull)n.split_reads, (ull)n.mapq60, (ull)n.mapq0);
+    if (a.verify)
+        appendf(js, "  \"max_edits\": %u,\n  \"max_permille\": %u,\n  \"verified\": %llu,\n  \"unverified\": %llu,\n"
+                    "  \"edits\": %llu,\n  \"verified_bases\": %llu,\n",
+                a.max_edits, a.max_div, (ull)n.verified, (ull)n.unverified, (ull)n.edits_sum, (ull)n.verified_bases);
+    if (a.extend)
+        appendf(js, "  \"penalty\": %u,\n  \"end_bonus\": %u,\n  \"ext_max_edits\": %u,\n  \"rows_extended\": %llu,\n"
+                    "  \"bases_gained\": %llu,\n  \"bases_clipped\": %llu,\n  \"full_length_rows\": %llu,\n",
+                a.penalty, a.end_bonus, a.ext_max_edits, (ull)n.rows_extended, (ull)n.bases_gained, (ull)n.bases_clipped, (ull)n.full_length_rows);
+    if (aligns)
+        appendf(js, "  \"matches\": %llu,\n  \"mismatches\": %llu,\n  \"insertions\": %llu,\n  \"deletions\": %llu,\n"
+                    "  \"cigar_ops\": %llu,\n",
+                (ull)n.op_bases[DCN_CIGAR_EQUAL], (ull)n.op_bases[DCN_CIGAR_DIFF], (ull)n.op_bases[DCN_CIGAR_INS], (ull)n.op_bases[DCN_CIGAR_DEL],
+                (ull)n.cigar_ops);
+    if (piles) {
+        appendf(js, "  \"min_mapq\": %u,\n  \"all_ranks\": %s,\n  \"min_depth\": %u,\n  \"min_permille\": %u,\n"
+                    "  \"rows_selected\": %llu,\n  \"rows_added\": %llu,\n  \"positions_covered\": %llu,\n  \"sites\": %llu,\n",
+                a.min_mapq, yes(a.all_ranks), a.min_depth, a.min_frac, (ull)n.rows_selected, (ull)n.rows_added, (ull)n.covered, (ull)n.sites);
+        const char *const column_names[DCN_PILEUP_COLUMNS] = {"A", "C", "G", "T", "N", "del", "ins", "rev"};
+        js += "  \"columns\": {";
+        for (int col = 0; col < DCN_PILEUP_COLUMNS; ++col) appendf(js, "%s\"%s\": %llu", col ? ", " : "", column_names[col], (ull)n.column_sum[col]);
+        js += "},\n";
+    }
+    if (a.consensus)
+        appendf(js, "  \"fill_ref\": %s,\n  \"insertion_events\": %llu,\n  \"inserted_bases\": %llu,\n  \"insertion_alleles\": %llu,\n"
+                    "  \"substitutions\": %llu,\n  \"deleted_positions\": %llu,\n  \"consensus_bases\": %llu,\n  \"uncalled_positions\": %llu,\n",
+                yes(a.fill_ref), (ull)n.insertion_events, (ull)n.inserted_bases, (ull)n.insertion_alleles, (ull)n.substitutions,
+                (ull)n.deleted_positions, (ull)n.consensus_bases, (ull)n.uncalled_positions);
+    if (a.call)
+        appendf(js, "  \"min_base_qual\": %u,\n  \"qual_offset\": %u,\n  \"quality_sums\": {\"A\": %llu, \"C\": %llu, \"G\": %llu, \"T\": %llu},\n",
+                a.min_baseq, a.qual_offset, (ull)n.qual_sum[0], (ull)n.qual_sum[1], (ull)n.qual_sum[2], (ull)n.qual_sum[3]);
+    if (a.genotype)
+        appendf(js, "  \"ploidy\": %u,\n  \"min_gq\": %u,\n  \"min_qual\": %u,\n  \"genotyped_positions\": %llu,\n  \"vcf_sites\": %llu,\n"
+                    "  \"het_sites\": %llu,\n  \"hom_alt_sites\": %llu,\n",
+                a.ploidy, a.min_gq, a.min_qual, (ull)n.genotyped_positions, (ull)n.vcf_sites, (ull)n.het_sites, (ull)n.hom_alt_sites);
+    if (a.markdup)
+        appendf(js, "  \"duplicates_both_ends\": %s,\n  \"keep_duplicates\": %s,\n  \"reads_keyed\": %llu,\n  \"duplicate_reads\": %llu,\n"
+                    "  \"distinct_fragments\": %llu,\n",
+                yes(a.both_ends), yes(a.keep_duplicates), (ull)n.reads_keyed, (ull)(n.reads_keyed - n.distinct_fragments), (ull)n.distinct_fragments);
+    if (a.indels)
+        appendf(js, "  \"indel_qual\": %u,\n  \"min_indel_count\": %u,\n  \"deletion_events\": %llu,\n  \"deleted_bases\": %llu,\n"
+                    "  \"indel_sites\": %llu,\n  \"insertion_sites\": %llu,\n  \"deletion_sites\": %llu,\n  \"het_indel_sites\": %llu,\n"
+                    "  \"hom_indel_sites\": %llu,\n",
+                a.indel_qual, a.min_indel_count, (ull)n.deletion_events, (ull)n.deleted_bases, (ull)n.indel_sites, (ull)n.insertion_sites,
+                (ull)n.deletion_sites, (ull)n.het_indel_sites, (ull)n.hom_indel_sites);
+    if (a.normalize)
+        appendf(js, "  \"left_aligned_rows\": %llu,\n  \"left_aligned_gaps\": %llu,\n  \"left_align_columns\": %llu,\n"
+                    "  \"left_align_merged_gaps\": %llu,\n",
+                (ull)n.left.rows_changed, (ull)n.left.gaps_shifted, (ull)n.left.columns_passed, (ull)n.left.gaps_merged);
+    if (a.strand)
+        appendf(js, "  \"max_sb\": %u,\n  \"min_alt_strand\": %u,\n  \"min_strand_depth\": %u,\n  \"strand_bias_sites\": %llu,\n"
+                    "  \"one_strand_sites\": %llu,\n  \"filtered_sites\": %llu,\n",
+                a.max_sb, a.min_alt_strand, a.min_strand_depth, (ull)n.strand_bias_sites, (ull)n.one_strand_sites, (ull)n.filtered_sites);
+    if (a.gvcf) {
+        appendf(js, "  \"blocks\": %llu,\n  \"block_bases\": %llu,\n  \"variant_positions\": %llu,\n  \"no_coverage_bases\": %llu,\n"
+                    "  \"uncalled_bases\": %llu,\n  \"ref_bases\": %llu,\n  \"ref_bases_by_band\": [",
+                (ull)n.blocks, (ull)n.block_bases, (ull)(n.record_bases - n.block_bases), (ull)n.no_coverage_bases, (ull)n.uncalled_bases,
+                (ull)n.ref_bases);
+        for (size_t b = 0; b < n.ref_bases_by_band.size(); ++b) appendf(js, "%s%llu", b ? ", " : "", (ull)n.ref_bases_by_band[b]);
+        js += "],\n  \"gq_bands\": [";
+        for (size_t b = 0; b < a.gq_bands.size(); ++b) appendf(js, "%s%u", b ? ", " : "", a.gq_bands[b]);
+        js += "],\n";
+    }
+    if (a.phase)
+        appendf(js, "  \"min_link_reads\": %u,\n  \"max_link_minor\": %u,\n  \"phase_sites\": %llu,\n  \"phase_sets\": %llu,\n"
+                    "  \"phased_sites\": %llu,\n  \"links_joined\": %llu,\n  \"rows_linking\": %llu,\n  \"phase_set_n50\": %llu,\n",
+                a.min_link_reads, a.max_link_minor, (ull)n.phase_sites, (ull)n.phase_sets, (ull)n.phased_sites, (ull)n.links_joined,
+                (ull)n.rows_linking, (ull)n.phase_n50);
+    appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
+    for (uint32_t r = 0; r < R.n_records; ++r) {
+        js += (r ? ",\n    {" : "\n    {");
+        js += "\"name\": " + json_str(R.names[r]);
+        appendf(js, ", \"length\": %u, \"placements\": %llu}", R.lens[r], (ull)n.per_record[r]);
+    }
+    return js + "\n  ]\n}\n";
+}
+
+CallOptions call_options(const MapArgs &a) {
+    CallOptions o;
+    o.ploidy = a.ploidy, o.min_depth = a.min_depth, o.min_frac = a.min_frac, o.min_gq = a.min_gq, o.min_qual = a.min_qual;
+    o.indel_qual = a.indel_qual, o.min_indel_count = a.min_indel_count;
+    o.max_sb = a.max_sb, o.min_alt_strand = a.min_alt_strand, o.min_strand_depth = a.min_strand_depth;
+    o.min_link_reads = a.min_link_reads, o.max_link_minor = a.max_link_minor, o.gq_bands = a.gq_bands;
+    return o;
+}
+
+// A run of one subcommand of the family.  Every mode flag of MapArgs sets all the earlier ones, so a stage asks for the
+// earliest mode that needs it.  A new mode adds its switch to load(), its calls to the stage whose data it reads (a batch
+// stage for what looks at reads, a stretch stage for what looks at counters), its text to map_text.hpp and its counters
+// to MapCounts and the two reports.
+struct MapRun {
+    const MapArgs &a;
     const Stopwatch watch;
-    const auto no_qualities = [&a](const std::string &name) {
-        die(std::string(a.phase ? "phase" : a.gvcf ? "gvcf" : a.strand ? "strand" : a.normalize ? "normalize" : a.indels ? "indels" : a.markdup ? "markdup" : a.genotype ? "genotype" : "call") + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
-    };
+    // the mode's name for its messages, and what follows from the flags
+    const char *const mode = a.phase ? "phase" : a.gvcf ? "gvcf" : a.strand ? "strand" : a.normalize ? "normalize" : a.indels ? "indels" : a.markdup ? "markdup" : a.genotype ? "genotype" : "call";
+    const bool piles = a.pileup || a.consensus || (a.extend && (a.has_pileup_out || a.has_sites)); // (the map's counters are used)
+    const bool aligns = a.align || (a.extend && a.has_output);                                      // (the rows' runs are asked for)
+    const bool prints = !a.extend || a.has_output;                                                  // (`extend` prints PAF only when asked to)
+    const CallOptions opt = call_options(a);
+    AnchorRef R;
+    MapCounts n;
     std::unique_ptr<FastxReader> reads; // (`call` looks at the first record before the reference is loaded)
-    if (a.call) {
+    TextOut out, dup_out, sites_out, pile_file, fasta_out, variants_out, callable_out;
+    TextOut *tsv = nullptr;                  // the pileup table: -o in `pileup`, --pileup from `extend` on, else none
+    std::unique_ptr<Output> vcf_out, gvcf_out; // (.gz as BGZF, .zst and .xz by extension, as filter's outputs)
+    // the batch: its reads, the rows placed, their extension, distances and runs, the rows selected for the pile-up
+    dcn_place_split_params prm = {};
+    dcn_extend_params xprm = {};
+    dcn_verify_params vprm = {};
+    dcn_duplicate_params dprm = {};
+    dcn_pileup_qual_params qprm = {};
+    Batch b;
+    uint32_t n_reads = 0;
+    uint64_t n_rows = 0;
+    const dcn_split_placement *use = nullptr; // the rows of verify, align and pileup: pl, or xpl in `extend`
+    std::vector<uint64_t> place_off, cigar_off, dup_first;
+    std::vector<dcn_split_placement> pl, xpl, chosen; // (xpl: the rows just placed with the four coordinates of their extension)
+    std::vector<dcn_extension> ext;
+    std::vector<uint32_t> edits, cigar, pile_edits; // (`extend` with -o keeps align's edits of every row for the PAF)
+    std::vector<uint8_t> dup_flags, quals;          // (`call`: the quality lines of the batch, parallel to its bases)
+    std::string rows, dup_rows;
+    // (`phase`) the heterozygous SNV sites in the list's order, their results, and the next site the output stage meets
+    std::vector<dcn_phase_site> ph_sites;
+    std::vector<dcn_phase_result> ph_res;
+    std::vector<dcn_genotype_site> ph_geno;
+    size_t ph_cursor = 0;
+    // the stretch: what is fetched, what is called, and the lines
+    struct Stretch {
+        uint32_t r;
+        uint64_t start, n;
+    };
+    const dcn_pileup_call_params cprm = pileup_call_params(opt);
+    const dcn_genotype_params gprm = genotype_params(opt);
+    const dcn_indel_params iprm = indel_params(opt);
+    const dcn_strand_params sprm = strand_params(opt);
+    const dcn_block_params bprm = block_params(opt);
+    std::vector<uint32_t> counts, qsums, planes, site_info, ind_reverse;
+    std::vector<uint64_t> site_pos, breaks;
+    std::vector<uint8_t> ref_text, ref_more, calls, allele_bases, geno_gt, ind_bases;
+    std::vector<dcn_insertion_allele> alleles;
+    std::vector<dcn_genotype_site> geno_sites;
+    std::vector<dcn_indel_site> ind_sites;
+    std::vector<dcn_strand_query> strand_queries;
+    std::vector<dcn_strand_site> snv_strand, ind_strand;
+    std::vector<dcn_reference_block> blocks, fresh; // (blocks: the one that the stretch before left open, then this stretch's)
+    std::string seq, variant_rows, site_rows;
+    PosLines snv_lines, indel_lines, vcf_lines, block_lines, gvcf_lines;
+    CallableBed bed;
+
+    explicit MapRun(const MapArgs &args) : a(args) {}
+    static void write(Output &o, const std::string &text) { o.write(std::vector<char>(text.begin(), text.end())); }
+    [[noreturn]] void no_qualities(const std::string &name) const {
+        die(std::string(mode) + " needs base qualities, and record '" + name + "' has none (FASTA): consensus takes reads without");
+    }
+
+    // ---- before the first batch -------------------------------------------------------------------------------------------
+    void check_arguments() { // (`call` and later: what ends before any device call)
+        if (!a.call) return;
         if (a.ref.empty()) die("the following required arguments were not provided: <REF>");
         if (a.genotype && !a.has_fasta && !a.has_variants && !a.has_pileup_out && !a.has_sites && !a.has_vcf && !a.has_summary && !a.has_duplicates && !a.has_gvcf && !a.has_callable && !a.has_phase_sets && !a.has_links)
             die(std::string("nothing to write: give at least one of -o <OUTPUT>, --variants <FILE>, --pileup <FILE>, --sites <FILE>, --vcf <FILE>, ") +
@@ -3932,818 +4141,257 @@ int run_map(const MapArgs &a) {
         std::string name;
         if (reads->begins_with_fasta(&name)) no_qualities(name);
     }
-    AnchorRef R;
-    load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w, 
-                    a.align || a.pileup || a.extend ? "DCN_CLI_ALIGN_BATCH_BASES" : a.verify ? "DCN_CLI_VERIFY_BATCH_BASES" : "DCN_CLI_MAP_BATCH_BASES", a.quiet, a.verify);
-    Context &ctx = *R.ctx;
-    const bool piles = a.pileup || a.consensus || (a.extend && (a.has_pileup_out || a.has_sites)); // (the map's counters are used)
-    if (piles) deacon::check(dcn_anchor_map_pileup_enable(R.map.p, 1)); // (after the records: a pileup does not grow)
-    if (a.consensus) deacon::check(dcn_anchor_map_pileup_keep_insertions(R.map.p, 1)); // (before the first row adds)
-    if (a.call) deacon::check(dcn_anchor_map_pileup_keep_qualities(R.map.p, 1));
-    if (a.indels) deacon::check(dcn_anchor_map_pileup_keep_deletions(R.map.p, 1));
-    if (a.normalize) deacon::check(dcn_anchor_map_pileup_left_align(R.map.p, 1)); // (rule N8: before the first row adds)
-    if (a.strand) deacon::check(dcn_anchor_map_pileup_keep_strands(R.map.p, 1));     // (rule S1: likewise)
-    if (a.markdup) deacon::check(dcn_anchor_map_duplicates_enable(R.map.p, 1));
-    dcn_duplicate_params dprm = {};
-    dprm.row_stride = sizeof(dcn_split_placement);
-    dprm.paired = 0; // (mates are placed independently here: a read is a unit)
-    dprm.both_ends = a.both_ends ? 1 : 0;
-    std::vector<uint8_t> dup_flags;
-    std::vector<uint64_t> dup_first;
-    std::string dup_rows;
-    TextOut dup_out;
-    if (a.has_duplicates) {
-        dup_out.open(a.duplicates, false);
-        dup_out.write("read\tordinal\tfirst\trecord\tstrand\tpos5\n");
+    void load() { // the reference as an anchor map, with what the mode keeps beside the counters
+        load_anchor_ref(R, a.ref, a.has_index, a.index, a.k, a.w,
+                        a.align || a.pileup || a.extend ? "DCN_CLI_ALIGN_BATCH_BASES" : a.verify ? "DCN_CLI_VERIFY_BATCH_BASES" : "DCN_CLI_MAP_BATCH_BASES", a.quiet, a.verify);
+        if (piles) deacon::check(dcn_anchor_map_pileup_enable(R.map.p, 1)); // (after the records: a pileup does not grow)
+        if (a.consensus) deacon::check(dcn_anchor_map_pileup_keep_insertions(R.map.p, 1)); // (before the first row adds)
+        if (a.call) deacon::check(dcn_anchor_map_pileup_keep_qualities(R.map.p, 1));
+        if (a.indels) deacon::check(dcn_anchor_map_pileup_keep_deletions(R.map.p, 1));
+        if (a.normalize) deacon::check(dcn_anchor_map_pileup_left_align(R.map.p, 1)); // (rule N8: before the first row adds)
+        if (a.strand) deacon::check(dcn_anchor_map_pileup_keep_strands(R.map.p, 1));     // (rule S1: likewise)
+        if (a.markdup) deacon::check(dcn_anchor_map_duplicates_enable(R.map.p, 1));
+        n.per_record.assign(R.n_records, 0);
+        n.ref_bases_by_band.assign(a.gq_bands.size() + 1, 0);
+        prm.band_bases = a.band, prm.min_votes = a.min_votes, prm.prefix_length = a.prefix_length, prm.max_placements = a.max_placements;
+        xprm.penalty = a.penalty, xprm.end_bonus = a.end_bonus, xprm.max_edits = a.ext_max_edits, xprm.row_stride = sizeof(dcn_split_placement);
+        vprm.max_edits = a.max_edits, vprm.max_permille = a.max_div, vprm.row_stride = sizeof(dcn_split_placement);
+        dprm.row_stride = sizeof(dcn_split_placement);
+        dprm.paired = 0; // (mates are placed independently here: a read is a unit)
+        dprm.both_ends = a.both_ends ? 1 : 0;
+        qprm.qual_offset = a.qual_offset, qprm.min_base_qual = a.min_baseq;
     }
-    dcn_pileup_qual_params qprm = {};
-    qprm.qual_offset = a.qual_offset;
-    qprm.min_base_qual = a.min_baseq;
-    std::vector<uint8_t> quals; // (`call`: the quality lines of the batch, parallel to its bases)
-    dcn_place_split_params prm = {};
-    prm.band_bases = a.band;
-    prm.min_votes = a.min_votes;
-    prm.prefix_length = a.prefix_length;
-    prm.max_placements = a.max_placements;
-    TextOut out;
-    const bool prints = !a.extend || a.has_output; // (`extend` prints PAF only when asked to)
-    if (prints) out.open(a.output, true);
-    if (!reads) reads.reset(new FastxReader(a.input));
-    FastxReader &rd = *reads;
-    uint64_t reads_in = 0, placed = 0, split_reads = 0, placements = 0, mapq60 = 0, mapq0 = 0;
-    uint64_t rows_extended = 0, bases_gained = 0, bases_clipped = 0, full_length_rows = 0; // (extend)
-    dcn_extend_params xprm = {};
-    xprm.penalty = a.penalty;
-    xprm.end_bonus = a.end_bonus;
-    xprm.max_edits = a.ext_max_edits;
-    xprm.row_stride = sizeof(dcn_split_placement);
-    std::vector<dcn_extension> ext;
-    std::vector<dcn_split_placement> xpl; // the rows just placed with the four coordinates of their extension
-    std::vector<uint32_t> pile_edits;     // (`extend` with -o keeps align's edits of every row for the PAF)
-    std::string tags;
-    uint64_t verified = 0, unverified = 0, edits_sum = 0, verified_bases = 0;
-    uint64_t op_bases[16] = {}, cigar_ops = 0; // (align: bases per op code, and runs)
-    uint64_t rows_selected = 0, rows_added = 0; // (pileup)
-    std::vector<dcn_split_placement> chosen;
-    dcn_verify_params vprm = {};
-    vprm.max_edits = a.max_edits;
-    vprm.max_permille = a.max_div;
-    vprm.row_stride = sizeof(dcn_split_placement);
-    std::vector<uint64_t> per_record(R.n_records, 0);
-    Batch b;
-    std::vector<uint64_t> place_off;
-    std::vector<dcn_split_placement> pl;
-    std::vector<uint32_t> edits, cigar;
-    std::vector<uint64_t> cigar_off;
-    std::string rows;
-    // (`phase`) the second pass: the same batches, the same rows, the same duplicate marking, and dcn_phase_batch in the pileup
-    // call's place; nothing is counted or written a second time
-    bool second_pass = false;
-    uint64_t rows_linking = 0;
-    const auto on_batch = [&] {
-        const uint32_t n_reads = (uint32_t)b.recs.size();
-        ctx.fit(b.offsets.back());
+    void open_batch_outputs() {
+        if (a.has_duplicates) dup_out.open(a.duplicates, false), dup_out.write(duplicates_header());
+        if (prints) out.open(a.output, true);
+        if (!reads) reads.reset(new FastxReader(a.input));
+    }
+
+    // ---- per batch --------------------------------------------------------------------------------------------------------
+    void place() {
+        n_reads = (uint32_t)b.recs.size();
+        R.ctx->fit(b.offsets.back());
         place_off.assign((size_t)n_reads + 1, 0);
-        pl.resize((size_t)n_reads * a.max_placements);  // (never more than max_placements per read)
-        deacon::check(dcn_place_split_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &prm, place_off.data(),
-                                            pl.data(), pl.size(), nullptr));
-        if (a.extend) { // the rows just placed, grown over the flanks of their reads: what every call below takes
-            ext.resize(place_off[n_reads]);
-            deacon::check(dcn_extend_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &xprm, place_off.data(), pl.data(),
-                                           place_off[n_reads], ext.data()));
-            xpl.assign(pl.begin(), pl.begin() + (ptrdiff_t)place_off[n_reads]);
-            for (size_t q = 0; q < xpl.size(); ++q) {
-                xpl[q].read_start = ext[q].read_start, xpl[q].read_end = ext[q].read_end;
-                xpl[q].ref_start = ext[q].ref_start, xpl[q].ref_end = ext[q].ref_end;
-            }
+        pl.resize((size_t)n_reads * a.max_placements); // (never more than max_placements per read)
+        deacon::check(dcn_place_split_batch(R.ctx->p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &prm, place_off.data(), pl.data(), pl.size(), nullptr));
+        n_rows = place_off[n_reads];
+        use = pl.data();
+    }
+    void extend() { // the rows just placed, grown over the flanks of their reads: what every call below takes
+        ext.resize(n_rows);
+        deacon::check(dcn_extend_batch(R.ctx->p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &xprm, place_off.data(), pl.data(), n_rows, ext.data()));
+        xpl.assign(pl.begin(), pl.begin() + (ptrdiff_t)n_rows);
+        for (size_t q = 0; q < xpl.size(); ++q) {
+            xpl[q].read_start = ext[q].read_start, xpl[q].read_end = ext[q].read_end;
+            xpl[q].ref_start = ext[q].ref_start, xpl[q].ref_end = ext[q].ref_end;
         }
-        const dcn_split_placement *const use = a.extend ? xpl.data() : pl.data(); // the rows of verify, align and pileup
-        const bool aligns = a.align || (a.extend && a.has_output);
-        if (aligns && !second_pass) { // the same reads, the rows just placed: their distances and the runs of the verified ones
-            edits.resize(place_off[n_reads]);
-            cigar_off.assign(place_off[n_reads] + 1, 0);
-            for (int attempt = 0;; ++attempt) {
-                const int rc = dcn_align_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), use,
-                                               place_off[n_reads], edits.data(), cigar_off.data(), cigar.data(), cigar.size());
-                if (rc != DCN_ERR_CAPACITY || attempt) {
-                    deacon::check(rc);
-                    break;
-                }
-                cigar.resize(cigar_off[place_off[n_reads]]); // (the size the first call reported)
-            }
-        } else if (a.extend && !piles && !second_pass) { // (neither output: the distances of the extended rows, for the summary)
-            edits.resize(place_off[n_reads]);
-            deacon::check(dcn_verify_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), use,
-                                           place_off[n_reads], edits.data()));
+        use = xpl.data();
+    }
+    // the rows' distances, and the runs of the verified ones where PAF shows them; a pile-up reports the distances itself
+    void align_or_verify() {
+        if (aligns) {
+            edits.resize(n_rows);
+            cigar_off.assign(n_rows + 1, 0);
+            with_room(cigar, [&](uint32_t *into, size_t room, uint64_t &count) {
+                const int rc = dcn_align_batch(R.ctx->p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), use, n_rows,
+                                               edits.data(), cigar_off.data(), into, room);
+                // dcn_align_batch reports its size in the last offset, which is complete whenever it says DCN_ERR_CAPACITY for
+                // cigar.  Were an earlier step of it to say so with the offsets still 0, the count stays 0 and the error is
+                // passed on after this one call: the same text and exit code as from a second call.
+                count = cigar_off[n_rows];
+                return rc;
+            });
+        } else if (a.verify && !piles) { // (`extend` with neither output: the distances of the extended rows, for the summary)
+            edits.resize(n_rows);
+            deacon::check(dcn_verify_batch(R.ctx->p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), use, n_rows, edits.data()));
         }
-        if (piles) { // the rows just placed, those that --min-mapq and the rank leave: unplaced in a copy
-            std::vector<uint32_t> &into = aligns ? pile_edits : edits;
-            into.resize(place_off[n_reads]);
-            chosen.assign(use, use + (ptrdiff_t)place_off[n_reads]);
-            for (dcn_split_placement &p : chosen) {
-                if (p.mapq >= a.min_mapq && (a.all_ranks || p.rank == 0)) rows_selected += !second_pass;
-                else p.record = UINT32_MAX;
-            }
-            if (a.markdup) { // the selected rows' ends against every read so far: one call per batch, so an ordinal is a read's number
-                dup_flags.assign(n_reads, 0);
-                dup_first.assign(n_reads, 0);
-                deacon::check(dcn_mark_duplicates_batch(R.map.p, b.offsets.data(), n_reads, &dprm, place_off.data(), chosen.data(),
-                                                        place_off[n_reads], dup_flags.data(), dup_first.data(), nullptr));
-                dup_rows.clear();
-                for (uint32_t r = 0; r < n_reads; ++r) {
-                    if (!dup_flags[r]) continue;
-                    if (a.has_duplicates && !second_pass) { // rule D3's end, from the read's first selected row
-                        uint64_t q = place_off[r];
-                        while (chosen[q].record == UINT32_MAX) ++q;
-                        const dcn_split_placement &p = chosen[q];
-                        const long long pos5 = p.reverse ? (long long)(p.ref_end + p.read_start) : (long long)p.ref_start - (long long)p.read_start;
-                        dup_rows.append(id_token(b, b.recs[r]));
-                        dup_rows += '\t' + std::to_string(reads_in + r) + '\t' + std::to_string(dup_first[r]) + '\t' + R.names[p.record] + '\t' +
-                                    (p.reverse ? '-' : '+') + '\t' + std::to_string(pos5) + '\n';
-                    }
-                    if (!a.keep_duplicates)
-                        for (uint64_t q = place_off[r]; q < place_off[r + 1]; ++q) chosen[q].record = UINT32_MAX;
-                }
-                if (a.has_duplicates && !second_pass) dup_out.write(dup_rows);
-            }
-            uint64_t added = 0;
-            if (a.call) {
-                quals.resize(b.offsets.back());
-                for (uint32_t r = 0; r < n_reads; ++r) {
-                    const Rec &rec = b.recs[r];
-                    if (rec.qual_off == NO_QUAL) no_qualities(std::string(id_token(b, rec)));
-                    std::memcpy(quals.data() + b.offsets[r], b.chars() + rec.qual_off, rec.seq_len);
-                }
-                if (second_pass) {
-                    uint64_t linking = 0;
-                    deacon::check(dcn_phase_batch(ctx.p, R.map.p, b.bases.data(), quals.data(), b.offsets.data(), n_reads, &vprm, &qprm,
-                                                  place_off.data(), chosen.data(), place_off[n_reads], into.data(), &linking));
-                    rows_linking += linking;
-                    return;
-                }
-                deacon::check(dcn_pileup_batch_qual(ctx.p, R.map.p, b.bases.data(), quals.data(), b.offsets.data(), n_reads, &vprm, &qprm,
-                                                    place_off.data(), chosen.data(), place_off[n_reads], into.data(), &added));
-            } else
-                deacon::check(dcn_pileup_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), chosen.data(),
-                                               place_off[n_reads], into.data(), &added));
-            rows_added += added;
-        } else if (a.verify && !a.align && !a.extend) {
-            edits.resize(place_off[n_reads]);
-            deacon::check(dcn_verify_batch(ctx.p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), pl.data(),
-                                           place_off[n_reads], edits.data()));
+    }
+    // the rows that --min-mapq and the rank leave: unplaced in a copy.  Gives their number.
+    uint64_t select() {
+        uint64_t selected = 0;
+        chosen.assign(use, use + (ptrdiff_t)n_rows);
+        for (dcn_split_placement &p : chosen) {
+            if (p.mapq >= a.min_mapq && (a.all_ranks || p.rank == 0)) ++selected;
+            else p.record = UINT32_MAX;
         }
+        return selected;
+    }
+    // the selected rows' ends against every read so far: one call per batch, so an ordinal is a read's number
+    void mark_duplicates() {
+        dup_flags.assign(n_reads, 0);
+        dup_first.assign(n_reads, 0);
+        deacon::check(dcn_mark_duplicates_batch(R.map.p, b.offsets.data(), n_reads, &dprm, place_off.data(), chosen.data(), n_rows, dup_flags.data(),
+                                                dup_first.data(), nullptr));
+    }
+    void write_duplicate_rows() { // rule D3's end, from the read's first selected row
+        dup_rows.clear();
+        for (uint32_t r = 0; r < n_reads; ++r) {
+            if (!dup_flags[r]) continue;
+            uint64_t q = place_off[r];
+            while (chosen[q].record == UINT32_MAX) ++q;
+            append_duplicate_row(dup_rows, std::string(id_token(b, b.recs[r])), n.reads_in + r, dup_first[r], R.names[chosen[q].record], chosen[q]);
+        }
+        dup_out.write(dup_rows);
+    }
+    void drop_duplicates() {
+        for (uint32_t r = 0; r < n_reads; ++r)
+            for (uint64_t q = place_off[r]; dup_flags[r] && q < place_off[r + 1]; ++q) chosen[q].record = UINT32_MAX;
+    }
+    void select_and_mark(bool first_time) { // what both passes of `phase` hand on: the same rows both times
+        const uint64_t selected = select();
+        if (first_time) n.rows_selected += selected;
+        if (!a.markdup) return;
+        mark_duplicates();
+        if (first_time && a.has_duplicates) write_duplicate_rows();
+        if (!a.keep_duplicates) drop_duplicates();
+    }
+    void read_qualities() {
+        quals.resize(b.offsets.back());
+        for (uint32_t r = 0; r < n_reads; ++r) {
+            const Rec &rec = b.recs[r];
+            if (rec.qual_off == NO_QUAL) no_qualities(std::string(id_token(b, rec)));
+            std::memcpy(quals.data() + b.offsets[r], b.chars() + rec.qual_off, rec.seq_len);
+        }
+    }
+    std::vector<uint32_t> &pile_distances() { return aligns ? pile_edits : edits; }
+    void pile_up() {
+        std::vector<uint32_t> &into = pile_distances();
+        into.resize(n_rows);
+        uint64_t added = 0;
+        if (a.call) {
+            read_qualities();
+            deacon::check(dcn_pileup_batch_qual(R.ctx->p, R.map.p, b.bases.data(), quals.data(), b.offsets.data(), n_reads, &vprm, &qprm, place_off.data(),
+                                                chosen.data(), n_rows, into.data(), &added));
+        } else
+            deacon::check(dcn_pileup_batch(R.ctx->p, R.map.p, b.bases.data(), b.offsets.data(), n_reads, &vprm, place_off.data(), chosen.data(), n_rows,
+                                           into.data(), &added));
+        n.rows_added += added;
+    }
+    void link() { // (`phase`) dcn_phase_batch in the pileup call's place
+        std::vector<uint32_t> &into = pile_distances();
+        into.resize(n_rows);
+        read_qualities();
+        uint64_t linking = 0;
+        deacon::check(dcn_phase_batch(R.ctx->p, R.map.p, b.bases.data(), quals.data(), b.offsets.data(), n_reads, &vprm, &qprm, place_off.data(),
+                                      chosen.data(), n_rows, into.data(), &linking));
+        n.rows_linking += linking;
+    }
+    void tally_and_print() {
+        std::string tags;
         rows.clear();
         for (uint32_t r = 0; r < n_reads; ++r) {
             const Rec &rec = b.recs[r];
             const uint64_t p0 = place_off[r], p1 = place_off[r + 1];
-            ++reads_in;
-            if (p1 > p0) ++placed;
-            if (p1 > p0 + 1) ++split_reads;
-            placements += p1 - p0;
+            ++n.reads_in;
+            if (p1 > p0) ++n.placed;
+            if (p1 > p0 + 1) ++n.split_reads;
+            n.placements += p1 - p0;
             const std::string name(p1 > p0 ? id_token(b, rec) : std::string_view());
             for (uint64_t q = p0; q < p1; ++q) {
                 const dcn_split_placement &p = use[q];
-                ++per_record[p.record];
-                mapq60 += p.mapq == 60, mapq0 += p.mapq == 0;
-                if (a.extend) { // what the flanks gave, and what is left of the read: in the record's direction
-                    const uint64_t lo = pl[q].read_start - p.read_start, hi = p.read_end - pl[q].read_end;
-                    const uint64_t clip_lo = p.read_start, clip_hi = rec.seq_len - p.read_end;
-                    rows_extended += lo + hi > 0, bases_gained += lo + hi, bases_clipped += clip_lo + clip_hi;
-                    full_length_rows += clip_lo + clip_hi == 0;
-                    tags = "\txl:i:" + std::to_string(p.reverse ? hi : lo) + "\txr:i:" + std::to_string(p.reverse ? lo : hi) +
-                           "\tcl:i:" + std::to_string(p.reverse ? clip_hi : clip_lo) + "\tcr:i:" + std::to_string(p.reverse ? clip_lo : clip_hi);
-                    if (!a.has_output) { // (no PAF: the distances count, as in pileup)
-                        if (edits[q] == DCN_VERIFY_OVER) ++unverified;
-                        else if (edits[q] != DCN_VERIFY_UNPLACED) ++verified, edits_sum += edits[q];
-                        continue;
-                    }
+                ++n.per_record[p.record];
+                n.mapq60 += p.mapq == 60, n.mapq0 += p.mapq == 0;
+                if (a.extend) { // what the flanks gave, and what is left of the read
+                    const uint64_t gained = (pl[q].read_start - p.read_start) + (p.read_end - pl[q].read_end), clipped = p.read_start + (rec.seq_len - p.read_end);
+                    n.rows_extended += gained > 0, n.bases_gained += gained, n.bases_clipped += clipped, n.full_length_rows += clipped == 0;
                 }
-                if (a.pileup) { // (no PAF here: a row that was left out is neither verified nor unverified)
-                    if (edits[q] == DCN_VERIFY_OVER) ++unverified;
-                    else if (edits[q] != DCN_VERIFY_UNPLACED) ++verified, edits_sum += edits[q];
+                if (a.pileup || (a.extend && !a.has_output)) { // (no PAF here: the distances count)
+                    n.tally_distance(edits[q]);
                     continue;
                 }
+                if (a.extend) tags = extend_tags(pl[q], p, rec.seq_len);
                 if (a.verify) {
                     if (edits[q] == DCN_VERIFY_OVER) {
-                        ++unverified;
+                        ++n.unverified;
                         if (a.verified_only) continue;
                     } else {
-                        ++verified, edits_sum += edits[q];
-                        verified_bases += std::max<uint64_t>(p.read_end - p.read_start, p.ref_end - p.ref_start);
+                        ++n.verified, n.edits_sum += edits[q];
+                        n.verified_bases += std::max<uint64_t>(p.read_end - p.read_start, p.ref_end - p.ref_start);
                     }
                 }
-                if (aligns) {
-                    const uint32_t *const runs = cigar.data() + cigar_off[q];
-                    const uint64_t n_ops = cigar_off[q + 1] - cigar_off[q];
-                    cigar_ops += n_ops;
-                    for (uint64_t o = 0; o < n_ops; ++o) op_bases[runs[o] & 15u] += runs[o] >> 4;
-                    append_paf(rows, name, rec.seq_len, p, R.names[p.record], R.lens[p.record], R.k, edits[q], runs, n_ops, a.extend ? tags : std::string());
-                    continue;
-                }
-                append_paf(rows, name, rec.seq_len, p, R.names[p.record], R.lens[p.record], R.k, a.verify ? edits[q] : DCN_VERIFY_UNPLACED);
+                const uint32_t *const runs = aligns ? cigar.data() + cigar_off[q] : nullptr;
+                const uint64_t n_ops = aligns ? cigar_off[q + 1] - cigar_off[q] : 0;
+                n.cigar_ops += n_ops;
+                for (uint64_t o = 0; o < n_ops; ++o) n.op_bases[runs[o] & 15u] += runs[o] >> 4;
+                append_paf(rows, name, rec.seq_len, p, R.names[p.record], R.lens[p.record], R.k, a.verify ? edits[q] : DCN_VERIFY_UNPLACED, runs, n_ops, tags);
             }
         }
         if (prints) out.write(rows);
-    };
-    for_each_batch(rd, b, R.batch_bases, R.batch_reads, on_batch);
-    // (`phase`) between the pile-up and the output: the heterozygous SNV sites of every record from the genotype, a stretch at
-    // a time (a0 the record's base when the genotype holds it, else the lower column); the list set on the map; the duplicate
-    // set emptied and the input read again through the same batch loop, which hands the rows to dcn_phase_batch; the solve.
-    // The counters are still on the map for the output stage below.
-    std::vector<dcn_phase_site> ph_sites;
-    std::vector<dcn_phase_result> ph_res;
-    uint64_t phase_set_count = 0, phased_sites = 0, links_joined = 0, phase_n50 = 0;
-    if (a.phase) {
-        dcn_genotype_params gp = {};
-        gp.ploidy = a.ploidy, gp.min_depth = a.min_depth, gp.min_gq = a.min_gq, gp.min_qual = a.min_qual, gp.err_centi = 477, gp.het_centi = 301;
-        const char *const env = std::getenv("DCN_CLI_STRETCH_BASES");
-        const uint64_t step = env && *env ? std::max<uint64_t>(std::strtoull(env, nullptr, 10), 1) : 1u << 20;
-        std::vector<dcn_genotype_site> gs;
+    }
+    // One batch of the input.  The first pass places, counts, piles up and prints.  (`phase`) The second pass sees the same
+    // batches and hands the same rows, selected and marked as the first time, to link(): it runs no stage that counts or writes.
+    enum class Pass { First, Link };
+    void batch(Pass pass) {
+        place();
+        if (a.extend) extend();
+        if (pass == Pass::Link) {
+            select_and_mark(false);
+            link();
+            return;
+        }
+        align_or_verify();
+        if (piles) select_and_mark(true), pile_up();
+        tally_and_print();
+    }
+
+    // ---- (`phase`) between the pile-up and the output: the counters are still on the map for the output stage ----------------
+    void list_het_sites() { // from the genotype, a stretch at a time
+        const uint64_t step = stretch_bases();
         for (uint32_t r = 0; r < R.n_records; ++r)
             for (uint64_t start = 0; start < R.lens[r]; start += step) {
-                const uint64_t n = std::min<uint64_t>(step, R.lens[r] - start);
+                const uint64_t len = std::min<uint64_t>(step, R.lens[r] - start);
                 uint64_t n_geno = 0;
-                for (int attempt = 0;; ++attempt) {
-                    const int rc = dcn_anchor_map_genotype(R.map.p, &gp, r, start, n, nullptr, nullptr, gs.data(), gs.size(), &n_geno);
-                    if (rc != DCN_ERR_CAPACITY || attempt) {
-                        deacon::check(rc);
-                        break;
-                    }
-                    gs.resize(n_geno);
-                }
-                for (uint64_t i = 0; i < n_geno; ++i) {
-                    const dcn_genotype_site &g = gs[i];
-                    unsigned x = g.gt, y = 0;
-                    for (y = 0; (y + 1) * (y + 2) / 2 <= g.gt; ++y) {}
-                    x = g.gt - y * (y + 1) / 2;
-                    if (x == y) continue;
-                    dcn_phase_site site = {};
-                    site.pos = g.pos, site.record = r;
-                    site.a0 = (uint8_t)(y == g.ref_code ? y : x); // (x < y: the record's base, else the lower column)
-                    site.a1 = (uint8_t)(y == g.ref_code ? x : y);
-                    ph_sites.push_back(site);
-                }
+                with_room(ph_geno, [&](dcn_genotype_site *into, size_t room, uint64_t &count) {
+                    const int rc = dcn_anchor_map_genotype(R.map.p, &gprm, r, start, len, nullptr, nullptr, into, room, &n_geno);
+                    count = n_geno;
+                    return rc;
+                });
+                dcn_phase_site site;
+                for (uint64_t i = 0; i < n_geno; ++i)
+                    if (phase_site_of(ph_geno[i], a.ploidy, r, site)) ph_sites.push_back(site);
             }
+        n.phase_sites = ph_sites.size();
+    }
+    // the list set on the map; the duplicate set emptied and the input read again through the same batch stages; the solve
+    void phase() {
+        list_het_sites();
         deacon::check(dcn_anchor_map_phase_sites(R.map.p, ph_sites.data(), ph_sites.size()));
         if (!ph_sites.empty()) {
             deacon::check(dcn_anchor_map_duplicates_reset(R.map.p));
             FastxReader again(a.input);
-            second_pass = true;
-            for_each_batch(again, b, R.batch_bases, R.batch_reads, on_batch);
-            second_pass = false;
-            dcn_phase_params pp = {};
-            pp.min_reads = a.min_link_reads, pp.max_minor_permille = a.max_link_minor;
+            for_each_batch(again, b, R.batch_bases, R.batch_reads, [this] { batch(Pass::Link); });
+            const dcn_phase_params pp = phase_params(opt);
             ph_res.resize(ph_sites.size());
             deacon::check(dcn_anchor_map_phase_solve(R.map.p, &pp, ph_res.data()));
         }
         TextOut sets_out, links_out;
-        if (a.has_phase_sets) sets_out.open(a.phase_sets, false), sets_out.write("record\tfirst_pos\tlast_pos\tsites\n");
-        if (a.has_links) links_out.open(a.links, false), links_out.write("record\tpos\tnext_pos\tn00\tn01\tn10\tn11\tjoined\n");
-        std::string set_rows, link_rows;
-        std::vector<uint64_t> spans;
-        for (size_t s = 0; s < ph_sites.size();) {
-            size_t e = s + 1; // the set [s, e)
-            while (e < ph_sites.size() && !(ph_res[e].flags & DCN_PHASE_HEAD)) ++e;
-            if (e - s >= 2) {
-                ++phase_set_count, phased_sites += e - s;
-                spans.push_back(ph_sites[e - 1].pos - ph_sites[s].pos + 1);
-                set_rows += R.names[ph_sites[s].record] + '\t' + std::to_string(ph_sites[s].pos) + '\t' + std::to_string(ph_sites[e - 1].pos) + '\t' +
-                            std::to_string(e - s) + '\n';
-            }
-            s = e;
-        }
-        for (size_t s = 0; s + 1 < ph_sites.size(); ++s) {
-            links_joined += (ph_res[s].flags & DCN_PHASE_JOINED) != 0;
-            if (ph_sites[s + 1].record != ph_sites[s].record) continue;
-            link_rows += R.names[ph_sites[s].record] + '\t' + std::to_string(ph_sites[s].pos) + '\t' + std::to_string(ph_sites[s + 1].pos);
-            for (int c = 0; c < 4; ++c) link_rows += '\t' + std::to_string(ph_res[s].link[c]);
-            link_rows += (ph_res[s].flags & DCN_PHASE_JOINED) ? "\t1\n" : "\t0\n";
-        }
-        std::sort(spans.begin(), spans.end(), std::greater<uint64_t>());
-        uint64_t total = 0, sum = 0;
-        for (uint64_t v : spans) total += v;
-        for (uint64_t v : spans) {
-            sum += v;
-            if (2 * sum >= total) {
-                phase_n50 = v;
-                break;
-            }
-        }
-        if (a.has_phase_sets) sets_out.write(set_rows), sets_out.finish();
-        if (a.has_links) links_out.write(link_rows), links_out.finish();
+        if (a.has_phase_sets) sets_out.open(a.phase_sets, false), sets_out.write(phase_sets_header());
+        if (a.has_links) links_out.open(a.links, false), links_out.write(links_header());
+        const PhaseSets sets = phase_sets(ph_sites.data(), ph_res.data(), ph_sites.size(), R.names);
+        n.phase_sets = sets.sets, n.phased_sites = sets.phased_sites, n.links_joined = sets.links_joined, n.phase_n50 = sets.n50;
+        if (a.has_phase_sets) sets_out.write(sets.set_rows), sets_out.finish();
+        if (a.has_links) links_out.write(sets.link_rows), links_out.finish();
     }
-    size_t ph_cursor = 0; // the next site of the list: the output stage meets them in the list's order
-    // pileup: the counters of every record, a stretch at a time, as TSV; the sites of the same stretches
-    uint64_t covered = 0, n_sites = 0, column_sum[DCN_PILEUP_COLUMNS] = {};
-    uint64_t insertion_events = 0, inserted_bases = 0, insertion_alleles = 0, substitutions = 0, deleted_positions = 0, consensus_bases = 0,
-             uncalled_positions = 0; // (consensus)
-    uint64_t qual_sum[4] = {};       // (call)
-    uint64_t genotyped_positions = 0, vcf_sites = 0, het_sites = 0, hom_alt_sites = 0; // (genotype)
-    uint64_t deletion_events = 0, deleted_bases = 0, indel_sites = 0, insertion_sites = 0, deletion_sites = 0, het_indel_sites = 0,
-             hom_indel_sites = 0; // (indels)
-    uint64_t strand_bias_sites = 0, one_strand_sites = 0, filtered_sites = 0; // (strand)
-    uint64_t n_blocks = 0, block_bases = 0, no_coverage_bases = 0, uncalled_bases = 0, ref_bases = 0, record_bases = 0; // (gvcf)
-    std::vector<uint64_t> ref_bases_by_band(a.gq_bands.size() + 1, 0);
-    if (piles) {
-        TextOut sites_out, pile_file, fasta_out, variants_out;
-        std::unique_ptr<Output> vcf_out; // (.gz as BGZF, .zst and .xz by extension, as filter's outputs)
-        const auto vcf_write = [&vcf_out](const std::string &text) { vcf_out->write(std::vector<char>(text.begin(), text.end())); };
-        std::unique_ptr<Output> gvcf_out; // (`gvcf`)
-        const auto gvcf_write = [&gvcf_out](const std::string &text) { gvcf_out->write(std::vector<char>(text.begin(), text.end())); };
-        TextOut callable_out;
-        std::string vcf_head; // the header without its #CHROM line
-        if (a.has_vcf || a.has_gvcf) { // VCF 4.2, SNVs only: indels stay in --variants (`indels`: and as INDEL lines here)
-            if (a.has_vcf) vcf_out.reset(new Output(a.vcf, 2));
-            std::string head = std::string("##fileformat=VCFv4.2\n##source=deacon-hip ") + VERSION + "\n";
-            for (uint32_t r = 0; r < R.n_records; ++r) head += "##contig=<ID=" + R.names[r] + ",length=" + std::to_string(R.lens[r]) + ">\n";
-            if (a.strand)
-                head += "##FILTER=<ID=strand_bias,Description=\"SB at or above --max-sb: the allele and the strand are not independent\">\n"
-                        "##FILTER=<ID=one_strand,Description=\"Both strands cover the site, the allele is on fewer than --min-alt-strand reads of one\">\n";
-            head += "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Depth: reads with a base, an N or a deletion at the position\">\n";
-            if (a.strand)
-                head += "##INFO=<ID=SB,Number=1,Type=Float,Description=\"Strand bias: chi-square of the 2 x 2 table of allele by strand, one degree of freedom\">\n";
-            if (a.indels)
-                head += "##INFO=<ID=INDEL,Number=0,Type=Flag,Description=\"An insertion or a deletion\">\n"
-                        "##INFO=<ID=IDV,Number=1,Type=Integer,Description=\"Reads that carry the allele\">\n"
-                        "##INFO=<ID=IEV,Number=1,Type=Integer,Description=\"Insertions behind, or deletions that begin at, the position, of any allele\">\n";
-            if (a.normalize) head += "##left_aligned=The positions of insertions and deletions are left-aligned per read\n";
-            head += "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
-                    "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality: phred gap to the second best genotype, at most 99\">\n"
-                    "##FORMAT=<ID=DP,Number=1,Type=Integer,Description=\"Bases A, C, G, T of at least the minimum base quality\">\n"
-                    "##FORMAT=<ID=AD,Number=R,Type=Integer,Description=\"Such bases per allele\">\n";
-            if (a.strand)
-                head += "##FORMAT=<ID=ADF,Number=R,Type=Integer,Description=\"AD on the forward strand\">\n"
-                        "##FORMAT=<ID=ADR,Number=R,Type=Integer,Description=\"AD on the reverse strand\">\n";
-            head += "##FORMAT=<ID=PL,Number=G,Type=Integer,Description=\"Phred-scaled genotype likelihoods, at most 255\">\n";
-            if (a.phase) head += "##FORMAT=<ID=PS,Number=1,Type=Integer,Description=\"Phase set: POS of the first site of the set the genotype is phased in\">\n";
-            vcf_head = head;
-            head += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + a.sample + "\n";
-            if (a.has_vcf) vcf_write(head);
-        }
-        if (a.has_gvcf) { // the --vcf header and, in front of #CHROM, what the block lines use
-            gvcf_out.reset(new Output(a.gvcf_out, 2));
-            std::string head = vcf_head +
-                               "##ALT=<ID=NON_REF,Description=\"Any allele other than the reference's: the line is a reference block\">\n"
-                               "##INFO=<ID=END,Number=1,Type=Integer,Description=\"Last position of the block\">\n"
-                               "##FORMAT=<ID=MIN_DP,Number=1,Type=Integer,Description=\"Smallest DP of the block's positions\">\n";
-            for (size_t b = 0; b <= a.gq_bands.size(); ++b) {
-                const unsigned lo = b ? a.gq_bands[b - 1] : 0u, hi = b < a.gq_bands.size() ? a.gq_bands[b] : 100u;
-                head += "##GVCFBlock" + std::to_string(lo) + "-" + std::to_string(hi) + "=minGQ=" + std::to_string(lo) + "(inclusive),maxGQ=" +
-                        std::to_string(hi) + "(exclusive)\n";
-            }
-            gvcf_write(head + "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + a.sample + "\n");
+
+    // ---- the output: the counters of every record, a stretch at a time ----------------------------------------------------------
+    void open_record_outputs() {
+        if (a.has_vcf || a.has_gvcf) {
+            const std::string head = vcf_header(VERSION, VcfModes{a.indels, a.normalize, a.strand, a.phase}, R.names, R.lens);
+            if (a.has_vcf) vcf_out.reset(new Output(a.vcf, 2)), write(*vcf_out, head + vcf_chrom_line(a.sample));
+            if (a.has_gvcf) gvcf_out.reset(new Output(a.gvcf_out, 2)), write(*gvcf_out, head + gvcf_header_lines(a.gq_bands) + vcf_chrom_line(a.sample));
         }
         if (a.has_callable) callable_out.open(a.callable, false);
-        dcn_genotype_params gprm = {};
-        gprm.ploidy = a.ploidy;
-        gprm.min_depth = a.min_depth;
-        gprm.min_gq = a.min_gq;
-        gprm.min_qual = a.min_qual;
-        gprm.err_centi = 477; // 1000 log10 3 and 1000 log10 2, rounded: rule G2's and G3's conventions
-        gprm.het_centi = 301;
-        std::vector<uint8_t> geno_gt;
-        std::vector<dcn_genotype_site> geno_sites;
-        std::string vcf_rows;
-        dcn_indel_params iprm = {}; // (`indels`)
-        iprm.ploidy = a.ploidy;
-        iprm.min_depth = a.min_depth;
-        iprm.min_gq = a.min_gq;
-        iprm.min_qual = a.min_qual;
-        iprm.min_count = a.min_indel_count;
-        iprm.indel_centi = 100 * a.indel_qual;
-        iprm.het_centi = 301;
-        std::vector<dcn_indel_site> ind_sites;
-        std::vector<uint8_t> ind_bases, ref_more;
-        dcn_strand_params sprm = {}; // (`strand`)
-        sprm.max_sb_centi = a.max_sb;
-        sprm.min_alt_strand = a.min_alt_strand;
-        sprm.min_strand_depth = a.min_strand_depth;
-        std::vector<dcn_strand_query> strand_queries;
-        std::vector<dcn_strand_site> snv_strand, ind_strand;
-        std::vector<uint32_t> ind_reverse, planes;
-        // the FILTER column and SB of a site, and its place in the summary
-        const auto strand_filter = [&](const dcn_strand_site &e) {
-            strand_bias_sites += (e.flags & DCN_STRAND_BIAS) != 0, one_strand_sites += (e.flags & DCN_STRAND_ONE_SIDED) != 0, filtered_sites += e.flags != 0;
-            return std::string(e.flags == 0 ? "PASS" : e.flags == DCN_STRAND_BIAS ? "strand_bias" : e.flags == DCN_STRAND_ONE_SIDED ? "one_strand" : "strand_bias;one_strand");
-        };
-        const auto strand_sb = [](const dcn_strand_site &e) {
-            char text[32];
-            std::snprintf(text, sizeof text, "%u.%02u", e.sb_centi / 100u, e.sb_centi % 100u);
-            return std::string(text);
-        };
-        std::vector<std::pair<uint64_t, size_t>> snv_at; // per SNV line of the stretch: its POS and where it begins in vcf_rows
-        std::string merged_rows;
-        if (a.indels) deacon::check(dcn_anchor_map_deletions_info(R.map.p, &deletion_events, &deleted_bases));
+        if (a.indels) deacon::check(dcn_anchor_map_deletions_info(R.map.p, &n.deletion_events, &n.deleted_bases));
         if (a.has_sites) sites_out.open(a.sites, false);
         if (a.has_fasta) fasta_out.open(a.fasta, true);
-        if (a.has_variants) variants_out.open(a.variants, false);
-        if (a.has_variants) variants_out.write(a.call ? "record\tpos\ttype\tref\talt\tdepth\tcount\tevents\tref_qual\talt_qual\n"
-                                                      : "record\tpos\ttype\tref\talt\tdepth\tcount\tevents\n");
-        if (a.consensus) deacon::check(dcn_anchor_map_insertions_info(R.map.p, &insertion_events, &inserted_bases));
-        std::vector<uint8_t> calls, allele_bases;
-        std::vector<dcn_insertion_allele> alleles;
-        std::string seq, variant_rows;
+        if (a.has_variants) variants_out.open(a.variants, false), variants_out.write(variants_header(a.call));
+        if (a.consensus) deacon::check(dcn_anchor_map_insertions_info(R.map.p, &n.insertion_events, &n.inserted_bases));
         if (a.extend && a.has_pileup_out) pile_file.open(a.pileup_out, false);
-        TextOut *const tsv = a.pileup ? &out : a.has_pileup_out ? &pile_file : nullptr; // (`extend --sites` alone: no table)
-        if (tsv)
-            tsv->write(a.strand ? "record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\tqA\tqC\tqG\tqT\trA\trC\trG\trT\n"
-                       : a.call ? "record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\tqA\tqC\tqG\tqT\n"
-                                : "record\tpos\tref\tA\tC\tG\tT\tN\tdel\tins\trev\n");
-        if (a.has_sites) sites_out.write("record\tpos\tref\tcall\tdepth\tflags\n");
-        dcn_pileup_call_params cprm = {};
-        cprm.min_depth = a.min_depth;
-        cprm.min_permille = a.min_frac;
-        // (DCN_CLI_STRETCH_BASES: a test hook, so that a short record has the seams between two stretches)
-        const char *const stretch_env = std::getenv("DCN_CLI_STRETCH_BASES");
-        const uint64_t stretch = stretch_env && *stretch_env ? std::max<uint64_t>(std::strtoull(stretch_env, nullptr, 10), 1) : 1u << 20;
-        std::vector<uint32_t> counts, site_info, qsums;
-        // (`call`) the mean quality of a column's bases at a position, rounded down; "." when it has none
-        const auto mean_qual = [](const uint32_t *c, const uint32_t *qs, int col) {
-            return col < 0 || c[col] == 0 ? std::string(".") : std::to_string(qs[col] / c[col]);
-        };
-        const auto base_column = [](char ch) { return ch == 'A' ? DCN_PILEUP_A : ch == 'C' ? DCN_PILEUP_C : ch == 'G' ? DCN_PILEUP_G : ch == 'T' ? DCN_PILEUP_T : -1; };
-        std::vector<uint64_t> site_pos;
-        std::vector<uint8_t> ref_text;
-        std::string site_rows;
-        // (`gvcf`) rules B1-B9 a stretch at a time: the stretch's blocks behind the one block that the stretch before left open at
-        // the seam, merged (rule B7); every block but an open last one is final and goes out, with the stretch's VCF lines, in
-        // POS order, a block's line in front of a VCF line of its POS.  No per-position bytes are fetched.
-        dcn_block_params bprm = {};
-        bprm.ploidy = a.ploidy, bprm.min_depth = a.min_depth, bprm.min_gq = a.min_gq, bprm.min_qual = a.min_qual, bprm.err_centi = 477, bprm.het_centi = 301;
-        bprm.n_edges = (uint32_t)std::min<size_t>(a.gq_bands.size(), 16);
-        for (size_t b = 0; b < a.gq_bands.size() && b < 16; ++b) bprm.edges[b] = (uint8_t)std::min(a.gq_bands[b], 255u);
-        std::vector<dcn_reference_block> blocks, fresh;
-        std::vector<uint64_t> breaks;
-        std::string gvcf_rows;
-        uint64_t bed_from = 0, bed_to = 0; // the callable interval that is open, [bed_from, bed_to) with label bed_label
-        const char *bed_label = nullptr;
-        std::string bed_rows;
-        const auto bed_add = [&](uint32_t r, uint64_t from, uint64_t to, const char *label) { // label = nullptr: the record ends
-            if (label && bed_label == label && bed_to == from) {
-                bed_to = to;
-                return;
-            }
-            if (bed_label && bed_to > bed_from)
-                bed_rows += R.names[r] + '\t' + std::to_string(bed_from) + '\t' + std::to_string(bed_to) + '\t' + bed_label + '\n';
-            bed_from = from, bed_to = to, bed_label = label;
-        };
-        static const char *const LABEL_NO_COVERAGE = "NO_COVERAGE", *const LABEL_LOW = "LOW_CONFIDENCE", *const LABEL_CALLABLE = "CALLABLE";
-        uint64_t bed_cursor = 0; // the first position of the record that no final block and no gap in front of one has covered
-        for (uint32_t r = 0; r < R.n_records; ++r) {
-            if (a.has_fasta) fasta_out.write(">" + R.names[r] + "\n");
-            record_bases += R.lens[r];
-            blocks.clear();
-            bed_cursor = 0, bed_label = nullptr;
-            for (uint64_t start = 0; start < R.lens[r]; start += stretch) {
-                const uint64_t n = std::min<uint64_t>(stretch, R.lens[r] - start);
-                counts.resize(n * DCN_PILEUP_COLUMNS);
-                if (a.consensus) calls.resize(n);
-                ref_text.resize(n);
-                deacon::check(dcn_anchor_map_pileup_fetch(R.map.p, r, start, n, counts.data()));
-                if (a.call) {
-                    qsums.resize(n * 4);
-                    deacon::check(dcn_anchor_map_pileup_fetch_qualities(R.map.p, r, start, n, qsums.data()));
-                    for (uint64_t q = 0; q < n * 4; ++q) qual_sum[q & 3] += qsums[q];
-                }
-                if (a.strand && tsv) {
-                    planes.resize(n * 4);
-                    deacon::check(dcn_anchor_map_pileup_fetch_strands(R.map.p, r, start, n, planes.data()));
-                }
-                deacon::check(dcn_anchor_map_fetch(R.map.p, r, start, n, ref_text.data()));
-                rows.clear();
-                for (uint64_t q = 0; q < n; ++q) {
-                    const uint32_t *const c = counts.data() + q * DCN_PILEUP_COLUMNS;
-                    uint64_t depth = 0;
-                    for (int col = 0; col <= DCN_PILEUP_DEL; ++col) depth += c[col];
-                    for (int col = 0; col < DCN_PILEUP_COLUMNS; ++col) column_sum[col] += c[col];
-                    covered += depth > 0;
-                    if (!a.all_positions && depth == 0 && c[DCN_PILEUP_INS] == 0) continue;
-                    rows += R.names[r] + '\t' + std::to_string(start + q) + '\t' + (char)ref_text[q];
-                    for (int col = 0; col < DCN_PILEUP_COLUMNS; ++col) rows += '\t' + std::to_string(c[col]);
-                    if (a.call)
-                        for (int col = 0; col < 4; ++col) rows += '\t' + std::to_string(qsums[q * 4 + col]);
-                    if (a.strand && tsv)
-                        for (int col = 0; col < 4; ++col) rows += '\t' + std::to_string(planes[q * 4 + col]);
-                    rows += '\n';
-                }
-                if (tsv) tsv->write(rows);
-                uint64_t found = 0;
-                for (int attempt = 0;; ++attempt) { // (dcn_locate_batch's convention: the first call reports the size)
-                    const int rc = dcn_anchor_map_pileup_call(R.map.p, &cprm, r, start, n, a.consensus ? calls.data() : nullptr, site_pos.data(), site_info.data(),
-                                                              site_pos.size(), &found);
-                    if (rc != DCN_ERR_CAPACITY || attempt) {
-                        deacon::check(rc);
-                        break;
-                    }
-                    site_pos.resize(found);
-                    site_info.resize(found);
-                }
-                n_sites += found;
-                if (a.consensus) { // rule L7 over the stretch: the called insertions, then position by position
-                    uint64_t n_alleles = 0, n_inserted = 0;
-                    for (int attempt = 0;; ++attempt) {
-                        const int rc = dcn_anchor_map_insertions_call(R.map.p, &cprm, r, start, n, alleles.data(), alleles.size(), allele_bases.data(),
-                                                                      allele_bases.size(), &n_alleles, &n_inserted);
-                        if (rc != DCN_ERR_CAPACITY || attempt) {
-                            deacon::check(rc);
-                            break;
-                        }
-                        alleles.resize(n_alleles);
-                        allele_bases.resize(n_inserted);
-                    }
-                    insertion_alleles += n_alleles;
-                    seq.clear();
-                    variant_rows.clear();
-                    uint64_t next = 0; // the next allele: they are in ascending position
-                    for (uint64_t q = 0; q < n; ++q) {
-                        const uint32_t *const c = counts.data() + q * DCN_PILEUP_COLUMNS;
-                        uint64_t depth = 0;
-                        for (int col = 0; col <= DCN_PILEUP_DEL; ++col) depth += c[col];
-                        const dcn_insertion_allele *const al = next < n_alleles && alleles[next].pos == start + q ? &alleles[next++] : nullptr;
-                        const auto insertion = [&] {
-                            const std::string alt((const char *)allele_bases.data() + al->bases_offset, al->len);
-                            seq += alt;
-                            if (a.has_variants)
-                                variant_rows += R.names[r] + '\t' + std::to_string(start + q) + '\t' + (al->flags & DCN_INSERTION_FRONT ? "INS_FRONT" : "INS") +
-                                                "\t.\t" + alt + '\t' + std::to_string(depth) + '\t' + std::to_string(al->count) + '\t' +
-                                                std::to_string(al->events) + (a.call ? "\t.\t.\n" : "\n");
-                        };
-                        if (al && (al->flags & DCN_INSERTION_FRONT)) insertion();
-                        const char call = (char)calls[q], ref = (char)ref_text[q];
-                        if (call == 'N') { // (not called: P6 writes N there and nowhere else)
-                            ++uncalled_positions;
-                            seq += a.fill_ref ? ref : 'N';
-                        } else {
-                            const uint32_t best = call == '-' ? c[DCN_PILEUP_DEL] : c[call == 'A' ? DCN_PILEUP_A : call == 'C' ? DCN_PILEUP_C : call == 'G' ? DCN_PILEUP_G : DCN_PILEUP_T];
-                            if (call != '-') seq += call;
-                            if (call == '-') ++deleted_positions;
-                            else if (call != ref) ++substitutions;
-                            if (a.has_variants && call != ref) {
-                                variant_rows += R.names[r] + '\t' + std::to_string(start + q) + '\t' + (call == '-' ? "DEL" : "SUB") + '\t' + ref + '\t' + call +
-                                                '\t' + std::to_string(depth) + '\t' + std::to_string(best) + "\t0";
-                                if (a.call && call == '-') variant_rows += "\t.\t.";
-                                else if (a.call)
-                                    variant_rows += '\t' + mean_qual(c, qsums.data() + q * 4, base_column(ref)) + '\t' + mean_qual(c, qsums.data() + q * 4, base_column(call));
-                                variant_rows += '\n';
-                            }
-                        }
-                        if (al && !(al->flags & DCN_INSERTION_FRONT)) insertion();
-                    }
-                    consensus_bases += seq.size();
-                    if (a.has_fasta) fasta_out.write(seq);
-                    if (a.has_variants) variants_out.write(variant_rows);
-                }
-                if (a.genotype) { // rules G1-G8 over the stretch; a site's line is written from the site alone
-                    geno_gt.resize(n);
-                    uint64_t n_geno = 0;
-                    for (int attempt = 0;; ++attempt) {
-                        const int rc = dcn_anchor_map_genotype(R.map.p, &gprm, r, start, n, geno_gt.data(), nullptr, geno_sites.data(), geno_sites.size(), &n_geno);
-                        if (rc != DCN_ERR_CAPACITY || attempt) {
-                            deacon::check(rc);
-                            break;
-                        }
-                        geno_sites.resize(n_geno);
-                    }
-                    for (uint64_t q = 0; q < n; ++q) genotyped_positions += geno_gt[q] != DCN_GENOTYPE_NONE;
-                    vcf_sites += n_geno;
-                    vcf_rows.clear();
-                    snv_at.clear();
-                    uint64_t gvcf_indels = 0; // (`gvcf`) the INDEL lines of the stretch: their positions are the breaks
-                    if (a.strand) { // rules S3, S5 and S6 at the stretch's sites: ALT = the genotype's alleles other than the record's base
-                        strand_queries.assign(n_geno, dcn_strand_query{});
-                        snv_strand.resize(n_geno);
-                        for (uint64_t i = 0; i < n_geno; ++i) {
-                            const dcn_genotype_site &g = geno_sites[i];
-                            unsigned x = g.gt, y = g.gt;
-                            if (a.ploidy == 2)
-                                for (y = 0; (y + 1) * (y + 2) / 2 <= g.gt; ++y) {}
-                            if (a.ploidy == 2) x = g.gt - y * (y + 1) / 2;
-                            strand_queries[i].pos = g.pos;
-                            strand_queries[i].ref_code = g.ref_code;
-                            strand_queries[i].alt_mask = ((1u << x) | (1u << y)) & ~(1u << g.ref_code);
-                        }
-                        deacon::check(dcn_anchor_map_strand_evidence(R.map.p, &sprm, r, strand_queries.data(), n_geno, snv_strand.data()));
-                    }
-                    for (uint64_t i = 0; i < n_geno; ++i) {
-                        const dcn_genotype_site &g = geno_sites[i];
-                        if (a.indels) snv_at.emplace_back(g.pos + 1, vcf_rows.size());
-                        // the genotype's alleles x <= y (G3's order: index y (y + 1) / 2 + x), then (REF, ALTs in A C G T order)
-                        unsigned x = g.gt, y = g.gt;
-                        if (a.ploidy == 2)
-                            for (y = 0; (y + 1) * (y + 2) / 2 <= g.gt; ++y) {}
-                        if (a.ploidy == 2) x = g.gt - y * (y + 1) / 2;
-                        (x != y ? het_sites : hom_alt_sites) += 1;
-                        unsigned alleles[3] = {g.ref_code, 0, 0}, n_alleles = 1;
-                        if (x != g.ref_code) alleles[n_alleles++] = x;
-                        if (y != g.ref_code && y != x) alleles[n_alleles++] = y;
-                        const auto index_of = [&](unsigned c) { return c == alleles[0] ? 0u : c == alleles[1] ? 1u : 2u; };
-                        const auto pair_index = [](unsigned p, unsigned q2) { return p <= q2 ? q2 * (q2 + 1) / 2 + p : p * (p + 1) / 2 + q2; };
-                        // (`phase`) the site's entry of the list, when the line is heterozygous and its set has two sites or more
-                        const dcn_phase_result *ph = nullptr;
-                        size_t ph_at = 0;
-                        if (a.phase && x != y) {
-                            while (ph_cursor < ph_sites.size() &&
-                                   (ph_sites[ph_cursor].record < r || (ph_sites[ph_cursor].record == r && ph_sites[ph_cursor].pos < g.pos)))
-                                ++ph_cursor;
-                            if (ph_cursor < ph_res.size() && ph_sites[ph_cursor].record == r && ph_sites[ph_cursor].pos == g.pos &&
-                                ((ph_res[ph_cursor].flags & DCN_PHASE_JOINED) || !(ph_res[ph_cursor].flags & DCN_PHASE_HEAD)))
-                                ph = &ph_res[ph_cursor], ph_at = ph_cursor;
-                        }
-                        vcf_rows += R.names[r] + '\t' + std::to_string(g.pos + 1) + "\t.\t" + "ACGT"[g.ref_code] + '\t';
-                        for (unsigned k = 1; k < n_alleles; ++k) vcf_rows += std::string(k > 1 ? "," : "") + "ACGT"[alleles[k]];
-                        if (a.strand)
-                            vcf_rows += '\t' + std::to_string(g.qual) + '\t' + strand_filter(snv_strand[i]) + "\tDP=" + std::to_string(g.depth) +
-                                        ";SB=" + strand_sb(snv_strand[i]) + (ph ? "\tGT:GQ:DP:AD:ADF:ADR:PL:PS\t" : "\tGT:GQ:DP:AD:ADF:ADR:PL\t");
-                        else
-                            vcf_rows += '\t' + std::to_string(g.qual) + "\tPASS\tDP=" + std::to_string(g.depth) + "\tGT:GQ:DP:AD:PL\t";
-                        if (ph) { // haplotype 1 carries a[hap], haplotype 2 a[1 - hap] (rule H6)
-                            const unsigned al[2] = {ph_sites[ph_at].a0, ph_sites[ph_at].a1};
-                            vcf_rows += std::to_string(index_of(al[ph->hap & 1u])) + '|' + std::to_string(index_of(al[1u - (ph->hap & 1u)]));
-                        } else if (a.ploidy == 2) vcf_rows += std::to_string(std::min(index_of(x), index_of(y))) + '/' + std::to_string(std::max(index_of(x), index_of(y)));
-                        else vcf_rows += std::to_string(index_of(x));
-                        vcf_rows += ':' + std::to_string(g.gq) + ':' + std::to_string((uint64_t)g.ad[0] + g.ad[1] + g.ad[2] + g.ad[3]) + ':';
-                        for (unsigned k = 0; k < n_alleles; ++k) vcf_rows += (k ? "," : "") + std::to_string(g.ad[alleles[k]]);
-                        vcf_rows += ':';
-                        if (a.strand) { // over the same alleles as AD
-                            for (unsigned k = 0; k < n_alleles; ++k) vcf_rows += (k ? "," : "") + std::to_string(snv_strand[i].fwd[alleles[k]]);
-                            vcf_rows += ':';
-                            for (unsigned k = 0; k < n_alleles; ++k) vcf_rows += (k ? "," : "") + std::to_string(snv_strand[i].rev[alleles[k]]);
-                            vcf_rows += ':';
-                        }
-                        bool first = true;
-                        for (unsigned j = 0; j < n_alleles; ++j)
-                            for (unsigned i2 = 0; i2 <= (a.ploidy == 2 ? j : 0u); ++i2) {
-                                const unsigned at = a.ploidy == 2 ? pair_index(alleles[i2], alleles[j]) : alleles[j];
-                                vcf_rows += (first ? "" : ",") + std::to_string(g.pl[at]);
-                                first = false;
-                            }
-                        if (ph) vcf_rows += ':' + std::to_string(ph->set_pos + 1);
-                        vcf_rows += '\n';
-                    }
-                    if (a.indels) { // rules I1-I8 over the stretch: the INDEL lines, merged into the SNV lines by POS, the SNV line of a POS first
-                        uint64_t n_ind = 0, n_ind_bases = 0;
-                        for (int attempt = 0;; ++attempt) {
-                            const int rc = dcn_anchor_map_indels_genotype(R.map.p, &iprm, r, start, n, ind_sites.data(), ind_sites.size(), ind_bases.data(),
-                                                                          ind_bases.size(), &n_ind, &n_ind_bases);
-                            if (rc != DCN_ERR_CAPACITY || attempt) {
-                                deacon::check(rc);
-                                break;
-                            }
-                            ind_sites.resize(n_ind);
-                            ind_bases.resize(n_ind_bases);
-                        }
-                        indel_sites += n_ind;
-                        gvcf_indels = n_ind;
-                        if (a.strand) { // rule S4: the winners' reverse events from the ledgers, then the table, the score and the flags
-                            ind_reverse.resize(n_ind);
-                            ind_strand.resize(n_ind);
-                            strand_queries.assign(n_ind, dcn_strand_query{});
-                            deacon::check(dcn_anchor_map_indels_strand(R.map.p, r, ind_sites.data(), n_ind, ind_bases.data(), ind_reverse.data()));
-                            for (uint64_t i = 0; i < n_ind; ++i) {
-                                strand_queries[i].pos = ind_sites[i].pos;
-                                strand_queries[i].kind = 1;
-                                strand_queries[i].count = ind_sites[i].count;
-                                strand_queries[i].count_reverse = ind_reverse[i];
-                            }
-                            deacon::check(dcn_anchor_map_strand_evidence(R.map.p, &sprm, r, strand_queries.data(), n_ind, ind_strand.data()));
-                        }
-                        // bases [from, from + count) of the record: the stretch's own, or fetched where a line reaches beyond it
-                        const auto ref_bases = [&](uint64_t from, uint64_t count) {
-                            if (from >= start && from + count <= start + n) return std::string((const char *)ref_text.data() + (from - start), count);
-                            ref_more.resize(count);
-                            deacon::check(dcn_anchor_map_fetch(R.map.p, r, from, count, ref_more.data()));
-                            return std::string(ref_more.begin(), ref_more.end());
-                        };
-                        merged_rows.clear();
-                        size_t next_snv = 0;
-                        const auto snvs_up_to = [&](uint64_t pos) {
-                            while (next_snv < snv_at.size() && snv_at[next_snv].first <= pos) {
-                                const size_t from = snv_at[next_snv].second, to = next_snv + 1 < snv_at.size() ? snv_at[next_snv + 1].second : vcf_rows.size();
-                                merged_rows.append(vcf_rows, from, to - from);
-                                ++next_snv;
-                            }
-                        };
-                        for (uint64_t i = 0; i < n_ind; ++i) {
-                            const dcn_indel_site &s = ind_sites[i];
-                            uint64_t pos1 = 0;
-                            std::string ref_allele, alt;
-                            if (s.flags & DCN_INDEL_DELETION) {
-                                ++deletion_sites;
-                                if (s.len >= R.lens[r]) // (every placement of the tool holds a k-mer of '=' bases)
-                                    die("internal error: a deletion of the whole record '" + R.names[r] + "'");
-                                ref_allele = ref_bases(s.pos > 0 ? s.pos - 1 : 0, (uint64_t)s.len + 1);
-                                pos1 = s.pos > 0 ? s.pos : 1;
-                                alt = s.pos > 0 ? ref_allele.substr(0, 1) : ref_allele.substr(s.len, 1);
-                            } else {
-                                ++insertion_sites;
-                                const std::string ins((const char *)ind_bases.data() + s.bases_offset, s.len);
-                                const bool front = (s.flags & DCN_INDEL_FRONT) != 0;
-                                ref_allele = ref_bases(front && s.pos > 0 ? s.pos - 1 : s.pos, 1);
-                                pos1 = front ? (s.pos > 0 ? s.pos : 1) : s.pos + 1;
-                                alt = front && s.pos == 0 ? ins + ref_allele : ref_allele + ins;
-                            }
-                            const bool hom = s.gt == a.ploidy; // V/V, or V at ploidy 1
-                            (hom ? hom_indel_sites : het_indel_sites) += 1;
-                            const uint32_t others = s.depth >= s.count ? s.depth - s.count : 0;
-                            snvs_up_to(pos1);
-                            merged_rows += R.names[r] + '\t' + std::to_string(pos1) + "\t.\t" + ref_allele + '\t' + alt + '\t' + std::to_string(s.qual) + '\t' +
-                                           (a.strand ? strand_filter(ind_strand[i]) : std::string("PASS")) + "\tINDEL;DP=" + std::to_string(s.depth) +
-                                           ";IDV=" + std::to_string(s.count) + ";IEV=" + std::to_string(s.events) +
-                                           (a.strand ? ";SB=" + strand_sb(ind_strand[i]) + "\tGT:GQ:DP:AD:ADF:ADR:PL\t" : std::string("\tGT:GQ:DP:AD:PL\t")) +
-                                           (a.ploidy == 1 ? "1" : hom ? "1/1" : "0/1") + ':' + std::to_string(s.gq) + ':' +
-                                           std::to_string((uint64_t)others + s.count) + ':' + std::to_string(others) + ',' + std::to_string(s.count) + ':';
-                            if (a.strand) { // o,a split by strand: rule S4's table, a,c forward and b,d reverse
-                                const uint32_t *const t = ind_strand[i].table;
-                                merged_rows += std::to_string(t[0]) + ',' + std::to_string(t[2]) + ':' + std::to_string(t[1]) + ',' + std::to_string(t[3]) + ':';
-                            }
-                            merged_rows += std::to_string(s.pl[0]) + ',' + std::to_string(s.pl[1]);
-                            if (a.ploidy == 2) merged_rows += ',' + std::to_string(s.pl[2]);
-                            merged_rows += '\n';
-                        }
-                        snvs_up_to(UINT64_MAX);
-                        vcf_rows.swap(merged_rows);
-                    }
-                    if (a.has_vcf) vcf_write(vcf_rows);
-                    if (a.gvcf) {
-                        breaks.clear();
-                        for (uint64_t i = 0; i < ind_sites.size() && i < gvcf_indels; ++i) breaks.push_back(ind_sites[i].pos);
-                        uint64_t n_fresh = 0;
-                        for (int attempt = 0;; ++attempt) {
-                            const int rc = dcn_anchor_map_reference_blocks(R.map.p, &bprm, r, start, n, breaks.data(), breaks.size(), nullptr, fresh.data(),
-                                                                           fresh.size(), &n_fresh);
-                            if (rc != DCN_ERR_CAPACITY || attempt) {
-                                deacon::check(rc);
-                                break;
-                            }
-                            fresh.resize(n_fresh);
-                        }
-                        blocks.insert(blocks.end(), fresh.begin(), fresh.begin() + n_fresh);
-                        uint64_t kept = 0;
-                        deacon::check(dcn_reference_blocks_merge(blocks.data(), blocks.size(), &kept));
-                        blocks.resize(kept);
-                        const bool last_stretch = start + n == R.lens[r];
-                        // the last block stays open while the record goes on behind it
-                        const bool open = !last_stretch && kept > 0 && blocks[kept - 1].pos + blocks[kept - 1].len == start + n;
-                        const uint64_t n_final = open ? kept - 1 : kept;
-                        gvcf_rows.clear();
-                        size_t line = 0; // where the next VCF line of the stretch begins in vcf_rows
-                        const auto vcf_lines_before = [&](uint64_t pos1) { // the VCF lines whose POS is under pos1
-                            while (line < vcf_rows.size()) {
-                                const size_t tab = vcf_rows.find('\t', line), end = vcf_rows.find('\n', line) + 1;
-                                if (std::strtoull(vcf_rows.c_str() + tab + 1, nullptr, 10) >= pos1) break;
-                                gvcf_rows.append(vcf_rows, line, end - line);
-                                line = end;
-                            }
-                        };
-                        for (uint64_t i = 0; i < n_final; ++i) {
-                            const dcn_reference_block &b = blocks[i];
-                            ++n_blocks, block_bases += b.len;
-                            const bool is_ref = b.cls >= DCN_BLOCK_REF;
-                            if (b.cls == DCN_BLOCK_NO_COVERAGE) no_coverage_bases += b.len;
-                            else if (!is_ref) uncalled_bases += b.len;
-                            else ref_bases += b.len, ref_bases_by_band[std::min<size_t>(b.cls - DCN_BLOCK_REF, ref_bases_by_band.size() - 1)] += b.len;
-                            if (a.has_callable) {
-                                if (b.pos > bed_cursor) bed_add(r, bed_cursor, b.pos, LABEL_CALLABLE); // VARIANT positions
-                                bed_add(r, b.pos, b.pos + b.len, b.cls == DCN_BLOCK_NO_COVERAGE ? LABEL_NO_COVERAGE : is_ref ? LABEL_CALLABLE : LABEL_LOW);
-                                bed_cursor = b.pos + b.len;
-                            }
-                            if (!a.has_gvcf) continue;
-                            vcf_lines_before(b.pos + 1);
-                            uint8_t base = 'N';
-                            if (b.pos >= start) base = ref_text[b.pos - start];
-                            else deacon::check(dcn_anchor_map_fetch(R.map.p, r, b.pos, 1, &base));
-                            gvcf_rows += R.names[r] + '\t' + std::to_string(b.pos + 1) + "\t.\t" + (char)std::toupper(base) + "\t<NON_REF>\t.\t.\tEND=" +
-                                         std::to_string(b.pos + b.len) + "\tGT:GQ:DP:MIN_DP\t" +
-                                         (is_ref ? (a.ploidy == 2 ? "0/0" : "0") : (a.ploidy == 2 ? "./." : ".")) + ':' + std::to_string(b.min_gq) + ':' +
-                                         std::to_string(b.sum_depth / b.len) + ':' + std::to_string(b.min_depth) + '\n';
-                        }
-                        if (a.has_gvcf) {
-                            vcf_lines_before(UINT64_MAX);
-                            gvcf_write(gvcf_rows);
-                        }
-                        blocks.erase(blocks.begin(), blocks.begin() + n_final);
-                        if (last_stretch && a.has_callable) {
-                            if (R.lens[r] > bed_cursor) bed_add(r, bed_cursor, R.lens[r], LABEL_CALLABLE);
-                            bed_add(r, 0, 0, nullptr);
-                            callable_out.write(bed_rows);
-                            bed_rows.clear();
-                        }
-                    }
-                }
-                if (!a.has_sites) continue;
-                site_rows.clear();
-                for (uint64_t i = 0; i < found; ++i) {
-                    const uint32_t *const c = counts.data() + (site_pos[i] - start) * DCN_PILEUP_COLUMNS;
-                    uint64_t depth = 0;
-                    for (int col = 0; col <= DCN_PILEUP_DEL; ++col) depth += c[col];
-                    const uint32_t code = (site_info[i] >> 8) & 0xFFu;
-                    site_rows += R.names[r] + '\t' + std::to_string(site_pos[i]) + '\t' + (char)ref_text[site_pos[i] - start] + '\t' +
-                                 (code <= 4 ? "ACGT-"[code] : 'N') + '\t' + std::to_string(depth) + '\t' + std::to_string(site_info[i] & 0xFFu) + '\n';
-                }
-                sites_out.write(site_rows);
-            }
-            if (a.has_fasta) fasta_out.write("\n");
-        }
+        tsv = a.pileup ? &out : a.has_pileup_out ? &pile_file : nullptr; // (`extend --sites` alone: no table)
+        if (tsv) tsv->write(pileup_header(a.call, a.strand));
+        if (a.has_sites) sites_out.write(sites_header());
+    }
+    void close_record_outputs() {
         if (a.has_sites) sites_out.finish();
         if (a.has_fasta) fasta_out.finish();
         if (a.has_variants) variants_out.finish();
@@ -4752,155 +4400,259 @@ int run_map(const MapArgs &a) {
         if (a.has_callable) callable_out.finish();
         if (a.extend && a.has_pileup_out) pile_file.finish();
     }
-    if (prints) out.finish();
-    uint64_t reads_keyed = 0, distinct_fragments = 0; // (markdup)
-    if (a.markdup) deacon::check(dcn_anchor_map_duplicates_info(R.map.p, nullptr, &reads_keyed, &distinct_fragments));
-    if (a.has_duplicates) dup_out.finish();
-    dcn_left_align_info left = {}; // (normalize)
-    if (a.normalize) deacon::check(dcn_anchor_map_pileup_left_align_info(R.map.p, &left));
-    const double secs = watch.seconds();
-    if (!a.quiet) {
-        if (a.extend)
-            std::fprintf(stderr, "Extended %llu of %llu placements by %llu bases (%llu bases clipped, %llu placements full length)\n",
-                         (unsigned long long)rows_extended, (unsigned long long)placements, (unsigned long long)bases_gained,
-                         (unsigned long long)bases_clipped, (unsigned long long)full_length_rows);
-        if (a.markdup)
-            std::fprintf(stderr, "Marked %llu of %llu reads with an end as duplicates%s\n", (unsigned long long)(reads_keyed - distinct_fragments),
-                         (unsigned long long)reads_keyed, a.keep_duplicates ? " (kept)" : "");
-        if (piles)
-            std::fprintf(stderr, "Piled up %llu of %llu placements on %llu positions (%llu sites)\n", (unsigned long long)rows_added,
-                         (unsigned long long)placements, (unsigned long long)covered, (unsigned long long)n_sites);
-        if (a.consensus)
-            std::fprintf(stderr, "Consensus of %llu bases: %llu substitutions, %llu deleted positions, %llu insertions of %llu events, %llu positions without a call\n",
-                         (unsigned long long)consensus_bases, (unsigned long long)substitutions, (unsigned long long)deleted_positions,
-                         (unsigned long long)insertion_alleles, (unsigned long long)insertion_events, (unsigned long long)uncalled_positions);
-        if (a.indels)
-            std::fprintf(stderr, "Genotyped %llu indel sites (%llu insertions, %llu deletions) over %llu deletion events of %llu bases\n",
-                         (unsigned long long)indel_sites, (unsigned long long)insertion_sites, (unsigned long long)deletion_sites,
-                         (unsigned long long)deletion_events, (unsigned long long)deleted_bases);
-        if (a.normalize)
-            std::fprintf(stderr, "Left-aligned %llu gaps over %llu columns in %llu of %llu placements (%llu gaps merged)\n",
-                         (unsigned long long)left.gaps_shifted, (unsigned long long)left.columns_passed, (unsigned long long)left.rows_changed,
-                         (unsigned long long)left.rows_aligned, (unsigned long long)left.gaps_merged);
-        if (a.strand)
-            std::fprintf(stderr, "Filtered %llu VCF lines by strand (%llu strand_bias, %llu one_strand)\n", (unsigned long long)filtered_sites,
-                         (unsigned long long)strand_bias_sites, (unsigned long long)one_strand_sites);
-        if (a.gvcf)
-            std::fprintf(stderr, "Cut %llu bases into %llu reference blocks (%llu bases reference, %llu not called, %llu without coverage)\n",
-                         (unsigned long long)record_bases, (unsigned long long)n_blocks, (unsigned long long)ref_bases, (unsigned long long)uncalled_bases,
-                         (unsigned long long)no_coverage_bases);
-        if (a.phase)
-            std::fprintf(stderr, "Phased %llu of %llu heterozygous SNV sites in %llu sets (%llu links joined, %llu placements linking)\n",
-                         (unsigned long long)phased_sites, (unsigned long long)ph_sites.size(), (unsigned long long)phase_set_count,
-                         (unsigned long long)links_joined, (unsigned long long)rows_linking);
-        if (a.verify && !a.pileup)
-            std::fprintf(stderr, "Verified %llu of %llu placements (%llu edits over %llu bases)\n", (unsigned long long)verified,
-                         (unsigned long long)placements, (unsigned long long)edits_sum, (unsigned long long)verified_bases);
-        if (a.align || (a.extend && a.has_output))
-            std::fprintf(stderr, "Aligned %llu placements in %llu runs (%llu =, %llu X, %llu I, %llu D)\n", (unsigned long long)verified,
-                         (unsigned long long)cigar_ops, (unsigned long long)op_bases[DCN_CIGAR_EQUAL], (unsigned long long)op_bases[DCN_CIGAR_DIFF],
-                         (unsigned long long)op_bases[DCN_CIGAR_INS], (unsigned long long)op_bases[DCN_CIGAR_DEL]);
-        std::fprintf(stderr, "Mapped %llu of %llu reads in %llu placements (%llu reads with two or more) in %s\n",
-                     (unsigned long long)placed, (unsigned long long)reads_in, (unsigned long long)placements,
-                     (unsigned long long)split_reads, fmt_duration(secs).c_str());
+    void fetch(const Stretch &s) { // counts, quality sums, strand planes (for the table alone), reference text
+        counts.resize(s.n * DCN_PILEUP_COLUMNS);
+        ref_text.resize(s.n);
+        deacon::check(dcn_anchor_map_pileup_fetch(R.map.p, s.r, s.start, s.n, counts.data()));
+        if (a.call) {
+            qsums.resize(s.n * 4);
+            deacon::check(dcn_anchor_map_pileup_fetch_qualities(R.map.p, s.r, s.start, s.n, qsums.data()));
+            for (uint64_t q = 0; q < s.n * 4; ++q) n.qual_sum[q & 3] += qsums[q];
+        }
+        if (a.strand && tsv) {
+            planes.resize(s.n * 4);
+            deacon::check(dcn_anchor_map_pileup_fetch_strands(R.map.p, s.r, s.start, s.n, planes.data()));
+        }
+        deacon::check(dcn_anchor_map_fetch(R.map.p, s.r, s.start, s.n, ref_text.data()));
     }
-    if (a.has_summary) {
-        std::string js = summary_head() + ",\n  \"reference\": " + json_str(a.ref) + ",\n  \"input\": " + json_str(a.input);
-        appendf(js, ",\n  \"k\": %u,\n  \"w\": %u,\n  \"band_bases\": %u,\n  \"min_votes\": %u,\n  \"prefix_length\": %zu,\n"
-                    "  \"records\": %u,\n  \"keys\": %llu,\n  \"anchors\": %llu,\n  \"repeats\": %llu,\n"
-                    "  \"reads\": %llu,\n  \"placed\": %llu,\n  \"max_placements\": %u,\n  \"placements\": %llu,\n"
-                    "  \"split_reads\": %llu,\n  \"mapq60\": %llu,\n  \"mapq0\": %llu,\n",
-                (unsigned)R.k, (unsigned)R.w, a.band, a.min_votes, a.prefix_length, R.m_records, (unsigned long long)R.m_keys,
-                (unsigned long long)R.m_anchors, (unsigned long long)R.m_repeats, (unsigned long long)reads_in,
-                (unsigned long long)placed, a.max_placements, (unsigned long long)placements, (unsigned long long)split_reads,
-                (unsigned long long)mapq60, (unsigned long long)mapq0);
-        if (a.verify)
-            appendf(js, "  \"max_edits\": %u,\n  \"max_permille\": %u,\n  \"verified\": %llu,\n  \"unverified\": %llu,\n"
-                        "  \"edits\": %llu,\n  \"verified_bases\": %llu,\n",
-                    a.max_edits, a.max_div, (unsigned long long)verified, (unsigned long long)unverified, (unsigned long long)edits_sum,
-                    (unsigned long long)verified_bases);
-        if (a.extend)
-            appendf(js, "  \"penalty\": %u,\n  \"end_bonus\": %u,\n  \"ext_max_edits\": %u,\n  \"rows_extended\": %llu,\n"
-                        "  \"bases_gained\": %llu,\n  \"bases_clipped\": %llu,\n  \"full_length_rows\": %llu,\n",
-                    a.penalty, a.end_bonus, a.ext_max_edits, (unsigned long long)rows_extended, (unsigned long long)bases_gained,
-                    (unsigned long long)bases_clipped, (unsigned long long)full_length_rows);
-        if (a.align || (a.extend && a.has_output))
-            appendf(js, "  \"matches\": %llu,\n  \"mismatches\": %llu,\n  \"insertions\": %llu,\n  \"deletions\": %llu,\n"
-                        "  \"cigar_ops\": %llu,\n",
-                    (unsigned long long)op_bases[DCN_CIGAR_EQUAL], (unsigned long long)op_bases[DCN_CIGAR_DIFF],
-                    (unsigned long long)op_bases[DCN_CIGAR_INS], (unsigned long long)op_bases[DCN_CIGAR_DEL], (unsigned long long)cigar_ops);
-        if (piles) {
-            appendf(js, "  \"min_mapq\": %u,\n  \"all_ranks\": %s,\n  \"min_depth\": %u,\n  \"min_permille\": %u,\n"
-                        "  \"rows_selected\": %llu,\n  \"rows_added\": %llu,\n  \"positions_covered\": %llu,\n  \"sites\": %llu,\n",
-                    a.min_mapq, a.all_ranks ? "true" : "false", a.min_depth, a.min_frac, (unsigned long long)rows_selected,
-                    (unsigned long long)rows_added, (unsigned long long)covered, (unsigned long long)n_sites);
-            const char *const column_names[DCN_PILEUP_COLUMNS] = {"A", "C", "G", "T", "N", "del", "ins", "rev"};
-            js += "  \"columns\": {";
-            for (int col = 0; col < DCN_PILEUP_COLUMNS; ++col)
-                appendf(js, "%s\"%s\": %llu", col ? ", " : "", column_names[col], (unsigned long long)column_sum[col]);
-            js += "},\n";
+    void table_rows(const Stretch &s) {
+        rows.clear();
+        for (uint64_t q = 0; q < s.n; ++q) {
+            const uint32_t *const c = counts.data() + q * DCN_PILEUP_COLUMNS;
+            const uint64_t depth = position_depth(c);
+            for (int col = 0; col < DCN_PILEUP_COLUMNS; ++col) n.column_sum[col] += c[col];
+            n.covered += depth > 0;
+            if (!tsv || (!a.all_positions && depth == 0 && c[DCN_PILEUP_INS] == 0)) continue;
+            append_pileup_row(rows, R.names[s.r], s.start + q, (char)ref_text[q], c, a.call ? qsums.data() + q * 4 : nullptr,
+                              a.strand ? planes.data() + q * 4 : nullptr);
         }
-        if (a.consensus)
-            appendf(js, "  \"fill_ref\": %s,\n  \"insertion_events\": %llu,\n  \"inserted_bases\": %llu,\n  \"insertion_alleles\": %llu,\n"
-                        "  \"substitutions\": %llu,\n  \"deleted_positions\": %llu,\n  \"consensus_bases\": %llu,\n  \"uncalled_positions\": %llu,\n",
-                    a.fill_ref ? "true" : "false", (unsigned long long)insertion_events, (unsigned long long)inserted_bases,
-                    (unsigned long long)insertion_alleles, (unsigned long long)substitutions, (unsigned long long)deleted_positions,
-                    (unsigned long long)consensus_bases, (unsigned long long)uncalled_positions);
-        if (a.call)
-            appendf(js, "  \"min_base_qual\": %u,\n  \"qual_offset\": %u,\n  \"quality_sums\": {\"A\": %llu, \"C\": %llu, \"G\": %llu, \"T\": %llu},\n",
-                    a.min_baseq, a.qual_offset, (unsigned long long)qual_sum[0], (unsigned long long)qual_sum[1], (unsigned long long)qual_sum[2],
-                    (unsigned long long)qual_sum[3]);
-        if (a.genotype)
-            appendf(js, "  \"ploidy\": %u,\n  \"min_gq\": %u,\n  \"min_qual\": %u,\n  \"genotyped_positions\": %llu,\n  \"vcf_sites\": %llu,\n"
-                        "  \"het_sites\": %llu,\n  \"hom_alt_sites\": %llu,\n",
-                    a.ploidy, a.min_gq, a.min_qual, (unsigned long long)genotyped_positions, (unsigned long long)vcf_sites,
-                    (unsigned long long)het_sites, (unsigned long long)hom_alt_sites);
-        if (a.markdup)
-            appendf(js, "  \"duplicates_both_ends\": %s,\n  \"keep_duplicates\": %s,\n  \"reads_keyed\": %llu,\n  \"duplicate_reads\": %llu,\n"
-                        "  \"distinct_fragments\": %llu,\n",
-                    a.both_ends ? "true" : "false", a.keep_duplicates ? "true" : "false", (unsigned long long)reads_keyed,
-                    (unsigned long long)(reads_keyed - distinct_fragments), (unsigned long long)distinct_fragments);
-        if (a.indels)
-            appendf(js, "  \"indel_qual\": %u,\n  \"min_indel_count\": %u,\n  \"deletion_events\": %llu,\n  \"deleted_bases\": %llu,\n"
-                        "  \"indel_sites\": %llu,\n  \"insertion_sites\": %llu,\n  \"deletion_sites\": %llu,\n  \"het_indel_sites\": %llu,\n"
-                        "  \"hom_indel_sites\": %llu,\n",
-                    a.indel_qual, a.min_indel_count, (unsigned long long)deletion_events, (unsigned long long)deleted_bases,
-                    (unsigned long long)indel_sites, (unsigned long long)insertion_sites, (unsigned long long)deletion_sites,
-                    (unsigned long long)het_indel_sites, (unsigned long long)hom_indel_sites);
-        if (a.normalize)
-            appendf(js, "  \"left_aligned_rows\": %llu,\n  \"left_aligned_gaps\": %llu,\n  \"left_align_columns\": %llu,\n"
-                        "  \"left_align_merged_gaps\": %llu,\n",
-                    (unsigned long long)left.rows_changed, (unsigned long long)left.gaps_shifted, (unsigned long long)left.columns_passed,
-                    (unsigned long long)left.gaps_merged);
-        if (a.strand)
-            appendf(js, "  \"max_sb\": %u,\n  \"min_alt_strand\": %u,\n  \"min_strand_depth\": %u,\n  \"strand_bias_sites\": %llu,\n"
-                        "  \"one_strand_sites\": %llu,\n  \"filtered_sites\": %llu,\n",
-                    a.max_sb, a.min_alt_strand, a.min_strand_depth, (unsigned long long)strand_bias_sites, (unsigned long long)one_strand_sites,
-                    (unsigned long long)filtered_sites);
-        if (a.gvcf) {
-            appendf(js, "  \"blocks\": %llu,\n  \"block_bases\": %llu,\n  \"variant_positions\": %llu,\n  \"no_coverage_bases\": %llu,\n"
-                        "  \"uncalled_bases\": %llu,\n  \"ref_bases\": %llu,\n  \"ref_bases_by_band\": [",
-                    (unsigned long long)n_blocks, (unsigned long long)block_bases, (unsigned long long)(record_bases - block_bases),
-                    (unsigned long long)no_coverage_bases, (unsigned long long)uncalled_bases, (unsigned long long)ref_bases);
-            for (size_t b = 0; b < ref_bases_by_band.size(); ++b) appendf(js, "%s%llu", b ? ", " : "", (unsigned long long)ref_bases_by_band[b]);
-            js += "],\n  \"gq_bands\": [";
-            for (size_t b = 0; b < a.gq_bands.size(); ++b) appendf(js, "%s%u", b ? ", " : "", a.gq_bands[b]);
-            js += "],\n";
+        if (tsv) tsv->write(rows);
+    }
+    uint64_t call_sites(const Stretch &s) { // rule P6 over the stretch: the calls (`consensus`) and the sites
+        if (a.consensus) calls.resize(s.n);
+        uint64_t found = 0;
+        with_room(site_pos, site_info, [&](uint64_t *pos, size_t room, uint32_t *info, size_t, uint64_t &count_pos, uint64_t &count_info) {
+            const int rc = dcn_anchor_map_pileup_call(R.map.p, &cprm, s.r, s.start, s.n, a.consensus ? calls.data() : nullptr, pos, info, room, &found);
+            count_pos = count_info = found; // (one capacity for both, site_pos's: they are of one size)
+            return rc;
+        });
+        n.sites += found;
+        return found;
+    }
+    void write_site_rows(const Stretch &s, uint64_t found) {
+        site_rows.clear();
+        for (uint64_t i = 0; i < found; ++i)
+            append_site_row(site_rows, R.names[s.r], site_pos[i], (char)ref_text[site_pos[i] - s.start], site_info[i],
+                            position_depth(counts.data() + (site_pos[i] - s.start) * DCN_PILEUP_COLUMNS));
+        sites_out.write(site_rows);
+    }
+    void consensus(const Stretch &s) { // rule L7 over the stretch: the called insertions, then position by position
+        uint64_t n_alleles = 0, n_inserted = 0;
+        with_room(alleles, allele_bases, [&](dcn_insertion_allele *al, size_t room, uint8_t *bases, size_t base_room, uint64_t &count, uint64_t &base_count) {
+            const int rc = dcn_anchor_map_insertions_call(R.map.p, &cprm, s.r, s.start, s.n, al, room, bases, base_room, &n_alleles, &n_inserted);
+            count = n_alleles, base_count = n_inserted;
+            return rc;
+        });
+        n.insertion_alleles += n_alleles;
+        seq.clear();
+        variant_rows.clear();
+        uint64_t next = 0; // the next allele: they are in ascending position
+        for (uint64_t q = 0; q < s.n; ++q) {
+            const uint32_t *const c = counts.data() + q * DCN_PILEUP_COLUMNS;
+            const dcn_insertion_allele *const al = next < n_alleles && alleles[next].pos == s.start + q ? &alleles[next++] : nullptr;
+            const auto insertion = [&] {
+                const std::string alt((const char *)allele_bases.data() + al->bases_offset, al->len);
+                seq += alt;
+                if (a.has_variants) append_insertion_variant(variant_rows, R.names[s.r], s.start + q, *al, alt, position_depth(c), a.call);
+            };
+            if (al && (al->flags & DCN_INSERTION_FRONT)) insertion();
+            const char call = (char)calls[q], ref = (char)ref_text[q];
+            if (call == 'N') { // (not called: P6 writes N there and nowhere else)
+                ++n.uncalled_positions;
+                seq += a.fill_ref ? ref : 'N';
+            } else {
+                if (call != '-') seq += call;
+                if (call == '-') ++n.deleted_positions;
+                else if (call != ref) ++n.substitutions;
+                if (a.has_variants && call != ref) append_call_variant(variant_rows, R.names[s.r], s.start + q, ref, call, c, a.call ? qsums.data() + q * 4 : nullptr);
+            }
+            if (al && !(al->flags & DCN_INSERTION_FRONT)) insertion();
         }
-        if (a.phase)
-            appendf(js, "  \"min_link_reads\": %u,\n  \"max_link_minor\": %u,\n  \"phase_sites\": %llu,\n  \"phase_sets\": %llu,\n"
-                        "  \"phased_sites\": %llu,\n  \"links_joined\": %llu,\n  \"rows_linking\": %llu,\n  \"phase_set_n50\": %llu,\n",
-                    a.min_link_reads, a.max_link_minor, (unsigned long long)ph_sites.size(), (unsigned long long)phase_set_count,
-                    (unsigned long long)phased_sites, (unsigned long long)links_joined, (unsigned long long)rows_linking, (unsigned long long)phase_n50);
-        appendf(js, "  \"time\": %.17g,\n  \"placements_by_record\": [", secs);
+        n.consensus_bases += seq.size();
+        if (a.has_fasta) fasta_out.write(seq);
+        if (a.has_variants) variants_out.write(variant_rows);
+    }
+    // (`phase`) the site's entry of the list, when the line is heterozygous and its set has two sites or more; else SIZE_MAX
+    size_t phased_entry(uint32_t r, uint64_t pos) {
+        while (ph_cursor < ph_sites.size() && (ph_sites[ph_cursor].record < r || (ph_sites[ph_cursor].record == r && ph_sites[ph_cursor].pos < pos))) ++ph_cursor;
+        const bool phased = ph_cursor < ph_res.size() && ph_sites[ph_cursor].record == r && ph_sites[ph_cursor].pos == pos &&
+                            ((ph_res[ph_cursor].flags & DCN_PHASE_JOINED) || !(ph_res[ph_cursor].flags & DCN_PHASE_HEAD));
+        return phased ? ph_cursor : SIZE_MAX;
+    }
+    void write_snv_lines(const Stretch &s) { // rules G1-G8 over the stretch; a site's line is written from the site alone
+        geno_gt.resize(s.n);
+        uint64_t n_geno = 0;
+        with_room(geno_sites, [&](dcn_genotype_site *into, size_t room, uint64_t &count) {
+            const int rc = dcn_anchor_map_genotype(R.map.p, &gprm, s.r, s.start, s.n, geno_gt.data(), nullptr, into, room, &n_geno);
+            count = n_geno;
+            return rc;
+        });
+        for (uint64_t q = 0; q < s.n; ++q) n.genotyped_positions += geno_gt[q] != DCN_GENOTYPE_NONE;
+        n.vcf_sites += n_geno;
+        if (a.strand) { // rules S3, S5 and S6 at the stretch's sites
+            strand_queries.resize(n_geno);
+            snv_strand.resize(n_geno);
+            for (uint64_t i = 0; i < n_geno; ++i) strand_queries[i] = snv_strand_query(geno_sites[i], a.ploidy);
+            deacon::check(dcn_anchor_map_strand_evidence(R.map.p, &sprm, s.r, strand_queries.data(), n_geno, snv_strand.data()));
+        }
+        snv_lines.clear();
+        for (uint64_t i = 0; i < n_geno; ++i) {
+            const dcn_genotype_site &g = geno_sites[i];
+            const GenotypeAlleles gt = genotype_alleles(g.gt, a.ploidy);
+            (gt.x != gt.y ? n.het_sites : n.hom_alt_sites) += 1;
+            const size_t ph = a.phase && gt.x != gt.y ? phased_entry(s.r, g.pos) : SIZE_MAX;
+            if (a.strand) n.tally_strand(snv_strand[i]);
+            append_snv_line(snv_lines.begin_line(g.pos + 1), R.names[s.r], g, a.ploidy, a.strand ? &snv_strand[i] : nullptr,
+                            ph != SIZE_MAX ? &ph_sites[ph] : nullptr, ph != SIZE_MAX ? &ph_res[ph] : nullptr);
+        }
+    }
+    uint64_t write_indel_lines(const Stretch &s) { // rules I1-I8 over the stretch.  Gives the number of sites.
+        uint64_t n_ind = 0, n_ind_bases = 0;
+        with_room(ind_sites, ind_bases, [&](dcn_indel_site *sites, size_t room, uint8_t *bases, size_t base_room, uint64_t &count, uint64_t &base_count) {
+            const int rc = dcn_anchor_map_indels_genotype(R.map.p, &iprm, s.r, s.start, s.n, sites, room, bases, base_room, &n_ind, &n_ind_bases);
+            count = n_ind, base_count = n_ind_bases;
+            return rc;
+        });
+        n.indel_sites += n_ind;
+        if (a.strand) { // rule S4: the winners' reverse events from the ledgers, then the table, the score and the flags
+            ind_reverse.resize(n_ind);
+            ind_strand.resize(n_ind);
+            strand_queries.assign(n_ind, dcn_strand_query{});
+            deacon::check(dcn_anchor_map_indels_strand(R.map.p, s.r, ind_sites.data(), n_ind, ind_bases.data(), ind_reverse.data()));
+            for (uint64_t i = 0; i < n_ind; ++i) {
+                strand_queries[i].pos = ind_sites[i].pos;
+                strand_queries[i].kind = 1;
+                strand_queries[i].count = ind_sites[i].count;
+                strand_queries[i].count_reverse = ind_reverse[i];
+            }
+            deacon::check(dcn_anchor_map_strand_evidence(R.map.p, &sprm, s.r, strand_queries.data(), n_ind, ind_strand.data()));
+        }
+        const auto fetch_more = [&](uint64_t from, uint64_t count) { // where a line reaches beyond the stretch
+            ref_more.resize(count);
+            deacon::check(dcn_anchor_map_fetch(R.map.p, s.r, from, count, ref_more.data()));
+            return std::string(ref_more.begin(), ref_more.end());
+        };
+        const auto ref_bases = [&](uint64_t from, uint64_t count) { return reference_bases(ref_text.data(), s.start, s.n, from, count, fetch_more); };
+        indel_lines.clear();
+        for (uint64_t i = 0; i < n_ind; ++i) {
+            const dcn_indel_site &site = ind_sites[i];
+            const bool deletion = (site.flags & DCN_INDEL_DELETION) != 0;
+            ++(deletion ? n.deletion_sites : n.insertion_sites);
+            if (deletion && site.len >= R.lens[s.r]) // (every placement of the tool holds a k-mer of '=' bases)
+                die("internal error: a deletion of the whole record '" + R.names[s.r] + "'");
+            const IndelAlleles v = indel_alleles(site, ind_bases.data(), ref_bases);
+            (indel_is_hom(site, a.ploidy) ? n.hom_indel_sites : n.het_indel_sites) += 1;
+            if (a.strand) n.tally_strand(ind_strand[i]);
+            append_indel_line(indel_lines.begin_line(v.pos1), R.names[s.r], v, site, a.ploidy, a.strand ? &ind_strand[i] : nullptr);
+        }
+        return n_ind;
+    }
+    // (`gvcf`) rules B1-B9 a stretch at a time: the stretch's blocks behind the one block that the stretch before left open at
+    // the seam, merged (rule B7); every block but an open last one is final and goes out, with the stretch's VCF lines, in
+    // POS order, a block's line in front of a VCF line of its POS.  No per-position bytes are fetched.  The INDEL lines of
+    // the stretch are the breaks.
+    void write_blocks(const Stretch &s, const PosLines &vcf, uint64_t n_indels) {
+        breaks.clear();
+        for (uint64_t i = 0; i < n_indels; ++i) breaks.push_back(ind_sites[i].pos);
+        uint64_t n_fresh = 0;
+        with_room(fresh, [&](dcn_reference_block *into, size_t room, uint64_t &count) {
+            const int rc = dcn_anchor_map_reference_blocks(R.map.p, &bprm, s.r, s.start, s.n, breaks.data(), breaks.size(), nullptr, into, room, &n_fresh);
+            count = n_fresh;
+            return rc;
+        });
+        blocks.insert(blocks.end(), fresh.begin(), fresh.begin() + n_fresh);
+        uint64_t kept = 0;
+        deacon::check(dcn_reference_blocks_merge(blocks.data(), blocks.size(), &kept));
+        blocks.resize(kept);
+        const bool last_stretch = s.start + s.n == R.lens[s.r];
+        // the last block stays open while the record goes on behind it
+        const bool open = !last_stretch && kept > 0 && blocks[kept - 1].pos + blocks[kept - 1].len == s.start + s.n;
+        const uint64_t n_final = open ? kept - 1 : kept;
+        block_lines.clear();
+        for (uint64_t i = 0; i < n_final; ++i) {
+            const dcn_reference_block &blk = blocks[i];
+            ++n.blocks, n.block_bases += blk.len;
+            if (blk.cls == DCN_BLOCK_NO_COVERAGE) n.no_coverage_bases += blk.len;
+            else if (blk.cls < DCN_BLOCK_REF) n.uncalled_bases += blk.len;
+            else n.ref_bases += blk.len, n.ref_bases_by_band[std::min<size_t>(blk.cls - DCN_BLOCK_REF, n.ref_bases_by_band.size() - 1)] += blk.len;
+            if (a.has_callable) bed.add_block(R.names[s.r], blk.pos, blk.len, blk.cls);
+            if (!a.has_gvcf) continue;
+            uint8_t base = 'N';
+            if (blk.pos >= s.start) base = ref_text[blk.pos - s.start];
+            else deacon::check(dcn_anchor_map_fetch(R.map.p, s.r, blk.pos, 1, &base));
+            append_block_line(block_lines.begin_line(blk.pos + 1), R.names[s.r], blk, base, a.ploidy);
+        }
+        if (a.has_gvcf) {
+            merge_by_pos(block_lines, vcf, false, gvcf_lines);
+            write(*gvcf_out, gvcf_lines.text);
+        }
+        blocks.erase(blocks.begin(), blocks.begin() + n_final);
+        if (last_stretch && a.has_callable) {
+            bed.end_record(R.names[s.r], R.lens[s.r]);
+            callable_out.write(bed.rows);
+            bed.rows.clear();
+        }
+    }
+    void write_stretch(const Stretch &s) {
+        fetch(s);
+        table_rows(s);
+        const uint64_t found = call_sites(s);
+        if (a.consensus) consensus(s);
+        if (a.genotype) {
+            write_snv_lines(s);
+            const uint64_t n_indels = a.indels ? write_indel_lines(s) : 0;
+            // the INDEL lines merged into the SNV lines by POS, the SNV line of a POS first
+            if (a.indels) merge_by_pos(indel_lines, snv_lines, true, vcf_lines);
+            const PosLines &vcf = a.indels ? vcf_lines : snv_lines;
+            if (a.has_vcf) write(*vcf_out, vcf.text);
+            if (a.gvcf) write_blocks(s, vcf, n_indels);
+        }
+        if (a.has_sites) write_site_rows(s, found);
+    }
+    void write_records() {
+        open_record_outputs();
+        const uint64_t stretch = stretch_bases();
         for (uint32_t r = 0; r < R.n_records; ++r) {
-            js += (r ? ",\n    {" : "\n    {");
-            js += "\"name\": " + json_str(R.names[r]);
-            appendf(js, ", \"length\": %u, \"placements\": %llu}", R.lens[r], (unsigned long long)per_record[r]);
+            if (a.has_fasta) fasta_out.write(">" + R.names[r] + "\n");
+            n.record_bases += R.lens[r];
+            blocks.clear();
+            for (uint64_t start = 0; start < R.lens[r]; start += stretch) write_stretch(Stretch{r, start, std::min<uint64_t>(stretch, R.lens[r] - start)});
+            if (a.has_fasta) fasta_out.write("\n");
         }
-        js += "\n  ]\n}\n";
-        write_text_file(a.summary, js);
+        close_record_outputs();
     }
+
+    // ---- close, report, summarise -------------------------------------------------------------------------------------------
+    void finish() {
+        if (prints) out.finish();
+        if (a.markdup) deacon::check(dcn_anchor_map_duplicates_info(R.map.p, nullptr, &n.reads_keyed, &n.distinct_fragments));
+        if (a.has_duplicates) dup_out.finish();
+        if (a.normalize) deacon::check(dcn_anchor_map_pileup_left_align_info(R.map.p, &n.left));
+        const double secs = watch.seconds();
+        if (!a.quiet) map_report(a, n, piles, aligns, secs);
+        if (a.has_summary) write_text_file(a.summary, map_summary(a, R, n, piles, aligns, secs));
+    }
+};
+
+int run_map(const MapArgs &a) {
+    MapRun run(a);
+    run.check_arguments();
+    run.load();
+    run.open_batch_outputs();
+    for_each_batch(*run.reads, run.b, run.R.batch_bases, run.R.batch_reads, [&run] { run.batch(MapRun::Pass::First); });
+    if (a.phase) run.phase();
+    if (run.piles) run.write_records();
+    run.finish();
     return 0;
 }
 

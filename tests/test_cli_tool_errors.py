@@ -12,6 +12,7 @@ HELP = os.path.join(ROOT, "tests", "golden", "cli_help")
 X33 = ["-x", "a"] * 33
 LIST = "a comma-separated list of 0-based index positions"
 ODD = "Constraint violated: k + w - 1 must be odd (k=31, w=16)"
+NOTHING = "nothing to write: give at least one of -o <OUTPUT>, --variants <FILE>, --pileup <FILE>, --sites <FILE>, "
 
 # (arguments, the one `Error: ...` line, what stderr holds in front of it)
 ERRORS = [
@@ -51,6 +52,36 @@ ERRORS = [
      "Deacon-hip v{v}; mode: build; input: single; options: capacity=400M\n"),
     (["index", "build", "--min-count", "2", "-k", "31", "-w", "16", "x.fa"], ODD,
      "Deacon-hip v{v}; mode: build; input: single; options: capacity=as needed, min_count=2, max_count=0\n"),
+    # the map family (one driver, run_map): the texts of the tool as it was before run_map was cut into stages
+    (["map"], "the following required arguments were not provided: <REF>", ""),
+    (["call"], "the following required arguments were not provided: <REF>", ""),
+    (["genotype", "REF"], f"{NOTHING}--vcf <FILE>, -s <SUMMARY>", ""),
+    (["markdup", "REF"], f"{NOTHING}--vcf <FILE>, --duplicates <FILE>, -s <SUMMARY>", ""),
+    (["gvcf", "REF"], f"{NOTHING}--vcf <FILE>, --gvcf <FILE>, --callable <FILE>, --duplicates <FILE>, -s <SUMMARY>", ""),
+    (["phase", "REF", "reads.fq"],
+     f"{NOTHING}--vcf <FILE>, --gvcf <FILE>, --callable <FILE>, --phase-sets <FILE>, --links <FILE>, --duplicates <FILE>, -s <SUMMARY>", ""),
+    (["phase", "--ploidy", "1", "REF", "reads.fq"], "phase needs --ploidy 2: a haploid genotype has no heterozygous site to phase", ""),
+    (["phase", "REF"],
+     "phase reads its input twice (the pile-up, then the links between the sites that were found): give a file, not stdin", ""),
+    (["map", "--verified-only"], "unexpected argument '--verified-only'", ""),
+    (["verify", "REF", "--min-mapq", "3"], "unexpected argument '--min-mapq'", ""),
+    (["pileup", "REF", "--pileup", "x"], "unexpected argument '--pileup'", ""),
+    (["extend", "REF", "--verified-only"], "unexpected argument '--verified-only'", ""),
+    (["call", "REF", "--vcf", "x"], "unexpected argument '--vcf'", ""),
+    (["genotype", "--gvcf", "x"], "unexpected argument '--gvcf'", ""),
+    (["gvcf", "REF", "--links", "x"], "unexpected argument '--links'", ""),
+    (["map", "REF", "-N", "0"], "invalid value for -N: must be 1..8", ""),
+    (["verify", "REF", "--max-div", "1001"], "invalid value for --max-div: must be 0..1000", ""),
+    (["pileup", "REF", "--min-mapq", "61"], "invalid value for --min-mapq: must be 0..60", ""),
+    (["extend", "REF", "--penalty", "1"], "invalid value for --penalty: must be 2..255", ""),
+    (["call", "REF", "--min-baseq", "256"], "invalid value for --min-baseq: must be 0..255", ""),
+    (["genotype", "REF", "--min-gq", "100"], "invalid value for --min-gq: must be 0..99", ""),
+    (["gvcf", "REF", "--gq-bands", "20,x"], "invalid value for --gq-bands: must be 0..255", ""),
+    (["phase", "REF", "--max-link-minor", "1001"], "invalid value for --max-link-minor: must be 0..1000", ""),
+    (["phase", "REF", "--vcf"], "missing value for --vcf", ""),
+    (["map", "a", "b", "c"], "map takes one input: mates are independent here, run it once per file (unexpected argument 'c')", ""),
+    (["verify", "REF", "a", "b"], "verify takes one input: mates are independent here, run it once per file (unexpected argument 'b')", ""),
+    (["phase", "a", "b", "c"], "phase takes one input: mates are independent here, run it once per file (unexpected argument 'c')", ""),
 ]
 
 HELPS = ["classify", "mask", "place", "index", "index build", "index info", "index union", "index diff", "index intersect",
